@@ -25,6 +25,9 @@ value = solved node-AVIs / second over all ranks (failed items do not count; the
 Extra objects on the JSON line: "roofline" (HBM bound; achieved = algorithmic bytes of SURVEY.md section 8(d) per launch /
 mean launch duration, measured live with HIP events on the launch stream) and "cpu_baseline" (the CPU oracle -- a port, not
 PATH -- on the host cores, rank 0, N = 1).  ``--config 5`` measures BASELINE configs[4] (512 nodes x 256 variables) instead.
+
+``--dump-outputs DIR`` writes what the last timed step returned (DIR/<name>.npy, float64) after the measurement.  The inputs
+depend on the arguments alone (seeded node records and parameter ring), so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -39,10 +42,11 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 NODES, NVAR, NCON, NPAR = 10_000, 32, 32, 8
-HBM_PEAK_GBS = 8000.0     # MI355X HBM3E spec, /opt/skills/guides/MI355X_MICROARCH.md:36
+HBM_PEAK_GBS = 8000.0     # MI355X HBM3E spec
 FP64_PEAK_TFLOPS = 78.6   # vector = matrix fp64 (datasheet; confirmed here: 64 cycles per v_mfma_f64_16x16x4, tools/mfma_rate)
 PREWARM_STEPS = 800
 RING = 64
+DUMP_MAX_BYTES = 64 << 20
 
 
 def parse_args():
@@ -74,7 +78,16 @@ def parse_args():
                     help="N = 1: leader-follower pairs (n = m = 32) of the net the outer_loop object runs through solve(); 0 skips it")
     ap.add_argument("--no-schedule", action="store_true",
                     help="natural node order (default: longest-first schedule refreshed from the pivot counts every 16 steps)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller (z, status, resid, pivots, "
+                         "active, the primal iterate x; all nodes of all ranks) as DIR/<name>.npy in float64, at most "
+                         f"{DUMP_MAX_BYTES >> 20} MB in all (beyond that a fixed, seeded sample of the nodes, listed in node_index.npy)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
 
 
 def maybe_spawn_ranks(args):
@@ -125,12 +138,13 @@ def main():
     eng.set_option(_qlib.OPT_SYM_ROUTE, args.sym_route)
     env = dict(eng=eng, dist=dist, use_dist=use_dist, world=world, rank=rank, dev=torch.device(f"cuda:{local_rank}"),
                np=np, torch=torch)
+    outputs = {} if args.dump_outputs else None
     if args.config == 5:
-        out = run_config5(env, args)
+        out = run_config5(env, args, outputs)
     else:
         nodes = args.nodes if args.nodes is not None else NODES
         first = run_case(env, args, nodes, args.scaling, args.steps, args.warmup, prewarm=not args.no_prewarm,
-                         with_cpu=(world == 1 and not args.no_cpu_baseline))
+                         with_cpu=(world == 1 and not args.no_cpu_baseline), outputs=outputs)
         out = first
         if world > 1 and not args.no_second_scaling:
             other = "weak" if args.scaling == "strong" else "strong"
@@ -139,14 +153,45 @@ def main():
                 out[f"{other}_scaling"] = {k: second[k] for k in ("value", "unit", "ms_per_step", "steps", "warmup")} | {
                     "nodes": second["config"]["nodes"], "nodes_per_gpu": second["config"]["nodes_per_gpu"],
                     "exchange": second["config"]["exchange"], "frac": second["roofline"]["frac"]}
+    if rank == 0 and outputs is not None:
+        write_outputs(np, args.dump_outputs, outputs)
     if rank == 0:
         print(json.dumps(out), flush=True)
     if use_dist:
         dist.destroy_process_group()
 
 
-def run_case(env, args, nodes, scaling, steps, warmup, prewarm, with_cpu):
-    """One measurement of the config-4 sweep; returns the JSON object (on every rank; rank 0's is printed)."""
+def snapshot_outputs(env, res, x):
+    """What the timed path handed its caller in its last step -- the result buffers and the primal iterate x it wrote --
+    copied to the host in float64 (exact for the integer status / pivot counts and the 0/1 active-set masks).  N > 1: the
+    ranks' node ranges are contiguous and in rank order, so rank 0 receives the whole net's arrays in node order."""
+    np, dist = env["np"], env["dist"]
+    snap = {k: res[k].double().cpu().numpy() for k in ("z", "status", "resid", "pivots", "active") if res.get(k) is not None}
+    snap["x"] = x.double().cpu().numpy()
+    if env["use_dist"]:
+        parts = [None] * env["world"]
+        dist.all_gather_object(parts, snap)
+        snap = {k: np.concatenate([pt[k] for pt in parts]) for k in snap}
+    return snap
+
+
+def write_outputs(np, out_dir, outputs):
+    """DIR/<name>.npy for every array of snapshot_outputs.  Above DUMP_MAX_BYTES a fixed sample of the nodes (seed 0, in node
+    order) is written instead, the same rows of every array, and node_index.npy lists them."""
+    nodes = len(outputs["status"])
+    row_bytes = sum(a.nbytes // max(len(a), 1) for a in outputs.values())
+    keep = max(1, DUMP_MAX_BYTES // (row_bytes + 8))
+    if nodes > keep:
+        idx = np.sort(np.random.default_rng(0).choice(nodes, size=keep, replace=False))
+        outputs = {k: a[idx] for k, a in outputs.items()} | {"node_index": idx.astype(np.float64)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
+def run_case(env, args, nodes, scaling, steps, warmup, prewarm, with_cpu, outputs=None):
+    """One measurement of the config-4 sweep; returns the JSON object (on every rank; rank 0's is printed).  A dict passed
+    as `outputs` receives what the last timed step returned (snapshot_outputs)."""
     np, torch = env["np"], env["torch"]
     eng, dist, use_dist, world, rank, dev = env["eng"], env["dist"], env["use_dist"], env["world"], env["rank"], env["dev"]
     from qpn_amd import sharding, synthetic
@@ -202,15 +247,18 @@ def run_case(env, args, nodes, scaling, steps, warmup, prewarm, with_cpu):
     bufs = {"asm": None, "sol": None}      # output buffers are allocated once and reused
     kstep = [0]
 
+    def local_x():
+        """This rank's rows of the iterate: where a step writes its primal blocks."""
+        if shared is not None:
+            return shared.x[lo_id:hi_id]
+        if gathered is not None:
+            return gathered.x_local
+        return x_all[lo_id:hi_id]
+
     def step():
         w = ring[kstep[0] % RING]
         kstep[0] += 1
-        if shared is not None:
-            xloc = shared.x[lo_id:hi_id]
-        elif gathered is not None:
-            xloc = gathered.x_local
-        else:
-            xloc = x_all[lo_id:hi_id]
+        xloc = local_x()
         if args.unfused:
             bufs["asm"] = eng.assemble_nodes(*drec, w, out=bufs["asm"])
             Mc, q, lo, hi, kind = bufs["asm"]
@@ -323,6 +371,8 @@ def run_case(env, args, nodes, scaling, steps, warmup, prewarm, with_cpu):
     dt = time.perf_counter() - t0
     kern_ms_all = ev0.elapsed_time(ev1) / max(steps, 1)
     kern_ms = evm.elapsed_time(ev1) / (steps - 1) if steps >= 2 else kern_ms_all
+    if outputs is not None:
+        outputs.update(snapshot_outputs(env, res, local_x()))
 
     sweep_ok = shared is None or float(shared.out[3]) == 0.0        # no barrier of the timed region was missed
     solved_local = int((res["status"] == 1).sum().item()) if sweep_ok else 0      # a missed barrier voids the run
@@ -644,7 +694,7 @@ def cpu_baseline(np, Q, R, qd, A, B, l, u, w, budget_s=1.0):
                       "-- not Julia+PATH"}
 
 
-def run_config5(env, args):
+def run_config5(env, args, outputs=None):
     """BASELINE configs[4]: 512 nodes x 256 variables (n = m = 256, N_red = 512), the large per-node KKT path (blocked MFMA
     crash, then Stage B by block principal pivoting with the delayed-update Lemke kernel behind it, csrc/qpn_avi_schur_big*.hip).
     Bound: fp64 matrix/vector pipe; flops per solve = N^3/3 (one factorisation) + 2 N^2 per Lemke pivot,
@@ -677,7 +727,7 @@ def run_config5(env, args):
     handle.close()
     eng.set_option(qlib.OPT_SYM_ROUTE, args.sym_route)
     handle = eng.upload_nodes(*drec)
-    steps = min(args.steps, 50)
+    steps = args.steps
     warmup = min(args.warmup, 5)
     out = None
     x = torch.zeros((cnt, n), dtype=torch.float64, device=dev)
@@ -701,6 +751,8 @@ def run_config5(env, args):
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     ms = ev0.elapsed_time(ev1) / steps
+    if outputs is not None:
+        outputs.update(snapshot_outputs(env, out, x))
     solved = int((out["status"] == 1).sum().item())
     mean_piv = float(piv_sum.item()) / (steps * cnt)
     # the kernel's counter includes the n crash pivots (all free variables enter): those ARE the factorisation (N^3/3);
