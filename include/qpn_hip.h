@@ -363,6 +363,18 @@ int qpn_verify_nodes(qpn_ctx *ctx, int32_t batch, int32_t n, int32_t m, int32_t 
                      const double *w, int64_t stride_w, double tol, int32_t *solution,
                      double *lambda, int32_t *path, int mem);
 
+/* ---- batched reduced-Hessian convexity check, check_qp_convexity (src/qp_processing.jl:39-55) ----------
+ *   Qd [batch][n][n] and Ad [batch][m][n] column-major per node as above, eq [batch][m] uint8: 1 marks an
+ *   implicit equality row (polyhedra.implicit_bounds).  Z = an orthonormal basis of null(Ad[eq, :]) (the rank
+ *   by Julia's rule, count sigma_i > min(k, n) * eps * sigma_max, with all-zero rows left out of k);
+ *   H = Z' (Qd + Qd') Z.  convex [batch] int32 = all eigenvalues of H > -tol; min_eig [batch] = the smallest
+ *   one (+inf when H is empty); null_dim [batch] int32 = n - rank.  A non-finite entry of Qd or of a selected
+ *   row gives convex = 0, min_eig = NaN, null_dim = -1.  tol = 1e-6 (:39).  1 <= n <= 256, 0 <= m <= 1024
+ *   (QPN_ERR_SIZE beyond).  n <= 32: one wavefront per node; up to 128: one workgroup per node in LDS;
+ *   beyond: one workgroup per node over a global workspace. */
+int qpn_convexity_nodes(qpn_ctx *ctx, int32_t batch, int32_t n, int32_t m, const double *Qd, const double *Ad,
+                        const uint8_t *eq, double tol, int32_t *convex, double *min_eig, int32_t *null_dim, int mem);
+
 #ifdef __cplusplus
 }
 #endif

@@ -189,6 +189,24 @@ function solve_nodes!(nodes::Nodes, x::Union{Nothing,StridedMatrix{Float64}}, w:
     (z, status, resid, pivots, active)
 end
 
+"""
+    convexity_nodes(Qd, Ad, eq; tol=1e-6) -> (convex, min_eig, null_dim)
+
+check_qp_convexity (src/qp_processing.jl:39-55) for a batch: Qd [n, n, batch], Ad [m, n, batch] (Julia's column-major
+arrays are the ABI layout as they are), eq [m, batch] (1 = implicit equality row, from `implicit_bounds`).
+"""
+function convexity_nodes(Qd::Array{Float64,3}, Ad::Array{Float64,3}, eq::Matrix{UInt8}; tol::Float64 = 1e-6)
+    n, batch = size(Qd, 1), size(Qd, 3)
+    m = size(Ad, 1)
+    convex = zeros(Int32, batch); min_eig = zeros(batch); null_dim = zeros(Int32, batch)
+    rc = ccall((:qpn_convexity_nodes, LIB), Cint,
+               (Ptr{Cvoid}, Int32, Int32, Int32, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{UInt8}, Cdouble, Ptr{Int32}, Ptr{Cdouble},
+                Ptr{Int32}, Cint),
+               ctx(), batch, n, m, Qd, Ad, eq, tol, convex, min_eig, null_dim, QPN_MEM_HOST)
+    rc == 0 || error("qpn_convexity_nodes failed ($rc)")
+    (convex, min_eig, null_dim)
+end
+
 function verify_nodes(nodes::Nodes, xd::Matrix{Float64}, w::VecOrMat{Float64}; tol::Float64 = 1e-4)
     solution = zeros(Int32, nodes.batch); path = zeros(Int32, nodes.batch); lambda = zeros(max(nodes.m, 1), nodes.batch)
     rc = ccall((:qpn_verify_nodes_h, LIB), Cint,

@@ -47,6 +47,8 @@ def solve_base(qpn, x_init, level=1, proj_vectors=None, rng=None, engine=None):
             if level < qpn.num_levels():                                             # :32-42
                 low = solve_base(qpn, x, level=level + 1, proj_vectors=proj_vectors, rng=rng, engine=engine)
                 if not low["solved"]:
+                    if opts.check_convexity and "error" in low:                     # a non-convex node below names itself
+                        return dict(solved=False, x_fail=x, x_opt=None, error=low["error"])
                     return dict(solved=False, x_fail=x, x_opt=None)
                 S = low["Sol"]; x = low["x_opt"]
             else:

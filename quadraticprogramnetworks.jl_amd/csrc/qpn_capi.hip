@@ -1437,6 +1437,54 @@ int qpn_verify_nodes(qpn_ctx *ctx, int32_t batch, int32_t n, int32_t m, int32_t 
                             lambda, path, mem);
 }
 
+int qpn_convexity_nodes(qpn_ctx *ctx, int32_t batch, int32_t n, int32_t m, const double *Qd, const double *Ad,
+                        const uint8_t *eq, double tol, int32_t *convex, double *min_eig, int32_t *null_dim, int mem)
+{
+    if (!ctx) return QPN_ERR_ARG;
+    if (batch < 0 || n <= 0 || m < 0) return fail_arg(ctx, "qpn_convexity_nodes: bad sizes");
+    if (n > QPN_CONVEXITY_MAX_N || m > QPN_CONVEXITY_MAX_M) {
+        ctx->last_error = "qpn_convexity_nodes: n <= 256, m <= 1024 in ABI v1";
+        return QPN_ERR_SIZE;
+    }
+    if (!Qd || (m > 0 && (!Ad || !eq)) || !convex || !min_eig || !null_dim) return fail_arg(ctx, "qpn_convexity_nodes: null pointer");
+    if (mem != QPN_MEM_HOST && mem != QPN_MEM_DEVICE) return fail_arg(ctx, "qpn_convexity_nodes: bad mem kind");
+    if (batch == 0) return QPN_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const size_t bQ = (size_t)batch * n * n * 8, bA = (size_t)batch * m * n * 8, be = (size_t)batch * m;
+    const size_t gbytes = qpn_convexity_workspace_bytes(batch, n, m);
+    void *gws = nullptr;
+    if (mem == QPN_MEM_DEVICE) {
+        if (gbytes) {
+            Carver cv(ctx);
+            cv.add(&gws, gbytes);
+            int rc = cv.commit();
+            if (rc != QPN_OK) return rc;
+        }
+        HIPCHK(ctx, qpn_launch_convexity(batch, n, m, Qd, Ad, eq, tol, convex, min_eig, null_dim, gws, s));
+        return QPN_OK;
+    }
+    double *dQ, *dA = nullptr, *dmin; uint8_t *de = nullptr; int32_t *dcvx, *dnull;
+    Carver cv(ctx);
+    cv.add((void **)&dQ, bQ);
+    if (m > 0) { cv.add((void **)&dA, bA); cv.add((void **)&de, be); }
+    cv.add((void **)&dcvx, (size_t)batch * 4); cv.add((void **)&dmin, (size_t)batch * 8); cv.add((void **)&dnull, (size_t)batch * 4);
+    if (gbytes) cv.add(&gws, gbytes);
+    int rc = cv.commit();
+    if (rc != QPN_OK) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(dQ, Qd, bQ, hipMemcpyHostToDevice, s));
+    if (m > 0) {
+        HIPCHK(ctx, hipMemcpyAsync(dA, Ad, bA, hipMemcpyHostToDevice, s));
+        HIPCHK(ctx, hipMemcpyAsync(de, eq, be, hipMemcpyHostToDevice, s));
+    }
+    HIPCHK(ctx, qpn_launch_convexity(batch, n, m, dQ, dA, de, tol, dcvx, dmin, dnull, gws, s));
+    HIPCHK(ctx, hipMemcpyAsync(convex, dcvx, (size_t)batch * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipMemcpyAsync(min_eig, dmin, (size_t)batch * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipMemcpyAsync(null_dim, dnull, (size_t)batch * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    return QPN_OK;
+}
+
 } // extern "C"
 
 namespace {

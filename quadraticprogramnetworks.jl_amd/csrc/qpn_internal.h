@@ -207,6 +207,13 @@ hipError_t qpn_launch_verify_nodes(int32_t batch, int32_t n, int32_t m, int32_t 
                                    double *gws = nullptr);       // gws: [batch][2][pad16(m)^2] Gram block / factor of verify_wide_node (n or m > 64)
 int qpn_verify_max_dim();
 
+// qpn_convexity.hip: check_qp_convexity for a batch of nodes (n <= 256, m <= 1024); gws: qpn_convexity_workspace_bytes
+hipError_t qpn_launch_convexity(int32_t batch, int32_t n, int32_t m, const double *Qd, const double *Ad, const uint8_t *eq,
+                                double tol, int32_t *convex, double *min_eig, int32_t *null_dim, void *gws, hipStream_t stream);
+size_t qpn_convexity_workspace_bytes(int32_t batch, int32_t n, int32_t m);
+#define QPN_CONVEXITY_MAX_N 256
+#define QPN_CONVEXITY_MAX_M 1024
+
 // ---- wave64 helpers (CDNA4: one wavefront = 64 lanes) --------------------------------
 #ifdef __HIPCC__
 // (A5+A6) reduced single-node KKT assembly of item b by ONE wavefront (src/avi.jl:205-251 + :305-377):

@@ -591,6 +591,31 @@ class Engine:
         return sol, lam[:, :m], path
 
 
+    def convexity_nodes(self, Qc, Ac, eq, tol=1e-6):
+        """Batched check_qp_convexity (src/qp_processing.jl:39-55) on node blocks: Qc [batch, n, n] and Ac [batch, n, m] in
+        the ABI layout, eq [batch, m] uint8 (the implicit equality rows) -> (convex [batch] int32, min_eig [batch],
+        null_dim [batch] int32)."""
+        dev = self._mode(Qc, Ac, eq)
+        self._bind_stream(dev)
+        if not dev:
+            Qc, Ac = self._host(Qc, np.float64), self._host(Ac, np.float64)
+            eq = self._host(eq, np.uint8)
+        else:
+            self._require_dev64(Qc, Ac)
+            if eq.dtype != torch.uint8 or not eq.is_contiguous():
+                raise QpnError("eq must be a contiguous uint8 tensor")
+        batch, n = Qc.shape[0], Qc.shape[-1]
+        m = eq.shape[1]
+        convex = self._alloc(dev, (batch,), np.int32)
+        min_eig = self._alloc(dev, (batch,), np.float64)
+        null_dim = self._alloc(dev, (batch,), np.int32)
+        rc = self.lib.qpn_convexity_nodes(self.ctx, batch, n, m, _ptr(Qc), _ptr(Ac) if m else None, _ptr(eq) if m else None,
+                                          float(tol), _ptr(convex), _ptr(min_eig), _ptr(null_dim),
+                                          MEM_DEVICE if dev else MEM_HOST)
+        self._chk(rc, "qpn_convexity_nodes")
+        return convex, min_eig, null_dim
+
+
 class Nodes:
     """Resident node records (``qpn_nodes_upload``): the records of a level's single-node pools live in HBM owned by the
     library; a sweep hands over only the parameters ``w`` and the output buffers.  What the outer loop

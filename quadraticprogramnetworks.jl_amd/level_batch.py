@@ -440,10 +440,15 @@ _VERIFY_MSGS = {0: "Current point is infeasible when using tolerance {tol}.", 1:
                 4: "Current point is suboptimal (via QP).", 5: "Solving for duals failed."}
 
 
-def verify_items(qpn, items, x, engine, tol=1e-4):
+def verify_items(qpn, items, x, engine, tol=1e-4, check_convexity=False):
     """verify_solution (src/qp_processing.jl:57-149) for MANY (node, child pieces) items: one qpn_verify_nodes call per
-    record shape.  items: list of (pid, [child Poly, ...]).  Returns (records, batches, one result dict per item)."""
+    record shape.  items: list of (pid, [child Poly, ...]).  Returns (records, batches, one result dict per item).
+    check_convexity runs check_qp_convexity (:69) on every item first: qp_processing.check_convexity_items, which raises
+    NonConvexQPError for the first non-convex item."""
     eng = engine
+    if check_convexity:
+        from .qp_processing import check_convexity_items
+        check_convexity_items(qpn, items, eng)
     leaf_ids = tuple(pid for pid, ch in items if not ch)
     all_leaf = len(leaf_ids) == len(items)
     if all_leaf:
@@ -691,7 +696,7 @@ def process_level(qpn, players: Sequence[int], x, S: Dict[int, list], engine=Non
         for combo in combos:
             items.append((pid, [S[j][ji] for j, ji in zip(children, combo)]))
             owner.append(pid)
-    recs, batches, rets = verify_items(qpn, items, x, eng)
+    recs, batches, rets = verify_items(qpn, items, x, eng, check_convexity=qpn.options.check_convexity)
     results = {}
     first = {}
     for i, (pid, _) in enumerate(items):

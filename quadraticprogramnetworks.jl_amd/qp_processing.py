@@ -1,6 +1,6 @@
-"""Host-side mirror of src/qp_processing.jl for the hot path: verify_solution (:57-149),
+"""Host-side mirror of src/qp_processing.jl for the hot path: check_qp_convexity (:39-55), verify_solution (:57-149),
 solve_qp(...; solver=:PATH) (:12-33) and the batch boundary process_qp (:151-241).  The
-arithmetic runs on the GPU (qpn_verify_nodes / qpn_solve_avi_batch)."""
+arithmetic runs on the GPU (qpn_convexity_nodes / qpn_verify_nodes / qpn_solve_avi_batch)."""
 from __future__ import annotations
 
 import itertools
@@ -13,6 +13,97 @@ from .engine import colmajor
 from .programs import Poly
 
 INF = np.inf
+
+
+CONVEXITY_TOL = 1e-6                        # check_qp_convexity's tol (src/qp_processing.jl:39)
+
+
+class NonConvexQPError(RuntimeError):
+    """check_qp_convexity's error (src/qp_processing.jl:52): the node's Hessian is not positive semidefinite on the null space
+    of its implicit equality rows.  .pid is the node, .min_eig the smallest eigenvalue of Z' (Q + Q') Z."""
+
+    def __init__(self, pid, min_eig):
+        super().__init__(f"QP {pid} is not convex. Exiting.")
+        self.pid = pid
+        self.min_eig = float(min_eig)
+
+
+def convexity_blocks(blocks, engine=None, tol=CONVEXITY_TOL):
+    """check_qp_convexity for MANY nodes: ONE implicit_bounds_batch call for all constraint stacks, then one qpn_convexity_nodes
+    call per (n, padded m).  blocks: list of (pid, Qd [n, n], A [m, c], l, u, dec) with A the stack's rows over some columns
+    that hold every variable they read, dec the positions of the node's decision variables among those columns.  Raises
+    NonConvexQPError for the FIRST non-convex block in list order; returns (min_eig, null_dim) per block otherwise."""
+    from .level_batch import ROW_PAD
+    from .polyhedra import implicit_bounds_batch
+    eng = _eng(engine)
+    blocks = list(blocks)
+    withrows = [k for k, b in enumerate(blocks) if len(b[3])]
+    eqs = [np.zeros(0, bool)] * len(blocks)
+    if withrows:
+        got = implicit_bounds_batch([(np.atleast_2d(np.asarray(blocks[k][2], dtype=np.float64)), np.asarray(blocks[k][3], dtype=np.float64),
+                                      np.asarray(blocks[k][4], dtype=np.float64)) for k in withrows], eng, tol=tol)
+        for k, (eq, _vals) in zip(withrows, got):
+            eqs[k] = np.asarray(eq, bool)
+    groups: Dict[tuple, List[int]] = {}
+    for k, (_pid, Qd, _A, l, _u, _dec) in enumerate(blocks):
+        m = len(l)
+        mp = max(ROW_PAD, -(-m // ROW_PAD) * ROW_PAD) if m else 0
+        groups.setdefault((np.shape(Qd)[0], mp), []).append(k)
+    convex = np.zeros(len(blocks), bool); min_eig = np.zeros(len(blocks)); null_dim = np.zeros(len(blocks), np.int64)
+    for (n, mp), idx in sorted(groups.items()):
+        Qc = np.zeros((len(idx), n, n)); Ac = np.zeros((len(idx), n, mp)); eq = np.zeros((len(idx), mp), np.uint8)
+        for t, k in enumerate(idx):
+            _pid, Qd, A, l, _u, dec = blocks[k]
+            m = len(l)
+            Qc[t] = np.asarray(Qd, dtype=np.float64).T
+            if m:
+                Ac[t, :, :m] = np.atleast_2d(np.asarray(A, dtype=np.float64))[:, np.asarray(dec, dtype=np.int64)].T
+                eq[t, :m] = eqs[k]
+        cvx, lam, nd = eng.convexity_nodes(Qc, Ac, eq, tol=tol)
+        convex[idx] = np.asarray(cvx) != 0; min_eig[idx] = np.asarray(lam); null_dim[idx] = np.asarray(nd)
+    for k, b in enumerate(blocks):                                  # the reference's order: the first failure raises
+        if not convex[k]:
+            raise NonConvexQPError(b[0], min_eig[k])
+    return list(zip(min_eig.tolist(), null_dim.tolist()))
+
+
+def check_qp_convexity(Q, A, l, u, dec_inds, pid, tol=CONVEXITY_TOL, engine=None):
+    """src/qp_processing.jl:39-55: raises NonConvexQPError unless Q[dec, dec] + Q[dec, dec]' is positive semidefinite (all
+    eigenvalues > -tol) on the null space of the implicit equality rows of {l <= A x <= u} restricted to dec_inds.
+    Q is the node's full n_total x n_total cost matrix, A the stack's rows over all variables.  Returns (min_eig, null_dim)."""
+    Q = np.asarray(Q, dtype=np.float64)
+    dec = np.asarray(list(dec_inds), dtype=np.int64)
+    A = np.asarray(A, dtype=np.float64).reshape(-1, Q.shape[0])
+    return convexity_blocks([(pid, Q[np.ix_(dec, dec)], A, np.asarray(l, dtype=np.float64).ravel(),
+                              np.asarray(u, dtype=np.float64).ravel(), dec)], engine=engine, tol=tol)[0]
+
+
+def check_convexity_items(qpn, items, engine, tol=CONVEXITY_TOL):
+    """check_qp_convexity for every (pid, [child Poly, ...]) item of a verify batch (level_batch.verify_items), in the items'
+    order (players in order, then sub-piece combinations in Iterators.product order).  The answer depends on the node and its
+    constraint stack alone, never on x, so it is kept per (pid, the appended pieces by identity) for the solve; only items not
+    seen before go to the engine, in one implicit_bounds_batch call and one qpn_convexity_nodes call per record shape."""
+    from .level_batch import node_record
+    memo = qpn.__dict__.setdefault("_convexity_memo", {})
+    todo, keys = [], []
+    for pid, ch in items:
+        key = (pid, tuple(id(P) for P in ch), tol)
+        ent = memo.get(key)
+        if ent is not None and all(a is b for a, b in zip(ent[0], ch)):
+            continue
+        if key in keys:
+            continue
+        rec = node_record(qpn, pid, ch)
+        n = rec["Qd"].shape[0]
+        A = np.hstack([rec["Ad"], rec["B"]]) if len(rec["l"]) else np.zeros((0, n + rec["par"].size))
+        todo.append((pid, rec["Qd"], A, rec["l"], rec["u"], np.arange(n)))
+        keys.append(key)
+    if not todo:
+        return
+    got = convexity_blocks(todo, engine=engine, tol=tol)           # raises for the first non-convex item
+    chs = {(pid, tuple(id(P) for P in ch), tol): tuple(ch) for pid, ch in items}
+    for key, r in zip(keys, got):
+        memo[key] = (chs[key], r)
 
 
 def node_record(qp, constraints: List[Poly], dec_inds, x):
@@ -34,9 +125,11 @@ def node_record(qp, constraints: List[Poly], dec_inds, x):
 
 def verify_solution(qp, pid, constraints: List[Poly], dec_inds, x, check_convexity=False, tol=1e-4,
                     engine=None):
-    """src/qp_processing.jl:57-149 -> dict(solution, lam, e, path)."""
+    """src/qp_processing.jl:57-149 -> dict(solution, lam, e, path).  check_convexity runs check_qp_convexity (:69) first."""
     rec = node_record(qp, constraints, dec_inds, x)
     m = len(rec["l"])
+    if check_convexity:
+        check_qp_convexity(qp.f.Q, rec["A"], rec["l"], rec["u"], dec_inds, pid, engine=engine)
     sol, lam, path = _eng(engine).verify_nodes(colmajor(rec["Qd"])[None], colmajor(rec["R"])[None], rec["qd"][None],
                                                colmajor(rec["Ad"])[None], colmajor(rec["B"])[None],
                                                rec["l"][None], rec["u"][None], rec["xd"][None], rec["w"], tol=tol)
@@ -52,15 +145,21 @@ _VERIFY_MSGS = {0: "Current point is infeasible when using tolerance {tol}.", 1:
                 4: "Current point is suboptimal (via QP).", 5: "Solving for duals failed."}
 
 
-def verify_solutions_batched(qp, pid, constraint_lists: List[List[Poly]], dec_inds, x, tol=1e-4, engine=None):
+def verify_solutions_batched(qp, pid, constraint_lists: List[List[Poly]], dec_inds, x, tol=1e-4, engine=None,
+                             check_convexity=False):
     """verify_solution for MANY constraint stacks of the same node in ONE qpn_verify_nodes call -- the
     sub-piece combinations of src/qp_processing.jl:162-205: the stacks
     share Q, q, x and differ only in the appended child pieces.  Ragged stacks are padded with inert rows
     (0' x in [-inf, inf]: never infeasible, never active, so they enter neither the least-squares system
-    of :114-115 nor the fallback of :129-137).  Returns one verify_solution dict per stack, in order."""
+    of :114-115 nor the fallback of :129-137).  Returns one verify_solution dict per stack, in order.  check_convexity checks
+    every stack first (one batch; the first non-convex stack raises NonConvexQPError)."""
     recs = [node_record(qp, cons, dec_inds, x) for cons in constraint_lists]
     if not recs:
         return []
+    if check_convexity:
+        dec = np.asarray(list(dec_inds), dtype=np.int64)
+        Qd = np.asarray(qp.f.Q, dtype=np.float64)[np.ix_(dec, dec)]
+        convexity_blocks([(pid, Qd, r["A"], r["l"], r["u"], dec) for r in recs], engine=engine)
     nb = len(recs)
     n = recs[0]["Qd"].shape[0]
     p = recs[0]["R"].shape[1]
