@@ -247,7 +247,7 @@ int qpn_ctx_set_auto_schedule(qpn_ctx *ctx, int32_t period);
  *                      (default: ONE wavefront per node for max(n, m) <= 48, one workgroup per node beyond), 0 = the general
  *                      route (assembled blocks -> the route of large nodes / the general kernels): the cross-check of the tests.
  *                      (Round 3's values 2 and 3 -- round 2's three-kernel route, the workgroup kernel for 33 .. 48 -- are gone;
- *                      the library reads no environment variable; diagnostic builds with -DQPN_DEV_SWITCHES accept a preset.)
+ *                      the library reads no environment variable.)
  *   QPN_OPT_BIG_ROUTE  kept for callers that set the default: takes 1 only (the blocked matrix-core crash straight from the
  *                      records, BASELINE config 5); round 2's route over an assembled M is gone as a node-record switch -- the
  *                      same kernels serve large node-shaped items passed as M through qpn_solve_avi_batch.

@@ -85,7 +85,9 @@ __global__ __launch_bounds__(TPB) void avi_solve_big(AviBatchArgs a, double *ws)
     const int tid = threadIdx.x;
     const int b = blockIdx.x;
     if (a.only_if && a.only_if[b] != a.only_if_value) return;
-    const int N = a.n_items ? a.n_items[b] : a.N, NC = N + 1;     // per-item size (reduced Schur problems)
+    // (N is uniform; readfirstlane keeps the register allocation it had as a per-item size: 116 VGPRs, 58 SGPR spill lanes
+    // instead of 117 and 66)
+    const int N = __builtin_amdgcn_readfirstlane(a.N), NC = N + 1;
 
     __shared__ BigShared S;
     extern __shared__ __attribute__((aligned(16))) unsigned char dyn[];
@@ -624,36 +626,23 @@ hipError_t launch_big_kernel(const AviBatchArgs &a, double *dict, hipStream_t st
 } // namespace
 
 // Large items.  Node-shaped ones (a kind vector is given) first try the blocked MFMA crash of
-// qpn_avi_schur_big.hip: stage A -> Lemke on the m x m Schur problem (this kernel, per-item sizes) -> finish;
-// what it declines (status -1), and everything else, runs on the general kernel.
+// qpn_avi_schur_big.hip: stage A -> Lemke on the m x m Schur problem -> finish; what it declines (status -1), and
+// everything else, runs on the general kernel.
 hipError_t qpn_launch_avi_solve_big(const AviBatchArgs &a, double *workspace, hipStream_t stream)
 {
     if (a.batch <= 0) return hipSuccess;
     const int N = a.N;
-    static const bool no_schur = [] { const char *e = QPN_DEV_ENV("QPN_AVI_BIG_KERNEL"); return e && e[0] == 'g'; }();   // "general"
-    if (a.kind == nullptr || a.only_if != nullptr || a.n_items != nullptr || no_schur) return launch_big_kernel(a, workspace, stream);
+    if (a.kind == nullptr || a.only_if != nullptr) return launch_big_kernel(a, workspace, stream);
     double *dict = workspace;
     void *sb = workspace + (size_t)a.batch * (size_t)N * (size_t)(N + 1);
     uint8_t *ones = reinterpret_cast<uint8_t *>(static_cast<char *>(sb) + qpn_schur_big_workspace_bytes(a.batch, N));
     SchurBigWs w{};
-    static const bool lemke_general = [] { const char *e = QPN_DEV_ENV("QPN_AVI_BIG_LEMKE"); return e && e[0] == 'g'; }();
     // node path with m <= 64 (uniform, known here): the Schur problems go to the one-wavefront register kernel
-    const bool lemke_reg = !lemke_general && a.nd.Qd && a.nd.m >= 1 && a.nd.m <= 64 && a.nd.n + a.nd.m == N &&
+    const bool lemke_reg = a.nd.Qd && a.nd.m >= 1 && a.nd.m <= 64 && a.nd.n + a.nd.m == N &&
                            (a.max_pivots <= 0 || a.max_pivots - a.nd.n >= 1);
-    hipError_t e = qpn_launch_schur_big_stage_a(a, sb, &w, !(lemke_general || lemke_reg), stream);
+    hipError_t e = qpn_launch_schur_big_stage_a(a, sb, &w, !lemke_reg, stream);
     if (e != hipSuccess) return e;
-    if (lemke_general) {
-        // A/B path: the general large-item kernel on the Schur problem (per-item sizes), one full dictionary pass per pivot
-        hipLaunchKernelGGL(fill_ones_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, stream, ones, N);
-        AviBatchArgs r{};
-        r.batch = a.batch; r.N = N; r.n_items = w.nred; r.vec_stride = N;
-        r.M = w.S; r.strideM = w.s_stride; r.q = w.c; r.l = w.l2; r.u = w.u2; r.kind = ones; r.stride_kind = 0;
-        r.z = w.lam; r.status = w.st2; r.pivots = w.piv2; r.resid = nullptr; r.active = nullptr;
-        r.check_tol = a.check_tol; r.piv_tol = a.piv_tol; r.feas_tol = a.feas_tol; r.comp_tol = a.comp_tol;
-        r.max_pivots = a.max_pivots; r.flags = a.flags | QPN_AVI_FLAG_COLD_START;
-        r.only_if = a.status; r.only_if_value = -2;
-        e = launch_big_kernel(r, dict, stream);
-    } else if (lemke_reg) {
+    if (lemke_reg) {
         // the Schur problems are all-GAVI items of size m -- the one-wavefront register kernel solves them (same pivot
         // rule), no workgroup barriers, no dictionary in HBM
         hipLaunchKernelGGL(fill_ones_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, stream, ones, N);

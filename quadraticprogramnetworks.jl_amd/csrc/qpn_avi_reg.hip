@@ -949,3 +949,19 @@ hipError_t qpn_launch_avi_solve_reg(const AviBatchArgs &a, hipStream_t stream)
     else hipLaunchKernelGGL(avi_solve_reg<8>, grid, block, 0, stream, a);
     return hipGetLastError();
 }
+
+int qpn_avi_max_n() { return qpn_avi_big_max_n(); }   // N <= 64: one wavefront; larger: qpn_avi_big.hip
+
+// Items of shape [free STD x n | GAVI x m] (a node's reduced KKT system) take the MFMA Schur-complement kernel; it flags
+// everything else (and any item whose H block fails its no-pivoting test) with status = -1, and the register kernel solves
+// exactly those in a second, gated launch.  Pure box-MCP batches (kind == NULL) and already gated launches go straight to
+// the register kernel.
+hipError_t qpn_launch_avi_solve(const AviBatchArgs &a, hipStream_t stream)
+{
+    if (a.kind == nullptr || a.only_if != nullptr || a.N < 2) return qpn_launch_avi_solve_reg(a, stream);
+    hipError_t e = qpn_launch_avi_solve_schur(a, nullptr, nullptr, nullptr, nullptr, stream);
+    if (e != hipSuccess) return e;
+    AviBatchArgs g = a;
+    g.only_if = a.status; g.only_if_value = -1; g.scan = 1;
+    return qpn_launch_avi_solve_reg(g, stream);
+}

@@ -1249,12 +1249,6 @@ hipError_t qpn_launch_avi_solve_schur_nodes(const AviBatchArgs &a, hipStream_t s
 {
     if (a.batch <= 0) return hipSuccess;
     SchurDebug d{nullptr, nullptr, nullptr, nullptr};
-#ifdef QPN_DIAG
-    // diagnostic builds only: extra dynamic LDS per block lowers the occupancy (occupancy-sensitivity experiments)
-    static const unsigned pad = [] { const char *e = QPN_DEV_ENV("QPN_DEBUG_LDS_PAD"); return e ? (unsigned)atoi(e) : 0u; }();
-#else
-    const unsigned pad = 0;
-#endif
     // resident wavefronts of this kernel: 16 per CU (LDS- and VGPR-bound, see the kernel header)
     static int resident[64] = {};
     int dev = 0;
@@ -1265,21 +1259,20 @@ hipError_t qpn_launch_avi_solve_schur_nodes(const AviBatchArgs &a, hipStream_t s
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
         resident[dev] = 16 * cus;
     }
-    static const bool no_stagger = [] { const char *e = QPN_DEV_ENV("QPN_NO_STAGGER"); return e && e[0] == '1'; }();   // A/B switch
     // a partial round has no burst to spread; other CU counts (partitioned modes) run without the stagger
-    const bool stag = !no_stagger && resident[dev] == kResidentMI355X && a.batch > kResidentMI355X;
+    const bool stag = resident[dev] == kResidentMI355X && a.batch > kResidentMI355X;
     const bool full = a.nd.n == 32 && a.nd.m == 32, half = a.nd.n == 16 && a.nd.m == 16;
     const dim3 grid((unsigned)a.batch), block(WAVE);
     if (full && a.nd.sym) {
-        if (stag) hipLaunchKernelGGL((avi_solve_schur<true, kResidentMI355X, 32, true>), grid, block, pad, stream, a, d);
-        else hipLaunchKernelGGL((avi_solve_schur<true, 0, 32, true>), grid, block, pad, stream, a, d);
+        if (stag) hipLaunchKernelGGL((avi_solve_schur<true, kResidentMI355X, 32, true>), grid, block, 0, stream, a, d);
+        else hipLaunchKernelGGL((avi_solve_schur<true, 0, 32, true>), grid, block, 0, stream, a, d);
         return hipGetLastError();
     }
-    if (stag && full) hipLaunchKernelGGL((avi_solve_schur<true, kResidentMI355X, 32>), grid, block, pad, stream, a, d);
-    else if (stag && half) hipLaunchKernelGGL((avi_solve_schur<true, kResidentMI355X, 16>), grid, block, pad, stream, a, d);
-    else if (stag) hipLaunchKernelGGL((avi_solve_schur<true, kResidentMI355X, 0>), grid, block, pad, stream, a, d);
-    else if (full) hipLaunchKernelGGL((avi_solve_schur<true, 0, 32>), grid, block, pad, stream, a, d);
-    else if (half) hipLaunchKernelGGL((avi_solve_schur<true, 0, 16>), grid, block, pad, stream, a, d);
-    else hipLaunchKernelGGL((avi_solve_schur<true, 0, 0>), grid, block, pad, stream, a, d);
+    if (stag && full) hipLaunchKernelGGL((avi_solve_schur<true, kResidentMI355X, 32>), grid, block, 0, stream, a, d);
+    else if (stag && half) hipLaunchKernelGGL((avi_solve_schur<true, kResidentMI355X, 16>), grid, block, 0, stream, a, d);
+    else if (stag) hipLaunchKernelGGL((avi_solve_schur<true, kResidentMI355X, 0>), grid, block, 0, stream, a, d);
+    else if (full) hipLaunchKernelGGL((avi_solve_schur<true, 0, 32>), grid, block, 0, stream, a, d);
+    else if (half) hipLaunchKernelGGL((avi_solve_schur<true, 0, 16>), grid, block, 0, stream, a, d);
+    else hipLaunchKernelGGL((avi_solve_schur<true, 0, 0>), grid, block, 0, stream, a, d);
     return hipGetLastError();
 }

@@ -1,6 +1,6 @@
 // qpn_capi.hip -- the extern "C" boundary of libqpn_hip.so (include/qpn_hip.h).
 // Host-side staging, argument checking and error mapping only; all arithmetic is in the
-// HIP kernels (qpn_avi_solve.hip, qpn_kkt.hip, qpn_verify.hip).  No exceptions cross the ABI.
+// HIP kernels (qpn_avi_*.hip, qpn_kkt.hip, qpn_verify.hip, ...).  No exceptions cross the ABI.
 #include <climits>
 #include <cmath>
 #include <cstdint>
@@ -137,8 +137,6 @@ int qpn_ctx_create(int device_id, qpn_ctx **out)
         delete ctx; return QPN_ERR_HIP;
     }
     ctx->stream = ctx->own_stream;
-    // diagnostic builds (-DQPN_DEV_SWITCHES) only: a preset of the mid-size route, read ONCE here; qpn_ctx_set_option overrides it
-    if (const char *e = QPN_DEV_ENV("QPN_NODES_MID")) { if (e[0] >= '0' && e[0] <= '1' && !e[1]) ctx->mid_route = e[0] - '0'; }
     *out = ctx;
     return QPN_OK;
 }
@@ -846,12 +844,112 @@ void nodes_sync_route(qpn_ctx *ctx, qpn_nodes *h)
     h->route_epoch = ctx->route_epoch;
 }
 
+// Which kernels take the nodes of one qpn_solve_nodes call: decided once per call, from the shape, the pivot budget and the
+// context's route options.
+enum class NodeRoute {
+    fused32,    // n, m <= 32: the fused MFMA kernel (qpn_avi_schur.hip)
+    mid,        // 33 .. 128: the fused mid-size kernels (qpn_avi_schur48.hip, qpn_avi_schur_wg.hip, qpn_avi_schur_wg2.hip)
+    big2,       // n 65 .. 256, m <= 256: the blocked crash straight from the records (qpn_avi_schur_big2.hip)
+    general,    // assembled blocks on qpn_launch_avi_solve / qpn_launch_avi_solve_big
+};
+
+NodeRoute node_route(const qpn_ctx *ctx, int32_t n, int32_t m, const qpn_avi_opts &o)
+{
+    if (n <= 32 && m <= 32 && m >= 1) return NodeRoute::fused32;
+    // the crash of the larger fused routes makes n pivots: a caller-set budget has to leave Lemke at least one
+    const bool budget = o.max_pivots <= 0 || o.max_pivots - n >= 1;
+    // QPN_OPT_MID_ROUTE = 0 sends the mid-size nodes down the general route
+    if (budget && ctx->mid_route == 1 && (qpn_schur_wg_shape(n, m) || qpn_schur_wg2_shape(n, m))) return NodeRoute::mid;
+    if (budget && qpn_schur_big2_shape(n, m)) return NodeRoute::big2;
+    return NodeRoute::general;
+}
+
+struct NodeWs {                 // workspace of the general kernels: assembled blocks, large-item dictionaries (null when not carved)
+    double *M, *q, *l, *u; uint8_t *kind; double *big;
+};
+
+// Decline protocol of the fused routes.  Which nodes a fused kernel declines (status = -1) depends on Qd, Ad, l, u alone (block
+// pivots of H, equality rows), never on w: a handle asks once -- the kernel counts its declines into decl_dev, declines_end sends
+// the count to the host behind an event -- and leaves the general launches out once it knows that none does.
+// *need_general: whether the general launches behind the fused kernel are needed.
+int declines_begin(qpn_ctx *ctx, qpn_nodes *h, AviBatchArgs &a, bool *need_general)
+{
+    *need_general = true;
+    if (!h) return QPN_OK;
+    nodes_poll_declines(h);
+    *need_general = h->decl_state != 2;
+    if (h->decl_state == 0) {
+        HIPCHK(ctx, hipMemsetAsync(h->decl_dev, 0, 4, ctx->stream));
+        a.decl_count = h->decl_dev;
+    }
+    return QPN_OK;
+}
+
+int declines_end(qpn_ctx *ctx, qpn_nodes *h)
+{
+    if (!h || h->decl_state != 0) return QPN_OK;
+    HIPCHK(ctx, hipMemcpyAsync(h->decl_host, h->decl_dev, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipEventRecord(h->decl_ev, ctx->stream));
+    h->decl_state = 1;
+    return QPN_OK;
+}
+
+// Does the handle keep a longest-first schedule for launches of this size?  Only for launches beyond the fused kernel's resident
+// set (`from` nodes): a smaller one has no tail to shorten.
+bool schedules(const qpn_nodes *h, int32_t batch, int32_t from) { return h && h->period > 0 && batch > from; }
+
+// The handle's longest-first schedule for the NEXT sweeps: the fused kernel keeps the smoothed pivot counts h->key up to date,
+// the order is re-sorted from them every `period` sweeps while they settle (eight refreshes), every 4 x period afterwards: the
+// sort is a one-workgroup launch (14 us) that the next sweep waits for.
+int schedule_refresh(qpn_ctx *ctx, qpn_nodes *h, int32_t batch)
+{
+    const int32_t per = h->calls < 8 * h->period ? h->period : 4 * h->period;
+    if (h->calls % per == 0) {
+        HIPCHK(ctx, qpn_launch_order_by_pivots(nullptr, batch, h->order, ctx->stream, h->key));
+        h->order_valid = true;
+    }
+    h->calls++;
+    return QPN_OK;
+}
+
+// the replicas of the iterate on peer GPUs (qpn_set_primal_mirrors): every primal block the kernel stores to x goes there too
+void set_mirrors(const qpn_ctx *ctx, AviBatchArgs &a, ptrdiff_t x_off)
+{
+    a.n_mirror = ctx->mirror_count;
+    for (int k = 0; k < ctx->mirror_count; ++k) a.mirror[k] = ctx->mirror_peer[k] + x_off;
+}
+
+// The general kernels, over the nodes a fused route declined (gated: status = -1) or over all of them.  The 32-class's is ONE
+// small scan-mode register launch (assemble_in_scan: its waves pick the flagged nodes, assemble their blocks into the workspace
+// and solve them); every other route assembles the blocks first and solves them on qpn_launch_avi_solve / _big.
+int solve_general(qpn_ctx *ctx, const AviBatchArgs &a, const NodeWs &ws, bool gated, bool assemble_in_scan)
+{
+    if (!ws.M) return fail_arg(ctx, "qpn_solve_nodes: internal error (no workspace for the general path)");
+    hipStream_t s = ctx->stream;
+    const int N = a.N;
+    AviBatchArgs g = a;
+    g.decl_count = nullptr;
+    g.M = ws.M; g.strideM = (int64_t)N * N; g.q = ws.q; g.l = ws.l; g.u = ws.u; g.kind = ws.kind; g.stride_kind = N;
+    if (gated) { g.only_if = a.status; g.only_if_value = -1; }
+    if (assemble_in_scan) {
+        g.scan = 1; g.assemble_first = 1;
+        HIPCHK(ctx, qpn_launch_avi_solve_reg(g, s));
+        return QPN_OK;
+    }
+    const NodeSrc &r = a.nd;
+    HIPCHK(ctx, qpn_launch_assemble_nodes(a.batch, r.n, r.m, r.p, r.Qd, r.R, r.qd, r.Ad, r.B, r.l, r.u, r.w, r.stride_w, ws.M,
+                                          ws.q, ws.l, ws.u, ws.kind, s, g.only_if, g.only_if_value));
+    if (N > 64) HIPCHK(ctx, qpn_launch_avi_solve_big(g, ws.big, s));
+    else HIPCHK(ctx, qpn_launch_avi_solve(g, s));
+    return QPN_OK;
+}
+
 // The launches of one sweep over device-resident records and outputs.  `h` (may be null) owns the records:
-// its decline knowledge and its schedule are used and refreshed.  wM.. = assembled-block workspace for the
-// general path (null only when h knows that no node declines).
+// its decline knowledge and its schedule are used and refreshed.  ws = workspace of the general kernels (not carved
+// only when h knows that no node declines).
 int solve_nodes_launch(qpn_ctx *ctx, qpn_nodes *h, int32_t batch, int32_t n, int32_t m, int32_t p, const NodeDev &d,
-                       int64_t stride_w, const qpn_avi_opts &o, double *x_dev, int64_t stride_x, double *wM, double *wq,
-                       double *wl, double *wu, uint8_t *wk, double *wbig, bool wg_shape)
+                       int64_t stride_w, const qpn_avi_opts &o, double *x_dev, int64_t stride_x, const NodeWs &ws,
+                       NodeRoute route)
 {
     hipStream_t s = ctx->stream;
     const int N = n + m;
@@ -863,143 +961,71 @@ int solve_nodes_launch(qpn_ctx *ctx, qpn_nodes *h, int32_t batch, int32_t n, int
 #ifdef QPN_STAMPS
     a.stamps = g_stamps;
 #endif
-    const bool mfma_shape = n <= 32 && m <= 32 && m >= 1;
-    bool x_in_kernel = false;
-    if (x_dev && mfma_shape) { a.x = x_dev; a.stride_x = stride_x; }      // written by the solve kernels themselves
     // replicas on peer GPUs: only when the whole written range lies inside the registered buffer
     const size_t x_span = x_dev ? ((size_t)(batch - 1) * (size_t)stride_x + (size_t)n) * 8 : 0;
     const bool mirrored = x_dev && ctx->mirror_count > 0 && (const char *)x_dev >= (const char *)ctx->mirror_own &&
                           (const char *)x_dev + x_span <= (const char *)ctx->mirror_own + ctx->mirror_bytes;
     const ptrdiff_t x_off = mirrored ? x_dev - ctx->mirror_own : 0;
-    if (mirrored && mfma_shape) {
-        a.n_mirror = ctx->mirror_count;
-        for (int k = 0; k < ctx->mirror_count; ++k) a.mirror[k] = ctx->mirror_peer[k] + x_off;
-    }
-    if (mfma_shape) {
+    bool x_in_kernel = false;
+    int rc = QPN_OK;
+    if (route == NodeRoute::fused32) {
+        // the fused kernel, and the general kernel behind it, write the primal blocks themselves
+        if (x_dev) { a.x = x_dev; a.stride_x = stride_x; x_in_kernel = true; }
+        if (mirrored) set_mirrors(ctx, a, x_off);
         // schedule hint (longest first): the handle's own, else the context's
         // the smoothed counts are fed by every sweep while the schedule settles (128 sweeps), by every fourth one afterwards:
         // a sample of the sweeps tells the order as well, and the solve kernel's read-modify-write of its node's key is
         // 0.5 % of the sweep
-        if (h && h->period > 0 && batch > 4096 && (h->calls < 128 || (h->calls & 3) == 0)) a.sched_key = h->key;
+        if (schedules(h, batch, 4096) && (h->calls < 128 || (h->calls & 3) == 0)) a.sched_key = h->key;
         if (h && h->order_valid) a.order = h->order;
         else if (ctx->order_count == batch && (!h || ctx->order_user)) a.order = ctx->order;     // a caller-installed order also serves handles
-        bool need_general = true;
-        if (h) {
-            nodes_poll_declines(h);
-            need_general = h->decl_state != 2;
-            if (h->decl_state == 0) {
-                HIPCHK(ctx, hipMemsetAsync(h->decl_dev, 0, 4, s));
-                a.decl_count = h->decl_dev;
-            }
-        }
-        // fused kernel; items it declines (status = -1) are assembled and solved by the general kernel
-        // (one small scan-mode launch: its waves pick the flagged items, assemble their blocks into the
-        // workspace and solve them)
+        bool need_general;
+        if ((rc = declines_begin(ctx, h, a, &need_general)) != QPN_OK) return rc;
         HIPCHK(ctx, qpn_launch_avi_solve_schur_nodes(a, s));
-        if (need_general) {
-            if (!wM) return fail_arg(ctx, "qpn_solve_nodes: internal error (no workspace for the general path)");
-            AviBatchArgs g = a;
-            g.decl_count = nullptr;
-            g.M = wM; g.strideM = (int64_t)N * N; g.q = wq; g.l = wl; g.u = wu; g.kind = wk; g.stride_kind = N;
-            g.only_if = d.st; g.only_if_value = -1; g.scan = 1; g.assemble_first = 1;
-            HIPCHK(ctx, qpn_launch_avi_solve_reg(g, s));
-        }
-        if (h && h->decl_state == 0) {
-            // which nodes decline depends on Qd, Ad, l, u alone (block pivots of H, equality rows), never on w: ask once
-            HIPCHK(ctx, hipMemcpyAsync(h->decl_host, h->decl_dev, 4, hipMemcpyDeviceToHost, s));
-            HIPCHK(ctx, hipEventRecord(h->decl_ev, s));
-            h->decl_state = 1;
-        }
+        if (need_general && (rc = solve_general(ctx, a, ws, true, true)) != QPN_OK) return rc;
+        if ((rc = declines_end(ctx, h)) != QPN_OK) return rc;
         if (h) {
-            // the handle's own longest-first schedule for the NEXT sweeps (launches that fill the GPU only)
-            if (h->period > 0 && batch > 4096) {
-                // the solve kernel keeps the smoothed counts up to date (every sweep); the order is re-sorted from them every
-                // `period` sweeps while they settle (eight refreshes), every 4 x period afterwards: the sort is a
-                // one-workgroup launch (14 us) that the next sweep waits for
-                const int32_t per = h->calls < 8 * h->period ? h->period : 4 * h->period;
-                if (h->calls % per == 0) {
-                    HIPCHK(ctx, qpn_launch_order_by_pivots(nullptr, batch, h->order, s, h->key));
-                    h->order_valid = true;
-                }
-                h->calls++;
-            }
+            if (schedules(h, batch, 4096) && (rc = schedule_refresh(ctx, h, batch)) != QPN_OK) return rc;
         } else if (ctx->auto_period > 0 && !ctx->order_user && d.pv && batch > 4096) {
             // automatic longest-first schedule for the NEXT calls over this batch (launches that fill the GPU only)
             if (ctx->auto_batch != batch) { ctx->auto_batch = batch; ctx->auto_calls = 0; }
             if (ctx->auto_calls % ctx->auto_period == 0) {
-                int rc = order_reserve(ctx, batch);
-                if (rc != QPN_OK) return rc;
+                if ((rc = order_reserve(ctx, batch)) != QPN_OK) return rc;
                 HIPCHK(ctx, qpn_launch_order_by_pivots(d.pv, batch, ctx->order, s));
                 ctx->order_count = batch;
             }
             ctx->auto_calls++;
         }
-    } else if (wg_shape) {
+    } else if (route == NodeRoute::mid) {
         // mid-size nodes (n, m <= 128): one wavefront (max(n, m) <= 48) or one workgroup per node straight from the records, ONE
-        // launch (qpn_avi_schur48.hip, qpn_avi_schur_wg.hip, qpn_avi_schur_wg2.hip); what they decline (status = -1) is assembled
-        // and solved by the general kernels in gated launches
-        bool need_general = true;
-        if (h) {
-            nodes_poll_declines(h);
-            need_general = h->decl_state != 2;
-            if (h->decl_state == 0) {
-                HIPCHK(ctx, hipMemsetAsync(h->decl_dev, 0, 4, s));
-                a.decl_count = h->decl_dev;
-            }
+        // launch; what they decline (status = -1) is assembled and solved by the general kernels in gated launches
+        bool need_general;
+        if ((rc = declines_begin(ctx, h, a, &need_general)) != QPN_OK) return rc;
+        AviBatchArgs f = a;
+        // the kernel writes the primal blocks into the iterate itself once it is known that nothing declines (the general
+        // kernels behind it do not); until then the strided copy below does
+        if (x_dev && !need_general) {
+            f.x = x_dev; f.stride_x = stride_x; x_in_kernel = true;
+            if (mirrored) set_mirrors(ctx, f, x_off);
         }
-        {
-            // the kernel writes the primal blocks into the iterate itself once it is known that nothing declines (the
-            // general kernels behind it do not); until then the strided copy below does
-            if (x_dev && !need_general) {
-                a.x = x_dev; a.stride_x = stride_x; x_in_kernel = true;
-                if (mirrored) {
-                    a.n_mirror = ctx->mirror_count;
-                    for (int k = 0; k < ctx->mirror_count; ++k) a.mirror[k] = ctx->mirror_peer[k] + x_off;
-                }
-            }
-            // the handle's longest-first schedule as in the 32-class (launches beyond the resident set only: 2 048 wavefronts of the
-            // one-wavefront kernel, 1 024 workgroups of the 49-64 class, 256 of the 65-128 class): the kernel feeds the smoothed
-            // pivot counts, the order is re-sorted from them
-            const bool one_wave = qpn_schur48_shape(n, m), two_role = qpn_schur_wg2_shape(n, m);
-            const bool sched = h && h->period > 0 && batch > (one_wave ? 2048 : (two_role ? 256 : 1024));
-            if (sched) { a.sched_key = h->key; if (h->order_valid) a.order = h->order; }
-            if (two_role) HIPCHK(ctx, qpn_launch_schur_wg2_nodes(a, s));
-            else if (one_wave) HIPCHK(ctx, qpn_launch_avi_solve_schur48_nodes(a, s));
-            else HIPCHK(ctx, qpn_launch_schur_wg_nodes(a, s));
-            a.sched_key = nullptr; a.order = nullptr;
-            if (sched) {
-                const int32_t per = h->calls < 8 * h->period ? h->period : 4 * h->period;
-                if (h->calls % per == 0) {
-                    HIPCHK(ctx, qpn_launch_order_by_pivots(nullptr, batch, h->order, s, h->key));
-                    h->order_valid = true;
-                }
-                h->calls++;
-            }
-            a.x = nullptr; a.n_mirror = 0;
-        }
-        if (need_general) {
-            if (!wM) return fail_arg(ctx, "qpn_solve_nodes: internal error (no workspace for the general path)");
-            HIPCHK(ctx, qpn_launch_assemble_nodes(batch, n, m, p, d.Q, d.R, d.q, d.A, d.B, d.l, d.u, d.w, stride_w, wM, wq, wl,
-                                                  wu, wk, s, d.st, -1));
-            AviBatchArgs g = a;
-            g.decl_count = nullptr;
-            g.M = wM; g.strideM = (int64_t)N * N; g.q = wq; g.l = wl; g.u = wu; g.kind = wk; g.stride_kind = N;
-            g.only_if = d.st; g.only_if_value = -1;
-            if (N > 64) HIPCHK(ctx, qpn_launch_avi_solve_big(g, wbig, s));
-            else HIPCHK(ctx, qpn_launch_avi_solve(g, s));
-        }
-        if (h && h->decl_state == 0) {
-            HIPCHK(ctx, hipMemcpyAsync(h->decl_host, h->decl_dev, 4, hipMemcpyDeviceToHost, s));
-            HIPCHK(ctx, hipEventRecord(h->decl_ev, s));
-            h->decl_state = 1;
-        }
-    } else if (qpn_schur_big2_shape(n, m) && wbig && (o.max_pivots <= 0 || o.max_pivots - n >= 1)) {
-        // large nodes (BASELINE config 5): the blocked crash straight from the records (qpn_avi_schur_big2.hip), the
-        // delayed-update Lemke kernel on the Schur problems, read-back and post-check on the records; no M is assembled unless a
-        // node declines -- those (status = -1) are assembled and solved by the general kernel in gated launches
+        // the handle's longest-first schedule as in the 32-class (launches beyond the resident set only: 2 048 wavefronts of the
+        // one-wavefront kernel, 1 024 workgroups of the 49-64 class, 256 of the 65-128 class)
+        const bool one_wave = qpn_schur48_shape(n, m), two_role = qpn_schur_wg2_shape(n, m);
+        const bool sched = schedules(h, batch, one_wave ? 2048 : (two_role ? 256 : 1024));
+        if (sched) { f.sched_key = h->key; if (h->order_valid) f.order = h->order; }
+        if (two_role) HIPCHK(ctx, qpn_launch_schur_wg2_nodes(f, s));
+        else if (one_wave) HIPCHK(ctx, qpn_launch_avi_solve_schur48_nodes(f, s));
+        else HIPCHK(ctx, qpn_launch_schur_wg_nodes(f, s));
+        if (sched && (rc = schedule_refresh(ctx, h, batch)) != QPN_OK) return rc;
+        if (need_general && (rc = solve_general(ctx, a, ws, true, false)) != QPN_OK) return rc;
+        if ((rc = declines_end(ctx, h)) != QPN_OK) return rc;
+    } else if (route == NodeRoute::big2) {
+        // large nodes (BASELINE config 5): the blocked crash straight from the records, the delayed-update Lemke kernel on the
+        // Schur problems, read-back and post-check on the records; no M is assembled unless a node declines -- those
+        // (status = -1) are assembled and solved by the general kernel in gated launches
         SchurBigWs sw{};
-        double *dict = wbig;
-        void *sb = wbig + (size_t)batch * (size_t)N * (size_t)(N + 1);
+        double *dict = ws.big;
+        void *sb = ws.big + (size_t)batch * (size_t)N * (size_t)(N + 1);
         HIPCHK(ctx, qpn_launch_schur_big2_stage_a(a, sb, dict, &sw, s));
         // Stage B: resident records with symmetric Qd blocks (a.nd.sym) go through block principal pivoting first; whatever it
         // leaves (and every node otherwise) is the delayed-update Lemke kernel's
@@ -1008,21 +1034,11 @@ int solve_nodes_launch(qpn_ctx *ctx, qpn_nodes *h, int32_t batch, int32_t n, int
         if (bpp) HIPCHK(ctx, qpn_launch_schur_big_bpp(a, sw, dict, s));
         HIPCHK(ctx, qpn_launch_schur_big_lemke(a, sw, dict, s, bpp ? 1 : 0));
         HIPCHK(ctx, qpn_launch_schur_big2_finish(a, sw, s));
-        HIPCHK(ctx, qpn_launch_assemble_nodes(batch, n, m, p, d.Q, d.R, d.q, d.A, d.B, d.l, d.u, d.w, stride_w, wM, wq, wl,
-                                              wu, wk, s, d.st, -1));
-        AviBatchArgs g = a;
-        g.M = wM; g.strideM = (int64_t)N * N; g.q = wq; g.l = wl; g.u = wu; g.kind = wk; g.stride_kind = N;
-        g.only_if = d.st; g.only_if_value = -1;
-        HIPCHK(ctx, qpn_launch_avi_solve_big(g, wbig, s));
+        if ((rc = solve_general(ctx, a, ws, true, false)) != QPN_OK) return rc;
     } else {
-        HIPCHK(ctx, qpn_launch_assemble_nodes(batch, n, m, p, d.Q, d.R, d.q, d.A, d.B, d.l, d.u, d.w, stride_w, wM, wq, wl,
-                                              wu, wk, s));
-        AviBatchArgs g = a;
-        g.M = wM; g.strideM = (int64_t)N * N; g.q = wq; g.l = wl; g.u = wu; g.kind = wk; g.stride_kind = N;
-        if (N > 64) HIPCHK(ctx, qpn_launch_avi_solve_big(g, wbig, s));
-        else HIPCHK(ctx, qpn_launch_avi_solve(g, s));
+        if ((rc = solve_general(ctx, a, ws, false, false)) != QPN_OK) return rc;
     }
-    if (x_dev && !mfma_shape && !x_in_kernel) {     // general sizes: strided device copy of the primal blocks (and to the replicas)
+    if (x_dev && !x_in_kernel) {     // strided device copy of the primal blocks (and to the replicas)
         HIPCHK(ctx, hipMemcpy2DAsync(x_dev, (size_t)stride_x * 8, d.z, (size_t)N * 8, (size_t)n * 8, (size_t)batch,
                                      hipMemcpyDeviceToDevice, s));
         for (int k = 0; mirrored && k < ctx->mirror_count; ++k)
@@ -1047,24 +1063,21 @@ int solve_nodes_any(qpn_ctx *ctx, qpn_nodes *h, int32_t batch, int32_t n, int32_
     const size_t bN = (size_t)batch * N;
     const NodeSizes sz = node_sizes(batch, n, m, p, stride_w);
     const bool host = mem == QPN_MEM_HOST;
-    const bool mfma_shape = n <= 32 && m <= 32 && m >= 1;
-    // the handle may already know that the general path has nothing to do: no workspace for it then
+    const NodeRoute route = node_route(ctx, n, m, o);
+    // the handle may already know that the general path behind a fused route has nothing to do: no workspace for it then
     nodes_poll_declines(h);
     nodes_sync_route(ctx, h);
-    // mid-size nodes: the fused kernels (no workspace); QPN_OPT_MID_ROUTE = 0 sends them down the general route
-    const bool mid_ok = qpn_schur_wg_shape(n, m) && (o.max_pivots <= 0 || o.max_pivots - n >= 1);
-    const bool wg2_ok = qpn_schur_wg2_shape(n, m) && (o.max_pivots <= 0 || o.max_pivots - n >= 1);
-    const bool wg_shape = ctx->mid_route == 1 && (mid_ok || wg2_ok);
-    const bool need_ws = !(h && (mfma_shape || wg_shape) && h->decl_state == 2);
+    const bool fused = route == NodeRoute::fused32 || route == NodeRoute::mid;
+    const bool need_ws = !(h && fused && h->decl_state == 2);
 
     NodeDev d{Qd, R, qd, Ad, B, l, u, w, z, status, resid, pivots, active};
-    double *wM = nullptr, *wq = nullptr, *wl = nullptr, *wu = nullptr, *wbig = nullptr; uint8_t *wk = nullptr;
+    NodeWs ws{};
     double *hQ, *hR, *hq, *hA, *hB, *hl, *hu, *hw, *hz = nullptr, *hres, *hx = nullptr; int32_t *hst, *hpv; uint8_t *hact;
     Carver cv(ctx);
     if (need_ws) {
-        cv.add((void **)&wM, bN * N * 8); cv.add((void **)&wq, bN * 8); cv.add((void **)&wl, bN * 8);
-        cv.add((void **)&wu, bN * 8); cv.add((void **)&wk, bN);
-        if (N > 64) cv.add((void **)&wbig, qpn_avi_big_workspace_bytes(batch, N));
+        cv.add((void **)&ws.M, bN * N * 8); cv.add((void **)&ws.q, bN * 8); cv.add((void **)&ws.l, bN * 8);
+        cv.add((void **)&ws.u, bN * 8); cv.add((void **)&ws.kind, bN);
+        if (N > 64) cv.add((void **)&ws.big, qpn_avi_big_workspace_bytes(batch, N));
     }
     const bool z_ws = !z;          // no z wanted (handle calls): the kernels still need somewhere to put it
     if (host) {
@@ -1076,7 +1089,7 @@ int solve_nodes_any(qpn_ctx *ctx, qpn_nodes *h, int32_t batch, int32_t n, int32_
         cv.add((void **)&hw, sz.w + 8); cv.add((void **)&hz, bN * 8);
         cv.add((void **)&hres, (size_t)batch * 8); cv.add((void **)&hst, (size_t)batch * 4);
         cv.add((void **)&hpv, (size_t)batch * 4); cv.add((void **)&hact, bN);
-        if (x && mfma_shape) cv.add((void **)&hx, (size_t)batch * n * 8);
+        if (x && route == NodeRoute::fused32) cv.add((void **)&hx, (size_t)batch * n * 8);
     } else if (z_ws) cv.add((void **)&hz, bN * 8);
     int rc = cv.commit();
     if (rc != QPN_OK) return rc;
@@ -1101,7 +1114,7 @@ int solve_nodes_any(qpn_ctx *ctx, qpn_nodes *h, int32_t batch, int32_t n, int32_
 
     double *x_dev = host ? hx : x;
     const int64_t sx_dev = host ? (int64_t)n : stride_x;
-    rc = solve_nodes_launch(ctx, h, batch, n, m, p, d, stride_w, o, x_dev, sx_dev, wM, wq, wl, wu, wk, wbig, wg_shape);
+    rc = solve_nodes_launch(ctx, h, batch, n, m, p, d, stride_w, o, x_dev, sx_dev, ws, route);
     if (rc != QPN_OK) return rc;
     if (host) {
         if (z) HIPCHK(ctx, hipMemcpyAsync(z, d.z, bN * 8, hipMemcpyDeviceToHost, s));

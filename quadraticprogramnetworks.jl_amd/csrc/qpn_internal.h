@@ -7,16 +7,6 @@
 
 #include "../../include/qpn_hip.h"
 
-// Developer switches on the environment (kernel A/B, diagnostic routes) exist in diagnostic builds only
-// (csrc/build.sh -DQPN_DEV_SWITCHES): the product library dispatches on its arguments and on qpn_ctx_set_option alone and
-// never reads the environment.
-#ifdef QPN_DEV_SWITCHES
-#include <stdlib.h>
-#define QPN_DEV_ENV(name) getenv(name)
-#else
-#define QPN_DEV_ENV(name) (static_cast<const char *>(nullptr))
-#endif
-
 // per-node records (qpn_solve_nodes): the solve kernel assembles the KKT blocks on the fly
 struct NodeSrc {
     int32_t n, m, p;
@@ -71,9 +61,7 @@ struct AviBatchArgs {
     double *mirror[QPN_MAX_MIRRORS];
     // optional schedule of the fused node kernel: wavefront i solves node order[i] (a permutation)
     const int32_t *order;
-    // large-item kernel only: per-item size override (items of different N <= this->N in one launch; vectors
-    // are then laid out with stride vec_stride, the workspace with the launch-wide N)
-    const int32_t *n_items;
+    // optional stride of the per-item vectors (0: N); reduced problems keep their parent's
     int64_t vec_stride;
     // fused node kernel only: counts the items it declines (status = -1), for callers that own the records and
     // want to know whether the general-kernel launch behind it has anything to do (qpn_nodes handles); may be null
@@ -90,10 +78,6 @@ struct QpnPerDeviceOnce {
     int device() const { int d = 0; (void)hipGetDevice(&d); return d & 63; }
 };
 
-// qpn_avi_solve.hip
-hipError_t qpn_launch_avi_solve(const AviBatchArgs &a, hipStream_t stream);      // dispatcher
-hipError_t qpn_launch_avi_solve_lds1(const AviBatchArgs &a, hipStream_t stream); // LDS-tableau kernel
-int qpn_avi_max_n();
 
 // qpn_avi_big.hip: 64 < N <= 1024, one workgroup per item, dictionary in an HBM workspace
 int qpn_avi_big_max_n();
@@ -101,9 +85,7 @@ size_t qpn_avi_big_workspace_bytes(int batch, int N);
 hipError_t qpn_launch_avi_solve_big(const AviBatchArgs &a, double *workspace, hipStream_t stream);
 
 // A8: nodes with n or m above this take the workgroup kernel verify_wide_node (qpn_verify.hip), the others one wavefront per node
-#ifndef QPN_VERIFY_WIDE_FROM
-#define QPN_VERIFY_WIDE_FROM 64
-#endif
+constexpr int QPN_VERIFY_WIDE_FROM = 64;
 // ... and the few nodes of the 33 .. 64 class with more than 32 active rows (verify_node64 flags them) take the same kernel out
 // of a workspace of this many slots (a device counter hands them out; nodes beyond it go to round 1's kernels)
 constexpr int QPN_VERIFY_MID_SLOTS = 256;
@@ -146,7 +128,9 @@ hipError_t qpn_launch_avi_solve_schur(const AviBatchArgs &a, double *dbgS, doubl
 hipError_t qpn_launch_avi_solve_schur_nodes(const AviBatchArgs &a, hipStream_t stream);   // a.nd set, a.M unused
 
 // qpn_avi_reg.hip
+hipError_t qpn_launch_avi_solve(const AviBatchArgs &a, hipStream_t stream);      // dispatcher: Schur kernel, then the register kernel
 hipError_t qpn_launch_avi_solve_reg(const AviBatchArgs &a, hipStream_t stream);  // register-tableau kernel
+int qpn_avi_max_n();
 
 // qpn_kkt.hip
 hipError_t qpn_launch_order_by_pivots(const int32_t *pivots, int32_t count, int32_t *order, hipStream_t stream,

@@ -11,7 +11,7 @@
 //                   `\` of :115), sign/residual test (:119).  Nodes that fail it get their
 //                   bounded-LSQ box-AVI (Ad Ad', -Ad q~, sign bounds; :129-137 with the PATH MCP
 //                   of :12-27 reduced to its lambda block) written to scratch, path = -1.
-//   avi_solve_lds1  (qpn_avi_solve.hip) gated on path == -1.
+//   qpn_launch_avi_solve (the register kernel, qpn_avi_reg.hip) gated on path == -1.
 //   verify_stage2   accepts iff || Ad' lambda - q~ ||_2 <= 1e-4 (:138).
 #include "qpn_internal.h"
 #include "qpn_tile_chol.h"
@@ -1692,7 +1692,7 @@ hipError_t qpn_launch_verify_nodes(int32_t batch, int32_t n, int32_t m, int32_t 
     a.Qd = Qd; a.R = R; a.qd = qd; a.Ad = Ad; a.B = B; a.l = l; a.u = u; a.xd = xd; a.w = w;
     a.stride_w = stride_w; a.tol = tol; a.solution = solution; a.lambda = lambda; a.path = path;
     a.sG = sG; a.sq = sq; a.slb = slb; a.sub = sub; a.sz = sz;
-    if (n > 64 || m > 64) {
+    if (n > QPN_VERIFY_WIDE_FROM || m > QPN_VERIFY_WIDE_FROM) {
         // wide nodes: verify_wide_node (up to 128 active rows, every path inside the workgroup), then round 1's kernels over what it
         // flagged -2 (their bounded-LSQ fallback is a large box-AVI, N = m, on the large-item kernel)
         if (m >= 1 && gws) {

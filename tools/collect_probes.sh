@@ -11,7 +11,6 @@ run bash tools/pivot_cost.sh
 run python3 tools/lpt_probe.py
 run python3 tools/verify_rate.py
 run python3 tools/host_cost.py
-CNT=512 run python3 tools/config5_probe.py
 for n in 1250 2500 4096 5000 10000 20480 40960; do
   echo "===== bench.py --nodes $n" >> "$O"
   python3 bench.py --nodes $n --steps 100 --warmup 20 --no-cpu-baseline 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('nodes', d['config']['nodes'], 'value', round(d['value']/1e6,2), 'M solves/s, ms_per_step', round(d['ms_per_step'],4), 'roofline frac', round(d['roofline']['frac'],4))" >> "$O"
