@@ -19,33 +19,9 @@
 // transposed through a 5 KB LDS stage; the post-check re-reads it (served by L2 / Infinity Cache).
 #include "qpn_internal.h"
 
-#define QINF __builtin_huge_val()
-
 namespace {
 
-constexpr int WAVE = 64;
-
-#ifdef QPN_STAMPS
-#define STAMP(slot)                                                     \
-    do {                                                                \
-        unsigned long long now__ = __builtin_amdgcn_s_memtime();        \
-        __builtin_amdgcn_s_waitcnt(0xC07F);                             \
-        stamp_acc[slot] += now__ - stamp_last;                          \
-        stamp_last = now__;                                             \
-    } while (0)
-#else
-#define STAMP(slot) do { } while (0)
-#endif
-
-// Every workgroup of this file is ONE wavefront: LDS operations of a wave execute in issue order, so ordering between a
-// lane's store and another lane's load needs no s_barrier and no drain of the memory counters -- only that the compiler
-// keeps the program order of the LDS accesses and does not move them across this point (as in qpn_avi_schur.hip).
-__device__ __forceinline__ void wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
+// Every workgroup of this file is ONE wavefront: wave_sync (qpn_internal.h) orders its LDS accesses, no s_barrier needed.
 
 template <int BS> struct Geo {
     static constexpr int NB = 8 * BS;        // padded dimension held in registers
@@ -112,10 +88,7 @@ __device__ __forceinline__ void avi_solve_reg_item(const AviBatchArgs &a, const 
     __shared__ double sl[NB], su[NB], snb[2 * NB + 2];
     __shared__ int sat[NB], elist[8 * NB + 8];
 
-#ifdef QPN_STAMPS
-    unsigned long long stamp_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    unsigned long long stamp_last = __builtin_amdgcn_s_memtime();
-#endif
+    STAMP_DECL;
     const double *Mg = a.M + (size_t)b * (size_t)a.strideM;
     const size_t vo = (size_t)b * (size_t)(a.vec_stride ? a.vec_stride : N);     // vectors of item b (reduced problems keep the parent's stride)
     const int max_piv = a.max_pivots > 0 ? a.max_pivots : 50 * N + 100;

@@ -36,30 +36,7 @@
 #include <cstdlib>
 #include <type_traits>
 
-#define QINF __builtin_huge_val()
-
 namespace {
-
-constexpr int WAVE = 64;
-
-#ifdef QPN_STAMPS
-#define STAMP(slot)                                                     \
-    do {                                                                \
-        unsigned long long now__ = __builtin_amdgcn_s_memtime();        \
-        __builtin_amdgcn_s_waitcnt(0xC07F);                             \
-        stamp_acc[slot] += now__ - stamp_last;                          \
-        stamp_last = now__;                                             \
-    } while (0)
-#else
-#define STAMP(slot) do { } while (0)
-#endif
-
-typedef double d4 __attribute__((ext_vector_type(4)));
-
-#define MFMA(a_, b_, c_) __builtin_amdgcn_mfma_f64_16x16x4f64((a_), (b_), (c_), 0, 0, 0)
-// D = C - A B: on gfx950 the BLGP field of the fp64 MFMAs holds NEG modifiers (bit 0: A, bit 1: B, bit 2: C;
-// tools/mfma_neg_probe.hip), so an operand's sign costs no VALU instruction
-#define MFMA_NEGA(a_, b_, c_) __builtin_amdgcn_mfma_f64_16x16x4f64((a_), (b_), (c_), 0, 0, 1)
 
 // 8 tiles of the top half, named (no arrays: see qpn_avi_reg.hip)
 #define TL(I, J) tl_##I##_##J
@@ -68,50 +45,7 @@ typedef double d4 __attribute__((ext_vector_type(4)));
 
 struct SchurDebug { double *S, *c, *W, *h; };
 
-// The workgroup IS one wavefront: LDS operations of a wave execute in issue order, so ordering between
-// a lane's store and another lane's load needs no s_barrier and no drain of the memory counters -- only
-// that the compiler keeps the program order of the LDS accesses (it must: they may alias) and does not
-// move them across this point.
-__device__ __forceinline__ void wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// 1/x (callers guarantee |x| is well away from 0 on every lane whose result is used).  v_rcp_f64 is good to
-// 4.6e-8; one Newton step brings it to <= 2.3e-15 relative (10 ulp), two give the correctly rounded quotient
-// (tools/rcp_probe.hip).  The pivoting arithmetic uses one step: its results are certified by the post-check
-// on the original blocks, and 1e-15 is far inside the 1e-9 parity bar.
-// max(a, |b|) in ONE instruction (fmax(a, fabs(b)) costs three: the compiler canonicalises both operands first; the
-// callers feed no NaNs that matter: a NaN entry fails the pivot test and the item goes to the general kernel)
-// v[l] + v[l ^ 32] in every lane (gfx950: v_permlane32_swap exchanges the upper half of one register with the lower half of another)
-__device__ __forceinline__ double sum_halves(double v)
-{
-    const int lo = __double2loint(v), hi = __double2hiint(v);
-    const auto c = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
-    const auto d = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
-    return __hiloint2double(d[0], c[0]) + __hiloint2double(d[1], c[1]);
-}
-__device__ __forceinline__ double min_abs_nc(double a, double b)      // min(a, |b|)
-{
-    double r;
-    asm("v_min_f64 %0, %1, |%2|" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ double max_abs_nc(double a, double b)
-{
-    double r;
-    asm("v_max_f64 %0, %1, |%2|" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-
-__device__ __forceinline__ double rcp64(double x)
-{
-    double r = __builtin_amdgcn_rcp(x);
-    const double e = fma(-x, r, 1.0);
-    return fma(r, e, r);
-}
+// The workgroup IS one wavefront: wave_sync (qpn_internal.h) orders its LDS accesses, no s_barrier needed.
 
 #define QPN_STG_UNIT 64       /* stagger step of the first round: 64 x 64 clocks = 1.7 us per wave slot */
 constexpr int kResidentMI355X = 16 * 256;      // wavefronts of this kernel resident at once: 16 per CU, 256 CUs
@@ -196,9 +130,8 @@ __global__ __launch_bounds__(WAVE, 4) void avi_solve_schur(AviBatchArgs a, Schur
     const double *Mg = NODES ? nullptr : a.M + (size_t)b * (size_t)a.strideM;
     const size_t vo = (size_t)b * (size_t)N;
     const bool act = l < N;
+    STAMP_DECL;
 #ifdef QPN_STAMPS
-    unsigned long long stamp_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    unsigned long long stamp_last = __builtin_amdgcn_s_memtime();
     const unsigned long long stamp_rt0 = __builtin_amdgcn_s_memrealtime() & 0xffffffffull;
 #endif
     // node records (fused path): M = [[Qd, -Ad'],[Ad, 0]], q = [qd + R w; B w], src/avi.jl:205-251 + :305-377

@@ -10,31 +10,7 @@
 // (an equality row, a block pivot below the threshold) are flagged status = -1 for the general path, as in the other kernels.
 #include "qpn_internal.h"
 
-#define QINF __builtin_huge_val()
-
 namespace {
-
-typedef double d4 __attribute__((ext_vector_type(4)));
-#define MFMA(a_, b_, c_) __builtin_amdgcn_mfma_f64_16x16x4f64((a_), (b_), (c_), 0, 0, 0)
-#define MFMA_NEGA(a_, b_, c_) __builtin_amdgcn_mfma_f64_16x16x4f64((a_), (b_), (c_), 0, 0, 1)      // D = C - A B (gfx950 NEG bits)
-
-__device__ __forceinline__ void wsync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-__device__ __forceinline__ double rcp64_(double x)
-{
-    double r = __builtin_amdgcn_rcp(x);
-    const double e = fma(-x, r, 1.0);
-    return fma(r, e, r);
-}
-#ifdef QPN_STAMPS
-#define STAMP(slot) do { unsigned long long now__ = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_s_waitcnt(0xC07F); stamp_acc[slot] += now__ - stamp_last; stamp_last = now__; } while (0)
-#else
-#define STAMP(slot) do { } while (0)
-#endif
 
 constexpr int T3 = 3, NP = 48, SAS = 49;       // tiles a side, padded size, column stride of the LDS block buffer (odd: conflict-free)
 
@@ -48,10 +24,7 @@ __global__ __launch_bounds__(64, 2) void avi_solve_schur48(AviBatchArgs a)
         if (l == 0) { a.status[b] = -1; if (a.decl_count) atomicAdd(a.decl_count, 1); }
     };
     if (!(n >= 1 && n <= NP && m >= 0 && m <= NP)) { decline(); return; }
-#ifdef QPN_STAMPS
-    unsigned long long stamp_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    unsigned long long stamp_last = __builtin_amdgcn_s_memtime();
-#endif
+    STAMP_DECL;
 
     // block buffer: Qd while the H tiles are built, then Ad ([column of x][constraint row]) through the S product, then W~ for the
     // read-back, then the solution in item order.  18 816 + 1 664 B = 20 480 B: EIGHT wavefronts per CU (two per SIMD); q never
@@ -109,7 +82,7 @@ __global__ __launch_bounds__(64, 2) void avi_solve_schur48(AviBatchArgs a)
             for (int t = 0; t < 16; ++t) { sA[(c0 + t) * SAS + l] = v[t]; mabs = fmax(mabs, fabs(v[t])); }
         }
     }
-    wsync();
+    wave_sync();
     // the top half [H | C~] in the accumulator layout of v_mfma_f64_16x16x4_f64: tile (I, J), register g, lane (lq, lc) holds
     // row 16 I + 4 g + lq, column 16 J + lc
     d4 T[T3][2 * T3];
@@ -124,7 +97,7 @@ __global__ __launch_bounds__(64, 2) void avi_solve_schur48(AviBatchArgs a)
                 if (rr == cc && rr >= n) v = 1.0;                     // padded x rows: identity
                 T[I][J][g] = v;
             }
-    wsync();
+    wave_sync();
     // ---- Ad -> LDS: sA[x column j][constraint row r] (zero-padded)
 #pragma unroll 1
     for (int c0 = 0; c0 < NP; c0 += 16) {
@@ -141,7 +114,7 @@ __global__ __launch_bounds__(64, 2) void avi_solve_schur48(AviBatchArgs a)
             for (int t = 0; t < 16; ++t) { sA[(c0 + t) * SAS + l] = v[t]; mabs = fmax(mabs, fabs(v[t])); }
         }
     }
-    wsync();
+    wave_sync();
     // the tiles hold -C = +Ad' (W~ = -W: S = D - A W = A W~, x = W~ lambda - h)
 #pragma unroll
     for (int I = 0; I < T3; ++I)
@@ -178,7 +151,7 @@ __global__ __launch_bounds__(64, 2) void avi_solve_schur48(AviBatchArgs a)
                         sU[rr * 4 + kcol] = v;
                     }
             }
-            wsync();
+            wave_sync();
             double pm[4][4];
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
@@ -192,7 +165,7 @@ __global__ __launch_bounds__(64, 2) void avi_solve_schur48(AviBatchArgs a)
 #pragma unroll
             for (int s = 0; s < 4; ++s) {
                 okp = okp && fabs(pm[s][s]) >= diag_thr;
-                rd[s] = rcp64_(pm[s][s]);
+                rd[s] = rcp64(pm[s][s]);
 #pragma unroll
                 for (int i = s + 1; i < 4; ++i) {
                     const double f = pm[i][s] * rd[s];
@@ -217,7 +190,7 @@ __global__ __launch_bounds__(64, 2) void avi_solve_schur48(AviBatchArgs a)
                     kx -= fma(up[3], x3, fma(up[2], x2, fma(up[1], x1, up[0] * x0)));
                     *reinterpret_cast<d4 *>(sU + l * 4) = up;
                 }
-                wsync();
+                wave_sync();
                 double au[T3];
 #pragma unroll
                 for (int I = 0; I < T3; ++I) au[I] = sU[(16 * I + lc) * 4 + lq];
@@ -230,7 +203,7 @@ __global__ __launch_bounds__(64, 2) void avi_solve_schur48(AviBatchArgs a)
                         for (int I = 0; I < T3; ++I) T[I][J] = MFMA_NEGA(au[I], vraw, T[I][J]);
                     }
                 }
-                wsync();
+                wave_sync();
             }
         }
     }
@@ -265,7 +238,7 @@ __global__ __launch_bounds__(64, 2) void avi_solve_schur48(AviBatchArgs a)
                     for (int Jb = 0; Jb < T3; ++Jb) SB[Ib][Jb] = MFMA(ao[Ib], T[I][T3 + Jb][g], SB[Ib][Jb]);
             }
         }
-    wsync();
+    wave_sync();
     double xb = 0.0;
     {
         const bool lowr = l < m;
@@ -281,7 +254,7 @@ __global__ __launch_bounds__(64, 2) void avi_solve_schur48(AviBatchArgs a)
 
     // W~ leaves the registers for the Lemke phase: it takes Ad's place in the block buffer, [x row][constraint], for the read-back
     // (the post-check reads Ad from memory again: the records of this node are a few microseconds old in L2 / the memory-side cache)
-    wsync();
+    wave_sync();
 #pragma unroll
     for (int I = 0; I < T3; ++I)
 #pragma unroll
@@ -302,7 +275,7 @@ __global__ __launch_bounds__(64, 2) void avi_solve_schur48(AviBatchArgs a)
     int satv = 0;
     int rowvar = actb ? l : -1, colvar = actb ? NBP + l : (l == XC ? VTH : -1);
     double nbval = 0.0, tcol = 0.0;
-    wsync();
+    wave_sync();
     // the dictionary: SJ<Jb>[4 Ib + g] = row 16 Ib + 4 g + lq, column 16 Jb + lc -- three 16-element register vectors (12 used):
     // static element accesses are plain registers, the pivot row is read with a wave-uniform DYNAMIC index (s_set_gpr_idx:
     // no branch tree, no scratch), and the exchange is one asm block per column tile, so that every dictionary register has ONE
@@ -362,12 +335,12 @@ __global__ __launch_bounds__(64, 2) void avi_solve_schur48(AviBatchArgs a)
             if (Jc == 0) { FOR_K(M_PUB, 0) } else if (Jc == 1) { FOR_K(M_PUB, 1) } else { FOR_K(M_PUB, 2) }
 #undef M_PUB
         }
-        wsync();
+        wave_sync();
         const double cm = actb ? sucol[myslot] : 0.0;
         STAMP(6);   // (diagnostic builds: entering column through LDS)
         // ---- ratio test (two-pass Harris with 1e-10 slack; largest pivot among ties, the artificial first)
         const double gdir = __hiloint2double(__double2hiint(cm) ^ (sneg ? (int)0x80000000 : 0), __double2loint(cm));
-        const double rc = rcp64_(gdir);
+        const double rc = rcp64(gdir);
         const bool gneg = __double2hiint(gdir) < 0;
         const double tb = gneg ? lo : hi;
         const bool cnd = actb && (fabs(gdir) > ptol) && (fabs(tb) < QINF);
@@ -429,7 +402,7 @@ __global__ __launch_bounds__(64, 2) void avi_solve_schur48(AviBatchArgs a)
             const double delta = sneg ? -step : step;
             const int vl = readlane_i32(rowvar, r);
             const double enter_val = readlane_f64(nbval, c) + delta;
-            wsync();
+            wave_sync();
             {
                 const double pa = svrow[lc], pb = svrow[16 + lc], pc = svrow[32 + lc], px = svrow[XC];
                 v0 = pa * inv; v1 = pb * inv; v2 = pc * inv;
@@ -531,16 +504,16 @@ __global__ __launch_bounds__(64, 2) void avi_solve_schur48(AviBatchArgs a)
 #undef M_XBLOCK
         }
         c = cnext;
-        wsync();
+        wave_sync();
         STAMP(3);   // (... row, bookkeeping, exchange)
     }
 
     STAMP(3);   // Lemke
     // ---- read back: lambda_k, then x = W~ lambda - h -------------------------------------------------------------
-    wsync();
+    wave_sync();
     if (actb) sval[rowvar] = xb;
     if (l <= XC) sval[colvar] = nbval;
-    wsync();
+    wave_sync();
     // x_l = (W~ lambda)_l - h_l, lane l <-> row l: W~ from the block buffer, lambda broadcast from sval
     double wl = 0.0;
     {
@@ -560,10 +533,10 @@ __global__ __launch_bounds__(64, 2) void avi_solve_schur48(AviBatchArgs a)
         if (i0 < N) zk0 = i0 < n ? wl - kx : sval[NBP + (i0 - n)];
         if (i1 < N) zk1 = sval[NBP + (i1 - n)];                  // (n <= 48 < 64: the second round holds multipliers only)
     }
-    wsync();
+    wave_sync();
     if (l < N) SZ(l) = zk0;
     if (64 + l < N) SZ(64 + l) = zk1;
-    wsync();
+    wave_sync();
 
     STAMP(4);   // read-back
     // ---- post-check against the ORIGINAL blocks, src/avi.jl:71-76 / :148-156 -------------------------------

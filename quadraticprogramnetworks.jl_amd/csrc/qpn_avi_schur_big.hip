@@ -24,8 +24,6 @@
 #include "qpn_internal.h"
 #include "qpn_tile_chol.h"
 
-#define QINF __builtin_huge_val()
-
 namespace {
 
 constexpr int TPB = 256;
@@ -33,11 +31,6 @@ constexpr int PW = 16;                  // panel width (block pivot size)
 constexpr int NMAXA = 512;              // rows of the top half held in LDS as U' (512 x 17 doubles = 68 KB)
 constexpr int LDU = PW + 1;
 __host__ __device__ constexpr int sb_pend_stride(int m) { return ((m + 1 + 15) & ~31) + 16; }
-
-typedef double d4 __attribute__((ext_vector_type(4)));
-#define MFMA(a_, b_, c_) __builtin_amdgcn_mfma_f64_16x16x4f64((a_), (b_), (c_), 0, 0, 0)
-
-__device__ __forceinline__ int pad16(int v) { return (v + 15) & ~15; }
 
 struct SbShared {
     double red[TPB / 64];    // one slot per wave (sb_block_*)
@@ -700,28 +693,14 @@ __global__ __launch_bounds__(TPB) void schur_big_finish(AviBatchArgs a, SchurBig
 // it (1 MB read + written at m = 256); every KP pivots the pending pairs are folded into T_base with a rank-KP
 // MFMA pass.  Entries of the exchanged row / column carry a relative error ~ eps |p| (cancellation in the
 // rank-1 form); the result is certified by the post-check on the original blocks like every other path.
-#ifdef QPN_STAMPS
-#define LSTAMP(slot)                                                    \
-    do {                                                                \
-        unsigned long long now__ = __builtin_amdgcn_s_memtime();        \
-        __builtin_amdgcn_s_waitcnt(0xC07F);                             \
-        stamp_acc[slot] += now__ - stamp_last;                          \
-        stamp_last = now__;                                             \
-    } while (0)
-#else
-#define LSTAMP(slot) do { } while (0)
-#endif
 template <int KP>
 __global__ __launch_bounds__(TPB) void schur_big_lemke(AviBatchArgs a, SchurBigWs w, double *dict, int m_lo, int m_hi, int after_bpp)
 {
     const int tid = threadIdx.x, b = blockIdx.x;
     if (a.status[b] != -2) return;
     if (after_bpp && w.st2[b] == QPN_SUCCESS) return;       // schur_big_bpp (below) has finished this node and written lambda
-#ifdef QPN_STAMPS
     // (diagnostic builds: thread 0's clocks per phase, second half of a [2][batch][8] buffer -- tools/big2_stamps.py)
-    unsigned long long stamp_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    unsigned long long stamp_last = __builtin_amdgcn_s_memtime();
-#endif
+    STAMP_DECL;
     const int wave = tid >> 6, lane = tid & 63, lc = lane & 15, lq = lane >> 4;
     // (row stride of T_base: a multiple of 16 doubles -- with m + 1 every 16-column run of a row straddles two cache lines and
     // the fold's tile stores are partial-sector writes)
@@ -817,7 +796,7 @@ __global__ __launch_bounds__(TPB) void schur_big_lemke(AviBatchArgs a, SchurBigW
         return r == 0x7fffffff ? -1 : r;
     };
 
-    LSTAMP(0);   // setup
+    STAMP(0);   // setup
     while (status == QPN_MAX_ITERS) {
         if (pivots >= max_piv) break;
         // ---- entering column of the CURRENT dictionary: T_base column minus the pending rank-1 terms
@@ -830,7 +809,7 @@ __global__ __launch_bounds__(TPB) void schur_big_lemke(AviBatchArgs a, SchurBigW
             for (int k = 0; k < npend; ++k) v = fma(-PA[k * mA + i], PB[k * mB + c], v);
             cm[h] = v;
         }
-        LSTAMP(1);   // entering column (T_base + pending terms)
+        STAMP(1);   // entering column (T_base + pending terms)
         // ---- ratio test
         double gdir[2], rc[2], dd[2], d1min = QINF;
         bool cndlo[2], cnd[2];
@@ -861,7 +840,7 @@ __global__ __launch_bounds__(TPB) void schur_big_lemke(AviBatchArgs a, SchurBigW
             }
         }
         const int r = sb_block_argbest(ag, myr, S, tid);
-        LSTAMP(2);   // ratio test + the two reductions
+        STAMP(2);   // ratio test + the two reductions
         const int ncand = r < 0 ? 0 : 1;
         if (ncand == 0) {
             // the entering variable reaches its own opposite bound first: no basis change
@@ -916,7 +895,7 @@ __global__ __launch_bounds__(TPB) void schur_big_lemke(AviBatchArgs a, SchurBigW
             else xb[h] = fma(delta, cm[h], xb[h]);
         }
         __syncthreads();
-        LSTAMP(3);   // pivot row (T_base + pending terms) -> pending pair
+        STAMP(3);   // pivot row (T_base + pending terms) -> pending pair
         if (tid == 0) { colvar[c] = vl; cnb[c] = leave_val; }
         npend++;
         pivots++;
@@ -943,7 +922,7 @@ __global__ __launch_bounds__(TPB) void schur_big_lemke(AviBatchArgs a, SchurBigW
         }
         __syncthreads();
         c = col_of(vn);
-        LSTAMP(4);   // bookkeeping + the next column's index
+        STAMP(4);   // bookkeeping + the next column's index
         if (c < 0) { status = QPN_FAILURE; break; }
         // ---- fold the pending pairs into T_base: rank-KP MFMA pass over its tiles
         if (npend == KP) {
@@ -985,10 +964,10 @@ __global__ __launch_bounds__(TPB) void schur_big_lemke(AviBatchArgs a, SchurBigW
             npend = 0;
             __threadfence_block();
             __syncthreads();
-            LSTAMP(5);   // fold of KP pending pairs
+            STAMP(5);   // fold of KP pending pairs
         }
     }
-    LSTAMP(6);
+    STAMP(6);
 #ifdef QPN_STAMPS
     if (tid == 0 && a.stamps) for (int k = 0; k < 8; ++k) a.stamps[((size_t)a.batch + b) * 8 + k] = stamp_acc[k];
 #endif
@@ -1227,20 +1206,11 @@ hipError_t qpn_launch_schur_big_stage_a(const AviBatchArgs &a, void *ws, SchurBi
     int32_t *ip = reinterpret_cast<int32_t *>(p);
     w.st2 = ip; ip += batch; w.piv2 = ip; ip += batch; w.nsplit = ip; ip += batch; w.nred = ip; ip += batch;
     *out = w;
-    static QpnPerDeviceOnce attr_once;
-    const int attr_dev = attr_once.device();
-    if (!attr_once.done[attr_dev]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(schur_big_stage_a<false>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024);
-        if (e != hipSuccess) return e;
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(schur_big_stage_a<true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-        if (e != hipSuccess) return e;
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(schur_big_finish),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 16 * 1024);
-        if (e != hipSuccess) return e;
-        attr_once.done[attr_dev] = true;
-    }
+    static QpnLdsLimits lds_limits;
+    if (const hipError_t e = lds_limits.raise({{schur_big_stage_a<false>, 100 * 1024}, {schur_big_stage_a<true>, 150 * 1024},
+                                               {schur_big_finish, 16 * 1024}});
+        e != hipSuccess)
+        return e;
     // node path: every item has the record's (n, m), known here -- small nodes keep their top half in LDS
     if (a.nd.Qd && a.nd.n >= 1 && a.nd.m >= 1 && a.nd.n + a.nd.m == N) {
         const size_t n_pad = (size_t)((a.nd.n + 15) & ~15), m_pad = (size_t)((a.nd.m + 15) & ~15);
@@ -1271,17 +1241,10 @@ hipError_t qpn_launch_schur_big_finish(const AviBatchArgs &a, const SchurBigWs &
 // kernel's dictionary workspace (batch x N x (N+1) doubles), reused here as T_base.
 hipError_t qpn_launch_schur_big_lemke(const AviBatchArgs &a, const SchurBigWs &w, double *dict, hipStream_t stream, int after_bpp)
 {
-    static QpnPerDeviceOnce attr_once;
-    const int attr_dev = attr_once.device();
-    if (!attr_once.done[attr_dev]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(schur_big_lemke<16>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-        if (e != hipSuccess) return e;
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(schur_big_lemke<8>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-        if (e != hipSuccess) return e;
-        attr_once.done[attr_dev] = true;
-    }
+    static QpnLdsLimits lds_limits;
+    if (const hipError_t e = lds_limits.raise({{schur_big_lemke<16>, 150 * 1024}, {schur_big_lemke<8>, 150 * 1024}});
+        e != hipSuccess)
+        return e;
     // The reduced size m of an item is known on the device only (stage A found the split), and the LDS of a launch
     // is sized on the host: two launches, each taking the items of its own m range -- m <= ceil(N / 2) (a node
     // with no more constraint rows than variables: config 5) gets 16 pending pairs in <= 80 KB, i.e. two
@@ -1313,13 +1276,8 @@ hipError_t qpn_launch_schur_big_lemke(const AviBatchArgs &a, const SchurBigWs &w
 hipError_t qpn_launch_schur_big_bpp(const AviBatchArgs &a, const SchurBigWs &w, double *dict, hipStream_t stream)
 {
     const size_t bytes = (size_t)bpp_tiles(BPP_KMAX / 16) * BPP_TSZ * sizeof(double);       // 60 928 B: two workgroups per CU
-    static QpnPerDeviceOnce attr_once;
-    const int attr_dev = attr_once.device();
-    if (!attr_once.done[attr_dev]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(schur_big_bpp), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-        if (e != hipSuccess) return e;
-        attr_once.done[attr_dev] = true;
-    }
+    static QpnLdsLimits lds_limits;
+    if (const hipError_t e = lds_limits.raise({{schur_big_bpp, (int)bytes}}); e != hipSuccess) return e;
     hipLaunchKernelGGL(schur_big_bpp, dim3((unsigned)a.batch), dim3(TPB), bytes, stream, a, w, dict);
     return hipGetLastError();
 }

@@ -25,17 +25,12 @@
 #include <type_traits>
 #include <cstdlib>
 
-#define QINF __builtin_huge_val()
-
 namespace {
 
 constexpr int TPB2 = 1024;              // 16 wavefronts
 constexpr int LDP = 80;                 // row stride of the pivot block / its inverse (== 16 mod 32: rows lq, lq + 1 on other banks)
 constexpr int LDD = 17;                 // row stride of the inverted diagonal tile
 constexpr int JC = 4;                   // column tiles per staged block of W in the S product
-typedef double d4 __attribute__((ext_vector_type(4)));
-#define MFMA(a_, b_, c_) __builtin_amdgcn_mfma_f64_16x16x4f64((a_), (b_), (c_), 0, 0, 0)
-#define MFMA_NEGA(a_, b_, c_) __builtin_amdgcn_mfma_f64_16x16x4f64((a_), (b_), (c_), 0, 0, 1)      // D = C - A B
 
 // LDS map of the elimination (doubles)
 constexpr int MC = 13;                              // column tiles per mega-chunk of pivot rows
@@ -47,27 +42,10 @@ constexpr int OFF_RED = OFF_G + 256;                // block reductions, flags  
 constexpr int LDS_DOUBLES = OFF_RED + 32;           // 19 008 doubles = 148.5 KB: one workgroup per CU
 constexpr int LDS_SPROD = 2 * 16 * 256 + 256;       // the S product: two blocks of W (4 block rows x JC tiles) + b
 
-#ifdef QPN_STAMPS
-#define STAMP(slot)                                                     \
-    do {                                                                \
-        unsigned long long now__ = __builtin_amdgcn_s_memtime();        \
-        __builtin_amdgcn_s_waitcnt(0xC07F);                             \
-        stamp_acc[slot] += now__ - stamp_last;                          \
-        stamp_last = now__;                                             \
-    } while (0)
-#else
-#define STAMP(slot) do { } while (0)
-#endif
-
-__device__ __forceinline__ int pad16(int v) { return (v + 15) & ~15; }
-__device__ __forceinline__ double max_abs(double a, double b)      // max(a, |b|)
-{
-    double r;
-    asm("v_max_f64 %0, %1, |%2|" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-
-__device__ __forceinline__ double rcp64(double x)      // two Newton steps on v_rcp_f64: <= 1 ulp of 1 / x for normal x
+// two Newton steps on v_rcp_f64: <= 1 ulp of 1 / x for normal x.  Deliberately not the one-step rcp64 of qpn_internal.h:
+// invert16 below forms the explicit inverse of the pivot block from these reciprocals, and that inverse multiplies every pivot
+// row of the rank-64 update -- one step less would change this kernel's results.
+__device__ __forceinline__ double rcp64_2nr(double x)
 {
     double r = __builtin_amdgcn_rcp(x);
     r = fma(fma(-x, r, 1.0), r, r);
@@ -93,7 +71,7 @@ __device__ bool invert16(const double *P, int ldp, double *D, double thr, double
         const double piv = readlane_f64(ar[s_], s_);
         ok = ok && (fabs(piv) >= thr);
         mp = fmin(mp, fabs(piv));
-        const double r = rcp64(piv);
+        const double r = rcp64_2nr(piv);
         const double e = (li == s_) ? 1.0 : 0.0;
         const double g = (ar[s_] - e) * r;
 #pragma unroll
@@ -165,7 +143,7 @@ __global__ __launch_bounds__(256) void schur_big2_convert(AviBatchArgs a, SchurB
         for (int q = 0; q < 4; ++q)
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-                mabs = max_abs(mabs, v[q][g]);
+                mabs = max_abs_nc(mabs, v[q][g]);
                 if (t0 + q < nt) Tt[((size_t)(t0 + q) << 8) + g * 64 + lane] = v[q][g];
             }
     }
@@ -196,10 +174,7 @@ __global__ __launch_bounds__(TPB2, 1) void schur_big2_eliminate(AviBatchArgs a, 
     int *const sFlag = reinterpret_cast<int *>(sRed + 24);
     double *const Tt = w.Tt + (size_t)b * (size_t)w.tt_stride;
     auto tile = [&](int I_, int J_) -> double * { return Tt + ((size_t)(I_ * nct + J_) << 8); };
-#ifdef QPN_STAMPS
-    unsigned long long stamp_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    unsigned long long stamp_last = __builtin_amdgcn_s_memtime();
-#endif
+    STAMP_DECL;
     if constexpr (MODE == 2) { if (a.status[b] != -4) return; }
     // equality rows are not taken here (their multiplier would have to be crashed in)
     int bad_row = 0;
@@ -350,7 +325,7 @@ __global__ __launch_bounds__(TPB2, 1) void schur_big2_eliminate(AviBatchArgs a, 
             }
             if constexpr (FIRST) {
 #pragma unroll
-                for (int t = 0; t < 16; ++t) mabs = max_abs(mabs, u[t]);
+                for (int t = 0; t < 16; ++t) mabs = max_abs_nc(mabs, u[t]);
             }
 #pragma unroll
             for (int t = 0; t < 16; ++t) if (16 * I + lc == 64 * kb + 4 * t + lq) u[t] -= 1.0;      // pivot rows carry P - I
@@ -395,7 +370,7 @@ __global__ __launch_bounds__(TPB2, 1) void schur_big2_eliminate(AviBatchArgs a, 
                     }
                     if constexpr (FIRST) {
 #pragma unroll
-                        for (int g = 0; g < 4; ++g) mabs = max_abs(mabs, ct[g]);
+                        for (int g = 0; g < 4; ++g) mabs = max_abs_nc(mabs, ct[g]);
                     }
                     const double *const vb = sV + (jj << 10) + lane;
                     if (bw == 4) {
@@ -695,23 +670,12 @@ hipError_t qpn_launch_schur_big2_stage_a(const AviBatchArgs &a, void *ws, double
     // (the top half of a node: pad16(n) rows of pad16(n) + pad16(m) + 16 doubles -- inside the stride above for n, m <= 256)
     const size_t need = (size_t)((a.nd.n + 15) & ~15) * (size_t)(((a.nd.n + 15) & ~15) + ((a.nd.m + 15) & ~15) + 16);
     if (!qpn_schur_big2_shape(a.nd.n, a.nd.m) || a.nd.n + a.nd.m != N || need > (size_t)w.tt_stride) return hipErrorInvalidValue;
-    static QpnPerDeviceOnce attr_once;
-    const int attr_dev = attr_once.device();
-    if (!attr_once.done[attr_dev]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(schur_big2_eliminate<0>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DOUBLES * (int)sizeof(double));
-        if (e != hipSuccess) return e;
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(schur_big2_eliminate<1>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DOUBLES * (int)sizeof(double));
-        if (e != hipSuccess) return e;
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(schur_big2_eliminate<2>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DOUBLES * (int)sizeof(double));
-        if (e != hipSuccess) return e;
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(schur_big2_sprod),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, LDS_SPROD * (int)sizeof(double));
-        if (e != hipSuccess) return e;
-        attr_once.done[attr_dev] = true;
-    }
+    static QpnLdsLimits lds_limits;
+    constexpr int elim_bytes = LDS_DOUBLES * (int)sizeof(double);
+    if (const hipError_t e = lds_limits.raise({{schur_big2_eliminate<0>, elim_bytes}, {schur_big2_eliminate<1>, elim_bytes},
+                                               {schur_big2_eliminate<2>, elim_bytes}, {schur_big2_sprod, LDS_SPROD * (int)sizeof(double)}});
+        e != hipSuccess)
+        return e;
     const dim3 grid((unsigned)batch);
     if ((a.nd.n & 15) == 0 && (a.nd.m & 15) == 0) {
         hipLaunchKernelGGL(schur_big2_eliminate<1>, grid, dim3(TPB2), LDS_DOUBLES * sizeof(double), stream, a, w);

@@ -29,96 +29,10 @@
 // elimination) and one-step Newton reciprocals: parity bar DESIGN.md section 2.
 #include "qpn_internal.h"
 
-#define QINF __builtin_huge_val()
-
 namespace {
 
 constexpr int VLD = 144;                // row stride of the published pivot rows (128 columns; == 16 mod 32)
-typedef double d4 __attribute__((ext_vector_type(4)));
 typedef double d16 __attribute__((ext_vector_type(16)));
-#define MFMA(a_, b_, c_) __builtin_amdgcn_mfma_f64_16x16x4f64((a_), (b_), (c_), 0, 0, 0)
-#define MFMA_NEGA(a_, b_, c_) __builtin_amdgcn_mfma_f64_16x16x4f64((a_), (b_), (c_), 0, 0, 1)      // D = C - A B (gfx950 NEG bits)
-
-
-__device__ __forceinline__ void wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-__device__ __forceinline__ double rcp64(double x)      // one Newton step on v_rcp_f64: <= 10 ulp (tools/rcp_probe.hip)
-{
-    double r = __builtin_amdgcn_rcp(x);
-    const double e = fma(-x, r, 1.0);
-    return fma(r, e, r);
-}
-__device__ __forceinline__ double max_abs_nc(double a, double b)
-{
-    double r;
-    asm("v_max_f64 %0, %1, |%2|" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-// min over all 64 lanes of v and the wave-uniform `lim`, returned wave-uniform: four DPP row stages, row_bcast:15 into rows
-// 1 and 3, row_bcast:31 into rows 2 and 3, lane 63 read out (callers feed no NaNs; non-candidates carry +inf)
-__device__ __forceinline__ double wave_min64_with_limit_f64(double v, double lim)
-{
-    {
-        const double ls = udbl(lim);
-        double r;
-        asm("v_min_f64 %0, %1, %2\n\ts_nop 1" : "=v"(r) : "v"(v), "s"(ls));
-        v = r;
-    }
-    v = min_f64_nc(v, dpp_f64<0xB1>(v));
-    v = min_f64_nc(v, dpp_f64<0x4E>(v));
-    v = min_f64_nc(v, dpp_f64<0x141>(v));
-    v = min_f64_nc(v, dpp_f64<0x140>(v));
-    {
-        int lo = __double2loint(v), hi = __double2hiint(v);
-        lo = __builtin_amdgcn_update_dpp(lo, lo, 0x142, 0xA, 0xF, false);      // rows 1, 3 <- lane 15 of rows 0, 2
-        hi = __builtin_amdgcn_update_dpp(hi, hi, 0x142, 0xA, 0xF, false);
-        v = min_f64_nc(v, __hiloint2double(hi, lo));
-    }
-    {
-        int lo = __double2loint(v), hi = __double2hiint(v);
-        lo = __builtin_amdgcn_update_dpp(lo, lo, 0x143, 0xC, 0xF, false);      // rows 2, 3 <- lane 31
-        hi = __builtin_amdgcn_update_dpp(hi, hi, 0x143, 0xC, 0xF, false);
-        v = min_f64_nc(v, __hiloint2double(hi, lo));
-    }
-    return readlane_f64(v, 63);
-}
-
-// lane id recomputed on the spot (v_mbcnt on the full EXEC mask; opaque, so the compiler does not keep the copy from the
-// start of the kernel alive -- and spill it -- across the phases): every phase derives its own lane coordinates
-__device__ __forceinline__ int lane_id_fresh()
-{
-    int x = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-    asm volatile("" : "+v"(x));
-    return x;
-}
-// v + (v of lane ^ 16) + (v of lane ^ 32) + (v of lane ^ 48): gfx950's row / half swaps (VALU, no LDS trip, no address registers)
-__device__ __forceinline__ double xsum_rows(double v)
-{
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    const auto a = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
-    const auto b = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-    const double s = __hiloint2double(b[0], a[0]) + __hiloint2double(b[1], a[1]);
-    lo = __double2loint(s); hi = __double2hiint(s);
-    const auto c = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
-    const auto d = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
-    return __hiloint2double(d[0], c[0]) + __hiloint2double(d[1], c[1]);
-}
-
-#ifdef QPN_STAMPS
-#define STAMP(slot)                                                     \
-    do {                                                                \
-        unsigned long long now__ = __builtin_amdgcn_s_memtime();        \
-        __builtin_amdgcn_s_waitcnt(0xC07F);                             \
-        stamp_acc[slot] += now__ - stamp_last;                          \
-        stamp_last = now__;                                             \
-    } while (0)
-#else
-#define STAMP(slot) do { } while (0)
-#endif
 
 // LDS map (doubles).  The big area is, in turn: the Qd staging block [n_pad][n_pad + 2], the published pivot rows
 // [2][4][VLD], W~ for the S product [n_pad][m_pad], S on its way into the Stage-B layout [m_pad][m_pad + 1], Ad for the
@@ -173,10 +87,7 @@ __global__ __launch_bounds__(64 * (NT > MT ? NT : MT), 4) void schur_wg_nodes(Av
             if (a.decl_count) atomicAdd(a.decl_count, 1);
         }
     };
-#ifdef QPN_STAMPS
-    unsigned long long stamp_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    unsigned long long stamp_last = __builtin_amdgcn_s_memtime();
-#endif
+    STAMP_DECL;
 
     // ---- load: wave v takes row tile v of [H | C~] straight into the MFMA C/D layout --------------------------
     // H(r, c) = Qd[c * n + r] (padded rows: identity), C~(r, k) = Ad[r * m + k] (Ad is m x n column-major)
@@ -528,42 +439,13 @@ __global__ __launch_bounds__(64 * (NT > MT ? NT : MT), 4) void schur_wg_nodes(Av
     __syncthreads();
     STAMP(4);   // W~ hand-over, S product, tile hand-over, Ad staging
     int code = uni(sDecI[0]);
-    // sixteen-way scalar dispatch on a wave-uniform index (0..15; anything else: nothing): leaf k names register k statically
+    // the sixteen register tiles as asm operands of DISPATCH16 (qpn_internal.h)
 #define T_OPS_RW [t0] "+v"(TD(0)), [t1] "+v"(TD(1)), [t2] "+v"(TD(2)), [t3] "+v"(TD(3)), [t4] "+v"(TD(4)), [t5] "+v"(TD(5)),       \
                  [t6] "+v"(TD(6)), [t7] "+v"(TD(7)), [t8] "+v"(TD(8)), [t9] "+v"(TD(9)), [t10] "+v"(TD(10)), [t11] "+v"(TD(11)),   \
                  [t12] "+v"(TD(12)), [t13] "+v"(TD(13)), [t14] "+v"(TD(14)), [t15] "+v"(TD(15))
 #define T_OPS_R [t0] "v"(TD(0)), [t1] "v"(TD(1)), [t2] "v"(TD(2)), [t3] "v"(TD(3)), [t4] "v"(TD(4)), [t5] "v"(TD(5)),             \
                 [t6] "v"(TD(6)), [t7] "v"(TD(7)), [t8] "v"(TD(8)), [t9] "v"(TD(9)), [t10] "v"(TD(10)), [t11] "v"(TD(11)),         \
                 [t12] "v"(TD(12)), [t13] "v"(TD(13)), [t14] "v"(TD(14)), [t15] "v"(TD(15))
-#define DISPATCH16(P, L0, L1, L2, L3, L4, L5, L6, L7, L8, L9, L10, L11, L12, L13, L14, L15)                                        \
-    /* (numeric local labels, all referenced forwards: the compiler may duplicate an asm statement -- loop peeling --, and named  \
-        labels would then be defined twice; P only documents the call site) */                                                     \
-    "s_cmp_gt_u32 %[cs], 7\n\ts_cbranch_scc1 20f\n\t"                                                                             \
-    "s_cmp_gt_u32 %[cs], 3\n\ts_cbranch_scc1 4f\n\t"                                                                              \
-    "s_cmp_gt_u32 %[cs], 1\n\ts_cbranch_scc1 2f\n\t"                                                                              \
-    "s_cmp_eq_u32 %[cs], 0\n\ts_cbranch_scc0 1f\n\t"                                                                              \
-    L0 "\n\ts_branch 30f\n"                                                                                                        \
-    "1:\n\t" L1 "\n\ts_branch 30f\n"                                                                                              \
-    "2:\n\ts_cmp_eq_u32 %[cs], 2\n\ts_cbranch_scc0 3f\n\t" L2 "\n\ts_branch 30f\n"                                              \
-    "3:\n\t" L3 "\n\ts_branch 30f\n"                                                                                              \
-    "4:\n\ts_cmp_gt_u32 %[cs], 5\n\ts_cbranch_scc1 6f\n\t"                                                                       \
-    "s_cmp_eq_u32 %[cs], 4\n\ts_cbranch_scc0 5f\n\t" L4 "\n\ts_branch 30f\n"                                                    \
-    "5:\n\t" L5 "\n\ts_branch 30f\n"                                                                                              \
-    "6:\n\ts_cmp_eq_u32 %[cs], 6\n\ts_cbranch_scc0 7f\n\t" L6 "\n\ts_branch 30f\n"                                              \
-    "7:\n\t" L7 "\n\ts_branch 30f\n"                                                                                              \
-    "20:\n\ts_cmp_gt_u32 %[cs], 15\n\ts_cbranch_scc1 30f\n\t"                                                                    \
-    "s_cmp_gt_u32 %[cs], 11\n\ts_cbranch_scc1 12f\n\t"                                                                            \
-    "s_cmp_gt_u32 %[cs], 9\n\ts_cbranch_scc1 10f\n\t"                                                                             \
-    "s_cmp_eq_u32 %[cs], 8\n\ts_cbranch_scc0 9f\n\t" L8 "\n\ts_branch 30f\n"                                                    \
-    "9:\n\t" L9 "\n\ts_branch 30f\n"                                                                                              \
-    "10:\n\ts_cmp_eq_u32 %[cs], 10\n\ts_cbranch_scc0 11f\n\t" L10 "\n\ts_branch 30f\n"                                         \
-    "11:\n\t" L11 "\n\ts_branch 30f\n"                                                                                            \
-    "12:\n\ts_cmp_gt_u32 %[cs], 13\n\ts_cbranch_scc1 14f\n\t"                                                                    \
-    "s_cmp_eq_u32 %[cs], 12\n\ts_cbranch_scc0 13f\n\t" L12 "\n\ts_branch 30f\n"                                                 \
-    "13:\n\t" L13 "\n\ts_branch 30f\n"                                                                                            \
-    "14:\n\ts_cmp_eq_u32 %[cs], 14\n\ts_cbranch_scc0 15f\n\t" L14 "\n\ts_branch 30f\n"                                         \
-    "15:\n\t" L15 "\n"                                                                                                            \
-    "30:\n\t"
     while (code != CODE_STOP) {
         c = uni(c);
         // ---- the entering column, published by the lanes that hold it: row i goes to [i & 3][i >> 2]
@@ -773,7 +655,6 @@ __global__ __launch_bounds__(64 * (NT > MT ? NT : MT), 4) void schur_wg_nodes(Av
         par ^= 1;
         STAMP(7);   // the exchange
     }
-#undef DISPATCH16
 #undef T_OPS_R
 #undef T_OPS_RW
 #undef FOR_T

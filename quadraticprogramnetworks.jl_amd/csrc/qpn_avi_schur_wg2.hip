@@ -25,90 +25,9 @@
 // launches.  One workgroup per CU (the W~ hand-over alone is up to 128 KB of LDS).
 #include "qpn_internal.h"
 
-#define QINF __builtin_huge_val()
-
 namespace {
 
 constexpr int VLD = 272;                // row stride of the published pivot rows (256 columns; == 16 mod 32)
-typedef double d4 __attribute__((ext_vector_type(4)));
-#define MFMA(a_, b_, c_) __builtin_amdgcn_mfma_f64_16x16x4f64((a_), (b_), (c_), 0, 0, 0)
-#define MFMA_NEGA(a_, b_, c_) __builtin_amdgcn_mfma_f64_16x16x4f64((a_), (b_), (c_), 0, 0, 1)      // D = C - A B (gfx950 NEG bits)
-
-__device__ __forceinline__ void wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-__device__ __forceinline__ double rcp64(double x)      // one Newton step on v_rcp_f64: <= 10 ulp (tools/rcp_probe.hip)
-{
-    double r = __builtin_amdgcn_rcp(x);
-    const double e = fma(-x, r, 1.0);
-    return fma(r, e, r);
-}
-__device__ __forceinline__ double max_abs_nc(double a, double b)
-{
-    double r;
-    asm("v_max_f64 %0, %1, |%2|" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-// min over all 64 lanes of v and the wave-uniform `lim`, returned wave-uniform (see qpn_avi_schur_wg.hip)
-__device__ __forceinline__ double wave_min64_with_limit_f64(double v, double lim)
-{
-    {
-        const double ls = udbl(lim);
-        double r;
-        asm("v_min_f64 %0, %1, %2\n\ts_nop 1" : "=v"(r) : "v"(v), "s"(ls));
-        v = r;
-    }
-    v = min_f64_nc(v, dpp_f64<0xB1>(v));
-    v = min_f64_nc(v, dpp_f64<0x4E>(v));
-    v = min_f64_nc(v, dpp_f64<0x141>(v));
-    v = min_f64_nc(v, dpp_f64<0x140>(v));
-    {
-        int lo = __double2loint(v), hi = __double2hiint(v);
-        lo = __builtin_amdgcn_update_dpp(lo, lo, 0x142, 0xA, 0xF, false);      // rows 1, 3 <- lane 15 of rows 0, 2
-        hi = __builtin_amdgcn_update_dpp(hi, hi, 0x142, 0xA, 0xF, false);
-        v = min_f64_nc(v, __hiloint2double(hi, lo));
-    }
-    {
-        int lo = __double2loint(v), hi = __double2hiint(v);
-        lo = __builtin_amdgcn_update_dpp(lo, lo, 0x143, 0xC, 0xF, false);      // rows 2, 3 <- lane 31
-        hi = __builtin_amdgcn_update_dpp(hi, hi, 0x143, 0xC, 0xF, false);
-        v = min_f64_nc(v, __hiloint2double(hi, lo));
-    }
-    return readlane_f64(v, 63);
-}
-__device__ __forceinline__ int lane_id_fresh()
-{
-    int x = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-    asm volatile("" : "+v"(x));
-    return x;
-}
-// v + (v of lane ^ 16) + (v of lane ^ 32) + (v of lane ^ 48): gfx950's row / half swaps (VALU, no LDS trip)
-__device__ __forceinline__ double xsum_rows(double v)
-{
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    const auto a = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
-    const auto b = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-    const double s = __hiloint2double(b[0], a[0]) + __hiloint2double(b[1], a[1]);
-    lo = __double2loint(s); hi = __double2hiint(s);
-    const auto c = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
-    const auto d = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
-    return __hiloint2double(d[0], c[0]) + __hiloint2double(d[1], c[1]);
-}
-
-#ifdef QPN_STAMPS
-#define STAMP(slot)                                                     \
-    do {                                                                \
-        unsigned long long now__ = __builtin_amdgcn_s_memtime();        \
-        __builtin_amdgcn_s_waitcnt(0xC07F);                             \
-        stamp_acc[slot] += now__ - stamp_last;                          \
-        stamp_last = now__;                                             \
-    } while (0)
-#else
-#define STAMP(slot) do { } while (0)
-#endif
 
 // LDS map (doubles; ~151 KB at n = m = 128: one workgroup per CU).  The big area is, in turn: two Qd panels [2][16][n_pad + 2], the published pivot rows [2][4][VLD], W~
 // for the S product [n_pad][m_pad], the S tiles changing hands [NR][NR][4][64], Ad for the post-check [n][m | 1].
@@ -134,37 +53,6 @@ __host__ __device__ constexpr int wg2_lds_doubles(int n, int m, int pad)
     if (n * (m | 1) > big) big = n * (m | 1);
     return OFF_BIG + big;
 }
-
-// sixteen-way scalar dispatch on a wave-uniform index (0..15; anything else: nothing): leaf k names register k statically
-#define DISPATCH16(P, L0, L1, L2, L3, L4, L5, L6, L7, L8, L9, L10, L11, L12, L13, L14, L15)                                        \
-    /* (numeric local labels, all referenced forwards: the compiler may duplicate an asm statement -- loop peeling --, and named  \
-        labels would then be defined twice; P only documents the call site) */                                                     \
-    "s_cmp_gt_u32 %[cs], 7\n\ts_cbranch_scc1 20f\n\t"                                                                             \
-    "s_cmp_gt_u32 %[cs], 3\n\ts_cbranch_scc1 4f\n\t"                                                                              \
-    "s_cmp_gt_u32 %[cs], 1\n\ts_cbranch_scc1 2f\n\t"                                                                              \
-    "s_cmp_eq_u32 %[cs], 0\n\ts_cbranch_scc0 1f\n\t"                                                                              \
-    L0 "\n\ts_branch 30f\n"                                                                                                        \
-    "1:\n\t" L1 "\n\ts_branch 30f\n"                                                                                              \
-    "2:\n\ts_cmp_eq_u32 %[cs], 2\n\ts_cbranch_scc0 3f\n\t" L2 "\n\ts_branch 30f\n"                                              \
-    "3:\n\t" L3 "\n\ts_branch 30f\n"                                                                                              \
-    "4:\n\ts_cmp_gt_u32 %[cs], 5\n\ts_cbranch_scc1 6f\n\t"                                                                       \
-    "s_cmp_eq_u32 %[cs], 4\n\ts_cbranch_scc0 5f\n\t" L4 "\n\ts_branch 30f\n"                                                    \
-    "5:\n\t" L5 "\n\ts_branch 30f\n"                                                                                              \
-    "6:\n\ts_cmp_eq_u32 %[cs], 6\n\ts_cbranch_scc0 7f\n\t" L6 "\n\ts_branch 30f\n"                                              \
-    "7:\n\t" L7 "\n\ts_branch 30f\n"                                                                                              \
-    "20:\n\ts_cmp_gt_u32 %[cs], 15\n\ts_cbranch_scc1 30f\n\t"                                                                    \
-    "s_cmp_gt_u32 %[cs], 11\n\ts_cbranch_scc1 12f\n\t"                                                                            \
-    "s_cmp_gt_u32 %[cs], 9\n\ts_cbranch_scc1 10f\n\t"                                                                             \
-    "s_cmp_eq_u32 %[cs], 8\n\ts_cbranch_scc0 9f\n\t" L8 "\n\ts_branch 30f\n"                                                    \
-    "9:\n\t" L9 "\n\ts_branch 30f\n"                                                                                              \
-    "10:\n\ts_cmp_eq_u32 %[cs], 10\n\ts_cbranch_scc0 11f\n\t" L10 "\n\ts_branch 30f\n"                                         \
-    "11:\n\t" L11 "\n\ts_branch 30f\n"                                                                                            \
-    "12:\n\ts_cmp_gt_u32 %[cs], 13\n\ts_cbranch_scc1 14f\n\t"                                                                    \
-    "s_cmp_eq_u32 %[cs], 12\n\ts_cbranch_scc0 13f\n\t" L12 "\n\ts_branch 30f\n"                                                 \
-    "13:\n\t" L13 "\n\ts_branch 30f\n"                                                                                            \
-    "14:\n\ts_cmp_eq_u32 %[cs], 14\n\ts_cbranch_scc0 15f\n\t" L14 "\n\ts_branch 30f\n"                                         \
-    "15:\n\t" L15 "\n"                                                                                                            \
-    "30:\n\t"
 
 #define DISPATCH16_X(...) DISPATCH16(__VA_ARGS__)       /* (arguments expanded first: LEAVES16 below yields sixteen of them) */
 
@@ -213,10 +101,7 @@ __global__ __launch_bounds__(128 * NR, (NR >= 7) ? 4 : 3) void schur_wg2_nodes(A
         }
     };
 
-#ifdef QPN_STAMPS
-    unsigned long long stamp_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    unsigned long long stamp_last = __builtin_amdgcn_s_memtime();
-#endif
+    STAMP_DECL;
     // ---- load ---------------------------------------------------------------------------------------------------------
     // H(r, c) = Qd[c * n + r] (padded rows: identity), C~(r, k) = Ad[r * m + k] (Ad is m x n column-major)
     const d4 z4 = {0.0, 0.0, 0.0, 0.0};
@@ -1127,18 +1012,13 @@ hipError_t qpn_launch_schur_wg2_nodes(const AviBatchArgs &a, hipStream_t stream)
     const int big = n > m ? n : m;
     const int NR = big <= 80 ? 5 : big <= 96 ? 6 : big <= 112 ? 7 : 8;
     const size_t lds = (size_t)wg2_lds_doubles(n, m, 16 * NR) * sizeof(double);
-    static QpnPerDeviceOnce once;
-    const int dev = once.device();
-    if (!once.done[dev]) {
-        // (dynamic LDS beyond 64 KB needs the attribute, once per device and kernel; the largest class needs 151 KB)
-        const int mx = 156 * 1024;
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&schur_wg2_nodes<5>), hipFuncAttributeMaxDynamicSharedMemorySize, mx);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(&schur_wg2_nodes<6>), hipFuncAttributeMaxDynamicSharedMemorySize, mx);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(&schur_wg2_nodes<7>), hipFuncAttributeMaxDynamicSharedMemorySize, mx);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(&schur_wg2_nodes<8>), hipFuncAttributeMaxDynamicSharedMemorySize, mx);
-        if (e != hipSuccess) return e;
-        once.done[dev] = true;
-    }
+    // (dynamic LDS beyond 64 KB needs the attribute, once per device and kernel; the largest class needs 151 KB)
+    static QpnLdsLimits lds_limits;
+    constexpr int mx = 156 * 1024;
+    if (const hipError_t e = lds_limits.raise({{schur_wg2_nodes<5>, mx}, {schur_wg2_nodes<6>, mx},
+                                               {schur_wg2_nodes<7>, mx}, {schur_wg2_nodes<8>, mx}});
+        e != hipSuccess)
+        return e;
     const dim3 grid((unsigned)batch);
     switch (NR) {
     case 5: hipLaunchKernelGGL((schur_wg2_nodes<5>), grid, dim3(640), lds, stream, a); break;

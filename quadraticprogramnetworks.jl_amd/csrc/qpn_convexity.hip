@@ -396,14 +396,9 @@ hipError_t qpn_launch_convexity(int32_t batch, int32_t n, int32_t m, const doubl
     if (cls == CVX_WAVE) {
         const size_t slice = slice_bytes(n, m, 64);
         const size_t lds = slice * CVX_WAVES;
-        static QpnPerDeviceOnce attr_once;        // the largest wave-class request is 160 KiB: above the 64 KiB default
-        const int dev = attr_once.device();
-        if (!attr_once.done[dev]) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(convexity_wave_kernel),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)(CVX_WAVE_SLICE_MAX * CVX_WAVES));
-            if (e != hipSuccess) return e;
-            attr_once.done[dev] = true;
-        }
+        static QpnLdsLimits lds_limits;        // the largest wave-class request is 160 KiB: above the 64 KiB default
+        if (const hipError_t e = lds_limits.raise({{convexity_wave_kernel, (int)(CVX_WAVE_SLICE_MAX * CVX_WAVES)}}); e != hipSuccess)
+            return e;
         const unsigned grid = (unsigned)((batch + CVX_WAVES - 1) / CVX_WAVES);
         hipLaunchKernelGGL(convexity_wave_kernel, dim3(grid), dim3(64 * CVX_WAVES), lds, s, batch, n, m, Qd, Ad, eq, tol, convex,
                            min_eig, null_dim, slice);
@@ -411,14 +406,8 @@ hipError_t qpn_launch_convexity(int32_t batch, int32_t n, int32_t m, const doubl
     }
     if (cls == CVX_GROUP_LDS) {
         const size_t slice = slice_bytes(n, m, CVX_GROUP);
-        static QpnPerDeviceOnce attr_once;
-        const int dev = attr_once.device();
-        if (!attr_once.done[dev]) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(convexity_group_kernel<true>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)CVX_GROUP_SLICE_MAX);
-            if (e != hipSuccess) return e;
-            attr_once.done[dev] = true;
-        }
+        static QpnLdsLimits lds_limits;
+        if (const hipError_t e = lds_limits.raise({{convexity_group_kernel<true>, (int)CVX_GROUP_SLICE_MAX}}); e != hipSuccess) return e;
         hipLaunchKernelGGL(convexity_group_kernel<true>, dim3((unsigned)batch), dim3(CVX_GROUP), slice, s, 0, batch, n, m, Qd, Ad,
                            eq, tol, convex, min_eig, null_dim, static_cast<unsigned char *>(nullptr), slice);
         return hipGetLastError();

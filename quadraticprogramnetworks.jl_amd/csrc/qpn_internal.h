@@ -2,6 +2,7 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <initializer_list>
 #include <stddef.h>
 #include <stdint.h>
 
@@ -71,11 +72,30 @@ struct AviBatchArgs {
     int32_t *sched_key;
 };
 
-// Function attributes (dynamic LDS limits) are per device: a launcher sets them once per device it is used on.
-// (Two host threads racing here both set the same value.)
-struct QpnPerDeviceOnce {
+// Function attributes (dynamic LDS limits) are per device: a launcher raises its kernels' limits once per device it is used on,
+// through a static QpnLdsLimits:  static QpnLdsLimits lds_limits;  ... lds_limits.raise({{kernel_a, bytes_a}, {kernel_b, bytes_b}})
+// sets the attribute kernel by kernel in that order and returns the first error; the device counts as done only once every
+// call has succeeded.  (Two host threads racing here both set the same value.)
+struct QpnLdsLimit {
+    const void *kernel;
+    int bytes;
+    template <typename K> QpnLdsLimit(K *k, int b) : kernel(reinterpret_cast<const void *>(k)), bytes(b) {}
+};
+struct QpnLdsLimits {
     bool done[64] = {};
-    int device() const { int d = 0; (void)hipGetDevice(&d); return d & 63; }
+    hipError_t raise(std::initializer_list<QpnLdsLimit> limits)
+    {
+        int d = 0;
+        (void)hipGetDevice(&d);
+        d &= 63;
+        if (done[d]) return hipSuccess;
+        for (const QpnLdsLimit &k : limits) {
+            const hipError_t e = hipFuncSetAttribute(k.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, k.bytes);
+            if (e != hipSuccess) return e;
+        }
+        done[d] = true;
+        return hipSuccess;
+    }
 };
 
 
@@ -200,6 +220,33 @@ size_t qpn_convexity_workspace_bytes(int32_t batch, int32_t n, int32_t m);
 
 // ---- wave64 helpers (CDNA4: one wavefront = 64 lanes) --------------------------------
 #ifdef __HIPCC__
+constexpr int WAVE = 64;
+#define QINF __builtin_huge_val()
+
+typedef double d4 __attribute__((ext_vector_type(4)));
+#define MFMA(a_, b_, c_) __builtin_amdgcn_mfma_f64_16x16x4f64((a_), (b_), (c_), 0, 0, 0)
+// D = C - A B: on gfx950 the BLGP field of the fp64 MFMAs holds NEG modifiers (bit 0: A, bit 1: B, bit 2: C;
+// tools/mfma_neg_probe.hip), so an operand's sign costs no VALU instruction
+#define MFMA_NEGA(a_, b_, c_) __builtin_amdgcn_mfma_f64_16x16x4f64((a_), (b_), (c_), 0, 0, 1)
+
+// diagnostic builds (-DQPN_STAMPS): a kernel declares its clocks with STAMP_DECL; STAMP(slot) adds the clocks since the previous
+// stamp to stamp_acc[slot]; where the sums go is each kernel's own business
+#ifdef QPN_STAMPS
+#define STAMP_DECL                                                      \
+    unsigned long long stamp_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};         \
+    unsigned long long stamp_last = __builtin_amdgcn_s_memtime()
+#define STAMP(slot)                                                     \
+    do {                                                                \
+        unsigned long long now__ = __builtin_amdgcn_s_memtime();        \
+        __builtin_amdgcn_s_waitcnt(0xC07F);                             \
+        stamp_acc[slot] += now__ - stamp_last;                          \
+        stamp_last = now__;                                             \
+    } while (0)
+#else
+#define STAMP_DECL (void)0      // (not an empty do-while: even that changes the code generated around it)
+#define STAMP(slot) do { } while (0)
+#endif
+
 // (A5+A6) reduced single-node KKT assembly of item b by ONE wavefront (src/avi.jl:205-251 + :305-377):
 // M = [[Qd, -Ad'],[Ad, 0]] column-major, q = [qd + R w; B w], bounds [free; l..u], kinds [STD; GAVI].
 // Column j of M (length N = n+m) is written by lanes striding the rows: coalesced.
@@ -372,6 +419,34 @@ __device__ __forceinline__ double wave_min32_with_limit_f64(double v, double lim
     }
     return readlane_f64(v, 31);
 }
+// min over all 64 lanes of v and the wave-uniform `lim`, returned wave-uniform: four DPP row stages, row_bcast:15 into rows
+// 1 and 3, row_bcast:31 into rows 2 and 3, lane 63 read out (callers feed no NaNs; non-candidates carry +inf)
+__device__ __forceinline__ double wave_min64_with_limit_f64(double v, double lim)
+{
+    {
+        const double ls = udbl(lim);
+        double r;
+        asm("v_min_f64 %0, %1, %2\n\ts_nop 1" : "=v"(r) : "v"(v), "s"(ls));
+        v = r;
+    }
+    v = min_f64_nc(v, dpp_f64<0xB1>(v));
+    v = min_f64_nc(v, dpp_f64<0x4E>(v));
+    v = min_f64_nc(v, dpp_f64<0x141>(v));
+    v = min_f64_nc(v, dpp_f64<0x140>(v));
+    {
+        int lo = __double2loint(v), hi = __double2hiint(v);
+        lo = __builtin_amdgcn_update_dpp(lo, lo, 0x142, 0xA, 0xF, false);      // rows 1, 3 <- lane 15 of rows 0, 2
+        hi = __builtin_amdgcn_update_dpp(hi, hi, 0x142, 0xA, 0xF, false);
+        v = min_f64_nc(v, __hiloint2double(hi, lo));
+    }
+    {
+        int lo = __double2loint(v), hi = __double2hiint(v);
+        lo = __builtin_amdgcn_update_dpp(lo, lo, 0x143, 0xC, 0xF, false);      // rows 2, 3 <- lane 31
+        hi = __builtin_amdgcn_update_dpp(hi, hi, 0x143, 0xC, 0xF, false);
+        v = min_f64_nc(v, __hiloint2double(hi, lo));
+    }
+    return readlane_f64(v, 63);
+}
 __device__ __forceinline__ double wave_sum_f64(double v)
 {
 #pragma unroll
@@ -403,4 +478,98 @@ __device__ __forceinline__ double udbl(double v)
     int hi = __builtin_amdgcn_readfirstlane(__double2hiint(v));
     return __hiloint2double(hi, lo);
 }
+// Ordering among the lanes of ONE wavefront: LDS operations of a wave execute in issue order, so ordering between a lane's
+// store and another lane's load needs no s_barrier and no drain of the memory counters -- only that the compiler keeps the
+// program order of the LDS accesses (it must: they may alias) and does not move them across this point.
+__device__ __forceinline__ void wave_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+// 1/x (callers guarantee |x| is well away from 0 on every lane whose result is used).  v_rcp_f64 is good to
+// 4.6e-8; one Newton step brings it to <= 2.3e-15 relative (10 ulp), two give the correctly rounded quotient
+// (tools/rcp_probe.hip).  The pivoting arithmetic uses one step: its results are certified by the post-check
+// on the original blocks, and 1e-15 is far inside the 1e-9 parity bar.
+__device__ __forceinline__ double rcp64(double x)
+{
+    double r = __builtin_amdgcn_rcp(x);
+    const double e = fma(-x, r, 1.0);
+    return fma(r, e, r);
+}
+// max(a, |b|) in ONE instruction (fmax(a, fabs(b)) costs three: the compiler canonicalises both operands first; the
+// callers feed no NaNs that matter: a NaN entry fails the pivot test and the item goes to the general kernel)
+__device__ __forceinline__ double max_abs_nc(double a, double b)
+{
+    double r;
+    asm("v_max_f64 %0, %1, |%2|" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+__device__ __forceinline__ double min_abs_nc(double a, double b)      // min(a, |b|)
+{
+    double r;
+    asm("v_min_f64 %0, %1, |%2|" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+// v[l] + v[l ^ 32] in every lane (gfx950: v_permlane32_swap exchanges the upper half of one register with the lower half of another)
+__device__ __forceinline__ double sum_halves(double v)
+{
+    const int lo = __double2loint(v), hi = __double2hiint(v);
+    const auto c = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
+    const auto d = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
+    return __hiloint2double(d[0], c[0]) + __hiloint2double(d[1], c[1]);
+}
+// v + (v of lane ^ 16) + (v of lane ^ 32) + (v of lane ^ 48): gfx950's row / half swaps (VALU, no LDS trip, no address registers)
+__device__ __forceinline__ double xsum_rows(double v)
+{
+    int lo = __double2loint(v), hi = __double2hiint(v);
+    const auto a = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
+    const auto b = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
+    const double s = __hiloint2double(b[0], a[0]) + __hiloint2double(b[1], a[1]);
+    lo = __double2loint(s); hi = __double2hiint(s);
+    const auto c = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
+    const auto d = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
+    return __hiloint2double(d[0], c[0]) + __hiloint2double(d[1], c[1]);
+}
+// lane id recomputed on the spot (v_mbcnt on the full EXEC mask; opaque, so the compiler does not keep the copy from the
+// start of the kernel alive -- and spill it -- across the phases): every phase derives its own lane coordinates
+__device__ __forceinline__ int lane_id_fresh()
+{
+    int x = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    asm volatile("" : "+v"(x));
+    return x;
+}
+__device__ __forceinline__ int pad16(int v) { return (v + 15) & ~15; }
+
+// sixteen-way scalar dispatch on a wave-uniform index %[cs] (0..15; anything else: nothing) inside an asm statement: leaf k
+// names register k statically
+#define DISPATCH16(P, L0, L1, L2, L3, L4, L5, L6, L7, L8, L9, L10, L11, L12, L13, L14, L15)                                        \
+    /* (numeric local labels, all referenced forwards: the compiler may duplicate an asm statement -- loop peeling --, and named  \
+        labels would then be defined twice; P only documents the call site) */                                                     \
+    "s_cmp_gt_u32 %[cs], 7\n\ts_cbranch_scc1 20f\n\t"                                                                             \
+    "s_cmp_gt_u32 %[cs], 3\n\ts_cbranch_scc1 4f\n\t"                                                                              \
+    "s_cmp_gt_u32 %[cs], 1\n\ts_cbranch_scc1 2f\n\t"                                                                              \
+    "s_cmp_eq_u32 %[cs], 0\n\ts_cbranch_scc0 1f\n\t"                                                                              \
+    L0 "\n\ts_branch 30f\n"                                                                                                        \
+    "1:\n\t" L1 "\n\ts_branch 30f\n"                                                                                              \
+    "2:\n\ts_cmp_eq_u32 %[cs], 2\n\ts_cbranch_scc0 3f\n\t" L2 "\n\ts_branch 30f\n"                                              \
+    "3:\n\t" L3 "\n\ts_branch 30f\n"                                                                                              \
+    "4:\n\ts_cmp_gt_u32 %[cs], 5\n\ts_cbranch_scc1 6f\n\t"                                                                       \
+    "s_cmp_eq_u32 %[cs], 4\n\ts_cbranch_scc0 5f\n\t" L4 "\n\ts_branch 30f\n"                                                    \
+    "5:\n\t" L5 "\n\ts_branch 30f\n"                                                                                              \
+    "6:\n\ts_cmp_eq_u32 %[cs], 6\n\ts_cbranch_scc0 7f\n\t" L6 "\n\ts_branch 30f\n"                                              \
+    "7:\n\t" L7 "\n\ts_branch 30f\n"                                                                                              \
+    "20:\n\ts_cmp_gt_u32 %[cs], 15\n\ts_cbranch_scc1 30f\n\t"                                                                    \
+    "s_cmp_gt_u32 %[cs], 11\n\ts_cbranch_scc1 12f\n\t"                                                                            \
+    "s_cmp_gt_u32 %[cs], 9\n\ts_cbranch_scc1 10f\n\t"                                                                             \
+    "s_cmp_eq_u32 %[cs], 8\n\ts_cbranch_scc0 9f\n\t" L8 "\n\ts_branch 30f\n"                                                    \
+    "9:\n\t" L9 "\n\ts_branch 30f\n"                                                                                              \
+    "10:\n\ts_cmp_eq_u32 %[cs], 10\n\ts_cbranch_scc0 11f\n\t" L10 "\n\ts_branch 30f\n"                                         \
+    "11:\n\t" L11 "\n\ts_branch 30f\n"                                                                                            \
+    "12:\n\ts_cmp_gt_u32 %[cs], 13\n\ts_cbranch_scc1 14f\n\t"                                                                    \
+    "s_cmp_eq_u32 %[cs], 12\n\ts_cbranch_scc0 13f\n\t" L12 "\n\ts_branch 30f\n"                                                 \
+    "13:\n\t" L13 "\n\ts_branch 30f\n"                                                                                            \
+    "14:\n\ts_cmp_eq_u32 %[cs], 14\n\ts_cbranch_scc0 15f\n\t" L14 "\n\ts_branch 30f\n"                                         \
+    "15:\n\t" L15 "\n"                                                                                                            \
+    "30:\n\t"
 #endif

@@ -6,11 +6,7 @@
 // (lane i <-> row i of a column-major block), no LDS staging needed.
 #include "qpn_internal.h"
 
-#define QINF __builtin_huge_val()
-
 namespace {
-
-constexpr int WAVE = 64;
 
 // ---- (A3) check_avi_solution: one wave per item, lanes stride the rows -------------------
 __global__ __launch_bounds__(256) void check_avi_kernel(int32_t batch, int32_t N, const double *M,

@@ -17,8 +17,6 @@
 
 namespace {
 
-constexpr double QINF = __builtin_huge_val();
-
 __global__ __launch_bounds__(256) void recipes_batch_kernel(int32_t nodes, int32_t N, const uint8_t *masks, const long long *offsets,
                                                             long long total, uint8_t *K, int32_t *node_of)
 {

@@ -13,12 +13,6 @@
 constexpr int TC_TLD = 17, TC_TSZ = 16 * TC_TLD;
 __host__ __device__ constexpr int tc_tiles(int T) { return T * (T + 1) / 2; }
 __device__ __forceinline__ int tc_toff(int i, int j) { return (i * (i + 1) / 2 + j) * TC_TSZ; }
-__device__ __forceinline__ void tc_wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // Every thread of the workgroup calls it (block barriers inside).  *fail (LDS, 0 on entry) is set when a pivot is not above
 // piv_rel x max(1, first diagonal of its tile); returns false then (uniform), the tiles are left half-factored.
@@ -101,7 +95,7 @@ __device__ __forceinline__ bool tc_factor(double *tiles, int T, int *fail, doubl
         // longest item of a step; it now runs next to the update instead of after it)
         if (wave == 0) {
             update_tile(j, j + 1, j + 1);
-            tc_wave_sync();
+            wave_sync();
             diag_tile(j + 1);
         } else {
             const int nt = T - 1 - j, np_ = nt * (nt + 1) / 2;
@@ -129,9 +123,9 @@ __device__ __forceinline__ void tc_solve(const double *tiles, double *rhs, int T
 #pragma unroll
             for (int c = 0; c < 16; ++c) yv = fma(Li[lane * TC_TLD + c], rhs[16 * j + c], yv);
         }
-        tc_wave_sync();
+        wave_sync();
         if (lane < 16) rhs[16 * j + lane] = yv;
-        tc_wave_sync();
+        wave_sync();
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             const int row = lane + 64 * h;
@@ -143,7 +137,7 @@ __device__ __forceinline__ void tc_solve(const double *tiles, double *rhs, int T
                 rhs[row] = acc;
             }
         }
-        tc_wave_sync();
+        wave_sync();
     }
     for (int j = T - 1; j >= 0; --j) {
         // x_j = Linv_jj' r_j (lane <-> column c of tile column j: x_c = sum_{r >= c} Linv(r, c) r_r) ...
@@ -153,9 +147,9 @@ __device__ __forceinline__ void tc_solve(const double *tiles, double *rhs, int T
 #pragma unroll
             for (int r2 = 0; r2 < 16; ++r2) xv = fma(Li[r2 * TC_TLD + lane], rhs[16 * j + r2], xv);
         }
-        tc_wave_sync();
+        wave_sync();
         if (lane < 16) rhs[16 * j + lane] = xv;
-        tc_wave_sync();
+        wave_sync();
         // ... then every earlier position gives up its share: r_p -= sum_r L(16 j + r, p) x_r  (two positions per lane)
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
@@ -168,6 +162,6 @@ __device__ __forceinline__ void tc_solve(const double *tiles, double *rhs, int T
                 rhs[pcol] = acc;
             }
         }
-        tc_wave_sync();
+        wave_sync();
     }
 }

@@ -17,11 +17,8 @@
 #include "qpn_tile_chol.h"
 #include <type_traits>
 
-#define QINF __builtin_huge_val()
-
 namespace {
 
-constexpr int WAVE = 64;
 // Leading dimension of the two LDS matrices (odd: column and row sweeps are both conflict-light).  Two size
 // classes: n, m <= 32 -> 33 (17 KB of LDS per node, 9 nodes resident per CU); n, m <= 64 -> 65 (67 KB, 2 per CU).
 
@@ -226,21 +223,7 @@ __global__ __launch_bounds__(WAVE) void verify_stage1(VerifyArgs a)
 // from its ascending chains by summation order only.
 typedef double vd4 __attribute__((ext_vector_type(4)));
 typedef double vd2 __attribute__((ext_vector_type(2)));
-#define VMFMA(a_, b_, c_) __builtin_amdgcn_mfma_f64_16x16x4f64((a_), (b_), (c_), 0, 0, 0)
 
-__device__ __forceinline__ void vwave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-__device__ __forceinline__ double vsum_halves(double v)      // v[l] + v[l ^ 32] in every lane
-{
-    const int lo = __double2loint(v), hi = __double2hiint(v);
-    const auto c = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
-    const auto d = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
-    return __hiloint2double(d[0], c[0]) + __hiloint2double(d[1], c[1]);
-}
 __device__ __forceinline__ double vadd2(double a, double b) { return a + b; }
 __device__ __forceinline__ double wave_sum32_f64(double v)   // sum over lanes 0..31 (lanes 32..63 ignored), wave-uniform
 {
@@ -298,7 +281,7 @@ __global__ __launch_bounds__(WAVE, 4) void verify_node32(VerifyArgs a)
         for (int k = 0; k < 4; ++k) { accr = fma(rv[k], wv[k], accr); accb = fma(bv[k], wv[k], accb); }
     }
     if (l < 32) sx[(l & 1) * 16 + (l >> 1)] = xv;
-    vwave_sync();
+    wave_sync();
     if (!FULL) {
 #pragma unroll
         for (int t = 0; t < 16; ++t) {
@@ -318,8 +301,8 @@ __global__ __launch_bounds__(WAVE, 4) void verify_node32(VerifyArgs a)
             a0 = fma(va[2 * j], xx[0], a0); a1 = fma(va[2 * j + 1], xx[1], a1);
         }
     }
-    const double qt = vsum_halves(q0 + q1) + qdv;             // q~ of row r5, in both halves
-    const double ax = vsum_halves(a0 + a1);                   // (Ad x + B w) of row r5, in both halves
+    const double qt = sum_halves(q0 + q1) + qdv;             // q~ of row r5, in both halves
+    const double ax = sum_halves(a0 + a1);                   // (Ad x + B w) of row r5, in both halves
     const bool isrow = FULL || r5 < m;
 
     // :86  feasibility, tol 1e-3 (Slice membership, src/sets.jl:851-854)
@@ -354,18 +337,18 @@ __global__ __launch_bounds__(WAVE, 4) void verify_node32(VerifyArgs a)
     double rn0 = 0.0, rn1 = 0.0;
 #pragma unroll
     for (int t = 0; t < 16; t += 2) { rn0 = fma(va[t], va[t], rn0); rn1 = fma(va[t + 1], va[t + 1], rn1); }
-    const double rn2 = vsum_halves(rn0 + rn1);
+    const double rn2 = sum_halves(rn0 + rn1);
     const double dinv = rn2 > 0.0 ? 1.0 / sqrt(rn2) : 0.0;
     const double rsc = mysgr * dinv;
     // ---- A_bar' (signed, scaled active rows, compacted) and q~ to LDS
-    vwave_sync();                                             // (the x reads are done)
+    wave_sync();                                             // (the x reads are done)
     if (mycol >= 0) {
 #pragma unroll
         for (int t = 0; t < 16; ++t) sM[mycol * V32_LDA + 2 * t + ch] = rsc * va[t];
         if (ch == 0) sd[mycol] = dinv;
     }
     if (l < 32) sx[(l & 1) * 16 + (l >> 1)] = (FULL || l < n) ? qt : 0.0;
-    vwave_sync();
+    wave_sync();
     // (Ad q~)_r for every row (the fallback's -Ad q~ too), then the right-hand side A_bar' q~ by column
     double g0 = 0.0, g1 = 0.0;
     {
@@ -376,9 +359,9 @@ __global__ __launch_bounds__(WAVE, 4) void verify_node32(VerifyArgs a)
             g0 = fma(va[2 * j], qq[0], g0); g1 = fma(va[2 * j + 1], qq[1], g1);
         }
     }
-    const double aq = vsum_halves(g0 + g1);                   // (Ad q~)_r5
+    const double aq = sum_halves(g0 + g1);                   // (Ad q~)_r5
     if (mycol >= 0 && ch == 0) sv[mycol] = rsc * aq;
-    vwave_sync();
+    wave_sync();
     const double rhs = (l < k) ? sv[l] : 0.0;                 // A_bar' q~ by column (lane c < k <-> column c)
     const double dcol = (l < k) ? sd[l] : 0.0;                // this column's scale
     const int lc = l & 15, lq = l >> 4;
@@ -406,11 +389,11 @@ __global__ __launch_bounds__(WAVE, 4) void verify_node32(VerifyArgs a)
                 x1[s] = (16 + lc < k && (FULL || t < n)) ? v1 : 0.0;
             }
         }
-        vwave_sync();                                         // operands are in; the region changes hands
+        wave_sync();                                         // operands are in; the region changes hands
         {
             vd4 g00 = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
-            for (int s = 0; s < 8; ++s) g00 = VMFMA(x0[s], x0[s], g00);
+            for (int s = 0; s < 8; ++s) g00 = MFMA(x0[s], x0[s], g00);
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const int i = lq + 4 * g, j = lc;
@@ -419,7 +402,7 @@ __global__ __launch_bounds__(WAVE, 4) void verify_node32(VerifyArgs a)
             if (two) {
                 vd4 g01 = {0.0, 0.0, 0.0, 0.0}, g11 = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
-                for (int s = 0; s < 8; ++s) { g01 = VMFMA(x0[s], x1[s], g01); g11 = VMFMA(x1[s], x1[s], g11); }
+                for (int s = 0; s < 8; ++s) { g01 = MFMA(x0[s], x1[s], g01); g11 = MFMA(x1[s], x1[s], g11); }
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
                     const int i = lq + 4 * g, j = 16 + lc;
@@ -428,7 +411,7 @@ __global__ __launch_bounds__(WAVE, 4) void verify_node32(VerifyArgs a)
                 }
             }
         }
-        vwave_sync();
+        wave_sync();
         // lane i < k <-> row i.  Column ord[s] of the region becomes column s of the factor (the freed column), as in verify_stage1.
         bool done = !inP;
         int mystep = -1;
@@ -464,7 +447,7 @@ __global__ __launch_bounds__(WAVE, 4) void verify_node32(VerifyArgs a)
             if (l == pv) { done = true; mystep = s; bvec = ws; myinv = inv; }
             if (l == s) ordv = pv;
             rank++;
-            vwave_sync();
+            wave_sync();
         }
         // back substitution L' y = w, column-oriented: y of the last pivot first; a lane pivoted at step a < s' takes
         // L(ord[s'], a) -- row ord[s'] of its own (freed) column -- times y_{ord[s']} off its right-hand side
@@ -476,7 +459,7 @@ __global__ __launch_bounds__(WAVE, 4) void verify_node32(VerifyArgs a)
             if (l == pvs) y = ys;
         }
         y_out = y; pivoted = mystep >= 0;
-        vwave_sync();                                         // (the factor's reads are done)
+        wave_sync();                                         // (the factor's reads are done)
     };
     auto stage_active_rows = [&]() {
         if (mycol >= 0) {
@@ -487,7 +470,7 @@ __global__ __launch_bounds__(WAVE, 4) void verify_node32(VerifyArgs a)
     // r = A_bar y - q~ by lane t < n (y handed over through sv), on the staged active rows; returns this lane's entry
     auto residual_entry = [&](double y) -> double {
         if (l < k) sv[l] = y;
-        vwave_sync();
+        wave_sync();
         double s0 = (l < 32) ? -qt : 0.0;
         const int tcol = (l < 32 && (FULL || l < n)) ? l : 0;
         for (int c0 = 0; c0 < k; c0 += 4) {
@@ -546,7 +529,7 @@ __global__ __launch_bounds__(WAVE, 4) void verify_node32(VerifyArgs a)
                 if (leave) { inP = false; ycur = 0.0; }
                 if (++iters > cap) { failed = true; break; }
                 stage_active_rows();
-                vwave_sync();
+                wave_sync();
                 bool pv2;
                 lsq_on(inP, sl, pv2);
                 if (inP && !pv2) { inP = false; ycur = 0.0; }                       // dependent on the others: out, at zero
@@ -556,7 +539,7 @@ __global__ __launch_bounds__(WAVE, 4) void verify_node32(VerifyArgs a)
             stage_active_rows();
             rt = residual_entry(ycur);
             if (l < 32) sx[l] = rt;                           // (sx is free: q~ lives in registers by now)
-            vwave_sync();
+            wave_sync();
             double wgr = 0.0;
             if (mine) {
                 const vd2 *rowc = reinterpret_cast<const vd2 *>(sM + l * V32_LDA);
@@ -576,7 +559,7 @@ __global__ __launch_bounds__(WAVE, 4) void verify_node32(VerifyArgs a)
             const int enter = wave_first(cand && wgr == wmax);
             if (l == enter) inP = true;
             if (++iters > cap) { failed = true; break; }
-            vwave_sync();
+            wave_sync();
             bool pv2;
             lsq_on(inP, sl, pv2);
             if (inP && !pv2) { inP = false; if (l == enter) blocked = true; }
@@ -584,7 +567,7 @@ __global__ __launch_bounds__(WAVE, 4) void verify_node32(VerifyArgs a)
             if (!(s_enter > 0.0)) {                           // numerically it should be: leave it out for good and carry on
                 if (l == enter) { inP = false; blocked = true; }
                 stage_active_rows();
-                vwave_sync();
+                wave_sync();
                 lsq_on(inP, sl, pv2);
                 if (inP && !pv2) inP = false;
             }
@@ -598,7 +581,7 @@ __global__ __launch_bounds__(WAVE, 4) void verify_node32(VerifyArgs a)
         const double res = wave_sum32_f64(rt * rt);
         const bool ok = sqrt(res) <= 1e-4;
         if (l < k) sv[l] = ycur;
-        vwave_sync();
+        wave_sync();
         if (l < m) lam[l] = (mycol >= 0) ? rsc * sv[mycol] : 0.0;
         if (l == 0) { a.solution[b] = ok ? 1 : 0; a.path[b] = ok ? 3 : 4; }
     }
@@ -649,7 +632,7 @@ __global__ __launch_bounds__(WAVE, 2) void verify_node64(VerifyArgs a)
 #pragma unroll
         for (int k = 0; k < 4; ++k) { qt = fma(rv[k], wv[k], qt); ax = fma(bv[k], wv[k], ax); }
     }
-    vwave_sync();
+    wave_sync();
     // ---- pass 1: q~ (:58-60) and ax (:84), 16 columns of Qd and of Ad in flight per panel
     // (the rows' squared lengths come out of the same values: a second pass over Ad for them and for Ad q~ is not needed -- the
     //  right-hand side is only wanted on the active rows, which pass 2 reads anyway)
@@ -698,9 +681,9 @@ __global__ __launch_bounds__(WAVE, 2) void verify_node64(VerifyArgs a)
     else if (cls == 2) mycol = np + __popcll(bn & below);
     else if (cls == 3) mycol = np + nn + __popcll(bb & below);
     const double mysgr = (cls == 2) ? -1.0 : 1.0;
-    vwave_sync();                                             // (the x reads are done)
+    wave_sync();                                             // (the x reads are done)
     sx[l] = isx ? qt : 0.0;
-    vwave_sync();
+    wave_sync();
     // ---- pass 2: the active rows of Ad again (L2 / Infinity Cache): (Ad q~)_r, and the signed, equilibrated rows to LDS
     double aq = 0.0;
     const double dinv = rn2 > 0.0 ? 1.0 / sqrt(rn2) : 0.0;
@@ -725,7 +708,7 @@ __global__ __launch_bounds__(WAVE, 2) void verify_node64(VerifyArgs a)
         }
     }
     if (mycol >= 0) { sv[mycol] = rsc * aq; sd[mycol] = dinv; }
-    vwave_sync();
+    wave_sync();
     const double rhs = (l < k) ? sv[l] : 0.0;
     const double dcol = (l < k) ? sd[l] : 0.0;
     const int lc = l & 15, lq = l >> 4;
@@ -749,8 +732,8 @@ __global__ __launch_bounds__(WAVE, 2) void verify_node64(VerifyArgs a)
                 }
 #pragma unroll
                 for (int u_ = 0; u_ < 4; ++u_) {
-                    g00 = VMFMA(x0[u_], x0[u_], g00);
-                    if (two) { g01 = VMFMA(x0[u_], x1[u_], g01); g11 = VMFMA(x1[u_], x1[u_], g11); }
+                    g00 = MFMA(x0[u_], x0[u_], g00);
+                    if (two) { g01 = MFMA(x0[u_], x1[u_], g01); g11 = MFMA(x1[u_], x1[u_], g11); }
                 }
             }
 #pragma unroll
@@ -764,7 +747,7 @@ __global__ __launch_bounds__(WAVE, 2) void verify_node64(VerifyArgs a)
                 }
             }
         }
-        vwave_sync();
+        wave_sync();
         bool done = !inP;
         int mystep = -1;
         double diag = inP ? sG[l * V32_LDG + l] : 0.0;
@@ -799,7 +782,7 @@ __global__ __launch_bounds__(WAVE, 2) void verify_node64(VerifyArgs a)
             if (l == pv) { done = true; mystep = s; bvec = ws; myinv = inv; }
             if (l == s) ordv = pv;
             rank++;
-            vwave_sync();
+            wave_sync();
         }
         double y = 0.0;
         for (int s = rank - 1; s >= 0; --s) {
@@ -809,12 +792,12 @@ __global__ __launch_bounds__(WAVE, 2) void verify_node64(VerifyArgs a)
             if (l == pvs) y = ys;
         }
         y_out = y; pivoted = mystep >= 0;
-        vwave_sync();
+        wave_sync();
     };
     // r = A_bar y - q~, lane t < n
     auto residual_entry = [&](double y) -> double {
         if (l < k) sv[l] = y;
-        vwave_sync();
+        wave_sync();
         double s0 = -qt;
         const int tcol = isx ? l : 0;
         for (int c0 = 0; c0 < k; c0 += 4) {
@@ -869,9 +852,9 @@ __global__ __launch_bounds__(WAVE, 2) void verify_node64(VerifyArgs a)
             }
             if (failed) break;
             rt = residual_entry(ycur);
-            vwave_sync();
+            wave_sync();
             sx[l] = rt;                                       // (q~ lives in registers by now)
-            vwave_sync();
+            wave_sync();
             double wgr = 0.0;
             if (mine) {
                 const vd2 *rowc = reinterpret_cast<const vd2 *>(sM + l * V64_LDA);
@@ -909,7 +892,7 @@ __global__ __launch_bounds__(WAVE, 2) void verify_node64(VerifyArgs a)
         const double res = wave_sum_f64(rt * rt);
         const bool ok = sqrt(res) <= 1e-4;
         if (l < k) sv[l] = ycur;
-        vwave_sync();
+        wave_sync();
         if (isrow) lam[l] = (mycol >= 0) ? rsc * sv[mycol] : 0.0;
         if (l == 0) { a.solution[b] = ok ? 1 : 0; a.path[b] = ok ? 3 : 4; }
     }
@@ -1182,7 +1165,7 @@ __global__ __launch_bounds__(WTPB) __attribute__((amdgpu_waves_per_eu(2, 2))) vo
             for (int s4 = 0; s4 < wp / 4; ++s4) {
                 const double av = ci < k ? cur[(4 * s4 + lq) * ldp + ri] : 0.0;
                 const double bv = cj < k ? cur[(4 * s4 + lq) * ldp + rj] : 0.0;
-                acc[q] = VMFMA(av, bv, acc[q]);
+                acc[q] = MFMA(av, bv, acc[q]);
             }
         }
         if (pn + 1 < npanel) store_panel(nxt);
@@ -1696,13 +1679,8 @@ hipError_t qpn_launch_verify_nodes(int32_t batch, int32_t n, int32_t m, int32_t 
         // wide nodes: verify_wide_node (up to 128 active rows, every path inside the workgroup), then round 1's kernels over what it
         // flagged -2 (their bounded-LSQ fallback is a large box-AVI, N = m, on the large-item kernel)
         if (m >= 1 && gws) {
-            static QpnPerDeviceOnce attr_once;
-            const int dv = attr_once.device();
-            if (!attr_once.done[dv]) {
-                hipError_t e0 = hipFuncSetAttribute(reinterpret_cast<const void *>(verify_wide_node), hipFuncAttributeMaxDynamicSharedMemorySize, 72 * 1024);
-                if (e0 != hipSuccess) return e0;
-                attr_once.done[dv] = true;
-            }
+            static QpnLdsLimits lds_limits;
+            if (const hipError_t e = lds_limits.raise({{verify_wide_node, 72 * 1024}}); e != hipSuccess) return e;
             const int wp = m <= 256 ? 16 : 8;
             // the panels, and room for a k x k factor (k <= min(m, 128)) up to what two workgroups per CU allow
             size_t dyn = (size_t)2 * wp * (size_t)(m | 1) * sizeof(double);
@@ -1739,13 +1717,8 @@ hipError_t qpn_launch_verify_nodes(int32_t batch, int32_t n, int32_t m, int32_t 
         if (gws) {
             // the nodes it flagged (more than 32 active rows: a handful in thousands) go to the workgroup kernel first -- ~35 us for
             // such a node instead of ~130 us on the one-wavefront kernels of round 1, which bound the whole call's tail
-            static QpnPerDeviceOnce attr_once;
-            const int dv = attr_once.device();
-            if (!attr_once.done[dv]) {
-                hipError_t e0 = hipFuncSetAttribute(reinterpret_cast<const void *>(verify_wide_node), hipFuncAttributeMaxDynamicSharedMemorySize, 72 * 1024);
-                if (e0 != hipSuccess) return e0;
-                attr_once.done[dv] = true;
-            }
+            static QpnLdsLimits lds_limits;
+            if (const hipError_t e = lds_limits.raise({{verify_wide_node, 72 * 1024}}); e != hipSuccess) return e;
             const size_t mp16 = (size_t)((m + 15) & ~15);
             int *ctr = reinterpret_cast<int *>(gws + (size_t)QPN_VERIFY_MID_SLOTS * 2 * mp16 * mp16);
             hipError_t e0 = hipMemsetAsync(ctr, 0, 4, stream);
