@@ -66,20 +66,69 @@ int fail_arg(qpn_ctx *ctx, const char *msg)
 
 int order_reserve(qpn_ctx *ctx, int32_t count);
 
-// carve `bytes` (256-B aligned) out of the ctx workspace; grows it when needed
-struct Carver {
+// The buffers of one entry point call.  Device mode (QPN_MEM_DEVICE): the caller's pointers go to the kernels as they are.
+// Host mode (QPN_MEM_HOST): each buffer gets a slot (256-B aligned) of the ctx workspace, begin() uploads the inputs in the
+// order they were registered, finish() downloads the outputs in that order and waits for them.  Scratch and library-owned
+// host data get a slot in both modes.  A slot of 0 bytes is a null pointer.  begin() writes the registered pointer variables
+// and finish() reads them: they have to live until the call returns.
+struct Stage {
     qpn_ctx *ctx;
+    const char *who;
+    bool host, bad_mem;
     size_t need = 0;
-    std::vector<std::pair<void **, size_t>> slots;
-    explicit Carver(qpn_ctx *c) : ctx(c) {}
-    void add(void **p, size_t bytes)
+    struct Slot { void **dev; size_t off; };
+    struct Copy { void **dev; void *host; size_t bytes, hpitch = 0, dpitch = 0, rows = 0; };   // rows > 0: 2-D, rows x bytes
+    std::vector<Slot> slots;
+    std::vector<Copy> up, down;
+
+    Stage(qpn_ctx *c, int mem, const char *w)
+        : ctx(c), who(w), host(mem == QPN_MEM_HOST), bad_mem(mem != QPN_MEM_HOST && mem != QPN_MEM_DEVICE) {}
+    int check() const { return bad_mem ? fail_arg(ctx, (std::string(who) + ": bad mem kind").c_str()) : QPN_OK; }
+
+    template <class T> void carve(T *&dev, size_t bytes)
     {
-        size_t off = need;
+        dev = nullptr;
+        if (!bytes) return;
+        slots.push_back({(void **)&dev, need});
         need += (bytes + 255) & ~(size_t)255;
-        slots.emplace_back(p, off);
     }
-    int commit()
+    // an input; `pad` extra bytes keep the pointer valid when the array is empty or absent
+    template <class T> void in(T *&dev, const void *src, size_t bytes, size_t pad = 0)
     {
+        if (!host) { dev = (T *)src; return; }
+        carve(dev, src || pad ? bytes + pad : 0);
+        if (src && bytes) up.push_back({(void **)&dev, (void *)src, bytes});
+    }
+    // an output (host mode carves it even when the caller does not want it)
+    template <class T> void out(T *&dev, void *dst, size_t bytes, size_t pad = 0)
+    {
+        if (!host) { dev = (T *)dst; return; }
+        carve(dev, bytes + pad);
+        if (dst && bytes) down.push_back({(void **)&dev, dst, bytes});
+    }
+    template <class T> void inout(T *&dev, T *p, size_t bytes, bool upload)
+    {
+        if (!host) { dev = p; return; }
+        carve(dev, bytes);
+        if (p && upload) up.push_back({(void **)&dev, p, bytes});
+        if (p) down.push_back({(void **)&dev, p, bytes});
+    }
+    // host mode: `rows` blocks of `bytes` from a staged buffer (pitch dpitch) to the caller's (pitch hpitch)
+    template <class T> void out2d(T *const &dev, size_t dpitch, void *dst, size_t hpitch, size_t bytes, size_t rows)
+    {
+        if (host) down.push_back({(void **)&dev, dst, bytes, hpitch, dpitch, rows});
+    }
+    template <class T> void scratch(T *&dev, size_t bytes) { carve(dev, bytes); }
+    // host data the kernels read in either mode (index maps, offsets)
+    template <class T> void lib_in(T *&dev, const void *src, size_t bytes)
+    {
+        carve(dev, bytes);
+        if (bytes) up.push_back({(void **)&dev, (void *)src, bytes});
+    }
+
+    int begin()
+    {
+        if (int rc = check()) return rc;
         if (need > ctx->ws_bytes) {
             HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
             if (ctx->ws) HIPCHK(ctx, hipFree(ctx->ws));
@@ -88,10 +137,45 @@ struct Carver {
             HIPCHK(ctx, hipMalloc(&ctx->ws, want));
             ctx->ws_bytes = want;
         }
-        for (auto &s : slots) *s.first = static_cast<char *>(ctx->ws) + s.second;
+        for (auto &s : slots) *s.dev = static_cast<char *>(ctx->ws) + s.off;
+        for (auto &c : up) HIPCHK(ctx, hipMemcpyAsync(*c.dev, c.host, c.bytes, hipMemcpyHostToDevice, ctx->stream));
+        return QPN_OK;
+    }
+    int finish()
+    {
+        if (!host) return QPN_OK;
+        for (auto &c : down) {
+            if (c.rows) HIPCHK(ctx, hipMemcpy2DAsync(c.host, c.hpitch, *c.dev, c.dpitch, c.bytes, c.rows, hipMemcpyDeviceToHost, ctx->stream));
+            else HIPCHK(ctx, hipMemcpyAsync(c.host, *c.dev, c.bytes, hipMemcpyDeviceToHost, ctx->stream));
+        }
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
         return QPN_OK;
     }
 };
+
+struct NodeSizes { size_t Q, R, q, A, B, lu, w; };
+NodeSizes node_sizes(int32_t batch, int32_t n, int32_t m, int32_t p, int64_t stride_w)
+{
+    NodeSizes s;
+    s.Q = (size_t)batch * n * n * 8; s.R = (size_t)batch * n * p * 8; s.q = (size_t)batch * n * 8;
+    s.A = (size_t)batch * m * n * 8; s.B = (size_t)batch * m * p * 8; s.lu = (size_t)batch * m * 8;
+    // (w goes up only when p > 0: a stride alone names no data)
+    s.w = p ? (stride_w ? (size_t)(batch - 1) * stride_w + p : (size_t)p) * 8 : 0;
+    return s;
+}
+
+struct NodeDev {                // device views of one call's node records, parameters and outputs
+    const double *Q, *R, *q, *A, *B, *l, *u, *w;
+    double *z; int32_t *st; double *res; int32_t *pv; uint8_t *act;
+};
+
+// the seven record arrays (the padded ones stay valid when empty)
+void stage_records(Stage &st, NodeDev &d, const NodeSizes &sz, const double *Qd, const double *R, const double *qd,
+                   const double *Ad, const double *B, const double *l, const double *u)
+{
+    st.in(d.Q, Qd, sz.Q); st.in(d.R, R, sz.R, 8); st.in(d.q, qd, sz.q); st.in(d.A, Ad, sz.A, 8);
+    st.in(d.B, B, sz.B, 8); st.in(d.l, l, sz.lu, 8); st.in(d.u, u, sz.lu, 8);
+}
 
 } // namespace
 
@@ -247,58 +331,25 @@ int qpn_solve_avi_batch(qpn_ctx *ctx, int32_t batch, int32_t N, const double *M,
     a.check_tol = o.check_tol; a.piv_tol = o.piv_tol; a.feas_tol = o.feas_tol; a.comp_tol = o.comp_tol;
     a.max_pivots = o.max_pivots;
     a.flags = o.flags & 0xFFFF;           // (the upper bits are internal: QPN_AVI_IFLAG_*)
-
-    if (mem == QPN_MEM_DEVICE) {
-        a.M = M; a.q = q; a.l = l; a.u = u; a.kind = kind; a.z = z; a.status = status;
-        a.resid = resid; a.pivots = pivots; a.active = active;
 #ifdef QPN_STAMPS
-        a.stamps = g_stamps;
+    if (mem == QPN_MEM_DEVICE) a.stamps = g_stamps;
 #endif
-        if (big) {
-            double *wsp;
-            Carver cvb(ctx);
-            cvb.add((void **)&wsp, qpn_avi_big_workspace_bytes(batch, N));
-            int rcb = cvb.commit();
-            if (rcb != QPN_OK) return rcb;
-            HIPCHK(ctx, qpn_launch_avi_solve_big(a, wsp, ctx->stream));
-        } else {
-            HIPCHK(ctx, qpn_launch_avi_solve(a, ctx->stream));
-        }
-        return QPN_OK;
-    }
-    if (mem != QPN_MEM_HOST) return fail_arg(ctx, "qpn_solve_avi_batch: bad mem kind");
 
     const size_t bN = (size_t)batch * N;
     const size_t mBytes = sizeof(double) * (strideM ? (size_t)(batch - 1) * strideM + (size_t)N * N : (size_t)N * N);
     const size_t kBytes = kind ? (stride_kind ? (size_t)(batch - 1) * stride_kind + N : (size_t)N) : 0;
-    double *dM, *dq, *dl, *du, *dz, *dres; int32_t *dst, *dpv; uint8_t *dk = nullptr, *dact;
-    Carver cv(ctx);
-    cv.add((void **)&dM, mBytes); cv.add((void **)&dq, bN * 8); cv.add((void **)&dl, bN * 8);
-    cv.add((void **)&du, bN * 8); cv.add((void **)&dz, bN * 8); cv.add((void **)&dres, (size_t)batch * 8);
-    cv.add((void **)&dst, (size_t)batch * 4); cv.add((void **)&dpv, (size_t)batch * 4);
-    cv.add((void **)&dact, bN); cv.add((void **)&dk, kBytes ? kBytes : 1);
+    Stage st(ctx, mem, "qpn_solve_avi_batch");
+    st.in(a.M, M, mBytes); st.in(a.q, q, bN * 8); st.in(a.l, l, bN * 8); st.in(a.u, u, bN * 8);
+    st.inout(a.z, z, bN * 8, true); st.in(a.kind, kind, kBytes);
+    st.out(a.status, status, (size_t)batch * 4); st.out(a.resid, resid, (size_t)batch * 8);
+    st.out(a.pivots, pivots, (size_t)batch * 4); st.out(a.active, active, bN);
     double *wsb = nullptr;
-    if (big) cv.add((void **)&wsb, qpn_avi_big_workspace_bytes(batch, N));
-    int rc = cv.commit();
+    if (big) st.scratch(wsb, qpn_avi_big_workspace_bytes(batch, N));
+    int rc = st.begin();
     if (rc != QPN_OK) return rc;
-    hipStream_t s = ctx->stream;
-    HIPCHK(ctx, hipMemcpyAsync(dM, M, mBytes, hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, hipMemcpyAsync(dq, q, bN * 8, hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, hipMemcpyAsync(dl, l, bN * 8, hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, hipMemcpyAsync(du, u, bN * 8, hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, hipMemcpyAsync(dz, z, bN * 8, hipMemcpyHostToDevice, s));
-    if (kind) HIPCHK(ctx, hipMemcpyAsync(dk, kind, kBytes, hipMemcpyHostToDevice, s));
-    a.M = dM; a.q = dq; a.l = dl; a.u = du; a.kind = kind ? dk : nullptr; a.z = dz; a.status = dst;
-    a.resid = dres; a.pivots = dpv; a.active = dact;
-    if (big) HIPCHK(ctx, qpn_launch_avi_solve_big(a, wsb, s));
-    else HIPCHK(ctx, qpn_launch_avi_solve(a, s));
-    HIPCHK(ctx, hipMemcpyAsync(z, dz, bN * 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(ctx, hipMemcpyAsync(status, dst, (size_t)batch * 4, hipMemcpyDeviceToHost, s));
-    if (resid) HIPCHK(ctx, hipMemcpyAsync(resid, dres, (size_t)batch * 8, hipMemcpyDeviceToHost, s));
-    if (pivots) HIPCHK(ctx, hipMemcpyAsync(pivots, dpv, (size_t)batch * 4, hipMemcpyDeviceToHost, s));
-    if (active) HIPCHK(ctx, hipMemcpyAsync(active, dact, bN, hipMemcpyDeviceToHost, s));
-    HIPCHK(ctx, hipStreamSynchronize(s));
-    return QPN_OK;
+    if (big) HIPCHK(ctx, qpn_launch_avi_solve_big(a, wsb, ctx->stream));
+    else HIPCHK(ctx, qpn_launch_avi_solve(a, ctx->stream));
+    return st.finish();
 }
 
 int qpn_solve_mcp_csc(qpn_ctx *ctx, int32_t N, const int32_t *colptr, const int32_t *rowval,
@@ -333,34 +384,18 @@ int qpn_check_avi_batch(qpn_ctx *ctx, int32_t batch, int32_t N, const double *M,
     if (batch == 0) return QPN_OK;
     if (!M || !q || !l || !u || !z || !degree) return fail_arg(ctx, "qpn_check_avi_batch: null pointer");
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (mem == QPN_MEM_DEVICE) {
-        HIPCHK(ctx, qpn_launch_check_avi(batch, N, M, strideM, q, l, u, kind, kind ? stride_kind : 0, z,
-                                         tol, degree, r, ctx->stream));
-        return QPN_OK;
-    }
     const size_t bN = (size_t)batch * N;
     const size_t mBytes = sizeof(double) * (strideM ? (size_t)(batch - 1) * strideM + (size_t)N * N : (size_t)N * N);
     const size_t kBytes = kind ? (stride_kind ? (size_t)(batch - 1) * stride_kind + N : (size_t)N) : 0;
-    double *dM, *dq, *dl, *du, *dz, *dr; int32_t *dd; uint8_t *dk;
-    Carver cv(ctx);
-    cv.add((void **)&dM, mBytes); cv.add((void **)&dq, bN * 8); cv.add((void **)&dl, bN * 8);
-    cv.add((void **)&du, bN * 8); cv.add((void **)&dz, bN * 8); cv.add((void **)&dr, bN * 8);
-    cv.add((void **)&dd, (size_t)batch * 4); cv.add((void **)&dk, kBytes ? kBytes : 1);
-    int rc = cv.commit();
+    const double *dM, *dq, *dl, *du, *dz; const uint8_t *dk; int32_t *dd; double *dr;
+    Stage st(ctx, mem, "qpn_check_avi_batch");
+    st.in(dM, M, mBytes); st.in(dq, q, bN * 8); st.in(dl, l, bN * 8); st.in(du, u, bN * 8); st.in(dz, z, bN * 8);
+    st.in(dk, kind, kBytes);
+    st.out(dd, degree, (size_t)batch * 4); st.out(dr, r, bN * 8);
+    int rc = st.begin();
     if (rc != QPN_OK) return rc;
-    hipStream_t s = ctx->stream;
-    HIPCHK(ctx, hipMemcpyAsync(dM, M, mBytes, hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, hipMemcpyAsync(dq, q, bN * 8, hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, hipMemcpyAsync(dl, l, bN * 8, hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, hipMemcpyAsync(du, u, bN * 8, hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, hipMemcpyAsync(dz, z, bN * 8, hipMemcpyHostToDevice, s));
-    if (kind) HIPCHK(ctx, hipMemcpyAsync(dk, kind, kBytes, hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, qpn_launch_check_avi(batch, N, dM, strideM, dq, dl, du, kind ? dk : nullptr,
-                                     kind ? stride_kind : 0, dz, tol, dd, dr, s));
-    HIPCHK(ctx, hipMemcpyAsync(degree, dd, (size_t)batch * 4, hipMemcpyDeviceToHost, s));
-    if (r) HIPCHK(ctx, hipMemcpyAsync(r, dr, bN * 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(ctx, hipStreamSynchronize(s));
-    return QPN_OK;
+    HIPCHK(ctx, qpn_launch_check_avi(batch, N, dM, strideM, dq, dl, du, dk, kind ? stride_kind : 0, dz, tol, dd, dr, ctx->stream));
+    return st.finish();
 }
 
 int qpn_comp_indices(qpn_ctx *ctx, int64_t count, const double *zv, const double *rv,
@@ -372,39 +407,15 @@ int qpn_comp_indices(qpn_ctx *ctx, int64_t count, const double *zv, const double
     if (count == 0) return QPN_OK;
     if (!zv || !rv || !l || !u || !mask) return fail_arg(ctx, "qpn_comp_indices: null pointer");
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (mem == QPN_MEM_DEVICE) {
-        HIPCHK(ctx, qpn_launch_comp_indices(count, zv, rv, l, u, tol, shift, mask, ctx->stream));
-        return QPN_OK;
-    }
-    double *dz, *dr, *dl, *du; uint8_t *dm;
-    Carver cv(ctx);
     const size_t nb = (size_t)count * 8;
-    cv.add((void **)&dz, nb); cv.add((void **)&dr, nb); cv.add((void **)&dl, nb); cv.add((void **)&du, nb);
-    cv.add((void **)&dm, (size_t)count);
-    int rc = cv.commit();
+    const double *dz, *dr, *dl, *du; uint8_t *dm;
+    Stage st(ctx, mem, "qpn_comp_indices");
+    st.in(dz, zv, nb); st.in(dr, rv, nb); st.in(dl, l, nb); st.in(du, u, nb); st.out(dm, mask, (size_t)count);
+    int rc = st.begin();
     if (rc != QPN_OK) return rc;
-    hipStream_t s = ctx->stream;
-    HIPCHK(ctx, hipMemcpyAsync(dz, zv, nb, hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, hipMemcpyAsync(dr, rv, nb, hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, hipMemcpyAsync(dl, l, nb, hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, hipMemcpyAsync(du, u, nb, hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, qpn_launch_comp_indices(count, dz, dr, dl, du, tol, shift, dm, s));
-    HIPCHK(ctx, hipMemcpyAsync(mask, dm, (size_t)count, hipMemcpyDeviceToHost, s));
-    HIPCHK(ctx, hipStreamSynchronize(s));
-    return QPN_OK;
+    HIPCHK(ctx, qpn_launch_comp_indices(count, dz, dr, dl, du, tol, shift, dm, ctx->stream));
+    return st.finish();
 }
-
-namespace {
-struct NodeSizes { size_t Q, R, q, A, B, lu, w; };
-NodeSizes node_sizes(int32_t batch, int32_t n, int32_t m, int32_t p, int64_t stride_w)
-{
-    NodeSizes s;
-    s.Q = (size_t)batch * n * n * 8; s.R = (size_t)batch * n * p * 8; s.q = (size_t)batch * n * 8;
-    s.A = (size_t)batch * m * n * 8; s.B = (size_t)batch * m * p * 8; s.lu = (size_t)batch * m * 8;
-    s.w = (stride_w ? (size_t)(batch - 1) * stride_w + p : (size_t)p) * 8;
-    return s;
-}
-} // namespace
 
 int qpn_assemble_nodes(qpn_ctx *ctx, int32_t batch, int32_t n, int32_t m, int32_t p,
                        const double *Qd, const double *R, const double *qd, const double *Ad,
@@ -420,43 +431,21 @@ int qpn_assemble_nodes(qpn_ctx *ctx, int32_t batch, int32_t n, int32_t m, int32_
         return fail_arg(ctx, "qpn_assemble_nodes: null pointer");
     if (stride_w != 0 && stride_w < p) return fail_arg(ctx, "qpn_assemble_nodes: stride_w < p");
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (mem == QPN_MEM_DEVICE) {
-        HIPCHK(ctx, qpn_launch_assemble_nodes(batch, n, m, p, Qd, R, qd, Ad, B, l, u, w, stride_w, Mout,
-                                              qout, lout, uout, kind_out, ctx->stream));
-        return QPN_OK;
-    }
     const NodeSizes sz = node_sizes(batch, n, m, p, stride_w);
     const int N = n + m;
     const size_t bN = (size_t)batch * N;
-    double *dQ, *dR, *dq, *dA, *dB, *dl, *du, *dw, *dM, *dqo, *dlo, *duo; uint8_t *dk;
-    Carver cv(ctx);
-    cv.add((void **)&dQ, sz.Q); cv.add((void **)&dR, sz.R + 8); cv.add((void **)&dq, sz.q);
-    cv.add((void **)&dA, sz.A + 8); cv.add((void **)&dB, sz.B + 8); cv.add((void **)&dl, sz.lu + 8);
-    cv.add((void **)&du, sz.lu + 8); cv.add((void **)&dw, sz.w + 8);
-    cv.add((void **)&dM, bN * N * 8); cv.add((void **)&dqo, bN * 8); cv.add((void **)&dlo, bN * 8);
-    cv.add((void **)&duo, bN * 8); cv.add((void **)&dk, bN);
-    int rc = cv.commit();
+    NodeDev d{};
+    double *dM, *dqo, *dlo, *duo; uint8_t *dk;
+    Stage st(ctx, mem, "qpn_assemble_nodes");
+    stage_records(st, d, sz, Qd, R, qd, Ad, B, l, u);
+    st.in(d.w, w, sz.w, 8);
+    st.out(dM, Mout, bN * N * 8); st.out(dqo, qout, bN * 8); st.out(dlo, lout, bN * 8); st.out(duo, uout, bN * 8);
+    st.out(dk, kind_out, bN);
+    int rc = st.begin();
     if (rc != QPN_OK) return rc;
-    hipStream_t s = ctx->stream;
-    HIPCHK(ctx, hipMemcpyAsync(dQ, Qd, sz.Q, hipMemcpyHostToDevice, s));
-    if (sz.R) HIPCHK(ctx, hipMemcpyAsync(dR, R, sz.R, hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, hipMemcpyAsync(dq, qd, sz.q, hipMemcpyHostToDevice, s));
-    if (sz.A) HIPCHK(ctx, hipMemcpyAsync(dA, Ad, sz.A, hipMemcpyHostToDevice, s));
-    if (sz.B) HIPCHK(ctx, hipMemcpyAsync(dB, B, sz.B, hipMemcpyHostToDevice, s));
-    if (sz.lu) {
-        HIPCHK(ctx, hipMemcpyAsync(dl, l, sz.lu, hipMemcpyHostToDevice, s));
-        HIPCHK(ctx, hipMemcpyAsync(du, u, sz.lu, hipMemcpyHostToDevice, s));
-    }
-    if (p > 0) HIPCHK(ctx, hipMemcpyAsync(dw, w, sz.w, hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, qpn_launch_assemble_nodes(batch, n, m, p, dQ, dR, dq, dA, dB, dl, du, dw, stride_w, dM,
-                                          dqo, dlo, duo, dk, s));
-    HIPCHK(ctx, hipMemcpyAsync(Mout, dM, bN * N * 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(ctx, hipMemcpyAsync(qout, dqo, bN * 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(ctx, hipMemcpyAsync(lout, dlo, bN * 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(ctx, hipMemcpyAsync(uout, duo, bN * 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(ctx, hipMemcpyAsync(kind_out, dk, bN, hipMemcpyDeviceToHost, s));
-    HIPCHK(ctx, hipStreamSynchronize(s));
-    return QPN_OK;
+    HIPCHK(ctx, qpn_launch_assemble_nodes(batch, n, m, p, d.Q, d.R, d.q, d.A, d.B, d.l, d.u, d.w, stride_w, dM, dqo, dlo, duo, dk,
+                                          ctx->stream));
+    return st.finish();
 }
 
 // ---- (F1) local pieces ------------------------------------------------------------------------------------------
@@ -465,11 +454,12 @@ int qpn_recipes_from_masks(qpn_ctx *ctx, int32_t N, const uint8_t *mask, int64_t
 {
     if (!ctx) return QPN_ERR_ARG;
     if (N <= 0 || !mask || first < 0 || count < 0 || (count > 0 && !K)) return fail_arg(ctx, "qpn_recipes_from_masks: bad argument");
-    if (mem != QPN_MEM_HOST && mem != QPN_MEM_DEVICE) return fail_arg(ctx, "qpn_recipes_from_masks: bad mem kind");
+    Stage st(ctx, mem, "qpn_recipes_from_masks");
+    if (int rc = st.check()) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     std::vector<uint8_t> hm((size_t)N);
-    if (mem == QPN_MEM_HOST) memcpy(hm.data(), mask, (size_t)N);
+    if (st.host) memcpy(hm.data(), mask, (size_t)N);
     else { HIPCHK(ctx, hipMemcpyAsync(hm.data(), mask, (size_t)N, hipMemcpyDeviceToHost, s)); HIPCHK(ctx, hipStreamSynchronize(s)); }
     int64_t tot = 1;
     for (int i = 0; i < N; ++i) {
@@ -479,20 +469,12 @@ int qpn_recipes_from_masks(qpn_ctx *ctx, int32_t N, const uint8_t *mask, int64_t
     if (total) *total = tot;
     if (count == 0) return QPN_OK;
     if (first >= tot || (int64_t)count > tot - first) return fail_arg(ctx, "qpn_recipes_from_masks: first + count beyond the number of recipes");
-    if (mem == QPN_MEM_DEVICE) {
-        HIPCHK(ctx, qpn_launch_recipes(N, mask, first, count, K, s));
-        return QPN_OK;
-    }
-    uint8_t *dm, *dK;
-    Carver cv(ctx);
-    cv.add((void **)&dm, (size_t)N); cv.add((void **)&dK, (size_t)count * N);
-    int rc = cv.commit();
+    const uint8_t *dm; uint8_t *dK;
+    st.in(dm, mask, (size_t)N); st.out(dK, K, (size_t)count * N);
+    int rc = st.begin();
     if (rc != QPN_OK) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(dm, mask, (size_t)N, hipMemcpyHostToDevice, s));
     HIPCHK(ctx, qpn_launch_recipes(N, dm, first, count, dK, s));
-    HIPCHK(ctx, hipMemcpyAsync(K, dK, (size_t)count * N, hipMemcpyDeviceToHost, s));
-    HIPCHK(ctx, hipStreamSynchronize(s));
-    return QPN_OK;
+    return st.finish();
 }
 
 int qpn_recipes_batch(qpn_ctx *ctx, int32_t nodes, int32_t N, const uint8_t *masks, const int64_t *offsets, uint8_t *K,
@@ -500,8 +482,9 @@ int qpn_recipes_batch(qpn_ctx *ctx, int32_t nodes, int32_t N, const uint8_t *mas
 {
     if (!ctx) return QPN_ERR_ARG;
     if (nodes <= 0 || N <= 0 || !masks || !offsets) return fail_arg(ctx, "qpn_recipes_batch: bad argument");
-    if (mem != QPN_MEM_HOST && mem != QPN_MEM_DEVICE) return fail_arg(ctx, "qpn_recipes_batch: bad mem kind");
-    if (offsets[0] != 0) return fail_arg(ctx, "qpn_recipes_batch: offsets[0] must be 0");
+    Stage st(ctx, mem, "qpn_recipes_batch");
+    if (int rc = st.check()) return rc;
+    if (offsets[0] != 0)return fail_arg(ctx, "qpn_recipes_batch: offsets[0] must be 0");
     for (int b = 0; b < nodes; ++b)
         if (offsets[b + 1] < offsets[b]) return fail_arg(ctx, "qpn_recipes_batch: offsets must not decrease");
     const int64_t total = offsets[nodes];
@@ -512,31 +495,21 @@ int qpn_recipes_batch(qpn_ctx *ctx, int32_t nodes, int32_t N, const uint8_t *mas
     hipStream_t s = ctx->stream;
     // a node may ask for at most the number of recipes its masks have (host masks are checked here; device masks are the
     // caller's: a count beyond the product wraps around inside the product, it cannot leave the arrays)
-    if (mem == QPN_MEM_HOST)
+    if (st.host)
         for (int b = 0; b < nodes; ++b) {
             int64_t tot = 1;
             for (int i = 0; i < N; ++i) { const int r = __builtin_popcount(masks[(size_t)b * N + i]); if (r > 1) tot = (tot > INT64_MAX / r) ? INT64_MAX : tot * r; }
             if (offsets[b + 1] - offsets[b] > tot) return fail_arg(ctx, "qpn_recipes_batch: a node asks for more recipes than its masks have");
         }
-    long long *doff; uint8_t *dm = nullptr, *dK = nullptr; int32_t *dno = nullptr;
-    Carver cv(ctx);
-    cv.add((void **)&doff, (size_t)(nodes + 1) * 8);
-    if (mem == QPN_MEM_HOST) { cv.add((void **)&dm, (size_t)nodes * N); cv.add((void **)&dK, (size_t)total * N); cv.add((void **)&dno, (size_t)total * 4); }
-    int rc = cv.commit();
+    const long long *doff; const uint8_t *dm; uint8_t *dK; int32_t *dno;
+    st.lib_in(doff, offsets, (size_t)(nodes + 1) * 8);
+    st.in(dm, masks, (size_t)nodes * N); st.out(dK, K, (size_t)total * N); st.out(dno, node_of, (size_t)total * 4);
+    int rc = st.begin();
     if (rc != QPN_OK) return rc;
-    // (the offsets go through a synchronous copy: the host array is the caller's and may be pageable)
-    HIPCHK(ctx, hipMemcpyAsync(doff, offsets, (size_t)(nodes + 1) * 8, hipMemcpyHostToDevice, s));
+    // (the offsets are the caller's host array, which may be pageable: the copy must be done before the call returns)
     HIPCHK(ctx, hipStreamSynchronize(s));
-    if (mem == QPN_MEM_DEVICE) {
-        HIPCHK(ctx, qpn_launch_recipes_batch(nodes, N, masks, doff, total, K, node_of, s));
-        return QPN_OK;
-    }
-    HIPCHK(ctx, hipMemcpyAsync(dm, masks, (size_t)nodes * N, hipMemcpyHostToDevice, s));
     HIPCHK(ctx, qpn_launch_recipes_batch(nodes, N, dm, doff, total, dK, dno, s));
-    HIPCHK(ctx, hipMemcpyAsync(K, dK, (size_t)total * N, hipMemcpyDeviceToHost, s));
-    HIPCHK(ctx, hipMemcpyAsync(node_of, dno, (size_t)total * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(ctx, hipStreamSynchronize(s));
-    return QPN_OK;
+    return st.finish();
 }
 
 int qpn_reduced_pieces(qpn_ctx *ctx, int32_t pieces, int32_t nodes, int32_t n, int32_t m, int32_t p, const double *Qd,
@@ -551,58 +524,31 @@ int qpn_reduced_pieces(qpn_ctx *ctx, int32_t pieces, int32_t nodes, int32_t n, i
     if (!Qd || !qd || (m > 0 && (!Ad || !l || !u)) || (p > 0 && (!R || (m > 0 && !B))) || !K || !Ar || !lr || !ur || !rows || !flags)
         return fail_arg(ctx, "qpn_reduced_pieces: null pointer");
     if (!node_of && nodes < pieces) return fail_arg(ctx, "qpn_reduced_pieces: fewer record sets than pieces and no node_of");
-    if (mem != QPN_MEM_HOST && mem != QPN_MEM_DEVICE) return fail_arg(ctx, "qpn_reduced_pieces: bad mem kind");
+    Stage st(ctx, mem, "qpn_reduced_pieces");
+    if (int rc = st.check()) return rc;
     if (!(tol >= 0.0)) return fail_arg(ctx, "qpn_reduced_pieces: bad tolerance");
     if (qpn_reduce_pieces_lds(n, m, p) > 60 * 1024) { ctx->last_error = "qpn_reduced_pieces: too many parameters for one workgroup's LDS"; return QPN_ERR_SIZE; }
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     const int N = n + m;
     const size_t rws = 2 * (size_t)N, cols = (size_t)N + p, cap = (size_t)n + 2 * (size_t)m, oc = (size_t)n + p;
-    const NodeSizes sz = node_sizes(nodes, n, m, p, 0);
-    if (mem == QPN_MEM_HOST && node_of)
+    if (st.host && node_of)
         for (int t = 0; t < pieces; ++t)
             if (node_of[t] < 0 || node_of[t] >= nodes) return fail_arg(ctx, "qpn_reduced_pieces: node_of outside 0..nodes-1");
-    double *dAp, *dlp, *dup; uint8_t *dkeep;
-    double *dQ = nullptr, *dR = nullptr, *dq = nullptr, *dA = nullptr, *dB = nullptr, *dl = nullptr, *du = nullptr, *dAr = nullptr, *dlr = nullptr,
-           *dur = nullptr;
-    int32_t *dno = nullptr, *drows = nullptr, *dflags = nullptr; uint8_t *dK = nullptr;
-    Carver cv(ctx);
-    cv.add((void **)&dAp, (size_t)pieces * rws * cols * 8); cv.add((void **)&dlp, (size_t)pieces * rws * 8);
-    cv.add((void **)&dup, (size_t)pieces * rws * 8); cv.add((void **)&dkeep, (size_t)pieces * rws);
-    if (mem == QPN_MEM_HOST) {
-        cv.add((void **)&dQ, sz.Q); cv.add((void **)&dR, sz.R + 8); cv.add((void **)&dq, sz.q); cv.add((void **)&dA, sz.A + 8);
-        cv.add((void **)&dB, sz.B + 8); cv.add((void **)&dl, sz.lu + 8); cv.add((void **)&du, sz.lu + 8);
-        if (node_of) cv.add((void **)&dno, (size_t)pieces * 4);
-        cv.add((void **)&dK, (size_t)pieces * N); cv.add((void **)&dAr, (size_t)pieces * oc * cap * 8);
-        cv.add((void **)&dlr, (size_t)pieces * cap * 8 + 8); cv.add((void **)&dur, (size_t)pieces * cap * 8 + 8);
-        cv.add((void **)&drows, (size_t)pieces * 4); cv.add((void **)&dflags, (size_t)pieces * 4);
-    }
-    int rc = cv.commit();
+    NodeDev d{};
+    const int32_t *dno; const uint8_t *dK;
+    double *dAp, *dlp, *dup, *dAr, *dlr, *dur; uint8_t *dkeep; int32_t *drows, *dflags;
+    st.scratch(dAp, (size_t)pieces * rws * cols * 8); st.scratch(dlp, (size_t)pieces * rws * 8);
+    st.scratch(dup, (size_t)pieces * rws * 8); st.scratch(dkeep, (size_t)pieces * rws);
+    stage_records(st, d, node_sizes(nodes, n, m, p, 0), Qd, R, qd, Ad, B, l, u);
+    st.in(dno, node_of, (size_t)pieces * 4); st.in(dK, K, (size_t)pieces * N);
+    st.out(dAr, Ar, (size_t)pieces * oc * cap * 8); st.out(dlr, lr, (size_t)pieces * cap * 8, 8);
+    st.out(dur, ur, (size_t)pieces * cap * 8, 8); st.out(drows, rows, (size_t)pieces * 4); st.out(dflags, flags, (size_t)pieces * 4);
+    int rc = st.begin();
     if (rc != QPN_OK) return rc;
-    if (mem == QPN_MEM_DEVICE) {
-        HIPCHK(ctx, qpn_launch_local_pieces(pieces, nodes, n, m, p, Qd, R, qd, Ad, B, l, u, node_of, K, dAp, dlp, dup, dkeep, s));
-        HIPCHK(ctx, qpn_launch_reduce_pieces(pieces, n, m, p, tol, dAp, dlp, dup, dkeep, Ar, lr, ur, rows, flags, s));
-        return QPN_OK;
-    }
-    HIPCHK(ctx, hipMemcpyAsync(dQ, Qd, sz.Q, hipMemcpyHostToDevice, s));
-    if (sz.R) HIPCHK(ctx, hipMemcpyAsync(dR, R, sz.R, hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, hipMemcpyAsync(dq, qd, sz.q, hipMemcpyHostToDevice, s));
-    if (sz.A) HIPCHK(ctx, hipMemcpyAsync(dA, Ad, sz.A, hipMemcpyHostToDevice, s));
-    if (sz.B) HIPCHK(ctx, hipMemcpyAsync(dB, B, sz.B, hipMemcpyHostToDevice, s));
-    if (sz.lu) { HIPCHK(ctx, hipMemcpyAsync(dl, l, sz.lu, hipMemcpyHostToDevice, s)); HIPCHK(ctx, hipMemcpyAsync(du, u, sz.lu, hipMemcpyHostToDevice, s)); }
-    if (node_of) HIPCHK(ctx, hipMemcpyAsync(dno, node_of, (size_t)pieces * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, hipMemcpyAsync(dK, K, (size_t)pieces * N, hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, qpn_launch_local_pieces(pieces, nodes, n, m, p, dQ, dR, dq, dA, dB, dl, du, dno, dK, dAp, dlp, dup, dkeep, s));
+    HIPCHK(ctx, qpn_launch_local_pieces(pieces, nodes, n, m, p, d.Q, d.R, d.q, d.A, d.B, d.l, d.u, dno, dK, dAp, dlp, dup, dkeep, s));
     HIPCHK(ctx, qpn_launch_reduce_pieces(pieces, n, m, p, tol, dAp, dlp, dup, dkeep, dAr, dlr, dur, drows, dflags, s));
-    HIPCHK(ctx, hipMemcpyAsync(Ar, dAr, (size_t)pieces * oc * cap * 8, hipMemcpyDeviceToHost, s));
-    if (cap) {
-        HIPCHK(ctx, hipMemcpyAsync(lr, dlr, (size_t)pieces * cap * 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(ctx, hipMemcpyAsync(ur, dur, (size_t)pieces * cap * 8, hipMemcpyDeviceToHost, s));
-    }
-    HIPCHK(ctx, hipMemcpyAsync(rows, drows, (size_t)pieces * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(ctx, hipMemcpyAsync(flags, dflags, (size_t)pieces * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(ctx, hipStreamSynchronize(s));
-    return QPN_OK;
+    return st.finish();
 }
 
 int qpn_local_pieces(qpn_ctx *ctx, int32_t pieces, int32_t nodes, int32_t n, int32_t m, int32_t p, const double *Qd,
@@ -617,44 +563,25 @@ int qpn_local_pieces(qpn_ctx *ctx, int32_t pieces, int32_t nodes, int32_t n, int
     if (!Qd || !qd || (m > 0 && (!Ad || !l || !u)) || (p > 0 && (!R || (m > 0 && !B))) || !K || !Ap || !lp || !up || !keep)
         return fail_arg(ctx, "qpn_local_pieces: null pointer");
     if (!node_of && nodes < pieces) return fail_arg(ctx, "qpn_local_pieces: fewer record sets than pieces and no node_of");
-    if (mem != QPN_MEM_HOST && mem != QPN_MEM_DEVICE) return fail_arg(ctx, "qpn_local_pieces: bad mem kind");
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
-    if (mem == QPN_MEM_DEVICE) {
-        HIPCHK(ctx, qpn_launch_local_pieces(pieces, nodes, n, m, p, Qd, R, qd, Ad, B, l, u, node_of, K, Ap, lp, up, keep, s));
-        return QPN_OK;
-    }
-    if (node_of)
+    Stage st(ctx, mem, "qpn_local_pieces");
+    if (st.host && node_of)
         for (int t = 0; t < pieces; ++t)
             if (node_of[t] < 0 || node_of[t] >= nodes) return fail_arg(ctx, "qpn_local_pieces: node_of outside 0..nodes-1");
     const int N = n + m;
-    const NodeSizes sz = node_sizes(nodes, n, m, p, 0);
     const size_t rows = 2 * (size_t)N, cols = (size_t)N + p;
-    double *dQ, *dR, *dq, *dA, *dB, *dl, *du, *dAp, *dlp, *dup; int32_t *dno = nullptr; uint8_t *dK, *dkeep;
-    Carver cv(ctx);
-    cv.add((void **)&dQ, sz.Q); cv.add((void **)&dR, sz.R + 8); cv.add((void **)&dq, sz.q); cv.add((void **)&dA, sz.A + 8);
-    cv.add((void **)&dB, sz.B + 8); cv.add((void **)&dl, sz.lu + 8); cv.add((void **)&du, sz.lu + 8);
-    if (node_of) cv.add((void **)&dno, (size_t)pieces * 4);
-    cv.add((void **)&dK, (size_t)pieces * N); cv.add((void **)&dAp, (size_t)pieces * rows * cols * 8);
-    cv.add((void **)&dlp, (size_t)pieces * rows * 8); cv.add((void **)&dup, (size_t)pieces * rows * 8);
-    cv.add((void **)&dkeep, (size_t)pieces * rows);
-    int rc = cv.commit();
+    NodeDev d{};
+    const int32_t *dno; const uint8_t *dK;
+    double *dAp, *dlp, *dup; uint8_t *dkeep;
+    stage_records(st, d, node_sizes(nodes, n, m, p, 0), Qd, R, qd, Ad, B, l, u);
+    st.in(dno, node_of, (size_t)pieces * 4); st.in(dK, K, (size_t)pieces * N);
+    st.out(dAp, Ap, (size_t)pieces * rows * cols * 8); st.out(dlp, lp, (size_t)pieces * rows * 8);
+    st.out(dup, up, (size_t)pieces * rows * 8); st.out(dkeep, keep, (size_t)pieces * rows);
+    int rc = st.begin();
     if (rc != QPN_OK) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(dQ, Qd, sz.Q, hipMemcpyHostToDevice, s));
-    if (sz.R) HIPCHK(ctx, hipMemcpyAsync(dR, R, sz.R, hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, hipMemcpyAsync(dq, qd, sz.q, hipMemcpyHostToDevice, s));
-    if (sz.A) HIPCHK(ctx, hipMemcpyAsync(dA, Ad, sz.A, hipMemcpyHostToDevice, s));
-    if (sz.B) HIPCHK(ctx, hipMemcpyAsync(dB, B, sz.B, hipMemcpyHostToDevice, s));
-    if (sz.lu) { HIPCHK(ctx, hipMemcpyAsync(dl, l, sz.lu, hipMemcpyHostToDevice, s)); HIPCHK(ctx, hipMemcpyAsync(du, u, sz.lu, hipMemcpyHostToDevice, s)); }
-    if (node_of) HIPCHK(ctx, hipMemcpyAsync(dno, node_of, (size_t)pieces * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, hipMemcpyAsync(dK, K, (size_t)pieces * N, hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, qpn_launch_local_pieces(pieces, nodes, n, m, p, dQ, dR, dq, dA, dB, dl, du, dno, dK, dAp, dlp, dup, dkeep, s));
-    HIPCHK(ctx, hipMemcpyAsync(Ap, dAp, (size_t)pieces * rows * cols * 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(ctx, hipMemcpyAsync(lp, dlp, (size_t)pieces * rows * 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(ctx, hipMemcpyAsync(up, dup, (size_t)pieces * rows * 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(ctx, hipMemcpyAsync(keep, dkeep, (size_t)pieces * rows, hipMemcpyDeviceToHost, s));
-    HIPCHK(ctx, hipStreamSynchronize(s));
-    return QPN_OK;
+    HIPCHK(ctx, qpn_launch_local_pieces(pieces, nodes, n, m, p, d.Q, d.R, d.q, d.A, d.B, d.l, d.u, dno, dK, dAp, dlp, dup, dkeep,
+                                        ctx->stream));
+    return st.finish();
 }
 
 // ---- (A6) pool assembly -------------------------------------------------------------------------------------
@@ -685,7 +612,6 @@ int qpn_assemble_pools(qpn_ctx *ctx, const qpn_pool_shape *sh, int form, int32_t
     if (rc != QPN_OK) return rc == QPN_ERR_ARG ? fail_arg(ctx, "qpn_assemble_pools: bad pool shape or form") : rc;
     if (batch < 0) return fail_arg(ctx, "qpn_assemble_pools: batch < 0");
     if (batch == 0) return QPN_OK;
-    if (mem != QPN_MEM_HOST && mem != QPN_MEM_DEVICE) return fail_arg(ctx, "qpn_assemble_pools: bad mem kind");
     if (!sh->dpos) return fail_arg(ctx, "qpn_assemble_pools: null dpos");
     const int nd = sh->nd, p = sh->p;
     int sn = 0, sm = 0;
@@ -728,49 +654,24 @@ int qpn_assemble_pools(qpn_ctx *ctx, const qpn_pool_shape *sh, int form, int32_t
     const size_t bQd = span(stride_Qd, szQd), bQp = span(stride_Qp, szQp), bqd = span(stride_qd, sn), bAd = span(stride_Ad, szAd),
                  bBp = span(stride_Bp, szBp), blu = span(stride_lu, sm), bw = span(stride_w, p);
     const size_t bM = span(strideM, (size_t)N * N), bN = (size_t)batch * N;
-    int32_t *dmaps;
-    double *dQd = nullptr, *dQp = nullptr, *dqd = nullptr, *dAd = nullptr, *dBp = nullptr, *dl = nullptr, *du = nullptr, *dw = nullptr;
-    double *dM = nullptr, *dq = nullptr, *dlo = nullptr, *dhi = nullptr; uint8_t *dk = nullptr;
-    Carver cv(ctx);
-    cv.add((void **)&dmaps, maps.size() * 4);
-    if (mem == QPN_MEM_HOST) {
-        cv.add((void **)&dQd, bQd + 8); cv.add((void **)&dQp, bQp + 8); cv.add((void **)&dqd, bqd + 8); cv.add((void **)&dAd, bAd + 8);
-        cv.add((void **)&dBp, bBp + 8); cv.add((void **)&dl, blu + 8); cv.add((void **)&du, blu + 8); cv.add((void **)&dw, bw + 8);
-        cv.add((void **)&dM, bM); cv.add((void **)&dq, bN * 8); cv.add((void **)&dlo, bN * 8); cv.add((void **)&dhi, bN * 8);
-        cv.add((void **)&dk, bN);
-    }
-    rc = cv.commit();
-    if (rc != QPN_OK) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(dmaps, maps.data(), maps.size() * 4, hipMemcpyHostToDevice, s));
     QpnPoolLaunch L{};
     L.batch = batch; L.form = form; L.nd = nd; L.sn = sn; L.sm = sm; L.p = p;
-    L.xi_owner = dmaps; L.xi_dpos = dmaps + sn; L.con_owner = dmaps + 2 * sn; L.dec_src = dmaps + 2 * sn + sm;
     L.s_Qd = stride_Qd; L.s_Qp = stride_Qp; L.s_qd = stride_qd; L.s_Ad = stride_Ad; L.s_Bp = stride_Bp; L.s_lu = stride_lu;
     L.s_w = stride_w; L.s_M = strideM;
-    if (mem == QPN_MEM_HOST) {
-        HIPCHK(ctx, hipMemcpyAsync(dQd, Qd, bQd, hipMemcpyHostToDevice, s));
-        if (szQp) HIPCHK(ctx, hipMemcpyAsync(dQp, Qp, bQp, hipMemcpyHostToDevice, s));
-        HIPCHK(ctx, hipMemcpyAsync(dqd, qd, bqd, hipMemcpyHostToDevice, s));
-        if (szAd) HIPCHK(ctx, hipMemcpyAsync(dAd, Ad, bAd, hipMemcpyHostToDevice, s));
-        if (szBp) HIPCHK(ctx, hipMemcpyAsync(dBp, Bp, bBp, hipMemcpyHostToDevice, s));
-        if (sm) { HIPCHK(ctx, hipMemcpyAsync(dl, l, blu, hipMemcpyHostToDevice, s)); HIPCHK(ctx, hipMemcpyAsync(du, u, blu, hipMemcpyHostToDevice, s)); }
-        if (p) HIPCHK(ctx, hipMemcpyAsync(dw, w, bw, hipMemcpyHostToDevice, s));
-        L.Qd = dQd; L.Qp = dQp; L.qd = dqd; L.Ad = dAd; L.Bp = dBp; L.l = dl; L.u = du; L.w = dw;
-        L.M = dM; L.q = dq; L.lo = dlo; L.hi = dhi; L.kind = dk;
-    } else {
-        // (the maps were copied from a host vector that dies with this call: the copy must have left it)
-        L.Qd = Qd; L.Qp = Qp; L.qd = qd; L.Ad = Ad; L.Bp = Bp; L.l = l; L.u = u; L.w = w;
-        L.M = Mout; L.q = qout; L.lo = lout; L.hi = uout; L.kind = kind_out;
-    }
+    const int32_t *dmaps;
+    Stage st(ctx, mem, "qpn_assemble_pools");
+    st.lib_in(dmaps, maps.data(), maps.size() * 4);
+    // (an empty item uploads nothing, whatever its stride)
+    st.in(L.Qd, Qd, bQd, 8); st.in(L.Qp, Qp, szQp ? bQp : 0, 8); st.in(L.qd, qd, bqd, 8); st.in(L.Ad, Ad, szAd ? bAd : 0, 8);
+    st.in(L.Bp, Bp, szBp ? bBp : 0, 8); st.in(L.l, l, sm ? blu : 0, 8); st.in(L.u, u, sm ? blu : 0, 8); st.in(L.w, w, p ? bw : 0, 8);
+    st.out(L.M, Mout, bM); st.out(L.q, qout, bN * 8); st.out(L.lo, lout, bN * 8); st.out(L.hi, uout, bN * 8); st.out(L.kind, kind_out, bN);
+    rc = st.begin();
+    if (rc != QPN_OK) return rc;
+    L.xi_owner = dmaps; L.xi_dpos = dmaps + sn; L.con_owner = dmaps + 2 * sn; L.dec_src = dmaps + 2 * sn + sm;
     HIPCHK(ctx, qpn_launch_assemble_pools(L, s));
-    if (mem == QPN_MEM_HOST) {
-        HIPCHK(ctx, hipMemcpyAsync(Mout, dM, bM, hipMemcpyDeviceToHost, s));
-        HIPCHK(ctx, hipMemcpyAsync(qout, dq, bN * 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(ctx, hipMemcpyAsync(lout, dlo, bN * 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(ctx, hipMemcpyAsync(uout, dhi, bN * 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(ctx, hipMemcpyAsync(kind_out, dk, bN, hipMemcpyDeviceToHost, s));
-    }
-    HIPCHK(ctx, hipStreamSynchronize(s));      // host mode: results; device mode: the pageable maps copy must be done
+    if ((rc = st.finish()) != QPN_OK) return rc;
+    // (device mode: the maps were copied from a host vector that dies with this call: the copy must have left it)
+    if (!st.host) HIPCHK(ctx, hipStreamSynchronize(s));
     return QPN_OK;
 }
 
@@ -812,11 +713,6 @@ struct qpn_nodes {
 };
 
 namespace {
-
-struct NodeDev {                // device views of one qpn_solve_nodes call
-    const double *Q, *R, *q, *A, *B, *l, *u, *w;
-    double *z; int32_t *st; double *res; int32_t *pv; uint8_t *act;
-};
 
 // one pass over the resident Qd blocks (behind the copies on the context's stream); waits for the answer
 hipError_t nodes_check_symmetry(qpn_ctx *ctx, qpn_nodes *h)
@@ -1054,15 +950,13 @@ int solve_nodes_any(qpn_ctx *ctx, qpn_nodes *h, int32_t batch, int32_t n, int32_
                     const double *w, int64_t stride_w, double *z, int32_t *status, double *resid, int32_t *pivots,
                     uint8_t *active, const qpn_avi_opts *opts, int mem, double *x, int64_t stride_x)
 {
-    if (mem != QPN_MEM_HOST && mem != QPN_MEM_DEVICE) return fail_arg(ctx, "qpn_solve_nodes: bad mem kind");
+    Stage st(ctx, mem, "qpn_solve_nodes");
+    if (int rc = st.check()) return rc;
     const int N = n + m;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     qpn_avi_opts o;
     if (opts) o = *opts; else qpn_avi_default_opts(&o);
-    hipStream_t s = ctx->stream;
     const size_t bN = (size_t)batch * N;
-    const NodeSizes sz = node_sizes(batch, n, m, p, stride_w);
-    const bool host = mem == QPN_MEM_HOST;
     const NodeRoute route = node_route(ctx, n, m, o);
     // the handle may already know that the general path behind a fused route has nothing to do: no workspace for it then
     nodes_poll_declines(h);
@@ -1070,67 +964,31 @@ int solve_nodes_any(qpn_ctx *ctx, qpn_nodes *h, int32_t batch, int32_t n, int32_
     const bool fused = route == NodeRoute::fused32 || route == NodeRoute::mid;
     const bool need_ws = !(h && fused && h->decl_state == 2);
 
-    NodeDev d{Qd, R, qd, Ad, B, l, u, w, z, status, resid, pivots, active};
     NodeWs ws{};
-    double *hQ, *hR, *hq, *hA, *hB, *hl, *hu, *hw, *hz = nullptr, *hres, *hx = nullptr; int32_t *hst, *hpv; uint8_t *hact;
-    Carver cv(ctx);
     if (need_ws) {
-        cv.add((void **)&ws.M, bN * N * 8); cv.add((void **)&ws.q, bN * 8); cv.add((void **)&ws.l, bN * 8);
-        cv.add((void **)&ws.u, bN * 8); cv.add((void **)&ws.kind, bN);
-        if (N > 64) cv.add((void **)&ws.big, qpn_avi_big_workspace_bytes(batch, N));
+        st.scratch(ws.M, bN * N * 8); st.scratch(ws.q, bN * 8); st.scratch(ws.l, bN * 8); st.scratch(ws.u, bN * 8);
+        st.scratch(ws.kind, bN);
+        if (N > 64) st.scratch(ws.big, qpn_avi_big_workspace_bytes(batch, N));
     }
-    const bool z_ws = !z;          // no z wanted (handle calls): the kernels still need somewhere to put it
-    if (host) {
-        if (!h) {
-            cv.add((void **)&hQ, sz.Q); cv.add((void **)&hR, sz.R + 8); cv.add((void **)&hq, sz.q);
-            cv.add((void **)&hA, sz.A + 8); cv.add((void **)&hB, sz.B + 8); cv.add((void **)&hl, sz.lu + 8);
-            cv.add((void **)&hu, sz.lu + 8);
-        }
-        cv.add((void **)&hw, sz.w + 8); cv.add((void **)&hz, bN * 8);
-        cv.add((void **)&hres, (size_t)batch * 8); cv.add((void **)&hst, (size_t)batch * 4);
-        cv.add((void **)&hpv, (size_t)batch * 4); cv.add((void **)&hact, bN);
-        if (x && route == NodeRoute::fused32) cv.add((void **)&hx, (size_t)batch * n * 8);
-    } else if (z_ws) cv.add((void **)&hz, bN * 8);
-    int rc = cv.commit();
+    const NodeSizes sz = node_sizes(batch, n, m, p, stride_w);
+    NodeDev d{Qd, R, qd, Ad, B, l, u};     // (a handle's records are resident)
+    if (!h) stage_records(st, d, sz, Qd, R, qd, Ad, B, l, u);
+    st.in(d.w, w, sz.w, 8);
+    if (z) st.inout(d.z, z, bN * 8, !(o.flags & QPN_AVI_FLAG_COLD_START));
+    else { st.scratch(d.z, bN * 8); o.flags |= QPN_AVI_FLAG_COLD_START; }   // no z wanted (handle calls): the kernels still need one
+    st.out(d.st, status, (size_t)batch * 4); st.out(d.res, resid, (size_t)batch * 8); st.out(d.pv, pivots, (size_t)batch * 4);
+    st.out(d.act, active, bN);
+    // host mode: the primal blocks come down on their own (2.5 MB at 10 000 nodes; z is twice that), from a buffer of their own
+    // when the fused kernel writes them
+    const bool x_ws = st.host && x && route == NodeRoute::fused32;
+    double *hx = nullptr;
+    if (x_ws) st.scratch(hx, (size_t)batch * n * 8);
+    if (x) st.out2d(x_ws ? hx : d.z, (size_t)(x_ws ? n : N) * 8, x, (size_t)stride_x * 8, (size_t)n * 8, (size_t)batch);
+    int rc = st.begin();
     if (rc != QPN_OK) return rc;
-    if (host) {
-        if (!h) {
-            HIPCHK(ctx, hipMemcpyAsync(hQ, Qd, sz.Q, hipMemcpyHostToDevice, s));
-            if (sz.R) HIPCHK(ctx, hipMemcpyAsync(hR, R, sz.R, hipMemcpyHostToDevice, s));
-            HIPCHK(ctx, hipMemcpyAsync(hq, qd, sz.q, hipMemcpyHostToDevice, s));
-            if (sz.A) HIPCHK(ctx, hipMemcpyAsync(hA, Ad, sz.A, hipMemcpyHostToDevice, s));
-            if (sz.B) HIPCHK(ctx, hipMemcpyAsync(hB, B, sz.B, hipMemcpyHostToDevice, s));
-            if (sz.lu) {
-                HIPCHK(ctx, hipMemcpyAsync(hl, l, sz.lu, hipMemcpyHostToDevice, s));
-                HIPCHK(ctx, hipMemcpyAsync(hu, u, sz.lu, hipMemcpyHostToDevice, s));
-            }
-            d.Q = hQ; d.R = hR; d.q = hq; d.A = hA; d.B = hB; d.l = hl; d.u = hu;
-        }
-        if (p > 0) HIPCHK(ctx, hipMemcpyAsync(hw, w, sz.w, hipMemcpyHostToDevice, s));
-        if (z && !(o.flags & QPN_AVI_FLAG_COLD_START)) HIPCHK(ctx, hipMemcpyAsync(hz, z, bN * 8, hipMemcpyHostToDevice, s));
-        else if (!z) o.flags |= QPN_AVI_FLAG_COLD_START;
-        d.w = hw; d.z = hz; d.res = hres; d.st = hst; d.pv = hpv; d.act = hact;
-    } else if (z_ws) { d.z = hz; o.flags |= QPN_AVI_FLAG_COLD_START; }
-
-    double *x_dev = host ? hx : x;
-    const int64_t sx_dev = host ? (int64_t)n : stride_x;
-    rc = solve_nodes_launch(ctx, h, batch, n, m, p, d, stride_w, o, x_dev, sx_dev, ws, route);
+    rc = solve_nodes_launch(ctx, h, batch, n, m, p, d, stride_w, o, st.host ? hx : x, st.host ? (int64_t)n : stride_x, ws, route);
     if (rc != QPN_OK) return rc;
-    if (host) {
-        if (z) HIPCHK(ctx, hipMemcpyAsync(z, d.z, bN * 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(ctx, hipMemcpyAsync(status, d.st, (size_t)batch * 4, hipMemcpyDeviceToHost, s));
-        if (resid) HIPCHK(ctx, hipMemcpyAsync(resid, d.res, (size_t)batch * 8, hipMemcpyDeviceToHost, s));
-        if (pivots) HIPCHK(ctx, hipMemcpyAsync(pivots, d.pv, (size_t)batch * 4, hipMemcpyDeviceToHost, s));
-        if (active) HIPCHK(ctx, hipMemcpyAsync(active, d.act, bN, hipMemcpyDeviceToHost, s));
-        if (x && hx)       // the primal blocks come down on their own (2.5 MB at 10 000 nodes; z is twice that)
-            HIPCHK(ctx, hipMemcpy2DAsync(x, (size_t)stride_x * 8, hx, (size_t)n * 8, (size_t)n * 8, (size_t)batch,
-                                         hipMemcpyDeviceToHost, s));
-        else if (x)
-            HIPCHK(ctx, hipMemcpy2DAsync(x, (size_t)stride_x * 8, d.z, (size_t)N * 8, (size_t)n * 8, (size_t)batch,
-                                         hipMemcpyDeviceToHost, s));
-        HIPCHK(ctx, hipStreamSynchronize(s));
-    }
-    return QPN_OK;
+    return st.finish();
 }
 
 int verify_nodes_any(qpn_ctx *ctx, bool records_on_device, int32_t batch, int32_t n, int32_t m, int32_t p,
@@ -1392,22 +1250,16 @@ int qpn_order_nodes_by_pivots(qpn_ctx *ctx, const int32_t *pivots, int32_t count
 {
     if (!ctx) return QPN_ERR_ARG;
     if (!pivots || count <= 0) return fail_arg(ctx, "qpn_order_nodes_by_pivots: bad arguments");
-    if (mem != QPN_MEM_HOST && mem != QPN_MEM_DEVICE) return fail_arg(ctx, "qpn_order_nodes_by_pivots: bad mem kind");
+    Stage st(ctx, mem, "qpn_order_nodes_by_pivots");
+    if (int rc = st.check()) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     int rc = order_reserve(ctx, count);
     if (rc != QPN_OK) return rc;
-    const int32_t *dp = pivots;
-    if (mem == QPN_MEM_HOST) {
-        int32_t *tmp;
-        Carver cv(ctx);
-        cv.add((void **)&tmp, (size_t)count * 4);
-        rc = cv.commit();
-        if (rc != QPN_OK) return rc;
-        HIPCHK(ctx, hipMemcpyAsync(tmp, pivots, (size_t)count * 4, hipMemcpyHostToDevice, ctx->stream));
-        dp = tmp;
-    }
+    const int32_t *dp;
+    st.in(dp, pivots, (size_t)count * 4);
+    if ((rc = st.begin()) != QPN_OK) return rc;
     HIPCHK(ctx, qpn_launch_order_by_pivots(dp, count, ctx->order, ctx->stream));
-    if (mem == QPN_MEM_HOST) HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if ((rc = st.finish()) != QPN_OK) return rc;
     ctx->order_count = count;
     ctx->order_user = true;
     return QPN_OK;
@@ -1460,42 +1312,18 @@ int qpn_convexity_nodes(qpn_ctx *ctx, int32_t batch, int32_t n, int32_t m, const
         return QPN_ERR_SIZE;
     }
     if (!Qd || (m > 0 && (!Ad || !eq)) || !convex || !min_eig || !null_dim) return fail_arg(ctx, "qpn_convexity_nodes: null pointer");
-    if (mem != QPN_MEM_HOST && mem != QPN_MEM_DEVICE) return fail_arg(ctx, "qpn_convexity_nodes: bad mem kind");
+    Stage st(ctx, mem, "qpn_convexity_nodes");
+    if (int rc = st.check()) return rc;
     if (batch == 0) return QPN_OK;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
-    const size_t bQ = (size_t)batch * n * n * 8, bA = (size_t)batch * m * n * 8, be = (size_t)batch * m;
-    const size_t gbytes = qpn_convexity_workspace_bytes(batch, n, m);
-    void *gws = nullptr;
-    if (mem == QPN_MEM_DEVICE) {
-        if (gbytes) {
-            Carver cv(ctx);
-            cv.add(&gws, gbytes);
-            int rc = cv.commit();
-            if (rc != QPN_OK) return rc;
-        }
-        HIPCHK(ctx, qpn_launch_convexity(batch, n, m, Qd, Ad, eq, tol, convex, min_eig, null_dim, gws, s));
-        return QPN_OK;
-    }
-    double *dQ, *dA = nullptr, *dmin; uint8_t *de = nullptr; int32_t *dcvx, *dnull;
-    Carver cv(ctx);
-    cv.add((void **)&dQ, bQ);
-    if (m > 0) { cv.add((void **)&dA, bA); cv.add((void **)&de, be); }
-    cv.add((void **)&dcvx, (size_t)batch * 4); cv.add((void **)&dmin, (size_t)batch * 8); cv.add((void **)&dnull, (size_t)batch * 4);
-    if (gbytes) cv.add(&gws, gbytes);
-    int rc = cv.commit();
+    const double *dQ, *dA; const uint8_t *de; int32_t *dcvx, *dnull; double *dmin; void *gws;
+    st.in(dQ, Qd, (size_t)batch * n * n * 8); st.in(dA, Ad, (size_t)batch * m * n * 8); st.in(de, eq, (size_t)batch * m);
+    st.out(dcvx, convex, (size_t)batch * 4); st.out(dmin, min_eig, (size_t)batch * 8); st.out(dnull, null_dim, (size_t)batch * 4);
+    st.scratch(gws, qpn_convexity_workspace_bytes(batch, n, m));
+    int rc = st.begin();
     if (rc != QPN_OK) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(dQ, Qd, bQ, hipMemcpyHostToDevice, s));
-    if (m > 0) {
-        HIPCHK(ctx, hipMemcpyAsync(dA, Ad, bA, hipMemcpyHostToDevice, s));
-        HIPCHK(ctx, hipMemcpyAsync(de, eq, be, hipMemcpyHostToDevice, s));
-    }
-    HIPCHK(ctx, qpn_launch_convexity(batch, n, m, dQ, dA, de, tol, dcvx, dmin, dnull, gws, s));
-    HIPCHK(ctx, hipMemcpyAsync(convex, dcvx, (size_t)batch * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(ctx, hipMemcpyAsync(min_eig, dmin, (size_t)batch * 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(ctx, hipMemcpyAsync(null_dim, dnull, (size_t)batch * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(ctx, hipStreamSynchronize(s));
-    return QPN_OK;
+    HIPCHK(ctx, qpn_launch_convexity(batch, n, m, dQ, dA, de, tol, dcvx, dmin, dnull, gws, ctx->stream));
+    return st.finish();
 }
 
 } // extern "C"
@@ -1511,78 +1339,35 @@ int verify_nodes_any(qpn_ctx *ctx, bool records_on_device, int32_t batch, int32_
     if (batch == 0) return QPN_OK;
     if (n > qpn_verify_max_dim() || m > qpn_verify_max_dim()) { ctx->last_error = "qpn_verify_nodes: n, m <= 512 in ABI v1"; return QPN_ERR_SIZE; }
     const bool wide_avi = m > 64;         // the bounded-LSQ fallback of wide nodes runs on the large-item AVI kernel
-    double *wbig = nullptr;
     if (!Qd || !qd || !xd || (m > 0 && (!Ad || !l || !u || !lambda)) || (p > 0 && (!R || !w || (m > 0 && !B))) ||
         !solution || !path)
         return fail_arg(ctx, "qpn_verify_nodes: null pointer");
     if (stride_w != 0 && stride_w < p) return fail_arg(ctx, "qpn_verify_nodes: stride_w < p");
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
     const size_t mm = (size_t)(m > 0 ? m : 1);
-    // scratch of the bounded-LSQ fallback (src/qp_processing.jl:129-137): Gram block + vectors
-    double *sG, *sq, *slb, *sub, *sz, *sres, *gws = nullptr; int32_t *sst;
     const bool wide = n > QPN_VERIFY_WIDE_FROM || m > QPN_VERIFY_WIDE_FROM;
     const bool mid = !wide && (n > 32 || m > 32);      // verify_node64's class: a small slot workspace for the nodes it hands on
     const size_t mp16 = (size_t)((m + 15) & ~15);
-    if (mem == QPN_MEM_DEVICE) {
-        Carver cv(ctx);
-        cv.add((void **)&sG, (size_t)batch * mm * mm * 8); cv.add((void **)&sq, (size_t)batch * mm * 8);
-        cv.add((void **)&slb, (size_t)batch * mm * 8); cv.add((void **)&sub, (size_t)batch * mm * 8);
-        cv.add((void **)&sz, (size_t)batch * mm * 8); cv.add((void **)&sres, (size_t)batch * 8);
-        cv.add((void **)&sst, (size_t)batch * 4);
-        if (wide_avi) cv.add((void **)&wbig, qpn_avi_big_workspace_bytes(batch, m));
-        if (wide && m > 0) cv.add((void **)&gws, (size_t)batch * 2 * mp16 * mp16 * 8);
-        else if (mid && m > 0) cv.add((void **)&gws, (size_t)QPN_VERIFY_MID_SLOTS * 2 * mp16 * mp16 * 8 + 64);
-        int rc = cv.commit();
-        if (rc != QPN_OK) return rc;
-        HIPCHK(ctx, qpn_launch_verify_nodes(batch, n, m, p, Qd, R, qd, Ad, B, l, u, xd, w, stride_w, tol,
-                                            solution, lambda, path, sG, sq, slb, sub, sz, sres, sst, s, wbig, gws));
-        return QPN_OK;
-    }
-    if (mem != QPN_MEM_HOST) return fail_arg(ctx, "qpn_verify_nodes: bad mem kind");
     const NodeSizes sz_ = node_sizes(batch, n, m, p, stride_w);
-    const double *dQ = Qd, *dR = R, *dq = qd, *dA = Ad, *dB = B, *dl = l, *du = u;
-    double *sQ, *sR, *sqq, *sA, *sB, *sl, *su;
-    double *dw, *dx, *dlam; int32_t *dsol, *dpath;
-    Carver cv(ctx);
-    if (!records_on_device) {
-        cv.add((void **)&sQ, sz_.Q); cv.add((void **)&sR, sz_.R + 8); cv.add((void **)&sqq, sz_.q);
-        cv.add((void **)&sA, sz_.A + 8); cv.add((void **)&sB, sz_.B + 8); cv.add((void **)&sl, sz_.lu + 8);
-        cv.add((void **)&su, sz_.lu + 8);
-    }
-    cv.add((void **)&dw, sz_.w + 8); cv.add((void **)&dx, sz_.q);
-    cv.add((void **)&dlam, sz_.lu + 8); cv.add((void **)&dsol, (size_t)batch * 4);
-    cv.add((void **)&dpath, (size_t)batch * 4);
-    cv.add((void **)&sG, (size_t)batch * mm * mm * 8); cv.add((void **)&sq, (size_t)batch * mm * 8);
-    cv.add((void **)&slb, (size_t)batch * mm * 8); cv.add((void **)&sub, (size_t)batch * mm * 8);
-    cv.add((void **)&sz, (size_t)batch * mm * 8); cv.add((void **)&sres, (size_t)batch * 8);
-    cv.add((void **)&sst, (size_t)batch * 4);
-    if (wide_avi) cv.add((void **)&wbig, qpn_avi_big_workspace_bytes(batch, m));
-    if (wide && m > 0) cv.add((void **)&gws, (size_t)batch * 2 * mp16 * mp16 * 8);
-    else if (mid && m > 0) cv.add((void **)&gws, (size_t)QPN_VERIFY_MID_SLOTS * 2 * mp16 * mp16 * 8 + 64);
-    int rc = cv.commit();
+    Stage st(ctx, mem, "qpn_verify_nodes");
+    NodeDev d{Qd, R, qd, Ad, B, l, u};
+    if (!records_on_device) stage_records(st, d, sz_, Qd, R, qd, Ad, B, l, u);
+    const double *dx; double *dlam; int32_t *dsol, *dpath;
+    st.in(dx, xd, sz_.q); st.in(d.w, w, sz_.w, 8);
+    st.out(dsol, solution, (size_t)batch * 4); st.out(dpath, path, (size_t)batch * 4); st.out(dlam, lambda, sz_.lu, 8);
+    // scratch of the bounded-LSQ fallback (src/qp_processing.jl:129-137): Gram block + vectors
+    double *sG, *sq, *slb, *sub, *sz, *sres, *wbig = nullptr, *gws = nullptr; int32_t *sst;
+    st.scratch(sG, (size_t)batch * mm * mm * 8); st.scratch(sq, (size_t)batch * mm * 8);
+    st.scratch(slb, (size_t)batch * mm * 8); st.scratch(sub, (size_t)batch * mm * 8);
+    st.scratch(sz, (size_t)batch * mm * 8); st.scratch(sres, (size_t)batch * 8); st.scratch(sst, (size_t)batch * 4);
+    if (wide_avi) st.scratch(wbig, qpn_avi_big_workspace_bytes(batch, m));
+    if (wide && m > 0) st.scratch(gws, (size_t)batch * 2 * mp16 * mp16 * 8);
+    else if (mid && m > 0) st.scratch(gws, (size_t)QPN_VERIFY_MID_SLOTS * 2 * mp16 * mp16 * 8 + 64);
+    int rc = st.begin();
     if (rc != QPN_OK) return rc;
-    if (!records_on_device) {
-        HIPCHK(ctx, hipMemcpyAsync(sQ, Qd, sz_.Q, hipMemcpyHostToDevice, s));
-        if (sz_.R) HIPCHK(ctx, hipMemcpyAsync(sR, R, sz_.R, hipMemcpyHostToDevice, s));
-        HIPCHK(ctx, hipMemcpyAsync(sqq, qd, sz_.q, hipMemcpyHostToDevice, s));
-        if (sz_.A) HIPCHK(ctx, hipMemcpyAsync(sA, Ad, sz_.A, hipMemcpyHostToDevice, s));
-        if (sz_.B) HIPCHK(ctx, hipMemcpyAsync(sB, B, sz_.B, hipMemcpyHostToDevice, s));
-        if (sz_.lu) {
-            HIPCHK(ctx, hipMemcpyAsync(sl, l, sz_.lu, hipMemcpyHostToDevice, s));
-            HIPCHK(ctx, hipMemcpyAsync(su, u, sz_.lu, hipMemcpyHostToDevice, s));
-        }
-        dQ = sQ; dR = sR; dq = sqq; dA = sA; dB = sB; dl = sl; du = su;
-    }
-    HIPCHK(ctx, hipMemcpyAsync(dx, xd, sz_.q, hipMemcpyHostToDevice, s));
-    if (p > 0) HIPCHK(ctx, hipMemcpyAsync(dw, w, sz_.w, hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, qpn_launch_verify_nodes(batch, n, m, p, dQ, dR, dq, dA, dB, dl, du, dx, dw, stride_w, tol,
-                                        dsol, dlam, dpath, sG, sq, slb, sub, sz, sres, sst, s, wbig, gws));
-    HIPCHK(ctx, hipMemcpyAsync(solution, dsol, (size_t)batch * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(ctx, hipMemcpyAsync(path, dpath, (size_t)batch * 4, hipMemcpyDeviceToHost, s));
-    if (sz_.lu) HIPCHK(ctx, hipMemcpyAsync(lambda, dlam, sz_.lu, hipMemcpyDeviceToHost, s));
-    HIPCHK(ctx, hipStreamSynchronize(s));
-    return QPN_OK;
+    HIPCHK(ctx, qpn_launch_verify_nodes(batch, n, m, p, d.Q, d.R, d.q, d.A, d.B, d.l, d.u, dx, d.w, stride_w, tol,
+                                        dsol, dlam, dpath, sG, sq, slb, sub, sz, sres, sst, ctx->stream, wbig, gws));
+    return st.finish();
 }
 
 } // namespace
