@@ -350,6 +350,40 @@ int qpn_reduced_pieces(qpn_ctx *ctx, int32_t pieces, int32_t nodes, int32_t n, i
                        const double *u, const int32_t *node_of, const uint8_t *K, double tol, double *Ar, double *lr, double *ur,
                        int32_t *rows, int32_t *flags, int mem);
 
+/* ---- every recipe of a solution graph, chunk by chunk, finished on the device (QPNetOptions.max_pieces = None) --------------
+ * qpn_recipes_batch_range: qpn_recipes_batch from a starting recipe per node: node b gets the recipes
+ *   first[b] .. first[b] + offsets[b+1] - offsets[b] - 1 of its Cartesian product (row 0 the fastest digit).  first [nodes] int64
+ *   and offsets are ALWAYS host arrays; first[b] < 0 or a range beyond the product (device masks are read back to check it) is
+ *   QPN_ERR_ARG.  first == NULL is qpn_recipes_batch.
+ * qpn_finish_pieces: the finishing step of qpn_reduced_pieces' output (Ar [pieces][n+p][cap] column-major, lr, ur [pieces][cap],
+ *   rows, flags [pieces], cap = n + 2m, n + m <= 512).  Piece t belongs to item rec_of[t] (0 .. records-1); item k reads the
+ *   ncols[k] <= n + p columns take[k][0 .. ncols[k]-1] of Ar (in ascending global order: the item's column map), the point xk[k][.]
+ *   and the probe vector probe[k][.] on them (take, xk, probe: [records][n+p]).  Per piece, over those columns, with the host's
+ *   operations in the host's order (fp contraction off): every row scaled to a largest |coefficient| of 1 (bounds with it),
+ *   entries < 1e-8 dropped, the row divided by |its leading nonzero| (negated, bounds swapped, when that is negative).  Outputs:
+ *     status [pieces]  QPN_FIN_MEMBER: worst <= member_tol;  QPN_FIN_MERGE: two row projections on the probe vector are close
+ *                      after sorting (<= 1e-7 (1 + |h|)) or a valid row is all zero;  QPN_FIN_DUP: an equal earlier piece exists;
+ *                      QPN_FIN_FLAGGED: flags[t] != 0, nothing else is computed for the piece (worst 0, hash 0)
+ *     worst [pieces]   the largest violation of the point over the live rows (index < rows[t], some nonzero coefficient), >= 0
+ *     hash [pieces]    64 bits of the key: the rows rounded to 6 digits (rint(v 1e6) / 1e6 + 0.0), then the bounds rounded
+ *     dup_of [pieces]  for a member that is neither a merge candidate nor flagged: the earliest earlier such piece of the same item
+ *                      whose rows, rounded rows and rounded bounds are bit-equal (-1: none); -1 for every other piece
+ *     store_of [pieces] the piece's slot in the store, or -1.  Stored: the members that are neither duplicates nor flagged.
+ *     As [store_cap][n+p][cap] (column-major; columns >= ncols are 0), ls, us [store_cap][cap], rows_s [store_cap]: the
+ *                      normalised pieces, in piece order; *stored (host) = their number.  More than store_cap: QPN_ERR_SIZE.
+ *   Host mode copies back only the first *stored slots of the store. */
+#define QPN_FIN_MEMBER 1
+#define QPN_FIN_MERGE 2
+#define QPN_FIN_DUP 4
+#define QPN_FIN_FLAGGED 8
+int qpn_recipes_batch_range(qpn_ctx *ctx, int32_t nodes, int32_t N, const uint8_t *masks, const int64_t *first, const int64_t *offsets,
+                            uint8_t *K, int32_t *node_of, int mem);
+int qpn_finish_pieces(qpn_ctx *ctx, int32_t pieces, int32_t records, int32_t n, int32_t m, int32_t p, const double *Ar, const double *lr,
+                      const double *ur, const int32_t *rows, const int32_t *flags, const int32_t *rec_of, const int32_t *ncols,
+                      const int32_t *take, const double *xk, const double *probe, double member_tol, int32_t *status, double *worst,
+                      uint64_t *hash, int32_t *dup_of, int32_t *store_of, int32_t store_cap, double *As, double *ls, double *us,
+                      int32_t *rows_s, int32_t *stored, int mem);
+
 /* ---- (A8) batched per-node KKT verification, src/qp_processing.jl:57-149 ------------
  *   xd [batch][n] current decision values, w as above.
  *   solution [batch] int32 (1 = optimal for the node), lambda [batch][m] (sign: + at the lower

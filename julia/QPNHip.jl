@@ -291,6 +291,53 @@ function recipes_batch(masks::Matrix{UInt8}, counts::Vector{<:Integer})
 end
 
 """
+    recipes_batch_range(masks, first, counts) -> (K, node_of)
+
+`recipes_batch` from a starting recipe per node (`qpn_recipes_batch_range`): node b gets the recipes `first[b] .. first[b] +
+counts[b] - 1` (0-based) of its product, row 0 the fastest digit.  A range beyond the product is an error.
+"""
+function recipes_batch_range(masks::Matrix{UInt8}, first::Vector{<:Integer}, counts::Vector{<:Integer})
+    N, nodes = size(masks)
+    offsets = Int64[0; cumsum(Int64.(counts))]
+    total = Int(offsets[end])
+    K = zeros(UInt8, N, total); node_of = zeros(Int32, total)
+    rc = ccall((:qpn_recipes_batch_range, LIB), Cint,
+               (Ptr{Cvoid}, Int32, Int32, Ptr{UInt8}, Ptr{Int64}, Ptr{Int64}, Ptr{UInt8}, Ptr{Int32}, Cint),
+               ctx(), Int32(nodes), Int32(N), masks, Int64.(first), offsets, K, node_of, QPN_MEM_HOST)
+    rc == 0 || error("qpn_recipes_batch_range failed ($rc)")
+    (K, node_of)
+end
+
+"""
+    finish_pieces(Ar, lr, ur, rows, flags, rec_of, ncols, take, xk, probe, n, m; member_tol = 1e-5)
+        -> (status, worst, hash, dup_of, store_of, As, ls, us, rows_s)
+
+The finishing step of `reduced_pieces`' output (`qpn_finish_pieces`): every piece over its item's columns `take[1:ncols[k], k]`
+(0-based positions among the n + p columns, in ascending global order), normalised, with the point's worst violation, the merge
+test, the 64-bit hash of the rounded key and the earliest equal earlier piece (`dup_of`, 0-based, -1: none).  `rec_of` is 0-based.
+The store (`As[:, :, s]`, the cap x (n + p) row matrix of stored piece s) holds the members that are neither duplicates nor
+flagged; `store_of[t]` is a piece's 0-based slot or -1.  Status bits: 1 member, 2 merge candidate, 4 duplicate, 8 flagged.
+"""
+function finish_pieces(Ar::Array{Float64,3}, lr::Matrix{Float64}, ur::Matrix{Float64}, rows::Vector{Int32}, flags::Vector{Int32},
+                       rec_of::Vector{Int32}, ncols::Vector{Int32}, take::Matrix{Int32}, xk::Matrix{Float64}, probe::Matrix{Float64},
+                       n::Integer, m::Integer; member_tol::Float64 = 1e-5)
+    cap, oc, pieces = size(Ar); records = length(ncols); p = oc - n
+    status = zeros(Int32, pieces); worst = zeros(pieces); hash = zeros(UInt64, pieces); dup_of = zeros(Int32, pieces)
+    store_of = zeros(Int32, pieces)
+    As = zeros(cap, oc, pieces); ls = zeros(cap, pieces); us = zeros(cap, pieces); rows_s = zeros(Int32, pieces)
+    stored = Ref{Int32}(0)
+    rc = ccall((:qpn_finish_pieces, LIB), Cint,
+               (Ptr{Cvoid}, Int32, Int32, Int32, Int32, Int32, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int32}, Ptr{Int32},
+                Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Cdouble}, Ptr{Cdouble}, Cdouble, Ptr{Int32}, Ptr{Cdouble}, Ptr{UInt64},
+                Ptr{Int32}, Ptr{Int32}, Int32, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int32}, Ref{Int32}, Cint),
+               ctx(), Int32(pieces), Int32(records), Int32(n), Int32(m), Int32(p), Ar, lr, ur, rows, flags, rec_of, ncols, take, xk,
+               probe, member_tol, status, worst, hash, dup_of, store_of, Int32(pieces), As, ls, us, rows_s, stored, QPN_MEM_HOST)
+    rc == 0 || error("qpn_finish_pieces failed ($rc)")
+    S = Int(stored[])
+    (status, worst, hash, dup_of, store_of, As[:, :, 1:S], ls[:, 1:S], us[:, 1:S], rows_s[1:S])
+end
+
+"""
     reduced_pieces(Qd, R, qd, Ad, B, l, u, K, node_of; tol = 1e-9) -> (Ar, lr, ur, rows, flags)
 
 `local_piece` (src/avi_solutions.jl:400-496) for the recipes K (one column each) over the node records (third index = node, as

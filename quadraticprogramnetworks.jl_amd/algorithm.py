@@ -15,7 +15,9 @@ class CyclingError(RuntimeError):
 
 
 def solve(qpn, x_init=None, engine=None, rng=None):
-    """solve(qpn) / solve(qpn, x_init) -> dict(solved, x_opt, Sol, x_fail)."""
+    """solve(qpn) / solve(qpn, x_init) -> dict(solved, x_opt, Sol, x_fail).  A solved result also carries `truncated`: the
+    sorted ids of the nodes whose solution graph the cap QPNetOptions.max_pieces cut short in the sweep that produced the
+    answer (always [] with max_pieces=None)."""
     if x_init is None:
         x_init = qpn.default_initialization
     rng = rng if rng is not None else np.random.default_rng(1)
@@ -47,12 +49,15 @@ def solve_base(qpn, x_init, level=1, proj_vectors=None, rng=None, engine=None):
             if level < qpn.num_levels():                                             # :32-42
                 low = solve_base(qpn, x, level=level + 1, proj_vectors=proj_vectors, rng=rng, engine=engine)
                 if not low["solved"]:
-                    if opts.check_convexity and "error" in low:                     # a non-convex node below names itself
+                    if (opts.check_convexity or opts.max_pieces is None) and "error" in low:
+                        # a non-convex node below names itself, and so does one with more recipes than the uncapped route takes
                         return dict(solved=False, x_fail=x, x_opt=None, error=low["error"])
                     return dict(solved=False, x_fail=x, x_opt=None)
                 S = low["Sol"]; x = low["x_opt"]
+                cut = set(low["truncated"])                                          # the lower sweep whose Sol this one reads
             else:
                 S = {}
+                cut = set()
             players = sorted(qpn.network_depth_map[level])                           # :44
             child_level = sorted(set().union(*[qpn.network_edges[i] for i in players]))
             results = process_level(qpn, players, x, S, engine=engine,
@@ -99,7 +104,8 @@ def solve_base(qpn, x_init, level=1, proj_vectors=None, rng=None, engine=None):
                 continue
             if level == 1:
                 qpn.iterate_cache = {}
-            return dict(solved=True, x_opt=x, Sol=S)                                 # :116
+            cut.update(pid for pid, r in zip(players, results) if r.get("truncated"))
+            return dict(solved=True, x_opt=x, Sol=S, truncated=sorted(cut))          # :116
         raise RuntimeError("Can't find solution")                                    # :119
     except (RuntimeError, CyclingError) as err:                                      # :120-126
         qpn.iterate_cache = {}

@@ -1,6 +1,7 @@
 // qpn_capi.hip -- the extern "C" boundary of libqpn_hip.so (include/qpn_hip.h).
 // Host-side staging, argument checking and error mapping only; all arithmetic is in the
 // HIP kernels (qpn_avi_*.hip, qpn_kkt.hip, qpn_verify.hip, ...).  No exceptions cross the ABI.
+#include <algorithm>
 #include <climits>
 #include <cmath>
 #include <cstdint>
@@ -549,6 +550,176 @@ int qpn_reduced_pieces(qpn_ctx *ctx, int32_t pieces, int32_t nodes, int32_t n, i
     HIPCHK(ctx, qpn_launch_local_pieces(pieces, nodes, n, m, p, d.Q, d.R, d.q, d.A, d.B, d.l, d.u, dno, dK, dAp, dlp, dup, dkeep, s));
     HIPCHK(ctx, qpn_launch_reduce_pieces(pieces, n, m, p, tol, dAp, dlp, dup, dkeep, dAr, dlr, dur, drows, dflags, s));
     return st.finish();
+}
+
+int qpn_recipes_batch_range(qpn_ctx *ctx, int32_t nodes, int32_t N, const uint8_t *masks, const int64_t *first, const int64_t *offsets,
+                            uint8_t *K, int32_t *node_of, int mem)
+{
+    if (!first) return qpn_recipes_batch(ctx, nodes, N, masks, offsets, K, node_of, mem);
+    if (!ctx) return QPN_ERR_ARG;
+    if (nodes <= 0 || N <= 0 || !masks || !offsets) return fail_arg(ctx, "qpn_recipes_batch_range: bad argument");
+    Stage st(ctx, mem, "qpn_recipes_batch_range");
+    if (int rc = st.check()) return rc;
+    if (offsets[0] != 0) return fail_arg(ctx, "qpn_recipes_batch_range: offsets[0] must be 0");
+    for (int b = 0; b < nodes; ++b) {
+        if (offsets[b + 1] < offsets[b]) return fail_arg(ctx, "qpn_recipes_batch_range: offsets must not decrease");
+        if (first[b] < 0) return fail_arg(ctx, "qpn_recipes_batch_range: first must not be negative");
+    }
+    const int64_t total = offsets[nodes];
+    if (total == 0) return QPN_OK;
+    if (!K || !node_of) return fail_arg(ctx, "qpn_recipes_batch_range: null output");
+    if (total > INT32_MAX) { ctx->last_error = "qpn_recipes_batch_range: more than 2^31 - 1 recipes in one call"; return QPN_ERR_SIZE; }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    // every range must lie inside its node's product (device masks are read back for the check: nodes x N bytes)
+    std::vector<uint8_t> hm;
+    const uint8_t *mk = masks;
+    if (!st.host) {
+        hm.resize((size_t)nodes * N);
+        HIPCHK(ctx, hipMemcpyAsync(hm.data(), masks, hm.size(), hipMemcpyDeviceToHost, s));
+        HIPCHK(ctx, hipStreamSynchronize(s));
+        mk = hm.data();
+    }
+    for (int b = 0; b < nodes; ++b) {
+        int64_t tot = 1;
+        for (int i = 0; i < N; ++i) { const int r = __builtin_popcount(mk[(size_t)b * N + i]); if (r > 1) tot = (tot > INT64_MAX / r) ? INT64_MAX : tot * r; }
+        const int64_t cnt = offsets[b + 1] - offsets[b];
+        if (cnt > 0 && (first[b] >= tot || cnt > tot - first[b]))
+            return fail_arg(ctx, "qpn_recipes_batch_range: a node asks for recipes beyond its product");
+    }
+    const long long *doff, *dfirst; const uint8_t *dm; uint8_t *dK; int32_t *dno;
+    st.lib_in(doff, offsets, (size_t)(nodes + 1) * 8); st.lib_in(dfirst, first, (size_t)nodes * 8);
+    st.in(dm, masks, (size_t)nodes * N); st.out(dK, K, (size_t)total * N); st.out(dno, node_of, (size_t)total * 4);
+    int rc = st.begin();
+    if (rc != QPN_OK) return rc;
+    HIPCHK(ctx, hipStreamSynchronize(s));                            // (offsets and first may be pageable host arrays)
+    HIPCHK(ctx, qpn_launch_recipes_batch(nodes, N, dm, doff, total, dK, dno, s, dfirst));
+    return st.finish();
+}
+
+int qpn_finish_pieces(qpn_ctx *ctx, int32_t pieces, int32_t records, int32_t n, int32_t m, int32_t p, const double *Ar, const double *lr,
+                      const double *ur, const int32_t *rows, const int32_t *flags, const int32_t *rec_of, const int32_t *ncols,
+                      const int32_t *take, const double *xk, const double *probe, double member_tol, int32_t *status, double *worst,
+                      uint64_t *hash, int32_t *dup_of, int32_t *store_of, int32_t store_cap, double *As, double *ls, double *us,
+                      int32_t *rows_s, int32_t *stored, int mem)
+{
+    if (!ctx) return QPN_ERR_ARG;
+    if (pieces < 0 || records <= 0 || n <= 0 || m < 0 || p < 0 || store_cap < 0) return fail_arg(ctx, "qpn_finish_pieces: bad sizes");
+    if (!stored) return fail_arg(ctx, "qpn_finish_pieces: null pointer");
+    *stored = 0;
+    if (pieces == 0) return QPN_OK;
+    if (n + m > 512) { ctx->last_error = "qpn_finish_pieces: n + m <= 512 in ABI v1"; return QPN_ERR_SIZE; }
+    if (!Ar || !lr || !ur || !rows || !flags || !rec_of || !ncols || !take || !xk || !probe || !status || !worst || !hash || !dup_of ||
+        !store_of || (store_cap > 0 && (!As || !ls || !us || !rows_s)))
+        return fail_arg(ctx, "qpn_finish_pieces: null pointer");
+    if (!(member_tol >= 0.0)) return fail_arg(ctx, "qpn_finish_pieces: bad tolerance");
+    Stage st(ctx, mem, "qpn_finish_pieces");
+    if (int rc = st.check()) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const int oc = n + p, cap = n + 2 * m;
+    // the index arrays are checked on the host in both modes (device ones are read back: they are small)
+    std::vector<int32_t> h_rows, h_rec, h_nc, h_take;
+    const int32_t *cr = rows, *crec = rec_of, *cnc = ncols, *ctk = take;
+    if (!st.host) {
+        h_rows.resize(pieces); h_rec.resize(pieces); h_nc.resize(records); h_take.resize((size_t)records * oc);
+        HIPCHK(ctx, hipMemcpyAsync(h_rows.data(), rows, (size_t)pieces * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(ctx, hipMemcpyAsync(h_rec.data(), rec_of, (size_t)pieces * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(ctx, hipMemcpyAsync(h_nc.data(), ncols, (size_t)records * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(ctx, hipMemcpyAsync(h_take.data(), take, (size_t)records * oc * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(ctx, hipStreamSynchronize(s));
+        cr = h_rows.data(); crec = h_rec.data(); cnc = h_nc.data(); ctk = h_take.data();
+    }
+    for (int k = 0; k < records; ++k) {
+        if (cnc[k] < 0 || cnc[k] > oc) return fail_arg(ctx, "qpn_finish_pieces: ncols outside 0..n+p");
+        for (int c = 0; c < cnc[k]; ++c)
+            if (ctk[(size_t)k * oc + c] < 0 || ctk[(size_t)k * oc + c] >= oc) return fail_arg(ctx, "qpn_finish_pieces: take outside 0..n+p-1");
+    }
+    for (int t = 0; t < pieces; ++t) {
+        if (crec[t] < 0 || crec[t] >= records) return fail_arg(ctx, "qpn_finish_pieces: rec_of outside 0..records-1");
+        if (cr[t] < 0 || cr[t] > cap) return fail_arg(ctx, "qpn_finish_pieces: rows outside 0..n+2m");
+    }
+    const size_t P = (size_t)pieces;
+    const double *dAr, *dlr, *dur, *dxk, *dpr; const int32_t *drows, *dflags, *drec, *dnc, *dtk;
+    double *drsc, *drdiv, *dLn, *dUn, *dworst, *dAs, *dls, *dus;
+    int32_t *dstatus, *ddup, *dstore, *drows_s, *dord, *drun0, *dsrc; unsigned long long *dhash;
+    st.in(dAr, Ar, P * oc * cap * 8); st.in(dlr, lr, P * cap * 8); st.in(dur, ur, P * cap * 8);
+    st.in(drows, rows, P * 4); st.in(dflags, flags, P * 4); st.in(drec, rec_of, P * 4);
+    st.in(dnc, ncols, (size_t)records * 4); st.in(dtk, take, (size_t)records * oc * 4);
+    st.in(dxk, xk, (size_t)records * oc * 8); st.in(dpr, probe, (size_t)records * oc * 8);
+    st.scratch(drsc, P * cap * 8); st.scratch(drdiv, P * cap * 8); st.scratch(dLn, P * cap * 8); st.scratch(dUn, P * cap * 8);
+    st.scratch(dord, P * 4); st.scratch(drun0, P * 4); st.scratch(dsrc, P * 4);
+    st.out(dstatus, status, P * 4); st.out(dworst, worst, P * 8); st.out(dhash, hash, P * 8); st.out(ddup, dup_of, P * 4);
+    st.out(dstore, store_of, P * 4);
+    // the store: host mode copies back only the slots that are filled (below), not the whole capacity
+    const size_t scap = (size_t)store_cap;
+    if (st.host) { st.scratch(dAs, scap * oc * cap * 8); st.scratch(dls, scap * cap * 8); st.scratch(dus, scap * cap * 8); st.scratch(drows_s, scap * 4); }
+    else { dAs = As; dls = ls; dus = us; drows_s = rows_s; }
+    int rc = st.begin();
+    if (rc != QPN_OK) return rc;
+    HIPCHK(ctx, qpn_launch_finish_norm(pieces, oc, cap, dAr, dlr, dur, drows, dflags, drec, dnc, dtk, dxk, dpr, member_tol, drsc, drdiv, dLn,
+                                       dUn, dstatus, dworst, dhash, ddup, s));
+    // the duplicate candidates (members, neither merge candidates nor flagged) sorted by (item, hash, piece): equal keys are neighbours
+    std::vector<int32_t> h_st(P);
+    std::vector<unsigned long long> h_hash(P);
+    HIPCHK(ctx, hipMemcpyAsync(h_st.data(), dstatus, P * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipMemcpyAsync(h_hash.data(), dhash, P * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    std::vector<int32_t> ord, run0;
+    ord.reserve(P);
+    for (int t = 0; t < pieces; ++t)
+        if (h_st[t] == QPN_FIN_MEMBER) ord.push_back(t);
+    std::sort(ord.begin(), ord.end(), [&](int32_t a, int32_t b) {
+        if (crec[a] != crec[b]) return crec[a] < crec[b];
+        if (h_hash[a] != h_hash[b]) return h_hash[a] < h_hash[b];
+        return a < b;
+    });
+    run0.resize(ord.size());
+    bool any_run = false;
+    for (size_t q = 0; q < ord.size(); ++q) {
+        const bool same = q > 0 && crec[ord[q]] == crec[ord[q - 1]] && h_hash[ord[q]] == h_hash[ord[q - 1]];
+        run0[q] = same ? run0[q - 1] : (int32_t)q;
+        any_run |= same;
+    }
+    if (any_run) {
+        // (only the pieces that have an earlier one of the same hash need a comparison)
+        std::vector<int32_t> ord2, run2;
+        for (size_t q = 0; q < ord.size(); ++q)
+            if (run0[q] < (int32_t)q) { ord2.push_back((int32_t)q); }
+        // positions refer to the full sorted list: upload it, and the positions to check with their run starts
+        std::vector<int32_t> pos(ord2.size()), r0(ord2.size());
+        for (size_t i = 0; i < ord2.size(); ++i) { pos[i] = ord2[i]; r0[i] = run0[ord2[i]]; }
+        HIPCHK(ctx, hipMemcpyAsync(dord, ord.data(), ord.size() * 4, hipMemcpyHostToDevice, s));
+        HIPCHK(ctx, hipMemcpyAsync(drun0, pos.data(), pos.size() * 4, hipMemcpyHostToDevice, s));
+        HIPCHK(ctx, hipMemcpyAsync(dsrc, r0.data(), r0.size() * 4, hipMemcpyHostToDevice, s));
+        HIPCHK(ctx, qpn_launch_finish_dup((int32_t)pos.size(), dord, drun0, dsrc, oc, cap, dAr, drows, drec, dnc, dtk, drsc, drdiv, dLn, dUn,
+                                          dstatus, ddup, s));
+        HIPCHK(ctx, hipMemcpyAsync(h_st.data(), dstatus, P * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(ctx, hipStreamSynchronize(s));
+    }
+    // the store: members that are neither duplicates nor flagged, in piece order
+    std::vector<int32_t> h_store(P, -1), src;
+    for (int t = 0; t < pieces; ++t)
+        if ((h_st[t] & QPN_FIN_MEMBER) && !(h_st[t] & (QPN_FIN_DUP | QPN_FIN_FLAGGED))) { h_store[t] = (int32_t)src.size(); src.push_back(t); }
+    if (src.size() > scap) { ctx->last_error = "qpn_finish_pieces: more pieces to store than store_cap"; return QPN_ERR_SIZE; }
+    *stored = (int32_t)src.size();
+    HIPCHK(ctx, hipMemcpyAsync(dstore, h_store.data(), P * 4, hipMemcpyHostToDevice, s));
+    if (!src.empty()) {
+        HIPCHK(ctx, hipMemcpyAsync(dsrc, src.data(), src.size() * 4, hipMemcpyHostToDevice, s));
+        HIPCHK(ctx, qpn_launch_finish_store((int32_t)src.size(), dsrc, oc, cap, dAr, drows, drec, dnc, dtk, drsc, drdiv, dLn, dUn, dAs, dls, dus,
+                                            drows_s, s));
+    }
+    if (st.host && !src.empty()) {
+        const size_t S = src.size();
+        HIPCHK(ctx, hipMemcpyAsync(As, dAs, S * oc * cap * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(ctx, hipMemcpyAsync(ls, dls, S * cap * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(ctx, hipMemcpyAsync(us, dus, S * cap * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(ctx, hipMemcpyAsync(rows_s, drows_s, S * 4, hipMemcpyDeviceToHost, s));
+    }
+    rc = st.finish();
+    if (rc != QPN_OK) return rc;
+    HIPCHK(ctx, hipStreamSynchronize(s));                            // (the host vectors above are read by the copies)
+    return QPN_OK;
 }
 
 int qpn_local_pieces(qpn_ctx *ctx, int32_t pieces, int32_t nodes, int32_t n, int32_t m, int32_t p, const double *Qd,

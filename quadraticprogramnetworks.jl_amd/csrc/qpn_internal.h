@@ -171,8 +171,19 @@ hipError_t qpn_launch_local_pieces(int32_t batch, int32_t nodes, int32_t n, int3
 hipError_t qpn_launch_recipes(int32_t N, const uint8_t *mask, long long first, int32_t count, uint8_t *K, hipStream_t stream);
 // qpn_pieces.hip: a level's recipes / pieces with the multipliers eliminated, one call each
 hipError_t qpn_launch_recipes_batch(int32_t nodes, int32_t N, const uint8_t *masks, const long long *offsets, long long total, uint8_t *K,
-                                    int32_t *node_of, hipStream_t stream);
+                                    int32_t *node_of, hipStream_t stream, const long long *first = nullptr);
 size_t qpn_reduce_pieces_lds(int32_t n, int32_t m, int32_t p);
+// qpn_finish.hip: the finishing step of the pieces (normalise + member / merge / key, duplicates, compacted store)
+hipError_t qpn_launch_finish_norm(int32_t pieces, int32_t oc, int32_t cap, const double *Ar, const double *lr, const double *ur,
+                                  const int32_t *rows, const int32_t *flags, const int32_t *rec_of, const int32_t *ncols, const int32_t *take,
+                                  const double *xk, const double *probe, double member_tol, double *rsc, double *rdiv, double *Ln, double *Un,
+                                  int32_t *status, double *worst, unsigned long long *hash, int32_t *dup_of, hipStream_t stream);
+hipError_t qpn_launch_finish_dup(int32_t cnt, const int32_t *ord, const int32_t *pos, const int32_t *run0, int32_t oc, int32_t cap, const double *Ar,
+                                 const int32_t *rows, const int32_t *rec_of, const int32_t *ncols, const int32_t *take, const double *rsc,
+                                 const double *rdiv, const double *Ln, const double *Un, int32_t *status, int32_t *dup_of, hipStream_t stream);
+hipError_t qpn_launch_finish_store(int32_t stored, const int32_t *src, int32_t oc, int32_t cap, const double *Ar, const int32_t *rows,
+                                   const int32_t *rec_of, const int32_t *ncols, const int32_t *take, const double *rsc, const double *rdiv,
+                                   const double *Ln, const double *Un, double *As, double *ls, double *us, int32_t *rows_s, hipStream_t stream);
 hipError_t qpn_launch_reduce_pieces(int32_t pieces, int32_t n, int32_t m, int32_t p, double tol, double *Ap, const double *lp,
                                     const double *up, const uint8_t *keep, double *Ar, double *lr, double *ur, int32_t *rows_out,
                                     int32_t *flags_out, hipStream_t stream);

@@ -2,7 +2,8 @@
 // a level: the per-node map of src/algorithm.jl:44-52 meets process_solution_graph, src/avi.jl:447-477).
 //
 //   recipes_batch_kernel   all_Ks (src/avi_solutions.jl:200-215) for MANY solutions: recipe t belongs to the node b with
-//                          offsets[b] <= t < offsets[b+1] and is number t - offsets[b] of that node's Cartesian product
+//                          offsets[b] <= t < offsets[b+1] and is number t - offsets[b] (+ first[b], qpn_recipes_batch_range) of that
+//                          node's Cartesian product
 //   reduce_pieces_kernel   a local piece (local_piece, :400-496, made by local_pieces_kernel into a workspace) brought down from
 //                          [x_d; lambda; x_p] to [x_d; x_p]: every multiplier column is eliminated through the piece's own
 //                          equality rows -- the substitution of eliminate_variables (src/sets.jl:731-800), one column at a time,
@@ -18,7 +19,7 @@
 namespace {
 
 __global__ __launch_bounds__(256) void recipes_batch_kernel(int32_t nodes, int32_t N, const uint8_t *masks, const long long *offsets,
-                                                            long long total, uint8_t *K, int32_t *node_of)
+                                                            long long total, uint8_t *K, int32_t *node_of, const long long *first)
 {
     const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= total) return;
@@ -28,7 +29,7 @@ __global__ __launch_bounds__(256) void recipes_batch_kernel(int32_t nodes, int32
         if (offsets[mid] <= t) lo = mid; else hi = mid;
     }
     const int b = lo;
-    unsigned long long idx = (unsigned long long)(t - offsets[b]);
+    unsigned long long idx = (unsigned long long)(t - offsets[b] + (first ? first[b] : 0));     // (first: qpn_recipes_batch_range)
     const uint8_t *mask = masks + (size_t)b * N;
     for (int i = 0; i < N; ++i) {
         const unsigned mk = mask[i];
@@ -148,11 +149,11 @@ __global__ __launch_bounds__(256) void reduce_pieces_kernel(int32_t n, int32_t m
 } // namespace
 
 hipError_t qpn_launch_recipes_batch(int32_t nodes, int32_t N, const uint8_t *masks, const long long *offsets, long long total, uint8_t *K,
-                                    int32_t *node_of, hipStream_t stream)
+                                    int32_t *node_of, hipStream_t stream, const long long *first)
 {
     if (total <= 0) return hipSuccess;
     hipLaunchKernelGGL(recipes_batch_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, nodes, N, masks, offsets, total, K,
-                       node_of);
+                       node_of, first);
     return hipGetLastError();
 }
 

@@ -152,7 +152,7 @@ class Engine:
 
     def _alloc(self, dev, shape, dtype):
         if dev:
-            tdt = {np.float64: torch.float64, np.int32: torch.int32, np.uint8: torch.uint8}[dtype]
+            tdt = {np.float64: torch.float64, np.int32: torch.int32, np.uint8: torch.uint8, np.int64: torch.int64}[dtype]
             return torch.empty(shape, dtype=tdt, device=f"cuda:{self.device}")
         return np.empty(shape, dtype=dtype)
 
@@ -334,9 +334,10 @@ class Engine:
         return Ap, lp, up, keep
 
     # -- (F1, a level at a time) --------------------------------------------------------------------
-    def recipes_batch(self, masks, offsets):
+    def recipes_batch(self, masks, offsets, first=None):
         """all_Ks (src/avi_solutions.jl:200-215) for MANY solutions in one launch (qpn_recipes_batch): masks [nodes, N] uint8,
         offsets [nodes + 1] int64 (host; node b gets the first offsets[b+1] - offsets[b] recipes of its product).
+        first [nodes] int64 (host; qpn_recipes_batch_range): node b's recipes start at number first[b] of its product instead.
         Returns (K [total, N] uint8, node_of [total] int32)."""
         dev = self._mode(masks)
         self._bind_stream(dev)
@@ -349,10 +350,65 @@ class Engine:
         total = int(offsets[-1])
         K = self._alloc(dev, (total, N), np.uint8)
         node_of = self._alloc(dev, (total,), np.int32)
-        rc = self.lib.qpn_recipes_batch(self.ctx, nodes, N, _ptr(masks), _ptr(offsets), _ptr(K), _ptr(node_of),
-                                        MEM_DEVICE if dev else MEM_HOST)
-        self._chk(rc, "qpn_recipes_batch")
+        if first is None:
+            rc = self.lib.qpn_recipes_batch(self.ctx, nodes, N, _ptr(masks), _ptr(offsets), _ptr(K), _ptr(node_of),
+                                            MEM_DEVICE if dev else MEM_HOST)
+            self._chk(rc, "qpn_recipes_batch")
+            return K, node_of
+        first = np.ascontiguousarray(first, dtype=np.int64)
+        if first.shape != (nodes,):
+            raise ValueError("recipes_batch: first must have one entry per node")
+        rc = self.lib.qpn_recipes_batch_range(self.ctx, nodes, N, _ptr(masks), _ptr(first), _ptr(offsets), _ptr(K), _ptr(node_of),
+                                              MEM_DEVICE if dev else MEM_HOST)
+        self._chk(rc, "qpn_recipes_batch_range")
         return K, node_of
+
+    def finish_pieces(self, Ar, lr, ur, rows, flags, rec_of, ncols, take, xk, probe, n, m, member_tol=1e-5, store_cap=None):
+        """The finishing step of reduced_pieces' output (qpn_finish_pieces; level_batch.finish_pieces_host is its numpy twin):
+        piece t of item rec_of[t] over the item's columns take[k, :ncols[k]] (ascending global order), the point xk and the probe
+        vector on them ([records, n+p] each); Ar [pieces, n+p, n+2m].  Returns dict(status, worst, hash, dup_of, store_of [pieces], As [S, n+p, cap]
+        column-major, ls, us [S, cap], rows_s [S], stored = S): the store holds the members that are neither duplicates nor flagged.
+        Device inputs give device outputs (hash as int64 bits); the store then has room for store_cap (default: pieces) slots,
+        of which the first `stored` are filled."""
+        dev = self._mode(Ar, lr, ur, rows, flags, rec_of, ncols, take, xk, probe)
+        self._bind_stream(dev)
+        if not dev:
+            Ar, lr, ur, xk, probe = (self._host(a, np.float64) for a in (Ar, lr, ur, xk, probe))
+            rows, flags, rec_of, ncols, take = (self._host(a, np.int32) for a in (rows, flags, rec_of, ncols, take))
+        else:
+            self._require_dev64(Ar, lr, ur, xk, probe)
+            for t in (rows, flags, rec_of, ncols, take):
+                if t.dtype != torch.int32 or not t.is_contiguous():
+                    raise QpnError("finish_pieces: index arrays must be contiguous int32 tensors")
+        pieces, oc, cap = (int(v) for v in Ar.shape)
+        records = int(ncols.shape[0])
+        if tuple(take.shape) != (records, oc) or tuple(xk.shape) != (records, oc) or tuple(probe.shape) != (records, oc) \
+                or tuple(lr.shape) != (pieces, cap) or tuple(ur.shape) != (pieces, cap) or tuple(rows.shape) != (pieces,) \
+                or tuple(flags.shape) != (pieces,) or tuple(rec_of.shape) != (pieces,):
+            raise QpnError("finish_pieces: inconsistent shapes")
+        n, m = int(n), int(m)
+        p = oc - n
+        if cap != n + 2 * m or p < 0:
+            raise QpnError("finish_pieces: Ar must be [pieces, n + p, n + 2m]")
+        sc = pieces if store_cap is None else int(store_cap)
+        status = self._alloc(dev, (pieces,), np.int32)
+        worst = self._alloc(dev, (pieces,), np.float64)
+        hsh = self._alloc(dev, (pieces,), np.int64) if dev else np.empty(pieces, np.uint64)
+        dup_of = self._alloc(dev, (pieces,), np.int32)
+        store_of = self._alloc(dev, (pieces,), np.int32)
+        As = self._alloc(dev, (sc, oc, cap), np.float64)
+        ls = self._alloc(dev, (sc, cap), np.float64)
+        us = self._alloc(dev, (sc, cap), np.float64)
+        rows_s = self._alloc(dev, (sc,), np.int32)
+        stored = C.c_int32(0)
+        rc = self.lib.qpn_finish_pieces(self.ctx, pieces, records, n, m, p, _ptr(Ar), _ptr(lr), _ptr(ur), _ptr(rows), _ptr(flags),
+                                        _ptr(rec_of), _ptr(ncols), _ptr(take), _ptr(xk), _ptr(probe), float(member_tol), _ptr(status),
+                                        _ptr(worst), _ptr(hsh), _ptr(dup_of), _ptr(store_of), sc, _ptr(As), _ptr(ls), _ptr(us),
+                                        _ptr(rows_s), C.byref(stored), MEM_DEVICE if dev else MEM_HOST)
+        self._chk(rc, "qpn_finish_pieces")
+        S = int(stored.value)
+        return dict(status=status, worst=worst, hash=hsh, dup_of=dup_of, store_of=store_of, As=As[:S], ls=ls[:S], us=us[:S],
+                    rows_s=rows_s[:S], stored=S)
 
     def reduced_pieces(self, Qc, Rc, qd, Ac, Bc, l, u, K, node_of=None, tol=1e-9):
         """local_piece (src/avi_solutions.jl:400-496) for recipes K over node records, with the m multiplier columns eliminated

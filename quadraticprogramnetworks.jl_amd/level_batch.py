@@ -473,11 +473,192 @@ def verify_items(qpn, items, x, engine, tol=1e-4, check_convexity=False):
     return recs, batches, out
 
 
-def solution_pieces(qpn, recs, batches, rets, x, engine, want: Sequence[bool], tol=1e-2, max_pieces=64, member_tol=MEMBER_TOL):
+# The uncapped route (QPNetOptions.max_pieces = None) enumerates every recipe of a node, as the reference does
+# (src/qp_processing.jl:193-198, :231 -> all_Ks, src/avi_solutions.jl:200-215).  A node with more recipes than this is refused:
+# the route never truncates silently.
+MAX_RECIPES = 1 << 24
+# The recipes of a record batch go through the device in chunks whose reduced pieces, their workspace and the finished store
+# stay under this many bytes.
+CHUNK_BYTES = 256 << 20
+
+
+def _piece_masks(b, sel, rets, want, tol, eng):
+    """The code sets of every wanted record of a batch at (x, lambda) (comp_indices, src/avi_solutions.jl:511-562, refined by
+    _refine_row_codes) and the size of each one's recipe product."""
+    n, m = b.n, b.m
+    xd, w = b.last["xd"], b.last["w"]
+    lam = np.zeros((len(b), m))
+    for k, i in enumerate(b.where):
+        if want[i]:
+            lam[k, :b.m_true[k]] = rets[i]["lam"]
+    # the node's own GAVI at z = [x_d; lambda], w = x_p (src/avi.jl:447-477): r1 = Qd x + R w + qd - Ad' lambda, s = Ad x + B w
+    r1 = np.einsum("bji,bj->bi", b.Qc, xd) + np.einsum("bji,bj->bi", b.Rc, w) + b.qd - np.einsum("bij,bj->bi", b.Ac, lam)
+    s = np.einsum("bji,bj->bi", b.Ac, xd) + np.einsum("bji,bj->bi", b.Bc, w)
+    free_lo = np.full((len(sel), n), -INF); free_hi = np.full((len(sel), n), INF)
+    m1 = np.asarray(eng.comp_indices(xd[sel], r1[sel], free_lo, free_hi, tol=tol, shift=0))
+    m2 = np.asarray(eng.comp_indices(s[sel], lam[sel], b.l[sel], b.u[sel], tol=tol, shift=4)) if m else np.zeros((len(sel), 0), np.uint8)
+    for t, k in enumerate(sel):                          # inert padding rows: l = -inf, u = inf, lambda = 0 -> code 6 only
+        m2[t, b.m_true[k]:] = 1 << 5
+    if m:
+        m2 = _refine_row_codes(m2, s[sel], lam[sel], b.l[sel], b.u[sel], CODE_TOL)
+    masks = np.concatenate([m1, m2], axis=1).astype(np.uint8)
+    ok = ~np.any(masks == 0, axis=1)                     # a zero mask: (x, lambda) is no solution of the GAVI at this tolerance
+    pop = np.array([[bin(int(v)).count("1") for v in row] for row in masks], dtype=np.float64)
+    total = np.where(ok, np.prod(np.maximum(pop, 1.0), axis=1), 0.0)
+    return masks, total
+
+
+def _colsel(b, k):
+    """A record's piece columns [x_d; x_p present] in ascending global order, and where each sits among Ar's n + p columns."""
+    pk = np.nonzero(b.par[k] >= 0)[0]
+    cols = np.concatenate([b.dec[k], b.par[k][pk]])
+    order = np.argsort(cols, kind="stable")
+    return cols[order], np.concatenate([np.arange(b.n), b.n + pk])[order]
+
+
+def _finish_host(Ar, lr, ur, rows, plain, take_k, xk, probe):
+    """Pieces `plain` of one record (reduced_pieces' output) over the record's columns take_k in ascending global order,
+    normalised as Poly does (src/sets.jl:76-89: 1e-8 drop, leading coefficient +1); the point's worst violation per piece (xk:
+    the point on those columns); _dedupe's quick merge test; the 6-digit rounded keys.  Returns (worst, A3 [pieces, Rmax, cols],
+    L2, U2 [pieces, Rmax], merge, A6, LU6 [pieces, 2 Rmax]).  qpn_finish_pieces does the same operations in the same order."""
+    Rmax = Ar.shape[2]
+    # all of the record's pieces at once: rows over the columns in ascending order, normalised as Poly does
+    # (src/sets.jl:76-89: 1e-8 drop, leading coefficient +1), the point's worst violation per piece
+    A3 = np.ascontiguousarray(np.swapaxes(Ar[plain][:, take_k, :], 1, 2))        # [pieces, Rmax, columns]
+    L2 = lr[plain].astype(np.float64, copy=True); U2 = ur[plain].astype(np.float64, copy=True)
+    # (first to unit largest coefficient: the rows come out of the elimination at any scale -- a stationarity row of
+    #  size 1e-4 whose 1e-8 entry is dropped, then divided by a leading coefficient of 1e-6, misses its own point by
+    #  7e-3, and the parent calls the point infeasible: one pair in 5 000 at n = m = 32 cycled on exactly that)
+    big = np.max(np.abs(A3), axis=2)
+    sc = np.where(big > 0.0, 1.0 / np.where(big > 0.0, big, 1.0), 1.0)
+    A3 *= sc[..., None]
+    with np.errstate(invalid="ignore"):
+        L2 = L2 * sc; U2 = U2 * sc
+    A3[np.abs(A3) < 1e-8] = 0.0
+    nzm = A3 != 0
+    has = nzm.any(axis=2)
+    lead = np.where(has, np.take_along_axis(A3, nzm.argmax(axis=2)[..., None], axis=2)[..., 0], 1.0)
+    nrm = np.abs(lead); neg = has & (lead < 0)
+    A3 /= np.where(neg, -nrm, nrm)[..., None]
+    with np.errstate(invalid="ignore"):
+        ln, un = L2 / nrm, U2 / nrm
+    L2 = np.where(neg, -un, ln); U2 = np.where(neg, -ln, un)
+    ax = A3 @ xk
+    live = has & (np.arange(Rmax)[None, :] < rows[plain][:, None])
+    viol = np.where(live, np.maximum(L2 - ax, ax - U2), 0.0)
+    worst = np.max(viol, axis=1, initial=0.0)
+    # _dedupe's own quick test (equal normals project equally on a random vector; all-zero rows) for all pieces at once:
+    # the few that have something to merge go through it, the others are taken as they are
+    valid = np.arange(Rmax)[None, :] < rows[plain][:, None]
+    with np.errstate(invalid="ignore"):
+        hs = np.sort(np.where(valid, A3 @ probe, np.inf), axis=1)
+        close = np.diff(hs, axis=1) <= 1e-7 * (1.0 + np.abs(hs[:, 1:]))
+    merge = np.any(close & np.isfinite(hs[:, 1:]), axis=1) | np.any(valid & ~has, axis=1)
+    A6 = np.round(A3, 6) + 0.0                      # (the keys of the node's piece SET, rounded once for all pieces)
+    LU6 = np.round(np.concatenate([L2, U2], axis=1), 6)
+    return worst, A3, L2, U2, merge, A6, LU6
+
+
+_HG, _HC1, _HC2 = np.uint64(0x9E3779B97F4A7C15), np.uint64(0xBF58476D1CE4E5B9), np.uint64(0x94D049BB133111EB)
+
+
+def _fin64(z):
+    z = (z ^ (z >> np.uint64(30))) * _HC1
+    z = (z ^ (z >> np.uint64(27))) * _HC2
+    return z ^ (z >> np.uint64(31))
+
+
+def _key_hash(A6, L6, U6, r):
+    """64 bits of the keys of many pieces, as qpn_finish_pieces computes them: A6 [pieces, R, cols] the rounded rows, L6, U6
+    [pieces, R] the rounded bounds, r [pieces] the valid rows.  Word j of a key (the r x cols rows row-major, then the r lower and
+    the r upper bounds) adds fin64(bits + (j + 1) G); the sum (mod 2^64) is mixed once more with r."""
+    P, R, nc = A6.shape
+    r = np.asarray(r, dtype=np.int64)
+    i = np.arange(R, dtype=np.int64)
+    valid = i[None, :] < r[:, None]
+    with np.errstate(over="ignore"):
+        ia = (i[:, None] * nc + np.arange(nc, dtype=np.int64)[None, :] + 1).astype(np.uint64)
+        wa = _fin64(np.ascontiguousarray(A6, dtype=np.float64).view(np.uint64) + ia[None] * _HG)
+        il = (r[:, None] * nc + i[None, :] + 1).astype(np.uint64)
+        iu = (r[:, None] * nc + r[:, None] + i[None, :] + 1).astype(np.uint64)
+        wl = _fin64(np.ascontiguousarray(L6, dtype=np.float64).view(np.uint64) + il * _HG)
+        wu = _fin64(np.ascontiguousarray(U6, dtype=np.float64).view(np.uint64) + iu * _HG)
+        zero = np.uint64(0)
+        h = (np.where(valid[..., None], wa, zero).sum(axis=(1, 2), dtype=np.uint64) + np.where(valid, wl, zero).sum(axis=1, dtype=np.uint64)
+             + np.where(valid, wu, zero).sum(axis=1, dtype=np.uint64))
+        return _fin64(h ^ r.astype(np.uint64))
+
+
+def finish_pieces_host(Ar, lr, ur, rows, flags, rec_of, ncols, take, xk, probe, n, m, member_tol=MEMBER_TOL, store_cap=None):
+    """The numpy twin of Engine.finish_pieces (qpn_finish_pieces), for engines without it: _finish_host per record, then the
+    status words, hashes, duplicates and the compacted store with the ABI's meaning (include/qpn_hip.h)."""
+    Ar = np.asarray(Ar, dtype=np.float64); lr = np.asarray(lr, dtype=np.float64); ur = np.asarray(ur, dtype=np.float64)
+    rows = np.asarray(rows, dtype=np.int32); flags = np.asarray(flags, dtype=np.int32); rec_of = np.asarray(rec_of, dtype=np.int32)
+    ncols = np.asarray(ncols, dtype=np.int32); take = np.asarray(take, dtype=np.int32)
+    xk = np.asarray(xk, dtype=np.float64); probe = np.asarray(probe, dtype=np.float64)
+    P, oc, cap = Ar.shape
+    status = np.zeros(P, np.int32); worst = np.zeros(P); hsh = np.zeros(P, np.uint64); dup_of = np.full(P, -1, np.int32)
+    status[flags != 0] = 8
+    fin = {}
+    for k in np.unique(rec_of[flags == 0]).tolist():
+        plain = np.nonzero((rec_of == k) & (flags == 0))[0]
+        nc = int(ncols[k])
+        wk, A3, L2, U2, mg, A6, LU6 = _finish_host(Ar, lr, ur, rows, plain, take[k, :nc], xk[k, :nc], probe[k, :nc])
+        hsh[plain] = _key_hash(A6, LU6[:, :cap], LU6[:, cap:], rows[plain])
+        worst[plain] = wk
+        status[plain] = np.where(wk <= member_tol, 1, 0) | np.where(mg, 2, 0)
+        groups = {}
+        for j, t in enumerate(plain.tolist()):
+            fin[t] = (A3[j], L2[j], U2[j], nc)
+            if status[t] != 1:
+                continue
+            r = int(rows[t])
+            key = (A6[j, :r].tobytes(), LU6[j, :r].tobytes(), LU6[j, cap:cap + r].tobytes())
+            for t2, key2 in groups.setdefault(int(hsh[t]), []):
+                if key2 == key:
+                    dup_of[t] = t2; status[t] |= 4
+                    break
+            else:
+                groups[int(hsh[t])].append((t, key))
+    src = [t for t in range(P) if (status[t] & 1) and not (status[t] & 12)]
+    S = len(src)
+    if store_cap is not None and S > store_cap:
+        raise RuntimeError("finish_pieces: more pieces to store than store_cap")
+    store_of = np.full(P, -1, np.int32)
+    As = np.zeros((S, oc, cap)); ls = np.zeros((S, cap)); us = np.zeros((S, cap)); rows_s = np.zeros(S, np.int32)
+    for q, t in enumerate(src):
+        A3t, L2t, U2t, nc = fin[t]
+        store_of[t] = q; As[q, :nc, :] = A3t.T; ls[q] = L2t; us[q] = U2t; rows_s[q] = rows[t]
+    return dict(status=status, worst=worst, hash=hsh, dup_of=dup_of, store_of=store_of, As=As, ls=ls, us=us, rows_s=rows_s, stored=S)
+
+
+def _recipes_range_host(masks, first, counts):
+    """qpn_recipes_batch_range restated (engines whose recipes_batch has no `first`): node b's recipes first[b] .. first[b] +
+    counts[b] - 1 of its Cartesian product, row 0 the fastest digit."""
+    masks = np.asarray(masks, dtype=np.uint8)
+    nodes, N = masks.shape
+    K = np.zeros((int(np.sum(counts)), N), np.uint8); node_of = np.repeat(np.arange(nodes, dtype=np.int32), counts)
+    o = 0
+    for b in range(nodes):
+        cnt = int(counts[b])
+        idx = int(first[b]) + np.arange(cnt, dtype=np.int64)
+        for i in range(N):
+            codes = np.array([c + 1 for c in range(8) if (int(masks[b, i]) >> c) & 1], dtype=np.uint8)
+            if codes.size:
+                K[o:o + cnt, i] = codes[idx % codes.size]; idx = idx // codes.size
+        o += cnt
+    return K, node_of
+
+
+def solution_pieces(qpn, recs, batches, rets, x, engine, want: Sequence[bool], tol=1e-2, max_pieces=64, member_tol=MEMBER_TOL,
+                    truncated=None, _chunk=None):
     """The solution-graph pieces of MANY nodes around (x, lambda) (process_solution_graph, src/avi.jl:447-477 ->
     comp_indices -> all_Ks, src/avi_solutions.jl:200-215 -> local_piece, :400-496 -> the multipliers eliminated, the
     columns permuted back, :86-87), batched: per record shape one comp_indices pair, one recipes call, one pieces call.
-    Returns a list (per item; None where `want` is False) of lists of Poly in global coordinates."""
+    Returns a list (per item; None where `want` is False) of lists of Poly in global coordinates.
+    max_pieces: the first that many recipes of each item (a UserWarning names an item that has more; its index goes into the
+    set `truncated` when one is given); None: every recipe, chunk by chunk (_chunk overrides the chunk size), finished on the
+    device when the engine has finish_pieces (its numpy twin otherwise)."""
     from .avi_solutions import _dedupe, _probe_vector
     eng = engine
     x = np.asarray(x, dtype=np.float64)
@@ -487,30 +668,17 @@ def solution_pieces(qpn, recs, batches, rets, x, engine, want: Sequence[bool], t
         if not sel:
             continue
         n, m, p = b.n, b.m, b.p
-        xd, w = b.last["xd"], b.last["w"]
-        lam = np.zeros((len(b), m))
-        for k, i in enumerate(b.where):
-            if want[i]:
-                lam[k, :b.m_true[k]] = rets[i]["lam"]
-        # the node's own GAVI at z = [x_d; lambda], w = x_p (src/avi.jl:447-477): r1 = Qd x + R w + qd - Ad' lambda, s = Ad x + B w
-        r1 = np.einsum("bji,bj->bi", b.Qc, xd) + np.einsum("bji,bj->bi", b.Rc, w) + b.qd - np.einsum("bij,bj->bi", b.Ac, lam)
-        s = np.einsum("bji,bj->bi", b.Ac, xd) + np.einsum("bji,bj->bi", b.Bc, w)
-        free_lo = np.full((len(sel), n), -INF); free_hi = np.full((len(sel), n), INF)
-        m1 = np.asarray(eng.comp_indices(xd[sel], r1[sel], free_lo, free_hi, tol=tol, shift=0))
-        m2 = np.asarray(eng.comp_indices(s[sel], lam[sel], b.l[sel], b.u[sel], tol=tol, shift=4)) if m else np.zeros((len(sel), 0), np.uint8)
-        for t, k in enumerate(sel):                          # inert padding rows: l = -inf, u = inf, lambda = 0 -> code 6 only
-            m2[t, b.m_true[k]:] = 1 << 5
-        if m:
-            m2 = _refine_row_codes(m2, s[sel], lam[sel], b.l[sel], b.u[sel], CODE_TOL)
-        masks = np.concatenate([m1, m2], axis=1).astype(np.uint8)
-        ok = ~np.any(masks == 0, axis=1)                     # a zero mask: (x, lambda) is no solution of the GAVI at this tolerance
-        pop = np.array([[bin(int(v)).count("1") for v in row] for row in masks], dtype=np.float64)
-        total = np.where(ok, np.prod(np.maximum(pop, 1.0), axis=1), 0.0)
+        masks, total = _piece_masks(b, sel, rets, want, tol, eng)
+        if max_pieces is None:
+            _pieces_uncapped(qpn, recs, b, sel, masks, total, x, eng, member_tol, out, _chunk)
+            continue
         counts = np.minimum(total, max_pieces).astype(np.int64)
         for t, k in enumerate(sel):
             if total[t] > max_pieces:
                 warnings.warn(f"node {recs[b.where[k]]['pid']}: {int(total[t])} local recipes, only the first {max_pieces} "
                               "are expanded (max_pieces)")
+                if truncated is not None:
+                    truncated.add(b.where[k])
         offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
         if offsets[-1] == 0:
             for k in sel:
@@ -523,12 +691,7 @@ def solution_pieces(qpn, recs, batches, rets, x, engine, want: Sequence[bool], t
         Ar = np.asarray(Ar); lr = np.asarray(lr); ur = np.asarray(ur); rows = np.asarray(rows); flags = np.asarray(flags)
         for k in sel:
             out[b.where[k]] = []
-        colsel = {}                                          # per record: the piece's columns [x_d; x_p present] in ascending order
-        for k in sel:
-            pk = np.nonzero(b.par[k] >= 0)[0]
-            cols = np.concatenate([b.dec[k], b.par[k][pk]])
-            order = np.argsort(cols, kind="stable")
-            colsel[k] = (cols[order], np.concatenate([np.arange(n), n + pk])[order])
+        colsel = {k: _colsel(b, k) for k in sel}             # per record: the piece's columns [x_d; x_p present] in ascending order
         seen = {b.where[k]: set() for k in sel}
         fallback = {}                                        # per node: the piece the point misses least, for a node none of whose
                                                              # pieces passes (a solution graph is never empty, src/qp_processing.jl:233)
@@ -537,8 +700,7 @@ def solution_pieces(qpn, recs, batches, rets, x, engine, want: Sequence[bool], t
             # a piece the point fails here would be "infeasible" there by construction (MEMBER_TOL)
             if miss <= member_tol:
                 if key is None:
-                    cl, Al_ = Pg.local()
-                    key = (cl.tobytes(), (np.round(Al_, 6) + 0.0).tobytes(), np.round(np.concatenate([Pg.l, Pg.u]), 6).tobytes())
+                    key = _poly_key(Pg)
                 if key not in seen[i]:                       # the reference collects the pieces in a Set (src/avi_solutions.jl:104)
                     seen[i].add(key)
                     out[i].append(Pg)
@@ -556,40 +718,7 @@ def solution_pieces(qpn, recs, batches, rets, x, engine, want: Sequence[bool], t
             plain = ts[flags[t0:t1] == 0]
             miss_of = {}
             if plain.size:
-                # all of the record's pieces at once: rows over the columns in ascending order, normalised as Poly does
-                # (src/sets.jl:76-89: 1e-8 drop, leading coefficient +1), the point's worst violation per piece
-                A3 = np.ascontiguousarray(np.swapaxes(Ar[plain][:, take_k, :], 1, 2))        # [pieces, Rmax, columns]
-                L2 = lr[plain].astype(np.float64, copy=True); U2 = ur[plain].astype(np.float64, copy=True)
-                # (first to unit largest coefficient: the rows come out of the elimination at any scale -- a stationarity row of
-                #  size 1e-4 whose 1e-8 entry is dropped, then divided by a leading coefficient of 1e-6, misses its own point by
-                #  7e-3, and the parent calls the point infeasible: one pair in 5 000 at n = m = 32 cycled on exactly that)
-                big = np.max(np.abs(A3), axis=2)
-                sc = np.where(big > 0.0, 1.0 / np.where(big > 0.0, big, 1.0), 1.0)
-                A3 *= sc[..., None]
-                with np.errstate(invalid="ignore"):
-                    L2 = L2 * sc; U2 = U2 * sc
-                A3[np.abs(A3) < 1e-8] = 0.0
-                nzm = A3 != 0
-                has = nzm.any(axis=2)
-                lead = np.where(has, np.take_along_axis(A3, nzm.argmax(axis=2)[..., None], axis=2)[..., 0], 1.0)
-                nrm = np.abs(lead); neg = has & (lead < 0)
-                A3 /= np.where(neg, -nrm, nrm)[..., None]
-                with np.errstate(invalid="ignore"):
-                    ln, un = L2 / nrm, U2 / nrm
-                L2 = np.where(neg, -un, ln); U2 = np.where(neg, -ln, un)
-                ax = A3 @ x[cols_k]
-                live = has & (np.arange(Rmax)[None, :] < rows[plain][:, None])
-                viol = np.where(live, np.maximum(L2 - ax, ax - U2), 0.0)
-                worst = np.max(viol, axis=1, initial=0.0)
-                # _dedupe's own quick test (equal normals project equally on a random vector; all-zero rows) for all pieces at once:
-                # the few that have something to merge go through it, the others are taken as they are
-                valid = np.arange(Rmax)[None, :] < rows[plain][:, None]
-                with np.errstate(invalid="ignore"):
-                    hs = np.sort(np.where(valid, A3 @ _probe_vector(A3.shape[2]), np.inf), axis=1)
-                    close = np.diff(hs, axis=1) <= 1e-7 * (1.0 + np.abs(hs[:, 1:]))
-                merge = np.any(close & np.isfinite(hs[:, 1:]), axis=1) | np.any(valid & ~has, axis=1)
-                A6 = np.round(A3, 6) + 0.0                      # (the keys of the node's piece SET, rounded once for all pieces)
-                LU6 = np.round(np.concatenate([L2, U2], axis=1), 6)
+                worst, A3, L2, U2, merge, A6, LU6 = _finish_host(Ar, lr, ur, rows, plain, take_k, x[cols_k], _probe_vector(len(cols_k)))
                 ckey = cols_k.tobytes()
                 for j, t in enumerate(plain.tolist()):
                     r = int(rows[t])
@@ -597,16 +726,9 @@ def solution_pieces(qpn, recs, batches, rets, x, engine, want: Sequence[bool], t
                     miss_of[t] = (float(worst[j]), A3[j, :r].copy(), L2[j, :r].copy(), U2[j, :r].copy(), bool(merge[j]), key)
             for t in ts.tolist():
                 if flags[t]:
-                    P = _reduce_on_host(b, k, np.asarray(K)[t], eng)
-                    if P is None:
-                        continue
-                    Ah = np.ascontiguousarray(P[0][:, take_k]); big = np.max(np.abs(Ah), axis=1, initial=0.0)
-                    sc = np.where(big > 0.0, 1.0 / np.where(big > 0.0, big, 1.0), 1.0)
-                    with np.errstate(invalid="ignore"):
-                        Pg = _dedupe(Poly.from_sorted(qpn.num_vars, cols_k, Ah * sc[:, None], P[1] * sc, P[2] * sc))
-                    cl, Al_ = Pg.local()
-                    axp = Al_ @ x[cl]
-                    admit(i, Pg, float(np.max(np.maximum(Pg.l - axp, axp - Pg.u), initial=0.0)))
+                    Pg, miss = _flagged_piece(qpn, b, k, np.asarray(K)[t], eng, cols_k, take_k, x)
+                    if Pg is not None:
+                        admit(i, Pg, miss)
                 else:
                     miss, Aj, lj, uj, mg, key = miss_of[t]
                     Pg = Poly.from_sorted(qpn.num_vars, cols_k, Aj, lj, uj, normalise=False)
@@ -615,6 +737,161 @@ def solution_pieces(qpn, recs, batches, rets, x, engine, want: Sequence[bool], t
             if not out[i]:
                 out[i].append(Pg)
     return out
+
+
+def _poly_key(Pg):
+    """The key of a piece in its node's piece set: columns, rows rounded to 6 digits (no negative zeros), bounds rounded."""
+    cl, Al_ = Pg.local()
+    return (cl.tobytes(), (np.round(Al_, 6) + 0.0).tobytes(), np.round(np.concatenate([Pg.l, Pg.u]), 6).tobytes())
+
+
+def _flagged_piece(qpn, b, k, Krow, eng, cols_k, take_k, x):
+    """A piece the device elimination flagged, through the host restatement, normalised and merged; (Poly, miss) or (None, None)."""
+    from .avi_solutions import _dedupe
+    P = _reduce_on_host(b, k, Krow, eng)
+    if P is None:
+        return None, None
+    Ah = np.ascontiguousarray(P[0][:, take_k]); big = np.max(np.abs(Ah), axis=1, initial=0.0)
+    sc = np.where(big > 0.0, 1.0 / np.where(big > 0.0, big, 1.0), 1.0)
+    with np.errstate(invalid="ignore"):
+        Pg = _dedupe(Poly.from_sorted(qpn.num_vars, cols_k, Ah * sc[:, None], P[1] * sc, P[2] * sc))
+    cl, Al_ = Pg.local()
+    axp = Al_ @ x[cl]
+    return Pg, float(np.max(np.maximum(Pg.l - axp, axp - Pg.u), initial=0.0))
+
+
+def _supports_first(eng):
+    import inspect
+    try:
+        return "first" in inspect.signature(eng.recipes_batch).parameters
+    except (TypeError, ValueError):
+        return False
+
+
+def _pieces_uncapped(qpn, recs, b, sel, masks, total, x, eng, member_tol, out, chunk):
+    """Every recipe of the wanted records of batch b (max_pieces = None), in chunks of at most `chunk` pieces across the records'
+    concatenated recipes.  With an engine that has finish_pieces the batch's records go to the device once, the reduced pieces
+    stay there, and only the finished store and the per-piece words come back; otherwise finish_pieces_host does the same on
+    the host.  The pieces are admitted in recipe order exactly as the capped route admits them."""
+    from .avi_solutions import _dedupe, _probe_vector
+    n, m, p = b.n, b.m, b.p
+    for t, k in enumerate(sel):
+        if total[t] > MAX_RECIPES:
+            raise RuntimeError(f"node {recs[b.where[k]]['pid']}: {int(total[t])} local recipes, more than the 2^24 the uncapped "
+                               "solution graph (max_pieces=None) enumerates")
+    for k in sel:
+        out[b.where[k]] = []
+    counts = total.astype(np.int64)
+    G = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    if G[-1] == 0:
+        return
+    oc, cap, N = n + p, n + 2 * m, n + m
+    if chunk is None:
+        # per piece: K, reduced_pieces' output and its local-piece workspace, finish_pieces' scratch and store
+        per = N + 8 * (2 * (oc * cap + 2 * cap + 1) + 2 * N * (N + p) + 4 * N + 4 * cap + 4) + 64
+        chunk = max(1, CHUNK_BYTES // per)
+    dev = callable(getattr(eng, "finish_pieces", None)) and getattr(eng, "device", -1) >= 0
+    ranged = _supports_first(eng)
+    nb = len(b)
+    colsel = {k: _colsel(b, k) for k in sel}
+    take = np.zeros((nb, oc), np.int32); ncols = np.zeros(nb, np.int32); xk = np.zeros((nb, oc)); probe = np.zeros((nb, oc))
+    for k in sel:
+        cols_k, take_k = colsel[k]
+        nc = len(cols_k)
+        ncols[k] = nc; take[k, :nc] = take_k; xk[k, :nc] = x[cols_k]; probe[k, :nc] = _probe_vector(nc)
+    if dev:
+        import torch
+        dv = f"cuda:{eng.device}"
+        to = lambda a, dt=torch.float64: torch.as_tensor(np.ascontiguousarray(a), dtype=dt, device=dv)
+        recd = tuple(to(a) for a in (b.Qc, b.Rc, b.qd, b.Ac, b.Bc, b.l, b.u))      # the records go up once per batch
+        fin_in = (to(ncols, torch.int32), to(take, torch.int32), to(xk), to(probe))
+        masks_d = to(masks, torch.uint8)
+    seen = {b.where[k]: {} for k in sel}                 # per node: (columns, hash) -> the exact keys of its pieces
+    fallback = {}                                        # per node: (miss, Poly or the reduced piece to finish, record)
+    members = {b.where[k]: False for k in sel}
+
+    def admit(i, Pg, miss, key=None, h=None):
+        if miss <= member_tol:
+            members[i] = True
+            if key is None:
+                key = _poly_key(Pg)
+                cl, Al_ = Pg.local()
+                L6 = np.round(Pg.l, 6)[None]; U6 = np.round(Pg.u, 6)[None]
+                h = int(_key_hash((np.round(Al_, 6) + 0.0)[None], L6, U6, [Al_.shape[0]])[0])
+            bucket = seen[i].setdefault((key[0], h), [])
+            if key not in bucket:                        # the reference collects the pieces in a Set (src/avi_solutions.jl:104)
+                bucket.append(key)
+                out[i].append(Pg)
+        elif i not in fallback or miss < fallback[i][0]:
+            fallback[i] = (miss, Pg)
+
+    sel_a = np.asarray(sel, dtype=np.int32)
+    for c0 in range(0, int(G[-1]), chunk):
+        c1 = min(c0 + chunk, int(G[-1]))
+        lo = np.maximum(G[:-1], c0); hi = np.minimum(G[1:], c1)
+        part = np.nonzero(hi > lo)[0]                    # the wanted records with recipes in this chunk
+        first = (lo[part] - G[:-1][part]).astype(np.int64); cnt = (hi[part] - lo[part]).astype(np.int64)
+        offsets = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)
+        rec_of = np.repeat(sel_a[part], cnt)             # recipe -> record inside the batch (records ascend)
+        if dev:
+            K, _ = eng.recipes_batch(masks_d[torch.as_tensor(part, device=dv)].contiguous(), offsets, first=first)
+            rec_d = to(rec_of, torch.int32)
+            Ar, lr, ur, rows, flags = eng.reduced_pieces(*recd, K, rec_d)
+            fin = eng.finish_pieces(Ar, lr, ur, rows, flags, rec_d, *fin_in, n, m, member_tol=member_tol)
+            st = fin["status"].cpu().numpy(); worst = fin["worst"].cpu().numpy()
+            hsh = fin["hash"].cpu().numpy().view(np.uint64); store_of = fin["store_of"].cpu().numpy()
+            As = fin["As"].cpu().numpy(); ls = fin["ls"].cpu().numpy(); us = fin["us"].cpu().numpy(); rows_s = fin["rows_s"].cpu().numpy()
+            Kh = None
+        else:
+            if ranged:
+                K, _ = eng.recipes_batch(masks[part], offsets, first=first)
+            else:
+                K, _ = _recipes_range_host(masks[part], first, cnt)
+            Kh = np.asarray(K)
+            Ar, lr, ur, rows, flags = eng.reduced_pieces(b.Qc, b.Rc, b.qd, b.Ac, b.Bc, b.l, b.u, Kh, rec_of)
+            Ar = np.asarray(Ar); lr = np.asarray(lr); ur = np.asarray(ur)
+            fin = finish_pieces_host(Ar, lr, ur, rows, flags, rec_of, ncols, take, xk, probe, n, m, member_tol=member_tol)
+            st, worst, hsh, store_of = fin["status"], fin["worst"], fin["hash"], fin["store_of"]
+            As, ls, us, rows_s = fin["As"], fin["ls"], fin["us"], fin["rows_s"]
+        for q, k in enumerate(sel_a[part].tolist()):
+            i = b.where[k]
+            cols_k, take_k = colsel[k]
+            nc = len(cols_k); ckey = cols_k.tobytes()
+            for t in range(int(offsets[q]), int(offsets[q + 1])):
+                s_ = int(st[t])
+                if s_ & 8:                               # flagged: the host restatement, as on the capped route
+                    Krow = Kh[t] if Kh is not None else K[t].cpu().numpy()
+                    Pg, miss = _flagged_piece(qpn, b, k, Krow, eng, cols_k, take_k, x)
+                    if Pg is not None:
+                        admit(i, Pg, miss)
+                elif s_ & 1:
+                    if s_ & 4:                           # an equal earlier piece of this chunk is in the set already
+                        continue
+                    j = int(store_of[t]); r = int(rows_s[j])
+                    Aj = np.ascontiguousarray(As[j, :nc, :r].T); lj = ls[j, :r].copy(); uj = us[j, :r].copy()
+                    Pg = Poly.from_sorted(qpn.num_vars, cols_k, Aj, lj, uj, normalise=False)
+                    if s_ & 2:
+                        admit(i, _dedupe(Pg), 0.0)
+                    else:
+                        key = (ckey, (np.round(Aj, 6) + 0.0).tobytes(), np.round(np.concatenate([lj, uj]), 6).tobytes())
+                        admit(i, Pg, 0.0, key, int(hsh[t]))
+                elif not members[i] and (i not in fallback or float(worst[t]) < fallback[i][0]):
+                    # a candidate for the node without member pieces: kept reduced, finished only if it is still needed
+                    piece = tuple(np.asarray(a[t:t + 1].cpu() if dev else a[t:t + 1]) for a in (Ar, lr, ur, rows))
+                    fallback[i] = (float(worst[t]), piece, k, bool(s_ & 2))
+    for i, ent in fallback.items():
+        if out[i]:
+            continue
+        miss, Pg = ent[0], ent[1]
+        if not isinstance(Pg, Poly):                     # the reduced piece, finished on the host now (bit-equal to the device)
+            Ar1, lr1, ur1, rows1 = Pg
+            k, mg = ent[2], ent[3]
+            cols_k, take_k = colsel[k]
+            _, A3, L2, U2, _, _, _ = _finish_host(Ar1, lr1, ur1, rows1, np.zeros(1, np.int64), take_k, x[cols_k], _probe_vector(len(cols_k)))
+            r = int(rows1[0])
+            Pg = Poly.from_sorted(qpn.num_vars, cols_k, A3[0, :r].copy(), L2[0, :r].copy(), U2[0, :r].copy(), normalise=False)
+            Pg = _dedupe(Pg) if mg else Pg
+        out[i].append(Pg)
 
 
 def _refine_row_codes(m2, s, lam, l, u, mt):
@@ -711,14 +988,15 @@ def process_level(qpn, players: Sequence[int], x, S: Dict[int, list], engine=Non
                                 subpiece_assignments={j: ji for j, ji in zip(children, combos[fail])} if children else {})
             continue
         gen = (pid not in qpn.network_depth_map[1]) or qpn.options.gen_solution_map
-        results[pid] = dict(solution=True, S=None, failed=False)
+        results[pid] = dict(solution=True, S=None, failed=False, truncated=False)
         if pid in hits:
             continue
         if gen:
             for t in range(len(combos)):
                 want[i0 + t] = True
     if any(want):
-        pieces = solution_pieces(qpn, recs, batches, rets, x, eng, want)
+        cut = set()                                                                 # items whose graph the cap cut short
+        pieces = solution_pieces(qpn, recs, batches, rets, x, eng, want, max_pieces=qpn.options.max_pieces, truncated=cut)
         jobs, job_pid = [], []
         for pid in players:
             children, combos = combos_of[pid]
@@ -726,6 +1004,7 @@ def process_level(qpn, players: Sequence[int], x, S: Dict[int, list], engine=Non
             if not want[i0]:
                 continue
             per_combo = [pieces[i0 + t] for t in range(len(combos))]
+            results[pid]["truncated"] = any(i0 + t in cut for t in range(len(combos)))
             if len(combos) == 1:
                 results[pid]["S"] = per_combo[0]                                    # combine(...) with one solution set, :271-272
             else:

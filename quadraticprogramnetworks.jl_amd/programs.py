@@ -10,7 +10,7 @@ from __future__ import annotations
 
 import warnings
 from dataclasses import dataclass, field
-from typing import Dict, List, Set
+from typing import Dict, List, Optional, Set
 
 import numpy as np
 
@@ -267,6 +267,9 @@ class QPNetOptions:
     check_convexity: bool = False
     check_for_cycling: bool = True
     perturb_to_continue: bool = True
+    # not in the reference, which builds every node's whole solution graph (src/qp_processing.jl:193-198, :231): the recipes a
+    # node's graph is built from, per sub-piece combination (level_batch.solution_pieces).  None = every recipe, as the reference.
+    max_pieces: Optional[int] = 64
 
 
 class QPNet:
