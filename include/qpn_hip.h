@@ -409,6 +409,27 @@ int qpn_verify_nodes(qpn_ctx *ctx, int32_t batch, int32_t n, int32_t m, int32_t 
 int qpn_convexity_nodes(qpn_ctx *ctx, int32_t batch, int32_t n, int32_t m, const double *Qd, const double *Ad,
                         const uint8_t *eq, double tol, int32_t *convex, double *min_eig, int32_t *null_dim, int mem);
 
+/* ---- multiplier-vertex exploration, QPNetOptions.exploration_vertices (src/avi_solutions.jl:92-129, :241-382) ----------
+ * qpn_multiplier_vertices: per item, vertices of Lambda = { lambda : Ad' lambda = g, per-row class } -- the multiplier set of a
+ *   node at a point.  Ad [batch][m][n] column-major as above (so Ad' is [n][m] row-major), g [batch][n], cls [batch][m] uint8
+ *   (QPN_MV_GE: lambda_j >= 0, QPN_MV_LE: <= 0, QPN_MV_FREE, QPN_MV_ZERO: lambda_j = 0), lam0 [batch][m] the multiplier the
+ *   walk starts from (purified to a vertex).  Up to V vertices, distinct after rounding to 5 digits, in the breadth-first order
+ *   of a walk over adjacent bases (every tied leaving row, 2^-30 relative tie band; each basis factored afresh), at most
+ *   max_bases bases per item.  tol: pivot and zero tolerance on the row-equilibrated system (1e-9); feas: a sign-constrained
+ *   basic value down to -feas (times max(1, |rhs|)) counts as feasible (1e-6).  Outputs verts [batch][V][m] (unused slots 0),
+ *   count [batch], status [batch] (QPN_MV_*).  1 <= n, m <= 512 (QPN_ERR_SIZE beyond).  n, m <= 32: one wavefront per item;
+ *   up to 128: one workgroup per item in LDS; beyond: one workgroup per item over a global workspace.
+ * qpn_recipe_filter: recipes K [pieces][N] (codes 1..8) of product rows vrow_of [pieces] (int32) of masks [rows][N]; first_of
+ *   [rows] (int32) = the first row of the same item.  keep [pieces] uint8 = 0 when an earlier row s (first_of[v] <= s < v) of
+ *   the recipe's item holds every one of its codes (the reference's setdiff with the explored recipes), 1 otherwise. */
+enum { QPN_MV_GE = 0, QPN_MV_LE = 1, QPN_MV_FREE = 2, QPN_MV_ZERO = 3 };
+enum { QPN_MV_COMPLETE = 0, QPN_MV_VERTEX_BUDGET = 1, QPN_MV_BASIS_BUDGET = 2, QPN_MV_EMPTY = 3, QPN_MV_NO_VERTEX = 4 };
+int qpn_multiplier_vertices(qpn_ctx *ctx, int32_t batch, int32_t n, int32_t m, const double *Ad, const double *g, const uint8_t *cls,
+                            const double *lam0, int32_t V, int32_t max_bases, double tol, double feas, double *verts, int32_t *count,
+                            int32_t *status, int mem);
+int qpn_recipe_filter(qpn_ctx *ctx, int32_t pieces, int32_t rows, int32_t N, const uint8_t *masks, const uint8_t *K,
+                      const int32_t *vrow_of, const int32_t *first_of, uint8_t *keep, int mem);
+
 #ifdef __cplusplus
 }
 #endif

@@ -207,6 +207,41 @@ function convexity_nodes(Qd::Array{Float64,3}, Ad::Array{Float64,3}, eq::Matrix{
     (convex, min_eig, null_dim)
 end
 
+"""
+    multiplier_vertices(Ad, g, cls, lam0, V; max_bases=64V, tol=1e-9, feas=1e-6) -> (verts, count, status)
+
+Vertices of the multiplier sets {lambda : Ad' lambda = g, per-row class} of a batch (qpn_multiplier_vertices): Ad [m, n, batch],
+g [n, batch], cls [m, batch] (0 >= 0, 1 <= 0, 2 free, 3 = 0), lam0 [m, batch] the start.  verts [m, V, batch], count and
+status [batch] (0 complete, 1 vertex budget, 2 basis budget, 3 empty, 4 no vertex).
+"""
+function multiplier_vertices(Ad::Array{Float64,3}, g::Matrix{Float64}, cls::Matrix{UInt8}, lam0::Matrix{Float64}, V::Integer;
+                             max_bases::Integer = 64V, tol::Float64 = 1e-9, feas::Float64 = 1e-6)
+    m, n, batch = size(Ad)
+    verts = zeros(m, V, batch); count = zeros(Int32, batch); status = zeros(Int32, batch)
+    rc = ccall((:qpn_multiplier_vertices, LIB), Cint,
+               (Ptr{Cvoid}, Int32, Int32, Int32, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{UInt8}, Ptr{Cdouble}, Int32, Int32, Cdouble, Cdouble,
+                Ptr{Cdouble}, Ptr{Int32}, Ptr{Int32}, Cint),
+               ctx(), batch, n, m, Ad, g, cls, lam0, V, max_bases, tol, feas, verts, count, status, QPN_MEM_HOST)
+    rc == 0 || error("qpn_multiplier_vertices failed ($rc)")
+    (verts, count, status)
+end
+
+"""
+    recipe_filter(masks, K, vrow_of, first_of) -> keep
+
+qpn_recipe_filter: masks [N, rows], K [N, pieces] (codes 1..8), vrow_of [pieces] and first_of [rows] (0-based rows, Int32).
+keep[t] = 0 when an earlier row of the recipe's item holds every one of its codes.
+"""
+function recipe_filter(masks::Matrix{UInt8}, K::Matrix{UInt8}, vrow_of::Vector{Int32}, first_of::Vector{Int32})
+    N, rows = size(masks); pieces = size(K, 2)
+    keep = zeros(UInt8, pieces)
+    rc = ccall((:qpn_recipe_filter, LIB), Cint,
+               (Ptr{Cvoid}, Int32, Int32, Int32, Ptr{UInt8}, Ptr{UInt8}, Ptr{Int32}, Ptr{Int32}, Ptr{UInt8}, Cint),
+               ctx(), pieces, rows, N, masks, K, vrow_of, first_of, keep, QPN_MEM_HOST)
+    rc == 0 || error("qpn_recipe_filter failed ($rc)")
+    keep
+end
+
 function verify_nodes(nodes::Nodes, xd::Matrix{Float64}, w::VecOrMat{Float64}; tol::Float64 = 1e-4)
     solution = zeros(Int32, nodes.batch); path = zeros(Int32, nodes.batch); lambda = zeros(max(nodes.m, 1), nodes.batch)
     rc = ccall((:qpn_verify_nodes_h, LIB), Cint,

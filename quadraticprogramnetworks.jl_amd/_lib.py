@@ -22,6 +22,7 @@ ABI_SYMBOLS = (
     "qpn_nodes_upload", "qpn_nodes_update", "qpn_nodes_set_schedule", "qpn_nodes_free", "qpn_nodes_info", "qpn_solve_nodes_h",
     "qpn_verify_nodes_h", "qpn_pool_size", "qpn_assemble_pools", "qpn_local_pieces", "qpn_recipes_from_masks",
     "qpn_recipes_batch", "qpn_reduced_pieces", "qpn_convexity_nodes", "qpn_recipes_batch_range", "qpn_finish_pieces",
+    "qpn_multiplier_vertices", "qpn_recipe_filter",
 )
 
 MEM_HOST, MEM_DEVICE = 0, 1
@@ -133,6 +134,9 @@ def load_library():
     lib.qpn_finish_pieces.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                       C.c_double, vp, vp, vp, vp, vp, C.c_int32, vp, vp, vp, vp, C.POINTER(C.c_int32), C.c_int]
     lib.qpn_convexity_nodes.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, C.c_double, vp, vp, vp, C.c_int]
+    lib.qpn_multiplier_vertices.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_double,
+                                            C.c_double, vp, vp, vp, C.c_int]
+    lib.qpn_recipe_filter.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, C.c_int]
     del dp, ip, bp
     _lib = lib
     return lib

@@ -1497,6 +1497,52 @@ int qpn_convexity_nodes(qpn_ctx *ctx, int32_t batch, int32_t n, int32_t m, const
     return st.finish();
 }
 
+int qpn_multiplier_vertices(qpn_ctx *ctx, int32_t batch, int32_t n, int32_t m, const double *Ad, const double *g, const uint8_t *cls,
+                            const double *lam0, int32_t V, int32_t max_bases, double tol, double feas, double *verts, int32_t *count,
+                            int32_t *status, int mem)
+{
+    if (!ctx) return QPN_ERR_ARG;
+    if (batch < 0 || n <= 0 || m <= 0 || V <= 0 || max_bases <= 0) return fail_arg(ctx, "qpn_multiplier_vertices: bad sizes");
+    if (n > qpn_verify_max_dim() || m > qpn_verify_max_dim()) {
+        ctx->last_error = "qpn_multiplier_vertices: n, m <= 512 in ABI v1";
+        return QPN_ERR_SIZE;
+    }
+    if (!Ad || !g || !cls || !lam0 || !verts || !count || !status) return fail_arg(ctx, "qpn_multiplier_vertices: null pointer");
+    Stage st(ctx, mem, "qpn_multiplier_vertices");
+    if (int rc = st.check()) return rc;
+    if (batch == 0) return QPN_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const double *dA, *dg, *dl; const uint8_t *dc; double *dv; int32_t *dcnt, *dst; void *ws;
+    st.in(dA, Ad, (size_t)batch * n * m * 8); st.in(dg, g, (size_t)batch * n * 8); st.in(dc, cls, (size_t)batch * m);
+    st.in(dl, lam0, (size_t)batch * m * 8);
+    st.out(dv, verts, (size_t)batch * V * m * 8); st.out(dcnt, count, (size_t)batch * 4); st.out(dst, status, (size_t)batch * 4);
+    st.scratch(ws, qpn_multiplier_vertices_workspace_bytes(batch, n, m, max_bases));
+    int rc = st.begin();
+    if (rc != QPN_OK) return rc;
+    HIPCHK(ctx, hipMemsetAsync(dv, 0, (size_t)batch * V * m * 8, ctx->stream));
+    HIPCHK(ctx, qpn_launch_multiplier_vertices(batch, n, m, dA, dg, dc, dl, V, max_bases, tol, feas, dv, dcnt, dst, ws, ctx->stream));
+    return st.finish();
+}
+
+int qpn_recipe_filter(qpn_ctx *ctx, int32_t pieces, int32_t rows, int32_t N, const uint8_t *masks, const uint8_t *K,
+                      const int32_t *vrow_of, const int32_t *first_of, uint8_t *keep, int mem)
+{
+    if (!ctx) return QPN_ERR_ARG;
+    if (pieces < 0 || rows < 0 || N <= 0) return fail_arg(ctx, "qpn_recipe_filter: bad sizes");
+    if (pieces > 0 && (!masks || !K || !vrow_of || !first_of || !keep || rows == 0)) return fail_arg(ctx, "qpn_recipe_filter: null pointer");
+    Stage st(ctx, mem, "qpn_recipe_filter");
+    if (int rc = st.check()) return rc;
+    if (pieces == 0) return QPN_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const uint8_t *dm, *dK; const int32_t *dvr, *dfo; uint8_t *dk;
+    st.in(dm, masks, (size_t)rows * N); st.in(dK, K, (size_t)pieces * N); st.in(dvr, vrow_of, (size_t)pieces * 4);
+    st.in(dfo, first_of, (size_t)rows * 4); st.out(dk, keep, (size_t)pieces);
+    int rc = st.begin();
+    if (rc != QPN_OK) return rc;
+    HIPCHK(ctx, qpn_launch_recipe_filter(pieces, N, dm, dK, dvr, dfo, rows, dk, ctx->stream));
+    return st.finish();
+}
+
 } // extern "C"
 
 namespace {

@@ -226,6 +226,12 @@ int qpn_verify_max_dim();
 hipError_t qpn_launch_convexity(int32_t batch, int32_t n, int32_t m, const double *Qd, const double *Ad, const uint8_t *eq,
                                 double tol, int32_t *convex, double *min_eig, int32_t *null_dim, void *gws, hipStream_t stream);
 size_t qpn_convexity_workspace_bytes(int32_t batch, int32_t n, int32_t m);
+hipError_t qpn_launch_multiplier_vertices(int32_t batch, int32_t n, int32_t m, const double *E, const double *g, const uint8_t *cls,
+                                          const double *lam0, int32_t V, int32_t max_bases, double tol, double feas, double *verts,
+                                          int32_t *count, int32_t *status, void *ws, hipStream_t s);
+size_t qpn_multiplier_vertices_workspace_bytes(int32_t batch, int32_t n, int32_t m, int32_t max_bases);
+hipError_t qpn_launch_recipe_filter(int32_t pieces, int32_t N, const uint8_t *masks, const uint8_t *K, const int32_t *vrow_of,
+                                    const int32_t *first_of, int32_t rows, uint8_t *keep, hipStream_t s);
 #define QPN_CONVEXITY_MAX_N 256
 #define QPN_CONVEXITY_MAX_M 1024
 

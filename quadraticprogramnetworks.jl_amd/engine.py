@@ -671,6 +671,49 @@ class Engine:
         self._chk(rc, "qpn_convexity_nodes")
         return convex, min_eig, null_dim
 
+    def multiplier_vertices(self, Ac, g, cls, lam0, V, max_bases=None, tol=1e-9, feas=1e-6):
+        """Vertices of the multiplier sets Lambda = {lambda : Ad' lambda = g, classes} of many items (qpn_multiplier_vertices;
+        level_batch.multiplier_vertices_host is its numpy twin): Ac [batch, n, m] (Ad in the ABI layout), g [batch, n], cls
+        [batch, m] uint8 (level_batch.MV_GE / LE / FREE / ZERO), lam0 [batch, m] the start, V the vertex budget, max_bases the
+        basis budget (default 64 V).  Returns (verts [batch, V, m], count [batch] int32, status [batch] int32)."""
+        dev = self._mode(Ac, g, cls, lam0)
+        self._bind_stream(dev)
+        if not dev:
+            Ac, g, lam0 = (self._host(a, np.float64) for a in (Ac, g, lam0))
+            cls = self._host(cls, np.uint8)
+        else:
+            self._require_dev64(Ac, g, lam0)
+            if cls.dtype != torch.uint8 or not cls.is_contiguous():
+                raise QpnError("multiplier_vertices: cls must be a contiguous uint8 tensor")
+        batch, n, m = (int(v) for v in Ac.shape)
+        V = int(V)
+        mb = 64 * max(V, 1) if max_bases is None else int(max_bases)
+        if tuple(g.shape) != (batch, n) or tuple(cls.shape) != (batch, m) or tuple(lam0.shape) != (batch, m):
+            raise QpnError("multiplier_vertices: inconsistent shapes")
+        verts = self._alloc(dev, (batch, V, m), np.float64)
+        count = self._alloc(dev, (batch,), np.int32)
+        status = self._alloc(dev, (batch,), np.int32)
+        rc = self.lib.qpn_multiplier_vertices(self.ctx, batch, n, m, _ptr(Ac), _ptr(g), _ptr(cls), _ptr(lam0), V, mb, float(tol),
+                                              float(feas), _ptr(verts), _ptr(count), _ptr(status), MEM_DEVICE if dev else MEM_HOST)
+        self._chk(rc, "qpn_multiplier_vertices")
+        return verts, count, status
+
+    def recipe_filter(self, masks, K, vrow_of, first_of):
+        """qpn_recipe_filter (level_batch.recipe_filter_host is its numpy twin): keep [pieces] uint8, 0 for a recipe K[t] of
+        product row vrow_of[t] that an earlier product row of the same item (first_of[row] <= s < row) holds."""
+        dev = self._mode(masks, K, vrow_of, first_of)
+        self._bind_stream(dev)
+        if not dev:
+            masks, K = self._host(masks, np.uint8), self._host(K, np.uint8)
+            vrow_of, first_of = self._host(vrow_of, np.int32), self._host(first_of, np.int32)
+        rows, N = int(masks.shape[0]), int(masks.shape[1])
+        pieces = int(K.shape[0])
+        keep = self._alloc(dev, (pieces,), np.uint8)
+        rc = self.lib.qpn_recipe_filter(self.ctx, pieces, rows, N, _ptr(masks), _ptr(K), _ptr(vrow_of), _ptr(first_of), _ptr(keep),
+                                        MEM_DEVICE if dev else MEM_HOST)
+        self._chk(rc, "qpn_recipe_filter")
+        return keep
+
 
 class Nodes:
     """Resident node records (``qpn_nodes_upload``): the records of a level's single-node pools live in HBM owned by the

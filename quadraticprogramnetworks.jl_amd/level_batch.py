@@ -632,6 +632,351 @@ def finish_pieces_host(Ar, lr, ur, rows, flags, rec_of, ncols, take, xk, probe, 
     return dict(status=status, worst=worst, hash=hsh, dup_of=dup_of, store_of=store_of, As=As, ls=ls, us=us, rows_s=rows_s, stored=S)
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# multiplier-vertex exploration (QPNetOptions.exploration_vertices; src/avi_solutions.jl:92-129, :241-382)
+# ---------------------------------------------------------------------------------------------------------------------
+# Row classes of the multiplier set at the point, Lambda(x) = {lambda : Ad' lambda = g, per-row sign or zero}
+MV_GE, MV_LE, MV_FREE, MV_ZERO = 0, 1, 2, 3
+# status words of qpn_multiplier_vertices (include/qpn_hip.h)
+MV_COMPLETE, MV_VERTEX_BUDGET, MV_BASIS_BUDGET, MV_EMPTY, MV_NO_VERTEX = 0, 1, 2, 3, 4
+MV_TOL = 1e-9            # pivot and zero tolerance on the equilibrated rows
+MV_FEAS = 1e-6           # a basic sign-constrained multiplier down to -MV_FEAS (times the rhs scale) counts as 0
+MV_BAND = 1.0 - 2.0 ** -30
+MV_BASES_PER_VERTEX = 64     # default basis budget: this many bases per vertex asked for
+
+
+def multiplier_classes(m2):
+    """The row classes of Lambda(x) from the GAVI codes of the constraint rows (comp_indices, refined): code 5 alone >= 0,
+    code 7 alone <= 0, code 8 or both 5 and 7 free, code 6 alone = 0."""
+    m2 = np.asarray(m2, dtype=np.uint8)
+    b5 = (m2 >> 4) & 1 == 1; b7 = (m2 >> 6) & 1 == 1; b8 = (m2 >> 7) & 1 == 1
+    cls = np.full(m2.shape, MV_ZERO, np.uint8)
+    cls[b5 & ~b7] = MV_GE
+    cls[b7 & ~b5] = MV_LE
+    cls[b8 | (b5 & b7)] = MV_FREE
+    return cls
+
+
+def _mv_pivot(T, c, colof, tol):
+    """One Gauss-Jordan step on column c over the rows not yet pivoted: the largest |entry|, entries within 2^-30 of it count as
+    equal and the lowest row wins.  Returns the row, or -1 when every candidate is <= tol (the column depends on the pivoted ones)."""
+    a = np.where(colof < 0, np.abs(T[:, c]), -1.0)
+    amax = a.max() if a.size else -1.0
+    if not amax > tol:
+        return -1
+    r = int(np.nonzero(a >= amax * MV_BAND)[0][0])
+    p = T[r, c]
+    T[r] = T[r] / p
+    f = T[:, c].copy(); f[r] = 0.0
+    T -= f[:, None] * T[r][None, :]
+    colof[r] = c
+    return r
+
+
+def _mv_one(E, g, cls, lam0, V, max_bases, tol, feas):
+    """multiplier_vertices_host for one item: (vertices [k, m], status)."""
+    n, m = E.shape
+    keep = cls != MV_ZERO
+    sgn = cls == MV_GE
+    sgn |= cls == MV_LE
+    sig = np.where(cls == MV_LE, -1.0, 1.0)
+    T0 = np.zeros((n, m + 1))
+    T0[:, :m] = np.where(keep[None, :], E * sig[None, :], 0.0)
+    T0[:, m] = g
+    s = np.max(np.abs(T0[:, :m]), axis=1, initial=0.0)
+    gs = max(1.0, float(np.max(np.abs(g), initial=0.0)))
+    if np.any((s == 0.0) & (np.abs(g) > feas * gs)):
+        return np.zeros((0, m)), MV_EMPTY
+    nz = s > 0.0
+    T0[nz] = T0[nz] / s[nz][:, None]
+    T0[~nz, m] = 0.0
+    gs = max(1.0, float(np.max(np.abs(T0[:, m]), initial=0.0)))
+    free = np.nonzero(cls == MV_FREE)[0]
+    mu = np.where(keep, sig * lam0, 0.0)
+    mu = np.where(sgn & (mu < 0.0), 0.0, mu)
+    # 1. purification: the support of mu is made independent by moving along null directions until a sign-constrained
+    #    entry reaches 0 (the lowest such index when several do)
+    while True:
+        T = T0.copy(); colof = np.full(n, -1, np.int64); rowof = np.full(m, -1, np.int64)
+        for c in free.tolist():
+            r = _mv_pivot(T, c, colof, tol)
+            if r < 0:
+                return np.zeros((0, m)), MV_NO_VERTEX           # dependent free columns: Lambda(x) has a lineality space
+            rowof[c] = r
+        dep = -1
+        for c in np.nonzero(sgn & (mu > tol))[0].tolist():
+            r = _mv_pivot(T, c, colof, tol)
+            if r < 0:
+                dep = c
+                break
+            rowof[c] = r
+        if dep < 0:
+            break
+        d = np.zeros(m); d[dep] = 1.0
+        piv = np.nonzero(rowof >= 0)[0]
+        d[piv] = -T[rowof[piv], dep]
+        cand = sgn & ((rowof >= 0) | (np.arange(m) == dep))
+        if np.any(cand & (d < -tol)):
+            on = cand & (d < -tol); ratio = np.where(on, mu / np.where(on, -d, 1.0), np.inf); step = 1.0
+        else:
+            on = cand & (d > tol); ratio = np.where(on, mu / np.where(on, d, 1.0), np.inf); step = -1.0
+        th = ratio.min()
+        blk = int(np.nonzero(ratio <= th + th * 2.0 ** -30)[0][0])
+        mu = mu + (step * th) * d
+        mu[blk] = 0.0
+        mu = np.where(sgn & (mu < 0.0), 0.0, mu)
+    # 2. the rest of a basis, ascending; rows left without a pivot must have a zero right-hand side
+    for c in np.nonzero(sgn & ~(mu > tol))[0].tolist():
+        r = _mv_pivot(T, c, colof, tol)
+        if r >= 0:
+            rowof[c] = r
+    if np.any((colof < 0) & (np.abs(T[:, m]) > feas * gs)):
+        return np.zeros((0, m)), MV_EMPTY
+    # 3. breadth-first walk over feasible bases (every basis factored afresh from T0, its columns in ascending order)
+    visited = [frozenset(np.nonzero(rowof >= 0)[0].tolist())]
+    seen = {visited[0]}
+    overflow = False
+    verts, keys = [], []
+    head = 0
+    status = MV_COMPLETE
+    while head < len(visited):
+        B = sorted(visited[head]); head += 1
+        T = T0.copy(); colof = np.full(n, -1, np.int64); rowof = np.full(m, -1, np.int64)
+        ok = True
+        for c in B:
+            r = _mv_pivot(T, c, colof, tol)
+            if r < 0:
+                ok = False
+                break
+            rowof[c] = r
+        if not ok:
+            continue
+        mu = np.zeros(m)
+        bas = np.array(B, dtype=np.int64)
+        mu[bas] = T[rowof[bas], m]
+        if np.any(sgn & (mu < -feas * gs)):
+            continue
+        mu = np.where(sgn & (mu < tol * gs), 0.0, mu)
+        lam = sig * mu
+        key = (np.round(lam, 5) + 0.0).tobytes()
+        if key not in keys:
+            if len(verts) == V:
+                status = MV_VERTEX_BUDGET
+                break
+            keys.append(key); verts.append(lam)
+        for j in range(m):
+            if not sgn[j] or rowof[j] >= 0:
+                continue
+            th, rows = np.inf, []
+            for c in B:
+                if not sgn[c]:
+                    continue
+                a = T[rowof[c], j]
+                if a > tol:
+                    rt = mu[c] / a
+                    rows.append((c, rt))
+                    th = min(th, rt)
+            if not rows:
+                continue                                        # a ray: no vertex that way
+            lim = th + th * 2.0 ** -30
+            for c, rt in rows:
+                if rt <= lim:
+                    nb = visited[head - 1] - {c} | {j}
+                    if nb in seen:
+                        continue
+                    if len(visited) >= max_bases:
+                        overflow = True
+                        continue
+                    seen.add(nb); visited.append(nb)
+    if status == MV_COMPLETE and overflow:
+        status = MV_BASIS_BUDGET
+    return (np.array(verts) if verts else np.zeros((0, m))), status
+
+
+def multiplier_vertices_host(Ac, g, cls, lam0, V, max_bases=None, tol=MV_TOL, feas=MV_FEAS):
+    """The numpy twin of Engine.multiplier_vertices (qpn_multiplier_vertices), for engines without it.  Per item: Ac [n, m]
+    (the ABI layout of Ad, i.e. Ad'), g [n], the row classes cls [m] (MV_*), the multiplier lam0 [m] the vertex walk starts
+    from; up to V vertices of Lambda(x) = {lambda : Ad' lambda = g, classes} in breadth-first order, distinct after rounding
+    to 5 digits.  Returns (verts [batch, V, m], count [batch] int32, status [batch] int32)."""
+    Ac = np.asarray(Ac, dtype=np.float64); g = np.asarray(g, dtype=np.float64)
+    cls = np.asarray(cls, dtype=np.uint8); lam0 = np.asarray(lam0, dtype=np.float64)
+    batch, n, m = Ac.shape
+    max_bases = MV_BASES_PER_VERTEX * max(V, 1) if max_bases is None else int(max_bases)
+    verts = np.zeros((batch, V, m)); count = np.zeros(batch, np.int32); status = np.zeros(batch, np.int32)
+    for b in range(batch):
+        vb, st = _mv_one(Ac[b], g[b], cls[b], lam0[b], V, max_bases, tol, feas)
+        count[b] = len(vb); status[b] = st
+        if len(vb):
+            verts[b, :len(vb)] = vb
+    return verts, count, status
+
+
+def recipe_filter_host(masks, K, vrow_of, first_of):
+    """The numpy twin of Engine.recipe_filter (qpn_recipe_filter): recipe t of virtual row v = vrow_of[t] is kept unless an
+    earlier row s of the same item (first_of[v] <= s < v) holds it, i.e. every code of K[t] is in masks[s]: the reference's
+    setdiff(Ks, explored_Ks) (src/avi_solutions.jl:129).  Returns keep [pieces] uint8."""
+    masks = np.asarray(masks, dtype=np.uint8); K = np.asarray(K, dtype=np.uint8)
+    vrow_of = np.asarray(vrow_of, dtype=np.int64); first_of = np.asarray(first_of, dtype=np.int64)
+    keep = np.ones(K.shape[0], np.uint8)
+    bit = (np.uint8(1) << (K.astype(np.uint8) - np.uint8(1))).astype(np.uint8)
+    for t in range(K.shape[0]):
+        v = int(vrow_of[t])
+        for s in range(int(first_of[v]), v):
+            if np.all(masks[s] & bit[t]):
+                keep[t] = 0
+                break
+    return keep
+
+
+def _box_count(masks):
+    return float(np.prod([bin(int(v)).count("1") for v in masks]))
+
+
+def distinct_recipes(prod_masks):
+    """The number of distinct recipes over an item's products (boxes of codes), by inclusion-exclusion over earlier products."""
+    total = 0.0
+    for t in range(len(prod_masks)):
+        earlier = list(range(t))
+        for r in range(len(earlier) + 1):
+            for S in itertools.combinations(earlier, r):
+                mk = prod_masks[t].copy()
+                for s in S:
+                    mk &= prod_masks[s]
+                total += (-1.0) ** r * _box_count(mk)
+    return total
+
+
+def _multiplier_vertices(eng, Ac, g, cls, lam0, V):
+    fn = getattr(eng, "multiplier_vertices", None)
+    if callable(fn):
+        verts, count, status = fn(Ac, g, cls, lam0, V)
+        return np.asarray(verts), np.asarray(count), np.asarray(status)
+    return multiplier_vertices_host(Ac, g, cls, lam0, V)
+
+
+def _recipe_filter(eng, masks, K, vrow_of, first_of):
+    fn = getattr(eng, "recipe_filter", None)
+    if callable(fn):
+        return np.asarray(fn(masks, K, vrow_of, first_of))
+    return recipe_filter_host(masks, K, vrow_of, first_of)
+
+
+def explore_products(b, sel, rets, want, masks, total, tol, eng, E):
+    """The recipe products of the wanted records of batch b with multiplier-vertex exploration (E = exploration_vertices >= 2):
+    per item its own code sets, then the code sets (comp_indices at (x, v), refined as _piece_masks does) at up to E - 1
+    vertices v of Lambda(x) that differ from the verified multiplier after rounding to 5 digits, in the breadth-first order of
+    qpn_multiplier_vertices; a product whose code sets equal an earlier one of the item, or that has a row without a code, is
+    left out.  One vertex call for the batch.  Returns dict(vsel, vmasks, vtotal, vfirst: one entry per product, grouped by
+    item in the order of sel; distinct: per item the number of distinct recipes over its products)."""
+    n, m = b.n, b.m
+    xd, w = b.last["xd"], b.last["w"]
+    sel_a = np.asarray(sel, dtype=np.int64)
+    ok = total > 0
+    extra = [[] for _ in sel]
+    if m and ok.any():
+        lam0 = np.zeros((len(sel), m))
+        for t, k in enumerate(sel):
+            lam0[t, :b.m_true[k]] = rets[b.where[k]]["lam"]
+        g = np.einsum("bji,bj->bi", b.Qc[sel_a], xd[sel_a]) + np.einsum("bji,bj->bi", b.Rc[sel_a], w[sel_a]) + b.qd[sel_a]
+        cls = multiplier_classes(masks[:, n:])
+        on = np.nonzero(ok & np.any(cls != MV_ZERO, axis=1))[0]
+        if on.size:
+            verts, count, status = _multiplier_vertices(eng, b.Ac[sel_a[on]], g[on], cls[on], lam0[on], E)
+            vk, vl = [], []
+            for q, t in enumerate(on.tolist()):
+                key0 = (np.round(lam0[t], 5) + 0.0).tobytes()
+                got = 0
+                for j in range(int(count[q])):
+                    v = verts[q, j]
+                    if (np.round(v, 5) + 0.0).tobytes() == key0:
+                        continue
+                    if got == E - 1:
+                        break
+                    vk.append(t); vl.append(v); got += 1
+            if vk:
+                vk = np.asarray(vk)
+                rows = sel_a[vk]
+                lam = np.asarray(vl)
+                r1 = np.einsum("bji,bj->bi", b.Qc[rows], xd[rows]) + np.einsum("bji,bj->bi", b.Rc[rows], w[rows]) + b.qd[rows] \
+                    - np.einsum("bij,bj->bi", b.Ac[rows], lam)
+                s = np.einsum("bji,bj->bi", b.Ac[rows], xd[rows]) + np.einsum("bji,bj->bi", b.Bc[rows], w[rows])
+                free_lo = np.full((rows.size, n), -INF); free_hi = np.full((rows.size, n), INF)
+                m1 = np.asarray(eng.comp_indices(xd[rows], r1, free_lo, free_hi, tol=tol, shift=0))
+                m2 = np.asarray(eng.comp_indices(s, lam, b.l[rows], b.u[rows], tol=tol, shift=4))
+                for q, k in enumerate(rows.tolist()):
+                    m2[q, b.m_true[k]:] = 1 << 5
+                m2 = _refine_row_codes(m2, s, lam, b.l[rows], b.u[rows], CODE_TOL)
+                vm = np.concatenate([m1, m2], axis=1).astype(np.uint8)
+                for q, t in enumerate(vk.tolist()):
+                    if not np.any(vm[q] == 0):
+                        extra[t].append(vm[q])
+    vsel, vmasks, vfirst, distinct = [], [], [], np.zeros(len(sel))
+    for t, k in enumerate(sel):
+        prods = [masks[t]] if ok[t] else []
+        for mk in extra[t]:
+            if not any(np.array_equal(mk, p_) for p_ in prods):
+                prods.append(mk)
+        f0 = len(vsel)
+        for p_ in prods:
+            vsel.append(k); vmasks.append(p_); vfirst.append(f0)
+        distinct[t] = distinct_recipes(prods) if prods else 0.0
+    N = masks.shape[1]
+    vmasks = np.asarray(vmasks, dtype=np.uint8).reshape(len(vsel), N)
+    vtotal = np.array([_box_count(mk) for mk in vmasks], dtype=np.float64)
+    return dict(vsel=np.asarray(vsel, dtype=np.int64), vmasks=vmasks, vtotal=vtotal, vfirst=np.asarray(vfirst, dtype=np.int32),
+                distinct=distinct)
+
+
+def _explored_capped(eng, explore, cap):
+    """The first `cap` distinct recipes of every item over its products (explore_products), products in order and each in its
+    own recipe order: windows of at most the item's remaining need, enumerated from a running start per product and filtered
+    against the item's earlier products, until the item has `cap` recipes or its products are spent.  Returns (K, vrow_of)."""
+    vm, vt, vf = explore["vmasks"], explore["vtotal"].astype(np.int64), explore["vfirst"]
+    rows = vm.shape[0]
+    cur = np.zeros(rows, np.int64)                       # per product: the next recipe to enumerate
+    got = {}                                             # per item (its first row): recipes kept so far
+    kept = [[] for _ in range(rows)]                     # per product: the kept recipe blocks
+    ranged = _supports_first(eng)
+    # products that hold no recipe of their own (every one lies in an earlier product) are skipped outright
+    live = np.ones(rows, bool)
+    for v in range(rows):
+        if v > vf[v]:
+            live[v] = distinct_recipes(list(vm[vf[v]:v + 1])) > distinct_recipes(list(vm[vf[v]:v]))
+    while True:
+        act, cnt = [], []
+        for f0 in sorted(set(vf.tolist())):
+            have = got.get(f0, 0)
+            if have >= cap:
+                continue
+            v = f0
+            while v < rows and vf[v] == f0 and (not live[v] or cur[v] >= vt[v]):
+                v += 1
+            if v < rows and vf[v] == f0:
+                act.append(v); cnt.append(int(min(vt[v] - cur[v], cap - have)))
+        if not act:
+            break
+        act = np.asarray(act); cnt = np.asarray(cnt, dtype=np.int64)
+        offsets = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)
+        if ranged:
+            K, _ = eng.recipes_batch(vm[act], offsets, first=cur[act])
+        else:
+            K, _ = _recipes_range_host(vm[act], cur[act], cnt)
+        K = np.asarray(K)
+        node_of = np.repeat(np.arange(act.size), cnt)
+        keep = _recipe_filter(eng, vm, K, act[node_of], vf).astype(bool)
+        for q, v in enumerate(act.tolist()):
+            blk = K[offsets[q]:offsets[q + 1]][keep[offsets[q]:offsets[q + 1]]]
+            f0 = int(vf[v])
+            blk = blk[:cap - got.get(f0, 0)]
+            kept[v].append(blk)
+            got[f0] = got.get(f0, 0) + blk.shape[0]
+            cur[v] += cnt[q]
+    N = vm.shape[1]
+    Ks = [np.concatenate(kept[v]) if kept[v] else np.zeros((0, N), np.uint8) for v in range(rows)]
+    vrow_of = np.repeat(np.arange(rows), [k.shape[0] for k in Ks])
+    return (np.concatenate(Ks).astype(np.uint8) if rows else np.zeros((0, N), np.uint8)), vrow_of
+
+
 def _recipes_range_host(masks, first, counts):
     """qpn_recipes_batch_range restated (engines whose recipes_batch has no `first`): node b's recipes first[b] .. first[b] +
     counts[b] - 1 of its Cartesian product, row 0 the fastest digit."""
@@ -651,14 +996,17 @@ def _recipes_range_host(masks, first, counts):
 
 
 def solution_pieces(qpn, recs, batches, rets, x, engine, want: Sequence[bool], tol=1e-2, max_pieces=64, member_tol=MEMBER_TOL,
-                    truncated=None, _chunk=None):
+                    truncated=None, _chunk=None, exploration_vertices=0):
     """The solution-graph pieces of MANY nodes around (x, lambda) (process_solution_graph, src/avi.jl:447-477 ->
     comp_indices -> all_Ks, src/avi_solutions.jl:200-215 -> local_piece, :400-496 -> the multipliers eliminated, the
     columns permuted back, :86-87), batched: per record shape one comp_indices pair, one recipes call, one pieces call.
     Returns a list (per item; None where `want` is False) of lists of Poly in global coordinates.
     max_pieces: the first that many recipes of each item (a UserWarning names an item that has more; its index goes into the
     set `truncated` when one is given); None: every recipe, chunk by chunk (_chunk overrides the chunk size), finished on the
-    device when the engine has finish_pieces (its numpy twin otherwise)."""
+    device when the engine has finish_pieces (its numpy twin otherwise).
+    exploration_vertices E >= 2: the recipes of up to E - 1 further vertices of the multiplier set Lambda(x) join each item's
+    own (explore_products); a recipe an earlier product of the item holds is skipped, and max_pieces counts the distinct
+    recipes of the item.  E <= 1 launches nothing new."""
     from .avi_solutions import _dedupe, _probe_vector
     eng = engine
     x = np.asarray(x, dtype=np.float64)
@@ -669,24 +1017,41 @@ def solution_pieces(qpn, recs, batches, rets, x, engine, want: Sequence[bool], t
             continue
         n, m, p = b.n, b.m, b.p
         masks, total = _piece_masks(b, sel, rets, want, tol, eng)
+        explore = None
+        if exploration_vertices >= 2:
+            explore = explore_products(b, sel, rets, want, masks, total, tol, eng, exploration_vertices)
         if max_pieces is None:
-            _pieces_uncapped(qpn, recs, b, sel, masks, total, x, eng, member_tol, out, _chunk)
+            _pieces_uncapped(qpn, recs, b, sel, masks, total, x, eng, member_tol, out, _chunk, explore)
             continue
-        counts = np.minimum(total, max_pieces).astype(np.int64)
-        for t, k in enumerate(sel):
-            if total[t] > max_pieces:
-                warnings.warn(f"node {recs[b.where[k]]['pid']}: {int(total[t])} local recipes, only the first {max_pieces} "
-                              "are expanded (max_pieces)")
-                if truncated is not None:
-                    truncated.add(b.where[k])
-        offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
-        if offsets[-1] == 0:
-            for k in sel:
-                out[b.where[k]] = []
-            continue
-        K, node_of = eng.recipes_batch(masks, offsets)
-        node_of = np.asarray(node_of)
-        rec_of = np.asarray(sel, dtype=np.int32)[node_of]    # recipe -> record inside the batch
+        if explore is None:
+            counts = np.minimum(total, max_pieces).astype(np.int64)
+            for t, k in enumerate(sel):
+                if total[t] > max_pieces:
+                    warnings.warn(f"node {recs[b.where[k]]['pid']}: {int(total[t])} local recipes, only the first {max_pieces} "
+                                  "are expanded (max_pieces)")
+                    if truncated is not None:
+                        truncated.add(b.where[k])
+            offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+            if offsets[-1] == 0:
+                for k in sel:
+                    out[b.where[k]] = []
+                continue
+            K, node_of = eng.recipes_batch(masks, offsets)
+            node_of = np.asarray(node_of)
+            rec_of = np.asarray(sel, dtype=np.int32)[node_of]    # recipe -> record inside the batch
+        else:
+            for t, k in enumerate(sel):
+                if explore["distinct"][t] > max_pieces:
+                    warnings.warn(f"node {recs[b.where[k]]['pid']}: {int(explore['distinct'][t])} local recipes, only the first "
+                                  f"{max_pieces} are expanded (max_pieces)")
+                    if truncated is not None:
+                        truncated.add(b.where[k])
+            K, vrow_of = _explored_capped(eng, explore, max_pieces)
+            if K.shape[0] == 0:
+                for k in sel:
+                    out[b.where[k]] = []
+                continue
+            rec_of = explore["vsel"][vrow_of].astype(np.int32)
         Ar, lr, ur, rows, flags = eng.reduced_pieces(b.Qc, b.Rc, b.qd, b.Ac, b.Bc, b.l, b.u, np.asarray(K), rec_of)
         Ar = np.asarray(Ar); lr = np.asarray(lr); ur = np.asarray(ur); rows = np.asarray(rows); flags = np.asarray(flags)
         for k in sel:
@@ -768,17 +1133,24 @@ def _supports_first(eng):
         return False
 
 
-def _pieces_uncapped(qpn, recs, b, sel, masks, total, x, eng, member_tol, out, chunk):
+def _pieces_uncapped(qpn, recs, b, sel, masks, total, x, eng, member_tol, out, chunk, explore=None):
     """Every recipe of the wanted records of batch b (max_pieces = None), in chunks of at most `chunk` pieces across the records'
     concatenated recipes.  With an engine that has finish_pieces the batch's records go to the device once, the reduced pieces
     stay there, and only the finished store and the per-piece words come back; otherwise finish_pieces_host does the same on
-    the host.  The pieces are admitted in recipe order exactly as the capped route admits them."""
+    the host.  The pieces are admitted in recipe order exactly as the capped route admits them.
+    explore (explore_products): the products of the explored vertices take the place of the records' own, one row each, and the
+    recipes an earlier product of the same item holds are dropped after each chunk's enumeration (recipe_filter)."""
     from .avi_solutions import _dedupe, _probe_vector
     n, m, p = b.n, b.m, b.p
     for t, k in enumerate(sel):
-        if total[t] > MAX_RECIPES:
-            raise RuntimeError(f"node {recs[b.where[k]]['pid']}: {int(total[t])} local recipes, more than the 2^24 the uncapped "
+        cnt_t = total[t] if explore is None else explore["distinct"][t]
+        if cnt_t > MAX_RECIPES:
+            raise RuntimeError(f"node {recs[b.where[k]]['pid']}: {int(cnt_t)} local recipes, more than the 2^24 the uncapped "
                                "solution graph (max_pieces=None) enumerates")
+    if explore is not None:
+        for k in sel:
+            out[b.where[k]] = []                         # (an item without a product keeps an empty graph)
+        sel, masks, total = list(explore["vsel"].tolist()), explore["vmasks"], explore["vtotal"]
     for k in sel:
         out[b.where[k]] = []
     counts = total.astype(np.int64)
@@ -806,6 +1178,8 @@ def _pieces_uncapped(qpn, recs, b, sel, masks, total, x, eng, member_tol, out, c
         recd = tuple(to(a) for a in (b.Qc, b.Rc, b.qd, b.Ac, b.Bc, b.l, b.u))      # the records go up once per batch
         fin_in = (to(ncols, torch.int32), to(take, torch.int32), to(xk), to(probe))
         masks_d = to(masks, torch.uint8)
+        if explore is not None:
+            vfirst_d = to(explore["vfirst"], torch.int32)
     seen = {b.where[k]: {} for k in sel}                 # per node: (columns, hash) -> the exact keys of its pieces
     fallback = {}                                        # per node: (miss, Poly or the reduced piece to finish, record)
     members = {b.where[k]: False for k in sel}
@@ -834,8 +1208,17 @@ def _pieces_uncapped(qpn, recs, b, sel, masks, total, x, eng, member_tol, out, c
         offsets = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)
         rec_of = np.repeat(sel_a[part], cnt)             # recipe -> record inside the batch (records ascend)
         if dev:
-            K, _ = eng.recipes_batch(masks_d[torch.as_tensor(part, device=dv)].contiguous(), offsets, first=first)
+            part_d = torch.as_tensor(part, device=dv)
+            K, node_of = eng.recipes_batch(masks_d[part_d].contiguous(), offsets, first=first)
             rec_d = to(rec_of, torch.int32)
+            if explore is not None:
+                node_of = node_of.long()
+                keep = eng.recipe_filter(masks_d, K, part_d[node_of].to(torch.int32).contiguous(), vfirst_d).bool()
+                K = K[keep].contiguous(); rec_d = rec_d[keep].contiguous()
+                cnt_k = torch.bincount(node_of[keep], minlength=len(part)).cpu().numpy()
+                offsets = np.concatenate([[0], np.cumsum(cnt_k)]).astype(np.int64)
+                if offsets[-1] == 0:
+                    continue
             Ar, lr, ur, rows, flags = eng.reduced_pieces(*recd, K, rec_d)
             fin = eng.finish_pieces(Ar, lr, ur, rows, flags, rec_d, *fin_in, n, m, member_tol=member_tol)
             st = fin["status"].cpu().numpy(); worst = fin["worst"].cpu().numpy()
@@ -848,6 +1231,13 @@ def _pieces_uncapped(qpn, recs, b, sel, masks, total, x, eng, member_tol, out, c
             else:
                 K, _ = _recipes_range_host(masks[part], first, cnt)
             Kh = np.asarray(K)
+            if explore is not None:
+                node_of = np.repeat(np.arange(len(part)), cnt)
+                keep = _recipe_filter(eng, masks, Kh, part[node_of], explore["vfirst"]).astype(bool)
+                Kh = Kh[keep]; rec_of = rec_of[keep]
+                offsets = np.concatenate([[0], np.cumsum(np.bincount(node_of[keep], minlength=len(part)))]).astype(np.int64)
+                if offsets[-1] == 0:
+                    continue
             Ar, lr, ur, rows, flags = eng.reduced_pieces(b.Qc, b.Rc, b.qd, b.Ac, b.Bc, b.l, b.u, Kh, rec_of)
             Ar = np.asarray(Ar); lr = np.asarray(lr); ur = np.asarray(ur)
             fin = finish_pieces_host(Ar, lr, ur, rows, flags, rec_of, ncols, take, xk, probe, n, m, member_tol=member_tol)
@@ -996,7 +1386,8 @@ def process_level(qpn, players: Sequence[int], x, S: Dict[int, list], engine=Non
                 want[i0 + t] = True
     if any(want):
         cut = set()                                                                 # items whose graph the cap cut short
-        pieces = solution_pieces(qpn, recs, batches, rets, x, eng, want, max_pieces=qpn.options.max_pieces, truncated=cut)
+        pieces = solution_pieces(qpn, recs, batches, rets, x, eng, want, max_pieces=qpn.options.max_pieces, truncated=cut,
+                                 exploration_vertices=exploration_vertices)
         jobs, job_pid = [], []
         for pid in players:
             children, combos = combos_of[pid]

@@ -304,12 +304,14 @@ def combine_at(regions: List[List[Poly]], solutions: List[List[Poly]], x, engine
     return got
 
 
-def local_recipe_count(qpn, pid: int, x, S: Dict[int, list], engine=None):
+def local_recipe_count(qpn, pid: int, x, S: Dict[int, list], engine=None, exploration_vertices=0):
     """How many local pieces the node's solution graph has AT x: over every combination of the children's pieces for which
     the node is optimal (src/qp_processing.jl:162-205), the number of recipes compatible with the active-set masks of the
     node's own GAVI (process_solution_graph, src/avi.jl:447-477 -> comp_indices -> all_Ks, src/avi_solutions.jl:200-215):
     each of them is a non-empty piece containing x (local_piece, :400-496).  A lower bound of what the reference's graph
-    enumeration collects (its pieces start from these and grow by exploration), computable on the hot path alone."""
+    enumeration collects (its pieces start from these and grow by exploration), computable on the hot path alone.
+    exploration_vertices E >= 2: the distinct recipes over the products at the point and at up to E - 1 vertices of its
+    multiplier set (level_batch.explore_products' rule), as solution_pieces expands them."""
     from .avi import GAVI
     from .avi_solutions import comp_indices
     qp = qpn.qps[pid]
@@ -328,5 +330,32 @@ def local_recipe_count(qpn, pid: int, x, S: Dict[int, list], engine=None):
         g = GAVI(np.hstack([rec["Qd"], -rec["Ad"].T]), rec["R"], rec["qd"], np.full(n, -INF), np.full(n, INF),
                  np.hstack([rec["Ad"], np.zeros((m, m))]), rec["B"], rec["l"], rec["u"])
         mask = comp_indices(g, np.concatenate([rec["xd"], r["lam"]]), rec["w"], engine=engine)
-        total += int(np.prod([bin(int(v)).count("1") for v in mask]))
+        if exploration_vertices < 2 or m == 0 or np.any(np.asarray(mask) == 0):
+            total += int(np.prod([bin(int(v)).count("1") for v in mask]))
+            continue
+        total += int(_explored_count(g, rec, np.asarray(mask, dtype=np.uint8), np.asarray(r["lam"], dtype=np.float64), n,
+                                     exploration_vertices, engine))
     return total
+
+
+def _explored_count(g, rec, mask, lam0, n, E, engine):
+    """local_recipe_count's union over the products of the explored multiplier vertices."""
+    from . import level_batch as lb
+    from .avi_solutions import comp_indices
+    cls = lb.multiplier_classes(mask[n:])
+    rhs = rec["Qd"] @ rec["xd"] + rec["R"] @ rec["w"] + rec["qd"]
+    verts, count, _ = lb._multiplier_vertices(engine, np.ascontiguousarray(rec["Ad"].T)[None], rhs[None], cls[None], lam0[None], E)
+    key0 = (np.round(lam0, 5) + 0.0).tobytes()
+    prods = [mask]
+    got = 0
+    for j in range(int(count[0])):
+        v = np.asarray(verts[0, j])
+        if (np.round(v, 5) + 0.0).tobytes() == key0:
+            continue
+        if got == E - 1:
+            break
+        got += 1
+        mk = np.asarray(comp_indices(g, np.concatenate([rec["xd"], v]), rec["w"], engine=engine), dtype=np.uint8)
+        if not np.any(mk == 0) and not any(np.array_equal(mk, p_) for p_ in prods):
+            prods.append(mk)
+    return lb.distinct_recipes(prods)
