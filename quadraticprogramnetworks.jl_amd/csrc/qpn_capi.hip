@@ -58,6 +58,7 @@ int fail_arg(qpn_ctx *ctx, const char *msg)
     if (ctx) ctx->last_error = msg;
     return QPN_ERR_ARG;
 }
+int fail_arg(qpn_ctx *ctx, const char *who, const char *what) { return fail_arg(ctx, (std::string(who) + ": " + what).c_str()); }
 
 #define HIPCHK(ctx, call)                                        \
     do {                                                         \
@@ -84,7 +85,7 @@ struct Stage {
 
     Stage(qpn_ctx *c, int mem, const char *w)
         : ctx(c), who(w), host(mem == QPN_MEM_HOST), bad_mem(mem != QPN_MEM_HOST && mem != QPN_MEM_DEVICE) {}
-    int check() const { return bad_mem ? fail_arg(ctx, (std::string(who) + ": bad mem kind").c_str()) : QPN_OK; }
+    int check() const { return bad_mem ? fail_arg(ctx, who, "bad mem kind") : QPN_OK; }
 
     template <class T> void carve(T *&dev, size_t bytes)
     {
@@ -176,6 +177,79 @@ void stage_records(Stage &st, NodeDev &d, const NodeSizes &sz, const double *Qd,
 {
     st.in(d.Q, Qd, sz.Q); st.in(d.R, R, sz.R, 8); st.in(d.q, qd, sz.q); st.in(d.A, Ad, sz.A, 8);
     st.in(d.B, B, sz.B, 8); st.in(d.l, l, sz.lu, 8); st.in(d.u, u, sz.lu, 8);
+}
+
+// the number of recipes of one row of masks: the product of its codes' popcounts, saturating
+int64_t recipe_count(const uint8_t *row, int N)
+{
+    int64_t tot = 1;
+    for (int i = 0; i < N; ++i) {
+        const int r = __builtin_popcount(row[i]);
+        if (r > 1) tot = (tot > INT64_MAX / r) ? INT64_MAX : tot * r;
+    }
+    return tot;
+}
+
+// qpn_recipes_batch (first == nullptr: every node's recipes start at number 0 of its product) and qpn_recipes_batch_range
+int recipes_batch_any(qpn_ctx *ctx, const char *who, int32_t nodes, int32_t N, const uint8_t *masks, const int64_t *first,
+                      const int64_t *offsets, uint8_t *K, int32_t *node_of, int mem)
+{
+    if (!ctx) return QPN_ERR_ARG;
+    if (nodes <= 0 || N <= 0 || !masks || !offsets) return fail_arg(ctx, who, "bad argument");
+    Stage st(ctx, mem, who);
+    if (int rc = st.check()) return rc;
+    if (offsets[0] != 0) return fail_arg(ctx, who, "offsets[0] must be 0");
+    for (int b = 0; b < nodes; ++b) {
+        if (offsets[b + 1] < offsets[b]) return fail_arg(ctx, who, "offsets must not decrease");
+        if (first && first[b] < 0) return fail_arg(ctx, who, "first must not be negative");
+    }
+    const int64_t total = offsets[nodes];
+    if (total == 0) return QPN_OK;
+    if (!K || !node_of) return fail_arg(ctx, who, "null output");
+    if (total > INT32_MAX) { ctx->last_error = std::string(who) + ": more than 2^31 - 1 recipes in one call"; return QPN_ERR_SIZE; }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    // every node's range must lie inside its product.  Host masks are checked as they are; device masks are read back for the
+    // check (nodes x N bytes) when `first` is given, and are the caller's without it: a count beyond the product wraps around
+    // inside the product, it cannot leave the arrays
+    std::vector<uint8_t> hm;
+    const uint8_t *mk = masks;
+    if (!st.host && first) {
+        hm.resize((size_t)nodes * N);
+        HIPCHK(ctx, hipMemcpyAsync(hm.data(), masks, hm.size(), hipMemcpyDeviceToHost, s));
+        HIPCHK(ctx, hipStreamSynchronize(s));
+        mk = hm.data();
+    }
+    for (int b = 0; (st.host || first) && b < nodes; ++b) {
+        const int64_t tot = recipe_count(mk + (size_t)b * N, N), cnt = offsets[b + 1] - offsets[b], f = first ? first[b] : 0;
+        if (cnt > 0 && (f >= tot || cnt > tot - f)) return fail_arg(ctx, who, "a node asks for recipes beyond its product");
+    }
+    const long long *doff, *dfirst = nullptr; const uint8_t *dm; uint8_t *dK; int32_t *dno;
+    st.lib_in(doff, offsets, (size_t)(nodes + 1) * 8);
+    if (first) st.lib_in(dfirst, first, (size_t)nodes * 8);
+    st.in(dm, masks, (size_t)nodes * N); st.out(dK, K, (size_t)total * N); st.out(dno, node_of, (size_t)total * 4);
+    int rc = st.begin();
+    if (rc != QPN_OK) return rc;
+    // (offsets and first are the caller's host arrays, which may be pageable: the copies must be done before the call returns)
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    HIPCHK(ctx, qpn_launch_recipes_batch(nodes, N, dm, doff, total, dK, dno, s, dfirst));
+    return st.finish();
+}
+
+// what qpn_local_pieces and qpn_reduced_pieces ask of the arguments they share (`outputs`: none of the entry's own is null)
+int pieces_check(qpn_ctx *ctx, const char *who, bool host, int32_t pieces, int32_t nodes, int32_t n, int32_t m, int32_t p,
+                 const double *Qd, const double *R, const double *qd, const double *Ad, const double *B, const double *l,
+                 const double *u, const int32_t *node_of, const uint8_t *K, bool outputs)
+{
+    if (pieces < 0 || nodes <= 0 || n <= 0 || m < 0 || p < 0) return fail_arg(ctx, who, "bad sizes");
+    if (pieces == 0) return QPN_OK;
+    if (n + m > 512) { ctx->last_error = std::string(who) + ": n + m <= 512 in ABI v1"; return QPN_ERR_SIZE; }
+    if (!Qd || !qd || (m > 0 && (!Ad || !l || !u)) || (p > 0 && (!R || (m > 0 && !B))) || !K || !outputs)
+        return fail_arg(ctx, who, "null pointer");
+    if (!node_of && nodes < pieces) return fail_arg(ctx, who, "fewer record sets than pieces and no node_of");
+    for (int t = 0; t < pieces && host && node_of; ++t)
+        if (node_of[t] < 0 || node_of[t] >= nodes) return fail_arg(ctx, who, "node_of outside 0..nodes-1");
+    return QPN_OK;
 }
 
 } // namespace
@@ -462,11 +536,7 @@ int qpn_recipes_from_masks(qpn_ctx *ctx, int32_t N, const uint8_t *mask, int64_t
     std::vector<uint8_t> hm((size_t)N);
     if (st.host) memcpy(hm.data(), mask, (size_t)N);
     else { HIPCHK(ctx, hipMemcpyAsync(hm.data(), mask, (size_t)N, hipMemcpyDeviceToHost, s)); HIPCHK(ctx, hipStreamSynchronize(s)); }
-    int64_t tot = 1;
-    for (int i = 0; i < N; ++i) {
-        const int r = __builtin_popcount(hm[i]);
-        if (r > 1) tot = (tot > INT64_MAX / r) ? INT64_MAX : tot * r;
-    }
+    const int64_t tot = recipe_count(hm.data(), N);
     if (total) *total = tot;
     if (count == 0) return QPN_OK;
     if (first >= tot || (int64_t)count > tot - first) return fail_arg(ctx, "qpn_recipes_from_masks: first + count beyond the number of recipes");
@@ -481,36 +551,7 @@ int qpn_recipes_from_masks(qpn_ctx *ctx, int32_t N, const uint8_t *mask, int64_t
 int qpn_recipes_batch(qpn_ctx *ctx, int32_t nodes, int32_t N, const uint8_t *masks, const int64_t *offsets, uint8_t *K,
                       int32_t *node_of, int mem)
 {
-    if (!ctx) return QPN_ERR_ARG;
-    if (nodes <= 0 || N <= 0 || !masks || !offsets) return fail_arg(ctx, "qpn_recipes_batch: bad argument");
-    Stage st(ctx, mem, "qpn_recipes_batch");
-    if (int rc = st.check()) return rc;
-    if (offsets[0] != 0)return fail_arg(ctx, "qpn_recipes_batch: offsets[0] must be 0");
-    for (int b = 0; b < nodes; ++b)
-        if (offsets[b + 1] < offsets[b]) return fail_arg(ctx, "qpn_recipes_batch: offsets must not decrease");
-    const int64_t total = offsets[nodes];
-    if (total == 0) return QPN_OK;
-    if (!K || !node_of) return fail_arg(ctx, "qpn_recipes_batch: null output");
-    if (total > INT32_MAX) { ctx->last_error = "qpn_recipes_batch: more than 2^31 - 1 recipes in one call"; return QPN_ERR_SIZE; }
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
-    // a node may ask for at most the number of recipes its masks have (host masks are checked here; device masks are the
-    // caller's: a count beyond the product wraps around inside the product, it cannot leave the arrays)
-    if (st.host)
-        for (int b = 0; b < nodes; ++b) {
-            int64_t tot = 1;
-            for (int i = 0; i < N; ++i) { const int r = __builtin_popcount(masks[(size_t)b * N + i]); if (r > 1) tot = (tot > INT64_MAX / r) ? INT64_MAX : tot * r; }
-            if (offsets[b + 1] - offsets[b] > tot) return fail_arg(ctx, "qpn_recipes_batch: a node asks for more recipes than its masks have");
-        }
-    const long long *doff; const uint8_t *dm; uint8_t *dK; int32_t *dno;
-    st.lib_in(doff, offsets, (size_t)(nodes + 1) * 8);
-    st.in(dm, masks, (size_t)nodes * N); st.out(dK, K, (size_t)total * N); st.out(dno, node_of, (size_t)total * 4);
-    int rc = st.begin();
-    if (rc != QPN_OK) return rc;
-    // (the offsets are the caller's host array, which may be pageable: the copy must be done before the call returns)
-    HIPCHK(ctx, hipStreamSynchronize(s));
-    HIPCHK(ctx, qpn_launch_recipes_batch(nodes, N, dm, doff, total, dK, dno, s));
-    return st.finish();
+    return recipes_batch_any(ctx, "qpn_recipes_batch", nodes, N, masks, nullptr, offsets, K, node_of, mem);
 }
 
 int qpn_reduced_pieces(qpn_ctx *ctx, int32_t pieces, int32_t nodes, int32_t n, int32_t m, int32_t p, const double *Qd,
@@ -519,13 +560,10 @@ int qpn_reduced_pieces(qpn_ctx *ctx, int32_t pieces, int32_t nodes, int32_t n, i
                        int32_t *rows, int32_t *flags, int mem)
 {
     if (!ctx) return QPN_ERR_ARG;
-    if (pieces < 0 || nodes <= 0 || n <= 0 || m < 0 || p < 0) return fail_arg(ctx, "qpn_reduced_pieces: bad sizes");
-    if (pieces == 0) return QPN_OK;
-    if (n + m > 512) { ctx->last_error = "qpn_reduced_pieces: n + m <= 512 in ABI v1"; return QPN_ERR_SIZE; }
-    if (!Qd || !qd || (m > 0 && (!Ad || !l || !u)) || (p > 0 && (!R || (m > 0 && !B))) || !K || !Ar || !lr || !ur || !rows || !flags)
-        return fail_arg(ctx, "qpn_reduced_pieces: null pointer");
-    if (!node_of && nodes < pieces) return fail_arg(ctx, "qpn_reduced_pieces: fewer record sets than pieces and no node_of");
     Stage st(ctx, mem, "qpn_reduced_pieces");
+    if (int rc = pieces_check(ctx, st.who, st.host, pieces, nodes, n, m, p, Qd, R, qd, Ad, B, l, u, node_of, K, Ar && lr && ur && rows && flags))
+        return rc;
+    if (pieces == 0) return QPN_OK;
     if (int rc = st.check()) return rc;
     if (!(tol >= 0.0)) return fail_arg(ctx, "qpn_reduced_pieces: bad tolerance");
     if (qpn_reduce_pieces_lds(n, m, p) > 60 * 1024) { ctx->last_error = "qpn_reduced_pieces: too many parameters for one workgroup's LDS"; return QPN_ERR_SIZE; }
@@ -533,9 +571,6 @@ int qpn_reduced_pieces(qpn_ctx *ctx, int32_t pieces, int32_t nodes, int32_t n, i
     hipStream_t s = ctx->stream;
     const int N = n + m;
     const size_t rws = 2 * (size_t)N, cols = (size_t)N + p, cap = (size_t)n + 2 * (size_t)m, oc = (size_t)n + p;
-    if (st.host && node_of)
-        for (int t = 0; t < pieces; ++t)
-            if (node_of[t] < 0 || node_of[t] >= nodes) return fail_arg(ctx, "qpn_reduced_pieces: node_of outside 0..nodes-1");
     NodeDev d{};
     const int32_t *dno; const uint8_t *dK;
     double *dAp, *dlp, *dup, *dAr, *dlr, *dur; uint8_t *dkeep; int32_t *drows, *dflags;
@@ -555,46 +590,7 @@ int qpn_reduced_pieces(qpn_ctx *ctx, int32_t pieces, int32_t nodes, int32_t n, i
 int qpn_recipes_batch_range(qpn_ctx *ctx, int32_t nodes, int32_t N, const uint8_t *masks, const int64_t *first, const int64_t *offsets,
                             uint8_t *K, int32_t *node_of, int mem)
 {
-    if (!first) return qpn_recipes_batch(ctx, nodes, N, masks, offsets, K, node_of, mem);
-    if (!ctx) return QPN_ERR_ARG;
-    if (nodes <= 0 || N <= 0 || !masks || !offsets) return fail_arg(ctx, "qpn_recipes_batch_range: bad argument");
-    Stage st(ctx, mem, "qpn_recipes_batch_range");
-    if (int rc = st.check()) return rc;
-    if (offsets[0] != 0) return fail_arg(ctx, "qpn_recipes_batch_range: offsets[0] must be 0");
-    for (int b = 0; b < nodes; ++b) {
-        if (offsets[b + 1] < offsets[b]) return fail_arg(ctx, "qpn_recipes_batch_range: offsets must not decrease");
-        if (first[b] < 0) return fail_arg(ctx, "qpn_recipes_batch_range: first must not be negative");
-    }
-    const int64_t total = offsets[nodes];
-    if (total == 0) return QPN_OK;
-    if (!K || !node_of) return fail_arg(ctx, "qpn_recipes_batch_range: null output");
-    if (total > INT32_MAX) { ctx->last_error = "qpn_recipes_batch_range: more than 2^31 - 1 recipes in one call"; return QPN_ERR_SIZE; }
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
-    // every range must lie inside its node's product (device masks are read back for the check: nodes x N bytes)
-    std::vector<uint8_t> hm;
-    const uint8_t *mk = masks;
-    if (!st.host) {
-        hm.resize((size_t)nodes * N);
-        HIPCHK(ctx, hipMemcpyAsync(hm.data(), masks, hm.size(), hipMemcpyDeviceToHost, s));
-        HIPCHK(ctx, hipStreamSynchronize(s));
-        mk = hm.data();
-    }
-    for (int b = 0; b < nodes; ++b) {
-        int64_t tot = 1;
-        for (int i = 0; i < N; ++i) { const int r = __builtin_popcount(mk[(size_t)b * N + i]); if (r > 1) tot = (tot > INT64_MAX / r) ? INT64_MAX : tot * r; }
-        const int64_t cnt = offsets[b + 1] - offsets[b];
-        if (cnt > 0 && (first[b] >= tot || cnt > tot - first[b]))
-            return fail_arg(ctx, "qpn_recipes_batch_range: a node asks for recipes beyond its product");
-    }
-    const long long *doff, *dfirst; const uint8_t *dm; uint8_t *dK; int32_t *dno;
-    st.lib_in(doff, offsets, (size_t)(nodes + 1) * 8); st.lib_in(dfirst, first, (size_t)nodes * 8);
-    st.in(dm, masks, (size_t)nodes * N); st.out(dK, K, (size_t)total * N); st.out(dno, node_of, (size_t)total * 4);
-    int rc = st.begin();
-    if (rc != QPN_OK) return rc;
-    HIPCHK(ctx, hipStreamSynchronize(s));                            // (offsets and first may be pageable host arrays)
-    HIPCHK(ctx, qpn_launch_recipes_batch(nodes, N, dm, doff, total, dK, dno, s, dfirst));
-    return st.finish();
+    return recipes_batch_any(ctx, first ? "qpn_recipes_batch_range" : "qpn_recipes_batch", nodes, N, masks, first, offsets, K, node_of, mem);
 }
 
 int qpn_finish_pieces(qpn_ctx *ctx, int32_t pieces, int32_t records, int32_t n, int32_t m, int32_t p, const double *Ar, const double *lr,
@@ -728,17 +724,11 @@ int qpn_local_pieces(qpn_ctx *ctx, int32_t pieces, int32_t nodes, int32_t n, int
                      uint8_t *keep, int mem)
 {
     if (!ctx) return QPN_ERR_ARG;
-    if (pieces < 0 || nodes <= 0 || n <= 0 || m < 0 || p < 0) return fail_arg(ctx, "qpn_local_pieces: bad sizes");
-    if (pieces == 0) return QPN_OK;
-    if (n + m > 512) { ctx->last_error = "qpn_local_pieces: n + m <= 512 in ABI v1"; return QPN_ERR_SIZE; }
-    if (!Qd || !qd || (m > 0 && (!Ad || !l || !u)) || (p > 0 && (!R || (m > 0 && !B))) || !K || !Ap || !lp || !up || !keep)
-        return fail_arg(ctx, "qpn_local_pieces: null pointer");
-    if (!node_of && nodes < pieces) return fail_arg(ctx, "qpn_local_pieces: fewer record sets than pieces and no node_of");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
     Stage st(ctx, mem, "qpn_local_pieces");
-    if (st.host && node_of)
-        for (int t = 0; t < pieces; ++t)
-            if (node_of[t] < 0 || node_of[t] >= nodes) return fail_arg(ctx, "qpn_local_pieces: node_of outside 0..nodes-1");
+    if (int rc = pieces_check(ctx, st.who, st.host, pieces, nodes, n, m, p, Qd, R, qd, Ad, B, l, u, node_of, K, Ap && lp && up && keep))
+        return rc;
+    if (pieces == 0) return QPN_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
     const int N = n + m;
     const size_t rows = 2 * (size_t)N, cols = (size_t)N + p;
     NodeDev d{};

@@ -1,7 +1,8 @@
 """Host wrapper over the C-ABI (include/qpn_hip.h): one ``Engine`` = one ``qpn_ctx`` on one GPU.
 
 Buffers may be numpy arrays (host; the library stages them through HBM) or torch CUDA tensors
-(device; zero-copy, asynchronous on torch's current stream).  All matrix buffers are in the
+(device; zero-copy, asynchronous on torch's current stream: a tensor has to be of the ABI's element type for its argument,
+contiguous and on the engine's device, see ``Engine._stage``).  All matrix buffers are in the
 ABI layout: per item COLUMN-MAJOR (Julia), i.e. a ``(batch, N, N)`` array ``Mc`` holds
 ``Mc[b, j, i] = M_b[i, j]``.  ``colmajor()`` converts from the usual math layout.
 
@@ -37,6 +38,9 @@ def colmajor(M):
 
 def _torch_dt(dt):
     return {np.dtype(np.int32): torch.int32, np.dtype(np.float64): torch.float64, np.dtype(np.uint8): torch.uint8}[np.dtype(dt)]
+
+
+_DTYPES = dict(f64="float64", u8="uint8", i32="int32")      # Engine._stage's groups: the ABI's element types, by numpy / torch name
 
 
 def _is_dev(x):
@@ -97,40 +101,54 @@ class Engine:
             if s != self._bound:                 # (the binding call is skipped while the stream stays what it was)
                 # the binding is cached only once the library has accepted it (the call synchronises the old stream and can fail)
                 self._bound = None
-                self._chk(self.lib.qpn_ctx_set_stream(self.ctx, C.c_void_p(s)), "qpn_ctx_set_stream")
+                self._call("qpn_ctx_set_stream", C.c_void_p(s))
                 self._bound = s
         elif not dev:
             if self._bound != "own":
                 self._bound = None
-                self._chk(self.lib.qpn_ctx_use_own_stream(self.ctx), "qpn_ctx_use_own_stream")
+                self._call("qpn_ctx_use_own_stream")
                 self._bound = "own"
         self._t0 = time.perf_counter()
 
+    def _call(self, name, *args):
+        """Entry point `name` of the library on this context; counted, and a failure raised, under that one name."""
+        self._chk(getattr(self.lib, name)(self.ctx, *args), name)
+
+    @staticmethod
+    def _mem(dev):
+        return MEM_DEVICE if dev else MEM_HOST
+
     def synchronize(self):
-        self._chk(self.lib.qpn_ctx_synchronize(self.ctx), "qpn_ctx_synchronize")
+        self._call("qpn_ctx_synchronize")
 
     def default_opts(self) -> AviOpts:
         o = AviOpts()
         self.lib.qpn_avi_default_opts(C.byref(o))
         return o
 
-    def _mode(self, *arrs):
-        devs = [_is_dev(a) for a in arrs if a is not None]
+    def _stage(self, who, names, raw=(), **typed):
+        """The buffers of one call of method `who`, grouped by the element type the ABI declares for them (f64=, u8=, i32=;
+        None allowed anywhere; `names` names them, in the same order, for the error message).  Host or device is decided over
+        all of them and `raw` (buffers with a rule of their own, left to the caller), never a mix; the stream is bound; host
+        buffers become contiguous arrays of their type.  Device tensors go to the kernels as raw addresses, so they have to be
+        what the ABI says they are already: that dtype, contiguous, on the engine's device.  Returns [dev, *buffers]."""
+        devs = [_is_dev(a) for g in (raw, *typed.values()) for a in g if a is not None]
         if any(devs) and not all(devs):
             raise QpnError("mixing host and device buffers in one call")
-        return bool(devs and devs[0])
-
-    def _host(self, a, dtype):
-        return None if a is None else np.ascontiguousarray(a, dtype=dtype)
-
-    @staticmethod
-    def _require_dev64(*ts):
-        """Device arguments go to the kernels as raw addresses: they must be what the ABI says they are."""
-        for t in ts:
-            if t is None:
-                continue
-            if t.dtype != torch.float64 or not t.is_contiguous():
-                raise QpnError("device buffers must be contiguous float64 tensors")
+        dev = bool(devs and devs[0])
+        self._bind_stream(dev)
+        staged = [dev]
+        for kind, group in typed.items():
+            dt = getattr(torch if dev else np, _DTYPES[kind])
+            for a in group:
+                if a is not None:
+                    if not dev:
+                        a = np.ascontiguousarray(a, dtype=dt)
+                    elif a.dtype != dt or not a.is_contiguous() or a.device.index != self.device:
+                        raise QpnError(f"{who}: {names.split()[len(staged) - 1]} must be a contiguous {_DTYPES[kind]} tensor on "
+                                       f"cuda:{self.device}")
+                staged.append(a)
+        return staged
 
     @staticmethod
     def _x_stride(x_out, dev, batch, n):
@@ -165,42 +183,37 @@ class Engine:
         the kernel: no reset pass).  `out` may carry the dict of a previous call to reuse its
         buffers.  Returns dict(z, status, resid, pivots, active).
         """
-        dev = self._mode(Mc, q, l, u, z0, kind)
-        self._bind_stream(dev)
-        if not dev:
-            Mc, q, l, u = (self._host(a, np.float64) for a in (Mc, q, l, u))
-            kind = self._host(kind, np.uint8)
-        else:
-            self._require_dev64(Mc, q, l, u, z0)
+        dev, Mc, q, l, u, z0, kind = self._stage("solve_avi_batch", "Mc q l u z0 kind", f64=(Mc, q, l, u, z0), u8=(kind,))
         batch, N = q.shape
         strideM = 0 if Mc.ndim == 2 else N * N
         sk = 0 if (kind is None or kind.ndim == 1) else N
+        res, o = self._solve_outputs(dev, batch, N, z0, opts, want_active, out)
+        self._call("qpn_solve_avi_batch", batch, N, _ptr(Mc), strideM, _ptr(q), _ptr(l), _ptr(u), _ptr(kind), sk, _ptr(res["z"]),
+                   _ptr(res["status"]), _ptr(res["resid"]), _ptr(res["pivots"]), _ptr(res["active"]), C.byref(o), self._mem(dev))
+        return res
+
+    def _solve_outputs(self, dev, batch, N, z0, opts, want_active, out):
+        """The result dict of a solve (`out`'s buffers when its z has the right shape, else new ones) and its options: z starts
+        from z0, or cold -- the kernel's own cold start under the default options, zeros under the caller's."""
         o = opts if opts is not None else self.default_opts()
-        if out is not None and out["z"].shape == q.shape:
-            z, status, resid, pivots, active = out["z"], out["status"], out["resid"], out["pivots"], out["active"]
+        if out is not None and out["z"].shape == (batch, N):
+            res = {k: out[k] for k in ("z", "status", "resid", "pivots", "active")}
         else:
-            z = self._alloc(dev, (batch, N), np.float64)
-            status = self._alloc(dev, (batch,), np.int32)
-            resid = self._alloc(dev, (batch,), np.float64)
-            pivots = self._alloc(dev, (batch,), np.int32)
-            active = self._alloc(dev, (batch, N), np.uint8) if want_active else None
+            res = dict(z=self._alloc(dev, (batch, N), np.float64), status=self._alloc(dev, (batch,), np.int32),
+                       resid=self._alloc(dev, (batch,), np.float64), pivots=self._alloc(dev, (batch,), np.int32),
+                       active=self._alloc(dev, (batch, N), np.uint8) if want_active else None)
         if z0 is None:
             if opts is None:
                 o.flags |= _lib.AVI_FLAG_COLD_START
             elif dev:
-                z.zero_()
+                res["z"].zero_()
             else:
-                z[...] = 0.0
+                res["z"][...] = 0.0
         elif dev:
-            z.copy_(z0)
+            res["z"].copy_(z0)
         else:
-            z[...] = np.asarray(z0, dtype=np.float64)
-        rc = self.lib.qpn_solve_avi_batch(self.ctx, batch, N, _ptr(Mc), strideM, _ptr(q), _ptr(l),
-                                          _ptr(u), _ptr(kind), sk, _ptr(z), _ptr(status),
-                                          _ptr(resid), _ptr(pivots), _ptr(active), C.byref(o),
-                                          MEM_DEVICE if dev else MEM_HOST)
-        self._chk(rc, "qpn_solve_avi_batch")
-        return dict(z=z, status=status, resid=resid, pivots=pivots, active=active)
+            res["z"][...] = z0
+        return res, o
 
     def solve_mcp_csc(self, N, colptr, rowval, nzval, q, l, u, z0, opts=None):
         """One box-MCP in Julia's SparseMatrixCSC{Float64,Int32} layout (1-based): the argument
@@ -212,46 +225,29 @@ class Engine:
         z = np.array(z0, dtype=np.float64, copy=True)
         st, res, piv = C.c_int32(0), C.c_double(0), C.c_int32(0)
         o = opts if opts is not None else self.default_opts()
-        rc = self.lib.qpn_solve_mcp_csc(self.ctx, int(N), _ptr(colptr), _ptr(rowval), _ptr(nzval),
-                                        _ptr(q), _ptr(l), _ptr(u), _ptr(z), C.byref(st),
-                                        C.byref(res), C.byref(piv), C.byref(o))
-        self._chk(rc, "qpn_solve_mcp_csc")
+        self._call("qpn_solve_mcp_csc", int(N), _ptr(colptr), _ptr(rowval), _ptr(nzval), _ptr(q), _ptr(l), _ptr(u), _ptr(z),
+                   C.byref(st), C.byref(res), C.byref(piv), C.byref(o))
         return int(st.value), z, dict(resid=res.value, pivots=piv.value)
 
     # -- (A3) ------------------------------------------------------------------------------
     def check_avi_batch(self, Mc, q, l, u, z, kind=None, tol=1e-6, want_r=True):
-        dev = self._mode(Mc, q, l, u, z, kind)
-        self._bind_stream(dev)
-        if not dev:
-            Mc, q, l, u, z = (self._host(a, np.float64) for a in (Mc, q, l, u, z))
-            kind = self._host(kind, np.uint8)
-        else:
-            self._require_dev64(Mc, q, l, u, z)
+        dev, Mc, q, l, u, z, kind = self._stage("check_avi_batch", "Mc q l u z kind", f64=(Mc, q, l, u, z), u8=(kind,))
         batch, N = q.shape
         strideM = 0 if Mc.ndim == 2 else N * N
         sk = 0 if (kind is None or kind.ndim == 1) else N
         degree = self._alloc(dev, (batch,), np.int32)
         r = self._alloc(dev, (batch, N), np.float64) if want_r else None
-        rc = self.lib.qpn_check_avi_batch(self.ctx, batch, N, _ptr(Mc), strideM, _ptr(q), _ptr(l),
-                                          _ptr(u), _ptr(kind), sk, _ptr(z), float(tol),
-                                          _ptr(degree), _ptr(r), MEM_DEVICE if dev else MEM_HOST)
-        self._chk(rc, "qpn_check_avi_batch")
+        self._call("qpn_check_avi_batch", batch, N, _ptr(Mc), strideM, _ptr(q), _ptr(l), _ptr(u), _ptr(kind), sk, _ptr(z),
+                   float(tol), _ptr(degree), _ptr(r), self._mem(dev))
         return degree, r
 
     # -- (A9) ------------------------------------------------------------------------------
     def comp_indices(self, zv, rv, l, u, tol=1e-2, shift=0):
-        dev = self._mode(zv, rv, l, u)
-        self._bind_stream(dev)
-        if not dev:
-            zv, rv, l, u = (self._host(a, np.float64) for a in (zv, rv, l, u))
-        else:
-            self._require_dev64(zv, rv, l, u)
+        dev, zv, rv, l, u = self._stage("comp_indices", "zv rv l u", f64=(zv, rv, l, u))
         count = int(np.prod(zv.shape))
         mask = self._alloc(dev, tuple(zv.shape), np.uint8)
-        rc = self.lib.qpn_comp_indices(self.ctx, count, _ptr(zv), _ptr(rv), _ptr(l), _ptr(u),
-                                       float(tol), int(shift), _ptr(mask),
-                                       MEM_DEVICE if dev else MEM_HOST)
-        self._chk(rc, "qpn_comp_indices")
+        self._call("qpn_comp_indices", count, _ptr(zv), _ptr(rv), _ptr(l), _ptr(u), float(tol), int(shift), _ptr(mask),
+                   self._mem(dev))
         return mask
 
     # -- (A5+A6) ---------------------------------------------------------------------------
@@ -259,12 +255,7 @@ class Engine:
         """Per-node reduced KKT blocks.  Qc (batch,n,n), Rc (batch,p,n), Ac (batch,n,m),
         Bc (batch,p,m): all column-major per item (see ``colmajor``); w (p,) shared or (batch,p).
         `out` may carry the tuple of a previous call to reuse its buffers."""
-        dev = self._mode(Qc, Rc, qd, Ac, Bc, l, u, w)
-        self._bind_stream(dev)
-        if not dev:
-            Qc, Rc, qd, Ac, Bc, l, u, w = (self._host(a, np.float64) for a in (Qc, Rc, qd, Ac, Bc, l, u, w))
-        else:
-            self._require_dev64(Qc, Rc, qd, Ac, Bc, l, u, w)
+        dev, Qc, Rc, qd, Ac, Bc, l, u, w = self._stage("assemble_nodes", "Qc Rc qd Ac Bc l u w", f64=(Qc, Rc, qd, Ac, Bc, l, u, w))
         batch, n = qd.shape
         m = l.shape[1]
         p = w.shape[-1]
@@ -278,46 +269,31 @@ class Engine:
             lout = self._alloc(dev, (batch, N), np.float64)
             uout = self._alloc(dev, (batch, N), np.float64)
             kind = self._alloc(dev, (batch, N), np.uint8)
-        rc = self.lib.qpn_assemble_nodes(self.ctx, batch, n, m, p, _ptr(Qc), _ptr(Rc), _ptr(qd),
-                                         _ptr(Ac), _ptr(Bc), _ptr(l), _ptr(u), _ptr(w), sw,
-                                         _ptr(Mout), _ptr(qout), _ptr(lout), _ptr(uout), _ptr(kind),
-                                         MEM_DEVICE if dev else MEM_HOST)
-        self._chk(rc, "qpn_assemble_nodes")
+        self._call("qpn_assemble_nodes", batch, n, m, p, _ptr(Qc), _ptr(Rc), _ptr(qd), _ptr(Ac), _ptr(Bc), _ptr(l), _ptr(u), _ptr(w),
+                   sw, _ptr(Mout), _ptr(qout), _ptr(lout), _ptr(uout), _ptr(kind), self._mem(dev))
         return Mout, qout, lout, uout, kind
 
     # -- (F1) local pieces ------------------------------------------------------------------------
     def recipes_from_masks(self, mask, first=0, count=None):
         """all_Ks (src/avi_solutions.jl:200-215) from one solution's active-set masks (uint8 per row of z): recipes number
         first .. first+count-1 of the Cartesian product of the rows' code sets.  Returns (K [count, N] uint8, total)."""
-        dev = self._mode(mask)
-        self._bind_stream(dev)
-        if not dev:
-            mask = self._host(mask, np.uint8)
+        dev, mask = self._stage("recipes_from_masks", "mask", u8=(mask,))
         N = int(mask.shape[0])
         total = C.c_int64(0)
-        rc = self.lib.qpn_recipes_from_masks(self.ctx, N, _ptr(mask), 0, 0, None, C.byref(total), MEM_DEVICE if dev else MEM_HOST)
-        self._chk(rc, "qpn_recipes_from_masks")
+        self._call("qpn_recipes_from_masks", N, _ptr(mask), 0, 0, None, C.byref(total), self._mem(dev))
         tot = int(total.value)
         if count is None:
             count = tot - first
         K = self._alloc(dev, (count, N), np.uint8)
-        rc = self.lib.qpn_recipes_from_masks(self.ctx, N, _ptr(mask), int(first), int(count), _ptr(K), None,
-                                             MEM_DEVICE if dev else MEM_HOST)
-        self._chk(rc, "qpn_recipes_from_masks")
+        self._call("qpn_recipes_from_masks", N, _ptr(mask), int(first), int(count), _ptr(K), None, self._mem(dev))
         return K, tot
 
     def local_pieces(self, Qc, Rc, qd, Ac, Bc, l, u, K, node_of=None):
         """local_piece (src/avi_solutions.jl:400-496, before simplify) for recipes K [pieces, n+m] over node records in the
         ABI layout (as solve_nodes); node_of [pieces] int32 names each recipe's node (default: recipe t <-> node t).
         Returns (Ap [pieces, N+p, 2N] column-major per piece, lp, up [pieces, 2N], keep [pieces, 2N] uint8)."""
-        dev = self._mode(Qc, Rc, qd, Ac, Bc, l, u, K, node_of)
-        self._bind_stream(dev)
-        if not dev:
-            Qc, Rc, qd, Ac, Bc, l, u = (self._host(a, np.float64) for a in (Qc, Rc, qd, Ac, Bc, l, u))
-            K = self._host(K, np.uint8)
-            node_of = self._host(node_of, np.int32)
-        else:
-            self._require_dev64(Qc, Rc, qd, Ac, Bc, l, u)
+        dev, Qc, Rc, qd, Ac, Bc, l, u, K, node_of = self._stage("local_pieces", "Qc Rc qd Ac Bc l u K node_of",
+                                                                f64=(Qc, Rc, qd, Ac, Bc, l, u), u8=(K,), i32=(node_of,))
         nodes, n = qd.shape
         m = l.shape[1]
         p = Rc.shape[1]
@@ -327,10 +303,8 @@ class Engine:
         lp = self._alloc(dev, (pieces, 2 * N), np.float64)
         up = self._alloc(dev, (pieces, 2 * N), np.float64)
         keep = self._alloc(dev, (pieces, 2 * N), np.uint8)
-        rc = self.lib.qpn_local_pieces(self.ctx, pieces, nodes, n, m, p, _ptr(Qc), _ptr(Rc), _ptr(qd), _ptr(Ac), _ptr(Bc), _ptr(l),
-                                       _ptr(u), _ptr(node_of), _ptr(K), _ptr(Ap), _ptr(lp), _ptr(up), _ptr(keep),
-                                       MEM_DEVICE if dev else MEM_HOST)
-        self._chk(rc, "qpn_local_pieces")
+        self._call("qpn_local_pieces", pieces, nodes, n, m, p, _ptr(Qc), _ptr(Rc), _ptr(qd), _ptr(Ac), _ptr(Bc), _ptr(l), _ptr(u),
+                   _ptr(node_of), _ptr(K), _ptr(Ap), _ptr(lp), _ptr(up), _ptr(keep), self._mem(dev))
         return Ap, lp, up, keep
 
     # -- (F1, a level at a time) --------------------------------------------------------------------
@@ -339,10 +313,7 @@ class Engine:
         offsets [nodes + 1] int64 (host; node b gets the first offsets[b+1] - offsets[b] recipes of its product).
         first [nodes] int64 (host; qpn_recipes_batch_range): node b's recipes start at number first[b] of its product instead.
         Returns (K [total, N] uint8, node_of [total] int32)."""
-        dev = self._mode(masks)
-        self._bind_stream(dev)
-        if not dev:
-            masks = self._host(masks, np.uint8)
+        dev, masks = self._stage("recipes_batch", "masks", u8=(masks,))
         offsets = np.ascontiguousarray(offsets, dtype=np.int64)
         nodes, N = int(masks.shape[0]), int(masks.shape[1])
         if offsets.shape != (nodes + 1,):
@@ -351,16 +322,12 @@ class Engine:
         K = self._alloc(dev, (total, N), np.uint8)
         node_of = self._alloc(dev, (total,), np.int32)
         if first is None:
-            rc = self.lib.qpn_recipes_batch(self.ctx, nodes, N, _ptr(masks), _ptr(offsets), _ptr(K), _ptr(node_of),
-                                            MEM_DEVICE if dev else MEM_HOST)
-            self._chk(rc, "qpn_recipes_batch")
+            self._call("qpn_recipes_batch", nodes, N, _ptr(masks), _ptr(offsets), _ptr(K), _ptr(node_of), self._mem(dev))
             return K, node_of
         first = np.ascontiguousarray(first, dtype=np.int64)
         if first.shape != (nodes,):
             raise ValueError("recipes_batch: first must have one entry per node")
-        rc = self.lib.qpn_recipes_batch_range(self.ctx, nodes, N, _ptr(masks), _ptr(first), _ptr(offsets), _ptr(K), _ptr(node_of),
-                                              MEM_DEVICE if dev else MEM_HOST)
-        self._chk(rc, "qpn_recipes_batch_range")
+        self._call("qpn_recipes_batch_range", nodes, N, _ptr(masks), _ptr(first), _ptr(offsets), _ptr(K), _ptr(node_of), self._mem(dev))
         return K, node_of
 
     def finish_pieces(self, Ar, lr, ur, rows, flags, rec_of, ncols, take, xk, probe, n, m, member_tol=1e-5, store_cap=None):
@@ -370,16 +337,9 @@ class Engine:
         column-major, ls, us [S, cap], rows_s [S], stored = S): the store holds the members that are neither duplicates nor flagged.
         Device inputs give device outputs (hash as int64 bits); the store then has room for store_cap (default: pieces) slots,
         of which the first `stored` are filled."""
-        dev = self._mode(Ar, lr, ur, rows, flags, rec_of, ncols, take, xk, probe)
-        self._bind_stream(dev)
-        if not dev:
-            Ar, lr, ur, xk, probe = (self._host(a, np.float64) for a in (Ar, lr, ur, xk, probe))
-            rows, flags, rec_of, ncols, take = (self._host(a, np.int32) for a in (rows, flags, rec_of, ncols, take))
-        else:
-            self._require_dev64(Ar, lr, ur, xk, probe)
-            for t in (rows, flags, rec_of, ncols, take):
-                if t.dtype != torch.int32 or not t.is_contiguous():
-                    raise QpnError("finish_pieces: index arrays must be contiguous int32 tensors")
+        dev, Ar, lr, ur, xk, probe, rows, flags, rec_of, ncols, take = self._stage(
+            "finish_pieces", "Ar lr ur xk probe rows flags rec_of ncols take", f64=(Ar, lr, ur, xk, probe),
+            i32=(rows, flags, rec_of, ncols, take))
         pieces, oc, cap = (int(v) for v in Ar.shape)
         records = int(ncols.shape[0])
         if tuple(take.shape) != (records, oc) or tuple(xk.shape) != (records, oc) or tuple(probe.shape) != (records, oc) \
@@ -401,11 +361,9 @@ class Engine:
         us = self._alloc(dev, (sc, cap), np.float64)
         rows_s = self._alloc(dev, (sc,), np.int32)
         stored = C.c_int32(0)
-        rc = self.lib.qpn_finish_pieces(self.ctx, pieces, records, n, m, p, _ptr(Ar), _ptr(lr), _ptr(ur), _ptr(rows), _ptr(flags),
-                                        _ptr(rec_of), _ptr(ncols), _ptr(take), _ptr(xk), _ptr(probe), float(member_tol), _ptr(status),
-                                        _ptr(worst), _ptr(hsh), _ptr(dup_of), _ptr(store_of), sc, _ptr(As), _ptr(ls), _ptr(us),
-                                        _ptr(rows_s), C.byref(stored), MEM_DEVICE if dev else MEM_HOST)
-        self._chk(rc, "qpn_finish_pieces")
+        self._call("qpn_finish_pieces", pieces, records, n, m, p, _ptr(Ar), _ptr(lr), _ptr(ur), _ptr(rows), _ptr(flags), _ptr(rec_of),
+                   _ptr(ncols), _ptr(take), _ptr(xk), _ptr(probe), float(member_tol), _ptr(status), _ptr(worst), _ptr(hsh),
+                   _ptr(dup_of), _ptr(store_of), sc, _ptr(As), _ptr(ls), _ptr(us), _ptr(rows_s), C.byref(stored), self._mem(dev))
         S = int(stored.value)
         return dict(status=status, worst=worst, hash=hsh, dup_of=dup_of, store_of=store_of, As=As[:S], ls=ls[:S], us=us[:S],
                     rows_s=rows_s[:S], stored=S)
@@ -415,14 +373,8 @@ class Engine:
         through each piece's own equality rows (qpn_reduced_pieces).  Returns (Ar [pieces, n+p, cap] column-major per piece --
         Ar[t].T is the cap x (n+p) row matrix over [x_d; x_p] --, lr, ur [pieces, cap], rows [pieces], flags [pieces]),
         cap = n + 2m."""
-        dev = self._mode(Qc, Rc, qd, Ac, Bc, l, u, K, node_of)
-        self._bind_stream(dev)
-        if not dev:
-            Qc, Rc, qd, Ac, Bc, l, u = (self._host(a, np.float64) for a in (Qc, Rc, qd, Ac, Bc, l, u))
-            K = self._host(K, np.uint8)
-            node_of = self._host(node_of, np.int32)
-        else:
-            self._require_dev64(Qc, Rc, qd, Ac, Bc, l, u)
+        dev, Qc, Rc, qd, Ac, Bc, l, u, K, node_of = self._stage("reduced_pieces", "Qc Rc qd Ac Bc l u K node_of",
+                                                                f64=(Qc, Rc, qd, Ac, Bc, l, u), u8=(K,), i32=(node_of,))
         nodes, n = qd.shape
         m = l.shape[1]
         p = Rc.shape[1]
@@ -433,10 +385,8 @@ class Engine:
         ur = self._alloc(dev, (pieces, cap), np.float64)
         rows = self._alloc(dev, (pieces,), np.int32)
         flags = self._alloc(dev, (pieces,), np.int32)
-        rc = self.lib.qpn_reduced_pieces(self.ctx, pieces, nodes, n, m, p, _ptr(Qc), _ptr(Rc), _ptr(qd), _ptr(Ac), _ptr(Bc), _ptr(l),
-                                         _ptr(u), _ptr(node_of), _ptr(K), float(tol), _ptr(Ar), _ptr(lr), _ptr(ur), _ptr(rows),
-                                         _ptr(flags), MEM_DEVICE if dev else MEM_HOST)
-        self._chk(rc, "qpn_reduced_pieces")
+        self._call("qpn_reduced_pieces", pieces, nodes, n, m, p, _ptr(Qc), _ptr(Rc), _ptr(qd), _ptr(Ac), _ptr(Bc), _ptr(l), _ptr(u),
+                   _ptr(node_of), _ptr(K), float(tol), _ptr(Ar), _ptr(lr), _ptr(ur), _ptr(rows), _ptr(flags), self._mem(dev))
         return Ar, lr, ur, rows, flags
 
     # -- (A6) pool assembly ----------------------------------------------------------------------
@@ -449,15 +399,10 @@ class Engine:
         share_M (default: automatically when Qd and Ad are shared): write ONE M for the whole batch.
         Returns (Mc, q, lo, hi, kind) ready for solve_avi_batch (Mc (N, N) when shared)."""
         from ._lib import POOL_REDUCED, POOL_REFERENCE, PoolShape
-        dev = self._mode(Qd, Qp, qd, Ad, Bp, l, u, w)
-        self._bind_stream(dev)
+        dev, Qd, Qp, qd, Ad, Bp, l, u, w = self._stage("assemble_pools", "Qd Qp qd Ad Bp l u w", f64=(Qd, Qp, qd, Ad, Bp, l, u, w))
         n_i = np.ascontiguousarray(n_i, dtype=np.int32); m_i = np.ascontiguousarray(m_i, dtype=np.int32)
         dpos = np.ascontiguousarray(dpos, dtype=np.int32)
         sn, sm = int(n_i.sum()), int(m_i.sum())
-        if not dev:
-            Qd, Qp, qd, Ad, Bp, l, u, w = (self._host(a, np.float64) for a in (Qd, Qp, qd, Ad, Bp, l, u, w))
-        else:
-            self._require_dev64(Qd, Qp, qd, Ad, Bp, l, u, w)
         p = int(w.shape[-1])
         item_dims = dict(Qd=2, Qp=2, qd=1, Ad=2, Bp=2, l=1, u=1, w=1)
         arrs = dict(Qd=Qd, Qp=Qp, qd=qd, Ad=Ad, Bp=Bp, l=l, u=u, w=w)
@@ -492,11 +437,9 @@ class Engine:
         lout = self._alloc(dev, (batch, N), np.float64)
         uout = self._alloc(dev, (batch, N), np.float64)
         kind = self._alloc(dev, (batch, N), np.uint8)
-        rc = self.lib.qpn_assemble_pools(self.ctx, C.byref(shape), fcode, batch, _ptr(Qd), strides["Qd"], _ptr(Qp), strides["Qp"],
-                                         _ptr(qd), strides["qd"], _ptr(Ad), strides["Ad"], _ptr(Bp), strides["Bp"], _ptr(l), _ptr(u),
-                                         strides["l"], _ptr(w), strides["w"], _ptr(Mout), 0 if share_M else N * N, _ptr(qout),
-                                         _ptr(lout), _ptr(uout), _ptr(kind), MEM_DEVICE if dev else MEM_HOST)
-        self._chk(rc, "qpn_assemble_pools")
+        self._call("qpn_assemble_pools", C.byref(shape), fcode, batch, _ptr(Qd), strides["Qd"], _ptr(Qp), strides["Qp"], _ptr(qd),
+                   strides["qd"], _ptr(Ad), strides["Ad"], _ptr(Bp), strides["Bp"], _ptr(l), _ptr(u), strides["l"], _ptr(w),
+                   strides["w"], _ptr(Mout), 0 if share_M else N * N, _ptr(qout), _ptr(lout), _ptr(uout), _ptr(kind), self._mem(dev))
         return Mout, qout, lout, uout, kind
 
     # -- (A5+A6+A2+A3+A9 fused) --------------------------------------------------------------
@@ -507,76 +450,40 @@ class Engine:
         x_out (optional, [batch, >= n] fp64, rows may be strided): the primal blocks are also written
         there by the solve itself -- the outer sweep's x[decision_inds] = x_opt[decision_inds]
         (src/algorithm.jl:97-101)."""
-        dev = self._mode(Qc, Rc, qd, Ac, Bc, l, u, w, z0)
-        self._bind_stream(dev)
-        if not dev:
-            Qc, Rc, qd, Ac, Bc, l, u, w = (self._host(a, np.float64) for a in (Qc, Rc, qd, Ac, Bc, l, u, w))
-        else:
-            self._require_dev64(Qc, Rc, qd, Ac, Bc, l, u, w)
+        dev, Qc, Rc, qd, Ac, Bc, l, u, w, z0 = self._stage("solve_nodes", "Qc Rc qd Ac Bc l u w z0", f64=(Qc, Rc, qd, Ac, Bc, l, u, w, z0))
         batch, n = qd.shape
         m = l.shape[1]
         p = w.shape[-1]
         sw = 0 if w.ndim == 1 else p
-        N = n + m
-        o = opts if opts is not None else self.default_opts()
-        if out is not None and out["z"].shape == (batch, N):
-            z, status, resid, pivots, active = out["z"], out["status"], out["resid"], out["pivots"], out["active"]
-        else:
-            z = self._alloc(dev, (batch, N), np.float64)
-            status = self._alloc(dev, (batch,), np.int32)
-            resid = self._alloc(dev, (batch,), np.float64)
-            pivots = self._alloc(dev, (batch,), np.int32)
-            active = self._alloc(dev, (batch, N), np.uint8) if want_active else None
-        if z0 is None:
-            if opts is None:
-                o.flags |= _lib.AVI_FLAG_COLD_START
-            elif dev:
-                z.zero_()
-            else:
-                z[...] = 0.0
-        elif dev:
-            z.copy_(z0)
-        else:
-            z[...] = np.asarray(z0, dtype=np.float64)
+        res, o = self._solve_outputs(dev, batch, n + m, z0, opts, want_active, out)
         sx = self._x_stride(x_out, dev, batch, n)
-        rc = self.lib.qpn_solve_nodes_into(self.ctx, batch, n, m, p, _ptr(Qc), _ptr(Rc), _ptr(qd), _ptr(Ac),
-                                           _ptr(Bc), _ptr(l), _ptr(u), _ptr(w), sw, _ptr(z), _ptr(status),
-                                           _ptr(resid), _ptr(pivots), _ptr(active), C.byref(o),
-                                           MEM_DEVICE if dev else MEM_HOST, _ptr(x_out), sx)
-        self._chk(rc, "qpn_solve_nodes_into")
-        return dict(z=z, status=status, resid=resid, pivots=pivots, active=active)
+        self._call("qpn_solve_nodes_into", batch, n, m, p, _ptr(Qc), _ptr(Rc), _ptr(qd), _ptr(Ac), _ptr(Bc), _ptr(l), _ptr(u), _ptr(w),
+                   sw, _ptr(res["z"]), _ptr(res["status"]), _ptr(res["resid"]), _ptr(res["pivots"]), _ptr(res["active"]), C.byref(o),
+                   self._mem(dev), _ptr(x_out), sx)
+        return res
 
     def order_nodes_by_pivots(self, pivots):
         """Schedule hint for later solve_nodes calls over the SAME nodes: longest solves first, from the
         pivot counts of an earlier sweep (device or host int32 array).  Results do not depend on it."""
-        dev = self._mode(pivots)
-        self._bind_stream(dev)
-        if not dev:
-            pivots = self._host(pivots, np.int32)
-        rc = self.lib.qpn_order_nodes_by_pivots(self.ctx, _ptr(pivots), int(pivots.shape[0]),
-                                                MEM_DEVICE if dev else MEM_HOST)
-        self._chk(rc, "qpn_order_nodes_by_pivots")
+        dev, pivots = self._stage("order_nodes_by_pivots", "pivots", i32=(pivots,))
+        self._call("qpn_order_nodes_by_pivots", _ptr(pivots), int(pivots.shape[0]), self._mem(dev))
 
     def set_auto_schedule(self, period=16):
         """Period (in calls) of the context's own longest-first schedule refresh for solve_nodes batches that fill the
         GPU; 0 switches it off.  An explicit hint (order_nodes_by_pivots / set_node_order) takes precedence."""
-        self._chk(self.lib.qpn_ctx_set_auto_schedule(self.ctx, int(period)), "qpn_ctx_set_auto_schedule")
+        self._call("qpn_ctx_set_auto_schedule", int(period))
 
     def set_option(self, option, value):
         """Per-context route option (include/qpn_hip.h: QPN_OPT_*), e.g. set_option(OPT_MID_ROUTE, 2)."""
-        self._chk(self.lib.qpn_ctx_set_option(self.ctx, int(option), int(value)), "qpn_ctx_set_option")
+        self._call("qpn_ctx_set_option", int(option), int(value))
 
     def set_node_order(self, order=None):
         """Install a caller-made permutation of the nodes as the schedule (None clears the hint)."""
         if order is None:
-            self._chk(self.lib.qpn_set_node_order(self.ctx, None, 0, MEM_HOST), "qpn_set_node_order")
+            self._call("qpn_set_node_order", None, 0, self._mem(False))
             return
-        dev = self._mode(order)
-        self._bind_stream(dev)
-        if not dev:
-            order = self._host(order, np.int32)
-        rc = self.lib.qpn_set_node_order(self.ctx, _ptr(order), int(order.shape[0]), MEM_DEVICE if dev else MEM_HOST)
-        self._chk(rc, "qpn_set_node_order")
+        dev, order = self._stage("set_node_order", "order", i32=(order,))
+        self._call("qpn_set_node_order", _ptr(order), int(order.shape[0]), self._mem(dev))
 
     # -- (A8) ------------------------------------------------------------------------------
     # -- multi-GPU: shared iterate buffers, replicas, per-sweep status (include/qpn_hip.h) ----------
@@ -585,90 +492,73 @@ class Engine:
         from ._lib import IPC_HANDLE_BYTES, SHARED_FINE_GRAINED
         ptr = C.c_void_p()
         h = (C.c_uint8 * IPC_HANDLE_BYTES)()
-        rc = self.lib.qpn_shared_alloc(self.ctx, int(nbytes), SHARED_FINE_GRAINED if fine_grained else 0,
-                                       C.byref(ptr), h)
-        self._chk(rc, "qpn_shared_alloc")
+        self._call("qpn_shared_alloc", int(nbytes), SHARED_FINE_GRAINED if fine_grained else 0, C.byref(ptr), h)
         return int(ptr.value), bytes(h)
 
     def shared_open(self, handle: bytes) -> int:
         """Map a peer's shared buffer into this process; returns its address here."""
         ptr = C.c_void_p()
         h = (C.c_uint8 * len(handle)).from_buffer_copy(handle)
-        self._chk(self.lib.qpn_shared_open(self.ctx, h, C.byref(ptr)), "qpn_shared_open")
+        self._call("qpn_shared_open", h, C.byref(ptr))
         return int(ptr.value)
 
     def shared_close(self, addr: int):
-        self._chk(self.lib.qpn_shared_close(self.ctx, C.c_void_p(addr)), "qpn_shared_close")
+        self._call("qpn_shared_close", C.c_void_p(addr))
 
     def shared_free(self, addr: int):
-        self._chk(self.lib.qpn_shared_free(self.ctx, C.c_void_p(addr)), "qpn_shared_free")
+        self._call("qpn_shared_free", C.c_void_p(addr))
 
     def set_primal_mirrors(self, own_addr=0, nbytes=0, peer_addrs=()):
         """Later solve_nodes(x_out=...) calls whose x_out lies inside [own_addr, own_addr + nbytes) also store
         every primal block at the same offset of each peer buffer.  No arguments: clear."""
         arr = (C.c_void_p * max(len(peer_addrs), 1))(*[C.c_void_p(a) for a in peer_addrs])
-        rc = self.lib.qpn_set_primal_mirrors(self.ctx, C.c_void_p(own_addr), int(nbytes), len(peer_addrs), arr)
-        self._chk(rc, "qpn_set_primal_mirrors")
+        self._call("qpn_set_primal_mirrors", C.c_void_p(own_addr), int(nbytes), len(peer_addrs), arr)
 
     def sweep_status(self, status, resid, out, rank=0, world=1, boxes=None, epoch=0, timeout_ms=1000):
         """out[0:3] (device fp64, 4 entries) <- (items not solved, max resid, 1), combined over `world` ranks
         through their mailboxes when world > 1 (also the barrier after the replica stores); a missed barrier gives
         out[2] = 0 and out[3] += 1.  Asynchronous on the stream."""
-        self._bind_stream(True)
+        dev, status, resid, out = self._stage("sweep_status", "status resid out", i32=(status,), f64=(resid, out))
+        if not dev:
+            raise QpnError("sweep_status: device tensors only")
         arr = None
         if world > 1:
             arr = (C.c_void_p * world)(*[C.c_void_p(a) for a in boxes])
-        rc = self.lib.qpn_sweep_status(self.ctx, _ptr(status), _ptr(resid), int(status.shape[0]), _ptr(out),
-                                       int(rank), int(world), arr, int(epoch), int(timeout_ms))
-        self._chk(rc, "qpn_sweep_status")
+        self._call("qpn_sweep_status", _ptr(status), _ptr(resid), int(status.shape[0]), _ptr(out), int(rank), int(world), arr,
+                   int(epoch), int(timeout_ms))
         return out
 
     def verify_nodes(self, Qc, Rc, qd, Ac, Bc, l, u, xd, w, tol=1e-4):
         """Batched verify_solution (src/qp_processing.jl:57-149) -> (solution, lambda, path)."""
-        dev = self._mode(Qc, Rc, qd, Ac, Bc, l, u, xd, w)
-        self._bind_stream(dev)
-        if not dev:
-            Qc, Rc, qd, Ac, Bc, l, u, xd, w = (self._host(a, np.float64)
-                                               for a in (Qc, Rc, qd, Ac, Bc, l, u, xd, w))
-        else:
-            self._require_dev64(Qc, Rc, qd, Ac, Bc, l, u, xd, w)
+        dev, Qc, Rc, qd, Ac, Bc, l, u, xd, w = self._stage("verify_nodes", "Qc Rc qd Ac Bc l u xd w", f64=(Qc, Rc, qd, Ac, Bc, l, u, xd, w))
         batch, n = qd.shape
         m = l.shape[1]
         p = w.shape[-1]
-        sw = 0 if w.ndim == 1 else p
+        records = (batch, n, m, p, _ptr(Qc), _ptr(Rc), _ptr(qd), _ptr(Ac), _ptr(Bc), _ptr(l), _ptr(u))
+        return self._verify("qpn_verify_nodes", dev, records, batch, m, p, xd, w, tol)
+
+    def _verify(self, name, dev, records, batch, m, p, xd, w, tol):
+        """The common end of verify_nodes and Nodes.verify, which differ in where the records are (`records`: the arguments
+        that name them)."""
         sol = self._alloc(dev, (batch,), np.int32)
         path = self._alloc(dev, (batch,), np.int32)
         lam = self._alloc(dev, (batch, max(m, 1)), np.float64)
-        rc = self.lib.qpn_verify_nodes(self.ctx, batch, n, m, p, _ptr(Qc), _ptr(Rc), _ptr(qd),
-                                       _ptr(Ac), _ptr(Bc), _ptr(l), _ptr(u), _ptr(xd), _ptr(w), sw,
-                                       float(tol), _ptr(sol), _ptr(lam), _ptr(path),
-                                       MEM_DEVICE if dev else MEM_HOST)
-        self._chk(rc, "qpn_verify_nodes")
+        self._call(name, *records, _ptr(xd), _ptr(w), 0 if w.ndim == 1 else p, float(tol), _ptr(sol), _ptr(lam), _ptr(path),
+                   self._mem(dev))
         return sol, lam[:, :m], path
-
 
     def convexity_nodes(self, Qc, Ac, eq, tol=1e-6):
         """Batched check_qp_convexity (src/qp_processing.jl:39-55) on node blocks: Qc [batch, n, n] and Ac [batch, n, m] in
         the ABI layout, eq [batch, m] uint8 (the implicit equality rows) -> (convex [batch] int32, min_eig [batch],
         null_dim [batch] int32)."""
-        dev = self._mode(Qc, Ac, eq)
-        self._bind_stream(dev)
-        if not dev:
-            Qc, Ac = self._host(Qc, np.float64), self._host(Ac, np.float64)
-            eq = self._host(eq, np.uint8)
-        else:
-            self._require_dev64(Qc, Ac)
-            if eq.dtype != torch.uint8 or not eq.is_contiguous():
-                raise QpnError("eq must be a contiguous uint8 tensor")
+        dev, Qc, Ac, eq = self._stage("convexity_nodes", "Qc Ac eq", f64=(Qc, Ac), u8=(eq,))
         batch, n = Qc.shape[0], Qc.shape[-1]
         m = eq.shape[1]
         convex = self._alloc(dev, (batch,), np.int32)
         min_eig = self._alloc(dev, (batch,), np.float64)
         null_dim = self._alloc(dev, (batch,), np.int32)
-        rc = self.lib.qpn_convexity_nodes(self.ctx, batch, n, m, _ptr(Qc), _ptr(Ac) if m else None, _ptr(eq) if m else None,
-                                          float(tol), _ptr(convex), _ptr(min_eig), _ptr(null_dim),
-                                          MEM_DEVICE if dev else MEM_HOST)
-        self._chk(rc, "qpn_convexity_nodes")
+        self._call("qpn_convexity_nodes", batch, n, m, _ptr(Qc), _ptr(Ac) if m else None, _ptr(eq) if m else None, float(tol),
+                   _ptr(convex), _ptr(min_eig), _ptr(null_dim), self._mem(dev))
         return convex, min_eig, null_dim
 
     def multiplier_vertices(self, Ac, g, cls, lam0, V, max_bases=None, tol=1e-9, feas=1e-6):
@@ -676,15 +566,7 @@ class Engine:
         level_batch.multiplier_vertices_host is its numpy twin): Ac [batch, n, m] (Ad in the ABI layout), g [batch, n], cls
         [batch, m] uint8 (level_batch.MV_GE / LE / FREE / ZERO), lam0 [batch, m] the start, V the vertex budget, max_bases the
         basis budget (default 64 V).  Returns (verts [batch, V, m], count [batch] int32, status [batch] int32)."""
-        dev = self._mode(Ac, g, cls, lam0)
-        self._bind_stream(dev)
-        if not dev:
-            Ac, g, lam0 = (self._host(a, np.float64) for a in (Ac, g, lam0))
-            cls = self._host(cls, np.uint8)
-        else:
-            self._require_dev64(Ac, g, lam0)
-            if cls.dtype != torch.uint8 or not cls.is_contiguous():
-                raise QpnError("multiplier_vertices: cls must be a contiguous uint8 tensor")
+        dev, Ac, g, lam0, cls = self._stage("multiplier_vertices", "Ac g lam0 cls", f64=(Ac, g, lam0), u8=(cls,))
         batch, n, m = (int(v) for v in Ac.shape)
         V = int(V)
         mb = 64 * max(V, 1) if max_bases is None else int(max_bases)
@@ -693,25 +575,18 @@ class Engine:
         verts = self._alloc(dev, (batch, V, m), np.float64)
         count = self._alloc(dev, (batch,), np.int32)
         status = self._alloc(dev, (batch,), np.int32)
-        rc = self.lib.qpn_multiplier_vertices(self.ctx, batch, n, m, _ptr(Ac), _ptr(g), _ptr(cls), _ptr(lam0), V, mb, float(tol),
-                                              float(feas), _ptr(verts), _ptr(count), _ptr(status), MEM_DEVICE if dev else MEM_HOST)
-        self._chk(rc, "qpn_multiplier_vertices")
+        self._call("qpn_multiplier_vertices", batch, n, m, _ptr(Ac), _ptr(g), _ptr(cls), _ptr(lam0), V, mb, float(tol), float(feas),
+                   _ptr(verts), _ptr(count), _ptr(status), self._mem(dev))
         return verts, count, status
 
     def recipe_filter(self, masks, K, vrow_of, first_of):
         """qpn_recipe_filter (level_batch.recipe_filter_host is its numpy twin): keep [pieces] uint8, 0 for a recipe K[t] of
         product row vrow_of[t] that an earlier product row of the same item (first_of[row] <= s < row) holds."""
-        dev = self._mode(masks, K, vrow_of, first_of)
-        self._bind_stream(dev)
-        if not dev:
-            masks, K = self._host(masks, np.uint8), self._host(K, np.uint8)
-            vrow_of, first_of = self._host(vrow_of, np.int32), self._host(first_of, np.int32)
+        dev, masks, K, vrow_of, first_of = self._stage("recipe_filter", "masks K vrow_of first_of", u8=(masks, K), i32=(vrow_of, first_of))
         rows, N = int(masks.shape[0]), int(masks.shape[1])
         pieces = int(K.shape[0])
         keep = self._alloc(dev, (pieces,), np.uint8)
-        rc = self.lib.qpn_recipe_filter(self.ctx, pieces, rows, N, _ptr(masks), _ptr(K), _ptr(vrow_of), _ptr(first_of), _ptr(keep),
-                                        MEM_DEVICE if dev else MEM_HOST)
-        self._chk(rc, "qpn_recipe_filter")
+        self._call("qpn_recipe_filter", pieces, rows, N, _ptr(masks), _ptr(K), _ptr(vrow_of), _ptr(first_of), _ptr(keep), self._mem(dev))
         return keep
 
 
@@ -726,19 +601,13 @@ class Nodes:
 
     def __init__(self, eng: "Engine", Qc, Rc, qd, Ac, Bc, l, u):
         self.eng = eng
-        dev = eng._mode(Qc, Rc, qd, Ac, Bc, l, u)
-        eng._bind_stream(dev)
-        if not dev:
-            Qc, Rc, qd, Ac, Bc, l, u = (eng._host(a, np.float64) for a in (Qc, Rc, qd, Ac, Bc, l, u))
-        else:
-            eng._require_dev64(Qc, Rc, qd, Ac, Bc, l, u)
+        dev, Qc, Rc, qd, Ac, Bc, l, u = eng._stage("upload_nodes", "Qc Rc qd Ac Bc l u", f64=(Qc, Rc, qd, Ac, Bc, l, u))
         self.batch, self.n = qd.shape
         self.m = l.shape[1]
         self.p = Rc.shape[1]
         h = C.c_void_p()
-        rc = eng.lib.qpn_nodes_upload(eng.ctx, self.batch, self.n, self.m, self.p, _ptr(Qc), _ptr(Rc), _ptr(qd), _ptr(Ac),
-                                      _ptr(Bc), _ptr(l), _ptr(u), MEM_DEVICE if dev else MEM_HOST, C.byref(h))
-        eng._chk(rc, "qpn_nodes_upload")
+        eng._call("qpn_nodes_upload", self.batch, self.n, self.m, self.p, _ptr(Qc), _ptr(Rc), _ptr(qd), _ptr(Ac), _ptr(Bc), _ptr(l),
+                  _ptr(u), eng._mem(dev), C.byref(h))
         self.h = h
         self._fast = None
 
@@ -755,23 +624,17 @@ class Nodes:
 
     def update(self, field: str, data):
         """Replace one array of the records (same shape), e.g. the bounds after another child piece was chosen."""
-        dev = self.eng._mode(data)
-        self.eng._bind_stream(dev)
-        if not dev:
-            data = self.eng._host(data, np.float64)
-        else:
-            self.eng._require_dev64(data)
-        rc = self.eng.lib.qpn_nodes_update(self.eng.ctx, self.h, self.FIELDS[field], _ptr(data), MEM_DEVICE if dev else MEM_HOST)
-        self.eng._chk(rc, "qpn_nodes_update")
+        dev, data = self.eng._stage("Nodes.update", "data", f64=(data,))
+        self.eng._call("qpn_nodes_update", self.h, self.FIELDS[field], _ptr(data), self.eng._mem(dev))
 
     def info(self):
         """dict(decline_state, declined, scheduled, symmetric, sweeps) -- see qpn_nodes_info."""
         a = (C.c_int32 * 4)()
-        self.eng._chk(self.eng.lib.qpn_nodes_info(self.eng.ctx, self.h, a), "qpn_nodes_info")
+        self.eng._call("qpn_nodes_info", self.h, a)
         return dict(decline_state=a[0], declined=a[1], scheduled=bool(a[2] & 1), symmetric=bool(a[2] & 2), sweeps=a[3])
 
     def set_schedule(self, period=16):
-        self.eng._chk(self.eng.lib.qpn_nodes_set_schedule(self.eng.ctx, self.h, int(period)), "qpn_nodes_set_schedule")
+        self.eng._call("qpn_nodes_set_schedule", self.h, int(period))
 
     def solve(self, w, opts=None, want=("z", "resid", "pivots", "active"), out=None, x_out=None):
         """One sweep over the resident nodes with parameters w ((p,) shared or (batch, p)); cold duals.  `want` names the
@@ -794,10 +657,9 @@ class Nodes:
                 eng._chk(rc, "qpn_solve_nodes_h")
                 return out
             self._fast = None
-        dev = eng._mode(w, x_out)
-        eng._bind_stream(dev)
+        dev, = eng._stage("Nodes.solve", "", raw=(w, x_out))    # (w has its own rule: its rows may be strided)
         if not dev:
-            w = eng._host(w, np.float64)
+            w = np.ascontiguousarray(w, dtype=np.float64)
         elif w.dtype != torch.float64 or w.stride(-1) != 1:
             raise QpnError("w must be a float64 tensor with unit inner stride")
         N = self.n + self.m
@@ -834,9 +696,8 @@ class Nodes:
                        active=eng._alloc(dev, (self.batch, N), np.uint8) if "active" in want else None)
         sx = eng._x_stride(x_out, dev, self.batch, self.n)
         tail = (_ptr(out["z"]), _ptr(out["status"]), _ptr(out["resid"]), _ptr(out["pivots"]), _ptr(out["active"]), C.byref(o),
-                MEM_DEVICE if dev else MEM_HOST, _ptr(x_out), sx)
-        rc = eng.lib.qpn_solve_nodes_h(eng.ctx, self.h, _ptr(w), sw, *tail)
-        eng._chk(rc, "qpn_solve_nodes_h")
+                eng._mem(dev), _ptr(x_out), sx)
+        eng._call("qpn_solve_nodes_h", self.h, _ptr(w), sw, *tail)
         if dev and opts is None:
             # (o is kept alive: tail holds a reference to it; the tensors the addresses in `tail` came from are recorded with
             #  those addresses, so that the fast path above can tell when they are no longer what they were)
@@ -846,21 +707,8 @@ class Nodes:
         return out
 
     def verify(self, xd, w, tol=1e-4):
-        eng = self.eng
-        dev = eng._mode(xd, w)
-        eng._bind_stream(dev)
-        if not dev:
-            xd, w = eng._host(xd, np.float64), eng._host(w, np.float64)
-        else:
-            eng._require_dev64(xd, w)
-        sw = 0 if w.ndim == 1 else self.p
-        sol = eng._alloc(dev, (self.batch,), np.int32)
-        path = eng._alloc(dev, (self.batch,), np.int32)
-        lam = eng._alloc(dev, (self.batch, max(self.m, 1)), np.float64)
-        rc = eng.lib.qpn_verify_nodes_h(eng.ctx, self.h, _ptr(xd), _ptr(w), sw, float(tol), _ptr(sol), _ptr(lam), _ptr(path),
-                                        MEM_DEVICE if dev else MEM_HOST)
-        eng._chk(rc, "qpn_verify_nodes_h")
-        return sol, lam[:, :self.m], path
+        dev, xd, w = self.eng._stage("Nodes.verify", "xd w", f64=(xd, w))
+        return self.eng._verify("qpn_verify_nodes_h", dev, (self.h,), self.batch, self.m, self.p, xd, w, tol)
 
 
 _default = {}

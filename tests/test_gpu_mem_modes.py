@@ -1,6 +1,7 @@
 """Host buffers against device buffers: every C-ABI entry point that takes a `mem` argument gives bitwise the same outputs for
 the same inputs passed as numpy arrays (QPN_MEM_HOST, staged through the context's workspace) and as torch device tensors
-(QPN_MEM_DEVICE, handed to the kernels as they are), on every route and size class.  A `mem` that is neither is refused."""
+(QPN_MEM_DEVICE, handed to the kernels as they are), on every route and size class.  A `mem` that is neither is refused, and so
+is a device tensor that is not what the header declares for its argument."""
 import numpy as np
 import pytest
 
@@ -236,4 +237,57 @@ def test_unknown_mem_kind_is_refused(engine, monkeypatch, entry):
     finally:
         monkeypatch.undo()
         nodes.close()
+        engine.set_node_order(None)
+
+
+def _typed_device_args(engine):
+    """case -> (entry point, a well-formed device tensor for the argument, the call with that argument replaced)."""
+    import torch
+    zeros = lambda *s, dt=torch.float64: torch.zeros(s, dtype=dt, device=DEV)     # noqa: E731
+    n, m, N = 8, 4, 12
+    rec = [_dev(a) for a in _records(4, n, m, 3)[:7]]
+    Mc, q = zeros(4, N, N), zeros(4, N)
+    K, masks, kind = (zeros(4, N, dt=torch.uint8) for _ in range(3))
+    idx = zeros(4, dt=torch.int32)
+    return {
+        "local_pieces: K": ("qpn_local_pieces", K, lambda a: engine.local_pieces(*rec, a, node_of=idx)),
+        "local_pieces: node_of": ("qpn_local_pieces", idx, lambda a: engine.local_pieces(*rec, K, node_of=a)),
+        "reduced_pieces: K": ("qpn_reduced_pieces", K, lambda a: engine.reduced_pieces(*rec, a, node_of=idx)),
+        "reduced_pieces: node_of": ("qpn_reduced_pieces", idx, lambda a: engine.reduced_pieces(*rec, K, node_of=a)),
+        "recipes_from_masks: mask": ("qpn_recipes_from_masks", masks[0], lambda a: engine.recipes_from_masks(a)),
+        "recipes_batch: masks": ("qpn_recipes_batch", masks, lambda a: engine.recipes_batch(a, np.arange(5, dtype=np.int64))),
+        "solve_avi_batch: kind": ("qpn_solve_avi_batch", kind, lambda a: engine.solve_avi_batch(Mc, q, q, q, kind=a)),
+        "check_avi_batch: kind": ("qpn_check_avi_batch", kind, lambda a: engine.check_avi_batch(Mc, q, q, q, q, kind=a)),
+        "recipe_filter: masks": ("qpn_recipe_filter", masks, lambda a: engine.recipe_filter(a, K, idx, idx)),
+        "recipe_filter: K": ("qpn_recipe_filter", K, lambda a: engine.recipe_filter(masks, a, idx, idx)),
+        "recipe_filter: vrow_of": ("qpn_recipe_filter", idx, lambda a: engine.recipe_filter(masks, K, a, idx)),
+        "recipe_filter: first_of": ("qpn_recipe_filter", idx, lambda a: engine.recipe_filter(masks, K, idx, a)),
+        "order_nodes_by_pivots: pivots": ("qpn_order_nodes_by_pivots", idx, lambda a: engine.order_nodes_by_pivots(a)),
+        "set_node_order: order": ("qpn_set_node_order", idx, lambda a: engine.set_node_order(a)),
+    }
+
+
+@pytest.mark.parametrize("case", ["local_pieces: K", "local_pieces: node_of", "reduced_pieces: K", "reduced_pieces: node_of",
+                                  "recipes_from_masks: mask", "recipes_batch: masks", "solve_avi_batch: kind", "check_avi_batch: kind",
+                                  "recipe_filter: masks", "recipe_filter: K", "recipe_filter: vrow_of", "recipe_filter: first_of",
+                                  "order_nodes_by_pivots: pivots", "set_node_order: order"])
+def test_mistyped_device_argument_is_refused(engine, case):
+    """A device tensor goes to the kernels as a raw address, so every method refuses one that is not what include/qpn_hip.h
+    declares -- another integer type, a strided view, another GPU's memory -- before the library is called.  Each bad tensor
+    is zeros over at least the bytes of the well-formed one."""
+    import torch
+    from qpn_amd.engine import QpnError
+    entry, good, call = _typed_device_args(engine)[case]
+    bad = [torch.zeros(good.shape, dtype=torch.int64, device=DEV),
+           torch.zeros((*good.shape[:-1], 2 * good.shape[-1]), dtype=good.dtype, device=DEV)[..., ::2]]
+    assert bad[1].shape == good.shape and not bad[1].is_contiguous()
+    if torch.cuda.device_count() >= 2:
+        bad.append(good.to("cuda:1"))
+    before = engine.calls[entry]
+    try:
+        for a in bad:
+            with pytest.raises(QpnError, match=f"{case} must be a contiguous"):
+                call(a)
+        assert engine.calls[entry] == before
+    finally:
         engine.set_node_order(None)
