@@ -201,7 +201,13 @@ int qpn_solve_nodes_into(qpn_ctx *ctx, int32_t batch, int32_t n, int32_t m, int3
  * launch, and the longest-first schedule of its nodes (from exponentially smoothed pivot counts, which every sweep's
  * solve kernel updates; the order is re-sorted from them every `period` sweeps at first and every 4 x `period` once
  * settled; qpn_nodes_set_schedule, period 0 = natural order).
- * qpn_nodes_update replaces one array of the records (e.g. the bounds after a new child piece was chosen). */
+ * qpn_nodes_update replaces one array of the records (e.g. the bounds after a new child piece was chosen).
+ * Symmetric n = m = 32 records also keep the part of the solve that Qd and Ad alone decide (QPN_OPT_CRASH_CACHE): the first
+ * sweep stores it, the later ones reuse it, with bit-identical results.  Cost in HBM: the records are 22 KB per n = m = 32
+ * node, the crash cache adds 22 KB per node (symmetric records; the general variants -- 24 KB -- are not cached).  It is allocated
+ * by the first sweep that would use it; when that memory cannot be had the handle runs uncached.  qpn_nodes_update of
+ * QPN_NODE_QD or QPN_NODE_AD (and a change of QPN_OPT_SYM_ROUTE) drops it, the next sweep fills it again; updates of R, qd, B,
+ * l, u keep it. */
 typedef struct qpn_nodes qpn_nodes;
 enum { QPN_NODE_QD = 0, QPN_NODE_R = 1, QPN_NODE_Q = 2, QPN_NODE_AD = 3, QPN_NODE_B = 4, QPN_NODE_L = 5, QPN_NODE_U = 6 };
 int qpn_nodes_upload(qpn_ctx *ctx, int32_t batch, int32_t n, int32_t m, int32_t p, const double *Qd,
@@ -213,8 +219,9 @@ int qpn_nodes_free(qpn_ctx *ctx, qpn_nodes *nodes);
 /* info[0] = what is known about the general kernel's share of these records: 0 nothing yet, 1 the count of the first
  * sweep is on its way to the host, 2 no node needs it (sweeps are one launch), 3 some do; info[1] = that count (valid
  * in states 2, 3); info[2] = bit 0: a longest-first schedule is installed, bit 1: every Qd block of the records is bitwise
- * symmetric (settled by one pass when the records arrive or Qd is replaced; QPN_OPT_SYM_ROUTE); info[3] = sweeps since the
- * last schedule reset. */
+ * symmetric (settled by one pass when the records arrive or Qd is replaced; QPN_OPT_SYM_ROUTE), bit 2: a valid crash cache is
+ * installed, bit 3: the crash cache is refused (QPN_OPT_CRASH_CACHE = 0, records of a shape or route that is not cached, or its
+ * memory could not be had); info[3] = sweeps since the last schedule reset. */
 int qpn_nodes_info(qpn_ctx *ctx, qpn_nodes *nodes, int32_t info[4]);
 int qpn_solve_nodes_h(qpn_ctx *ctx, qpn_nodes *nodes, const double *w, int64_t stride_w, double *z,
                       int32_t *status, double *resid, int32_t *pivots, uint8_t *active,
@@ -258,11 +265,17 @@ int qpn_ctx_set_auto_schedule(qpn_ctx *ctx, int32_t period);
  *                      number of complementarity pairs switched; with a caller-set max_pivots the Lemke kernel, whose pivots
  *                      that budget counts, runs alone), 0 = the general variants.  Records with any asymmetric Qd, and records
  *                      passed per call, always take the general variants.
+ *   QPN_OPT_CRASH_CACHE resident symmetric n = m = 32 records on the symmetric route: 1 = the first sweep over a handle stores
+ *                      what the crash makes of Qd and Ad alone (panels, W~ = -H^-1 C, S = A H^-1 A', pivot-test verdicts; 22 KB
+ *                      per node) and later sweeps reuse it instead of recomputing it (default), 0 = never.  The cached sweeps
+ *                      perform the parameter-dependent operations in the same order on the same numbers: results are
+ *                      bit-identical either way, and the same nodes decline.
  * A resident handle remembers under which option values it learned that none of its nodes declines; after a change it asks again
  * on its next sweep (another kernel variant applies its pivot test to slightly different numbers). */
 #define QPN_OPT_MID_ROUTE 1
 #define QPN_OPT_BIG_ROUTE 2
 #define QPN_OPT_SYM_ROUTE 3
+#define QPN_OPT_CRASH_CACHE 4
 int qpn_ctx_set_option(qpn_ctx *ctx, int32_t option, int32_t value);
 
 /* ---- multi-GPU: replicas of the iterate on peer GPUs, written by the solve itself -----------------------

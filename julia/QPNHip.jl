@@ -415,7 +415,10 @@ clear_node_order!() = (ccall((:qpn_set_node_order, LIB), Cint, (Ptr{Cvoid}, Ptr{
 # SYM_ROUTE 1 = resident records whose Qd blocks are all bitwise symmetric take the kernel variants that use it (default), 0 = never.
 const QPN_OPT_MID_ROUTE = Int32(1)
 const QPN_OPT_BIG_ROUTE = Int32(2)
+# CRASH_CACHE 1 = resident symmetric n = m = 32 records keep the part of the crash that Qd and Ad alone decide across sweeps
+# (22 KB of HBM per node on top of the 22 KB of records; bit-identical results; default), 0 = never.
 const QPN_OPT_SYM_ROUTE = Int32(3)
+const QPN_OPT_CRASH_CACHE = Int32(4)
 function set_option!(option::Integer, value::Integer)
     rc = ccall((:qpn_ctx_set_option, LIB), Cint, (Ptr{Cvoid}, Int32, Int32), ctx(), Int32(option), Int32(value))
     rc == 0 || error("qpn_ctx_set_option failed ($rc)")

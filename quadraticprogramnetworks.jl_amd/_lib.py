@@ -34,6 +34,7 @@ SWEEP_BOX_BYTES = 512
 OPT_MID_ROUTE = 1
 OPT_BIG_ROUTE = 2
 OPT_SYM_ROUTE = 3
+OPT_CRASH_CACHE = 4
 
 
 class LibraryMissing(RuntimeError):

@@ -57,9 +57,15 @@ constexpr int kResidentMI355X = 16 * 256;      // wavefronts of this kernel resi
 // SYM: every Qd of the launch is bitwise symmetric (settled once for resident records, qpn_nodes_upload): the lower-left tile
 // of H is never loaded or updated -- its pivot columns are the pivot rows of the upper-right tile --, and the lower-left tile
 // of S = A H^-1 A' is the transpose of the upper-right one: 8 of the 88 fp64 MFMAs per solve less.
-template <bool NODES, int STAGGER = 0, int SHAPE = 0, bool SYM = false>
+// CRASH (resident symmetric n = m = 32 records only): Stage A does not depend on the sweep's parameters -- w enters through
+// q alone, and of Stage A's products only the extra column kx (g -> h = H^-1 g) carries q.  0 = compute, keep nothing;
+// 1 = compute and STORE the panels U' of the eight steps, the tiles W~ and S(0,0), S(0,1), S(1,1) and a pass / fail flag in
+// the handle's crash cache (layout: qpn_internal.h, kCrash*); 2 = REUSE them: no Qd staging, no factorisation, no MFMA --
+// kx is replayed with the stored U' by the same operations in the same order, so every output has the same bits.
+template <bool NODES, int STAGGER = 0, int SHAPE = 0, bool SYM = false, int CRASH = 0>
 __global__ __launch_bounds__(WAVE, 4) void avi_solve_schur(AviBatchArgs a, SchurDebug dbg)
 {
+    static_assert(CRASH == 0 || (NODES && SHAPE == 32 && SYM), "the crash cache exists for symmetric n = m = 32 node records");
     static_assert(SHAPE == 0 || SHAPE == 16 || SHAPE == 32, "compile-time shapes: 16 and 32");
     static_assert(!SYM || (NODES && SHAPE == 32), "the symmetric variant exists for n = m = 32 node records");
     static_assert(NODES || SHAPE != 16, "explicit M: N alone settles the split only at N = 64");
@@ -205,6 +211,78 @@ __global__ __launch_bounds__(WAVE, 4) void avi_solve_schur(AviBatchArgs a, Schur
 #define M_DECL(I, J) d4 TL(I, J);
     FOR_IJ(M_DECL)
 #undef M_DECL
+    double kx;                                  // extra column: g = q of the x rows, then h = H^-1 g (lanes 0..31)
+#define SB(Ib, Jb) sb_##Ib##_##Jb
+    d4 SB(0, 0), SB(0, 1), SB(1, 0), SB(1, 1);
+    double lo_pre = -QINF, hi_pre = QINF;       // bounds of pair l for Stage B
+    // this node's slice of the crash cache (addresses read from the kernarg segment on the spot, not kept in registers)
+    auto crash_base = [&]() -> double * {
+        typedef const AviBatchArgs __attribute__((address_space(4))) *kargs_c;
+        return ((kargs_c)__builtin_amdgcn_kernarg_segment_ptr())->crash + (size_t)b * kCrashDoubles;
+    };
+    // the value lane (l & 31) + 32 holds, on every lane (ds_bpermute: the LDS crossbar, no memory)
+    auto from_upper_half = [&](double v) -> double {
+        const int src = ((l & 31) + 32) * 4;
+        return __hiloint2double(__builtin_amdgcn_ds_bpermute(src, __double2hiint(v)), __builtin_amdgcn_ds_bpermute(src, __double2loint(v)));
+    };
+    auto crash_flag = [&]() -> uint8_t * {
+        typedef const AviBatchArgs __attribute__((address_space(4))) *kargs_c;
+        return ((kargs_c)__builtin_amdgcn_kernarg_segment_ptr())->crash_flag + b;
+    };
+    if constexpr (CRASH == 2) {
+        // ---- reuse.  ONE round of loads brings everything Stage B needs (each further dependent round trip costs a wave as much
+        // as the crash it replaces): Ad, U', S, the bounds and q.  To fit the registers, Ad goes straight into the LDS block
+        // buffer (LDS-DMA, one column of 32 rows = 256 B per instruction, lane <-> 4 bytes: the padded column stride stays) and
+        // U' is split over the two halves of the wavefront: lane l holds steps 0..3 of row l, lane l + 32 steps 4..7 of row l.
+        const uint8_t fl = *crash_flag();
+        const double *const cc = crash_base();
+        {
+            typedef const __attribute__((address_space(1))) void *gptr_t;
+            typedef __attribute__((address_space(3))) void *lptr_t;
+            const char *const ga = reinterpret_cast<const char *>(A_) + l * 4;
+#pragma unroll
+            for (int cj = 0; cj < 32; ++cj)
+                __builtin_amdgcn_global_load_lds((gptr_t)(ga + cj * 256), (lptr_t)(sA + cj * SAS), 4, 0, 0);
+        }
+        const double *const cu = cc + kCrashU + (l >> 5) * 512 + (l & 31) * 4;
+        d4 up0 = *reinterpret_cast<const d4 *>(cu), up1 = *reinterpret_cast<const d4 *>(cu + 128);
+        d4 up2 = *reinterpret_cast<const d4 *>(cu + 256), up3 = *reinterpret_cast<const d4 *>(cu + 384);
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            SB(0, 0)[g] = cc[kCrashS + ((0 * 4 + g) * 64 + l)];
+            SB(0, 1)[g] = cc[kCrashS + ((1 * 4 + g) * 64 + l)];
+            SB(1, 1)[g] = cc[kCrashS + ((2 * 4 + g) * 64 + l)];
+        }
+        if (l < 32) { lo_pre = a.nd.l[(size_t)b * 32 + l]; hi_pre = a.nd.u[(size_t)b * 32 + l]; }
+        const double ql = qelem(l);
+        // (the LDS-DMA writes are ordered for the readers below by this wait: they count on vmcnt like the loads)
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        // a node whose pivot test failed when the cache was filled declines as it did then (and is counted the same way)
+        if (ubool(fl != 1)) { decline(); return; }
+        SQ(l) = ql;
+        wave_sync();
+        kx = (l < 32) ? ql : 0.0;
+        // kx += U'[l] . kx[p0 .. p0 + 3], step by step: M_USOLVE's update with the stored panel
+#define M_REPLAY(KB, UP)                                                                            \
+        {                                                                                           \
+            const double x0 = readlane_f64(kx, 4 * (KB)), x1 = readlane_f64(kx, 4 * (KB) + 1);      \
+            const double x2 = readlane_f64(kx, 4 * (KB) + 2), x3 = readlane_f64(kx, 4 * (KB) + 3);  \
+            if (l < 32) {                                                                           \
+                const double t_ = fma(UP[3], x3, fma(UP[2], x2, fma(UP[1], x1, UP[0] * x0)));       \
+                kx = kx + t_;                                                                       \
+            }                                                                                       \
+        }
+        M_REPLAY(0, up0) M_REPLAY(1, up1) M_REPLAY(2, up2) M_REPLAY(3, up3)
+        // steps 4..7 come over from the upper half (data movement only)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            up0[k] = from_upper_half(up0[k]); up1[k] = from_upper_half(up1[k]);
+            up2[k] = from_upper_half(up2[k]); up3[k] = from_upper_half(up3[k]);
+        }
+        M_REPLAY(4, up0) M_REPLAY(5, up1) M_REPLAY(6, up2) M_REPLAY(7, up3)
+#undef M_REPLAY
+        if (l < 32) sz[l] = kx;
+    } else {
     double mabs = 0.0;
     if constexpr (NODES) {
         // Qd and Ad with fully coalesced loads (two columns of 32 rows per instruction = 512 contiguous
@@ -341,7 +419,6 @@ __global__ __launch_bounds__(WAVE, 4) void avi_solve_schur(AviBatchArgs a, Schur
         // (the first reader of A is behind the wave_syncs of Stage A)
     }
     // extra column: g = q of the x rows, lane l <-> row l of the top half (lanes >= 32 idle)
-    double kx;
     if constexpr (NODES) kx = (l < n) ? SQ(l) : 0.0; else kx = (l < n) ? qelem(l) : 0.0;
     double *const sP = sbuf + 128;              // Stage A: the 4 x 4 pivot block of the current step, raw (the sz block is idle)
     const double mscale = wave_max_f64(mabs);
@@ -402,6 +479,7 @@ __global__ __launch_bounds__(WAVE, 4) void avi_solve_schur(AviBatchArgs a, Schur
                 kx = NEGF ? kx + t_ : kx - t_;                                                  \
             }                                                                                   \
             *reinterpret_cast<d4 *>(sU + lr_ * 4) = up;                                         \
+            if constexpr (CRASH == 1) *reinterpret_cast<d4 *>(crash_base() + kCrashU + (p0 * 8 + lr_) * 4) = up; \
         }
 #define M_STEP(KB, JP, GP)                                                                          \
     if (!fail && 4 * (KB) < n) {       /* a block of padded rows is an identity pivot: nothing moves */ \
@@ -463,12 +541,20 @@ __global__ __launch_bounds__(WAVE, 4) void avi_solve_schur(AviBatchArgs a, Schur
 #undef FMS
 #undef M_COLTILE
 #undef M_GATHER
+    if constexpr (CRASH == 1) { if (l == 0) *crash_flag() = fail ? 2 : 1; }
     if (fail) { decline(); return; }
+    if constexpr (CRASH == 1) {
+        // W~ is final: tile register g of tile t at ((4 t + g) * 64 + lane), 512 contiguous bytes per store
+        double *const cw = crash_base() + kCrashW;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            cw[(0 * 4 + g) * 64 + l] = TL(0, 2)[g]; cw[(1 * 4 + g) * 64 + l] = TL(0, 3)[g];
+            cw[(2 * 4 + g) * 64 + l] = TL(1, 2)[g]; cw[(3 * 4 + g) * 64 + l] = TL(1, 3)[g];
+        }
+    }
 
     // ---- S = D - A W on the matrix cores, c = b - A h -----------------------------------------------------
     // W = TL(0..1, 2..3) (rows = x, an aligned group of 4 rows is a B operand), h = kx (lanes 0..31).
-#define SB(Ib, Jb) sb_##Ib##_##Jb
-    d4 SB(0, 0), SB(0, 1), SB(1, 0), SB(1, 1);
     if (l < 32) sz[l] = kx;
     if constexpr (NODES) {
         const d4 z4 = {0.0, 0.0, 0.0, 0.0};
@@ -509,13 +595,20 @@ __global__ __launch_bounds__(WAVE, 4) void avi_solve_schur(AviBatchArgs a, Schur
         }                                                                                           \
     }
     // bounds of pair l for Stage B: requested here so that the round trip hides behind the 32 MFMAs
-    double lo_pre = -QINF, hi_pre = QINF;
     if constexpr (NODES) {
         if (l < m) { lo_pre = a.nd.l[(size_t)b * nm + l]; hi_pre = a.nd.u[(size_t)b * nm + l]; }
     }
     M_SK(0, 0, 0) M_SK(0, 1, 1) M_SK(0, 2, 2) M_SK(0, 3, 3) M_SK(1, 0, 4) M_SK(1, 1, 5) M_SK(1, 2, 6) M_SK(1, 3, 7)
 #undef M_SK
 #undef M_SACC
+    if constexpr (CRASH == 1) {
+        double *const cs = crash_base() + kCrashS;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            cs[(0 * 4 + g) * 64 + l] = SB(0, 0)[g]; cs[(1 * 4 + g) * 64 + l] = SB(0, 1)[g]; cs[(2 * 4 + g) * 64 + l] = SB(1, 1)[g];
+        }
+    }
+    }   // (CRASH != 2)
     if constexpr (SYM) {
         // S(1,0) = S(0,1)'.  (Also exact and 0.5 % slower: on the matrix cores -- register kb of a tile in the accumulator layout IS
         // the A operand of its transpose's k-block kb, element (i = lc, k = lq) = X[4 kb + lq][lc], with B = rows 4 kb .. 4 kb + 3
@@ -562,7 +655,7 @@ __global__ __launch_bounds__(WAVE, 4) void avi_solve_schur(AviBatchArgs a, Schur
     }
     STAMP(6);   // crash on the matrix cores
 
-    if (dbg.S) {
+    if constexpr (CRASH != 2) if (dbg.S) {
         // diagnostic builds: dump S (32x32), c, W (32x32), h in row-major
 #define M_DUMPW(I, J)                                                                               \
     _Pragma("unroll") for (int g = 0; g < 4; ++g) {                                                 \
@@ -617,6 +710,25 @@ __global__ __launch_bounds__(WAVE, 4) void avi_solve_schur(AviBatchArgs a, Schur
     int rowvar = actb ? l : -1, colvar = actb ? NBP + l : (l == XC ? VTH : -1);
     double nbval = 0.0, tcol = 0.0;
     wave_sync();                      // Stage A and the c sweep are done with sbuf
+    // the fixed bounds of pair k as the pivot loop asks for them (wave-uniform k).  Reuse variant: they wait in the idle sz block
+    // of sbuf instead of three register pairs, and h waits for the read-back in sbuf[96 .. 127] (idle from here on: the
+    // transposition of S is done with it) -- the registers W~ arrives in while the loop runs
+    if constexpr (CRASH == 2) { if (actb) { sbuf[128 + l] = lo0; sbuf[160 + l] = hi0; sbuf[96 + l] = kx; } }
+    auto lo0_of = [&](int k) -> double { if constexpr (CRASH == 2) return udbl(sbuf[128 + k]); else return readlane_f64(lo0, k); };
+    auto hi0_of = [&](int k) -> double { if constexpr (CRASH == 2) return udbl(sbuf[160 + k]); else return readlane_f64(hi0, k); };
+    auto rng_of = [&](int k) -> double {
+        if constexpr (CRASH == 2) return udbl(sbuf[160 + k]) - udbl(sbuf[128 + k]); else return readlane_f64(rngv, k);
+    };
+    if constexpr (CRASH == 2) {
+        // W~ is needed by the read-back only: requested here, it arrives behind the pivot loop (in the registers the computing
+        // variants keep it in)
+        const double *const cw = crash_base() + kCrashW;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            TL(0, 2)[g] = cw[(0 * 4 + g) * 64 + l]; TL(0, 3)[g] = cw[(1 * 4 + g) * 64 + l];
+            TL(1, 2)[g] = cw[(2 * 4 + g) * 64 + l]; TL(1, 3)[g] = cw[(3 * 4 + g) * 64 + l];
+        }
+    }
 
     // the dictionary as two 8-vectors per lane: element 4 Ib + g of SJ<Jb> = row 16 Ib + 4 g + lq, column
     // 16 Jb + lc.  Static element accesses are plain registers; the pivot row is read with a wave-uniform
@@ -710,7 +822,7 @@ __global__ __launch_bounds__(WAVE, 4) void avi_solve_schur(AviBatchArgs a, Schur
             else {
                 const int k = ve;
                 const int au = sneg ? 0 : 1;
-                nbW = au ? readlane_f64(hi0, k) : readlane_f64(lo0, k);
+                nbW = au ? hi0_of(k) : lo0_of(k);
                 kW = k; auW = au;
                 pivots++;
                 cnext = col_of(NBP + k);
@@ -792,9 +904,9 @@ __global__ __launch_bounds__(WAVE, 4) void avi_solve_schur(AviBatchArgs a, Schur
                     // the multiplier d_k left at 0: p_k enters, moving off the bound it rests at
                     vn = k;
                     sneg = au != 0;
-                    self_lim = readlane_f64(rngv, k);           // +inf for a free pair
+                    self_lim = rng_of(k);           // +inf for a free pair
                     if (cls == 2) sneg = false;
-                    elo = readlane_f64(lo0, k); ehi = readlane_f64(hi0, k);
+                    elo = lo0_of(k); ehi = hi0_of(k);
                 }
             }
             // (colvar still holds the entering id veW at column c here -- the write-back is below --, so that
@@ -967,6 +1079,7 @@ __global__ __launch_bounds__(WAVE, 4) void avi_solve_schur(AviBatchArgs a, Schur
     int lE_ = l; asm volatile("" : "+v"(lE_));
     const int lcE = lE_ & 15, lqE = lE_ >> 4;
     wave_sync();
+    if constexpr (CRASH == 2) kx = sbuf[96 + (lE_ & 31)];
     if (actb) sval[rowvar] = xb;
     if (l <= XC) sval[colvar] = nbval;
     wave_sync();
@@ -1197,8 +1310,17 @@ hipError_t qpn_launch_avi_solve_schur_nodes(const AviBatchArgs &a, hipStream_t s
     const bool full = a.nd.n == 32 && a.nd.m == 32, half = a.nd.n == 16 && a.nd.m == 16;
     const dim3 grid((unsigned)a.batch), block(WAVE);
     if (full && a.nd.sym) {
-        if (stag) hipLaunchKernelGGL((avi_solve_schur<true, kResidentMI355X, 32, true>), grid, block, 0, stream, a, d);
-        else hipLaunchKernelGGL((avi_solve_schur<true, 0, 32, true>), grid, block, 0, stream, a, d);
+        const int crash = (a.crash && a.crash_flag) ? a.crash_mode : 0;
+        if (crash == 2) {
+            if (stag) hipLaunchKernelGGL((avi_solve_schur<true, kResidentMI355X, 32, true, 2>), grid, block, 0, stream, a, d);
+            else hipLaunchKernelGGL((avi_solve_schur<true, 0, 32, true, 2>), grid, block, 0, stream, a, d);
+        } else if (crash == 1) {
+            if (stag) hipLaunchKernelGGL((avi_solve_schur<true, kResidentMI355X, 32, true, 1>), grid, block, 0, stream, a, d);
+            else hipLaunchKernelGGL((avi_solve_schur<true, 0, 32, true, 1>), grid, block, 0, stream, a, d);
+        } else {
+            if (stag) hipLaunchKernelGGL((avi_solve_schur<true, kResidentMI355X, 32, true>), grid, block, 0, stream, a, d);
+            else hipLaunchKernelGGL((avi_solve_schur<true, 0, 32, true>), grid, block, 0, stream, a, d);
+        }
         return hipGetLastError();
     }
     if (stag && full) hipLaunchKernelGGL((avi_solve_schur<true, kResidentMI355X, 32>), grid, block, 0, stream, a, d);

@@ -42,6 +42,8 @@ struct qpn_ctx {
     int32_t route_epoch = 0;
     // QPN_OPT_SYM_ROUTE: 1 = resident records whose Qd blocks are all bitwise symmetric take the kernel variants that use it
     int32_t sym_route = 1;
+    // QPN_OPT_CRASH_CACHE: 1 = resident symmetric n = m = 32 records keep the parameter-free part of the crash across sweeps
+    int32_t crash_cache = 1;
 };
 
 namespace {
@@ -316,6 +318,11 @@ int qpn_ctx_set_option(qpn_ctx *ctx, int32_t option, int32_t value)
         if (value < 0 || value > 1) return fail_arg(ctx, "qpn_ctx_set_option: QPN_OPT_SYM_ROUTE takes 0 or 1");
         if (ctx->sym_route != value) ctx->route_epoch++;
         ctx->sym_route = value;
+        return QPN_OK;
+    case QPN_OPT_CRASH_CACHE:
+        // (no new route epoch: cached sweeps return the same bits, so what a handle knows about its declines stays true)
+        if (value < 0 || value > 1) return fail_arg(ctx, "qpn_ctx_set_option: QPN_OPT_CRASH_CACHE takes 0 or 1");
+        ctx->crash_cache = value;
         return QPN_OK;
     default:
         return fail_arg(ctx, "qpn_ctx_set_option: unknown option");
@@ -871,9 +878,45 @@ struct qpn_nodes {
     // the context's route epoch the decline knowledge was learned under (qpn_ctx_set_option bumps it: another kernel variant
     // applies its pivot test to slightly different numbers, so "no node declines" has to be asked again)
     int32_t route_epoch = 0;
+    // crash cache (symmetric n = m = 32 records): what Stage A of the fused kernel makes of Qd and Ad alone -- the panels U',
+    // the tiles W~ and S, a pass / fail flag per node (layout: qpn_internal.h) -- 22 528 bytes per node, allocated by the first
+    // sweep that would use it.  crash_state: 0 none, 1 valid (filled by one whole-batch sweep on crash_stream), -1 its memory
+    // could not be had (not asked for again).
+    double *crash = nullptr;
+    uint8_t *crash_flag = nullptr;
+    int crash_state = 0;
+    hipStream_t crash_stream = nullptr;
 };
 
 namespace {
+
+// Does the context's option set, and do the records, admit the crash cache?  (Symmetric n = m = 32 records on the symmetric
+// route; the other size classes and the general variants run uncached.)
+bool crash_cache_applies(const qpn_ctx *ctx, const qpn_nodes *h)
+{
+    return ctx->crash_cache == 1 && h->n == 32 && h->m == 32 && h->sym && ctx->sym_route == 1;
+}
+
+// Crash-cache mode of the next fused sweep over the handle's records: 2 reuse, 1 fill, 0 run uncached.  The buffer is
+// allocated here, once; a failed allocation is remembered and the handle runs uncached from then on.
+int crash_cache_mode(qpn_ctx *ctx, qpn_nodes *h, int32_t batch, bool own_order)
+{
+    if (!h || batch != h->batch || !crash_cache_applies(ctx, h) || h->crash_state < 0) return 0;
+    if (h->crash_state == 1) return h->crash_stream == ctx->stream ? 2 : 0;      // (filled on another stream: no ordering with it)
+    // a caller-installed order may leave nodes out (entries outside 0 .. count - 1): such a sweep fills nothing
+    if (!own_order) return 0;
+    if (!h->crash) {
+        hipError_t e = hipMalloc((void **)&h->crash, (size_t)batch * kCrashDoubles * sizeof(double));
+        if (e == hipSuccess) e = hipMalloc((void **)&h->crash_flag, (size_t)batch);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();            // (the failed allocation is not this sweep's error)
+            if (h->crash) (void)hipFree(h->crash);
+            h->crash = nullptr; h->crash_flag = nullptr; h->crash_state = -1;
+            return 0;
+        }
+    }
+    return 1;
+}
 
 // one pass over the resident Qd blocks (behind the copies on the context's stream); waits for the answer
 hipError_t nodes_check_symmetry(qpn_ctx *ctx, qpn_nodes *h)
@@ -899,6 +942,7 @@ void nodes_sync_route(qpn_ctx *ctx, qpn_nodes *h)
     if (h->decl_state == 1) (void)hipEventSynchronize(h->decl_ev);
     h->decl_state = 0;
     h->route_epoch = ctx->route_epoch;
+    if (h->crash_state == 1) h->crash_state = 0;        // the variants keep different tile sets
 }
 
 // Which kernels take the nodes of one qpn_solve_nodes call: decided once per call, from the shape, the pivot budget and the
@@ -1036,9 +1080,14 @@ int solve_nodes_launch(qpn_ctx *ctx, qpn_nodes *h, int32_t batch, int32_t n, int
         if (schedules(h, batch, 4096) && (h->calls < 128 || (h->calls & 3) == 0)) a.sched_key = h->key;
         if (h && h->order_valid) a.order = h->order;
         else if (ctx->order_count == batch && (!h || ctx->order_user)) a.order = ctx->order;     // a caller-installed order also serves handles
+        // resident symmetric n = m = 32 records: the first whole-batch sweep keeps the parameter-free part of the crash, the
+        // later ones reuse it (same stream: no host synchronisation)
+        const int crash = crash_cache_mode(ctx, h, batch, a.order == nullptr || (h && a.order == h->order));
+        if (crash) { a.crash = h->crash; a.crash_flag = h->crash_flag; a.crash_mode = crash; }
         bool need_general;
         if ((rc = declines_begin(ctx, h, a, &need_general)) != QPN_OK) return rc;
         HIPCHK(ctx, qpn_launch_avi_solve_schur_nodes(a, s));
+        if (crash == 1) { h->crash_state = 1; h->crash_stream = s; }
         if (need_general && (rc = solve_general(ctx, a, ws, true, true)) != QPN_OK) return rc;
         if ((rc = declines_end(ctx, h)) != QPN_OK) return rc;
         if (h) {
@@ -1188,6 +1237,8 @@ int qpn_nodes_free(qpn_ctx *ctx, qpn_nodes *h)
     (void)hipStreamSynchronize(ctx->stream);
     if (h->decl_ev) { (void)hipEventSynchronize(h->decl_ev); (void)hipEventDestroy(h->decl_ev); }
     if (h->buf) (void)hipFree(h->buf);
+    if (h->crash) (void)hipFree(h->crash);
+    if (h->crash_flag) (void)hipFree(h->crash_flag);
     if (h->decl_dev) (void)hipFree(h->decl_dev);
     if (h->decl_host) (void)hipHostFree(h->decl_host);
     if (h->order) (void)hipFree(h->order);
@@ -1251,6 +1302,8 @@ int qpn_nodes_update(qpn_ctx *ctx, qpn_nodes *h, int32_t field, const double *da
     // what was known about the old records is void (an answer still in flight must not be read as the new one's)
     if (h->decl_state == 1) HIPCHK(ctx, hipEventSynchronize(h->decl_ev));
     h->decl_state = 0;
+    // the crash cache is made of Qd and Ad alone: R, qd, B, l, u keep it (the memory stays for the next fill)
+    if ((field == QPN_NODE_QD || field == QPN_NODE_AD) && h->crash_state == 1) h->crash_state = 0;
     if (field == QPN_NODE_QD) HIPCHK(ctx, nodes_check_symmetry(ctx, h));
     return QPN_OK;
 }
@@ -1270,7 +1323,9 @@ int qpn_nodes_info(qpn_ctx *ctx, qpn_nodes *h, int32_t info[4])
     if (!h || !info) return fail_arg(ctx, "qpn_nodes_info: null argument");
     nodes_poll_declines(h);
     info[0] = h->decl_state; info[1] = h->decl_state >= 2 ? *h->decl_host : 0;
-    info[2] = (h->order_valid ? 1 : 0) | (h->sym ? 2 : 0); info[3] = h->calls;
+    const bool cached = h->crash_state == 1 && crash_cache_applies(ctx, h);
+    const bool refused = !crash_cache_applies(ctx, h) || h->crash_state < 0;
+    info[2] = (h->order_valid ? 1 : 0) | (h->sym ? 2 : 0) | (cached ? 4 : 0) | (refused ? 8 : 0); info[3] = h->calls;
     return QPN_OK;
 }
 

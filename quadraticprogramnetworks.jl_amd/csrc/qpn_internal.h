@@ -70,7 +70,17 @@ struct AviBatchArgs {
     // fused node kernel only: exponentially smoothed pivot count per node (units of 1/32 pivot), updated by every sweep
     // (key <- key - key/32 + pivots); the longest-first order of a resident-records handle is made from it.  May be null.
     int32_t *sched_key;
+    // fused node kernel, symmetric n = m = 32 resident records only: the handle's crash cache (kCrashDoubles per node) and its
+    // per-node flags (1 = crash passed, 2 = pivot test failed); crash_mode 0 = not used, 1 = this sweep fills it, 2 = reuses it
+    double *crash;
+    uint8_t *crash_flag;
+    int32_t crash_mode;
 };
+
+// Crash cache of one symmetric n = m = 32 node, in doubles from the node's base.  Everything sits in the layout the registers
+// have: U' step-major, [8 steps][32 rows] of 4 doubles (what lane < 32 writes to sU in step KB); the four W~ tiles and the three
+// S tiles with register g of tile t at ((4 t + g) * 64 + lane), so that every load and store moves 512 contiguous bytes.
+constexpr int kCrashU = 0, kCrashW = 1024, kCrashS = 2048, kCrashDoubles = 2816;      // 22 528 bytes per node
 
 // Function attributes (dynamic LDS limits) are per device: a launcher raises its kernels' limits once per device it is used on,
 // through a static QpnLdsLimits:  static QpnLdsLimits lds_limits;  ... lds_limits.raise({{kernel_a, bytes_a}, {kernel_b, bytes_b}})
