@@ -48,7 +48,6 @@ struct SchurDebug { double *S, *c, *W, *h; };
 // The workgroup IS one wavefront: wave_sync (qpn_internal.h) orders its LDS accesses, no s_barrier needed.
 
 #define QPN_STG_UNIT 64       /* stagger step of the first round: 64 x 64 clocks = 1.7 us per wave slot */
-constexpr int kResidentMI355X = 16 * 256;      // wavefronts of this kernel resident at once: 16 per CU, 256 CUs
 
 // SHAPE: 0 = sizes read at run time (any n, m <= 32); 32 / 16 = every item of the launch is n = m = SHAPE, a compile-time
 // constant: no ragged-shape code, bounds predicates or padding selects, and (16) no MFMAs on the padding tiles.
@@ -61,11 +60,18 @@ constexpr int kResidentMI355X = 16 * 256;      // wavefronts of this kernel resi
 // q alone, and of Stage A's products only the extra column kx (g -> h = H^-1 g) carries q.  0 = compute, keep nothing;
 // 1 = compute and STORE the panels U' of the eight steps, the tiles W~ and S(0,0), S(0,1), S(1,1) and a pass / fail flag in
 // the handle's crash cache (layout: qpn_internal.h, kCrash*); 2 = REUSE them: no Qd staging, no factorisation, no MFMA --
-// kx is replayed with the stored U' by the same operations in the same order, so every output has the same bits.
+// kx is replayed with the stored U' by the same operations in the same order, so every output has the same bits;
+// 3 = MIXED: the cache is valid and every wavefront picks one of the two Stage A bodies -- reuse as 2, or compute as 0 (storing
+// nothing) -- by a wave-uniform rule on its position in the launch (crash_mix_recomputes, qpn_internal.h: the launcher's share
+// of the positions below a.crash_reuse_from compute, spread evenly over each XCD's dispatch sequence).  The reuse body is bound
+// by HBM bytes and leaves the fp64 pipe half idle, the compute body the reverse; both give the same
+// bits, so the choice is free per wavefront.  The bodies join before the transposition of S(1,0); from there on there is one
+// copy of the code, with the fixed bounds and h parked in sbuf as in 2.
 template <bool NODES, int STAGGER = 0, int SHAPE = 0, bool SYM = false, int CRASH = 0>
 __global__ __launch_bounds__(WAVE, 4) void avi_solve_schur(AviBatchArgs a, SchurDebug dbg)
 {
     static_assert(CRASH == 0 || (NODES && SHAPE == 32 && SYM), "the crash cache exists for symmetric n = m = 32 node records");
+    static_assert(CRASH >= 0 && CRASH <= 3, "crash modes: 0 compute, 1 fill, 2 reuse, 3 mixed");
     static_assert(SHAPE == 0 || SHAPE == 16 || SHAPE == 32, "compile-time shapes: 16 and 32");
     static_assert(!SYM || (NODES && SHAPE == 32), "the symmetric variant exists for n = m = 32 node records");
     static_assert(NODES || SHAPE != 16, "explicit M: N alone settles the split only at N = 64");
@@ -229,7 +235,15 @@ __global__ __launch_bounds__(WAVE, 4) void avi_solve_schur(AviBatchArgs a, Schur
         typedef const AviBatchArgs __attribute__((address_space(4))) *kargs_c;
         return ((kargs_c)__builtin_amdgcn_kernarg_segment_ptr())->crash_flag + b;
     };
-    if constexpr (CRASH == 2) {
+    // which Stage A body this wavefront runs (wave-uniform; a compile-time constant unless CRASH == 3: there the launch position
+    // and two kernel arguments, read from the kernarg segment on the spot, settle it in scalar registers)
+    bool reuse_w = CRASH == 2;
+    if constexpr (CRASH == 3) {
+        typedef const AviBatchArgs __attribute__((address_space(4))) *kargs_m;
+        const kargs_m km = (kargs_m)__builtin_amdgcn_kernarg_segment_ptr();
+        reuse_w = !crash_mix_recomputes((int)blockIdx.x, km->crash_share, km->crash_reuse_from);
+    }
+    if constexpr (CRASH >= 2) if (reuse_w) {
         // ---- reuse.  ONE round of loads brings everything Stage B needs (each further dependent round trip costs a wave as much
         // as the crash it replaces): Ad, U', S, the bounds and q.  To fit the registers, Ad goes straight into the LDS block
         // buffer (LDS-DMA, one column of 32 rows = 256 B per instruction, lane <-> 4 bytes: the padded column stride stays) and
@@ -282,7 +296,9 @@ __global__ __launch_bounds__(WAVE, 4) void avi_solve_schur(AviBatchArgs a, Schur
         M_REPLAY(4, up0) M_REPLAY(5, up1) M_REPLAY(6, up2) M_REPLAY(7, up3)
 #undef M_REPLAY
         if (l < 32) sz[l] = kx;
-    } else {
+        goto stage_a_done;          // (one diamond: a second test of reuse_w hides from the compiler that the bodies exclude each other)
+    }
+    if constexpr (CRASH != 2) {
     double mabs = 0.0;
     if constexpr (NODES) {
         // Qd and Ad with fully coalesced loads (two columns of 32 rows per instruction = 512 contiguous
@@ -608,7 +624,8 @@ __global__ __launch_bounds__(WAVE, 4) void avi_solve_schur(AviBatchArgs a, Schur
             cs[(0 * 4 + g) * 64 + l] = SB(0, 0)[g]; cs[(1 * 4 + g) * 64 + l] = SB(0, 1)[g]; cs[(2 * 4 + g) * 64 + l] = SB(1, 1)[g];
         }
     }
-    }   // (CRASH != 2)
+    }   // (the computing body)
+stage_a_done: __attribute__((unused));
     if constexpr (SYM) {
         // S(1,0) = S(0,1)'.  (Also exact and 0.5 % slower: on the matrix cores -- register kb of a tile in the accumulator layout IS
         // the A operand of its transpose's k-block kb, element (i = lc, k = lq) = X[4 kb + lq][lc], with B = rows 4 kb .. 4 kb + 3
@@ -655,7 +672,7 @@ __global__ __launch_bounds__(WAVE, 4) void avi_solve_schur(AviBatchArgs a, Schur
     }
     STAMP(6);   // crash on the matrix cores
 
-    if constexpr (CRASH != 2) if (dbg.S) {
+    if constexpr (CRASH < 2) if (dbg.S) {
         // diagnostic builds: dump S (32x32), c, W (32x32), h in row-major
 #define M_DUMPW(I, J)                                                                               \
     _Pragma("unroll") for (int g = 0; g < 4; ++g) {                                                 \
@@ -713,15 +730,15 @@ __global__ __launch_bounds__(WAVE, 4) void avi_solve_schur(AviBatchArgs a, Schur
     // the fixed bounds of pair k as the pivot loop asks for them (wave-uniform k).  Reuse variant: they wait in the idle sz block
     // of sbuf instead of three register pairs, and h waits for the read-back in sbuf[96 .. 127] (idle from here on: the
     // transposition of S is done with it) -- the registers W~ arrives in while the loop runs
-    if constexpr (CRASH == 2) { if (actb) { sbuf[128 + l] = lo0; sbuf[160 + l] = hi0; sbuf[96 + l] = kx; } }
-    auto lo0_of = [&](int k) -> double { if constexpr (CRASH == 2) return udbl(sbuf[128 + k]); else return readlane_f64(lo0, k); };
-    auto hi0_of = [&](int k) -> double { if constexpr (CRASH == 2) return udbl(sbuf[160 + k]); else return readlane_f64(hi0, k); };
+    if constexpr (CRASH >= 2) { if (actb) { sbuf[128 + l] = lo0; sbuf[160 + l] = hi0; sbuf[96 + l] = kx; } }
+    auto lo0_of = [&](int k) -> double { if constexpr (CRASH >= 2) return udbl(sbuf[128 + k]); else return readlane_f64(lo0, k); };
+    auto hi0_of = [&](int k) -> double { if constexpr (CRASH >= 2) return udbl(sbuf[160 + k]); else return readlane_f64(hi0, k); };
     auto rng_of = [&](int k) -> double {
-        if constexpr (CRASH == 2) return udbl(sbuf[160 + k]) - udbl(sbuf[128 + k]); else return readlane_f64(rngv, k);
+        if constexpr (CRASH >= 2) return udbl(sbuf[160 + k]) - udbl(sbuf[128 + k]); else return readlane_f64(rngv, k);
     };
-    if constexpr (CRASH == 2) {
+    if constexpr (CRASH >= 2) if (reuse_w) {
         // W~ is needed by the read-back only: requested here, it arrives behind the pivot loop (in the registers the computing
-        // variants keep it in)
+        // variants -- and the computing wavefronts of a mixed launch -- keep it in)
         const double *const cw = crash_base() + kCrashW;
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
@@ -1079,7 +1096,7 @@ __global__ __launch_bounds__(WAVE, 4) void avi_solve_schur(AviBatchArgs a, Schur
     int lE_ = l; asm volatile("" : "+v"(lE_));
     const int lcE = lE_ & 15, lqE = lE_ >> 4;
     wave_sync();
-    if constexpr (CRASH == 2) kx = sbuf[96 + (lE_ & 31)];
+    if constexpr (CRASH >= 2) kx = sbuf[96 + (lE_ & 31)];
     if (actb) sval[rowvar] = xb;
     if (l <= XC) sval[colvar] = nbval;
     wave_sync();
@@ -1311,7 +1328,10 @@ hipError_t qpn_launch_avi_solve_schur_nodes(const AviBatchArgs &a, hipStream_t s
     const dim3 grid((unsigned)a.batch), block(WAVE);
     if (full && a.nd.sym) {
         const int crash = (a.crash && a.crash_flag) ? a.crash_mode : 0;
-        if (crash == 2) {
+        // a mixed launch (qpn_capi.hip sets the share): only beyond the resident set, where the reuse variant saturates HBM
+        if (crash == 2 && a.crash_share > 0 && a.crash_reuse_from > 0 && stag) {
+            hipLaunchKernelGGL((avi_solve_schur<true, kResidentMI355X, 32, true, 3>), grid, block, 0, stream, a, d);
+        } else if (crash == 2) {
             if (stag) hipLaunchKernelGGL((avi_solve_schur<true, kResidentMI355X, 32, true, 2>), grid, block, 0, stream, a, d);
             else hipLaunchKernelGGL((avi_solve_schur<true, 0, 32, true, 2>), grid, block, 0, stream, a, d);
         } else if (crash == 1) {

@@ -897,6 +897,29 @@ bool crash_cache_applies(const qpn_ctx *ctx, const qpn_nodes *h)
     return ctx->crash_cache == 1 && h->n == 32 && h->m == 32 && h->sym && ctx->sym_route == 1;
 }
 
+// Mixed reuse sweeps (qpn_avi_schur.hip, CRASH = 3): the share of the wavefronts that compute Stage A although the cache is
+// valid, in 1/256ths (0: plain reuse sweeps), and the tail rule -- how many launch positions BEFORE the last partial round of
+// the resident set already reuse, in 1/256ths of that set.  Both are tuning constants (-D for variant builds); no result
+// depends on them.
+#ifndef QPN_CRASH_MIX_SHARE
+#define QPN_CRASH_MIX_SHARE 96
+#endif
+#ifndef QPN_CRASH_MIX_TAIL
+#define QPN_CRASH_MIX_TAIL 0
+#endif
+constexpr int kCrashMixShare = QPN_CRASH_MIX_SHARE;
+constexpr int kCrashMixTail = QPN_CRASH_MIX_TAIL;
+static_assert(kCrashMixShare >= 0 && kCrashMixShare <= 256 && kCrashMixTail >= 0, "share in 1/256ths; tail >= 0");
+
+// First launch position of the all-reuse tail: the last partial round of the resident set (it is bound by latency, not by HBM:
+// the shorter chain wins there) and kCrashMixTail / 256 of a round before it.
+int32_t crash_mix_reuse_from(int32_t batch)
+{
+    const int64_t full = (int64_t)(batch / kResidentMI355X) * kResidentMI355X;
+    const int64_t from = full - (int64_t)kResidentMI355X * kCrashMixTail / 256;
+    return (int32_t)(from > 0 ? from : 0);
+}
+
 // Crash-cache mode of the next fused sweep over the handle's records: 2 reuse, 1 fill, 0 run uncached.  The buffer is
 // allocated here, once; a failed allocation is remembered and the handle runs uncached from then on.
 int crash_cache_mode(qpn_ctx *ctx, qpn_nodes *h, int32_t batch, bool own_order)
@@ -1084,6 +1107,12 @@ int solve_nodes_launch(qpn_ctx *ctx, qpn_nodes *h, int32_t batch, int32_t n, int
         // later ones reuse it (same stream: no host synchronisation)
         const int crash = crash_cache_mode(ctx, h, batch, a.order == nullptr || (h && a.order == h->order));
         if (crash) { a.crash = h->crash; a.crash_flag = h->crash_flag; a.crash_mode = crash; }
+        // a reuse sweep beyond the resident set is a mixed launch: kCrashMixShare / 256 of its wavefronts compute Stage A, which
+        // trades HBM bytes for fp64-pipe cycles (the two variants saturate one each); the tail reuses (the shorter chain)
+        if (crash == 2 && kCrashMixShare > 0 && batch > kResidentMI355X) {
+            a.crash_share = kCrashMixShare;
+            a.crash_reuse_from = crash_mix_reuse_from(batch);
+        }
         bool need_general;
         if ((rc = declines_begin(ctx, h, a, &need_general)) != QPN_OK) return rc;
         HIPCHK(ctx, qpn_launch_avi_solve_schur_nodes(a, s));

@@ -75,7 +75,30 @@ struct AviBatchArgs {
     double *crash;
     uint8_t *crash_flag;
     int32_t crash_mode;
+    // crash_mode 2 only: a mixed launch.  crash_share = the share of the wavefronts, in 1/256ths, that compute Stage A although the
+    // cache is valid (0: every wavefront reuses); crash_reuse_from = the launch position from which every wavefront reuses
+    // (the tail of the launch, which no longer saturates HBM).  The results do not depend on either (crash_mix_recomputes).
+    int32_t crash_share;
+    int32_t crash_reuse_from;
 };
+
+// Wavefronts of the fused 32-class kernel resident at once on an MI355X: 16 per CU (LDS- and VGPR-bound), 256 CUs.
+constexpr int kResidentMI355X = 16 * 256;
+
+// Mixed launches of the fused symmetric n = m = 32 kernel: does the wavefront at launch position `pos` (blockIdx.x) compute
+// Stage A instead of reusing the cache?  Consecutive workgroup ids go round-robin over the 8 XCDs, so the share is spread over
+// the position WITHIN an XCD, k = pos >> 3, by an error-diffusion (Bresenham) rule: position k computes when the running sum
+// k * share + phase crosses a multiple of 256.  Any run of L consecutive k of one XCD then holds L * share / 256 computing
+// wavefronts to within one.  The phases of the 8 XCDs are the 8 multiples of 32, in bit-reversed order: a row of 8 consecutive
+// positions (one k) then holds 8 * share / 256 to within one as well (Hermite's identity), and neighbouring dies do not lead
+// each other.  Wave-uniform scalar arithmetic; positions from reuse_from on always reuse.
+__host__ __device__ inline bool crash_mix_recomputes(int pos, int share, int reuse_from)
+{
+    if (pos >= reuse_from) return false;
+    const int x = pos & 7, k = pos >> 3;
+    const int phase = 32 * (((x & 1) << 2) | (x & 2) | (x >> 2));
+    return ((k * share + phase) & 255) + share >= 256;
+}
 
 // Crash cache of one symmetric n = m = 32 node, in doubles from the node's base.  Everything sits in the layout the registers
 // have: U' step-major, [8 steps][32 rows] of 4 doubles (what lane < 32 writes to sU in step KB); the four W~ tiles and the three
