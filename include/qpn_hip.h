@@ -443,6 +443,38 @@ int qpn_multiplier_vertices(qpn_ctx *ctx, int32_t batch, int32_t n, int32_t m, c
 int qpn_recipe_filter(qpn_ctx *ctx, int32_t pieces, int32_t rows, int32_t N, const uint8_t *masks, const uint8_t *K,
                       const int32_t *vrow_of, const int32_t *first_of, uint8_t *keep, int mem);
 
+/* ---- interior members of polyhedra: the prefilter of remove_subsets (src/sets.jl:889-902, the slack program of `exemplar`,
+ *      :591-642), node records made on the device ----------
+ * A batch of polyhedra {x : l <= A x <= u} of one size: A [batch][r][d] column-major per item (row i, column c at c * r + i),
+ * l, u [batch][r].  Row classes per item: eq = finite l and l == u;  lo = not eq and finite l;  hi = not eq and finite u.
+ * The caller passes capacities ne, nlo, nhi (at least the batch's largest class counts).  The record of an item is the node
+ *     min eps + delta/2 (|x|^2 + eps^2)   s.t.  a_i'x = l_i (eq),  a_i'x + eps >= l_i (lo),  a_i'x - eps <= u_i (hi)
+ * with the equality multipliers in the free block: nf = d + 1 + ne free variables [x; eps; mu_E], mp = max(16, nlo + nhi
+ * rounded up to 16) rows, in the layout of qpn_solve_nodes (p = 1, R = 0, B = 0, w = 0):
+ *     Qd [batch][nf][nf] = [[delta I_(d+1), -A_E'], [A_E, D]]  (D: 1 on idle multiplier slots, 0 on used ones),
+ *     qd [batch][nf] = [0_d; 1; -l_E],  Ad [batch][mp][nf]: slots 0 .. nlo-1 the lo rows [a_i, +1, 0] in (l_i, +inf), slots
+ *     nlo .. nlo+nhi-1 the hi rows [a_i, -1, 0] in (-inf, u_i), every other slot a zero row in (-inf, +inf).
+ * The rows of a class are taken in ascending row order.  An item with more rows of a class than its capacity is not cut
+ * short: flag [batch] uint8 = 1 for it, its record is that of a polyhedron without rows, and it has no member (ok = 0).
+ * Limits: nf + mp <= 1024 (as qpn_solve_nodes), r <= 4096; QPN_ERR_SIZE beyond.
+ *
+ * qpn_assemble_interior_nodes: the records alone (every word written, zeros included).
+ * qpn_interior_members: records (workspace of the context) -> the solve of qpn_solve_nodes with default options and a cold
+ *   start -> x_out [batch][d] = the member, ok [batch] uint8 = status == QPN_SUCCESS and eps <= 1e-6 and not flagged (x_out is
+ *   meaningful only where ok), status [batch] the solver's.  Host mode moves A, l, u up and x_out, ok, status down.
+ * qpn_members_outside: pair q asks whether member X[pi[q]] (X [Bi][d]) lies outside piece pj[q] of a group of Bj pieces of one
+ *   size (Aj [Bj][rj][d] column-major, lj, uj [Bj][rj]): out[q] = 1 when a row has a.x < l - t or a.x > u + t, a.x summed over
+ *   ascending columns (acc = acc + a * x[c], no contraction).  Order the pairs by piece where many members meet one piece: 16
+ *   consecutive pairs over one piece share one read of it.  Host index arrays out of range: QPN_ERR_ARG; device ones: that
+ *   pair answers 1 ("not settled here"). */
+int qpn_assemble_interior_nodes(qpn_ctx *ctx, int32_t batch, int32_t r, int32_t d, const double *A, const double *l, const double *u,
+                                double delta, int32_t ne, int32_t nlo, int32_t nhi, double *Qd, double *qd, double *Ad, double *lo,
+                                double *uo, uint8_t *flag, int mem);
+int qpn_interior_members(qpn_ctx *ctx, int32_t batch, int32_t r, int32_t d, const double *A, const double *l, const double *u,
+                         double delta, int32_t ne, int32_t nlo, int32_t nhi, double *x_out, uint8_t *ok, int32_t *status, int mem);
+int qpn_members_outside(qpn_ctx *ctx, int32_t pairs, int32_t d, int32_t rj, const double *Aj, const double *lj, const double *uj,
+                        int32_t Bj, const double *X, int32_t Bi, const int32_t *pi, const int32_t *pj, double t, uint8_t *out, int mem);
+
 #ifdef __cplusplus
 }
 #endif

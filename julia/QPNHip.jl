@@ -242,6 +242,72 @@ function recipe_filter(masks::Matrix{UInt8}, K::Matrix{UInt8}, vrow_of::Vector{I
     keep
 end
 
+"""
+    interior_members(A, l, u; delta=1e-2) -> (x, ok, status)
+
+One member per polyhedron {x : l <= A x <= u}, well inside its inequality rows (qpn_interior_members: the slack program of
+`exemplar` with a proximal term, equality rows kept; the node records are made on the device).  A [r, d, batch] (Julia's
+column-major arrays are the ABI layout as they are), l, u [r, batch].  x [d, batch] (meaningful where ok), ok [batch] (1 = a
+member), status [batch] the node solver's.
+"""
+function interior_members(A::Array{Float64,3}, l::Matrix{Float64}, u::Matrix{Float64}; delta::Float64 = 1e-2)
+    r, d, batch = size(A)
+    eq = isfinite.(l) .& (l .== u)
+    ne = Int32(maximum(sum(eq, dims = 1); init = 0))
+    nlo = Int32(maximum(sum(.!eq .& isfinite.(l), dims = 1); init = 0))
+    nhi = Int32(maximum(sum(.!eq .& isfinite.(u), dims = 1); init = 0))
+    x = zeros(d, batch); ok = zeros(UInt8, batch); status = zeros(Int32, batch)
+    rc = ccall((:qpn_interior_members, LIB), Cint,
+               (Ptr{Cvoid}, Int32, Int32, Int32, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cdouble, Int32, Int32, Int32, Ptr{Cdouble},
+                Ptr{UInt8}, Ptr{Int32}, Cint),
+               ctx(), batch, r, d, A, l, u, delta, ne, nlo, nhi, x, ok, status, QPN_MEM_HOST)
+    rc == 0 || error("qpn_interior_members failed ($rc)")
+    (x, ok, status)
+end
+
+"""
+    assemble_interior_nodes(A, l, u, ne, nlo, nhi; delta=1e-2) -> (Qd, qd, Ad, lo, uo, flag)
+
+The node records interior_members solves (qpn_assemble_interior_nodes): Qd [nf, nf, batch], qd [nf, batch], Ad [mp, nf, batch],
+lo, uo [mp, batch] with nf = d + 1 + ne, mp = max(16, nlo + nhi rounded up to 16); flag [batch] = 1 for an item with more rows
+of a class than slots (its record is that of a polyhedron without rows).
+"""
+function assemble_interior_nodes(A::Array{Float64,3}, l::Matrix{Float64}, u::Matrix{Float64}, ne::Integer, nlo::Integer,
+                                 nhi::Integer; delta::Float64 = 1e-2)
+    r, d, batch = size(A)
+    nf = d + 1 + ne
+    mp = max(16, cld(nlo + nhi, 16) * 16)
+    Qd = zeros(nf, nf, batch); qd = zeros(nf, batch); Ad = zeros(mp, nf, batch); lo = zeros(mp, batch); uo = zeros(mp, batch)
+    flag = zeros(UInt8, batch)
+    rc = ccall((:qpn_assemble_interior_nodes, LIB), Cint,
+               (Ptr{Cvoid}, Int32, Int32, Int32, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cdouble, Int32, Int32, Int32, Ptr{Cdouble},
+                Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{UInt8}, Cint),
+               ctx(), batch, r, d, A, l, u, delta, ne, nlo, nhi, Qd, qd, Ad, lo, uo, flag, QPN_MEM_HOST)
+    rc == 0 || error("qpn_assemble_interior_nodes failed ($rc)")
+    (Qd, qd, Ad, lo, uo, flag)
+end
+
+"""
+    members_outside(Aj, lj, uj, X, pi, pj; t=1e-5) -> out
+
+qpn_members_outside: out[q] = 1 when member X[:, pi[q]] violates a row of piece pj[q] (Aj [rj, d, Bj], lj, uj [rj, Bj]) by more
+than t.  pi, pj are 1-based here.
+"""
+function members_outside(Aj::Array{Float64,3}, lj::Matrix{Float64}, uj::Matrix{Float64}, X::Matrix{Float64}, pi::Vector{<:Integer},
+                         pj::Vector{<:Integer}; t::Float64 = 1e-5)
+    rj, d, Bj = size(Aj)
+    size(X, 1) == d || error("members_outside: X must have d rows")
+    pairs = length(pi)
+    pi0 = Int32.(pi .- 1); pj0 = Int32.(pj .- 1)
+    out = zeros(UInt8, pairs)
+    rc = ccall((:qpn_members_outside, LIB), Cint,
+               (Ptr{Cvoid}, Int32, Int32, Int32, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Int32, Ptr{Cdouble}, Int32, Ptr{Int32},
+                Ptr{Int32}, Cdouble, Ptr{UInt8}, Cint),
+               ctx(), pairs, d, rj, Aj, lj, uj, Bj, X, size(X, 2), pi0, pj0, t, out, QPN_MEM_HOST)
+    rc == 0 || error("qpn_members_outside failed ($rc)")
+    out
+end
+
 function verify_nodes(nodes::Nodes, xd::Matrix{Float64}, w::VecOrMat{Float64}; tol::Float64 = 1e-4)
     solution = zeros(Int32, nodes.batch); path = zeros(Int32, nodes.batch); lambda = zeros(max(nodes.m, 1), nodes.batch)
     rc = ccall((:qpn_verify_nodes_h, LIB), Cint,

@@ -23,6 +23,7 @@ ABI_SYMBOLS = (
     "qpn_verify_nodes_h", "qpn_pool_size", "qpn_assemble_pools", "qpn_local_pieces", "qpn_recipes_from_masks",
     "qpn_recipes_batch", "qpn_reduced_pieces", "qpn_convexity_nodes", "qpn_recipes_batch_range", "qpn_finish_pieces",
     "qpn_multiplier_vertices", "qpn_recipe_filter",
+    "qpn_assemble_interior_nodes", "qpn_interior_members", "qpn_members_outside",
 )
 
 MEM_HOST, MEM_DEVICE = 0, 1
@@ -138,6 +139,12 @@ def load_library():
     lib.qpn_multiplier_vertices.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_double,
                                             C.c_double, vp, vp, vp, C.c_int]
     lib.qpn_recipe_filter.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, C.c_int]
+    lib.qpn_assemble_interior_nodes.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, C.c_double, C.c_int32, C.c_int32,
+                                                C.c_int32, vp, vp, vp, vp, vp, vp, C.c_int]
+    lib.qpn_interior_members.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, C.c_double, C.c_int32, C.c_int32, C.c_int32,
+                                         vp, vp, vp, C.c_int]
+    lib.qpn_members_outside.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, C.c_int32, vp, C.c_int32, vp, vp, C.c_double,
+                                        vp, C.c_int]
     del dp, ip, bp
     _lib = lib
     return lib

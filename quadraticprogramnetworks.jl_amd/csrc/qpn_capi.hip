@@ -1620,6 +1620,119 @@ int qpn_recipe_filter(qpn_ctx *ctx, int32_t pieces, int32_t rows, int32_t N, con
 } // extern "C"
 
 namespace {
+
+// the record shape of a batch of interior-member queries (polyhedra.interior_member_records)
+struct MemberShape { int32_t nf, mp; };
+
+// what qpn_assemble_interior_nodes and qpn_interior_members ask of the arguments they share; *sh: the record shape
+int members_check(qpn_ctx *ctx, const char *who, int32_t batch, int32_t r, int32_t d, const double *A, const double *l, const double *u,
+                  int32_t ne, int32_t nlo, int32_t nhi, bool outputs, MemberShape *sh)
+{
+    if (batch < 0 || r <= 0 || d <= 0 || ne < 0 || nlo < 0 || nhi < 0) return fail_arg(ctx, who, "bad sizes");
+    const int64_t nf = (int64_t)d + 1 + ne, mi = (int64_t)nlo + nhi, mp = mi <= 16 ? 16 : (mi + 15) / 16 * 16;
+    if (nf + mp > qpn_avi_max_n() || r > QPN_MEMBERS_MAX_ROWS) {
+        ctx->last_error = std::string(who) + ": d + 1 + ne + mp <= 1024 and r <= 4096 in ABI v1";
+        return QPN_ERR_SIZE;
+    }
+    if (batch > 0 && (!A || !l || !u || !outputs)) return fail_arg(ctx, who, "null pointer");
+    sh->nf = (int32_t)nf; sh->mp = (int32_t)mp;
+    return QPN_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+// ---- interior members of polyhedra: records made on the device (qpn_members.hip) ------------------------------------------
+int qpn_assemble_interior_nodes(qpn_ctx *ctx, int32_t batch, int32_t r, int32_t d, const double *A, const double *l, const double *u,
+                                double delta, int32_t ne, int32_t nlo, int32_t nhi, double *Qd, double *qd, double *Ad, double *lo,
+                                double *uo, uint8_t *flag, int mem)
+{
+    if (!ctx) return QPN_ERR_ARG;
+    MemberShape sh;
+    Stage st(ctx, mem, "qpn_assemble_interior_nodes");
+    if (int rc = members_check(ctx, st.who, batch, r, d, A, l, u, ne, nlo, nhi, Qd && qd && Ad && lo && uo && flag, &sh)) return rc;
+    if (int rc = st.check()) return rc;
+    if (batch == 0) return QPN_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t B = (size_t)batch, nf = sh.nf, mp = sh.mp;
+    const double *dA, *dl, *du; double *dQ, *dq, *dAd, *dlo, *duo; uint8_t *dflag;
+    st.in(dA, A, B * r * d * 8); st.in(dl, l, B * r * 8); st.in(du, u, B * r * 8);
+    st.out(dQ, Qd, B * nf * nf * 8); st.out(dq, qd, B * nf * 8); st.out(dAd, Ad, B * nf * mp * 8);
+    st.out(dlo, lo, B * mp * 8); st.out(duo, uo, B * mp * 8); st.out(dflag, flag, B);
+    int rc = st.begin();
+    if (rc != QPN_OK) return rc;
+    HIPCHK(ctx, qpn_launch_interior_records(batch, r, d, dA, dl, du, delta, ne, nlo, nhi, dQ, dq, dAd, dlo, duo, dflag, ctx->stream));
+    return st.finish();
+}
+
+int qpn_interior_members(qpn_ctx *ctx, int32_t batch, int32_t r, int32_t d, const double *A, const double *l, const double *u,
+                         double delta, int32_t ne, int32_t nlo, int32_t nhi, double *x_out, uint8_t *ok, int32_t *status, int mem)
+{
+    if (!ctx) return QPN_ERR_ARG;
+    MemberShape sh;
+    Stage st(ctx, mem, "qpn_interior_members");
+    if (int rc = members_check(ctx, st.who, batch, r, d, A, l, u, ne, nlo, nhi, x_out && ok && status, &sh)) return rc;
+    if (int rc = st.check()) return rc;
+    if (batch == 0) return QPN_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    // the solve of qpn_solve_nodes over these records with p = 1, R = 0, B = 0, w = 0, default options and a cold start
+    const int32_t n = sh.nf, m = sh.mp, N = n + m;
+    qpn_avi_opts o;
+    qpn_avi_default_opts(&o);
+    o.flags |= QPN_AVI_FLAG_COLD_START;
+    const NodeRoute route = node_route(ctx, n, m, o);
+    const size_t B = (size_t)batch, bN = B * N;
+    NodeWs ws{};
+    st.scratch(ws.M, bN * N * 8); st.scratch(ws.q, bN * 8); st.scratch(ws.l, bN * 8); st.scratch(ws.u, bN * 8); st.scratch(ws.kind, bN);
+    if (N > 64) st.scratch(ws.big, qpn_avi_big_workspace_bytes(batch, N));
+    const double *dA, *dl, *du;
+    st.in(dA, A, B * r * d * 8); st.in(dl, l, B * r * 8); st.in(du, u, B * r * 8);
+    double *rQ, *rq, *rA, *rl, *ru, *zeros, *dx; uint8_t *dflag, *dok;
+    st.scratch(rQ, B * n * n * 8); st.scratch(rq, B * n * 8); st.scratch(rA, B * n * m * 8); st.scratch(rl, B * m * 8);
+    st.scratch(ru, B * m * 8);
+    const size_t nz = B * n + B * m + 1;                       // R [batch][n][1], B [batch][m][1], w [1]
+    st.scratch(zeros, nz * 8); st.scratch(dflag, B);
+    NodeDev nd{};
+    st.scratch(nd.z, bN * 8); st.out(nd.st, status, B * 4); st.scratch(nd.res, B * 8); st.scratch(nd.pv, B * 4); st.scratch(nd.act, bN);
+    st.out(dx, x_out, B * d * 8); st.out(dok, ok, B);
+    int rc = st.begin();
+    if (rc != QPN_OK) return rc;
+    HIPCHK(ctx, hipMemsetAsync(zeros, 0, nz * 8, s));
+    HIPCHK(ctx, qpn_launch_interior_records(batch, r, d, dA, dl, du, delta, ne, nlo, nhi, rQ, rq, rA, rl, ru, dflag, s));
+    nd.Q = rQ; nd.R = zeros; nd.q = rq; nd.A = rA; nd.B = zeros + B * n; nd.l = rl; nd.u = ru; nd.w = zeros + B * n + B * m;
+    if ((rc = solve_nodes_launch(ctx, nullptr, batch, n, m, 1, nd, 0, o, nullptr, 0, ws, route)) != QPN_OK) return rc;
+    HIPCHK(ctx, qpn_launch_members_extract(batch, d, N, nd.z, nd.st, dflag, dx, dok, s));
+    return st.finish();
+}
+
+int qpn_members_outside(qpn_ctx *ctx, int32_t pairs, int32_t d, int32_t rj, const double *Aj, const double *lj, const double *uj,
+                        int32_t Bj, const double *X, int32_t Bi, const int32_t *pi, const int32_t *pj, double t, uint8_t *out, int mem)
+{
+    if (!ctx) return QPN_ERR_ARG;
+    if (pairs < 0 || d <= 0 || rj <= 0 || Bj < 0 || Bi < 0) return fail_arg(ctx, "qpn_members_outside: bad sizes");
+    Stage st(ctx, mem, "qpn_members_outside");
+    if (int rc = st.check()) return rc;
+    if (pairs == 0) return QPN_OK;
+    if (!Aj || !lj || !uj || !X || !pi || !pj || !out || Bj == 0 || Bi == 0) return fail_arg(ctx, "qpn_members_outside: null pointer");
+    // host index arrays are checked here; device ones by the kernel (such a pair answers 1: not settled)
+    for (int q = 0; st.host && q < pairs; ++q)
+        if (pi[q] < 0 || pi[q] >= Bi || pj[q] < 0 || pj[q] >= Bj) return fail_arg(ctx, "qpn_members_outside: pair index out of range");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const double *dA, *dl, *du, *dX; const int32_t *dpi, *dpj; uint8_t *dout;
+    st.in(dA, Aj, (size_t)Bj * d * rj * 8); st.in(dl, lj, (size_t)Bj * rj * 8); st.in(du, uj, (size_t)Bj * rj * 8);
+    st.in(dX, X, (size_t)Bi * d * 8); st.in(dpi, pi, (size_t)pairs * 4); st.in(dpj, pj, (size_t)pairs * 4);
+    st.out(dout, out, (size_t)pairs);
+    int rc = st.begin();
+    if (rc != QPN_OK) return rc;
+    HIPCHK(ctx, qpn_launch_members_outside(pairs, d, rj, dA, dl, du, Bj, dX, Bi, dpi, dpj, t, dout, ctx->stream));
+    return st.finish();
+}
+
+} // extern "C"
+
+namespace {
 int verify_nodes_any(qpn_ctx *ctx, bool records_on_device, int32_t batch, int32_t n, int32_t m, int32_t p,
                      const double *Qd, const double *R, const double *qd, const double *Ad, const double *B,
                      const double *l, const double *u, const double *xd, const double *w, int64_t stride_w, double tol,

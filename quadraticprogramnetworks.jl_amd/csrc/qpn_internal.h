@@ -265,6 +265,16 @@ hipError_t qpn_launch_multiplier_vertices(int32_t batch, int32_t n, int32_t m, c
 size_t qpn_multiplier_vertices_workspace_bytes(int32_t batch, int32_t n, int32_t m, int32_t max_bases);
 hipError_t qpn_launch_recipe_filter(int32_t pieces, int32_t N, const uint8_t *masks, const uint8_t *K, const int32_t *vrow_of,
                                     const int32_t *first_of, int32_t rows, uint8_t *keep, hipStream_t s);
+// qpn_members.hip: interior-member node records made on the device, the members taken from the solve, members against pieces
+hipError_t qpn_launch_interior_records(int32_t batch, int32_t r, int32_t d, const double *A, const double *l, const double *u, double delta,
+                                       int32_t ne, int32_t nlo, int32_t nhi, double *Qd, double *qd, double *Ad, double *lo, double *uo,
+                                       uint8_t *flag, hipStream_t s);
+size_t qpn_interior_records_lds(int32_t r);
+hipError_t qpn_launch_members_extract(int32_t batch, int32_t d, int32_t N, const double *z, const int32_t *status, const uint8_t *flag,
+                                      double *x, uint8_t *ok, hipStream_t s);
+hipError_t qpn_launch_members_outside(int32_t pairs, int32_t d, int32_t rj, const double *Aj, const double *lj, const double *uj, int32_t Bj,
+                                      const double *X, int32_t Bi, const int32_t *pi, const int32_t *pj, double t, uint8_t *out, hipStream_t s);
+#define QPN_MEMBERS_MAX_ROWS 4096
 #define QPN_CONVEXITY_MAX_N 256
 #define QPN_CONVEXITY_MAX_M 1024
 

@@ -589,6 +589,58 @@ class Engine:
         self._call("qpn_recipe_filter", pieces, rows, N, _ptr(masks), _ptr(K), _ptr(vrow_of), _ptr(first_of), _ptr(keep), self._mem(dev))
         return keep
 
+    # -- interior members of polyhedra: records made on the device ---------------------------------------------
+    def _member_args(self, who, Ac, l, u, ne, nlo, nhi):
+        batch, d, r = (int(v) for v in Ac.shape)
+        if tuple(l.shape) != (batch, r) or tuple(u.shape) != (batch, r):
+            raise QpnError(f"{who}: inconsistent shapes")
+        ne, nlo, nhi = int(ne), int(nlo), int(nhi)
+        mi = nlo + nhi
+        return batch, r, d, ne, nlo, nhi, d + 1 + ne, max(16, -(-mi // 16) * 16)
+
+    def assemble_interior_nodes(self, Ac, l, u, delta, ne, nlo, nhi):
+        """The node records of the interior-member queries of a batch of polyhedra (qpn_assemble_interior_nodes;
+        polyhedra.interior_member_records is its numpy twin): Ac [batch, d, r] (A in the ABI layout, ``colmajor(A)``), l, u
+        [batch, r]; ne, nlo, nhi the slot counts of the three row classes.  Returns (Qc [batch, nf, nf], qd [batch, nf],
+        Ac [batch, nf, mp], l, u [batch, mp], flag [batch] uint8: 1 = more rows of a class than slots, inert record)."""
+        dev, Ac, l, u = self._stage("assemble_interior_nodes", "Ac l u", f64=(Ac, l, u))
+        batch, r, d, ne, nlo, nhi, nf, mp = self._member_args("assemble_interior_nodes", Ac, l, u, ne, nlo, nhi)
+        Qo = self._alloc(dev, (batch, nf, nf), np.float64)
+        qo = self._alloc(dev, (batch, nf), np.float64)
+        Ao = self._alloc(dev, (batch, nf, mp), np.float64)
+        lo = self._alloc(dev, (batch, mp), np.float64)
+        uo = self._alloc(dev, (batch, mp), np.float64)
+        flag = self._alloc(dev, (batch,), np.uint8)
+        self._call("qpn_assemble_interior_nodes", batch, r, d, _ptr(Ac), _ptr(l), _ptr(u), float(delta), ne, nlo, nhi, _ptr(Qo), _ptr(qo),
+                   _ptr(Ao), _ptr(lo), _ptr(uo), _ptr(flag), self._mem(dev))
+        return Qo, qo, Ao, lo, uo, flag
+
+    def interior_members(self, Ac, l, u, delta, ne, nlo, nhi):
+        """One interior member per polyhedron (qpn_interior_members): the records of assemble_interior_nodes are made in the
+        library's workspace, solved as solve_nodes(..., z0=None) solves them, and the members taken out.
+        Returns (x [batch, d], ok [batch] uint8, status [batch] int32); x is meaningful where ok."""
+        dev, Ac, l, u = self._stage("interior_members", "Ac l u", f64=(Ac, l, u))
+        batch, r, d, ne, nlo, nhi, _, _ = self._member_args("interior_members", Ac, l, u, ne, nlo, nhi)
+        x = self._alloc(dev, (batch, d), np.float64)
+        ok = self._alloc(dev, (batch,), np.uint8)
+        status = self._alloc(dev, (batch,), np.int32)
+        self._call("qpn_interior_members", batch, r, d, _ptr(Ac), _ptr(l), _ptr(u), float(delta), ne, nlo, nhi, _ptr(x), _ptr(ok),
+                   _ptr(status), self._mem(dev))
+        return x, ok, status
+
+    def members_outside(self, Ajc, lj, uj, X, pi, pj, t):
+        """qpn_members_outside (polyhedra.members_outside_host is its numpy twin): out [pairs] uint8, 1 where member X[pi[q]]
+        violates a row of piece pj[q] by more than t.  Ajc [Bj, d, rj] (ABI layout), lj, uj [Bj, rj], X [Bi, d], pi, pj int32."""
+        dev, Ajc, lj, uj, X, pi, pj = self._stage("members_outside", "Ajc lj uj X pi pj", f64=(Ajc, lj, uj, X), i32=(pi, pj))
+        Bj, d, rj = (int(v) for v in Ajc.shape)
+        pairs = int(pi.shape[0])
+        if tuple(lj.shape) != (Bj, rj) or tuple(uj.shape) != (Bj, rj) or X.ndim != 2 or int(X.shape[1]) != d or tuple(pj.shape) != (pairs,):
+            raise QpnError("members_outside: inconsistent shapes")
+        out = self._alloc(dev, (pairs,), np.uint8)
+        self._call("qpn_members_outside", pairs, d, rj, _ptr(Ajc), _ptr(lj), _ptr(uj), Bj, _ptr(X), int(X.shape[0]), _ptr(pi), _ptr(pj),
+                   float(t), _ptr(out), self._mem(dev))
+        return out
+
 
 class Nodes:
     """Resident node records (``qpn_nodes_upload``): the records of a level's single-node pools live in HBM owned by the

@@ -159,6 +159,129 @@ def issubset_batch_chunked(pairs, engine, tol=1e-6, chunk_bytes=None):
     return out
 
 
+def interior_member_counts(l, u):
+    """The slot counts (ne, nlo, nhi) of a batch's interior-member records: the largest number of equality rows (finite l == u),
+    of other rows with a finite lower bound and of other rows with a finite upper bound of any item.  l, u [B, r]."""
+    l = np.asarray(l, dtype=np.float64); u = np.asarray(u, dtype=np.float64)
+    eq = np.isfinite(l) & (l == u)
+    lo = ~eq & np.isfinite(l); hi = ~eq & np.isfinite(u)
+    return int(eq.sum(1).max(initial=0)), int(lo.sum(1).max(initial=0)), int(hi.sum(1).max(initial=0))
+
+
+def interior_member_records(A, l, u, delta):
+    """The node records of the interior-member queries of B polyhedra of one size, A [B, r, d] (math layout), l, u [B, r], packed
+    straight into the ABI's column-major blocks -> (Qc [B, nf, nf], qd [B, nf], Ac [B, nf, mp], ll, uu [B, mp]) with
+    nf = d + 1 + ne, mp = max(16, nlo + nhi rounded up to 16), (ne, nlo, nhi) = interior_member_counts(l, u); p = 1, R = 0, B = 0.
+    The counts of equality / lower / upper rows differ from piece to piece: the free block is padded with idle multipliers (a unit
+    diagonal entry, no coupling: mu = 0) and the rows with inert ones (0'z in (-inf, inf)) up to the batch's largest.
+    This is the numpy twin of Engine.assemble_interior_nodes (qpn_assemble_interior_nodes), and the route of engines without it."""
+    A = np.asarray(A, dtype=np.float64); l = np.asarray(l, dtype=np.float64); u = np.asarray(u, dtype=np.float64)
+    B, r, d = A.shape
+    eq = np.isfinite(l) & (l == u)
+    lo = ~eq & np.isfinite(l); hi = ~eq & np.isfinite(u)
+    ne, nlo, nhi = int(eq.sum(1).max(initial=0)), int(lo.sum(1).max(initial=0)), int(hi.sum(1).max(initial=0))
+
+    def pick(mask, cnt):                                  # first `cnt` row indices with the mask set, ascending; valid flags
+        order = np.argsort(~mask, axis=1, kind="stable")[:, :cnt]
+        return order, np.take_along_axis(mask, order, axis=1)
+
+    (E, Ev), (LO, LOv), (HI, HIv) = pick(eq, ne), pick(lo, nlo), pick(hi, nhi)
+    bidx = np.arange(B)[:, None]
+    rows_of = lambda sel, valid: A[bidx, sel] * valid[:, :, None]        # (whole rows by index pairs: no index broadcast over d)
+    nf = d + 1 + ne                                       # free block: [x; eps; mu_E]
+    mi = nlo + nhi
+    mp = max(16, -(-mi // 16) * 16)
+    Qc = np.zeros((B, nf, nf)); qd = np.zeros((B, nf)); Ac = np.zeros((B, nf, mp))
+    ll = np.full((B, mp), -INF); uu = np.full((B, mp), INF)
+    ar = np.arange(d + 1)
+    Qc[:, ar, ar] = delta
+    qd[:, d] = 1.0
+    if ne:
+        AE = rows_of(E, Ev)                               # [B, ne, d], zero rows in the idle slots
+        # math layout: Qd' = [[delta I, -A_E'], [A_E, 0]] (eps column of A_E is 0); Qc is its transpose per item
+        Qc[:, d + 1:, :d] = -AE
+        Qc[:, :d, d + 1:] = np.swapaxes(AE, 1, 2)
+        je = d + 1 + np.arange(ne)
+        Qc[:, je, je] = np.where(Ev, 0.0, 1.0)            # idle multipliers: 1 * mu = 0
+        qd[:, d + 1:] = np.where(Ev, -np.take_along_axis(l, E, axis=1), 0.0)
+    if nlo:
+        Ac[:, :d, :nlo] = np.swapaxes(rows_of(LO, LOv), 1, 2); Ac[:, d, :nlo] = np.where(LOv, 1.0, 0.0)
+        ll[:, :nlo] = np.where(LOv, np.take_along_axis(l, LO, axis=1), -INF)
+    if nhi:
+        Ac[:, :d, nlo:mi] = np.swapaxes(rows_of(HI, HIv), 1, 2); Ac[:, d, nlo:mi] = np.where(HIv, -1.0, 0.0)
+        uu[:, nlo:mi] = np.where(HIv, np.take_along_axis(u, HI, axis=1), INF)
+    return Qc, qd, Ac, ll, uu
+
+
+def members_outside_host(Ajc, lj, uj, X, pi, pj, t):
+    """The numpy twin of Engine.members_outside (qpn_members_outside), same operations in the same order: out [pairs] uint8, 1 where
+    member X[pi[q]] violates a row of piece pj[q] -- a.x < l - t or a.x > u + t -- with a.x summed over ascending columns,
+    acc = acc + a * x[c].  Ajc [Bj, d, rj] (the pieces' matrices in the ABI layout), lj, uj [Bj, rj], X [Bi, d]."""
+    Ajc = np.asarray(Ajc, dtype=np.float64); lj = np.asarray(lj, dtype=np.float64); uj = np.asarray(uj, dtype=np.float64)
+    X = np.asarray(X, dtype=np.float64); pi = np.asarray(pi, dtype=np.int64); pj = np.asarray(pj, dtype=np.int64)
+    Bj, d, rj = Ajc.shape
+    out = np.zeros(len(pi), np.uint8)
+    step = max(1, (1 << 24) // max(1, rj))                # (pairs x rows doubles per slice)
+    for s in range(0, len(pi), step):
+        qi, qj = pi[s:s + step], pj[s:s + step]
+        acc = np.zeros((len(qi), rj))
+        for c in range(d):
+            acc = acc + Ajc[qj, c, :] * X[qi, c][:, None]
+        with np.errstate(invalid="ignore"):
+            out[s:s + step] = np.any((acc < lj[qj] - t) | (acc > uj[qj] + t), axis=1)
+    return out
+
+
+PAIR_CHUNK = 1 << 22             # (member, piece) pairs of one members_outside call of remove_subsets_many, about
+
+
+def _on_device(engine):
+    return getattr(engine, "device", -1) >= 0
+
+
+def _interior_member_groups(trips, engine, delta=1e-2, chunk=20000):
+    """interior_members_batch's work: the queries packed by size (rows, columns), one engine call per pack of at most `chunk`.
+    -> list of dict(idx: positions in `trips`, x [B, d], ok [B], and with an engine that has interior_members also Ac [B, d, r],
+    l, u [B, r]: the pack as the engine got it).  x and ok stay where the engine left them (device tensors on a device engine)."""
+    groups = {}
+    prepared = []
+    for i, (A, l, u) in enumerate(trips):
+        A = np.atleast_2d(np.asarray(A, dtype=np.float64))
+        l = np.asarray(l, dtype=np.float64); u = np.asarray(u, dtype=np.float64)
+        prepared.append((A, l, u))
+        groups.setdefault((A.shape[0], A.shape[1]), []).append(i)
+    fused = callable(getattr(engine, "interior_members", None))
+    out = []
+    for (r, d), idx_all in sorted(groups.items()):
+        for c0 in range(0, len(idx_all), chunk):
+            idx = idx_all[c0:c0 + chunk]
+            B = len(idx)
+            A = np.stack([prepared[i][0] for i in idx]).reshape(B, r, d)
+            l = np.stack([prepared[i][1] for i in idx]).reshape(B, r); u = np.stack([prepared[i][2] for i in idx]).reshape(B, r)
+            if fused:
+                # the engine makes the records itself (qpn_interior_members): only the polyhedra go to it
+                from .engine import colmajor
+                ne, nlo, nhi = interior_member_counts(l, u)
+                if _on_device(engine):
+                    import torch
+                    dv = f"cuda:{engine.device}"
+                    A, l, u = (torch.as_tensor(a, dtype=torch.float64, device=dv) for a in (A, l, u))
+                Ac = colmajor(A)
+                x, ok, _ = engine.interior_members(Ac, l, u, delta, ne, nlo, nhi)
+                out.append(dict(idx=idx, x=x, ok=ok, Ac=Ac, l=l, u=u))
+                continue
+            Qc, qd, Ac, ll, uu = interior_member_records(A, l, u, delta)
+            nf, mp = qd.shape[1], ll.shape[1]
+            res = engine.solve_nodes(Qc, np.zeros((B, 1, nf)), qd, Ac, np.zeros((B, 1, mp)), ll, uu, np.zeros(1))
+            st = np.asarray(res["status"]); z = np.asarray(res["z"])
+            out.append(dict(idx=idx, x=z[:, :d], ok=(st == 1) & (z[:, d] <= 1e-6)))
+    return out
+
+
+def _to_host(a):
+    return a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)
+
+
 def interior_members_batch(trips, engine, delta=1e-2, chunk=20000):
     """One member per polyhedron (A, l, u), well inside its INEQUALITY rows: the slack program of `exemplar` (src/sets.jl:608-619)
     with the equality rows (l == u) kept as equalities -- a lower-dimensional piece gets a point of its relative interior instead
@@ -170,64 +293,81 @@ def interior_members_batch(trips, engine, delta=1e-2, chunk=20000):
     the fused node kernels take it, where the plain LP -- no pivots in its H block -- fell to the general kernel, the slowest
     call of a level's sweep.  The proximal term caps the slack at 1 / delta and picks the least-norm point among the deepest ones;
     the answer is used as ONE member of the polyhedron (remove_subsets_many), never as an optimum.
+    Queries over polyhedra of one size (rows, columns) are packed together: a level asks tens of thousands of them, a Python loop
+    per record costs more than their solve.  An engine with `interior_members` gets the polyhedra and makes the records on the
+    device (qpn_interior_members); any other gets the records from interior_member_records through solve_nodes.
     -> list of x or None (empty / no answer)."""
     out = [None] * len(trips)
-    # queries over polyhedra of one size (rows, columns) are packed together, straight into the ABI's column-major blocks: a level
-    # asks tens of thousands of them, a Python loop per record costs more than their solve.  The counts of equality / lower /
-    # upper rows differ from piece to piece: the free block is padded with idle multipliers (a unit diagonal entry, no coupling:
-    # mu = 0) and the rows with inert ones (0'z in (-inf, inf)) up to the group's largest, so that a level is a handful of calls
-    groups = {}
-    prepared = []
-    for i, (A, l, u) in enumerate(trips):
-        A = np.atleast_2d(np.asarray(A, dtype=np.float64))
-        l = np.asarray(l, dtype=np.float64); u = np.asarray(u, dtype=np.float64)
-        prepared.append((A, l, u))
-        groups.setdefault((A.shape[0], A.shape[1]), []).append(i)
-    for (r, d), idx_all in sorted(groups.items()):
-        for c0 in range(0, len(idx_all), chunk):
-            idx = idx_all[c0:c0 + chunk]
-            B = len(idx)
-            A = np.stack([prepared[i][0] for i in idx]).reshape(B, r, d)
-            l = np.stack([prepared[i][1] for i in idx]).reshape(B, r); u = np.stack([prepared[i][2] for i in idx]).reshape(B, r)
-            eq = np.isfinite(l) & (l == u)
-            lo = ~eq & np.isfinite(l); hi = ~eq & np.isfinite(u)
-            ne, nlo, nhi = int(eq.sum(1).max(initial=0)), int(lo.sum(1).max(initial=0)), int(hi.sum(1).max(initial=0))
-
-            def pick(mask, cnt):                                  # first `cnt` row indices with the mask set, ascending; valid flags
-                order = np.argsort(~mask, axis=1, kind="stable")[:, :cnt]
-                return order, np.take_along_axis(mask, order, axis=1)
-
-            (E, Ev), (LO, LOv), (HI, HIv) = pick(eq, ne), pick(lo, nlo), pick(hi, nhi)
-            bidx = np.arange(B)[:, None]
-            rows_of = lambda sel, valid: A[bidx, sel] * valid[:, :, None]        # (whole rows by index pairs: no index broadcast over d)
-            nf = d + 1 + ne                                       # free block: [x; eps; mu_E]
-            mi = nlo + nhi
-            mp = max(16, -(-mi // 16) * 16)
-            Qc = np.zeros((B, nf, nf)); qd = np.zeros((B, nf)); Ac = np.zeros((B, nf, mp))
-            ll = np.full((B, mp), -INF); uu = np.full((B, mp), INF)
-            ar = np.arange(d + 1)
-            Qc[:, ar, ar] = delta
-            qd[:, d] = 1.0
-            if ne:
-                AE = rows_of(E, Ev)                               # [B, ne, d], zero rows in the idle slots
-                # math layout: Qd' = [[delta I, -A_E'], [A_E, 0]] (eps column of A_E is 0); Qc is its transpose per item
-                Qc[:, d + 1:, :d] = -AE
-                Qc[:, :d, d + 1:] = np.swapaxes(AE, 1, 2)
-                je = d + 1 + np.arange(ne)
-                Qc[:, je, je] = np.where(Ev, 0.0, 1.0)            # idle multipliers: 1 * mu = 0
-                qd[:, d + 1:] = np.where(Ev, -np.take_along_axis(l, E, axis=1), 0.0)
-            if nlo:
-                Ac[:, :d, :nlo] = np.swapaxes(rows_of(LO, LOv), 1, 2); Ac[:, d, :nlo] = np.where(LOv, 1.0, 0.0)
-                ll[:, :nlo] = np.where(LOv, np.take_along_axis(l, LO, axis=1), -INF)
-            if nhi:
-                Ac[:, :d, nlo:mi] = np.swapaxes(rows_of(HI, HIv), 1, 2); Ac[:, d, nlo:mi] = np.where(HIv, -1.0, 0.0)
-                uu[:, nlo:mi] = np.where(HIv, np.take_along_axis(u, HI, axis=1), INF)
-            res = engine.solve_nodes(Qc, np.zeros((B, 1, nf)), qd, Ac, np.zeros((B, 1, mp)), ll, uu, np.zeros(1))
-            st = np.asarray(res["status"]); z = np.asarray(res["z"])
-            ok = (st == 1) & (z[:, d] <= 1e-6)
-            for k in np.nonzero(ok)[0]:
-                out[idx[k]] = z[k, :d].copy()
+    for g in _interior_member_groups(trips, engine, delta, chunk):
+        x = _to_host(g["x"]); ok = _to_host(g["ok"]).astype(bool)
+        for k in np.nonzero(ok)[0]:
+            out[g["idx"][k]] = x[k].copy()
     return out
+
+
+def _refuted_by_members(comp, flat, starts, engine, tol):
+    """remove_subsets_many's refutation matrices on an engine with `members_outside`: the members stay where the solve left
+    them, every (rows, columns) pack of second pieces is ONE members_outside call over the pack as interior_members got it, and
+    only the verdicts come to the host.  -> {list a: refuted [k, k] bool}."""
+    groups = _interior_member_groups(flat, engine)
+    nflat = len(flat)
+    grp_of = np.zeros(nflat, np.int64); pos_of = np.zeros(nflat, np.int64); xrow = np.zeros(nflat, np.int64)
+    ok_h = np.zeros(nflat, bool)
+    X_of, rows_d = {}, {}                                   # per member dimension d: the packs' members, one after the other
+    for g, grp in enumerate(groups):
+        idx = np.asarray(grp["idx"], dtype=np.int64)
+        d = int(grp["x"].shape[1])
+        grp_of[idx] = g; pos_of[idx] = np.arange(len(idx)); xrow[idx] = rows_d.get(d, 0) + np.arange(len(idx))
+        rows_d[d] = rows_d.get(d, 0) + len(idx)
+        ok_h[idx] = _to_host(grp["ok"]).astype(bool)
+        X_of.setdefault(d, []).append(grp["x"])
+    dev = _on_device(engine)
+    if dev:
+        import torch
+    cat = (lambda xs: xs[0] if len(xs) == 1 else torch.cat(xs)) if dev else (lambda xs: xs[0] if len(xs) == 1 else np.concatenate(xs))
+    X_of = {d: cat(xs) for d, xs in X_of.items()}
+    refuted = {a: np.zeros((len(trips), len(trips)), bool) for a, trips in enumerate(comp) if trips is not None}
+
+    def ask(blocks):
+        """One members_outside call per pack for the pairs of `blocks` [(list a, ii, jj)]; the verdicts go into refuted[a]."""
+        FI = np.concatenate([starts[a] + ii for a, ii, _ in blocks]); FJ = np.concatenate([starts[a] + jj for a, _, jj in blocks])
+        verdict = np.zeros(len(FI), bool)
+        gj = grp_of[FJ]
+        for g in np.unique(gj).tolist():
+            grp = groups[g]
+            sel = np.nonzero(gj == g)[0]
+            pi = xrow[FI[sel]].astype(np.int32); pj = pos_of[FJ[sel]].astype(np.int32)
+            if dev:
+                pi, pj = (torch.as_tensor(v, device=grp["x"].device) for v in (pi, pj))
+            Ac = grp["Ac"]
+            out = engine.members_outside(Ac, grp["l"], grp["u"], X_of[int(Ac.shape[1])], pi, pj, 10 * tol)
+            verdict[sel] = _to_host(out).astype(bool)
+        verdict &= ok_h[FI]                                 # (no member for the first piece: nothing is refuted by it)
+        p0 = 0
+        for a, ii, jj in blocks:
+            refuted[a][ii, jj] = verdict[p0:p0 + len(ii)]
+            p0 += len(ii)
+
+    # every ordered pair (first piece i, second piece j), i != j, of every list, ordered by the second piece -- the kernel reads a
+    # piece once for a run of pairs that share it -- and asked in slices of about PAIR_CHUNK pairs (a list of thousands of
+    # pieces has tens of millions of pairs: their index arrays are not all held at once)
+    blocks, held = [], 0
+    for a, trips in enumerate(comp):
+        if trips is None:
+            continue
+        k = len(trips)
+        step = max(1, PAIR_CHUNK // k)
+        for j0 in range(0, k, step):
+            j1 = min(k, j0 + step)
+            jj = np.repeat(np.arange(j0, j1), k); ii = np.tile(np.arange(k), j1 - j0)
+            keep = ii != jj
+            blocks.append((a, ii[keep], jj[keep])); held += int(keep.sum())
+            if held >= PAIR_CHUNK:
+                ask(blocks)
+                blocks, held = [], 0
+    if blocks:
+        ask(blocks)
+    return refuted
 
 
 def remove_subsets_many(lists, engine, tol=1e-6, prefilter=True):
@@ -239,9 +379,11 @@ def remove_subsets_many(lists, engine, tol=1e-6, prefilter=True):
     an LP (the reference's LP over P1 would come out below the bound by the same amount).  The member is a point of P1's
     relative interior (interior_members_batch: the slack LP of `exemplar`, src/sets.jl:591-642, over the inequality rows; one LP
     per piece, all pieces of the level in one batch) -- cells of a piecewise-affine solution map that merely touch are told
-    apart by it -- and only the pairs it does not settle go to the LPs (issubset_batch, chunked).  -> list of kept lists."""
+    apart by it -- and only the pairs it does not settle go to the LPs (issubset_batch, chunked).  An engine with
+    `interior_members` and `members_outside` also puts the members to the pieces itself (_refuted_by_members).
+    -> list of kept lists."""
     comp, jobs, where = [], [], []
-    flat, flat_of = [], []
+    flat, flat_of, starts = [], [], {}
     for a, polys in enumerate(lists):
         k = len(polys) if polys is not None else 0
         if k < 2:
@@ -251,9 +393,12 @@ def remove_subsets_many(lists, engine, tol=1e-6, prefilter=True):
         trips = [(P.block(cols), P.l, P.u) for P in polys]
         comp.append(trips)
         if prefilter:
+            starts[a] = len(flat)
             flat += trips; flat_of += [(a, i) for i in range(k)]
+    on_engine = bool(flat) and all(callable(getattr(engine, f, None)) for f in ("interior_members", "members_outside"))
+    refuted_of = _refuted_by_members(comp, flat, starts, engine, tol) if on_engine else {}
     member = {}
-    if flat:
+    if flat and not on_engine:
         for key, pt in zip(flat_of, interior_members_batch(flat, engine)):      # (no answer for a piece: its pairs go to the LPs)
             member[key] = pt
     sub = {}
@@ -262,7 +407,7 @@ def remove_subsets_many(lists, engine, tol=1e-6, prefilter=True):
             continue
         k = len(trips)
         have = [i for i in range(k) if member.get((a, i)) is not None]
-        refuted = np.zeros((k, k), bool)                    # refuted[i, j]: P1 = piece i has a member outside P2 = piece j
+        refuted = refuted_of.get(a, np.zeros((k, k), bool))  # refuted[i, j]: P1 = piece i has a member outside P2 = piece j
         if have:
             pts = np.stack([member[(a, i)] for i in have], axis=1)          # [d, members]
             for j in range(k):
