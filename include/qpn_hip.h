@@ -475,6 +475,55 @@ int qpn_interior_members(qpn_ctx *ctx, int32_t batch, int32_t r, int32_t d, cons
 int qpn_members_outside(qpn_ctx *ctx, int32_t pairs, int32_t d, int32_t rj, const double *Aj, const double *lj, const double *uj,
                         int32_t Bj, const double *X, int32_t Bi, const int32_t *pi, const int32_t *pj, double t, uint8_t *out, int mem);
 
+/* ---- batched LP solver for the polyhedral primitives: `exemplar`, `isempty`, `issubset`, `implicit_bounds` (src/sets.jl:591-713,
+ *      :376-407; one OSQP LP per question there) ----------
+ * qpn_solve_lps: `jobs` LPs over `polys` shared polyhedra {x : l <= A x <= u} of one size.  A [polys][r][d] column-major per item
+ * (row i, column c at c * r + i), l, u [polys][r] (+-inf allowed), poly_of [jobs] int32.  Job t minimises c_t'x with c_t =
+ * cost[t] (cost [jobs][d]) or, when cost == NULL, obj_sign[t] * row obj_row[t] of A[poly_of[t]] (int32 arrays; the device reads
+ * the row in place).  Outputs per job (x, obj, lambda, ray, iters may be NULL):
+ *   status [jobs] int32 (QPN_LP_*), x [jobs][d] (the optimum; for UNBOUNDED the feasible point the ray starts from; otherwise
+ *   the point reached), obj [jobs] = c'x on the unscaled data, iters [jobs] int32 (flips and pivots after the crash),
+ *   lambda [jobs][r]: OPTIMAL: c = A'lambda, + at the lower bound, - at the upper (the convention of qpn_verify_nodes);
+ *     INFEASIBLE: a Farkas vector y, A'y = 0 and sum(y_i > 0 ? y_i u_i : y_i l_i) < 0;  zeros otherwise,
+ *   ray [jobs][d]: UNBOUNDED: c'ray < 0, (A ray)_i >= 0 where l_i is finite, <= 0 where u_i is finite;  zeros otherwise.
+ * Method (polyhedra.solve_lps_host is its numpy twin and the normative statement; every output is bit-equal to it: each sum runs
+ * over the ascending index as acc = acc + a * b, no contraction): bounded-variable primal simplex on the row-activity form, x
+ * free, s = A x in [l, u].  (1) rows and their bounds scaled by 1 / max|a_i|; an all-zero row with l_i > 0 or u_i < 0 makes the
+ * job INFEASIBLE (Farkas vector -+e_i), otherwise it is inert.  (2) dictionary basic = T nonbasic, r x d, plus a cost row; ids
+ * x_j = j, s_i = d + i; start basic = s, T = A, cost row = c.  (3) crash, columns ascending: pivot on the largest |T_ij| among rows
+ * still holding an s (2^-30 relative band, lowest row); a column whose best entry is <= piv_tol stays nonbasic, free, at 0; a
+ * basic x never leaves.  (4) a nonbasic s starts at its finite bound nearest zero (the lower on a tie), at 0 without one.
+ * (5) phase 1 minimises the sum of the basic violations beyond feas_tol * max(1, |bound|), phase 2 minimises c; the phase is
+ * decided before every step.  (6) entering: reduced cost beyond opt_tol in a direction the value allows, never a fixed variable;
+ * the largest |reduced cost| (2^-30 band, lowest id); after 20 consecutive zero-length steps the lowest eligible id until a step
+ * is positive.  (7) ratio test: the entering variable's opposite bound (a flip, no pivot) and basic variables with |entry| >
+ * piv_tol; a violated basic blocks at the bound it violates when moving towards it, not when moving away; the smallest ratio,
+ * negative ones clamped to 0, ties within 1e-12 * max(1, ratio) to the lowest id.  (8) pivot p = T[i][j]: new row i = -T[i][k] / p,
+ * 1 / p at j; every other row and the cost row, f = their entry at j: T[k][c] += f * new_i[c], T[k][j] = f / p.  (9) phase 1
+ * without entering variable: INFEASIBLE; phase 2 without blocking candidate: UNBOUNDED; phase 2 without entering variable:
+ * OPTIMAL; a further step due after max_iters: ITER_LIMIT.  A claimed outcome is checked on the unscaled rows at check_tol --
+ * primal feasibility within check_tol * max(1, |bound|); |c - A'lambda| <= check_tol * max(1, |c_k|), a multiplier beyond +-check_tol only at its
+ * bound; |A'y| <= check_tol * max(1, |y|_inf) and the Farkas sum < 0; c'ray < 0 and the row conditions within check_tol *
+ * max(1, |ray|_inf) * max|a_i| -- and becomes QPN_LP_FAILURE when it fails them.
+ * opts == NULL: the defaults.  max_iters <= 0: 50 (r + d) + 100.  Host poly_of / obj_row out of range: QPN_ERR_ARG; device ones:
+ * that job answers QPN_LP_FAILURE with zeros and reads nothing.  1 <= d <= 256, 1 <= r <= 1024 (QPN_ERR_SIZE beyond).
+ * qpn_lp_kernel_class(r, d): 0 = one wavefront per job, dictionary in LDS, four jobs per workgroup; 1 = one workgroup of 256 per
+ * job in LDS; 2 = one workgroup per job over a slice of the context workspace, launched in chunks; -1 beyond the limits. */
+enum { QPN_LP_OPTIMAL = 1, QPN_LP_INFEASIBLE = 2, QPN_LP_UNBOUNDED = 3, QPN_LP_ITER_LIMIT = 4, QPN_LP_FAILURE = 5 };
+typedef struct {
+    double piv_tol;    /* 1e-9, on the row-scaled data */
+    double feas_tol;   /* 1e-9 */
+    double opt_tol;    /* 1e-9 */
+    double check_tol;  /* 1e-6, the post-check on the unscaled data */
+    int32_t max_iters; /* <= 0: 50 (r + d) + 100 */
+    int32_t reserved;
+} qpn_lp_opts;
+void qpn_lp_default_opts(qpn_lp_opts *opts);
+int qpn_lp_kernel_class(int32_t r, int32_t d);
+int qpn_solve_lps(qpn_ctx *ctx, int32_t polys, int32_t r, int32_t d, const double *A, const double *l, const double *u, int32_t jobs,
+                  const int32_t *poly_of, const double *cost, const int32_t *obj_row, const int32_t *obj_sign, const qpn_lp_opts *opts,
+                  int32_t *status, double *x, double *obj, double *lambda, double *ray, int32_t *iters, int mem);
+
 #ifdef __cplusplus
 }
 #endif

@@ -308,6 +308,36 @@ function members_outside(Aj::Array{Float64,3}, lj::Matrix{Float64}, uj::Matrix{F
     out
 end
 
+"""
+    solve_lps(A, l, u, poly_of; cost=nothing, obj_row=nothing, obj_sign=nothing, max_iters=0)
+        -> (status, x, obj, lambda, ray, iters)
+
+qpn_solve_lps: the LPs of `exemplar`, `isempty`, `issubset` and `implicit_bounds` (src/sets.jl:591-713, :376-407) as jobs over
+shared polyhedra A [r, d, polys], l, u [r, polys].  Job t minimises cost[:, t]'x over polyhedron poly_of[t] or, without `cost`,
+obj_sign[t] times row obj_row[t] of it (poly_of and obj_row are 1-based here).  status: 1 optimal, 2 infeasible (lambda is a
+Farkas vector), 3 unbounded (x + t ray stays feasible and c'ray < 0), 4 iteration limit, 5 failure.
+"""
+function solve_lps(A::Array{Float64,3}, l::Matrix{Float64}, u::Matrix{Float64}, poly_of::Vector{<:Integer};
+                   cost::Union{Nothing,Matrix{Float64}} = nothing, obj_row::Union{Nothing,Vector{<:Integer}} = nothing,
+                   obj_sign::Union{Nothing,Vector{<:Integer}} = nothing, max_iters::Integer = 0)
+    r, d, polys = size(A)
+    jobs = length(poly_of)
+    cost === nothing && (obj_row === nothing || obj_sign === nothing) && error("solve_lps: give cost, or obj_row and obj_sign")
+    po = Int32.(poly_of .- 1)
+    orow = cost === nothing ? Int32.(obj_row .- 1) : Int32[]
+    osg = cost === nothing ? Int32.(obj_sign) : Int32[]
+    opts = Ref((1e-9, 1e-9, 1e-9, 1e-6, Int32(max_iters), Int32(0)))      # qpn_lp_opts
+    status = zeros(Int32, jobs); x = zeros(d, jobs); obj = zeros(jobs); lam = zeros(r, jobs); ray = zeros(d, jobs)
+    iters = zeros(Int32, jobs)
+    rc = ccall((:qpn_solve_lps, LIB), Cint,
+               (Ptr{Cvoid}, Int32, Int32, Int32, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Int32, Ptr{Int32}, Ptr{Cdouble}, Ptr{Int32},
+                Ptr{Int32}, Ptr{Cvoid}, Ptr{Int32}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int32}, Cint),
+               ctx(), polys, r, d, A, l, u, jobs, po, cost === nothing ? C_NULL : cost, cost === nothing ? orow : C_NULL,
+               cost === nothing ? osg : C_NULL, opts, status, x, obj, lam, ray, iters, QPN_MEM_HOST)
+    rc == 0 || error("qpn_solve_lps failed ($rc)")
+    (status, x, obj, lam, ray, iters)
+end
+
 function verify_nodes(nodes::Nodes, xd::Matrix{Float64}, w::VecOrMat{Float64}; tol::Float64 = 1e-4)
     solution = zeros(Int32, nodes.batch); path = zeros(Int32, nodes.batch); lambda = zeros(max(nodes.m, 1), nodes.batch)
     rc = ccall((:qpn_verify_nodes_h, LIB), Cint,

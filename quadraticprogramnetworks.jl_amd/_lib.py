@@ -24,6 +24,7 @@ ABI_SYMBOLS = (
     "qpn_recipes_batch", "qpn_reduced_pieces", "qpn_convexity_nodes", "qpn_recipes_batch_range", "qpn_finish_pieces",
     "qpn_multiplier_vertices", "qpn_recipe_filter",
     "qpn_assemble_interior_nodes", "qpn_interior_members", "qpn_members_outside",
+    "qpn_lp_default_opts", "qpn_lp_kernel_class", "qpn_solve_lps",
 )
 
 MEM_HOST, MEM_DEVICE = 0, 1
@@ -54,6 +55,13 @@ class AviOpts(C.Structure):
     _fields_ = [("check_tol", C.c_double), ("piv_tol", C.c_double), ("feas_tol", C.c_double),
                 ("comp_tol", C.c_double), ("max_pivots", C.c_int32), ("flags", C.c_int32)]
 
+
+class LpOpts(C.Structure):
+    _fields_ = [("piv_tol", C.c_double), ("feas_tol", C.c_double), ("opt_tol", C.c_double), ("check_tol", C.c_double),
+                ("max_iters", C.c_int32), ("reserved", C.c_int32)]
+
+
+LP_OPTIMAL, LP_INFEASIBLE, LP_UNBOUNDED, LP_ITER_LIMIT, LP_FAILURE = 1, 2, 3, 4, 5
 
 _lib = None
 
@@ -145,6 +153,11 @@ def load_library():
                                          vp, vp, vp, C.c_int]
     lib.qpn_members_outside.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, C.c_int32, vp, C.c_int32, vp, vp, C.c_double,
                                         vp, C.c_int]
+    lib.qpn_lp_default_opts.argtypes = [C.POINTER(LpOpts)]
+    lib.qpn_lp_default_opts.restype = None
+    lib.qpn_lp_kernel_class.argtypes = [C.c_int32, C.c_int32]
+    lib.qpn_solve_lps.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, C.c_int32, vp, vp, vp, vp, C.POINTER(LpOpts),
+                                  vp, vp, vp, vp, vp, vp, C.c_int]
     del dp, ip, bp
     _lib = lib
     return lib

@@ -1730,6 +1730,56 @@ int qpn_members_outside(qpn_ctx *ctx, int32_t pairs, int32_t d, int32_t rj, cons
     return st.finish();
 }
 
+// ---- batched LP solver (qpn_lp.hip) ----------------------------------------------------------------------------------------
+void qpn_lp_default_opts(qpn_lp_opts *o)
+{
+    if (!o) return;
+    o->piv_tol = 1e-9; o->feas_tol = 1e-9; o->opt_tol = 1e-9; o->check_tol = 1e-6; o->max_iters = 0; o->reserved = 0;
+}
+
+int qpn_lp_kernel_class(int32_t r, int32_t d) { return qpn_lp_class(r, d); }
+
+int qpn_solve_lps(qpn_ctx *ctx, int32_t polys, int32_t r, int32_t d, const double *A, const double *l, const double *u, int32_t jobs,
+                  const int32_t *poly_of, const double *cost, const int32_t *obj_row, const int32_t *obj_sign, const qpn_lp_opts *opts,
+                  int32_t *status, double *x, double *obj, double *lambda, double *ray, int32_t *iters, int mem)
+{
+    if (!ctx) return QPN_ERR_ARG;
+    if (polys < 0 || jobs < 0 || r <= 0 || d <= 0) return fail_arg(ctx, "qpn_solve_lps: bad sizes");
+    if (r > QPN_LP_MAX_R || d > QPN_LP_MAX_D) { ctx->last_error = "qpn_solve_lps: d <= 256, r <= 1024 in ABI v1"; return QPN_ERR_SIZE; }
+    Stage st(ctx, mem, "qpn_solve_lps");
+    if (int rc = st.check()) return rc;
+    if (jobs == 0) return QPN_OK;
+    if (polys == 0 || !A || !l || !u || !poly_of || !status || (!cost && (!obj_row || !obj_sign))) return fail_arg(ctx, "qpn_solve_lps: null pointer");
+    // host index arrays are checked here; device ones by the kernel (such a job answers QPN_LP_FAILURE)
+    for (int t = 0; st.host && t < jobs; ++t)
+        if (poly_of[t] < 0 || poly_of[t] >= polys || (!cost && (obj_row[t] < 0 || obj_row[t] >= r)))
+            return fail_arg(ctx, "qpn_solve_lps: poly_of / obj_row out of range");
+    qpn_lp_opts o;
+    if (opts) o = *opts; else qpn_lp_default_opts(&o);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t P = (size_t)polys, J = (size_t)jobs;
+    LpArgs a{};
+    a.polys = polys; a.r = r; a.d = d; a.jobs = jobs;
+    a.piv_tol = o.piv_tol; a.feas_tol = o.feas_tol; a.opt_tol = o.opt_tol; a.check_tol = o.check_tol;
+    a.max_iters = o.max_iters > 0 ? o.max_iters : 50 * (r + d) + 100;
+    void *gws;
+    st.in(a.A, A, P * r * d * 8); st.in(a.l, l, P * r * 8); st.in(a.u, u, P * r * 8); st.in(a.poly_of, poly_of, J * 4);
+    st.in(a.cost, cost, J * d * 8);
+    st.in(a.obj_row, cost ? nullptr : obj_row, J * 4); st.in(a.obj_sign, cost ? nullptr : obj_sign, J * 4);
+    // (host mode: an output the caller does not want is not carved either -- the kernel skips a null one)
+    st.out(a.status, status, J * 4);
+    if (x || !st.host) st.out(a.x, x, J * d * 8);
+    if (obj || !st.host) st.out(a.obj, obj, J * 8);
+    if (lambda || !st.host) st.out(a.lam, lambda, J * r * 8);
+    if (ray || !st.host) st.out(a.ray, ray, J * d * 8);
+    if (iters || !st.host) st.out(a.iters, iters, J * 4);
+    st.scratch(gws, qpn_lp_workspace_bytes(jobs, r, d));
+    int rc = st.begin();
+    if (rc != QPN_OK) return rc;
+    HIPCHK(ctx, qpn_launch_solve_lps(a, gws, ctx->stream));
+    return st.finish();
+}
+
 } // extern "C"
 
 namespace {

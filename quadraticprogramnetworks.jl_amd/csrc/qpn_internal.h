@@ -275,6 +275,25 @@ hipError_t qpn_launch_members_extract(int32_t batch, int32_t d, int32_t N, const
 hipError_t qpn_launch_members_outside(int32_t pairs, int32_t d, int32_t rj, const double *Aj, const double *lj, const double *uj, int32_t Bj,
                                       const double *X, int32_t Bi, const int32_t *pi, const int32_t *pj, double t, uint8_t *out, hipStream_t s);
 #define QPN_MEMBERS_MAX_ROWS 4096
+
+// qpn_lp.hip: the batched LP solver (qpn_solve_lps).  Pointers are device pointers; x, obj, lam, ray, iters may be null.
+struct LpArgs {
+    int32_t polys, r, d, jobs;
+    const double *A, *l, *u;
+    const int32_t *poly_of;
+    const double *cost;                        // [jobs][d], or null: obj_sign[t] * row obj_row[t] of the job's polyhedron
+    const int32_t *obj_row, *obj_sign;
+    int32_t *status;
+    double *x, *obj, *lam, *ray;
+    int32_t *iters;
+    double piv_tol, feas_tol, opt_tol, check_tol;
+    int32_t max_iters;                         // resolved: > 0
+};
+#define QPN_LP_MAX_D 256
+#define QPN_LP_MAX_R 1024
+int qpn_lp_class(int32_t r, int32_t d);        // 0 wavefront, 1 workgroup in LDS, 2 workgroup over the workspace, -1 beyond the limits
+size_t qpn_lp_workspace_bytes(int32_t jobs, int32_t r, int32_t d);
+hipError_t qpn_launch_solve_lps(const LpArgs &a, void *gws, hipStream_t s);
 #define QPN_CONVEXITY_MAX_N 256
 #define QPN_CONVEXITY_MAX_M 1024
 

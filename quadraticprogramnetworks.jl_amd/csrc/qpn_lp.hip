@@ -1,0 +1,446 @@
+// qpn_lp.hip -- batched LP solver for the polyhedral primitives (qpn_solve_lps).
+//
+// Jobs over shared polyhedra: job t minimises c_t'x over {x : l <= A x <= u} of polyhedron poly_of[t], with c_t given or a signed
+// row of A read in place.  Bounded-variable primal simplex on the row-activity form (x free, s = A x in [l, u]); the method is
+// stated in include/qpn_hip.h and, operation by operation, by its numpy twin polyhedra.solve_lps_host, to which every output is
+// bit-equal: sums run over the ascending index as acc = acc + a * b (no contraction), maxima / minima / lowest ids are exact in
+// any order.  A team (one wavefront, or one workgroup of 256) works on one job:
+//   a lane per row     for the basic values, the ratio test and the row sums of the post-check,
+//   a lane per column  for the reduced costs, the pricing and the column sums of the post-check,
+//   the pivot update   column by column (a wavefront per column), lanes along the rows: the dictionary is column-major with an
+//                      odd leading dimension, so both access patterns are free of LDS bank conflicts.
+// Classes by the size of a job's slice (lp_slice_bytes): up to 16 KiB one wavefront per job, LP_WAVES jobs per workgroup, in
+// LDS; up to 156 KiB one workgroup per job in LDS; beyond, one workgroup per job over a slice of the context workspace, launched
+// in chunks.  Every loop is bounded: the crash by d, the simplex loop by max_iters.
+#include <climits>
+
+#include "qpn_internal.h"
+
+namespace {
+
+constexpr int LP_WAVES = 4;                     // jobs per workgroup in the wave class
+constexpr int LP_GROUP = 256;
+constexpr size_t LP_WAVE_SLICE_MAX = size_t(16) << 10;
+constexpr size_t LP_GROUP_SLICE_MAX = size_t(156) << 10;
+constexpr size_t LP_WS_CHUNK_BYTES = size_t(256) << 20;
+constexpr double LP_BAND = 1.0 - 0x1p-30;       // candidates within this factor of the best count as equal (PIV_BAND)
+constexpr double LP_TIE = 1e-12;
+constexpr int LP_BLAND_AFTER = 20;
+
+__host__ __device__ inline int lp_ld(int r) { return (r + 1) | 1; }
+// doubles: T [ld x d] (cost row = row r), colb [r + 1], xn dj xf ray c [d each], xb g ls us sc lam amax tgt [r each], red [8]
+__host__ __device__ inline size_t lp_slice_doubles(int r, int d)
+{
+    return (size_t)lp_ld(r) * d + (size_t)(r + 1) + 5 * (size_t)d + 8 * (size_t)r + 8;
+}
+size_t lp_slice_bytes(int r, int d) { return (lp_slice_doubles(r, d) * 8 + (size_t)(r + d) * 4 + 15) & ~(size_t)15; }
+
+template <int T> __device__ inline void team_sync()
+{
+    if (T == 64) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    } else {
+        __syncthreads();
+    }
+}
+
+// exact reductions over the team; every thread gets the result.  red: 4 doubles of the slice
+template <int T> __device__ inline double team_max(double v, double *red, int tid)
+{
+    for (int o = 32; o; o >>= 1) v = fmax(v, __shfl_xor(v, o));
+    if (T == 64) return v;
+    team_sync<T>();
+    if ((tid & 63) == 0) red[tid >> 6] = v;
+    team_sync<T>();
+    v = red[0];
+    for (int w = 1; w < T / 64; ++w) v = fmax(v, red[w]);
+    return v;
+}
+template <int T> __device__ inline double team_min(double v, double *red, int tid)
+{
+    for (int o = 32; o; o >>= 1) v = fmin(v, __shfl_xor(v, o));
+    if (T == 64) return v;
+    team_sync<T>();
+    if ((tid & 63) == 0) red[tid >> 6] = v;
+    team_sync<T>();
+    v = red[0];
+    for (int w = 1; w < T / 64; ++w) v = fmin(v, red[w]);
+    return v;
+}
+template <int T> __device__ inline int team_min_int(int v, double *red, int tid)
+{
+    for (int o = 32; o; o >>= 1) v = min(v, __shfl_xor(v, o));
+    if (T == 64) return v;
+    team_sync<T>();
+    if ((tid & 63) == 0) red[tid >> 6] = (double)v;
+    team_sync<T>();
+    v = (int)red[0];
+    for (int w = 1; w < T / 64; ++w) v = min(v, (int)red[w]);
+    return v;
+}
+
+// exchange the basic variable of row pi and the nonbasic one of column pj (the twin's _lp_pivot)
+template <int T> __device__ inline void lp_pivot(double *Tm, double *colb, int r, int d, int ld, int pi, int pj, int tid)
+{
+    const double p = Tm[(size_t)pj * ld + pi];
+    for (int k = tid; k <= r; k += T) colb[k] = Tm[(size_t)pj * ld + k];
+    team_sync<T>();
+    for (int c = tid; c < d; c += T) Tm[(size_t)c * ld + pi] = c == pj ? 1.0 / p : -Tm[(size_t)c * ld + pi] / p;
+    team_sync<T>();
+    const int lane = tid & 63;
+    for (int c = tid >> 6; c < d; c += T / 64) {
+        double *col = Tm + (size_t)c * ld;
+        const double ni = col[pi];
+        if (c == pj) {
+            for (int k = lane; k <= r; k += 64) if (k != pi) col[k] = colb[k] / p;
+        } else {
+            for (int k = lane; k <= r; k += 64) if (k != pi) col[k] = col[k] + colb[k] * ni;
+        }
+    }
+    team_sync<T>();
+}
+
+struct LpSlice {
+    double *Tm, *colb, *xn, *dj, *xf, *ray, *cv, *xb, *g, *ls, *us, *sc, *lam, *amx, *tgt, *red;
+    int *rb, *cn;
+    __device__ LpSlice(double *base, int r, int d)
+    {
+        Tm = base; colb = Tm + (size_t)lp_ld(r) * d; xn = colb + (r + 1); dj = xn + d; xf = dj + d; ray = xf + d; cv = ray + d;
+        xb = cv + d; g = xb + r; ls = g + r; us = ls + r; sc = us + r; lam = sc + r; amx = lam + r; tgt = amx + r; red = tgt + r;
+        rb = reinterpret_cast<int *>(red + 8); cn = rb + r;
+    }
+};
+
+// The solve of job t over polyhedron b.  Leaves x in S.xf, the multipliers / Farkas vector in S.lam, the ray in S.ray (zeroed by
+// the caller).  -> status; *iters, *objv.
+template <int T>
+__device__ int lp_core(const LpArgs &a, const LpSlice &S, int t, int b, int orow, int tid, int *iters_out, double *obj_out)
+{
+    const int r = a.r, d = a.d, ld = lp_ld(r);
+    const double *Ab = a.A + (size_t)b * r * d, *lb = a.l + (size_t)b * r, *ub = a.u + (size_t)b * r;
+    const double piv_tol = a.piv_tol, feas_tol = a.feas_tol, opt_tol = a.opt_tol, ct = a.check_tol;
+    double *Tm = S.Tm, *red = S.red;
+    int *rb = S.rb, *cn = S.cn;
+    *iters_out = 0; *obj_out = 0.0;
+
+    // 1. row scaling, 2. the dictionary
+    for (int j = tid; j < d; j += T) {
+        const double c = a.cost ? a.cost[(size_t)t * d + j] : (double)a.obj_sign[t] * Ab[(size_t)j * r + orow];
+        S.cv[j] = c; Tm[(size_t)j * ld + r] = c; cn[j] = j; S.xn[j] = 0.0;
+    }
+    int zbad = INT_MAX;
+    for (int i = tid; i < r; i += T) {
+        double m = 0.0;
+        for (int j = 0; j < d; ++j) m = fmax(m, fabs(Ab[(size_t)j * r + i]));
+        if (m == 0.0 && (ub[i] < 0.0 || lb[i] > 0.0)) zbad = min(zbad, i);
+        const double s = m > 0.0 ? 1.0 / m : 1.0;
+        S.amx[i] = m; S.sc[i] = s; S.ls[i] = lb[i] * s; S.us[i] = ub[i] * s; rb[i] = d + i;
+        for (int j = 0; j < d; ++j) Tm[(size_t)j * ld + i] = Ab[(size_t)j * r + i] * s;
+    }
+    team_sync<T>();
+    zbad = team_min_int<T>(zbad, red, tid);
+    if (zbad < r) {                                       // an all-zero row outside its bounds: the unit Farkas vector
+        if (tid == 0) S.lam[zbad] = ub[zbad] < 0.0 ? 1.0 : -1.0;
+        team_sync<T>();
+        return QPN_LP_INFEASIBLE;
+    }
+
+    // 3. crash
+    for (int j = 0; j < d; ++j) {
+        const double *col = Tm + (size_t)j * ld;
+        double m = 0.0;
+        for (int i = tid; i < r; i += T) if (rb[i] >= d) m = fmax(m, fabs(col[i]));
+        const double best = team_max<T>(m, red, tid);
+        if (!(best > piv_tol)) continue;
+        const double thr = best * LP_BAND;
+        int mi = INT_MAX;
+        for (int i = tid; i < r; i += T) if (rb[i] >= d && fabs(col[i]) >= thr) mi = min(mi, i);
+        const int pi = team_min_int<T>(mi, red, tid);
+        lp_pivot<T>(Tm, S.colb, r, d, ld, pi, j, tid);
+        if (tid == 0) { const int v = rb[pi]; rb[pi] = cn[j]; cn[j] = v; }
+        team_sync<T>();
+    }
+    // 4. nonbasic values
+    for (int j = tid; j < d; j += T) {
+        const int id = cn[j];
+        double v = 0.0;
+        if (id >= d) {
+            const double lo = S.ls[id - d], hi = S.us[id - d];
+            const bool fl = !isinf(lo) && lo == lo, fh = !isinf(hi) && hi == hi;
+            if (fl && fh) v = fabs(lo) <= fabs(hi) ? lo : hi;
+            else if (fl) v = lo;
+            else if (fh) v = hi;
+        }
+        S.xn[j] = v;
+    }
+    team_sync<T>();
+
+    int status = QPN_LP_FAILURE, iters = 0, degen = 0, e = -1;
+    double dirn = 0.0;
+    for (;;) {
+        // basic values, violations
+        int viol = 1;
+        for (int i = tid; i < r; i += T) {
+            double acc = 0.0;
+            for (int j = 0; j < d; ++j) {
+                const double v = S.xn[j];
+                if (v != 0.0) acc = acc + Tm[(size_t)j * ld + i] * v;
+            }
+            const int id = rb[i];
+            const double lo = id >= d ? S.ls[id - d] : -QINF, up = id >= d ? S.us[id - d] : QINF;
+            const bool below = acc < lo - feas_tol * fmax(1.0, fabs(lo)), above = acc > up + feas_tol * fmax(1.0, fabs(up));
+            S.xb[i] = acc; S.g[i] = below ? -1.0 : above ? 1.0 : 0.0;
+            if (below || above) viol = 0;
+        }
+        team_sync<T>();
+        const bool phase1 = team_min_int<T>(viol, red, tid) == 0;
+        // 5. reduced costs
+        for (int j = tid; j < d; j += T) {
+            const double *col = Tm + (size_t)j * ld;
+            double acc = col[r];
+            if (phase1) {
+                acc = 0.0;
+                for (int i = 0; i < r; ++i) {
+                    const double gi = S.g[i];
+                    if (gi != 0.0) acc = acc + gi * col[i];
+                }
+            }
+            S.dj[j] = acc;
+        }
+        team_sync<T>();
+        // 6. the entering variable
+        const bool bland = degen >= LP_BLAND_AFTER;
+        double m = 0.0;
+        int low = INT_MAX;
+        for (int j = tid; j < d; j += T) {
+            const int id = cn[j];
+            const double lo = id >= d ? S.ls[id - d] : -QINF, up = id >= d ? S.us[id - d] : QINF, v = S.xn[j], dv = S.dj[j];
+            if (lo != up && ((dv < -opt_tol && v < up) || (dv > opt_tol && v > lo))) { m = fmax(m, fabs(dv)); low = min(low, id); }
+        }
+        int eid;
+        if (bland) {
+            eid = team_min_int<T>(low, red, tid);
+        } else {
+            const double thr = team_max<T>(m, red, tid) * LP_BAND;
+            low = INT_MAX;
+            for (int j = tid; j < d; j += T) {
+                const int id = cn[j];
+                const double lo = id >= d ? S.ls[id - d] : -QINF, up = id >= d ? S.us[id - d] : QINF, v = S.xn[j], dv = S.dj[j];
+                if (lo != up && ((dv < -opt_tol && v < up) || (dv > opt_tol && v > lo)) && fabs(dv) >= thr) low = min(low, id);
+            }
+            eid = team_min_int<T>(low, red, tid);
+        }
+        if (eid == INT_MAX) { status = phase1 ? QPN_LP_INFEASIBLE : QPN_LP_OPTIMAL; break; }
+        for (int j = tid; j < d; j += T)
+            if (cn[j] == eid) {
+                const double up = eid >= d ? S.us[eid - d] : QINF;
+                red[4] = (double)j; red[5] = (S.dj[j] < -opt_tol && S.xn[j] < up) ? 1.0 : -1.0;
+            }
+        team_sync<T>();
+        e = (int)red[4]; dirn = red[5];
+        // 7. the ratio test
+        const double *ecol = Tm + (size_t)e * ld;
+        double tm = QINF;
+        for (int i = tid; i < r; i += T) {
+            const double av = ecol[i] * dirn, gi = S.g[i];
+            const int id = rb[i];
+            const double lo = id >= d ? S.ls[id - d] : -QINF, up = id >= d ? S.us[id - d] : QINF;
+            const double tg = av > 0.0 ? (gi < 0.0 ? lo : gi > 0.0 ? QINF : up) : (gi > 0.0 ? up : gi < 0.0 ? -QINF : lo);
+            const double ra = fabs(av) > piv_tol ? fmax((tg - S.xb[i]) / av, 0.0) : QINF;
+            S.colb[i] = ra; S.tgt[i] = tg;
+            tm = fmin(tm, ra);
+        }
+        const double elo = eid >= d ? S.ls[eid - d] : -QINF, eup = eid >= d ? S.us[eid - d] : QINF, exn = S.xn[e];
+        const double tflip = dirn > 0.0 ? eup - exn : exn - elo;
+        const double tmin = fmin(tflip, team_min<T>(tm, red, tid));
+        if (!(tmin < QINF)) { status = phase1 ? QPN_LP_FAILURE : QPN_LP_UNBOUNDED; break; }
+        const double thr = tmin + LP_TIE * fmax(1.0, tmin);
+        int w = INT_MAX;
+        for (int i = tid; i < r; i += T) if (S.colb[i] <= thr) w = min(w, rb[i]);
+        int win = team_min_int<T>(w, red, tid);
+        if (tflip <= thr && eid < win) win = eid;
+        if (win == INT_MAX) { status = QPN_LP_FAILURE; break; }   // (not-a-number data: no candidate compares)
+        if (iters >= a.max_iters) { status = QPN_LP_ITER_LIMIT; break; }   // a step is due and none is left
+        ++iters;
+        degen = tmin == 0.0 ? degen + 1 : 0;
+        if (win == eid) {                                 // a flip to the opposite bound: no pivot
+            team_sync<T>();
+            if (tid == 0) S.xn[e] = dirn > 0.0 ? eup : elo;
+            team_sync<T>();
+        } else {
+            for (int i = tid; i < r; i += T) if (rb[i] == win) { red[6] = (double)i; red[7] = S.tgt[i]; }
+            team_sync<T>();
+            const int pi = (int)red[6];
+            const double tv = red[7];
+            lp_pivot<T>(Tm, S.colb, r, d, ld, pi, e, tid);  // 8.
+            if (tid == 0) { rb[pi] = eid; cn[e] = win; S.xn[e] = tv; }
+            team_sync<T>();
+        }
+    }
+
+    // 9. the answer on the unscaled data, and the check of what it claims
+    for (int j = tid; j < d; j += T) if (cn[j] < d) S.xf[cn[j]] = S.xn[j];
+    for (int i = tid; i < r; i += T) if (rb[i] < d) S.xf[rb[i]] = S.xb[i];
+    team_sync<T>();
+    double obj = 0.0;
+    for (int k = 0; k < d; ++k) obj = obj + S.cv[k] * S.xf[k];
+    *iters_out = iters; *obj_out = obj;
+    if (status == QPN_LP_ITER_LIMIT || status == QPN_LP_FAILURE) return status;
+    int ok = 1;
+    double *s = S.xb;                                      // (the basic values are not needed any more)
+    for (int i = tid; i < r; i += T) {
+        double acc = 0.0;
+        for (int j = 0; j < d; ++j) acc = acc + Ab[(size_t)j * r + i] * S.xf[j];
+        s[i] = acc;
+        const double tl = ct * fmax(1.0, fabs(lb[i])), tu = ct * fmax(1.0, fabs(ub[i]));
+        if (status != QPN_LP_INFEASIBLE && !(acc >= lb[i] - tl && acc <= ub[i] + tu)) ok = 0;
+    }
+    if (status == QPN_LP_OPTIMAL) {
+        for (int j = tid; j < d; j += T) if (cn[j] >= d) S.lam[cn[j] - d] = S.dj[j] * S.sc[cn[j] - d];
+        team_sync<T>();
+        for (int k = tid; k < d; k += T) {
+            double acc = 0.0;
+            for (int i = 0; i < r; ++i) acc = acc + Ab[(size_t)k * r + i] * S.lam[i];
+            if (!(fabs(S.cv[k] - acc) <= ct * fmax(1.0, fabs(S.cv[k])))) ok = 0;
+        }
+        for (int i = tid; i < r; i += T) {
+            const double lm = S.lam[i];
+            if (lm > ct && !(fabs(s[i] - lb[i]) <= ct * fmax(1.0, fabs(lb[i])))) ok = 0;
+            if (lm < -ct && !(fabs(s[i] - ub[i]) <= ct * fmax(1.0, fabs(ub[i])))) ok = 0;
+        }
+    } else if (status == QPN_LP_UNBOUNDED) {
+        const double *ecol = Tm + (size_t)e * ld;
+        if (tid == 0 && cn[e] < d) S.ray[cn[e]] = dirn;
+        for (int i = tid; i < r; i += T) if (rb[i] < d) S.ray[rb[i]] = ecol[i] * dirn;
+        team_sync<T>();
+        double cr = 0.0, rmax = 0.0;
+        for (int k = 0; k < d; ++k) { cr = cr + S.cv[k] * S.ray[k]; rmax = fmax(rmax, fabs(S.ray[k])); }
+        if (!(cr < 0.0)) ok = 0;
+        for (int i = tid; i < r; i += T) {
+            double acc = 0.0;
+            for (int j = 0; j < d; ++j) acc = acc + Ab[(size_t)j * r + i] * S.ray[j];
+            const double tr = ct * fmax(1.0, rmax) * S.amx[i];
+            if (!isinf(lb[i]) && lb[i] == lb[i] && !(acc >= -tr)) ok = 0;
+            if (!isinf(ub[i]) && ub[i] == ub[i] && !(acc <= tr)) ok = 0;
+        }
+    } else {
+        for (int i = tid; i < r; i += T) if (rb[i] >= d) S.lam[rb[i] - d] = S.g[i] * S.sc[rb[i] - d];
+        for (int j = tid; j < d; j += T)
+            if (cn[j] >= d) {
+                const int k = cn[j] - d;
+                double y = -S.dj[j];
+                if ((y > 0.0 && !(fabs(ub[k]) < QINF)) || (y < 0.0 && !(fabs(lb[k]) < QINF))) y = 0.0;
+                S.lam[k] = y * S.sc[k];
+            }
+        team_sync<T>();
+        double ymax = 0.0, bound = 0.0;
+        for (int i = 0; i < r; ++i) {
+            const double y = S.lam[i];
+            ymax = fmax(ymax, fabs(y));
+            if (y > 0.0) bound = bound + y * ub[i];
+            else if (y < 0.0) bound = bound + y * lb[i];
+        }
+        ymax = fmax(1.0, ymax);
+        for (int k = tid; k < d; k += T) {
+            double acc = 0.0;
+            for (int i = 0; i < r; ++i) acc = acc + Ab[(size_t)k * r + i] * S.lam[i];
+            if (!(fabs(acc) <= ct * ymax)) ok = 0;
+        }
+        if (!(bound < 0.0)) ok = 0;
+    }
+    team_sync<T>();
+    return team_min_int<T>(ok, red, tid) ? status : QPN_LP_FAILURE;
+}
+
+template <int T> __device__ void lp_job(const LpArgs &a, int t, double *base, int tid)
+{
+    const int r = a.r, d = a.d;
+    const LpSlice S(base, r, d);
+    for (int j = tid; j < d; j += T) { S.xf[j] = 0.0; S.ray[j] = 0.0; }
+    for (int i = tid; i < r; i += T) S.lam[i] = 0.0;
+    if (tid < 8) S.red[tid] = 0.0;
+    team_sync<T>();
+    // an index out of range (device arrays are not read by the host): the job fails and reads nothing
+    const int b = a.poly_of[t], orow = a.cost ? 0 : a.obj_row[t];
+    int status = QPN_LP_FAILURE, iters = 0;
+    double obj = 0.0;
+    if (b >= 0 && b < a.polys && orow >= 0 && orow < r) status = lp_core<T>(a, S, t, b, orow, tid, &iters, &obj);
+    team_sync<T>();
+    if (a.x) for (int j = tid; j < d; j += T) a.x[(size_t)t * d + j] = S.xf[j];
+    if (a.ray) for (int j = tid; j < d; j += T) a.ray[(size_t)t * d + j] = S.ray[j];
+    if (a.lam) for (int i = tid; i < r; i += T) a.lam[(size_t)t * r + i] = S.lam[i];
+    if (tid == 0) {
+        a.status[t] = status;
+        if (a.obj) a.obj[t] = obj;
+        if (a.iters) a.iters[t] = iters;
+    }
+}
+
+__global__ __launch_bounds__(64 * LP_WAVES) void lp_wave_kernel(LpArgs a, size_t slice)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char lp_lds[];
+    const int w = threadIdx.x / 64;
+    const long long t = (long long)blockIdx.x * LP_WAVES + w;
+    if (t >= a.jobs) return;                              // a whole wavefront leaves: the others never wait for it
+    lp_job<64>(a, (int)t, reinterpret_cast<double *>(lp_lds + (size_t)w * slice), threadIdx.x % 64);
+}
+
+template <bool LDS> __global__ __launch_bounds__(LP_GROUP) void lp_group_kernel(LpArgs a, int32_t first, unsigned char *gws, size_t slice)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char lp_lds[];
+    unsigned char *base = LDS ? lp_lds : gws + (size_t)blockIdx.x * slice;
+    lp_job<LP_GROUP>(a, first + (int)blockIdx.x, reinterpret_cast<double *>(base), threadIdx.x);
+}
+
+int32_t lp_chunk(int32_t jobs, int32_t r, int32_t d)
+{
+    size_t c = LP_WS_CHUNK_BYTES / lp_slice_bytes(r, d);
+    if (c < 1) c = 1;
+    return (int32_t)(c < (size_t)jobs ? c : (size_t)jobs);
+}
+
+} // namespace
+
+int qpn_lp_class(int32_t r, int32_t d)
+{
+    if (r <= 0 || d <= 0 || r > QPN_LP_MAX_R || d > QPN_LP_MAX_D) return -1;
+    const size_t b = lp_slice_bytes(r, d);
+    return b <= LP_WAVE_SLICE_MAX ? 0 : b <= LP_GROUP_SLICE_MAX ? 1 : 2;
+}
+
+size_t qpn_lp_workspace_bytes(int32_t jobs, int32_t r, int32_t d)
+{
+    if (jobs <= 0 || qpn_lp_class(r, d) != 2) return 0;
+    return (size_t)lp_chunk(jobs, r, d) * lp_slice_bytes(r, d);
+}
+
+hipError_t qpn_launch_solve_lps(const LpArgs &a, void *gws, hipStream_t s)
+{
+    if (a.jobs <= 0) return hipSuccess;
+    const int cls = qpn_lp_class(a.r, a.d);
+    const size_t slice = lp_slice_bytes(a.r, a.d);
+    if (cls == 0) {
+        static QpnLdsLimits lds_limits;                  // (4 slices of 16 KiB: at the 64 KiB default, raised for clarity)
+        if (const hipError_t e = lds_limits.raise({{lp_wave_kernel, (int)(LP_WAVE_SLICE_MAX * LP_WAVES)}}); e != hipSuccess) return e;
+        const unsigned grid = (unsigned)((a.jobs + LP_WAVES - 1) / LP_WAVES);
+        hipLaunchKernelGGL(lp_wave_kernel, dim3(grid), dim3(64 * LP_WAVES), slice * LP_WAVES, s, a, slice);
+        return hipGetLastError();
+    }
+    if (cls == 1) {
+        static QpnLdsLimits lds_limits;
+        if (const hipError_t e = lds_limits.raise({{lp_group_kernel<true>, (int)LP_GROUP_SLICE_MAX}}); e != hipSuccess) return e;
+        hipLaunchKernelGGL(lp_group_kernel<true>, dim3((unsigned)a.jobs), dim3(LP_GROUP), slice, s, a, 0, static_cast<unsigned char *>(nullptr),
+                           slice);
+        return hipGetLastError();
+    }
+    const int32_t chunk = lp_chunk(a.jobs, a.r, a.d);
+    for (int32_t first = 0; first < a.jobs; first += chunk) {
+        const int32_t count = a.jobs - first < chunk ? a.jobs - first : chunk;
+        hipLaunchKernelGGL(lp_group_kernel<false>, dim3((unsigned)count), dim3(LP_GROUP), 0, s, a, first, static_cast<unsigned char *>(gws),
+                           slice);
+        if (const hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}

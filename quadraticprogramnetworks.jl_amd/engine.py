@@ -17,7 +17,7 @@ import time
 import numpy as np
 
 from . import _lib
-from ._lib import MEM_DEVICE, MEM_HOST, AviOpts
+from ._lib import MEM_DEVICE, MEM_HOST, AviOpts, LpOpts
 
 try:  # torch is plumbing (device memory, streams, torch.distributed), not a requirement to import
     import torch
@@ -639,6 +639,45 @@ class Engine:
         out = self._alloc(dev, (pairs,), np.uint8)
         self._call("qpn_members_outside", pairs, d, rj, _ptr(Ajc), _ptr(lj), _ptr(uj), Bj, _ptr(X), int(X.shape[0]), _ptr(pi), _ptr(pj),
                    float(t), _ptr(out), self._mem(dev))
+        return out
+
+    # -- the LP solver of the polyhedral primitives --------------------------------------------------------------
+    def default_lp_opts(self) -> LpOpts:
+        o = LpOpts()
+        self.lib.qpn_lp_default_opts(C.byref(o))
+        return o
+
+    def lp_kernel_class(self, r, d):
+        """Which kernel class takes LPs of r rows in d variables: 0 wavefront, 1 workgroup in LDS, 2 workgroup over the workspace,
+        -1 beyond the limits (qpn_lp_kernel_class)."""
+        return int(self.lib.qpn_lp_kernel_class(int(r), int(d)))
+
+    def solve_lps(self, Ac, l, u, poly_of, cost=None, obj_row=None, obj_sign=None, opts=None):
+        """LPs over shared polyhedra (qpn_solve_lps; polyhedra.solve_lps_host is its numpy twin, bit for bit): Ac [polys, d, r]
+        (A in the ABI layout, ``colmajor(A)``), l, u [polys, r], poly_of [jobs] int32; job t minimises cost[t]'x or, without
+        `cost`, obj_sign[t] * (row obj_row[t] of its polyhedron)'x (int32 arrays).  opts: LpOpts, a dict of its fields, or None.
+        Returns dict(status [jobs] int32 (_lib.LP_*), x [jobs, d], obj [jobs], lam [jobs, r], ray [jobs, d], iters [jobs] int32)."""
+        if cost is None and (obj_row is None or obj_sign is None):
+            raise QpnError("solve_lps: give cost, or obj_row and obj_sign")
+        if cost is not None:
+            obj_row = obj_sign = None
+        dev, Ac, l, u, cost, poly_of, obj_row, obj_sign = self._stage("solve_lps", "Ac l u cost poly_of obj_row obj_sign", f64=(Ac, l, u, cost),
+                                                                     i32=(poly_of, obj_row, obj_sign))
+        polys, d, r = (int(v) for v in Ac.shape)
+        jobs = int(poly_of.shape[0])
+        if tuple(l.shape) != (polys, r) or tuple(u.shape) != (polys, r) or (cost is not None and tuple(cost.shape) != (jobs, d)) or (
+                cost is None and (tuple(obj_row.shape) != (jobs,) or tuple(obj_sign.shape) != (jobs,))):
+            raise QpnError("solve_lps: inconsistent shapes")
+        if isinstance(opts, dict):
+            o = self.default_lp_opts()
+            for k, v in opts.items():
+                setattr(o, k, v)
+            opts = o
+        out = dict(status=self._alloc(dev, (jobs,), np.int32), x=self._alloc(dev, (jobs, d), np.float64), obj=self._alloc(dev, (jobs,), np.float64),
+                   lam=self._alloc(dev, (jobs, r), np.float64), ray=self._alloc(dev, (jobs, d), np.float64), iters=self._alloc(dev, (jobs,), np.int32))
+        self._call("qpn_solve_lps", polys, r, d, _ptr(Ac), _ptr(l), _ptr(u), jobs, _ptr(poly_of), _ptr(cost), _ptr(obj_row), _ptr(obj_sign),
+                   C.byref(opts) if opts is not None else None, _ptr(out["status"]), _ptr(out["x"]), _ptr(out["obj"]), _ptr(out["lam"]),
+                   _ptr(out["ray"]), _ptr(out["iters"]), self._mem(dev))
         return out
 
 

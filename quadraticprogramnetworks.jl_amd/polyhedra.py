@@ -511,6 +511,12 @@ def exemplar_slack_batch(polys, engine, tol=1e-2, slack_cap=1.0, strict=True):
             empty[b] = not ok; example[b] = x if ok else None
             continue
         todo.append(b)
+    if todo and _has_lps(engine):
+        # closed polyhedra: the answer depends on eps alone -- the LP solver; with an open bound it depends on which duals the
+        # solver returns: today's route
+        closed = [b for b in todo if not opens[b][0].any() and not opens[b][1].any()]
+        todo = [b for b in todo if opens[b][0].any() or opens[b][1].any()]
+        _exemplar_slack_lps(closed, trips, engine, tol, slack_cap, strict, empty, example, eps_out)
     if todo:
         dmax = max(trips[b][0].shape[1] for b in todo) + 1
         mmax = max(2 * trips[b][0].shape[0] for b in todo) + 1
@@ -577,6 +583,10 @@ def implicit_bounds_batch(polys, engine, tol=1e-4):
             else:
                 jobs.append((b, i, 1.0)); jobs.append((b, i, -1.0))
         out.append([eq, vals])
+    if jobs and _has_lps(engine):
+        ext = _row_extremes_lps(trips, jobs, engine)
+        jobs = []
+        _implicit_from_extremes(trips, out, ext, tol)
     if jobs:
         dmax = max(trips[b][0].shape[1] for b, _, _ in jobs); mmax = max(trips[b][0].shape[0] for b, _, _ in jobs)
         A2 = np.zeros((len(jobs), mmax, dmax)); l2 = np.full((len(jobs), mmax), -INF); u2 = np.full((len(jobs), mmax), INF)
@@ -636,12 +646,302 @@ def implicit_bounds_batch(polys, engine, tol=1e-4):
             else:
                 raise RuntimeError(f"implicit_bounds_batch: solver status {st[k]} on polyhedron {b}, row {i}")
             ext[(b, i, sg)] = v
-        for b, (A, l, u) in enumerate(trips):
-            eq, vals = out[b]
-            for i in range(A.shape[0]):
-                if (b, i, 1.0) in ext:
-                    lo_, hi_ = ext[(b, i, 1.0)], ext[(b, i, -1.0)]
-                    eq[i] = bool(np.isfinite(lo_) and np.isfinite(hi_) and abs(lo_ - hi_) <= tol)
-                    if eq[i]:
-                        vals[i] = 0.5 * (hi_ + lo_)
+        _implicit_from_extremes(trips, out, ext, tol)
     return [(eq, vals) for eq, vals in out]
+
+
+def _implicit_from_extremes(trips, out, ext, tol):
+    """implicit_bounds_batch's last step: rows whose minimum and maximum over the polyhedron coincide (ext[(b, i, +-1.0)])."""
+    for b, (A, l, u) in enumerate(trips):
+        eq, vals = out[b]
+        for i in range(A.shape[0]):
+            if (b, i, 1.0) in ext:
+                lo_, hi_ = ext[(b, i, 1.0)], ext[(b, i, -1.0)]
+                eq[i] = bool(np.isfinite(lo_) and np.isfinite(hi_) and abs(lo_ - hi_) <= tol)
+                if eq[i]:
+                    vals[i] = 0.5 * (hi_ + lo_)
+
+
+def _has_lps(engine):
+    return callable(getattr(engine, "solve_lps", None))
+
+
+def _row_extremes_lps(trips, jobs, engine):
+    """implicit_bounds_batch's LPs on an engine with `solve_lps`: the polyhedra that have jobs are packed by shape (rows,
+    columns) and go up once per pack; a job names its objective by (row, sign), so no cost vector and no copy of the
+    polyhedron is made for it; an unbounded row is the solver's own answer.  jobs: [(polyhedron, row, sign)].
+    -> {(b, i, sign): the extreme of a_i'x, -+inf when unbounded}."""
+    from .engine import colmajor
+    packs = {}
+    for b, i, sg in jobs:
+        packs.setdefault(trips[b][0].shape, {}).setdefault(b, []).append((i, sg))
+    ext = {}
+    for (r, d), of in sorted(packs.items()):
+        members = sorted(of)
+        A = np.stack([trips[b][0] for b in members]).reshape(len(members), r, d)
+        l = np.stack([trips[b][1] for b in members]).reshape(len(members), r); u = np.stack([trips[b][2] for b in members]).reshape(len(members), r)
+        keys = [(b, i, sg) for b in members for i, sg in of[b]]
+        poly_of = np.repeat(np.arange(len(members), dtype=np.int32), [len(of[b]) for b in members])
+        res = engine.solve_lps(colmajor(A), l, u, poly_of, obj_row=np.array([k[1] for k in keys], np.int32),
+                               obj_sign=np.array([int(k[2]) for k in keys], np.int32))
+        st = _to_host(res["status"]); obj = _to_host(res["obj"])
+        for t, (b, i, sg) in enumerate(keys):
+            if st[t] == LP_OPTIMAL:
+                ext[(b, i, sg)] = float(sg * obj[t])
+            elif st[t] == LP_UNBOUNDED:
+                ext[(b, i, sg)] = -INF if sg > 0 else INF       # (:691-693, :704-706)
+            else:
+                raise RuntimeError(f"implicit_bounds_batch: LP status {st[t]} on polyhedron {b}, row {i}")
+    return ext
+
+
+def _exemplar_slack_lps(items, trips, engine, tol, slack_cap, strict, empty, example, eps_out):
+    """exemplar_slack_batch's slack LPs of closed polyhedra on an engine with `solve_lps`, packed by shape: rows [A, 1] >= l,
+    [-A, 1] >= -u and eps >= -cap; the objective eps is the last row itself.  Fills empty, example, eps_out at `items`."""
+    from .engine import colmajor
+    packs = {}
+    for b in items:
+        packs.setdefault(trips[b][0].shape, []).append(b)
+    for (n, d), members in sorted(packs.items()):
+        k = len(members)
+        A = np.stack([trips[b][0] for b in members]).reshape(k, n, d)
+        A2 = np.zeros((k, 2 * n + 1, d + 1)); l2 = np.empty((k, 2 * n + 1))
+        A2[:, :n, :d] = A; A2[:, n:2 * n, :d] = -A; A2[:, :, d] = 1.0
+        l2[:, :n] = np.stack([trips[b][1] for b in members]).reshape(k, n); l2[:, n:2 * n] = -np.stack([trips[b][2] for b in members]).reshape(k, n)
+        l2[:, 2 * n] = -slack_cap
+        res = engine.solve_lps(colmajor(A2), l2, np.full((k, 2 * n + 1), INF), np.arange(k, dtype=np.int32),
+                               obj_row=np.full(k, 2 * n, np.int32), obj_sign=np.ones(k, np.int32))
+        st = _to_host(res["status"]); x = _to_host(res["x"])
+        for t, b in enumerate(members):
+            if st[t] != LP_OPTIMAL:
+                if strict:
+                    raise RuntimeError(f"exemplar_slack_batch: LP status {st[t]} on item {b}")
+                continue
+            eps_out[b] = x[t, d]
+            empty[b] = bool(x[t, d] > tol)
+            if not empty[b]:
+                example[b] = x[t, :d].copy()
+
+
+# ---- the LP solver (qpn_solve_lps): bounded-variable primal simplex, the numpy twin -----------------------------------------
+LP_OPTIMAL, LP_INFEASIBLE, LP_UNBOUNDED, LP_ITER_LIMIT, LP_FAILURE = 1, 2, 3, 4, 5
+LP_PIV_BAND = 1.0 - 2.0 ** -30                  # pivot / pricing candidates within this factor of the best count as equal
+LP_RATIO_TIE = 1e-12                            # ratios within this (relative, at least absolute) of the smallest count as tied
+LP_BLAND_AFTER = 20                             # consecutive zero-length steps before the lowest eligible id enters
+LP_DEFAULT_OPTS = dict(piv_tol=1e-9, feas_tol=1e-9, opt_tol=1e-9, check_tol=1e-6, max_iters=0)
+LP_MAX_D, LP_MAX_R = 256, 1024
+
+
+def _lp_pivot(T, i, j):
+    """Exchange the basic variable of row i and the nonbasic one of column j of the dictionary T [r + 1, d] (cost row last)."""
+    p = T[i, j]
+    col = T[:, j].copy()
+    new = -T[i, :] / p
+    new[j] = 1.0 / p
+    T += col[:, None] * new[None, :]
+    T[:, j] = col / p
+    T[i, :] = new
+
+
+def _lp_one(A, l, u, c, o):
+    """One LP  min c'x  s.t.  l <= A x <= u  (A [r, d] math layout) by the method of qpn_solve_lps (include/qpn_hip.h states it).
+    -> (status, x [d], obj, lambda [r], ray [d], iters)."""
+    r, d = A.shape
+    piv_tol, feas_tol, opt_tol, ct = o["piv_tol"], o["feas_tol"], o["opt_tol"], o["check_tol"]
+    max_iters = o["max_iters"] if o["max_iters"] > 0 else 50 * (r + d) + 100
+    x = np.zeros(d); lam = np.zeros(r); ray = np.zeros(d)
+    with np.errstate(all="ignore"):
+        # 1. row scaling; an all-zero row outside its bounds settles the job
+        amax = np.max(np.abs(A), axis=1)
+        for i in range(r):
+            if amax[i] == 0.0 and (u[i] < 0.0 or l[i] > 0.0):
+                lam[i] = 1.0 if u[i] < 0.0 else -1.0
+                return LP_INFEASIBLE, x, 0.0, lam, ray, 0
+        sc = np.ones(r)
+        nz = amax > 0.0
+        sc[nz] = 1.0 / amax[nz]
+        ls, us = l * sc, u * sc
+        # 2. the dictionary: basic = T nonbasic, the cost row below it
+        T = np.empty((r + 1, d))
+        T[:r] = A * sc[:, None]
+        T[r] = c
+        rb = d + np.arange(r); cn = np.arange(d)
+        # 3. crash: the x come into the basis, column by column
+        for j in range(d):
+            col = np.where(rb >= d, np.abs(T[:r, j]), 0.0)
+            best = np.max(col)
+            if not best > piv_tol:
+                continue
+            i = int(np.nonzero((rb >= d) & (col >= best * LP_PIV_BAND))[0][0])
+            _lp_pivot(T, i, j)
+            rb[i], cn[j] = cn[j], rb[i]
+        # 4. nonbasic values
+        xn = np.zeros(d)
+        for j in range(d):
+            if cn[j] >= d:
+                lo, hi = ls[cn[j] - d], us[cn[j] - d]
+                if np.isfinite(lo) and np.isfinite(hi):
+                    xn[j] = lo if abs(lo) <= abs(hi) else hi
+                elif np.isfinite(lo):
+                    xn[j] = lo
+                elif np.isfinite(hi):
+                    xn[j] = hi
+        status, iters, degen = LP_FAILURE, 0, 0
+        e, dirn, a, g, dj = -1, 0.0, None, None, None
+        while True:
+            lob = np.where(rb >= d, ls[np.maximum(rb - d, 0)], -INF); upb = np.where(rb >= d, us[np.maximum(rb - d, 0)], INF)
+            lon = np.where(cn >= d, ls[np.maximum(cn - d, 0)], -INF); upn = np.where(cn >= d, us[np.maximum(cn - d, 0)], INF)
+            xb = np.zeros(r)
+            for j in range(d):                          # (a nonbasic at 0 adds nothing)
+                if xn[j] != 0.0:
+                    xb = xb + T[:r, j] * xn[j]
+            below = xb < lob - feas_tol * np.maximum(1.0, np.abs(lob))
+            above = xb > upb + feas_tol * np.maximum(1.0, np.abs(upb))
+            g = np.where(below, -1.0, np.where(above, 1.0, 0.0))
+            phase1 = bool(np.any(g != 0.0))
+            if phase1:                                  # 5. the gradient of the sum of violations
+                dj = np.zeros(d)
+                for i in range(r):
+                    if g[i] != 0.0:
+                        dj = dj + g[i] * T[i, :]
+            else:
+                dj = T[r].copy()
+            # 6. the entering variable
+            free = lon != upn
+            inc = (dj < -opt_tol) & (xn < upn) & free
+            dec = (dj > opt_tol) & (xn > lon) & free
+            elig = inc | dec
+            if not elig.any():
+                status = LP_INFEASIBLE if phase1 else LP_OPTIMAL
+                break
+            if degen >= LP_BLAND_AFTER:
+                pick = elig
+            else:
+                mag = np.where(elig, np.abs(dj), 0.0)
+                pick = elig & (mag >= np.max(mag) * LP_PIV_BAND)
+            e = int(np.argmin(np.where(pick, cn, r + d)))
+            dirn = 1.0 if inc[e] else -1.0
+            # 7. the ratio test
+            a = T[:r, e] * dirn
+            tgt = np.where(a > 0.0, np.where(below, lob, np.where(above, INF, upb)), np.where(above, upb, np.where(below, -INF, lob)))
+            ratio = np.where(np.abs(a) > piv_tol, np.maximum((tgt - xb) / a, 0.0), INF)
+            tflip = upn[e] - xn[e] if dirn > 0.0 else xn[e] - lon[e]
+            tmin = min(tflip, np.min(ratio)) if r else tflip
+            if not tmin < INF:
+                status = LP_FAILURE if phase1 else LP_UNBOUNDED
+                break
+            thr = tmin + LP_RATIO_TIE * max(1.0, tmin)
+            win = int(np.min(np.where(ratio <= thr, rb, r + d))) if r else r + d
+            if tflip <= thr and cn[e] < win:
+                win = int(cn[e])
+            if win == r + d:                            # (not-a-number data: no candidate compares)
+                status = LP_FAILURE
+                break
+            if iters >= max_iters:                      # a step is due and none is left: a job that ends within max_iters keeps its outcome
+                status = LP_ITER_LIMIT
+                break
+            iters += 1
+            degen = degen + 1 if tmin == 0.0 else 0
+            if win == cn[e]:
+                xn[e] = upn[e] if dirn > 0.0 else lon[e]
+            else:
+                i = int(np.nonzero(rb == win)[0][0])
+                _lp_pivot(T, i, e)                      # 8.
+                rb[i], cn[e] = cn[e], rb[i]
+                xn[e] = tgt[i]
+        # 9. the answer on the unscaled data, and the check of what it claims
+        for j in range(d):
+            if cn[j] < d:
+                x[cn[j]] = xn[j]
+        for i in range(r):
+            if rb[i] < d:
+                x[rb[i]] = xb[i]
+        obj = 0.0
+        for k in range(d):
+            obj = obj + c[k] * x[k]
+        if status in (LP_ITER_LIMIT, LP_FAILURE):
+            return status, x, obj, lam, ray, iters
+        s = np.zeros(r)
+        for j in range(d):
+            s = s + A[:, j] * x[j]
+        tl = ct * np.maximum(1.0, np.abs(l)); tu = ct * np.maximum(1.0, np.abs(u))
+        ok = True
+        if status != LP_INFEASIBLE:
+            ok = bool(np.all((s >= l - tl) & (s <= u + tu)))
+        if status == LP_OPTIMAL:
+            for j in range(d):
+                if cn[j] >= d:
+                    lam[cn[j] - d] = dj[j] * sc[cn[j] - d]
+            for k in range(d):
+                acc = 0.0
+                for i in range(r):
+                    acc = acc + A[i, k] * lam[i]
+                ok = ok and bool(abs(c[k] - acc) <= ct * max(1.0, abs(c[k])))
+            ok = ok and bool(np.all(~(lam > ct) | (np.abs(s - l) <= tl)) and np.all(~(lam < -ct) | (np.abs(s - u) <= tu)))
+        elif status == LP_UNBOUNDED:
+            if cn[e] < d:
+                ray[cn[e]] = dirn
+            for i in range(r):
+                if rb[i] < d:
+                    ray[rb[i]] = a[i]
+            cr = 0.0
+            for k in range(d):
+                cr = cr + c[k] * ray[k]
+            ar = np.zeros(r)
+            for j in range(d):
+                ar = ar + A[:, j] * ray[j]
+            tr = ct * max(1.0, float(np.max(np.abs(ray)))) * amax
+            ok = ok and bool(cr < 0.0) and bool(np.all(~np.isfinite(l) | (ar >= -tr)) and np.all(~np.isfinite(u) | (ar <= tr)))
+        else:
+            for i in range(r):
+                if rb[i] >= d:
+                    lam[rb[i] - d] = g[i] * sc[rb[i] - d]
+            for j in range(d):
+                if cn[j] >= d:
+                    k = cn[j] - d
+                    y = -dj[j]
+                    if (y > 0.0 and not np.isfinite(u[k])) or (y < 0.0 and not np.isfinite(l[k])):
+                        y = 0.0
+                    lam[k] = y * sc[k]
+            ymax = max(1.0, float(np.max(np.abs(lam)))) if r else 1.0
+            for k in range(d):
+                acc = 0.0
+                for i in range(r):
+                    acc = acc + A[i, k] * lam[i]
+                ok = ok and bool(abs(acc) <= ct * ymax)
+            bound = 0.0
+            for i in range(r):
+                if lam[i] > 0.0:
+                    bound = bound + lam[i] * u[i]
+                elif lam[i] < 0.0:
+                    bound = bound + lam[i] * l[i]
+            ok = ok and bool(bound < 0.0)
+        return (status if ok else LP_FAILURE), x, obj, lam, ray, iters
+
+
+def solve_lps_host(Ac, l, u, poly_of, cost=None, obj_row=None, obj_sign=None, opts=None):
+    """The numpy twin of Engine.solve_lps (qpn_solve_lps), the normative statement of the method: the kernel does the same
+    operations in the same order (every sum over the ascending index as acc = acc + a * b, no contraction), so every output is
+    bit-equal.  Ac [polys, d, r] (the polyhedra's matrices in the ABI layout), l, u [polys, r] (+-inf allowed), poly_of [jobs];
+    the objective of job t is cost[t] or, without `cost`, obj_sign[t] * row obj_row[t] of its polyhedron.
+    -> dict(status [jobs] int32, x [jobs, d], obj [jobs], lam [jobs, r], ray [jobs, d], iters [jobs] int32).  A job whose
+    poly_of / obj_row is out of range answers LP_FAILURE with zeros (the kernel's rule for device index arrays)."""
+    Ac = np.asarray(Ac, dtype=np.float64); l = np.asarray(l, dtype=np.float64); u = np.asarray(u, dtype=np.float64)
+    polys, d, r = Ac.shape
+    poly_of = np.asarray(poly_of, dtype=np.int64)
+    jobs = len(poly_of)
+    o = dict(LP_DEFAULT_OPTS)
+    o.update(opts or {})
+    out = dict(status=np.zeros(jobs, np.int32), x=np.zeros((jobs, d)), obj=np.zeros(jobs), lam=np.zeros((jobs, r)),
+               ray=np.zeros((jobs, d)), iters=np.zeros(jobs, np.int32))
+    for t in range(jobs):
+        b = int(poly_of[t])
+        row_ok = cost is not None or 0 <= int(obj_row[t]) < r
+        if not (0 <= b < polys) or not row_ok:
+            out["status"][t] = LP_FAILURE
+            continue
+        A = np.ascontiguousarray(Ac[b].T)
+        c = np.asarray(cost[t], dtype=np.float64) if cost is not None else float(obj_sign[t]) * A[int(obj_row[t])]
+        st, x, obj, lam, ray, it = _lp_one(A, l[b], u[b], c, o)
+        out["status"][t] = st; out["x"][t] = x; out["obj"][t] = obj; out["lam"][t] = lam; out["ray"][t] = ray; out["iters"][t] = it
+    return out
