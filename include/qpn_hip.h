@@ -524,6 +524,41 @@ int qpn_solve_lps(qpn_ctx *ctx, int32_t polys, int32_t r, int32_t d, const doubl
                   const int32_t *poly_of, const double *cost, const int32_t *obj_row, const int32_t *obj_sign, const qpn_lp_opts *opts,
                   int32_t *status, double *x, double *obj, double *lambda, double *ray, int32_t *iters, int mem);
 
+/* qpn_issubset_pairs: `pairs` subset questions P1 within P2 (`issubset`, src/sets.jl:376-407) over B1 first pieces and B2 second
+ * pieces, one job per pair: first piece pi[q] against second piece pj[q].  A1 [B1][r1][d], A2 [B2][r2][d] column-major per item,
+ * l1, u1 [B1][r1], l2, u2 [B2][r2] (+-inf allowed), pi, pj [pairs] int32.  Outputs per pair (how, bound, val, lps, iters may be NULL):
+ *   sub [pairs] uint8: 1 for HOLDS and EMPTY, 0 otherwise;  how [pairs] int32 (QPN_SUBSET_*);
+ *   bound [pairs] int32: 2 i + side of the bound of P2 that decided (side 0 = l2[i], 1 = u2[i]), -1 where none did;
+ *   val [pairs]: the objective value that decided (BY_POINT, BY_OPTIMUM), 0 otherwise;
+ *   lps [pairs] int32: simplex solves started, the feasibility solve counted;  iters [pairs] int32: all their steps.
+ * Method (polyhedra.issubset_pairs_host is its numpy twin and the normative statement; every output is bit-equal to it, by the
+ * discipline of qpn_solve_lps, whose set-up, loop and check it runs):  (a) steps 1-8 of qpn_solve_lps on P1 with c = 0: the crash
+ * and phase 1 once per pair; an INFEASIBLE end whose Farkas certificate holds is EMPTY, otherwise FAILURE; ITER_LIMIT and FAILURE
+ * pass through.  (b) the rows i of P2 ascending, the lower bound (c = +a2_i, beta = l2[i]) before the upper (c = -a2_i, beta =
+ * -u2[i]); a non-finite bound is skipped.  (c) own-row skip: when rows k of P1 equal row i of P2 entry by entry (IEEE ==, unscaled)
+ * and max l1[k] >= l2[i] - tol (min u1[k] <= u2[i] + tol) over them, the bound holds on all of P1 and needs no work.  (d) point
+ * test: v = c'x at the point the previous solve ended at; v < beta - tol is BY_POINT.  (e) no second crash: the cost row of c in the
+ * current dictionary, column j: acc = 0; rows i ascending that hold an x: acc = acc + c[id] * T[i][j]; then + c[id] when column j
+ * holds an x.  (f) the loop with fresh step and degeneracy counters (max_iters per objective), then the check of step 9 on P1:
+ * OPTIMAL with obj < beta - tol is BY_OPTIMUM, otherwise the next bound; a certified ray is UNBOUNDED; a certificate that fails, or
+ * an INFEASIBLE end, is FAILURE.  (g) no bound left: HOLDS.
+ * Kernel classes are those of qpn_lp_kernel_class(r1, d); nothing of P2 is copied.  Host pi / pj out of range: QPN_ERR_ARG; device
+ * ones: that pair answers sub = 0, QPN_SUBSET_FAILURE, bound = -1, zeros elsewhere and reads nothing.  1 <= d <= 256, 1 <= r1, r2
+ * <= 1024 (QPN_ERR_SIZE beyond).  pairs == 0 succeeds. */
+enum {
+    QPN_SUBSET_HOLDS = 0,      /* every finite bound of P2 passed                                  sub = 1 */
+    QPN_SUBSET_BY_POINT = 1,   /* the current vertex of P1 lies below a bound by more than tol     sub = 0 */
+    QPN_SUBSET_BY_OPTIMUM = 2, /* a certified optimum lies below the bound by more than tol        sub = 0 */
+    QPN_SUBSET_UNBOUNDED = 3,  /* a bound's objective is unbounded below on P1, certified by a ray sub = 0 */
+    QPN_SUBSET_ITER_LIMIT = 4, /* the iteration limit was reached                                  sub = 0 */
+    QPN_SUBSET_FAILURE = 5,    /* failure, or a certificate that does not hold: the piece is kept  sub = 0 */
+    QPN_SUBSET_EMPTY = 6       /* P1 is empty, certified by the Farkas vector                      sub = 1 */
+};
+int qpn_issubset_pairs(qpn_ctx *ctx, int32_t d, int32_t B1, int32_t r1, const double *A1, const double *l1, const double *u1,
+                       int32_t B2, int32_t r2, const double *A2, const double *l2, const double *u2, int32_t pairs, const int32_t *pi,
+                       const int32_t *pj, double tol, const qpn_lp_opts *opts, uint8_t *sub, int32_t *how, int32_t *bound, double *val,
+                       int32_t *lps, int32_t *iters, int mem);
+
 #ifdef __cplusplus
 }
 #endif

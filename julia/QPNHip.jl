@@ -338,6 +338,37 @@ function solve_lps(A::Array{Float64,3}, l::Matrix{Float64}, u::Matrix{Float64}, 
     (status, x, obj, lam, ray, iters)
 end
 
+"""
+    issubset_pairs(A1, l1, u1, A2, l2, u2, pi, pj; tol=1e-6, max_iters=0) -> (sub, how, bound, val, lps, iters)
+
+qpn_issubset_pairs: `issubset(P1, P2)` (src/sets.jl:376-407) for pairs of pieces, one job per pair: first piece pi[q] of
+A1 [r1, d, B1], l1, u1 [r1, B1] against second piece pj[q] of A2 [r2, d, B2], l2, u2 [r2, B2] (pi, pj are 1-based here).  The crash
+and phase 1 over P1 run once, then the finite bounds of P2 are tried one after the other until one refutes.  sub[q] = 1 for how = 0
+(holds) and 6 (P1 empty); how 1: refuted by the current vertex, 2: by a certified optimum, 3: a bound's objective is unbounded,
+4: iteration limit, 5: failure.  bound: 2 i + side (0-based row i of P2, side 0 = lower, 1 = upper) of the bound that decided, -1
+without one; val: the value that decided; lps: solves started; iters: all their steps.
+"""
+function issubset_pairs(A1::Array{Float64,3}, l1::Matrix{Float64}, u1::Matrix{Float64}, A2::Array{Float64,3}, l2::Matrix{Float64},
+                        u2::Matrix{Float64}, pi::Vector{<:Integer}, pj::Vector{<:Integer}; tol::Float64 = 1e-6, max_iters::Integer = 0)
+    r1, d, B1 = size(A1)
+    r2, d2, B2 = size(A2)
+    d2 == d || error("issubset_pairs: A1 and A2 must have the same number of columns")
+    size(l1) == (r1, B1) && size(u1) == (r1, B1) && size(l2) == (r2, B2) && size(u2) == (r2, B2) || error("issubset_pairs: inconsistent shapes")
+    pairs = length(pi)
+    length(pj) == pairs || error("issubset_pairs: pi and pj must have the same length")
+    pi0 = Int32.(pi .- 1); pj0 = Int32.(pj .- 1)
+    opts = Ref((1e-9, 1e-9, 1e-9, 1e-6, Int32(max_iters), Int32(0)))      # qpn_lp_opts
+    sub = zeros(UInt8, pairs); how = zeros(Int32, pairs); bound = zeros(Int32, pairs); val = zeros(pairs)
+    lps = zeros(Int32, pairs); iters = zeros(Int32, pairs)
+    rc = ccall((:qpn_issubset_pairs, LIB), Cint,
+               (Ptr{Cvoid}, Int32, Int32, Int32, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Int32, Int32, Ptr{Cdouble}, Ptr{Cdouble},
+                Ptr{Cdouble}, Int32, Ptr{Int32}, Ptr{Int32}, Cdouble, Ptr{Cvoid}, Ptr{UInt8}, Ptr{Int32}, Ptr{Int32}, Ptr{Cdouble},
+                Ptr{Int32}, Ptr{Int32}, Cint),
+               ctx(), d, B1, r1, A1, l1, u1, B2, r2, A2, l2, u2, pairs, pi0, pj0, tol, opts, sub, how, bound, val, lps, iters, QPN_MEM_HOST)
+    rc == 0 || error("qpn_issubset_pairs failed ($rc)")
+    (sub, how, bound, val, lps, iters)
+end
+
 function verify_nodes(nodes::Nodes, xd::Matrix{Float64}, w::VecOrMat{Float64}; tol::Float64 = 1e-4)
     solution = zeros(Int32, nodes.batch); path = zeros(Int32, nodes.batch); lambda = zeros(max(nodes.m, 1), nodes.batch)
     rc = ccall((:qpn_verify_nodes_h, LIB), Cint,

@@ -24,7 +24,7 @@ ABI_SYMBOLS = (
     "qpn_recipes_batch", "qpn_reduced_pieces", "qpn_convexity_nodes", "qpn_recipes_batch_range", "qpn_finish_pieces",
     "qpn_multiplier_vertices", "qpn_recipe_filter",
     "qpn_assemble_interior_nodes", "qpn_interior_members", "qpn_members_outside",
-    "qpn_lp_default_opts", "qpn_lp_kernel_class", "qpn_solve_lps",
+    "qpn_lp_default_opts", "qpn_lp_kernel_class", "qpn_solve_lps", "qpn_issubset_pairs",
 )
 
 MEM_HOST, MEM_DEVICE = 0, 1
@@ -62,6 +62,7 @@ class LpOpts(C.Structure):
 
 
 LP_OPTIMAL, LP_INFEASIBLE, LP_UNBOUNDED, LP_ITER_LIMIT, LP_FAILURE = 1, 2, 3, 4, 5
+SUBSET_HOLDS, SUBSET_BY_POINT, SUBSET_BY_OPTIMUM, SUBSET_UNBOUNDED, SUBSET_ITER_LIMIT, SUBSET_FAILURE, SUBSET_EMPTY = 0, 1, 2, 3, 4, 5, 6
 
 _lib = None
 
@@ -158,6 +159,8 @@ def load_library():
     lib.qpn_lp_kernel_class.argtypes = [C.c_int32, C.c_int32]
     lib.qpn_solve_lps.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, C.c_int32, vp, vp, vp, vp, C.POINTER(LpOpts),
                                   vp, vp, vp, vp, vp, vp, C.c_int]
+    lib.qpn_issubset_pairs.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, C.c_int32, C.c_int32, vp, vp, vp, C.c_int32, vp, vp,
+                                       C.c_double, C.POINTER(LpOpts), vp, vp, vp, vp, vp, vp, C.c_int]
     del dp, ip, bp
     _lib = lib
     return lib

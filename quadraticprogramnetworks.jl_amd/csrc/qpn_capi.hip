@@ -1780,6 +1780,49 @@ int qpn_solve_lps(qpn_ctx *ctx, int32_t polys, int32_t r, int32_t d, const doubl
     return st.finish();
 }
 
+int qpn_issubset_pairs(qpn_ctx *ctx, int32_t d, int32_t B1, int32_t r1, const double *A1, const double *l1, const double *u1,
+                       int32_t B2, int32_t r2, const double *A2, const double *l2, const double *u2, int32_t pairs, const int32_t *pi,
+                       const int32_t *pj, double tol, const qpn_lp_opts *opts, uint8_t *sub, int32_t *how, int32_t *bound, double *val,
+                       int32_t *lps, int32_t *iters, int mem)
+{
+    if (!ctx) return QPN_ERR_ARG;
+    if (B1 < 0 || B2 < 0 || pairs < 0 || r1 <= 0 || r2 <= 0 || d <= 0) return fail_arg(ctx, "qpn_issubset_pairs: bad sizes");
+    if (r1 > QPN_LP_MAX_R || r2 > QPN_LP_MAX_R || d > QPN_LP_MAX_D) {
+        ctx->last_error = "qpn_issubset_pairs: d <= 256, r1, r2 <= 1024 in ABI v1";
+        return QPN_ERR_SIZE;
+    }
+    Stage st(ctx, mem, "qpn_issubset_pairs");
+    if (int rc = st.check()) return rc;
+    if (pairs == 0) return QPN_OK;
+    if (B1 == 0 || B2 == 0 || !A1 || !l1 || !u1 || !A2 || !l2 || !u2 || !pi || !pj || !sub) return fail_arg(ctx, "qpn_issubset_pairs: null pointer");
+    // host index arrays are checked here; device ones by the kernel (such a pair answers QPN_SUBSET_FAILURE)
+    for (int q = 0; st.host && q < pairs; ++q)
+        if (pi[q] < 0 || pi[q] >= B1 || pj[q] < 0 || pj[q] >= B2) return fail_arg(ctx, "qpn_issubset_pairs: pi / pj out of range");
+    qpn_lp_opts o;
+    if (opts) o = *opts; else qpn_lp_default_opts(&o);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t N = (size_t)pairs;
+    SubsetArgs a{};
+    a.d = d; a.B1 = B1; a.r1 = r1; a.B2 = B2; a.r2 = r2; a.pairs = pairs; a.tol = tol;
+    a.piv_tol = o.piv_tol; a.feas_tol = o.feas_tol; a.opt_tol = o.opt_tol; a.check_tol = o.check_tol;
+    a.max_iters = o.max_iters > 0 ? o.max_iters : 50 * (r1 + d) + 100;
+    void *gws;
+    st.in(a.A1, A1, (size_t)B1 * r1 * d * 8); st.in(a.l1, l1, (size_t)B1 * r1 * 8); st.in(a.u1, u1, (size_t)B1 * r1 * 8);
+    st.in(a.A2, A2, (size_t)B2 * r2 * d * 8); st.in(a.l2, l2, (size_t)B2 * r2 * 8); st.in(a.u2, u2, (size_t)B2 * r2 * 8);
+    st.in(a.pi, pi, N * 4); st.in(a.pj, pj, N * 4);
+    st.out(a.sub, sub, N);
+    if (how || !st.host) st.out(a.how, how, N * 4);
+    if (bound || !st.host) st.out(a.bound, bound, N * 4);
+    if (val || !st.host) st.out(a.val, val, N * 8);
+    if (lps || !st.host) st.out(a.lps, lps, N * 4);
+    if (iters || !st.host) st.out(a.iters, iters, N * 4);
+    st.scratch(gws, qpn_lp_workspace_bytes(pairs, r1, d));
+    int rc = st.begin();
+    if (rc != QPN_OK) return rc;
+    HIPCHK(ctx, qpn_launch_issubset_pairs(a, gws, ctx->stream));
+    return st.finish();
+}
+
 } // extern "C"
 
 namespace {

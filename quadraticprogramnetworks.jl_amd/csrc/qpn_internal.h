@@ -294,6 +294,20 @@ struct LpArgs {
 int qpn_lp_class(int32_t r, int32_t d);        // 0 wavefront, 1 workgroup in LDS, 2 workgroup over the workspace, -1 beyond the limits
 size_t qpn_lp_workspace_bytes(int32_t jobs, int32_t r, int32_t d);
 hipError_t qpn_launch_solve_lps(const LpArgs &a, void *gws, hipStream_t s);
+// ... and the subset tests over it (qpn_issubset_pairs).  how, bound, val, lps, iters may be null.
+struct SubsetArgs {
+    int32_t d, B1, r1, B2, r2, pairs;
+    const double *A1, *l1, *u1, *A2, *l2, *u2;
+    const int32_t *pi, *pj;
+    double tol;
+    uint8_t *sub;
+    int32_t *how, *bound;
+    double *val;
+    int32_t *lps, *iters;
+    double piv_tol, feas_tol, opt_tol, check_tol;
+    int32_t max_iters;                         // resolved: > 0, per objective
+};
+hipError_t qpn_launch_issubset_pairs(const SubsetArgs &a, void *gws, hipStream_t s);   // gws: qpn_lp_workspace_bytes(pairs, r1, d)
 #define QPN_CONVEXITY_MAX_N 256
 #define QPN_CONVEXITY_MAX_M 1024
 

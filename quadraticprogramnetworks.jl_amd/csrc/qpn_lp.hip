@@ -12,6 +12,11 @@
 // Classes by the size of a job's slice (lp_slice_bytes): up to 16 KiB one wavefront per job, LP_WAVES jobs per workgroup, in
 // LDS; up to 156 KiB one workgroup per job in LDS; beyond, one workgroup per job over a slice of the context workspace, launched
 // in chunks.  Every loop is bounded: the crash by d, the simplex loop by max_iters.
+//
+// qpn_issubset_pairs runs the same set-up, loop and check (lp_setup, lp_loop, lp_point, lp_check) with one
+// team per pair P1 within P2: the crash and phase 1 over P1 once, then the finite bounds of P2 one after the other as objectives
+// from the basis the previous one left, until one refutes (subset_core; polyhedra.issubset_pairs_host is its twin).  The slice is
+// that of an LP over P1; the row of P2 is read in place into its cost vector.
 #include <climits>
 
 #include "qpn_internal.h"
@@ -113,23 +118,26 @@ struct LpSlice {
     }
 };
 
-// The solve of job t over polyhedron b.  Leaves x in S.xf, the multipliers / Farkas vector in S.lam, the ray in S.ray (zeroed by
-// the caller).  -> status; *iters, *objv.
-template <int T>
-__device__ int lp_core(const LpArgs &a, const LpSlice &S, int t, int b, int orow, int tid, int *iters_out, double *obj_out)
+// One polyhedron {x : lb <= Ab x <= ub} and the tolerances of its solves
+struct LpProb {
+    int r, d;
+    const double *Ab, *lb, *ub;
+    double piv_tol, feas_tol, opt_tol, ct;
+    int max_iters;
+};
+
+// Steps 1-4 with the objective in S.cv: scaling, the dictionary, the crash, the nonbasic values.  -> QPN_LP_INFEASIBLE when an
+// all-zero row outside its bounds settles the job (its unit Farkas vector in S.lam), 0 otherwise.
+template <int T> __device__ int lp_setup(const LpProb &P, const LpSlice &S, int tid)
 {
-    const int r = a.r, d = a.d, ld = lp_ld(r);
-    const double *Ab = a.A + (size_t)b * r * d, *lb = a.l + (size_t)b * r, *ub = a.u + (size_t)b * r;
-    const double piv_tol = a.piv_tol, feas_tol = a.feas_tol, opt_tol = a.opt_tol, ct = a.check_tol;
+    const int r = P.r, d = P.d, ld = lp_ld(r);
+    const double *Ab = P.Ab, *lb = P.lb, *ub = P.ub;
+    const double piv_tol = P.piv_tol;
     double *Tm = S.Tm, *red = S.red;
     int *rb = S.rb, *cn = S.cn;
-    *iters_out = 0; *obj_out = 0.0;
 
     // 1. row scaling, 2. the dictionary
-    for (int j = tid; j < d; j += T) {
-        const double c = a.cost ? a.cost[(size_t)t * d + j] : (double)a.obj_sign[t] * Ab[(size_t)j * r + orow];
-        S.cv[j] = c; Tm[(size_t)j * ld + r] = c; cn[j] = j; S.xn[j] = 0.0;
-    }
+    for (int j = tid; j < d; j += T) { Tm[(size_t)j * ld + r] = S.cv[j]; cn[j] = j; S.xn[j] = 0.0; }
     int zbad = INT_MAX;
     for (int i = tid; i < r; i += T) {
         double m = 0.0;
@@ -176,7 +184,17 @@ __device__ int lp_core(const LpArgs &a, const LpSlice &S, int t, int b, int orow
         S.xn[j] = v;
     }
     team_sync<T>();
+    return 0;
+}
 
+// Steps 5-8: the simplex loop from the slice's dictionary, with its own step and degeneracy counters.  -> status; the steps,
+// and the last entering column and its direction (the ray of an UNBOUNDED end).
+template <int T> __device__ int lp_loop(const LpProb &P, const LpSlice &S, int tid, int *iters_out, int *e_out, double *dirn_out)
+{
+    const int r = P.r, d = P.d, ld = lp_ld(r);
+    const double piv_tol = P.piv_tol, feas_tol = P.feas_tol, opt_tol = P.opt_tol;
+    double *Tm = S.Tm, *red = S.red;
+    int *rb = S.rb, *cn = S.cn;
     int status = QPN_LP_FAILURE, iters = 0, degen = 0, e = -1;
     double dirn = 0.0;
     for (;;) {
@@ -262,7 +280,7 @@ __device__ int lp_core(const LpArgs &a, const LpSlice &S, int t, int b, int orow
         int win = team_min_int<T>(w, red, tid);
         if (tflip <= thr && eid < win) win = eid;
         if (win == INT_MAX) { status = QPN_LP_FAILURE; break; }   // (not-a-number data: no candidate compares)
-        if (iters >= a.max_iters) { status = QPN_LP_ITER_LIMIT; break; }   // a step is due and none is left
+        if (iters >= P.max_iters) { status = QPN_LP_ITER_LIMIT; break; }   // a step is due and none is left
         ++iters;
         degen = tmin == 0.0 ? degen + 1 : 0;
         if (win == eid) {                                 // a flip to the opposite bound: no pivot
@@ -279,15 +297,31 @@ __device__ int lp_core(const LpArgs &a, const LpSlice &S, int t, int b, int orow
             team_sync<T>();
         }
     }
+    *iters_out = iters; *e_out = e; *dirn_out = dirn;
+    return status;
+}
 
-    // 9. the answer on the unscaled data, and the check of what it claims
-    for (int j = tid; j < d; j += T) if (cn[j] < d) S.xf[cn[j]] = S.xn[j];
-    for (int i = tid; i < r; i += T) if (rb[i] < d) S.xf[rb[i]] = S.xb[i];
+// 9. the answer on the unscaled data: x into S.xf.  -> c'x
+template <int T> __device__ double lp_point(const LpProb &P, const LpSlice &S, int tid)
+{
+    const int r = P.r, d = P.d;
+    for (int j = tid; j < d; j += T) if (S.cn[j] < d) S.xf[S.cn[j]] = S.xn[j];
+    for (int i = tid; i < r; i += T) if (S.rb[i] < d) S.xf[S.rb[i]] = S.xb[i];
     team_sync<T>();
     double obj = 0.0;
     for (int k = 0; k < d; ++k) obj = obj + S.cv[k] * S.xf[k];
-    *iters_out = iters; *obj_out = obj;
-    if (status == QPN_LP_ITER_LIMIT || status == QPN_LP_FAILURE) return status;
+    return obj;
+}
+
+// ... and the check of what an OPTIMAL / UNBOUNDED / INFEASIBLE end claims: the multipliers / Farkas vector into S.lam, the ray
+// into S.ray (both zeroed by the caller).  -> status, or QPN_LP_FAILURE when the certificate does not hold.
+template <int T> __device__ int lp_check(const LpProb &P, const LpSlice &S, int status, int e, double dirn, int tid)
+{
+    const int r = P.r, d = P.d, ld = lp_ld(r);
+    const double *Ab = P.Ab, *lb = P.lb, *ub = P.ub;
+    const double ct = P.ct;
+    double *Tm = S.Tm, *red = S.red;
+    int *rb = S.rb, *cn = S.cn;
     int ok = 1;
     double *s = S.xb;                                      // (the basic values are not needed any more)
     for (int i = tid; i < r; i += T) {
@@ -354,6 +388,26 @@ __device__ int lp_core(const LpArgs &a, const LpSlice &S, int t, int b, int orow
     return team_min_int<T>(ok, red, tid) ? status : QPN_LP_FAILURE;
 }
 
+// The solve of job t over polyhedron b.  Leaves x in S.xf, the multipliers / Farkas vector in S.lam, the ray in S.ray (zeroed by
+// the caller).  -> status; *iters, *objv.
+template <int T>
+__device__ int lp_core(const LpArgs &a, const LpSlice &S, int t, int b, int orow, int tid, int *iters_out, double *obj_out)
+{
+    const int r = a.r, d = a.d;
+    const LpProb P{r, d, a.A + (size_t)b * r * d, a.l + (size_t)b * r, a.u + (size_t)b * r, a.piv_tol, a.feas_tol, a.opt_tol, a.check_tol,
+                   a.max_iters};
+    *iters_out = 0; *obj_out = 0.0;
+    for (int j = tid; j < d; j += T)
+        S.cv[j] = a.cost ? a.cost[(size_t)t * d + j] : (double)a.obj_sign[t] * P.Ab[(size_t)j * r + orow];
+    if (lp_setup<T>(P, S, tid)) return QPN_LP_INFEASIBLE;
+    int e;
+    double dirn;
+    const int status = lp_loop<T>(P, S, tid, iters_out, &e, &dirn);
+    *obj_out = lp_point<T>(P, S, tid);
+    if (status == QPN_LP_ITER_LIMIT || status == QPN_LP_FAILURE) return status;
+    return lp_check<T>(P, S, status, e, dirn, tid);
+}
+
 template <int T> __device__ void lp_job(const LpArgs &a, int t, double *base, int tid)
 {
     const int r = a.r, d = a.d;
@@ -392,6 +446,133 @@ template <bool LDS> __global__ __launch_bounds__(LP_GROUP) void lp_group_kernel(
     extern __shared__ __attribute__((aligned(16))) unsigned char lp_lds[];
     unsigned char *base = LDS ? lp_lds : gws + (size_t)blockIdx.x * slice;
     lp_job<LP_GROUP>(a, first + (int)blockIdx.x, reinterpret_cast<double *>(base), threadIdx.x);
+}
+
+// ---- subset tests: one team per pair ------------------------------------------------------------------------------------------
+struct SubsetOut { int how, bound, lps, iters; double val; };
+
+// P1 = first piece b1, P2 = second piece b2 (both in range).  Every value a branch depends on is the same in all threads of
+// the team (team reductions, or sums every thread runs over the slice), so a whole team leaves together.
+template <int T> __device__ void subset_core(const SubsetArgs &a, const LpSlice &S, int b1, int b2, int tid, SubsetOut &o)
+{
+    const int r = a.r1, d = a.d, r2 = a.r2, ld = lp_ld(r);
+    const LpProb P{r, d, a.A1 + (size_t)b1 * r * d, a.l1 + (size_t)b1 * r, a.u1 + (size_t)b1 * r, a.piv_tol, a.feas_tol, a.opt_tol,
+                   a.check_tol, a.max_iters};
+    const double *A2 = a.A2 + (size_t)b2 * r2 * d, *l2 = a.l2 + (size_t)b2 * r2, *u2 = a.u2 + (size_t)b2 * r2;
+    const double tol = a.tol;
+    for (int j = tid; j < d; j += T) { S.cv[j] = 0.0; S.xf[j] = 0.0; S.ray[j] = 0.0; }
+    for (int i = tid; i < r; i += T) S.lam[i] = 0.0;
+    team_sync<T>();
+    // (a) the feasibility solve
+    o.lps = 1;
+    if (lp_setup<T>(P, S, tid)) { o.how = QPN_SUBSET_EMPTY; return; }
+    int e, it;
+    double dirn;
+    int status = lp_loop<T>(P, S, tid, &it, &e, &dirn);
+    lp_point<T>(P, S, tid);
+    o.iters = it;
+    if (status == QPN_LP_INFEASIBLE) {
+        o.how = lp_check<T>(P, S, status, e, dirn, tid) == QPN_LP_INFEASIBLE ? QPN_SUBSET_EMPTY : QPN_SUBSET_FAILURE;
+        return;
+    }
+    if (status != QPN_LP_OPTIMAL) { o.how = status == QPN_LP_ITER_LIMIT ? QPN_SUBSET_ITER_LIMIT : QPN_SUBSET_FAILURE; return; }
+    // (b) the bounds of P2 in order
+    for (int i = 0; i < r2; ++i) {
+        const double l2i = l2[i], u2i = u2[i];
+        const bool fl = fabs(l2i) < QINF, fu = fabs(u2i) < QINF;
+        if (!fl && !fu) continue;
+        team_sync<T>();
+        for (int j = tid; j < d; j += T) S.cv[j] = A2[(size_t)j * r2 + i];
+        team_sync<T>();
+        // (c) rows of P1 equal to this one: the tightest of their bounds
+        double lo = -QINF, hi = QINF;
+        for (int k = tid; k < r; k += T) {
+            bool same = true;
+            for (int c = 0; c < d && same; ++c) same = P.Ab[(size_t)c * r + k] == S.cv[c];
+            if (same) { lo = fmax(lo, P.lb[k]); hi = fmin(hi, P.ub[k]); }
+        }
+        const double lo1 = team_max<T>(lo, S.red, tid);
+        const double hi1 = team_min<T>(hi, S.red, tid);
+        for (int side = 0; side < 2; ++side) {
+            double beta;
+            if (side == 0) {
+                if (!fl || lo1 >= l2i - tol) continue;
+                beta = l2i;
+            } else {
+                if (!fu || hi1 <= u2i + tol) continue;
+                beta = -u2i;
+                team_sync<T>();
+                for (int j = tid; j < d; j += T) S.cv[j] = -A2[(size_t)j * r2 + i];
+                team_sync<T>();
+            }
+            o.bound = 2 * i + side;
+            // (d) the point the previous solve ended at
+            double v = 0.0;
+            for (int k = 0; k < d; ++k) v = v + S.cv[k] * S.xf[k];
+            if (v < beta - tol) { o.how = QPN_SUBSET_BY_POINT; o.val = v; return; }
+            // (e) the cost row of c in the current dictionary
+            for (int j = tid; j < d; j += T) {
+                const double *col = S.Tm + (size_t)j * ld;
+                double acc = 0.0;
+                for (int k = 0; k < r; ++k) {
+                    const int id = S.rb[k];
+                    if (id < d) acc = acc + S.cv[id] * col[k];
+                }
+                if (S.cn[j] < d) acc = acc + S.cv[S.cn[j]];
+                S.Tm[(size_t)j * ld + r] = acc;
+            }
+            for (int j = tid; j < d; j += T) S.ray[j] = 0.0;
+            for (int k = tid; k < r; k += T) S.lam[k] = 0.0;
+            team_sync<T>();
+            // (f) solve and decide
+            ++o.lps;
+            status = lp_loop<T>(P, S, tid, &it, &e, &dirn);
+            const double obj = lp_point<T>(P, S, tid);
+            o.iters += it;
+            if (status == QPN_LP_ITER_LIMIT) { o.how = QPN_SUBSET_ITER_LIMIT; return; }
+            if (status == QPN_LP_FAILURE || status == QPN_LP_INFEASIBLE) { o.how = QPN_SUBSET_FAILURE; return; }
+            if (lp_check<T>(P, S, status, e, dirn, tid) == QPN_LP_FAILURE) { o.how = QPN_SUBSET_FAILURE; return; }
+            if (status == QPN_LP_UNBOUNDED) { o.how = QPN_SUBSET_UNBOUNDED; return; }
+            if (obj < beta - tol) { o.how = QPN_SUBSET_BY_OPTIMUM; o.val = obj; return; }
+            o.bound = -1;
+        }
+    }
+    o.how = QPN_SUBSET_HOLDS;                             // (g)
+}
+
+template <int T> __device__ void subset_job(const SubsetArgs &a, int q, double *base, int tid)
+{
+    const LpSlice S(base, a.r1, a.d);
+    if (tid < 8) S.red[tid] = 0.0;
+    team_sync<T>();
+    // an index out of range (device arrays are not read by the host): the pair fails and reads nothing
+    const int b1 = a.pi[q], b2 = a.pj[q];
+    SubsetOut o{QPN_SUBSET_FAILURE, -1, 0, 0, 0.0};
+    if (b1 >= 0 && b1 < a.B1 && b2 >= 0 && b2 < a.B2) subset_core<T>(a, S, b1, b2, tid, o);
+    if (tid == 0) {
+        a.sub[q] = o.how == QPN_SUBSET_HOLDS || o.how == QPN_SUBSET_EMPTY ? 1 : 0;
+        if (a.how) a.how[q] = o.how;
+        if (a.bound) a.bound[q] = o.bound;
+        if (a.val) a.val[q] = o.val;
+        if (a.lps) a.lps[q] = o.lps;
+        if (a.iters) a.iters[q] = o.iters;
+    }
+}
+
+__global__ __launch_bounds__(64 * LP_WAVES) void subset_wave_kernel(SubsetArgs a, size_t slice)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char lp_lds[];
+    const int w = threadIdx.x / 64;
+    const long long q = (long long)blockIdx.x * LP_WAVES + w;
+    if (q >= a.pairs) return;                             // a whole wavefront leaves: the others never wait for it
+    subset_job<64>(a, (int)q, reinterpret_cast<double *>(lp_lds + (size_t)w * slice), threadIdx.x % 64);
+}
+
+template <bool LDS> __global__ __launch_bounds__(LP_GROUP) void subset_group_kernel(SubsetArgs a, int32_t first, unsigned char *gws, size_t slice)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char lp_lds[];
+    unsigned char *base = LDS ? lp_lds : gws + (size_t)blockIdx.x * slice;
+    subset_job<LP_GROUP>(a, first + (int)blockIdx.x, reinterpret_cast<double *>(base), threadIdx.x);
 }
 
 int32_t lp_chunk(int32_t jobs, int32_t r, int32_t d)
@@ -439,6 +620,35 @@ hipError_t qpn_launch_solve_lps(const LpArgs &a, void *gws, hipStream_t s)
     for (int32_t first = 0; first < a.jobs; first += chunk) {
         const int32_t count = a.jobs - first < chunk ? a.jobs - first : chunk;
         hipLaunchKernelGGL(lp_group_kernel<false>, dim3((unsigned)count), dim3(LP_GROUP), 0, s, a, first, static_cast<unsigned char *>(gws),
+                           slice);
+        if (const hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+hipError_t qpn_launch_issubset_pairs(const SubsetArgs &a, void *gws, hipStream_t s)
+{
+    if (a.pairs <= 0) return hipSuccess;
+    const int cls = qpn_lp_class(a.r1, a.d);
+    const size_t slice = lp_slice_bytes(a.r1, a.d);
+    if (cls == 0) {
+        static QpnLdsLimits lds_limits;
+        if (const hipError_t e = lds_limits.raise({{subset_wave_kernel, (int)(LP_WAVE_SLICE_MAX * LP_WAVES)}}); e != hipSuccess) return e;
+        const unsigned grid = (unsigned)((a.pairs + LP_WAVES - 1) / LP_WAVES);
+        hipLaunchKernelGGL(subset_wave_kernel, dim3(grid), dim3(64 * LP_WAVES), slice * LP_WAVES, s, a, slice);
+        return hipGetLastError();
+    }
+    if (cls == 1) {
+        static QpnLdsLimits lds_limits;
+        if (const hipError_t e = lds_limits.raise({{subset_group_kernel<true>, (int)LP_GROUP_SLICE_MAX}}); e != hipSuccess) return e;
+        hipLaunchKernelGGL(subset_group_kernel<true>, dim3((unsigned)a.pairs), dim3(LP_GROUP), slice, s, a, 0,
+                           static_cast<unsigned char *>(nullptr), slice);
+        return hipGetLastError();
+    }
+    const int32_t chunk = lp_chunk(a.pairs, a.r1, a.d);
+    for (int32_t first = 0; first < a.pairs; first += chunk) {
+        const int32_t count = a.pairs - first < chunk ? a.pairs - first : chunk;
+        hipLaunchKernelGGL(subset_group_kernel<false>, dim3((unsigned)count), dim3(LP_GROUP), 0, s, a, first, static_cast<unsigned char *>(gws),
                            slice);
         if (const hipError_t e = hipGetLastError(); e != hipSuccess) return e;
     }

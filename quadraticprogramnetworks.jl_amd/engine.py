@@ -680,6 +680,33 @@ class Engine:
                    _ptr(out["ray"]), _ptr(out["iters"]), self._mem(dev))
         return out
 
+    def issubset_pairs(self, A1c, l1, u1, A2c, l2, u2, pi, pj, tol=1e-6, opts=None):
+        """Subset tests P1 ⊆ P2, one job per pair (qpn_issubset_pairs; polyhedra.issubset_pairs_host is its numpy twin, bit for
+        bit): first pieces A1c [B1, d, r1] (ABI layout, ``colmajor(A)``), l1, u1 [B1, r1]; second pieces A2c [B2, d, r2], l2, u2
+        [B2, r2]; pair q asks pi[q] against pj[q] (int32).  opts: LpOpts, a dict of its fields, or None.
+        Returns dict(sub [pairs] uint8, how [pairs] int32 (_lib.SUBSET_*), bound [pairs] int32, val [pairs], lps, iters [pairs] int32)."""
+        dev, A1c, l1, u1, A2c, l2, u2, pi, pj = self._stage("issubset_pairs", "A1c l1 u1 A2c l2 u2 pi pj", f64=(A1c, l1, u1, A2c, l2, u2),
+                                                            i32=(pi, pj))
+        if A1c.ndim != 3 or A2c.ndim != 3 or pi.ndim != 1:
+            raise QpnError("issubset_pairs: inconsistent shapes")
+        B1, d, r1 = (int(v) for v in A1c.shape)
+        B2, d2, r2 = (int(v) for v in A2c.shape)
+        pairs = int(pi.shape[0])
+        if d2 != d or tuple(l1.shape) != (B1, r1) or tuple(u1.shape) != (B1, r1) or tuple(l2.shape) != (B2, r2) or tuple(u2.shape) != (B2, r2) or (
+                tuple(pj.shape) != (pairs,)):
+            raise QpnError("issubset_pairs: inconsistent shapes")
+        if isinstance(opts, dict):
+            o = self.default_lp_opts()
+            for k, v in opts.items():
+                setattr(o, k, v)
+            opts = o
+        out = dict(sub=self._alloc(dev, (pairs,), np.uint8), how=self._alloc(dev, (pairs,), np.int32), bound=self._alloc(dev, (pairs,), np.int32),
+                   val=self._alloc(dev, (pairs,), np.float64), lps=self._alloc(dev, (pairs,), np.int32), iters=self._alloc(dev, (pairs,), np.int32))
+        self._call("qpn_issubset_pairs", d, B1, r1, _ptr(A1c), _ptr(l1), _ptr(u1), B2, r2, _ptr(A2c), _ptr(l2), _ptr(u2), pairs, _ptr(pi),
+                   _ptr(pj), float(tol), C.byref(opts) if opts is not None else None, _ptr(out["sub"]), _ptr(out["how"]), _ptr(out["bound"]),
+                   _ptr(out["val"]), _ptr(out["lps"]), _ptr(out["iters"]), self._mem(dev))
+        return out
+
 
 class Nodes:
     """Resident node records (``qpn_nodes_upload``): the records of a level's single-node pools live in HBM owned by the

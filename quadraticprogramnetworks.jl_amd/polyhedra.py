@@ -18,6 +18,14 @@ remove_subsets.  The reference's own decision rule -- the slack-minimising LP of
 tolerance bands and open bounds (rl / ru, :68-92, :354-356) -- is exemplar_slack_batch / isempty_slack_batch, and
 implicit_bounds_batch is `implicit_bounds` (:660-713): all of them LPs over the same rows, i.e. node-AVIs with Q = 0, batched
 through the same node solver (the general kernels take them: an LP's H block has no pivots for the matrix-core path).
+
+On an engine with `solve_lps` (qpn_solve_lps, a batched simplex with the outcomes OPTIMAL / INFEASIBLE / UNBOUNDED and a certificate
+for each) the LPs of exemplar_slack_batch and implicit_bounds_batch are jobs over shared polyhedra, and on one with
+`issubset_pairs` (qpn_issubset_pairs) a subset question P1 ⊆ P2 is ONE job: the crash and phase 1 over P1 once, then the finite
+bounds of P2 as objectives one after the other, from the basis the previous one left, until one refutes; issubset_batch packs the
+distinct polyhedra by shape and builds no query.  solve_lps_host and issubset_pairs_host are the numpy twins of the two entries:
+the normative statements of their methods, to which the kernels are bit-equal.  An engine without the methods (the oracle engine)
+keeps the node-AVI route.
 """
 from __future__ import annotations
 
@@ -79,7 +87,14 @@ def issubset_batch(pairs, engine, tol=1e-6):
     minimum falls below the bound by more than `tol` or the LP is unbounded.  Equivalently: P1 ⊆ P2 iff, for every
     finite bound of P2, P1 intersected with the closed half-space beyond that bound (moved out by `tol`) is EMPTY --
     one emptiness query per bound, all pairs and bounds in one `isempty_batch` call.  An empty P1 is a subset of
-    anything (the reference's LP is infeasible there and it answers false; noted, not mirrored)."""
+    anything (the reference's LP is infeasible there and it answers false; noted, not mirrored).
+
+    An engine with `issubset_pairs` (qpn_issubset_pairs) takes a pair as ONE job instead: the distinct polyhedra are packed by
+    shape, a call per pair of shapes, and no query is built (_issubset_pairs_route).  It compares the minimum with the bound
+    where the queries ask for emptiness beyond it: the verdicts can differ only where the minimum lies within rounding of
+    l2 - tol, and either verdict is sound there."""
+    if len(pairs) and _has_subset_pairs(engine):
+        return _issubset_pairs_route(pairs, engine, tol)
     queries, owner = [], []
     keyed = {}                                   # per polyhedron (the same object shows up in many pairs): its rows as hashable keys
 
@@ -135,25 +150,103 @@ def remove_subsets(polys, engine, tol=1e-6):
     return [p for p, s in zip(polys, is_subset) if not s], is_subset
 
 
+def _has_subset_pairs(engine):
+    return callable(getattr(engine, "issubset_pairs", None))
+
+
+def _subset_packs(pairs):
+    """The calls of issubset_pairs that answer `pairs`: the distinct polyhedra (by id: the same object shows up in many pairs) are
+    packed by shape (rows, columns), first and second pieces apart, and every pair of shapes is one call with its index arrays
+    into the two packs.  -> ([(positions in pairs, (A1c, l1, u1, A2c, l2, u2, pi, pj))], positions beyond the kernel's limits)."""
+    from .engine import colmajor
+    trips = {}
+
+    def trip_of(P):
+        got = trips.get(id(P))
+        if got is None:
+            A, l, u = (P.vectorize() if hasattr(P, "vectorize") else P)
+            A = np.atleast_2d(np.asarray(A, dtype=np.float64))
+            got = trips[id(P)] = (A, np.asarray(l, dtype=np.float64).reshape(A.shape[0]), np.asarray(u, dtype=np.float64).reshape(A.shape[0]), P)
+        return got
+
+    groups, beyond = {}, []
+    for k, (P1, P2) in enumerate(pairs):
+        A1, A2 = trip_of(P1)[0], trip_of(P2)[0]
+        if A1.shape[1] != A2.shape[1]:
+            raise ValueError(f"issubset_batch: pair {k} has polyhedra in {A1.shape[1]} and {A2.shape[1]} variables")
+        if max(A1.shape[0], A2.shape[0]) > LP_MAX_R or A1.shape[1] > LP_MAX_D or min(A1.shape + A2.shape) < 1:
+            beyond.append(k)
+        else:
+            groups.setdefault((A1.shape, A2.shape), []).append(k)
+    calls = []
+    for ((r1, d), (r2, _)), ks in sorted(groups.items()):
+        packs = ({}, {})                                     # id -> position, first and second pieces
+        idx = np.empty((2, len(ks)), np.int32)
+        for t, k in enumerate(ks):
+            for side in (0, 1):
+                idx[side, t] = packs[side].setdefault(id(pairs[k][side]), len(packs[side]))
+        arrs = []
+        for side, r in ((0, r1), (1, r2)):
+            members = [trips[i] for i in packs[side]]        # (insertion order = position)
+            arrs += [colmajor(np.stack([m[0] for m in members]).reshape(len(members), r, d)),
+                     np.stack([m[1] for m in members]), np.stack([m[2] for m in members])]
+        calls.append((ks, tuple(arrs) + (idx[0].copy(), idx[1].copy())))
+    return calls, beyond
+
+
+def _issubset_pairs_route(pairs, engine, tol):
+    """issubset_batch on an engine with `issubset_pairs`: one call per pair of shapes (_subset_packs), `sub` is the answer.  A
+    shape beyond the kernel's limits keeps the route of the emptiness queries."""
+    calls, beyond = _subset_packs(pairs)
+    out = np.ones(len(pairs), bool)
+    for ks, args in calls:
+        out[ks] = _to_host(engine.issubset_pairs(*args, tol=tol)["sub"]).astype(bool)
+    if beyond:
+        out[beyond] = issubset_batch([pairs[k] for k in beyond], _WithoutSubsetPairs(engine), tol=tol)
+    return out
+
+
+class _WithoutSubsetPairs:
+    """The engine without issubset_pairs: issubset_batch builds its emptiness queries."""
+
+    def __init__(self, eng):
+        self._eng = eng
+
+    def __getattr__(self, name):
+        if name == "issubset_pairs":
+            raise AttributeError(name)
+        return getattr(self._eng, name)
+
+
 LP_CHUNK_BYTES = 1 << 30          # padded input of one batched LP call (host arrays; the device copy is as large again)
 
 
 def issubset_batch_chunked(pairs, engine, tol=1e-6, chunk_bytes=None):
     """issubset_batch with the batch cut into calls whose padded host arrays stay below chunk_bytes (a level of a large net
-    asks millions of subset questions; one call for all of them would need their padded copies all at once)."""
+    asks millions of subset questions; one call for all of them would need their padded copies all at once).  On an engine with
+    `issubset_pairs` a call's arrays are the packs of its distinct polyhedra and two indices per pair: those bytes are counted."""
     chunk_bytes = chunk_bytes or LP_CHUNK_BYTES
     out = np.ones(len(pairs), bool)
+    packed = _has_subset_pairs(engine)                       # that route uploads every distinct polyhedron of a call once
     start = 0
     while start < len(pairs):
-        cost, stop = 0, start
+        cost, stop, seen = 0, start, set()
         while stop < len(pairs):
             (A1, l1, _), (A2, l2, u2) = [(_trip(P)) for P in pairs[stop]]
             rows1, d = np.atleast_2d(A1).shape
-            nq = int(np.isfinite(l2).sum() + np.isfinite(u2).sum())
-            c = nq * ((rows1 + 1) * d + d * d + 4 * (rows1 + 1 + d)) * 8
+            if packed:
+                c = 8                                        # its two indices; a polyhedron counts where it first shows up
+                for side, (P, A) in enumerate(zip(pairs[stop], (A1, A2))):
+                    if (side, id(P)) not in seen:
+                        c += (np.size(A) + 2 * np.atleast_2d(A).shape[0]) * 8
+            else:
+                nq = int(np.isfinite(l2).sum() + np.isfinite(u2).sum())
+                c = nq * ((rows1 + 1) * d + d * d + 4 * (rows1 + 1 + d)) * 8
             if stop > start and cost + c > chunk_bytes:
                 break
             cost += c; stop += 1
+            if packed:
+                seen.update((side, id(P)) for side, P in enumerate(pairs[stop - 1]))
         out[start:stop] = issubset_batch(pairs[start:stop], engine, tol=tol)
         start = stop
     return out
@@ -743,20 +836,30 @@ def _lp_pivot(T, i, j):
     T[i, :] = new
 
 
-def _lp_one(A, l, u, c, o):
-    """One LP  min c'x  s.t.  l <= A x <= u  (A [r, d] math layout) by the method of qpn_solve_lps (include/qpn_hip.h states it).
-    -> (status, x [d], obj, lambda [r], ray [d], iters)."""
+class _LpState:
+    """What a solve leaves for the next one over the same polyhedron: the dictionary T [r + 1, d] (cost row last), the ids of the
+    basic (rb) and nonbasic (cn) variables, the nonbasic values xn; and what the last loop left for the check (xb, g, dj, e, dirn, a)."""
+
+
+def _lp_setup(A, l, u, c, o):
+    """Steps 1-4 of qpn_solve_lps: scaling, the dictionary, the crash, the nonbasic values.  -> _LpState; S.zbad is the all-zero row
+    outside its bounds that settles the job (its unit Farkas vector in S.zlam), or None."""
     r, d = A.shape
-    piv_tol, feas_tol, opt_tol, ct = o["piv_tol"], o["feas_tol"], o["opt_tol"], o["check_tol"]
-    max_iters = o["max_iters"] if o["max_iters"] > 0 else 50 * (r + d) + 100
-    x = np.zeros(d); lam = np.zeros(r); ray = np.zeros(d)
+    S = _LpState()
+    S.A, S.l, S.u, S.r, S.d, S.o = A, l, u, r, d, o
+    S.max_iters = o["max_iters"] if o["max_iters"] > 0 else 50 * (r + d) + 100
+    S.zbad, S.iters, S.e, S.dirn, S.a, S.g, S.dj, S.xb = None, 0, -1, 0.0, None, None, None, np.zeros(r)
+    piv_tol = o["piv_tol"]
     with np.errstate(all="ignore"):
         # 1. row scaling; an all-zero row outside its bounds settles the job
         amax = np.max(np.abs(A), axis=1)
+        S.amax = amax
         for i in range(r):
             if amax[i] == 0.0 and (u[i] < 0.0 or l[i] > 0.0):
-                lam[i] = 1.0 if u[i] < 0.0 else -1.0
-                return LP_INFEASIBLE, x, 0.0, lam, ray, 0
+                S.zbad = i
+                S.zlam = np.zeros(r)
+                S.zlam[i] = 1.0 if u[i] < 0.0 else -1.0
+                return S
         sc = np.ones(r)
         nz = amax > 0.0
         sc[nz] = 1.0 / amax[nz]
@@ -786,6 +889,17 @@ def _lp_one(A, l, u, c, o):
                     xn[j] = lo
                 elif np.isfinite(hi):
                     xn[j] = hi
+    S.sc, S.ls, S.us, S.T, S.rb, S.cn, S.xn = sc, ls, us, T, rb, cn, xn
+    return S
+
+
+def _lp_loop(S):
+    """Steps 5-8: the simplex loop from the state's dictionary, with its own step and degeneracy counters.  -> status; the
+    steps in S.iters, the basic values, violations and reduced costs of the last round in S.xb, S.g, S.dj, the last entering
+    column and direction in S.e, S.dirn, S.a."""
+    r, d, T, rb, cn, xn, ls, us = S.r, S.d, S.T, S.rb, S.cn, S.xn, S.ls, S.us
+    piv_tol, feas_tol, opt_tol, max_iters = S.o["piv_tol"], S.o["feas_tol"], S.o["opt_tol"], S.max_iters
+    with np.errstate(all="ignore"):
         status, iters, degen = LP_FAILURE, 0, 0
         e, dirn, a, g, dj = -1, 0.0, None, None, None
         while True:
@@ -849,18 +963,34 @@ def _lp_one(A, l, u, c, o):
                 _lp_pivot(T, i, e)                      # 8.
                 rb[i], cn[e] = cn[e], rb[i]
                 xn[e] = tgt[i]
-        # 9. the answer on the unscaled data, and the check of what it claims
-        for j in range(d):
-            if cn[j] < d:
-                x[cn[j]] = xn[j]
-        for i in range(r):
-            if rb[i] < d:
-                x[rb[i]] = xb[i]
+    S.iters, S.e, S.dirn, S.a, S.g, S.dj, S.xb = iters, e, dirn, a, g, dj, xb
+    return status
+
+
+def _lp_point(S, c):
+    """Step 9, first half: the point the loop ended at, on the unscaled data.  -> (x [d], obj = c'x)."""
+    x = np.zeros(S.d)
+    with np.errstate(all="ignore"):
+        for j in range(S.d):
+            if S.cn[j] < S.d:
+                x[S.cn[j]] = S.xn[j]
+        for i in range(S.r):
+            if S.rb[i] < S.d:
+                x[S.rb[i]] = S.xb[i]
         obj = 0.0
-        for k in range(d):
+        for k in range(S.d):
             obj = obj + c[k] * x[k]
-        if status in (LP_ITER_LIMIT, LP_FAILURE):
-            return status, x, obj, lam, ray, iters
+    return x, obj
+
+
+def _lp_check(S, status, c, x):
+    """Step 9, second half: the check of what an OPTIMAL / UNBOUNDED / INFEASIBLE end claims, on the unscaled data at check_tol.
+    -> (ok, lambda [r], ray [d])."""
+    A, l, u, r, d, rb, cn, sc, amax = S.A, S.l, S.u, S.r, S.d, S.rb, S.cn, S.sc, S.amax
+    ct = S.o["check_tol"]
+    e, dirn, a, g, dj = S.e, S.dirn, S.a, S.g, S.dj
+    lam = np.zeros(r); ray = np.zeros(d)
+    with np.errstate(all="ignore"):
         s = np.zeros(r)
         for j in range(d):
             s = s + A[:, j] * x[j]
@@ -916,7 +1046,21 @@ def _lp_one(A, l, u, c, o):
                 elif lam[i] < 0.0:
                     bound = bound + lam[i] * l[i]
             ok = ok and bool(bound < 0.0)
-        return (status if ok else LP_FAILURE), x, obj, lam, ray, iters
+    return ok, lam, ray
+
+
+def _lp_one(A, l, u, c, o):
+    """One LP  min c'x  s.t.  l <= A x <= u  (A [r, d] math layout) by the method of qpn_solve_lps (include/qpn_hip.h states it):
+    set-up, loop, check -- the three parts issubset_pairs_host runs too.  -> (status, x [d], obj, lambda [r], ray [d], iters)."""
+    S = _lp_setup(A, l, u, c, o)
+    if S.zbad is not None:
+        return LP_INFEASIBLE, np.zeros(S.d), 0.0, S.zlam, np.zeros(S.d), 0
+    status = _lp_loop(S)
+    x, obj = _lp_point(S, c)
+    if status in (LP_ITER_LIMIT, LP_FAILURE):
+        return status, x, obj, np.zeros(S.r), np.zeros(S.d), S.iters
+    ok, lam, ray = _lp_check(S, status, c, x)
+    return (status if ok else LP_FAILURE), x, obj, lam, ray, S.iters
 
 
 def solve_lps_host(Ac, l, u, poly_of, cost=None, obj_row=None, obj_sign=None, opts=None):
@@ -944,4 +1088,126 @@ def solve_lps_host(Ac, l, u, poly_of, cost=None, obj_row=None, obj_sign=None, op
         c = np.asarray(cost[t], dtype=np.float64) if cost is not None else float(obj_sign[t]) * A[int(obj_row[t])]
         st, x, obj, lam, ray, it = _lp_one(A, l[b], u[b], c, o)
         out["status"][t] = st; out["x"][t] = x; out["obj"][t] = obj; out["lam"][t] = lam; out["ray"][t] = ray; out["iters"][t] = it
+    return out
+
+
+# ---- subset tests (qpn_issubset_pairs): one job per pair, the numpy twin ---------------------------------------------------------
+SUBSET_HOLDS, SUBSET_BY_POINT, SUBSET_BY_OPTIMUM, SUBSET_UNBOUNDED, SUBSET_ITER_LIMIT, SUBSET_FAILURE, SUBSET_EMPTY = 0, 1, 2, 3, 4, 5, 6
+
+
+def _subset_one(A1, l1, u1, A2, l2, u2, tol, o):
+    """One pair P1 ⊆ P2 by the method of qpn_issubset_pairs (A1 [r1, d], A2 [r2, d] math layout).
+    -> (how, bound, val, lps, iters)."""
+    d = A1.shape[1]
+    # (a) the feasibility solve: steps 1-8 with c = 0
+    zero = np.zeros(d)
+    S = _lp_setup(A1, l1, u1, zero, o)
+    if S.zbad is not None:
+        return SUBSET_EMPTY, -1, 0.0, 1, 0
+    status = _lp_loop(S)
+    x, _ = _lp_point(S, zero)
+    iters = S.iters
+    if status == LP_INFEASIBLE:
+        ok, _, _ = _lp_check(S, status, zero, x)
+        return (SUBSET_EMPTY if ok else SUBSET_FAILURE), -1, 0.0, 1, iters
+    if status != LP_OPTIMAL:
+        return (SUBSET_ITER_LIMIT if status == LP_ITER_LIMIT else SUBSET_FAILURE), -1, 0.0, 1, iters
+    lps = 1
+    with np.errstate(all="ignore"):
+        for i in range(A2.shape[0]):                        # (b) the bounds in order, the lower before the upper
+            fl, fu = bool(np.abs(l2[i]) < INF), bool(np.abs(u2[i]) < INF)
+            if not (fl or fu):
+                continue
+            # (c) rows of P1 equal to this one: the tightest of their bounds
+            same = np.all(A1 == A2[i][None, :], axis=1)
+            lo1, hi1 = -INF, INF
+            for k in range(A1.shape[0]):
+                if same[k]:
+                    lo1 = max(lo1, l1[k]) if l1[k] == l1[k] else lo1
+                    hi1 = min(hi1, u1[k]) if u1[k] == u1[k] else hi1
+            for side in (0, 1):
+                if side == 0:
+                    if not fl or lo1 >= l2[i] - tol:
+                        continue
+                    c, beta = A2[i].copy(), l2[i]
+                else:
+                    if not fu or hi1 <= u2[i] + tol:
+                        continue
+                    c, beta = -A2[i], -u2[i]
+                b = 2 * i + side
+                # (d) the point the previous solve ended at
+                v = 0.0
+                for k in range(d):
+                    v = v + c[k] * x[k]
+                if v < beta - tol:
+                    return SUBSET_BY_POINT, b, v, lps, iters
+                # (e) the cost row of c in the current dictionary
+                T, rb, cn = S.T, S.rb, S.cn
+                row = np.zeros(d)
+                for ii in range(S.r):
+                    if rb[ii] < d:
+                        row = row + c[rb[ii]] * T[ii, :]
+                for j in range(d):
+                    if cn[j] < d:
+                        row[j] = row[j] + c[cn[j]]
+                T[S.r] = row
+                # (f) solve and decide
+                lps += 1
+                status = _lp_loop(S)
+                x, obj = _lp_point(S, c)
+                iters += S.iters
+                if status == LP_ITER_LIMIT:
+                    return SUBSET_ITER_LIMIT, b, 0.0, lps, iters
+                if status == LP_FAILURE or status == LP_INFEASIBLE:
+                    return SUBSET_FAILURE, b, 0.0, lps, iters
+                ok, _, _ = _lp_check(S, status, c, x)
+                if not ok:
+                    return SUBSET_FAILURE, b, 0.0, lps, iters
+                if status == LP_UNBOUNDED:
+                    return SUBSET_UNBOUNDED, b, 0.0, lps, iters
+                if obj < beta - tol:
+                    return SUBSET_BY_OPTIMUM, b, obj, lps, iters
+    return SUBSET_HOLDS, -1, 0.0, lps, iters                # (g)
+
+
+def issubset_pairs_host(A1c, l1, u1, A2c, l2, u2, pi, pj, tol=1e-6, opts=None):
+    """The numpy twin of Engine.issubset_pairs (qpn_issubset_pairs), the normative statement of the method; every output of the
+    kernel is bit-equal to it.  Pair q asks whether first piece pi[q] ⊆ second piece pj[q].  A1c [B1, d, r1], A2c [B2, d, r2]
+    (ABI layout), l1, u1 [B1, r1], l2, u2 [B2, r2] (+-inf allowed).
+
+    (a) solve_lps_host's steps 1-8 on P1 with c = 0 (the crash and phase 1, once per pair); an INFEASIBLE end whose Farkas
+    certificate holds is EMPTY (sub = 1, the convention of issubset_batch), otherwise FAILURE.  (b) the rows of P2 ascending, the
+    lower bound (c = +a, beta = l2) before the upper (c = -a, beta = -u2), non-finite bounds skipped.  (c) a bound is skipped
+    when rows of P1 equal the row of P2 entry by entry (==, unscaled) and the largest of their l1 is >= l2 - tol (the smallest of
+    their u1 is <= u2 + tol).  (d) v = c'x at the point the previous solve ended at: v < beta - tol is BY_POINT.  (e) the cost
+    row of c in the current dictionary: column j, acc = 0, over the rows i ascending with an x basic acc = acc + c[rb[i]] * T[i, j],
+    then + c[cn[j]] when an x is nonbasic there.  (f) the loop with fresh step and degeneracy counters, step 9's check on P1:
+    OPTIMAL with obj < beta - tol is BY_OPTIMUM, a certified ray UNBOUNDED, a failed certificate or an INFEASIBLE end FAILURE,
+    ITER_LIMIT / FAILURE themselves.  (g) no bound left: HOLDS.
+    -> dict(sub [pairs] uint8, how [pairs] int32 (SUBSET_*), bound [pairs] int32 (2 i + side of the deciding bound, -1 without),
+    val [pairs] (the value that decided: BY_POINT, BY_OPTIMUM), lps [pairs] int32 (solves started, the feasibility solve counted),
+    iters [pairs] int32 (all steps)).  A pair whose pi / pj is out of range answers FAILURE with bound -1 and zeros (the kernel's
+    rule for device index arrays)."""
+    A1c = np.asarray(A1c, dtype=np.float64); l1 = np.asarray(l1, dtype=np.float64); u1 = np.asarray(u1, dtype=np.float64)
+    A2c = np.asarray(A2c, dtype=np.float64); l2 = np.asarray(l2, dtype=np.float64); u2 = np.asarray(u2, dtype=np.float64)
+    B1, B2 = A1c.shape[0], A2c.shape[0]
+    pi = np.asarray(pi, dtype=np.int64); pj = np.asarray(pj, dtype=np.int64)
+    n = len(pi)
+    o = dict(LP_DEFAULT_OPTS)
+    o.update(opts or {})
+    out = dict(sub=np.zeros(n, np.uint8), how=np.zeros(n, np.int32), bound=np.full(n, -1, np.int32), val=np.zeros(n),
+               lps=np.zeros(n, np.int32), iters=np.zeros(n, np.int32))
+    mats1, mats2 = {}, {}
+    for q in range(n):
+        a, b = int(pi[q]), int(pj[q])
+        if not (0 <= a < B1 and 0 <= b < B2):
+            out["how"][q] = SUBSET_FAILURE
+            continue
+        if a not in mats1:
+            mats1[a] = np.ascontiguousarray(A1c[a].T)
+        if b not in mats2:
+            mats2[b] = np.ascontiguousarray(A2c[b].T)
+        how, bound, val, lps, iters = _subset_one(mats1[a], l1[a], u1[a], mats2[b], l2[b], u2[b], float(tol), o)
+        out["how"][q] = how; out["bound"][q] = bound; out["val"][q] = val; out["lps"][q] = lps; out["iters"][q] = iters
+        out["sub"][q] = 1 if how in (SUBSET_HOLDS, SUBSET_EMPTY) else 0
     return out
