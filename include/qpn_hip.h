@@ -559,6 +559,48 @@ int qpn_issubset_pairs(qpn_ctx *ctx, int32_t d, int32_t B1, int32_t r1, const do
                        const int32_t *pj, double tol, const qpn_lp_opts *opts, uint8_t *sub, int32_t *how, int32_t *bound, double *val,
                        int32_t *lps, int32_t *iters, int mem);
 
+/* qpn_implicit_bounds: `implicit_bounds` (src/sets.jl:660-713) of `polys` polyhedra {x : l <= A x <= u} of one shape, one job per
+ * polyhedron: which rows have implicitly equal lower and upper bounds on the polyhedron, and their values.  A [polys][r][d]
+ * column-major per item, l, u [polys][r] (+-inf allowed), as for qpn_solve_lps.  Outputs (how, lo, hi, lps, iters, fail_row may be NULL):
+ *   status [polys] int32 (QPN_IB_*);  fail_row [polys] int32: the row whose solve ended the polyhedron, -1 without one;
+ *   eq [polys][r] uint8: 1 where the row is an (explicit or implicit) equality;  vals [polys][r]: its value there, +inf elsewhere;
+ *   how [polys][r] int32 (QPN_IB_HOW_*);  lo, hi [polys][r]: the extremes of a_i'x, -+inf when unbounded, NaN where no LP computed them;
+ *   lps [polys] int32: simplex solves started, the feasibility solve counted;  iters [polys] int32: all their steps.
+ * Method (polyhedra.implicit_bounds_host is its numpy twin and the normative statement; every output is bit-equal to it, by the
+ * discipline of qpn_solve_lps, whose set-up, loop and check it runs):  (0) a row with |l - u| <= tol or l == u is EXPLICIT: eq = 1,
+ * val = 0.5 (l + u); no LP takes it as objective.  Another row with l > u makes the polyhedron EMPTY before any LP (lps = 0).
+ * (a) steps 1-8 of qpn_solve_lps with c = 0: the crash and phase 1 once per
+ * polyhedron; an infeasible all-zero row, or an INFEASIBLE end whose Farkas certificate holds, is EMPTY, a certificate that fails
+ * FAILURE, ITER_LIMIT itself; the polyhedron stops there and its other rows keep eq = 0, val = +inf, UNDECIDED.  (b) witnesses: s =
+ * A x at the end point on the unscaled rows, columns ascending (acc = acc + a * x); wlo = whi = s, and after every later solve
+ * whose certificate holds wlo = s where s < wlo, whi = s where s > whi.  (c) the rows r - 1 ... 0 that are not explicit: whi - wlo
+ * > tol is BY_POINTS without an LP; otherwise the minimum, c = +a_i from the current basis (the cost row as in qpn_issubset_pairs
+ * (e), fresh step and degeneracy counters, max_iters per objective, the loop, the point, the check of step 9): a certified ray
+ * gives lo = -inf, UNBOUNDED; an optimum lo = obj, and whi - lo > tol is BY_POINTS; then the maximum with c = -a_i: hi = -obj or
+ * +inf.  eq = lo, hi finite and |lo - hi| <= tol: val = 0.5 (hi + lo), IMPLICIT; else BY_EXTREMES, or UNBOUNDED when one of the two
+ * is infinite.  ITER_LIMIT, an INFEASIBLE end or a failed certificate in one of these solves ends the polyhedron with that status
+ * and fail_row = the row.  flags & QPN_IB_ALL_EXTREMES: no BY_POINTS and no early exit after an unbounded minimum; every row that
+ * is not explicit gets both extremes and is decided by them alone.
+ * Kernel classes are those of qpn_lp_kernel_class(r, d).  1 <= d <= 256, 1 <= r <= 1024 (QPN_ERR_SIZE beyond).  polys == 0 succeeds. */
+enum {
+    QPN_IB_OK = 0,         /* every row decided */
+    QPN_IB_EMPTY = 1,      /* the polyhedron is empty, certified by the Farkas vector */
+    QPN_IB_ITER_LIMIT = 2, /* the iteration limit was reached (fail_row: the objective, -1: the feasibility solve) */
+    QPN_IB_FAILURE = 3     /* failure, or a certificate that does not hold */
+};
+enum {
+    QPN_IB_HOW_UNDECIDED = 0,   /* the polyhedron ended before the row's turn                       eq = 0 */
+    QPN_IB_HOW_EXPLICIT = 1,    /* |l - u| <= tol or l == u                                          eq = 1 */
+    QPN_IB_HOW_IMPLICIT = 2,    /* minimum and maximum are finite and within tol                    eq = 1 */
+    QPN_IB_HOW_BY_POINTS = 3,   /* two points the solves ended at differ by more than tol           eq = 0 */
+    QPN_IB_HOW_BY_EXTREMES = 4, /* minimum and maximum are finite and more than tol apart           eq = 0 */
+    QPN_IB_HOW_UNBOUNDED = 5    /* the minimum or the maximum is infinite, certified by a ray       eq = 0 */
+};
+#define QPN_IB_ALL_EXTREMES 1
+int qpn_implicit_bounds(qpn_ctx *ctx, int32_t polys, int32_t r, int32_t d, const double *A, const double *l, const double *u, double tol,
+                        int32_t flags, const qpn_lp_opts *opts, int32_t *status, int32_t *fail_row, uint8_t *eq, double *vals, int32_t *how,
+                        double *lo, double *hi, int32_t *lps, int32_t *iters, int mem);
+
 #ifdef __cplusplus
 }
 #endif

@@ -369,6 +369,52 @@ function issubset_pairs(A1::Array{Float64,3}, l1::Matrix{Float64}, u1::Matrix{Fl
     (sub, how, bound, val, lps, iters)
 end
 
+"""
+    implicit_bounds(polys; tol=1e-4, all_extremes=false, max_iters=0) -> [(implicitly_equality, vals), ...]
+
+qpn_implicit_bounds: `implicit_bounds(poly; tol)` (src/sets.jl:660-713) for a list of polyhedra `(A, l, u)` (A [r, d], l, u [r]), one
+job per polyhedron: the crash and phase 1 once, then the rows that are no explicit equalities from the last, the minimum and the
+maximum of each from the basis the previous solve left; a row whose values at two points the solves ended at differ by more than tol
+needs no LP.  Polyhedra of one shape go up in one call.  Returns per polyhedron `implicitly_equality::Vector{Bool}` and
+`vals::Vector{Float64}` (Inf where the row is no equality), as the reference does.  An empty polyhedron raises "Empty set" like the
+reference (:688-690); any other status names the polyhedron and the row whose solve ended it.
+"""
+function implicit_bounds(polys::Vector{<:Tuple{Matrix{Float64},Vector{Float64},Vector{Float64}}}; tol::Float64 = 1e-4,
+                         all_extremes::Bool = false, max_iters::Integer = 0)
+    out = Vector{Tuple{Vector{Bool},Vector{Float64}}}(undef, length(polys))
+    packs = Dict{Tuple{Int,Int},Vector{Int}}()
+    for (k, (A, l, u)) in enumerate(polys)
+        length(l) == size(A, 1) && length(u) == size(A, 1) || error("implicit_bounds: inconsistent shapes (polyhedron $k)")
+        push!(get!(packs, size(A), Int[]), k)
+    end
+    opts = Ref((1e-9, 1e-9, 1e-9, 1e-6, Int32(max_iters), Int32(0)))      # qpn_lp_opts
+    empty = Int[]
+    for ((r, d), members) in sort(collect(packs))
+        n = length(members)
+        A = Array{Float64,3}(undef, r, d, n); l = Matrix{Float64}(undef, r, n); u = Matrix{Float64}(undef, r, n)
+        for (t, k) in enumerate(members)
+            A[:, :, t] = polys[k][1]; l[:, t] = polys[k][2]; u[:, t] = polys[k][3]
+        end
+        status = zeros(Int32, n); fail_row = zeros(Int32, n); eq = zeros(UInt8, r, n); vals = zeros(r, n)
+        rc = ccall((:qpn_implicit_bounds, LIB), Cint,
+                   (Ptr{Cvoid}, Int32, Int32, Int32, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cdouble, Int32, Ptr{Cvoid}, Ptr{Int32},
+                    Ptr{Int32}, Ptr{UInt8}, Ptr{Cdouble}, Ptr{Int32}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int32}, Ptr{Int32}, Cint),
+                   ctx(), n, r, d, A, l, u, tol, Int32(all_extremes ? 1 : 0), opts, status, fail_row, eq, vals, C_NULL, C_NULL, C_NULL,
+                   C_NULL, C_NULL, QPN_MEM_HOST)
+        rc == 0 || error("qpn_implicit_bounds failed ($rc)")
+        for (t, k) in enumerate(members)
+            if status[t] == 1
+                push!(empty, k)
+            elseif status[t] != 0
+                error("implicit_bounds: status $(status[t]) on polyhedron $k, row $(fail_row[t] + 1)")
+            end
+            out[k] = (eq[:, t] .!= 0, vals[:, t])
+        end
+    end
+    isempty(empty) || error("Empty set (polyhedron $(minimum(empty)))")
+    out
+end
+
 function verify_nodes(nodes::Nodes, xd::Matrix{Float64}, w::VecOrMat{Float64}; tol::Float64 = 1e-4)
     solution = zeros(Int32, nodes.batch); path = zeros(Int32, nodes.batch); lambda = zeros(max(nodes.m, 1), nodes.batch)
     rc = ccall((:qpn_verify_nodes_h, LIB), Cint,

@@ -24,7 +24,7 @@ ABI_SYMBOLS = (
     "qpn_recipes_batch", "qpn_reduced_pieces", "qpn_convexity_nodes", "qpn_recipes_batch_range", "qpn_finish_pieces",
     "qpn_multiplier_vertices", "qpn_recipe_filter",
     "qpn_assemble_interior_nodes", "qpn_interior_members", "qpn_members_outside",
-    "qpn_lp_default_opts", "qpn_lp_kernel_class", "qpn_solve_lps", "qpn_issubset_pairs",
+    "qpn_lp_default_opts", "qpn_lp_kernel_class", "qpn_solve_lps", "qpn_issubset_pairs", "qpn_implicit_bounds",
 )
 
 MEM_HOST, MEM_DEVICE = 0, 1
@@ -63,6 +63,9 @@ class LpOpts(C.Structure):
 
 LP_OPTIMAL, LP_INFEASIBLE, LP_UNBOUNDED, LP_ITER_LIMIT, LP_FAILURE = 1, 2, 3, 4, 5
 SUBSET_HOLDS, SUBSET_BY_POINT, SUBSET_BY_OPTIMUM, SUBSET_UNBOUNDED, SUBSET_ITER_LIMIT, SUBSET_FAILURE, SUBSET_EMPTY = 0, 1, 2, 3, 4, 5, 6
+IB_OK, IB_EMPTY, IB_ITER_LIMIT, IB_FAILURE = 0, 1, 2, 3
+IB_HOW_UNDECIDED, IB_HOW_EXPLICIT, IB_HOW_IMPLICIT, IB_HOW_BY_POINTS, IB_HOW_BY_EXTREMES, IB_HOW_UNBOUNDED = 0, 1, 2, 3, 4, 5
+IB_ALL_EXTREMES = 1
 
 _lib = None
 
@@ -161,6 +164,8 @@ def load_library():
                                   vp, vp, vp, vp, vp, vp, C.c_int]
     lib.qpn_issubset_pairs.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, C.c_int32, C.c_int32, vp, vp, vp, C.c_int32, vp, vp,
                                        C.c_double, C.POINTER(LpOpts), vp, vp, vp, vp, vp, vp, C.c_int]
+    lib.qpn_implicit_bounds.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, C.c_double, C.c_int32, C.POINTER(LpOpts),
+                                        vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int]
     del dp, ip, bp
     _lib = lib
     return lib

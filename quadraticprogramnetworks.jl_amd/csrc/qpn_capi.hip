@@ -1823,6 +1823,42 @@ int qpn_issubset_pairs(qpn_ctx *ctx, int32_t d, int32_t B1, int32_t r1, const do
     return st.finish();
 }
 
+int qpn_implicit_bounds(qpn_ctx *ctx, int32_t polys, int32_t r, int32_t d, const double *A, const double *l, const double *u, double tol,
+                        int32_t flags, const qpn_lp_opts *opts, int32_t *status, int32_t *fail_row, uint8_t *eq, double *vals, int32_t *how,
+                        double *lo, double *hi, int32_t *lps, int32_t *iters, int mem)
+{
+    if (!ctx) return QPN_ERR_ARG;
+    if (polys < 0 || r <= 0 || d <= 0 || (flags & ~QPN_IB_ALL_EXTREMES)) return fail_arg(ctx, "qpn_implicit_bounds: bad sizes or flags");
+    if (r > QPN_LP_MAX_R || d > QPN_LP_MAX_D) { ctx->last_error = "qpn_implicit_bounds: d <= 256, r <= 1024 in ABI v1"; return QPN_ERR_SIZE; }
+    Stage st(ctx, mem, "qpn_implicit_bounds");
+    if (int rc = st.check()) return rc;
+    if (polys == 0) return QPN_OK;
+    if (!A || !l || !u || !status || !eq || !vals) return fail_arg(ctx, "qpn_implicit_bounds: null pointer");
+    qpn_lp_opts o;
+    if (opts) o = *opts; else qpn_lp_default_opts(&o);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t P = (size_t)polys;
+    IbArgs a{};
+    a.polys = polys; a.r = r; a.d = d; a.flags = flags; a.tol = tol;
+    a.piv_tol = o.piv_tol; a.feas_tol = o.feas_tol; a.opt_tol = o.opt_tol; a.check_tol = o.check_tol;
+    a.max_iters = o.max_iters > 0 ? o.max_iters : 50 * (r + d) + 100;
+    void *gws;
+    st.in(a.A, A, P * r * d * 8); st.in(a.l, l, P * r * 8); st.in(a.u, u, P * r * 8);
+    // (host mode: an output the caller does not want is not carved either -- the kernel skips a null one)
+    st.out(a.status, status, P * 4); st.out(a.eq, eq, P * r); st.out(a.vals, vals, P * r * 8);
+    if (fail_row || !st.host) st.out(a.fail_row, fail_row, P * 4);
+    if (how || !st.host) st.out(a.how, how, P * r * 4);
+    if (lo || !st.host) st.out(a.lo, lo, P * r * 8);
+    if (hi || !st.host) st.out(a.hi, hi, P * r * 8);
+    if (lps || !st.host) st.out(a.lps, lps, P * 4);
+    if (iters || !st.host) st.out(a.iters, iters, P * 4);
+    st.scratch(gws, qpn_lp_workspace_bytes(polys, r, d));
+    int rc = st.begin();
+    if (rc != QPN_OK) return rc;
+    HIPCHK(ctx, qpn_launch_implicit_bounds(a, gws, ctx->stream));
+    return st.finish();
+}
+
 } // extern "C"
 
 namespace {

@@ -308,6 +308,21 @@ struct SubsetArgs {
     int32_t max_iters;                         // resolved: > 0, per objective
 };
 hipError_t qpn_launch_issubset_pairs(const SubsetArgs &a, void *gws, hipStream_t s);   // gws: qpn_lp_workspace_bytes(pairs, r1, d)
+// ... and the implicit bounds of polyhedra (qpn_implicit_bounds), one job per polyhedron.  how, lo, hi, lps, iters, fail_row may be null.
+struct IbArgs {
+    int32_t polys, r, d, flags;
+    const double *A, *l, *u;
+    double tol;
+    int32_t *status, *fail_row;
+    uint8_t *eq;
+    double *vals;
+    int32_t *how;
+    double *lo, *hi;
+    int32_t *lps, *iters;
+    double piv_tol, feas_tol, opt_tol, check_tol;
+    int32_t max_iters;                         // resolved: > 0, per objective
+};
+hipError_t qpn_launch_implicit_bounds(const IbArgs &a, void *gws, hipStream_t s);     // gws: qpn_lp_workspace_bytes(polys, r, d)
 #define QPN_CONVEXITY_MAX_N 256
 #define QPN_CONVEXITY_MAX_M 1024
 

@@ -17,6 +17,12 @@
 // team per pair P1 within P2: the crash and phase 1 over P1 once, then the finite bounds of P2 one after the other as objectives
 // from the basis the previous one left, until one refutes (subset_core; polyhedra.issubset_pairs_host is its twin).  The slice is
 // that of an LP over P1; the row of P2 is read in place into its cost vector.
+//
+// qpn_implicit_bounds runs them with one team per polyhedron: the crash and phase 1 once, then the rows that
+// are no explicit equalities from the last to the first, the minimum and the maximum of each from the basis the previous solve
+// left; a row whose values at two points the solves ended at differ by more than tol needs no LP (ib_core;
+// polyhedra.implicit_bounds_host is its twin).  The slice is that of an LP; the witnesses stay in the registers of the lane that
+// owns the row, the answers go straight to the job's output rows.
 #include <climits>
 
 #include "qpn_internal.h"
@@ -575,6 +581,183 @@ template <bool LDS> __global__ __launch_bounds__(LP_GROUP) void subset_group_ker
     subset_job<LP_GROUP>(a, first + (int)blockIdx.x, reinterpret_cast<double *>(base), threadIdx.x);
 }
 
+// ---- implicit bounds: one team per polyhedron -----------------------------------------------------------------------------------
+// Rows a lane owns at the most: row i belongs to lane i % T.  ceil(QPN_LP_MAX_R / LP_GROUP) in the workgroup classes; in the
+// wavefront class a slice of at most 16 KiB holds r <= 195 rows (lp_slice_bytes >= 84 r), that is 4 per lane as well.
+constexpr int IB_NK = 4;
+static_assert(IB_NK * LP_GROUP >= QPN_LP_MAX_R && IB_NK * 64 >= LP_WAVE_SLICE_MAX / 84, "a lane's rows must fit its registers");
+
+struct IbOut { int status, fail_row, lps, iters; };
+
+// Polyhedron b (in range).  Every value a branch depends on is the same in all threads of the team (team reductions, values
+// read from the slice after a barrier, the polyhedron's own bounds), so a whole team leaves together.  The witnesses wlo / whi of
+// a lane's rows are registers: the arrays are indexed by unrolled constants only.
+template <int T> __device__ void ib_core(const IbArgs &a, const LpSlice &S, int b, int tid, IbOut &o)
+{
+    const int r = a.r, d = a.d, ld = lp_ld(r);
+    const LpProb P{r, d, a.A + (size_t)b * r * d, a.l + (size_t)b * r, a.u + (size_t)b * r, a.piv_tol, a.feas_tol, a.opt_tol, a.check_tol,
+                   a.max_iters};
+    const double tol = a.tol;
+    const bool every = (a.flags & QPN_IB_ALL_EXTREMES) != 0;
+    uint8_t *eq = a.eq + (size_t)b * r;
+    double *vals = a.vals + (size_t)b * r;
+    int32_t *how = a.how ? a.how + (size_t)b * r : nullptr;
+    double *lo = a.lo ? a.lo + (size_t)b * r : nullptr, *hi = a.hi ? a.hi + (size_t)b * r : nullptr;
+    // (0) explicit rows; the other rows' answers until an LP or two points decide them
+    int uncrossed = 1;
+#pragma unroll
+    for (int k = 0; k < IB_NK; ++k) {
+        const int i = tid + k * T;
+        if (i < r) {
+            const double li = P.lb[i], ui = P.ub[i];
+            const bool ex = fabs(li - ui) <= tol || li == ui;
+            if (!ex && li > ui) uncrossed = 0;
+            eq[i] = ex ? 1 : 0; vals[i] = ex ? 0.5 * (li + ui) : QINF;
+            if (how) how[i] = ex ? QPN_IB_HOW_EXPLICIT : QPN_IB_HOW_UNDECIDED;
+            if (lo) lo[i] = __builtin_nan("");
+            if (hi) hi[i] = __builtin_nan("");
+        }
+    }
+    for (int j = tid; j < d; j += T) { S.cv[j] = 0.0; S.xf[j] = 0.0; S.ray[j] = 0.0; }
+    for (int i = tid; i < r; i += T) S.lam[i] = 0.0;
+    team_sync<T>();
+    if (!team_min_int<T>(uncrossed, S.red, tid)) { o.status = QPN_IB_EMPTY; return; }   // crossed bounds: no LP is started
+    // (a) the feasibility solve
+    o.lps = 1;
+    if (lp_setup<T>(P, S, tid)) { o.status = QPN_IB_EMPTY; return; }
+    int e, it;
+    double dirn;
+    int status = lp_loop<T>(P, S, tid, &it, &e, &dirn);
+    lp_point<T>(P, S, tid);
+    o.iters = it;
+    if (status == QPN_LP_INFEASIBLE) {
+        o.status = lp_check<T>(P, S, status, e, dirn, tid) == QPN_LP_INFEASIBLE ? QPN_IB_EMPTY : QPN_IB_FAILURE;
+        return;
+    }
+    if (status != QPN_LP_OPTIMAL) { o.status = status == QPN_LP_ITER_LIMIT ? QPN_IB_ITER_LIMIT : QPN_IB_FAILURE; return; }
+    // (b) the witnesses: a lane per row, A read in place
+    double wlo[IB_NK], whi[IB_NK];
+#pragma unroll
+    for (int k = 0; k < IB_NK; ++k) {
+        const int i = tid + k * T;
+        double acc = 0.0;
+        if (i < r)
+            for (int j = 0; j < d; ++j) acc = acc + P.Ab[(size_t)j * r + i] * S.xf[j];
+        wlo[k] = acc; whi[k] = acc;
+    }
+    // (c) the rows from the last
+    for (int i = r - 1; i >= 0; --i) {
+        const double li = P.lb[i], ui = P.ub[i];
+        if (fabs(li - ui) <= tol || li == ui) continue;
+        const bool mine = i % T == tid;                   // this lane owns the row
+        // the witnesses of row i, from the lane that holds them
+        team_sync<T>();
+#pragma unroll
+        for (int k = 0; k < IB_NK; ++k)
+            if (tid + k * T == i) { S.red[5] = wlo[k]; S.red[6] = whi[k]; }
+        team_sync<T>();
+        double wl = S.red[5], wh = S.red[6];
+        if (!every && wh - wl > tol) {
+            if (mine && how) how[i] = QPN_IB_HOW_BY_POINTS;
+            continue;
+        }
+        double lov = 0.0, hiv = 0.0;
+        bool decided = false;
+        for (int side = 0; side < 2 && !decided; ++side) {
+            team_sync<T>();
+            for (int j = tid; j < d; j += T) { const double v = P.Ab[(size_t)j * r + i]; S.cv[j] = side ? -v : v; }
+            team_sync<T>();
+            // the cost row of c in the current dictionary (section 5g (e))
+            for (int j = tid; j < d; j += T) {
+                const double *col = S.Tm + (size_t)j * ld;
+                double acc = 0.0;
+                for (int k = 0; k < r; ++k) {
+                    const int id = S.rb[k];
+                    if (id < d) acc = acc + S.cv[id] * col[k];
+                }
+                if (S.cn[j] < d) acc = acc + S.cv[S.cn[j]];
+                S.Tm[(size_t)j * ld + r] = acc;
+            }
+            for (int j = tid; j < d; j += T) S.ray[j] = 0.0;
+            for (int k = tid; k < r; k += T) S.lam[k] = 0.0;
+            team_sync<T>();
+            ++o.lps;
+            status = lp_loop<T>(P, S, tid, &it, &e, &dirn);
+            const double obj = lp_point<T>(P, S, tid);
+            o.iters += it;
+            if (status == QPN_LP_ITER_LIMIT) { o.status = QPN_IB_ITER_LIMIT; o.fail_row = i; return; }
+            if (status == QPN_LP_FAILURE || status == QPN_LP_INFEASIBLE) { o.status = QPN_IB_FAILURE; o.fail_row = i; return; }
+            if (lp_check<T>(P, S, status, e, dirn, tid) == QPN_LP_FAILURE) { o.status = QPN_IB_FAILURE; o.fail_row = i; return; }
+            // (b) the rows at the new point: the check left A x in S.xb
+#pragma unroll
+            for (int k = 0; k < IB_NK; ++k) {
+                const int ii = tid + k * T;
+                if (ii < r) {
+                    const double s = S.xb[ii];
+                    wlo[k] = s < wlo[k] ? s : wlo[k]; whi[k] = s > whi[k] ? s : whi[k];
+                }
+            }
+            const double si = S.xb[i];
+            wl = si < wl ? si : wl; wh = si > wh ? si : wh;
+            if (side == 0) {
+                lov = status == QPN_LP_UNBOUNDED ? -QINF : obj;
+                if (mine && lo) lo[i] = lov;
+                if (!every) {
+                    if (status == QPN_LP_UNBOUNDED) {
+                        if (mine && how) how[i] = QPN_IB_HOW_UNBOUNDED;
+                        decided = true;
+                    } else if (wh - lov > tol) {
+                        if (mine && how) how[i] = QPN_IB_HOW_BY_POINTS;
+                        decided = true;
+                    }
+                }
+            } else {
+                hiv = status == QPN_LP_UNBOUNDED ? QINF : -obj;
+                if (mine && hi) hi[i] = hiv;
+            }
+        }
+        if (decided) continue;
+        const bool finite = fabs(lov) < QINF && fabs(hiv) < QINF;
+        const bool same = finite && fabs(lov - hiv) <= tol;
+        if (mine) {
+            if (same) { eq[i] = 1; vals[i] = 0.5 * (hiv + lov); }
+            if (how) how[i] = same ? QPN_IB_HOW_IMPLICIT : finite ? QPN_IB_HOW_BY_EXTREMES : QPN_IB_HOW_UNBOUNDED;
+        }
+    }
+    o.status = QPN_IB_OK;
+}
+
+template <int T> __device__ void ib_job(const IbArgs &a, int b, double *base, int tid)
+{
+    const LpSlice S(base, a.r, a.d);
+    if (tid < 8) S.red[tid] = 0.0;
+    team_sync<T>();
+    IbOut o{QPN_IB_FAILURE, -1, 0, 0};
+    ib_core<T>(a, S, b, tid, o);
+    if (tid == 0) {
+        a.status[b] = o.status;
+        if (a.fail_row) a.fail_row[b] = o.fail_row;
+        if (a.lps) a.lps[b] = o.lps;
+        if (a.iters) a.iters[b] = o.iters;
+    }
+}
+
+__global__ __launch_bounds__(64 * LP_WAVES) void ib_wave_kernel(IbArgs a, size_t slice)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char lp_lds[];
+    const int w = threadIdx.x / 64;
+    const long long b = (long long)blockIdx.x * LP_WAVES + w;
+    if (b >= a.polys) return;                             // a whole wavefront leaves: the others never wait for it
+    ib_job<64>(a, (int)b, reinterpret_cast<double *>(lp_lds + (size_t)w * slice), threadIdx.x % 64);
+}
+
+template <bool LDS> __global__ __launch_bounds__(LP_GROUP) void ib_group_kernel(IbArgs a, int32_t first, unsigned char *gws, size_t slice)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char lp_lds[];
+    unsigned char *base = LDS ? lp_lds : gws + (size_t)blockIdx.x * slice;
+    ib_job<LP_GROUP>(a, first + (int)blockIdx.x, reinterpret_cast<double *>(base), threadIdx.x);
+}
+
 int32_t lp_chunk(int32_t jobs, int32_t r, int32_t d)
 {
     size_t c = LP_WS_CHUNK_BYTES / lp_slice_bytes(r, d);
@@ -649,6 +832,35 @@ hipError_t qpn_launch_issubset_pairs(const SubsetArgs &a, void *gws, hipStream_t
     for (int32_t first = 0; first < a.pairs; first += chunk) {
         const int32_t count = a.pairs - first < chunk ? a.pairs - first : chunk;
         hipLaunchKernelGGL(subset_group_kernel<false>, dim3((unsigned)count), dim3(LP_GROUP), 0, s, a, first, static_cast<unsigned char *>(gws),
+                           slice);
+        if (const hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+hipError_t qpn_launch_implicit_bounds(const IbArgs &a, void *gws, hipStream_t s)
+{
+    if (a.polys <= 0) return hipSuccess;
+    const int cls = qpn_lp_class(a.r, a.d);
+    const size_t slice = lp_slice_bytes(a.r, a.d);
+    if (cls == 0) {
+        static QpnLdsLimits lds_limits;
+        if (const hipError_t e = lds_limits.raise({{ib_wave_kernel, (int)(LP_WAVE_SLICE_MAX * LP_WAVES)}}); e != hipSuccess) return e;
+        const unsigned grid = (unsigned)((a.polys + LP_WAVES - 1) / LP_WAVES);
+        hipLaunchKernelGGL(ib_wave_kernel, dim3(grid), dim3(64 * LP_WAVES), slice * LP_WAVES, s, a, slice);
+        return hipGetLastError();
+    }
+    if (cls == 1) {
+        static QpnLdsLimits lds_limits;
+        if (const hipError_t e = lds_limits.raise({{ib_group_kernel<true>, (int)LP_GROUP_SLICE_MAX}}); e != hipSuccess) return e;
+        hipLaunchKernelGGL(ib_group_kernel<true>, dim3((unsigned)a.polys), dim3(LP_GROUP), slice, s, a, 0, static_cast<unsigned char *>(nullptr),
+                           slice);
+        return hipGetLastError();
+    }
+    const int32_t chunk = lp_chunk(a.polys, a.r, a.d);
+    for (int32_t first = 0; first < a.polys; first += chunk) {
+        const int32_t count = a.polys - first < chunk ? a.polys - first : chunk;
+        hipLaunchKernelGGL(ib_group_kernel<false>, dim3((unsigned)count), dim3(LP_GROUP), 0, s, a, first, static_cast<unsigned char *>(gws),
                            slice);
         if (const hipError_t e = hipGetLastError(); e != hipSuccess) return e;
     }

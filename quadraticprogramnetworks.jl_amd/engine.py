@@ -707,6 +707,32 @@ class Engine:
                    _ptr(out["val"]), _ptr(out["lps"]), _ptr(out["iters"]), self._mem(dev))
         return out
 
+    def implicit_bounds(self, Ac, l, u, tol=1e-4, all_extremes=False, opts=None):
+        """`implicit_bounds` of polyhedra of one shape, one job per polyhedron (qpn_implicit_bounds; polyhedra.implicit_bounds_host
+        is its numpy twin, bit for bit): Ac [polys, d, r] (ABI layout, ``colmajor(A)``), l, u [polys, r].  all_extremes: every row
+        that is no explicit equality gets both extremes (QPN_IB_ALL_EXTREMES).  opts: LpOpts, a dict of its fields, or None.
+        Returns dict(status [polys] int32 (_lib.IB_*), fail_row [polys] int32, eq [polys, r] uint8, vals [polys, r], how [polys, r]
+        int32 (_lib.IB_HOW_*), lo, hi [polys, r], lps, iters [polys] int32)."""
+        dev, Ac, l, u = self._stage("implicit_bounds", "Ac l u", f64=(Ac, l, u))
+        if Ac.ndim != 3:
+            raise QpnError("implicit_bounds: inconsistent shapes")
+        polys, d, r = (int(v) for v in Ac.shape)
+        if tuple(l.shape) != (polys, r) or tuple(u.shape) != (polys, r):
+            raise QpnError("implicit_bounds: inconsistent shapes")
+        if isinstance(opts, dict):
+            o = self.default_lp_opts()
+            for k, v in opts.items():
+                setattr(o, k, v)
+            opts = o
+        out = dict(status=self._alloc(dev, (polys,), np.int32), fail_row=self._alloc(dev, (polys,), np.int32),
+                   eq=self._alloc(dev, (polys, r), np.uint8), vals=self._alloc(dev, (polys, r), np.float64),
+                   how=self._alloc(dev, (polys, r), np.int32), lo=self._alloc(dev, (polys, r), np.float64),
+                   hi=self._alloc(dev, (polys, r), np.float64), lps=self._alloc(dev, (polys,), np.int32), iters=self._alloc(dev, (polys,), np.int32))
+        self._call("qpn_implicit_bounds", polys, r, d, _ptr(Ac), _ptr(l), _ptr(u), float(tol), _lib.IB_ALL_EXTREMES if all_extremes else 0,
+                   C.byref(opts) if opts is not None else None, _ptr(out["status"]), _ptr(out["fail_row"]), _ptr(out["eq"]), _ptr(out["vals"]),
+                   _ptr(out["how"]), _ptr(out["lo"]), _ptr(out["hi"]), _ptr(out["lps"]), _ptr(out["iters"]), self._mem(dev))
+        return out
+
 
 class Nodes:
     """Resident node records (``qpn_nodes_upload``): the records of a level's single-node pools live in HBM owned by the

@@ -654,17 +654,74 @@ def isempty_slack_batch(polys, engine, tol=1e-4, x=None):
     return out
 
 
-def implicit_bounds_batch(polys, engine, tol=1e-4):
+def implicit_bounds_batch(polys, engine, tol=1e-4, route="jobs"):
     """`implicit_bounds(poly; tol)` (src/sets.jl:660-713) for a batch: which rows have implicitly equal lower and upper
     bounds on the polyhedron, and their values.  Per row that is not an explicit equality, the two LPs min / max a_i' x over
     the polyhedron (:676-706) -- ALL rows of ALL polyhedra in one call; an unbounded LP (RAY_TERM) gives -+inf as OSQP's
     status 4 does there.  An empty polyhedron raises "Empty set" like the reference (:688-690).
+    route="polyhedron" on an engine with `implicit_bounds` (qpn_implicit_bounds): ONE job per polyhedron -- the crash and phase 1
+    once, the rows' extremes from the basis the previous one left, a row whose values at two visited points differ by more than
+    tol refuted without an LP -- one call per shape, no node solve and no solve_lps call (_implicit_bounds_polyhedra); any other
+    engine, and a shape beyond the kernel's limits, keeps route="jobs".
     -> list of (implicitly_equality [n] bool, vals [n])."""
+    if route not in ("jobs", "polyhedron"):
+        raise ValueError(f"implicit_bounds_batch: unknown route {route!r}")
     trips = [tuple(np.asarray(a, dtype=np.float64) for a in _trip(p)) for p in polys]
     trips = [(np.atleast_2d(A), l, u) for A, l, u in trips]
-    empt = isempty_batch(trips, engine) if trips else np.zeros(0, bool)
+    if route == "polyhedron" and trips and callable(getattr(engine, "implicit_bounds", None)):
+        return _implicit_bounds_polyhedra(trips, engine, tol)
+    return _implicit_bounds_jobs(trips, engine, tol)
+
+
+def _implicit_bounds_polyhedra(trips, engine, tol):
+    """implicit_bounds_batch on an engine with `implicit_bounds`: the polyhedra packed by shape (rows, columns), one call per
+    shape; an EMPTY polyhedron raises "Empty set" for the lowest-numbered one, any other status the error that names the
+    polyhedron and the row whose solve ended it.  Shapes beyond the kernel's limits go the route of the jobs."""
+    from .engine import colmajor
+    packs, beyond = {}, []
+    for b, (A, l, u) in enumerate(trips):
+        r, d = A.shape
+        if r < 1 or d < 1 or r > LP_MAX_R or d > LP_MAX_D:
+            beyond.append(b)
+        else:
+            packs.setdefault((r, d), []).append(b)
+    out = [None] * len(trips)
+    empty, failed = [], []
+    for (r, d), members in sorted(packs.items()):
+        k = len(members)
+        A = np.stack([trips[b][0] for b in members]).reshape(k, r, d)
+        l = np.stack([trips[b][1] for b in members]).reshape(k, r); u = np.stack([trips[b][2] for b in members]).reshape(k, r)
+        res = engine.implicit_bounds(colmajor(A), l, u, tol=tol)
+        st = _to_host(res["status"]); fr = _to_host(res["fail_row"]); eq = _to_host(res["eq"]).astype(bool); vals = _to_host(res["vals"])
+        for t, b in enumerate(members):
+            if st[t] == IB_EMPTY:
+                empty.append(b)
+            elif st[t] != IB_OK:
+                failed.append((b, int(st[t]), int(fr[t])))
+            out[b] = (eq[t].copy(), vals[t].copy())
+    # (the emptiness of the shapes beyond the limits is asked before anything is raised: the lowest-numbered empty one is named)
+    empt = isempty_batch([trips[b] for b in beyond], engine) if beyond else np.zeros(0, bool)
+    empty += [b for b, e in zip(beyond, empt) if e]
+    if empty:
+        raise RuntimeError(f"Empty set (polyhedron {min(empty)})")
+    if failed:
+        b, st, row = min(failed)
+        raise RuntimeError(f"implicit_bounds_batch: status {st} on polyhedron {b}, row {row}")
+    if beyond:
+        for b, got in zip(beyond, _implicit_bounds_jobs([trips[b] for b in beyond], engine, tol, names=beyond, empt=empt)):
+            out[b] = got
+    return out
+
+
+def _implicit_bounds_jobs(trips, engine, tol, names=None, empt=None):
+    """implicit_bounds_batch's route of the jobs: the emptiness projection on the node solver (empt: its answer, when the caller
+    has it), then two LPs per row that is not an explicit equality.  names: the polyhedra's numbers in the caller's list (error
+    messages)."""
+    nm = (lambda b: b) if names is None else (lambda b: names[b])
+    if empt is None:
+        empt = isempty_batch(trips, engine) if trips else np.zeros(0, bool)
     if empt.any():
-        raise RuntimeError(f"Empty set (polyhedron {int(np.nonzero(empt)[0][0])})")
+        raise RuntimeError(f"Empty set (polyhedron {nm(int(np.nonzero(empt)[0][0]))})")
     jobs = []                                                   # (poly, row, sign)
     out = []
     for b, (A, l, u) in enumerate(trips):
@@ -677,7 +734,7 @@ def implicit_bounds_batch(polys, engine, tol=1e-4):
                 jobs.append((b, i, 1.0)); jobs.append((b, i, -1.0))
         out.append([eq, vals])
     if jobs and _has_lps(engine):
-        ext = _row_extremes_lps(trips, jobs, engine)
+        ext = _row_extremes_lps(trips, jobs, engine, nm)
         jobs = []
         _implicit_from_extremes(trips, out, ext, tol)
     if jobs:
@@ -737,7 +794,7 @@ def implicit_bounds_batch(polys, engine, tol=1e-4):
             elif st[k] == 2:
                 v = -INF if sg > 0 else INF                     # unbounded in that direction (:691-693, :704-706)
             else:
-                raise RuntimeError(f"implicit_bounds_batch: solver status {st[k]} on polyhedron {b}, row {i}")
+                raise RuntimeError(f"implicit_bounds_batch: solver status {st[k]} on polyhedron {nm(b)}, row {i}")
             ext[(b, i, sg)] = v
         _implicit_from_extremes(trips, out, ext, tol)
     return [(eq, vals) for eq, vals in out]
@@ -759,7 +816,7 @@ def _has_lps(engine):
     return callable(getattr(engine, "solve_lps", None))
 
 
-def _row_extremes_lps(trips, jobs, engine):
+def _row_extremes_lps(trips, jobs, engine, nm=lambda b: b):
     """implicit_bounds_batch's LPs on an engine with `solve_lps`: the polyhedra that have jobs are packed by shape (rows,
     columns) and go up once per pack; a job names its objective by (row, sign), so no cost vector and no copy of the
     polyhedron is made for it; an unbounded row is the solver's own answer.  jobs: [(polyhedron, row, sign)].
@@ -784,7 +841,7 @@ def _row_extremes_lps(trips, jobs, engine):
             elif st[t] == LP_UNBOUNDED:
                 ext[(b, i, sg)] = -INF if sg > 0 else INF       # (:691-693, :704-706)
             else:
-                raise RuntimeError(f"implicit_bounds_batch: LP status {st[t]} on polyhedron {b}, row {i}")
+                raise RuntimeError(f"implicit_bounds_batch: LP status {st[t]} on polyhedron {nm(b)}, row {i}")
     return ext
 
 
@@ -1210,4 +1267,135 @@ def issubset_pairs_host(A1c, l1, u1, A2c, l2, u2, pi, pj, tol=1e-6, opts=None):
         how, bound, val, lps, iters = _subset_one(mats1[a], l1[a], u1[a], mats2[b], l2[b], u2[b], float(tol), o)
         out["how"][q] = how; out["bound"][q] = bound; out["val"][q] = val; out["lps"][q] = lps; out["iters"][q] = iters
         out["sub"][q] = 1 if how in (SUBSET_HOLDS, SUBSET_EMPTY) else 0
+    return out
+
+
+# ---- implicit bounds (qpn_implicit_bounds): one job per polyhedron, the numpy twin ----------------------------------------------
+IB_OK, IB_EMPTY, IB_ITER_LIMIT, IB_FAILURE = 0, 1, 2, 3
+IB_HOW_UNDECIDED, IB_HOW_EXPLICIT, IB_HOW_IMPLICIT, IB_HOW_BY_POINTS, IB_HOW_BY_EXTREMES, IB_HOW_UNBOUNDED = 0, 1, 2, 3, 4, 5
+IB_ALL_EXTREMES = 1
+
+
+def _implicit_one(A, l, u, tol, flags, o):
+    """One polyhedron by the method of qpn_implicit_bounds (A [r, d] math layout).
+    -> (status, fail_row, eq [r] uint8, vals [r], how [r] int32, lo [r], hi [r], lps, iters)."""
+    r, d = A.shape
+    every = bool(flags & IB_ALL_EXTREMES)
+    eq = np.zeros(r, np.uint8); vals = np.full(r, INF); how = np.full(r, IB_HOW_UNDECIDED, np.int32)
+    lo = np.full(r, np.nan); hi = np.full(r, np.nan)
+    with np.errstate(all="ignore"):
+        # (0) explicit rows
+        explicit = (np.abs(l - u) <= tol) | (l == u)
+        eq[explicit] = 1; vals[explicit] = 0.5 * (l[explicit] + u[explicit]); how[explicit] = IB_HOW_EXPLICIT
+        if np.any(~explicit & (l > u)):                     # crossed bounds: no LP is started
+            return IB_EMPTY, -1, eq, vals, how, lo, hi, 0, 0
+        # (a) the feasibility solve: steps 1-8 with c = 0
+        zero = np.zeros(d)
+        S = _lp_setup(A, l, u, zero, o)
+        if S.zbad is not None:
+            return IB_EMPTY, -1, eq, vals, how, lo, hi, 1, 0
+        status = _lp_loop(S)
+        x, _ = _lp_point(S, zero)
+        lps, iters = 1, S.iters
+        if status == LP_INFEASIBLE:
+            ok, _, _ = _lp_check(S, status, zero, x)
+            return (IB_EMPTY if ok else IB_FAILURE), -1, eq, vals, how, lo, hi, lps, iters
+        if status != LP_OPTIMAL:
+            return (IB_ITER_LIMIT if status == LP_ITER_LIMIT else IB_FAILURE), -1, eq, vals, how, lo, hi, lps, iters
+
+        def rows_at(x):                                     # A x on the unscaled rows, columns ascending
+            s = np.zeros(r)
+            for j in range(d):
+                s = s + A[:, j] * x[j]
+            return s
+
+        # (b) the witnesses
+        s = rows_at(x)
+        wlo, whi = s.copy(), s.copy()
+        # (c) the rows from the last
+        for i in range(r - 1, -1, -1):
+            if explicit[i]:
+                continue
+            if not every and whi[i] - wlo[i] > tol:
+                how[i] = IB_HOW_BY_POINTS
+                continue
+            decided = False
+            for side in (0, 1):
+                c = A[i].copy() if side == 0 else -A[i]
+                # (§5g (e)) the cost row of c in the current dictionary
+                T, rb, cn = S.T, S.rb, S.cn
+                row = np.zeros(d)
+                for ii in range(r):
+                    if rb[ii] < d:
+                        row = row + c[rb[ii]] * T[ii, :]
+                for j in range(d):
+                    if cn[j] < d:
+                        row[j] = row[j] + c[cn[j]]
+                T[r] = row
+                lps += 1
+                status = _lp_loop(S)
+                x, obj = _lp_point(S, c)
+                iters += S.iters
+                if status == LP_ITER_LIMIT:
+                    return IB_ITER_LIMIT, i, eq, vals, how, lo, hi, lps, iters
+                if status == LP_FAILURE or status == LP_INFEASIBLE:
+                    return IB_FAILURE, i, eq, vals, how, lo, hi, lps, iters
+                ok, _, _ = _lp_check(S, status, c, x)
+                if not ok:
+                    return IB_FAILURE, i, eq, vals, how, lo, hi, lps, iters
+                s = rows_at(x)
+                wlo = np.where(s < wlo, s, wlo); whi = np.where(s > whi, s, whi)
+                if side == 0:
+                    lo[i] = -INF if status == LP_UNBOUNDED else obj
+                    if not every:
+                        if status == LP_UNBOUNDED:
+                            how[i] = IB_HOW_UNBOUNDED; decided = True
+                            break
+                        if whi[i] - lo[i] > tol:
+                            how[i] = IB_HOW_BY_POINTS; decided = True
+                            break
+                else:
+                    hi[i] = INF if status == LP_UNBOUNDED else -obj
+            if decided:
+                continue
+            if abs(lo[i]) < INF and abs(hi[i]) < INF and abs(lo[i] - hi[i]) <= tol:
+                eq[i] = 1; vals[i] = 0.5 * (hi[i] + lo[i]); how[i] = IB_HOW_IMPLICIT
+            else:
+                how[i] = IB_HOW_BY_EXTREMES if abs(lo[i]) < INF and abs(hi[i]) < INF else IB_HOW_UNBOUNDED
+    return IB_OK, -1, eq, vals, how, lo, hi, lps, iters
+
+
+def implicit_bounds_host(Ac, l, u, tol=1e-4, all_extremes=False, opts=None):
+    """The numpy twin of Engine.implicit_bounds (qpn_implicit_bounds), the normative statement of the method; every output of
+    the kernel is bit-equal to it.  `implicit_bounds` (src/sets.jl:660-713) with one job per polyhedron: Ac [polys, d, r] (ABI
+    layout), l, u [polys, r] (+-inf allowed).
+
+    (0) A row with |l - u| <= tol or l == u is EXPLICIT: eq = 1, val = 0.5 (l + u); no LP takes it as objective.  Another row
+    with l > u makes the polyhedron EMPTY before any LP (lps = 0: the simplex keeps a nonbasic row at one of its bounds and would
+    not see that they cross).  (a) solve_lps_host's steps 1-8 with c = 0 (the crash and phase 1, once): an infeasible all-zero row, or an INFEASIBLE end whose
+    Farkas certificate holds, is EMPTY, a certificate that fails FAILURE, ITER_LIMIT itself; the polyhedron stops there, its other
+    rows keep eq = 0, val = +inf, UNDECIDED.  (b) witnesses: s = A x at the end point on the unscaled rows, columns ascending
+    (acc = acc + a * x); wlo = whi = s, and after every later solve whose certificate holds wlo = s where s < wlo, whi = s where
+    s > whi.  (c) the rows r - 1 ... 0 that are not explicit: whi - wlo > tol is BY_POINTS without an LP; otherwise the minimum, c =
+    +a_i from the current basis (the cost row as in issubset_pairs_host (e), fresh step and degeneracy counters, the loop, the
+    point and step 9's check): a certified ray gives lo = -inf, UNBOUNDED; an optimum lo = obj, and whi - lo > tol is BY_POINTS;
+    then the maximum with c = -a_i: hi = -obj or +inf.  eq = lo, hi finite and |lo - hi| <= tol: val = 0.5 (hi + lo), IMPLICIT;
+    else BY_EXTREMES, or UNBOUNDED when one of the two is infinite.  ITER_LIMIT, an INFEASIBLE end or a failed certificate in one
+    of these solves ends the polyhedron with that status and fail_row = i.  all_extremes (QPN_IB_ALL_EXTREMES): no BY_POINTS and
+    no early exit after an unbounded minimum; every row that is not explicit gets both extremes and is decided by them alone.
+    -> dict(status [polys] int32 (IB_*), fail_row [polys] int32 (-1 without), eq [polys, r] uint8, vals [polys, r] (+inf where eq
+    = 0), how [polys, r] int32 (IB_HOW_*), lo, hi [polys, r] (NaN where no LP computed them), lps [polys] int32 (solves started,
+    the feasibility solve counted), iters [polys] int32 (all steps))."""
+    Ac = np.asarray(Ac, dtype=np.float64); l = np.asarray(l, dtype=np.float64); u = np.asarray(u, dtype=np.float64)
+    polys, d, r = Ac.shape
+    o = dict(LP_DEFAULT_OPTS)
+    o.update(opts or {})
+    flags = IB_ALL_EXTREMES if all_extremes else 0
+    out = dict(status=np.zeros(polys, np.int32), fail_row=np.full(polys, -1, np.int32), eq=np.zeros((polys, r), np.uint8),
+               vals=np.full((polys, r), INF), how=np.zeros((polys, r), np.int32), lo=np.full((polys, r), np.nan),
+               hi=np.full((polys, r), np.nan), lps=np.zeros(polys, np.int32), iters=np.zeros(polys, np.int32))
+    for b in range(polys):
+        got = _implicit_one(np.ascontiguousarray(Ac[b].T), l[b], u[b], float(tol), flags, o)
+        for k, v in zip(("status", "fail_row", "eq", "vals", "how", "lo", "hi", "lps", "iters"), got):
+            out[k][b] = v
     return out

@@ -16,6 +16,7 @@ INF = np.inf
 
 
 CONVEXITY_TOL = 1e-6                        # check_qp_convexity's tol (src/qp_processing.jl:39)
+IMPLICIT_BOUNDS_ROUTE = "jobs"              # implicit_bounds_batch's route for the convexity check: "jobs" or "polyhedron"
 
 
 class NonConvexQPError(RuntimeError):
@@ -28,9 +29,10 @@ class NonConvexQPError(RuntimeError):
         self.min_eig = float(min_eig)
 
 
-def convexity_blocks(blocks, engine=None, tol=CONVEXITY_TOL):
-    """check_qp_convexity for MANY nodes: ONE implicit_bounds_batch call for all constraint stacks, then one qpn_convexity_nodes
-    call per (n, padded m).  blocks: list of (pid, Qd [n, n], A [m, c], l, u, dec) with A the stack's rows over some columns
+def convexity_blocks(blocks, engine=None, tol=CONVEXITY_TOL, route=None):
+    """check_qp_convexity for MANY nodes: ONE implicit_bounds_batch call for all constraint stacks (by `route`, None: the module's
+    IMPLICIT_BOUNDS_ROUTE), then one qpn_convexity_nodes call per (n, padded m).
+    blocks: list of (pid, Qd [n, n], A [m, c], l, u, dec) with A the stack's rows over some columns
     that hold every variable they read, dec the positions of the node's decision variables among those columns.  Raises
     NonConvexQPError for the FIRST non-convex block in list order; returns (min_eig, null_dim) per block otherwise."""
     from .level_batch import ROW_PAD
@@ -41,7 +43,8 @@ def convexity_blocks(blocks, engine=None, tol=CONVEXITY_TOL):
     eqs = [np.zeros(0, bool)] * len(blocks)
     if withrows:
         got = implicit_bounds_batch([(np.atleast_2d(np.asarray(blocks[k][2], dtype=np.float64)), np.asarray(blocks[k][3], dtype=np.float64),
-                                      np.asarray(blocks[k][4], dtype=np.float64)) for k in withrows], eng, tol=tol)
+                                      np.asarray(blocks[k][4], dtype=np.float64)) for k in withrows], eng, tol=tol,
+                                    route=IMPLICIT_BOUNDS_ROUTE if route is None else route)
         for k, (eq, _vals) in zip(withrows, got):
             eqs[k] = np.asarray(eq, bool)
     groups: Dict[tuple, List[int]] = {}
@@ -78,7 +81,7 @@ def check_qp_convexity(Q, A, l, u, dec_inds, pid, tol=CONVEXITY_TOL, engine=None
                               np.asarray(u, dtype=np.float64).ravel(), dec)], engine=engine, tol=tol)[0]
 
 
-def check_convexity_items(qpn, items, engine, tol=CONVEXITY_TOL):
+def check_convexity_items(qpn, items, engine, tol=CONVEXITY_TOL, route=None):
     """check_qp_convexity for every (pid, [child Poly, ...]) item of a verify batch (level_batch.verify_items), in the items'
     order (players in order, then sub-piece combinations in Iterators.product order).  The answer depends on the node and its
     constraint stack alone, never on x, so it is kept per (pid, the appended pieces by identity) for the solve; only items not
@@ -100,7 +103,7 @@ def check_convexity_items(qpn, items, engine, tol=CONVEXITY_TOL):
         keys.append(key)
     if not todo:
         return
-    got = convexity_blocks(todo, engine=engine, tol=tol)           # raises for the first non-convex item
+    got = convexity_blocks(todo, engine=engine, tol=tol, route=route)           # raises for the first non-convex item
     chs = {(pid, tuple(id(P) for P in ch), tol): tuple(ch) for pid, ch in items}
     for key, r in zip(keys, got):
         memo[key] = (chs[key], r)

@@ -94,9 +94,9 @@ def main():
     seen = []
     real = polyhedra.implicit_bounds_batch
 
-    def capture(polys, engine, tol=1e-4):
+    def capture(polys, engine, tol=1e-4, **kw):
         seen.append([tuple(np.asarray(v, dtype=np.float64) for v in p) for p in polys])
-        return real(polys, engine, tol=tol)
+        return real(polys, engine, tol=tol, **kw)
 
     polyhedra.implicit_bounds_batch = capture
     try:
