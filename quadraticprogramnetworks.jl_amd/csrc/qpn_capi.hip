@@ -110,6 +110,12 @@ struct Stage {
         carve(dev, bytes + pad);
         if (dst && bytes) down.push_back({(void **)&dev, dst, bytes});
     }
+    // an optional output: host mode carves it only when the caller wants it (the kernel skips a null one)
+    template <class T> void out_opt(T *&dev, void *dst, size_t bytes)
+    {
+        dev = nullptr;
+        if (dst || !host) out(dev, dst, bytes);
+    }
     template <class T> void inout(T *&dev, T *p, size_t bytes, bool upload)
     {
         if (!host) { dev = p; return; }
@@ -156,6 +162,15 @@ struct Stage {
         return QPN_OK;
     }
 };
+
+// The tolerances of the LP entries' solves over polyhedra of r rows in d variables: the caller's options or, without, the defaults;
+// max_iters <= 0 is 50 (r + d) + 100.
+LpTol lp_tol(const qpn_lp_opts *opts, int32_t r, int32_t d)
+{
+    qpn_lp_opts o;
+    if (opts) o = *opts; else qpn_lp_default_opts(&o);
+    return LpTol{o.piv_tol, o.feas_tol, o.opt_tol, o.check_tol, o.max_iters > 0 ? o.max_iters : 50 * (r + d) + 100};
+}
 
 struct NodeSizes { size_t Q, R, q, A, B, lu, w; };
 NodeSizes node_sizes(int32_t batch, int32_t n, int32_t m, int32_t p, int64_t stride_w)
@@ -1754,25 +1769,21 @@ int qpn_solve_lps(qpn_ctx *ctx, int32_t polys, int32_t r, int32_t d, const doubl
     for (int t = 0; st.host && t < jobs; ++t)
         if (poly_of[t] < 0 || poly_of[t] >= polys || (!cost && (obj_row[t] < 0 || obj_row[t] >= r)))
             return fail_arg(ctx, "qpn_solve_lps: poly_of / obj_row out of range");
-    qpn_lp_opts o;
-    if (opts) o = *opts; else qpn_lp_default_opts(&o);
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const size_t P = (size_t)polys, J = (size_t)jobs;
     LpArgs a{};
     a.polys = polys; a.r = r; a.d = d; a.jobs = jobs;
-    a.piv_tol = o.piv_tol; a.feas_tol = o.feas_tol; a.opt_tol = o.opt_tol; a.check_tol = o.check_tol;
-    a.max_iters = o.max_iters > 0 ? o.max_iters : 50 * (r + d) + 100;
+    a.lp = lp_tol(opts, r, d);
     void *gws;
     st.in(a.A, A, P * r * d * 8); st.in(a.l, l, P * r * 8); st.in(a.u, u, P * r * 8); st.in(a.poly_of, poly_of, J * 4);
     st.in(a.cost, cost, J * d * 8);
     st.in(a.obj_row, cost ? nullptr : obj_row, J * 4); st.in(a.obj_sign, cost ? nullptr : obj_sign, J * 4);
-    // (host mode: an output the caller does not want is not carved either -- the kernel skips a null one)
     st.out(a.status, status, J * 4);
-    if (x || !st.host) st.out(a.x, x, J * d * 8);
-    if (obj || !st.host) st.out(a.obj, obj, J * 8);
-    if (lambda || !st.host) st.out(a.lam, lambda, J * r * 8);
-    if (ray || !st.host) st.out(a.ray, ray, J * d * 8);
-    if (iters || !st.host) st.out(a.iters, iters, J * 4);
+    st.out_opt(a.x, x, J * d * 8);
+    st.out_opt(a.obj, obj, J * 8);
+    st.out_opt(a.lam, lambda, J * r * 8);
+    st.out_opt(a.ray, ray, J * d * 8);
+    st.out_opt(a.iters, iters, J * 4);
     st.scratch(gws, qpn_lp_workspace_bytes(jobs, r, d));
     int rc = st.begin();
     if (rc != QPN_OK) return rc;
@@ -1798,24 +1809,21 @@ int qpn_issubset_pairs(qpn_ctx *ctx, int32_t d, int32_t B1, int32_t r1, const do
     // host index arrays are checked here; device ones by the kernel (such a pair answers QPN_SUBSET_FAILURE)
     for (int q = 0; st.host && q < pairs; ++q)
         if (pi[q] < 0 || pi[q] >= B1 || pj[q] < 0 || pj[q] >= B2) return fail_arg(ctx, "qpn_issubset_pairs: pi / pj out of range");
-    qpn_lp_opts o;
-    if (opts) o = *opts; else qpn_lp_default_opts(&o);
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const size_t N = (size_t)pairs;
     SubsetArgs a{};
     a.d = d; a.B1 = B1; a.r1 = r1; a.B2 = B2; a.r2 = r2; a.pairs = pairs; a.tol = tol;
-    a.piv_tol = o.piv_tol; a.feas_tol = o.feas_tol; a.opt_tol = o.opt_tol; a.check_tol = o.check_tol;
-    a.max_iters = o.max_iters > 0 ? o.max_iters : 50 * (r1 + d) + 100;
+    a.lp = lp_tol(opts, r1, d);
     void *gws;
     st.in(a.A1, A1, (size_t)B1 * r1 * d * 8); st.in(a.l1, l1, (size_t)B1 * r1 * 8); st.in(a.u1, u1, (size_t)B1 * r1 * 8);
     st.in(a.A2, A2, (size_t)B2 * r2 * d * 8); st.in(a.l2, l2, (size_t)B2 * r2 * 8); st.in(a.u2, u2, (size_t)B2 * r2 * 8);
     st.in(a.pi, pi, N * 4); st.in(a.pj, pj, N * 4);
     st.out(a.sub, sub, N);
-    if (how || !st.host) st.out(a.how, how, N * 4);
-    if (bound || !st.host) st.out(a.bound, bound, N * 4);
-    if (val || !st.host) st.out(a.val, val, N * 8);
-    if (lps || !st.host) st.out(a.lps, lps, N * 4);
-    if (iters || !st.host) st.out(a.iters, iters, N * 4);
+    st.out_opt(a.how, how, N * 4);
+    st.out_opt(a.bound, bound, N * 4);
+    st.out_opt(a.val, val, N * 8);
+    st.out_opt(a.lps, lps, N * 4);
+    st.out_opt(a.iters, iters, N * 4);
     st.scratch(gws, qpn_lp_workspace_bytes(pairs, r1, d));
     int rc = st.begin();
     if (rc != QPN_OK) return rc;
@@ -1834,24 +1842,20 @@ int qpn_implicit_bounds(qpn_ctx *ctx, int32_t polys, int32_t r, int32_t d, const
     if (int rc = st.check()) return rc;
     if (polys == 0) return QPN_OK;
     if (!A || !l || !u || !status || !eq || !vals) return fail_arg(ctx, "qpn_implicit_bounds: null pointer");
-    qpn_lp_opts o;
-    if (opts) o = *opts; else qpn_lp_default_opts(&o);
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const size_t P = (size_t)polys;
     IbArgs a{};
     a.polys = polys; a.r = r; a.d = d; a.flags = flags; a.tol = tol;
-    a.piv_tol = o.piv_tol; a.feas_tol = o.feas_tol; a.opt_tol = o.opt_tol; a.check_tol = o.check_tol;
-    a.max_iters = o.max_iters > 0 ? o.max_iters : 50 * (r + d) + 100;
+    a.lp = lp_tol(opts, r, d);
     void *gws;
     st.in(a.A, A, P * r * d * 8); st.in(a.l, l, P * r * 8); st.in(a.u, u, P * r * 8);
-    // (host mode: an output the caller does not want is not carved either -- the kernel skips a null one)
     st.out(a.status, status, P * 4); st.out(a.eq, eq, P * r); st.out(a.vals, vals, P * r * 8);
-    if (fail_row || !st.host) st.out(a.fail_row, fail_row, P * 4);
-    if (how || !st.host) st.out(a.how, how, P * r * 4);
-    if (lo || !st.host) st.out(a.lo, lo, P * r * 8);
-    if (hi || !st.host) st.out(a.hi, hi, P * r * 8);
-    if (lps || !st.host) st.out(a.lps, lps, P * 4);
-    if (iters || !st.host) st.out(a.iters, iters, P * 4);
+    st.out_opt(a.fail_row, fail_row, P * 4);
+    st.out_opt(a.how, how, P * r * 4);
+    st.out_opt(a.lo, lo, P * r * 8);
+    st.out_opt(a.hi, hi, P * r * 8);
+    st.out_opt(a.lps, lps, P * 4);
+    st.out_opt(a.iters, iters, P * 4);
     st.scratch(gws, qpn_lp_workspace_bytes(polys, r, d));
     int rc = st.begin();
     if (rc != QPN_OK) return rc;

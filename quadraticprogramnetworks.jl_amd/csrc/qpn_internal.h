@@ -277,6 +277,10 @@ hipError_t qpn_launch_members_outside(int32_t pairs, int32_t d, int32_t rj, cons
 #define QPN_MEMBERS_MAX_ROWS 4096
 
 // qpn_lp.hip: the batched LP solver (qpn_solve_lps).  Pointers are device pointers; x, obj, lam, ray, iters may be null.
+struct LpTol {                                 // the resolved tolerances of an entry's solves
+    double piv_tol, feas_tol, opt_tol, check_tol;
+    int32_t max_iters;                         // > 0, per objective
+};
 struct LpArgs {
     int32_t polys, r, d, jobs;
     const double *A, *l, *u;
@@ -286,8 +290,7 @@ struct LpArgs {
     int32_t *status;
     double *x, *obj, *lam, *ray;
     int32_t *iters;
-    double piv_tol, feas_tol, opt_tol, check_tol;
-    int32_t max_iters;                         // resolved: > 0
+    LpTol lp;
 };
 #define QPN_LP_MAX_D 256
 #define QPN_LP_MAX_R 1024
@@ -304,8 +307,7 @@ struct SubsetArgs {
     int32_t *how, *bound;
     double *val;
     int32_t *lps, *iters;
-    double piv_tol, feas_tol, opt_tol, check_tol;
-    int32_t max_iters;                         // resolved: > 0, per objective
+    LpTol lp;
 };
 hipError_t qpn_launch_issubset_pairs(const SubsetArgs &a, void *gws, hipStream_t s);   // gws: qpn_lp_workspace_bytes(pairs, r1, d)
 // ... and the implicit bounds of polyhedra (qpn_implicit_bounds), one job per polyhedron.  how, lo, hi, lps, iters, fail_row may be null.
@@ -319,8 +321,7 @@ struct IbArgs {
     int32_t *how;
     double *lo, *hi;
     int32_t *lps, *iters;
-    double piv_tol, feas_tol, opt_tol, check_tol;
-    int32_t max_iters;                         // resolved: > 0, per objective
+    LpTol lp;
 };
 hipError_t qpn_launch_implicit_bounds(const IbArgs &a, void *gws, hipStream_t s);     // gws: qpn_lp_workspace_bytes(polys, r, d)
 #define QPN_CONVEXITY_MAX_N 256

@@ -14,15 +14,18 @@
 // in chunks.  Every loop is bounded: the crash by d, the simplex loop by max_iters.
 //
 // qpn_issubset_pairs runs the same set-up, loop and check (lp_setup, lp_loop, lp_point, lp_check) with one
-// team per pair P1 within P2: the crash and phase 1 over P1 once, then the finite bounds of P2 one after the other as objectives
-// from the basis the previous one left, until one refutes (subset_core; polyhedra.issubset_pairs_host is its twin).  The slice is
-// that of an LP over P1; the row of P2 is read in place into its cost vector.
+// team per pair P1 within P2: the crash and phase 1 over P1 once (lp_feasible), then the finite bounds of P2 one after the other
+// as objectives from the basis the previous one left (lp_resolve), until one refutes (subset_core; polyhedra.issubset_pairs_host
+// is its twin).  The slice is that of an LP over P1; the row of P2 is read in place into its cost vector.
 //
-// qpn_implicit_bounds runs them with one team per polyhedron: the crash and phase 1 once, then the rows that
-// are no explicit equalities from the last to the first, the minimum and the maximum of each from the basis the previous solve
-// left; a row whose values at two points the solves ended at differ by more than tol needs no LP (ib_core;
+// qpn_implicit_bounds runs them with one team per polyhedron: lp_feasible once, then the rows that are no
+// explicit equalities from the last to the first, the minimum and the maximum of each by lp_resolve from the basis the previous
+// solve left; a row whose values at two points the solves ended at differ by more than tol needs no LP (ib_core;
 // polyhedra.implicit_bounds_host is its twin).  The slice is that of an LP; the witnesses stay in the registers of the lane that
 // owns the row, the answers go straight to the job's output rows.
+//
+// The three entries share the kernels and the launcher: lp_wave_kernel<Job> and lp_group_kernel<Job, LDS>
+// run the job function of the kind Job (LpJob, SubsetJob, IbJob), lp_launch<Job> picks the class and launches.
 #include <climits>
 
 #include "qpn_internal.h"
@@ -131,6 +134,10 @@ struct LpProb {
     double piv_tol, feas_tol, opt_tol, ct;
     int max_iters;
 };
+__device__ inline LpProb lp_prob(int r, int d, const double *Ab, const double *lb, const double *ub, const LpTol &t)
+{
+    return LpProb{r, d, Ab, lb, ub, t.piv_tol, t.feas_tol, t.opt_tol, t.check_tol, t.max_iters};
+}
 
 // Steps 1-4 with the objective in S.cv: scaling, the dictionary, the crash, the nonbasic values.  -> QPN_LP_INFEASIBLE when an
 // all-zero row outside its bounds settles the job (its unit Farkas vector in S.lam), 0 otherwise.
@@ -394,14 +401,63 @@ template <int T> __device__ int lp_check(const LpProb &P, const LpSlice &S, int 
     return team_min_int<T>(ok, red, tid) ? status : QPN_LP_FAILURE;
 }
 
+// The feasibility solve of the subset tests and the implicit bounds (sections 5g (a), 5h (a); the twin's _lp_feasible): steps 1-8 with
+// c = 0 from zeroed slice vectors.  -> QPN_LP_OPTIMAL (a point of the polyhedron in S.xf, its basis in the dictionary),
+// QPN_LP_INFEASIBLE (an all-zero row outside its bounds, *iters_out = 0, or an INFEASIBLE end whose Farkas certificate holds),
+// QPN_LP_ITER_LIMIT, or QPN_LP_FAILURE (a certificate that fails included).
+template <int T> __device__ int lp_feasible(const LpProb &P, const LpSlice &S, int tid, int *iters_out)
+{
+    const int r = P.r, d = P.d;
+    *iters_out = 0;
+    for (int j = tid; j < d; j += T) { S.cv[j] = 0.0; S.xf[j] = 0.0; S.ray[j] = 0.0; }
+    for (int i = tid; i < r; i += T) S.lam[i] = 0.0;
+    team_sync<T>();
+    if (lp_setup<T>(P, S, tid)) return QPN_LP_INFEASIBLE;
+    int e;
+    double dirn;
+    const int status = lp_loop<T>(P, S, tid, iters_out, &e, &dirn);
+    lp_point<T>(P, S, tid);
+    if (status == QPN_LP_INFEASIBLE)
+        return lp_check<T>(P, S, status, e, dirn, tid) == QPN_LP_INFEASIBLE ? QPN_LP_INFEASIBLE : QPN_LP_FAILURE;
+    return status == QPN_LP_OPTIMAL || status == QPN_LP_ITER_LIMIT ? status : QPN_LP_FAILURE;
+}
+
+// The solve of the objective in S.cv (all threads past a barrier) from the basis the previous solve over the polyhedron left
+// (the twin's _lp_resolve): the cost row of c in the current dictionary (section 5g (e)), the loop with fresh counters, the point
+// and the check.  -> QPN_LP_OPTIMAL or QPN_LP_UNBOUNDED, certified; QPN_LP_ITER_LIMIT; QPN_LP_FAILURE (of the loop, an INFEASIBLE
+// end, a certificate that fails).  x in S.xf, c'x in *obj_out and, after a check, A x in S.xb.
+template <int T> __device__ int lp_resolve(const LpProb &P, const LpSlice &S, int tid, int *iters_out, double *obj_out)
+{
+    const int r = P.r, d = P.d, ld = lp_ld(r);
+    for (int j = tid; j < d; j += T) {
+        const double *col = S.Tm + (size_t)j * ld;
+        double acc = 0.0;
+        for (int k = 0; k < r; ++k) {
+            const int id = S.rb[k];
+            if (id < d) acc = acc + S.cv[id] * col[k];
+        }
+        if (S.cn[j] < d) acc = acc + S.cv[S.cn[j]];
+        S.Tm[(size_t)j * ld + r] = acc;
+    }
+    for (int j = tid; j < d; j += T) S.ray[j] = 0.0;
+    for (int k = tid; k < r; k += T) S.lam[k] = 0.0;
+    team_sync<T>();
+    int e;
+    double dirn;
+    const int status = lp_loop<T>(P, S, tid, iters_out, &e, &dirn);
+    *obj_out = lp_point<T>(P, S, tid);
+    if (status == QPN_LP_ITER_LIMIT) return status;
+    if (status == QPN_LP_FAILURE || status == QPN_LP_INFEASIBLE) return QPN_LP_FAILURE;
+    return lp_check<T>(P, S, status, e, dirn, tid);
+}
+
 // The solve of job t over polyhedron b.  Leaves x in S.xf, the multipliers / Farkas vector in S.lam, the ray in S.ray (zeroed by
 // the caller).  -> status; *iters, *objv.
 template <int T>
 __device__ int lp_core(const LpArgs &a, const LpSlice &S, int t, int b, int orow, int tid, int *iters_out, double *obj_out)
 {
     const int r = a.r, d = a.d;
-    const LpProb P{r, d, a.A + (size_t)b * r * d, a.l + (size_t)b * r, a.u + (size_t)b * r, a.piv_tol, a.feas_tol, a.opt_tol, a.check_tol,
-                   a.max_iters};
+    const LpProb P = lp_prob(r, d, a.A + (size_t)b * r * d, a.l + (size_t)b * r, a.u + (size_t)b * r, a.lp);
     *iters_out = 0; *obj_out = 0.0;
     for (int j = tid; j < d; j += T)
         S.cv[j] = a.cost ? a.cost[(size_t)t * d + j] : (double)a.obj_sign[t] * P.Ab[(size_t)j * r + orow];
@@ -438,22 +494,6 @@ template <int T> __device__ void lp_job(const LpArgs &a, int t, double *base, in
     }
 }
 
-__global__ __launch_bounds__(64 * LP_WAVES) void lp_wave_kernel(LpArgs a, size_t slice)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char lp_lds[];
-    const int w = threadIdx.x / 64;
-    const long long t = (long long)blockIdx.x * LP_WAVES + w;
-    if (t >= a.jobs) return;                              // a whole wavefront leaves: the others never wait for it
-    lp_job<64>(a, (int)t, reinterpret_cast<double *>(lp_lds + (size_t)w * slice), threadIdx.x % 64);
-}
-
-template <bool LDS> __global__ __launch_bounds__(LP_GROUP) void lp_group_kernel(LpArgs a, int32_t first, unsigned char *gws, size_t slice)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char lp_lds[];
-    unsigned char *base = LDS ? lp_lds : gws + (size_t)blockIdx.x * slice;
-    lp_job<LP_GROUP>(a, first + (int)blockIdx.x, reinterpret_cast<double *>(base), threadIdx.x);
-}
-
 // ---- subset tests: one team per pair ------------------------------------------------------------------------------------------
 struct SubsetOut { int how, bound, lps, iters; double val; };
 
@@ -461,27 +501,19 @@ struct SubsetOut { int how, bound, lps, iters; double val; };
 // the team (team reductions, or sums every thread runs over the slice), so a whole team leaves together.
 template <int T> __device__ void subset_core(const SubsetArgs &a, const LpSlice &S, int b1, int b2, int tid, SubsetOut &o)
 {
-    const int r = a.r1, d = a.d, r2 = a.r2, ld = lp_ld(r);
-    const LpProb P{r, d, a.A1 + (size_t)b1 * r * d, a.l1 + (size_t)b1 * r, a.u1 + (size_t)b1 * r, a.piv_tol, a.feas_tol, a.opt_tol,
-                   a.check_tol, a.max_iters};
+    const int r = a.r1, d = a.d, r2 = a.r2;
+    const LpProb P = lp_prob(r, d, a.A1 + (size_t)b1 * r * d, a.l1 + (size_t)b1 * r, a.u1 + (size_t)b1 * r, a.lp);
     const double *A2 = a.A2 + (size_t)b2 * r2 * d, *l2 = a.l2 + (size_t)b2 * r2, *u2 = a.u2 + (size_t)b2 * r2;
     const double tol = a.tol;
-    for (int j = tid; j < d; j += T) { S.cv[j] = 0.0; S.xf[j] = 0.0; S.ray[j] = 0.0; }
-    for (int i = tid; i < r; i += T) S.lam[i] = 0.0;
-    team_sync<T>();
     // (a) the feasibility solve
+    int it;
     o.lps = 1;
-    if (lp_setup<T>(P, S, tid)) { o.how = QPN_SUBSET_EMPTY; return; }
-    int e, it;
-    double dirn;
-    int status = lp_loop<T>(P, S, tid, &it, &e, &dirn);
-    lp_point<T>(P, S, tid);
+    int status = lp_feasible<T>(P, S, tid, &it);
     o.iters = it;
-    if (status == QPN_LP_INFEASIBLE) {
-        o.how = lp_check<T>(P, S, status, e, dirn, tid) == QPN_LP_INFEASIBLE ? QPN_SUBSET_EMPTY : QPN_SUBSET_FAILURE;
+    if (status != QPN_LP_OPTIMAL) {
+        o.how = status == QPN_LP_INFEASIBLE ? QPN_SUBSET_EMPTY : status == QPN_LP_ITER_LIMIT ? QPN_SUBSET_ITER_LIMIT : QPN_SUBSET_FAILURE;
         return;
     }
-    if (status != QPN_LP_OPTIMAL) { o.how = status == QPN_LP_ITER_LIMIT ? QPN_SUBSET_ITER_LIMIT : QPN_SUBSET_FAILURE; return; }
     // (b) the bounds of P2 in order
     for (int i = 0; i < r2; ++i) {
         const double l2i = l2[i], u2i = u2[i];
@@ -516,28 +548,13 @@ template <int T> __device__ void subset_core(const SubsetArgs &a, const LpSlice 
             double v = 0.0;
             for (int k = 0; k < d; ++k) v = v + S.cv[k] * S.xf[k];
             if (v < beta - tol) { o.how = QPN_SUBSET_BY_POINT; o.val = v; return; }
-            // (e) the cost row of c in the current dictionary
-            for (int j = tid; j < d; j += T) {
-                const double *col = S.Tm + (size_t)j * ld;
-                double acc = 0.0;
-                for (int k = 0; k < r; ++k) {
-                    const int id = S.rb[k];
-                    if (id < d) acc = acc + S.cv[id] * col[k];
-                }
-                if (S.cn[j] < d) acc = acc + S.cv[S.cn[j]];
-                S.Tm[(size_t)j * ld + r] = acc;
-            }
-            for (int j = tid; j < d; j += T) S.ray[j] = 0.0;
-            for (int k = tid; k < r; k += T) S.lam[k] = 0.0;
-            team_sync<T>();
-            // (f) solve and decide
+            // (e) the cost row of c in the current dictionary, (f) solve and decide
+            double obj;
             ++o.lps;
-            status = lp_loop<T>(P, S, tid, &it, &e, &dirn);
-            const double obj = lp_point<T>(P, S, tid);
+            status = lp_resolve<T>(P, S, tid, &it, &obj);
             o.iters += it;
             if (status == QPN_LP_ITER_LIMIT) { o.how = QPN_SUBSET_ITER_LIMIT; return; }
-            if (status == QPN_LP_FAILURE || status == QPN_LP_INFEASIBLE) { o.how = QPN_SUBSET_FAILURE; return; }
-            if (lp_check<T>(P, S, status, e, dirn, tid) == QPN_LP_FAILURE) { o.how = QPN_SUBSET_FAILURE; return; }
+            if (status == QPN_LP_FAILURE) { o.how = QPN_SUBSET_FAILURE; return; }
             if (status == QPN_LP_UNBOUNDED) { o.how = QPN_SUBSET_UNBOUNDED; return; }
             if (obj < beta - tol) { o.how = QPN_SUBSET_BY_OPTIMUM; o.val = obj; return; }
             o.bound = -1;
@@ -565,22 +582,6 @@ template <int T> __device__ void subset_job(const SubsetArgs &a, int q, double *
     }
 }
 
-__global__ __launch_bounds__(64 * LP_WAVES) void subset_wave_kernel(SubsetArgs a, size_t slice)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char lp_lds[];
-    const int w = threadIdx.x / 64;
-    const long long q = (long long)blockIdx.x * LP_WAVES + w;
-    if (q >= a.pairs) return;                             // a whole wavefront leaves: the others never wait for it
-    subset_job<64>(a, (int)q, reinterpret_cast<double *>(lp_lds + (size_t)w * slice), threadIdx.x % 64);
-}
-
-template <bool LDS> __global__ __launch_bounds__(LP_GROUP) void subset_group_kernel(SubsetArgs a, int32_t first, unsigned char *gws, size_t slice)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char lp_lds[];
-    unsigned char *base = LDS ? lp_lds : gws + (size_t)blockIdx.x * slice;
-    subset_job<LP_GROUP>(a, first + (int)blockIdx.x, reinterpret_cast<double *>(base), threadIdx.x);
-}
-
 // ---- implicit bounds: one team per polyhedron -----------------------------------------------------------------------------------
 // Rows a lane owns at the most: row i belongs to lane i % T.  ceil(QPN_LP_MAX_R / LP_GROUP) in the workgroup classes; in the
 // wavefront class a slice of at most 16 KiB holds r <= 195 rows (lp_slice_bytes >= 84 r), that is 4 per lane as well.
@@ -594,9 +595,8 @@ struct IbOut { int status, fail_row, lps, iters; };
 // a lane's rows are registers: the arrays are indexed by unrolled constants only.
 template <int T> __device__ void ib_core(const IbArgs &a, const LpSlice &S, int b, int tid, IbOut &o)
 {
-    const int r = a.r, d = a.d, ld = lp_ld(r);
-    const LpProb P{r, d, a.A + (size_t)b * r * d, a.l + (size_t)b * r, a.u + (size_t)b * r, a.piv_tol, a.feas_tol, a.opt_tol, a.check_tol,
-                   a.max_iters};
+    const int r = a.r, d = a.d;
+    const LpProb P = lp_prob(r, d, a.A + (size_t)b * r * d, a.l + (size_t)b * r, a.u + (size_t)b * r, a.lp);
     const double tol = a.tol;
     const bool every = (a.flags & QPN_IB_ALL_EXTREMES) != 0;
     uint8_t *eq = a.eq + (size_t)b * r;
@@ -618,23 +618,16 @@ template <int T> __device__ void ib_core(const IbArgs &a, const LpSlice &S, int 
             if (hi) hi[i] = __builtin_nan("");
         }
     }
-    for (int j = tid; j < d; j += T) { S.cv[j] = 0.0; S.xf[j] = 0.0; S.ray[j] = 0.0; }
-    for (int i = tid; i < r; i += T) S.lam[i] = 0.0;
-    team_sync<T>();
     if (!team_min_int<T>(uncrossed, S.red, tid)) { o.status = QPN_IB_EMPTY; return; }   // crossed bounds: no LP is started
     // (a) the feasibility solve
+    int it;
     o.lps = 1;
-    if (lp_setup<T>(P, S, tid)) { o.status = QPN_IB_EMPTY; return; }
-    int e, it;
-    double dirn;
-    int status = lp_loop<T>(P, S, tid, &it, &e, &dirn);
-    lp_point<T>(P, S, tid);
+    int status = lp_feasible<T>(P, S, tid, &it);
     o.iters = it;
-    if (status == QPN_LP_INFEASIBLE) {
-        o.status = lp_check<T>(P, S, status, e, dirn, tid) == QPN_LP_INFEASIBLE ? QPN_IB_EMPTY : QPN_IB_FAILURE;
+    if (status != QPN_LP_OPTIMAL) {
+        o.status = status == QPN_LP_INFEASIBLE ? QPN_IB_EMPTY : status == QPN_LP_ITER_LIMIT ? QPN_IB_ITER_LIMIT : QPN_IB_FAILURE;
         return;
     }
-    if (status != QPN_LP_OPTIMAL) { o.status = status == QPN_LP_ITER_LIMIT ? QPN_IB_ITER_LIMIT : QPN_IB_FAILURE; return; }
     // (b) the witnesses: a lane per row, A read in place
     double wlo[IB_NK], whi[IB_NK];
 #pragma unroll
@@ -667,27 +660,12 @@ template <int T> __device__ void ib_core(const IbArgs &a, const LpSlice &S, int 
             team_sync<T>();
             for (int j = tid; j < d; j += T) { const double v = P.Ab[(size_t)j * r + i]; S.cv[j] = side ? -v : v; }
             team_sync<T>();
-            // the cost row of c in the current dictionary (section 5g (e))
-            for (int j = tid; j < d; j += T) {
-                const double *col = S.Tm + (size_t)j * ld;
-                double acc = 0.0;
-                for (int k = 0; k < r; ++k) {
-                    const int id = S.rb[k];
-                    if (id < d) acc = acc + S.cv[id] * col[k];
-                }
-                if (S.cn[j] < d) acc = acc + S.cv[S.cn[j]];
-                S.Tm[(size_t)j * ld + r] = acc;
-            }
-            for (int j = tid; j < d; j += T) S.ray[j] = 0.0;
-            for (int k = tid; k < r; k += T) S.lam[k] = 0.0;
-            team_sync<T>();
+            double obj;
             ++o.lps;
-            status = lp_loop<T>(P, S, tid, &it, &e, &dirn);
-            const double obj = lp_point<T>(P, S, tid);
+            status = lp_resolve<T>(P, S, tid, &it, &obj);
             o.iters += it;
             if (status == QPN_LP_ITER_LIMIT) { o.status = QPN_IB_ITER_LIMIT; o.fail_row = i; return; }
-            if (status == QPN_LP_FAILURE || status == QPN_LP_INFEASIBLE) { o.status = QPN_IB_FAILURE; o.fail_row = i; return; }
-            if (lp_check<T>(P, S, status, e, dirn, tid) == QPN_LP_FAILURE) { o.status = QPN_IB_FAILURE; o.fail_row = i; return; }
+            if (status == QPN_LP_FAILURE) { o.status = QPN_IB_FAILURE; o.fail_row = i; return; }
             // (b) the rows at the new point: the check left A x in S.xb
 #pragma unroll
             for (int k = 0; k < IB_NK; ++k) {
@@ -742,20 +720,36 @@ template <int T> __device__ void ib_job(const IbArgs &a, int b, double *base, in
     }
 }
 
-__global__ __launch_bounds__(64 * LP_WAVES) void ib_wave_kernel(IbArgs a, size_t slice)
+// ---- the kernels and the launcher of every job kind ------------------------------------------------------------------------------
+// A job kind names its argument struct and runs job t of it with a team of T threads on the slice at base.
+struct LpJob {
+    using Args = LpArgs;
+    template <int T> static __device__ void run(const Args &a, int t, double *base, int tid) { lp_job<T>(a, t, base, tid); }
+};
+struct SubsetJob {
+    using Args = SubsetArgs;
+    template <int T> static __device__ void run(const Args &a, int t, double *base, int tid) { subset_job<T>(a, t, base, tid); }
+};
+struct IbJob {
+    using Args = IbArgs;
+    template <int T> static __device__ void run(const Args &a, int t, double *base, int tid) { ib_job<T>(a, t, base, tid); }
+};
+
+template <class Job> __global__ __launch_bounds__(64 * LP_WAVES) void lp_wave_kernel(typename Job::Args a, int32_t count, size_t slice)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char lp_lds[];
     const int w = threadIdx.x / 64;
-    const long long b = (long long)blockIdx.x * LP_WAVES + w;
-    if (b >= a.polys) return;                             // a whole wavefront leaves: the others never wait for it
-    ib_job<64>(a, (int)b, reinterpret_cast<double *>(lp_lds + (size_t)w * slice), threadIdx.x % 64);
+    const long long t = (long long)blockIdx.x * LP_WAVES + w;
+    if (t >= count) return;                               // a whole wavefront leaves: the others never wait for it
+    Job::template run<64>(a, (int)t, reinterpret_cast<double *>(lp_lds + (size_t)w * slice), threadIdx.x % 64);
 }
 
-template <bool LDS> __global__ __launch_bounds__(LP_GROUP) void ib_group_kernel(IbArgs a, int32_t first, unsigned char *gws, size_t slice)
+template <class Job, bool LDS>
+__global__ __launch_bounds__(LP_GROUP) void lp_group_kernel(typename Job::Args a, int32_t first, unsigned char *gws, size_t slice)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char lp_lds[];
     unsigned char *base = LDS ? lp_lds : gws + (size_t)blockIdx.x * slice;
-    ib_job<LP_GROUP>(a, first + (int)blockIdx.x, reinterpret_cast<double *>(base), threadIdx.x);
+    Job::template run<LP_GROUP>(a, first + (int)blockIdx.x, reinterpret_cast<double *>(base), threadIdx.x);
 }
 
 int32_t lp_chunk(int32_t jobs, int32_t r, int32_t d)
@@ -763,6 +757,39 @@ int32_t lp_chunk(int32_t jobs, int32_t r, int32_t d)
     size_t c = LP_WS_CHUNK_BYTES / lp_slice_bytes(r, d);
     if (c < 1) c = 1;
     return (int32_t)(c < (size_t)jobs ? c : (size_t)jobs);
+}
+
+// `count` jobs of one kind over LPs of r rows in d variables, by the class of their slice; gws: qpn_lp_workspace_bytes(count, r, d)
+template <class Job> hipError_t lp_launch(const typename Job::Args &a, int32_t count, int32_t r, int32_t d, void *gws, hipStream_t s)
+{
+    if (count <= 0) return hipSuccess;
+    const int cls = qpn_lp_class(r, d);
+    const size_t slice = lp_slice_bytes(r, d);
+    if (cls < 2) {                                        // (4 slices of 16 KiB: at the 64 KiB default, raised for clarity)
+        static QpnLdsLimits lds_limits;
+        if (const hipError_t e = lds_limits.raise({{lp_wave_kernel<Job>, (int)(LP_WAVE_SLICE_MAX * LP_WAVES)},
+                                                   {lp_group_kernel<Job, true>, (int)LP_GROUP_SLICE_MAX}});
+            e != hipSuccess)
+            return e;
+    }
+    if (cls == 0) {
+        const unsigned grid = (unsigned)((count + LP_WAVES - 1) / LP_WAVES);
+        hipLaunchKernelGGL(lp_wave_kernel<Job>, dim3(grid), dim3(64 * LP_WAVES), slice * LP_WAVES, s, a, count, slice);
+        return hipGetLastError();
+    }
+    if (cls == 1) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(lp_group_kernel<Job, true>), dim3((unsigned)count), dim3(LP_GROUP), slice, s, a, 0,
+                           static_cast<unsigned char *>(nullptr), slice);
+        return hipGetLastError();
+    }
+    const int32_t chunk = lp_chunk(count, r, d);
+    for (int32_t first = 0; first < count; first += chunk) {
+        const int32_t n = count - first < chunk ? count - first : chunk;
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(lp_group_kernel<Job, false>), dim3((unsigned)n), dim3(LP_GROUP), 0, s, a, first,
+                           static_cast<unsigned char *>(gws), slice);
+        if (const hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    }
+    return hipSuccess;
 }
 
 } // namespace
@@ -780,89 +807,6 @@ size_t qpn_lp_workspace_bytes(int32_t jobs, int32_t r, int32_t d)
     return (size_t)lp_chunk(jobs, r, d) * lp_slice_bytes(r, d);
 }
 
-hipError_t qpn_launch_solve_lps(const LpArgs &a, void *gws, hipStream_t s)
-{
-    if (a.jobs <= 0) return hipSuccess;
-    const int cls = qpn_lp_class(a.r, a.d);
-    const size_t slice = lp_slice_bytes(a.r, a.d);
-    if (cls == 0) {
-        static QpnLdsLimits lds_limits;                  // (4 slices of 16 KiB: at the 64 KiB default, raised for clarity)
-        if (const hipError_t e = lds_limits.raise({{lp_wave_kernel, (int)(LP_WAVE_SLICE_MAX * LP_WAVES)}}); e != hipSuccess) return e;
-        const unsigned grid = (unsigned)((a.jobs + LP_WAVES - 1) / LP_WAVES);
-        hipLaunchKernelGGL(lp_wave_kernel, dim3(grid), dim3(64 * LP_WAVES), slice * LP_WAVES, s, a, slice);
-        return hipGetLastError();
-    }
-    if (cls == 1) {
-        static QpnLdsLimits lds_limits;
-        if (const hipError_t e = lds_limits.raise({{lp_group_kernel<true>, (int)LP_GROUP_SLICE_MAX}}); e != hipSuccess) return e;
-        hipLaunchKernelGGL(lp_group_kernel<true>, dim3((unsigned)a.jobs), dim3(LP_GROUP), slice, s, a, 0, static_cast<unsigned char *>(nullptr),
-                           slice);
-        return hipGetLastError();
-    }
-    const int32_t chunk = lp_chunk(a.jobs, a.r, a.d);
-    for (int32_t first = 0; first < a.jobs; first += chunk) {
-        const int32_t count = a.jobs - first < chunk ? a.jobs - first : chunk;
-        hipLaunchKernelGGL(lp_group_kernel<false>, dim3((unsigned)count), dim3(LP_GROUP), 0, s, a, first, static_cast<unsigned char *>(gws),
-                           slice);
-        if (const hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-    }
-    return hipSuccess;
-}
-
-hipError_t qpn_launch_issubset_pairs(const SubsetArgs &a, void *gws, hipStream_t s)
-{
-    if (a.pairs <= 0) return hipSuccess;
-    const int cls = qpn_lp_class(a.r1, a.d);
-    const size_t slice = lp_slice_bytes(a.r1, a.d);
-    if (cls == 0) {
-        static QpnLdsLimits lds_limits;
-        if (const hipError_t e = lds_limits.raise({{subset_wave_kernel, (int)(LP_WAVE_SLICE_MAX * LP_WAVES)}}); e != hipSuccess) return e;
-        const unsigned grid = (unsigned)((a.pairs + LP_WAVES - 1) / LP_WAVES);
-        hipLaunchKernelGGL(subset_wave_kernel, dim3(grid), dim3(64 * LP_WAVES), slice * LP_WAVES, s, a, slice);
-        return hipGetLastError();
-    }
-    if (cls == 1) {
-        static QpnLdsLimits lds_limits;
-        if (const hipError_t e = lds_limits.raise({{subset_group_kernel<true>, (int)LP_GROUP_SLICE_MAX}}); e != hipSuccess) return e;
-        hipLaunchKernelGGL(subset_group_kernel<true>, dim3((unsigned)a.pairs), dim3(LP_GROUP), slice, s, a, 0,
-                           static_cast<unsigned char *>(nullptr), slice);
-        return hipGetLastError();
-    }
-    const int32_t chunk = lp_chunk(a.pairs, a.r1, a.d);
-    for (int32_t first = 0; first < a.pairs; first += chunk) {
-        const int32_t count = a.pairs - first < chunk ? a.pairs - first : chunk;
-        hipLaunchKernelGGL(subset_group_kernel<false>, dim3((unsigned)count), dim3(LP_GROUP), 0, s, a, first, static_cast<unsigned char *>(gws),
-                           slice);
-        if (const hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-    }
-    return hipSuccess;
-}
-
-hipError_t qpn_launch_implicit_bounds(const IbArgs &a, void *gws, hipStream_t s)
-{
-    if (a.polys <= 0) return hipSuccess;
-    const int cls = qpn_lp_class(a.r, a.d);
-    const size_t slice = lp_slice_bytes(a.r, a.d);
-    if (cls == 0) {
-        static QpnLdsLimits lds_limits;
-        if (const hipError_t e = lds_limits.raise({{ib_wave_kernel, (int)(LP_WAVE_SLICE_MAX * LP_WAVES)}}); e != hipSuccess) return e;
-        const unsigned grid = (unsigned)((a.polys + LP_WAVES - 1) / LP_WAVES);
-        hipLaunchKernelGGL(ib_wave_kernel, dim3(grid), dim3(64 * LP_WAVES), slice * LP_WAVES, s, a, slice);
-        return hipGetLastError();
-    }
-    if (cls == 1) {
-        static QpnLdsLimits lds_limits;
-        if (const hipError_t e = lds_limits.raise({{ib_group_kernel<true>, (int)LP_GROUP_SLICE_MAX}}); e != hipSuccess) return e;
-        hipLaunchKernelGGL(ib_group_kernel<true>, dim3((unsigned)a.polys), dim3(LP_GROUP), slice, s, a, 0, static_cast<unsigned char *>(nullptr),
-                           slice);
-        return hipGetLastError();
-    }
-    const int32_t chunk = lp_chunk(a.polys, a.r, a.d);
-    for (int32_t first = 0; first < a.polys; first += chunk) {
-        const int32_t count = a.polys - first < chunk ? a.polys - first : chunk;
-        hipLaunchKernelGGL(ib_group_kernel<false>, dim3((unsigned)count), dim3(LP_GROUP), 0, s, a, first, static_cast<unsigned char *>(gws),
-                           slice);
-        if (const hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-    }
-    return hipSuccess;
-}
+hipError_t qpn_launch_solve_lps(const LpArgs &a, void *gws, hipStream_t s) { return lp_launch<LpJob>(a, a.jobs, a.r, a.d, gws, s); }
+hipError_t qpn_launch_issubset_pairs(const SubsetArgs &a, void *gws, hipStream_t s) { return lp_launch<SubsetJob>(a, a.pairs, a.r1, a.d, gws, s); }
+hipError_t qpn_launch_implicit_bounds(const IbArgs &a, void *gws, hipStream_t s) { return lp_launch<IbJob>(a, a.polys, a.r, a.d, gws, s); }

@@ -647,6 +647,15 @@ class Engine:
         self.lib.qpn_lp_default_opts(C.byref(o))
         return o
 
+    def _lp_opts(self, opts):
+        """opts of an LP entry -- LpOpts, a dict of its fields over the defaults, or None -> LpOpts or None."""
+        if not isinstance(opts, dict):
+            return opts
+        o = self.default_lp_opts()
+        for k, v in opts.items():
+            setattr(o, k, v)
+        return o
+
     def lp_kernel_class(self, r, d):
         """Which kernel class takes LPs of r rows in d variables: 0 wavefront, 1 workgroup in LDS, 2 workgroup over the workspace,
         -1 beyond the limits (qpn_lp_kernel_class)."""
@@ -668,11 +677,7 @@ class Engine:
         if tuple(l.shape) != (polys, r) or tuple(u.shape) != (polys, r) or (cost is not None and tuple(cost.shape) != (jobs, d)) or (
                 cost is None and (tuple(obj_row.shape) != (jobs,) or tuple(obj_sign.shape) != (jobs,))):
             raise QpnError("solve_lps: inconsistent shapes")
-        if isinstance(opts, dict):
-            o = self.default_lp_opts()
-            for k, v in opts.items():
-                setattr(o, k, v)
-            opts = o
+        opts = self._lp_opts(opts)
         out = dict(status=self._alloc(dev, (jobs,), np.int32), x=self._alloc(dev, (jobs, d), np.float64), obj=self._alloc(dev, (jobs,), np.float64),
                    lam=self._alloc(dev, (jobs, r), np.float64), ray=self._alloc(dev, (jobs, d), np.float64), iters=self._alloc(dev, (jobs,), np.int32))
         self._call("qpn_solve_lps", polys, r, d, _ptr(Ac), _ptr(l), _ptr(u), jobs, _ptr(poly_of), _ptr(cost), _ptr(obj_row), _ptr(obj_sign),
@@ -695,11 +700,7 @@ class Engine:
         if d2 != d or tuple(l1.shape) != (B1, r1) or tuple(u1.shape) != (B1, r1) or tuple(l2.shape) != (B2, r2) or tuple(u2.shape) != (B2, r2) or (
                 tuple(pj.shape) != (pairs,)):
             raise QpnError("issubset_pairs: inconsistent shapes")
-        if isinstance(opts, dict):
-            o = self.default_lp_opts()
-            for k, v in opts.items():
-                setattr(o, k, v)
-            opts = o
+        opts = self._lp_opts(opts)
         out = dict(sub=self._alloc(dev, (pairs,), np.uint8), how=self._alloc(dev, (pairs,), np.int32), bound=self._alloc(dev, (pairs,), np.int32),
                    val=self._alloc(dev, (pairs,), np.float64), lps=self._alloc(dev, (pairs,), np.int32), iters=self._alloc(dev, (pairs,), np.int32))
         self._call("qpn_issubset_pairs", d, B1, r1, _ptr(A1c), _ptr(l1), _ptr(u1), B2, r2, _ptr(A2c), _ptr(l2), _ptr(u2), pairs, _ptr(pi),
@@ -719,11 +720,7 @@ class Engine:
         polys, d, r = (int(v) for v in Ac.shape)
         if tuple(l.shape) != (polys, r) or tuple(u.shape) != (polys, r):
             raise QpnError("implicit_bounds: inconsistent shapes")
-        if isinstance(opts, dict):
-            o = self.default_lp_opts()
-            for k, v in opts.items():
-                setattr(o, k, v)
-            opts = o
+        opts = self._lp_opts(opts)
         out = dict(status=self._alloc(dev, (polys,), np.int32), fail_row=self._alloc(dev, (polys,), np.int32),
                    eq=self._alloc(dev, (polys, r), np.uint8), vals=self._alloc(dev, (polys, r), np.float64),
                    how=self._alloc(dev, (polys, r), np.int32), lo=self._alloc(dev, (polys, r), np.float64),

@@ -1120,6 +1120,43 @@ def _lp_one(A, l, u, c, o):
     return (status if ok else LP_FAILURE), x, obj, lam, ray, S.iters
 
 
+def _lp_feasible(A, l, u, o):
+    """The feasibility solve of issubset_pairs_host (a) and implicit_bounds_host (a) (the kernel's lp_feasible): steps 1-8 with
+    c = 0.  An infeasible all-zero row, or an INFEASIBLE end whose Farkas certificate holds, is LP_INFEASIBLE; one whose
+    certificate fails LP_FAILURE.  -> (LP_OPTIMAL / LP_INFEASIBLE / LP_ITER_LIMIT / LP_FAILURE, S, x [d]); the steps in S.iters."""
+    zero = np.zeros(A.shape[1])
+    S = _lp_setup(A, l, u, zero, o)
+    if S.zbad is not None:
+        return LP_INFEASIBLE, S, zero
+    status = _lp_loop(S)
+    x, _ = _lp_point(S, zero)
+    if status == LP_INFEASIBLE:
+        return (LP_INFEASIBLE if _lp_check(S, status, zero, x)[0] else LP_FAILURE), S, x
+    return (status if status in (LP_OPTIMAL, LP_ITER_LIMIT) else LP_FAILURE), S, x
+
+
+def _lp_resolve(S, c):
+    """The solve of objective c from the basis the previous solve over the polyhedron left (the kernel's lp_resolve): the cost
+    row of c in the current dictionary (issubset_pairs_host (e)), the loop with fresh step and degeneracy counters, the point and
+    step 9's check.  -> (LP_OPTIMAL or LP_UNBOUNDED, certified / LP_ITER_LIMIT / LP_FAILURE: a FAILURE of the loop, an INFEASIBLE
+    end, a certificate that fails; x [d]; obj = c'x); the steps in S.iters."""
+    T, rb, cn, r, d = S.T, S.rb, S.cn, S.r, S.d
+    with np.errstate(all="ignore"):
+        row = np.zeros(d)
+        for i in range(r):
+            if rb[i] < d:
+                row = row + c[rb[i]] * T[i, :]
+        for j in range(d):
+            if cn[j] < d:
+                row[j] = row[j] + c[cn[j]]
+        T[r] = row
+    status = _lp_loop(S)
+    x, obj = _lp_point(S, c)
+    if status == LP_INFEASIBLE or (status in (LP_OPTIMAL, LP_UNBOUNDED) and not _lp_check(S, status, c, x)[0]):
+        status = LP_FAILURE
+    return status, x, obj
+
+
 def solve_lps_host(Ac, l, u, poly_of, cost=None, obj_row=None, obj_sign=None, opts=None):
     """The numpy twin of Engine.solve_lps (qpn_solve_lps), the normative statement of the method: the kernel does the same
     operations in the same order (every sum over the ascending index as acc = acc + a * b, no contraction), so every output is
@@ -1157,19 +1194,10 @@ def _subset_one(A1, l1, u1, A2, l2, u2, tol, o):
     -> (how, bound, val, lps, iters)."""
     d = A1.shape[1]
     # (a) the feasibility solve: steps 1-8 with c = 0
-    zero = np.zeros(d)
-    S = _lp_setup(A1, l1, u1, zero, o)
-    if S.zbad is not None:
-        return SUBSET_EMPTY, -1, 0.0, 1, 0
-    status = _lp_loop(S)
-    x, _ = _lp_point(S, zero)
-    iters = S.iters
-    if status == LP_INFEASIBLE:
-        ok, _, _ = _lp_check(S, status, zero, x)
-        return (SUBSET_EMPTY if ok else SUBSET_FAILURE), -1, 0.0, 1, iters
+    status, S, x = _lp_feasible(A1, l1, u1, o)
+    lps, iters = 1, S.iters
     if status != LP_OPTIMAL:
-        return (SUBSET_ITER_LIMIT if status == LP_ITER_LIMIT else SUBSET_FAILURE), -1, 0.0, 1, iters
-    lps = 1
+        return {LP_INFEASIBLE: SUBSET_EMPTY, LP_ITER_LIMIT: SUBSET_ITER_LIMIT}.get(status, SUBSET_FAILURE), -1, 0.0, lps, iters
     with np.errstate(all="ignore"):
         for i in range(A2.shape[0]):                        # (b) the bounds in order, the lower before the upper
             fl, fu = bool(np.abs(l2[i]) < INF), bool(np.abs(u2[i]) < INF)
@@ -1198,27 +1226,13 @@ def _subset_one(A1, l1, u1, A2, l2, u2, tol, o):
                     v = v + c[k] * x[k]
                 if v < beta - tol:
                     return SUBSET_BY_POINT, b, v, lps, iters
-                # (e) the cost row of c in the current dictionary
-                T, rb, cn = S.T, S.rb, S.cn
-                row = np.zeros(d)
-                for ii in range(S.r):
-                    if rb[ii] < d:
-                        row = row + c[rb[ii]] * T[ii, :]
-                for j in range(d):
-                    if cn[j] < d:
-                        row[j] = row[j] + c[cn[j]]
-                T[S.r] = row
-                # (f) solve and decide
+                # (e) the cost row of c in the current dictionary, (f) solve and decide
                 lps += 1
-                status = _lp_loop(S)
-                x, obj = _lp_point(S, c)
+                status, x, obj = _lp_resolve(S, c)
                 iters += S.iters
                 if status == LP_ITER_LIMIT:
                     return SUBSET_ITER_LIMIT, b, 0.0, lps, iters
-                if status == LP_FAILURE or status == LP_INFEASIBLE:
-                    return SUBSET_FAILURE, b, 0.0, lps, iters
-                ok, _, _ = _lp_check(S, status, c, x)
-                if not ok:
+                if status == LP_FAILURE:
                     return SUBSET_FAILURE, b, 0.0, lps, iters
                 if status == LP_UNBOUNDED:
                     return SUBSET_UNBOUNDED, b, 0.0, lps, iters
@@ -1232,13 +1246,14 @@ def issubset_pairs_host(A1c, l1, u1, A2c, l2, u2, pi, pj, tol=1e-6, opts=None):
     kernel is bit-equal to it.  Pair q asks whether first piece pi[q] ⊆ second piece pj[q].  A1c [B1, d, r1], A2c [B2, d, r2]
     (ABI layout), l1, u1 [B1, r1], l2, u2 [B2, r2] (+-inf allowed).
 
-    (a) solve_lps_host's steps 1-8 on P1 with c = 0 (the crash and phase 1, once per pair); an INFEASIBLE end whose Farkas
+    (a) solve_lps_host's steps 1-8 on P1 with c = 0 (the crash and phase 1, once per pair; _lp_feasible); an INFEASIBLE end whose Farkas
     certificate holds is EMPTY (sub = 1, the convention of issubset_batch), otherwise FAILURE.  (b) the rows of P2 ascending, the
     lower bound (c = +a, beta = l2) before the upper (c = -a, beta = -u2), non-finite bounds skipped.  (c) a bound is skipped
     when rows of P1 equal the row of P2 entry by entry (==, unscaled) and the largest of their l1 is >= l2 - tol (the smallest of
     their u1 is <= u2 + tol).  (d) v = c'x at the point the previous solve ended at: v < beta - tol is BY_POINT.  (e) the cost
     row of c in the current dictionary: column j, acc = 0, over the rows i ascending with an x basic acc = acc + c[rb[i]] * T[i, j],
-    then + c[cn[j]] when an x is nonbasic there.  (f) the loop with fresh step and degeneracy counters, step 9's check on P1:
+    then + c[cn[j]] when an x is nonbasic there.  (f) the loop with fresh step and degeneracy counters, step 9's check on P1
+    ((e) and (f) are _lp_resolve):
     OPTIMAL with obj < beta - tol is BY_OPTIMUM, a certified ray UNBOUNDED, a failed certificate or an INFEASIBLE end FAILURE,
     ITER_LIMIT / FAILURE themselves.  (g) no bound left: HOLDS.
     -> dict(sub [pairs] uint8, how [pairs] int32 (SUBSET_*), bound [pairs] int32 (2 i + side of the deciding bound, -1 without),
@@ -1290,18 +1305,10 @@ def _implicit_one(A, l, u, tol, flags, o):
         if np.any(~explicit & (l > u)):                     # crossed bounds: no LP is started
             return IB_EMPTY, -1, eq, vals, how, lo, hi, 0, 0
         # (a) the feasibility solve: steps 1-8 with c = 0
-        zero = np.zeros(d)
-        S = _lp_setup(A, l, u, zero, o)
-        if S.zbad is not None:
-            return IB_EMPTY, -1, eq, vals, how, lo, hi, 1, 0
-        status = _lp_loop(S)
-        x, _ = _lp_point(S, zero)
+        status, S, x = _lp_feasible(A, l, u, o)
         lps, iters = 1, S.iters
-        if status == LP_INFEASIBLE:
-            ok, _, _ = _lp_check(S, status, zero, x)
-            return (IB_EMPTY if ok else IB_FAILURE), -1, eq, vals, how, lo, hi, lps, iters
         if status != LP_OPTIMAL:
-            return (IB_ITER_LIMIT if status == LP_ITER_LIMIT else IB_FAILURE), -1, eq, vals, how, lo, hi, lps, iters
+            return {LP_INFEASIBLE: IB_EMPTY, LP_ITER_LIMIT: IB_ITER_LIMIT}.get(status, IB_FAILURE), -1, eq, vals, how, lo, hi, lps, iters
 
         def rows_at(x):                                     # A x on the unscaled rows, columns ascending
             s = np.zeros(r)
@@ -1322,26 +1329,12 @@ def _implicit_one(A, l, u, tol, flags, o):
             decided = False
             for side in (0, 1):
                 c = A[i].copy() if side == 0 else -A[i]
-                # (§5g (e)) the cost row of c in the current dictionary
-                T, rb, cn = S.T, S.rb, S.cn
-                row = np.zeros(d)
-                for ii in range(r):
-                    if rb[ii] < d:
-                        row = row + c[rb[ii]] * T[ii, :]
-                for j in range(d):
-                    if cn[j] < d:
-                        row[j] = row[j] + c[cn[j]]
-                T[r] = row
                 lps += 1
-                status = _lp_loop(S)
-                x, obj = _lp_point(S, c)
+                status, x, obj = _lp_resolve(S, c)          # (the cost row of c in the current dictionary as in §5g (e))
                 iters += S.iters
                 if status == LP_ITER_LIMIT:
                     return IB_ITER_LIMIT, i, eq, vals, how, lo, hi, lps, iters
-                if status == LP_FAILURE or status == LP_INFEASIBLE:
-                    return IB_FAILURE, i, eq, vals, how, lo, hi, lps, iters
-                ok, _, _ = _lp_check(S, status, c, x)
-                if not ok:
+                if status == LP_FAILURE:
                     return IB_FAILURE, i, eq, vals, how, lo, hi, lps, iters
                 s = rows_at(x)
                 wlo = np.where(s < wlo, s, wlo); whi = np.where(s > whi, s, whi)
@@ -1372,13 +1365,13 @@ def implicit_bounds_host(Ac, l, u, tol=1e-4, all_extremes=False, opts=None):
 
     (0) A row with |l - u| <= tol or l == u is EXPLICIT: eq = 1, val = 0.5 (l + u); no LP takes it as objective.  Another row
     with l > u makes the polyhedron EMPTY before any LP (lps = 0: the simplex keeps a nonbasic row at one of its bounds and would
-    not see that they cross).  (a) solve_lps_host's steps 1-8 with c = 0 (the crash and phase 1, once): an infeasible all-zero row, or an INFEASIBLE end whose
+    not see that they cross).  (a) solve_lps_host's steps 1-8 with c = 0 (the crash and phase 1, once; _lp_feasible): an infeasible all-zero row, or an INFEASIBLE end whose
     Farkas certificate holds, is EMPTY, a certificate that fails FAILURE, ITER_LIMIT itself; the polyhedron stops there, its other
     rows keep eq = 0, val = +inf, UNDECIDED.  (b) witnesses: s = A x at the end point on the unscaled rows, columns ascending
     (acc = acc + a * x); wlo = whi = s, and after every later solve whose certificate holds wlo = s where s < wlo, whi = s where
     s > whi.  (c) the rows r - 1 ... 0 that are not explicit: whi - wlo > tol is BY_POINTS without an LP; otherwise the minimum, c =
     +a_i from the current basis (the cost row as in issubset_pairs_host (e), fresh step and degeneracy counters, the loop, the
-    point and step 9's check): a certified ray gives lo = -inf, UNBOUNDED; an optimum lo = obj, and whi - lo > tol is BY_POINTS;
+    point and step 9's check: _lp_resolve): a certified ray gives lo = -inf, UNBOUNDED; an optimum lo = obj, and whi - lo > tol is BY_POINTS;
     then the maximum with c = -a_i: hi = -obj or +inf.  eq = lo, hi finite and |lo - hi| <= tol: val = 0.5 (hi + lo), IMPLICIT;
     else BY_EXTREMES, or UNBOUNDED when one of the two is infinite.  ITER_LIMIT, an INFEASIBLE end or a failed certificate in one
     of these solves ends the polyhedron with that status and fail_row = i.  all_extremes (QPN_IB_ALL_EXTREMES): no BY_POINTS and

@@ -96,6 +96,33 @@ def test_class_boundaries_equal_the_twin_bit_for_bit(engine, which):
                                     {k: v[t] for k, v in want.items()})
 
 
+def test_workspace_class_runs_a_second_chunk(engine):
+    """More jobs of the workspace class than one chunk of the workspace holds: a class-2 slice is larger than 156 KiB and a chunk is
+    256 MiB, so 1685 jobs take at least two launches of the one launcher all three entries share (`first` > 0 in the second).  One
+    polyhedron, six distinct objectives in turn, cut off after three steps: the twin solves six LPs, every job equals its own."""
+    import torch
+    from qpn_amd import polyhedra
+    from qpn_amd.engine import colmajor
+    r, d = _class_shapes(engine)[2]
+    jobs = (256 << 20) // (156 << 10) + 5
+    assert engine.lp_kernel_class(r, 128) == 2 and d == 128 and jobs == 1685
+    A, l, u = lp_cases.bounded_batch(31, 1, r, d)
+    Ac = colmajor(A)
+    t = np.arange(jobs)
+    poly_of = np.zeros(jobs, np.int32); obj_row = (t % 3).astype(np.int32); obj_sign = np.where(t % 6 < 3, 1, -1).astype(np.int32)
+    opts = dict(max_iters=3)
+    six = polyhedra.solve_lps_host(Ac, l, u, poly_of[:6], obj_row=obj_row[:6], obj_sign=obj_sign[:6], opts=opts)
+    assert np.all(six["iters"] == 3) and len(set(six["obj"].tolist())) == 6
+    want = {k: np.ascontiguousarray(v[t % 6]) for k, v in six.items()}
+    _same_bits(engine.solve_lps(Ac, l, u, poly_of, obj_row=obj_row, obj_sign=obj_sign, opts=opts), want, "host mode")
+    dv = f"cuda:{engine.device}"
+    f = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64), device=dv)
+    i = lambda a: torch.as_tensor(a, device=dv)
+    got = engine.solve_lps(f(Ac), f(l), f(u), i(poly_of), obj_row=i(obj_row), obj_sign=i(obj_sign), opts=opts)
+    assert all(hasattr(v, "cpu") for v in got.values())
+    _same_bits(got, want, "device mode")
+
+
 def test_jobs_sharing_a_polyhedron(engine):
     """2 r jobs over the first polyhedron next to two over a second one: every job reads its polyhedron in place."""
     r, d = 11, 5

@@ -1,6 +1,9 @@
 """polyhedra.solve_lps_host -- the numpy twin of qpn_solve_lps and the normative statement of its method -- against an independent
 LP solver (scipy HiGHS) on a seeded family, with every certificate (multipliers, Farkas vector, ray) checked in plain numpy on the
 unscaled data, and on hand cases.  tests/lp_cases.py holds the family and the checks (the GPU suite shares them)."""
+import importlib.util
+import os
+
 import numpy as np
 import pytest
 from scipy.optimize import linprog
@@ -9,6 +12,7 @@ import qpn_amd  # noqa: F401
 from qpn_amd import polyhedra
 from qpn_amd.engine import colmajor
 
+import goldenio
 import lp_cases
 from lp_cases import FAILURE, INFEASIBLE, ITER_LIMIT, OPTIMAL, UNBOUNDED
 
@@ -122,6 +126,21 @@ def test_indices_out_of_range_answer_failure_and_zeros():
     got = polyhedra.solve_lps_host(colmajor(A), l, u, [0, 1, -1, 0], obj_row=[0, 0, 0, 2], obj_sign=[1, 1, 1, 1])
     assert list(got["status"]) == [OPTIMAL, FAILURE, FAILURE, FAILURE]
     assert not got["x"][1:].any() and not got["lam"][1:].any() and not got["iters"][1:].any()
+
+
+def test_the_twins_answer_what_the_recorded_commit_answered():
+    """tests/golden/lp_twin_record.json holds the digests of every output of solve_lps_host, issubset_pairs_host and
+    implicit_bounds_host on the families of the GPU suites, written by tests/golden/make_lp_twin_record.py from the commit before
+    the twins were last edited: the kernels are held bit-equal to the twins, this holds the twins bit-equal to themselves."""
+    spec = importlib.util.spec_from_file_location("make_lp_twin_record", os.path.join(goldenio.GOLD, "make_lp_twin_record.py"))
+    maker = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(maker)
+    want = goldenio.load("lp_twin_record.json")["cases"]
+    got = maker.record(polyhedra)
+    assert sorted(got) == sorted(want) and len(want) == 40
+    for name in sorted(want):
+        assert got[name]["histograms"] == want[name]["histograms"], name
+        assert got[name]["outputs"] == want[name]["outputs"], name
 
 
 # ---- the host functions on the LP route (an oracle engine that also has the twin as solve_lps) against the node-AVI route --------

@@ -1,12 +1,13 @@
 #!/usr/bin/env python3
 """Compiler resource table of every kernel in csrc/ (profiles/rNN_kernel_resources.md): compiles each translation unit with the
 flags of csrc/build.sh + -Rpass-analysis=kernel-resource-usage (objects go to a scratch directory, the in-tree build is not
-touched) and prints the markdown table.  Usage: python tools/kernel_resources.py > profiles/r03_kernel_resources.md"""
+touched) and prints the markdown table.  Usage: python tools/kernel_resources.py [unit ...] > profiles/r03_kernel_resources.md
+(units: translation units without the suffix, e.g. qpn_lp; none: all of them)"""
 import os, re, subprocess, sys, tempfile
 from concurrent.futures import ThreadPoolExecutor
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "quadraticprogramnetworks.jl_amd", "csrc")
-units = sorted(f[:-4] for f in os.listdir(SRC) if f.endswith(".hip"))
+units = sorted(f[:-4] for f in os.listdir(SRC) if f.endswith(".hip") and (len(sys.argv) == 1 or f[:-4] in sys.argv[1:]))
 tmp = tempfile.mkdtemp()
 
 
@@ -37,13 +38,13 @@ with ThreadPoolExecutor(6) as ex:
 names = demangle([r["name"] for r in rows])
 print("Compiler resource usage, gfx950, `hipcc -O3 -Rpass-analysis=kernel-resource-usage` (round 3, the flags of csrc/build.sh;\n"
       "`tools/kernel_resources.py`).  Dynamic LDS is set at launch and not in this table.\n")
-print("| kernel (file) | VGPRs | scratch B/lane | SGPR spills | VGPR spills | waves/SIMD | static LDS B |")
-print("|---|---|---|---|---|---|---|")
+print("| kernel (file) | SGPRs | VGPRs | AGPRs | scratch B/lane | SGPR spills | VGPR spills | waves/SIMD | static LDS B |")
+print("|---|---|---|---|---|---|---|---|---|")
 seen = set()
 for r, nm in sorted(zip(rows, names), key=lambda t: (t[0]["unit"], t[1])):
     key = (r["unit"], nm)
     if key in seen:
         continue
     seen.add(key)
-    print(f"| `{nm}` ({r['unit']}.hip) | {r.get('VGPRs', '')} | {r.get('ScratchSize', '')} | {r.get('SGPRs Spill', '')} | {r.get('VGPRs Spill', '')} | "
-          f"{r.get('Occupancy', '')} | {r.get('LDS Size', '')} |")
+    print(f"| `{nm}` ({r['unit']}.hip) | {r.get('TotalSGPRs', '')} | {r.get('VGPRs', '')} | {r.get('AGPRs', '')} | {r.get('ScratchSize', '')} | "
+          f"{r.get('SGPRs Spill', '')} | {r.get('VGPRs Spill', '')} | {r.get('Occupancy', '')} | {r.get('LDS Size', '')} |")
