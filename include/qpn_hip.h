@@ -484,11 +484,17 @@ int qpn_members_outside(qpn_ctx *ctx, int32_t pairs, int32_t d, int32_t rj, cons
  *   status [jobs] int32 (QPN_LP_*), x [jobs][d] (the optimum; for UNBOUNDED the feasible point the ray starts from; otherwise
  *   the point reached), obj [jobs] = c'x on the unscaled data, iters [jobs] int32 (flips and pivots after the crash),
  *   lambda [jobs][r]: OPTIMAL: c = A'lambda, + at the lower bound, - at the upper (the convention of qpn_verify_nodes);
- *     INFEASIBLE: a Farkas vector y, A'y = 0 and sum(y_i > 0 ? y_i u_i : y_i l_i) < 0;  zeros otherwise,
+ *     INFEASIBLE: a Farkas vector y, A'y = 0 and sum(y_i > 0 ? y_i u_i : y_i l_i) < 0 by the margin of step 9;  zeros otherwise
+ *     (ITER_LIMIT and every FAILURE, whatever produced it),
  *   ray [jobs][d]: UNBOUNDED: c'ray < 0, (A ray)_i >= 0 where l_i is finite, <= 0 where u_i is finite;  zeros otherwise.
  * Method (polyhedra.solve_lps_host is its numpy twin and the normative statement; every output is bit-equal to it: each sum runs
  * over the ascending index as acc = acc + a * b, no contraction): bounded-variable primal simplex on the row-activity form, x
- * free, s = A x in [l, u].  (1) rows and their bounds scaled by 1 / max|a_i|; an all-zero row with l_i > 0 or u_i < 0 makes the
+ * free, s = A x in [l, u].  (0) data screen: an entry of A or c that is not finite, a bound that is not a number, l_i = +inf or
+ * u_i = -inf makes the job QPN_LP_FAILURE at 0 steps with zeros (the comparisons of the method are not defined on such data).
+ * The screen reads the polyhedron and qpn_solve_lps' own c.  The objective of a warm solve (qpn_issubset_pairs (f): a row of P2)
+ * passes no screen: a non-finite entry there makes every comparison of the pricing false, the loop ends at once, the check of step
+ * 9 fails before and after step 10's rebuild, and that solve is QPN_LP_FAILURE.
+ * (1) rows and their bounds scaled by 1 / max|a_i|; an all-zero row with l_i > 0 or u_i < 0 makes the
  * job INFEASIBLE (Farkas vector -+e_i), otherwise it is inert.  (2) dictionary basic = T nonbasic, r x d, plus a cost row; ids
  * x_j = j, s_i = d + i; start basic = s, T = A, cost row = c.  (3) crash, columns ascending: pivot on the largest |T_ij| among rows
  * still holding an s (2^-30 relative band, lowest row); a column whose best entry is <= piv_tol stays nonbasic, free, at 0; a
@@ -503,8 +509,16 @@ int qpn_members_outside(qpn_ctx *ctx, int32_t pairs, int32_t d, int32_t rj, cons
  * without entering variable: INFEASIBLE; phase 2 without blocking candidate: UNBOUNDED; phase 2 without entering variable:
  * OPTIMAL; a further step due after max_iters: ITER_LIMIT.  A claimed outcome is checked on the unscaled rows at check_tol --
  * primal feasibility within check_tol * max(1, |bound|); |c - A'lambda| <= check_tol * max(1, |c_k|), a multiplier beyond +-check_tol only at its
- * bound; |A'y| <= check_tol * max(1, |y|_inf) and the Farkas sum < 0; c'ray < 0 and the row conditions within check_tol *
- * max(1, |ray|_inf) * max|a_i| -- and becomes QPN_LP_FAILURE when it fails them.
+ * bound; |A'y| <= check_tol * max(1, |y|_inf) and the Farkas sum < -sum_i |y_i| check_tol max(1, |bound_i|), bound_i the bound the
+ * sum takes of row i (infeasible even with every bound relaxed by the tolerance primal feasibility is judged at: a residual of A'y
+ * tolerated at check_tol |y|_inf makes a sum nearer to zero prove nothing); c'ray < 0 and the row conditions within check_tol *
+ * max(1, |ray|_inf) * max|a_i|.  (10) an end that is not certified -- a claimed outcome that fails its check, phase 1 without a
+ * blocking candidate, and in a warm solve (qpn_issubset_pairs (f), qpn_implicit_bounds (c)) an INFEASIBLE end -- has met the drift of
+ * a dictionary updated in place: the dictionary of the current basis is rebuilt from the scaled rows, T = A, cost row = c, then for
+ * the columns j ascending whose x is basic the pivot of step 3 among the rows whose s is nonbasic in that basis and still basic here
+ * (at most d pivots; the nonbasic s keep their values), and the loop runs once more, the step count going on towards max_iters.
+ * What that second loop ends with stands; not certified again, or a rebuild pivot <= piv_tol, is QPN_LP_FAILURE.  A loop that ends
+ * certified never rebuilds.
  * opts == NULL: the defaults.  max_iters <= 0: 50 (r + d) + 100.  Host poly_of / obj_row out of range: QPN_ERR_ARG; device ones:
  * that job answers QPN_LP_FAILURE with zeros and reads nothing.  1 <= d <= 256, 1 <= r <= 1024 (QPN_ERR_SIZE beyond).
  * qpn_lp_kernel_class(r, d): 0 = one wavefront per job, dictionary in LDS, four jobs per workgroup; 1 = one workgroup of 256 per
@@ -533,15 +547,15 @@ int qpn_solve_lps(qpn_ctx *ctx, int32_t polys, int32_t r, int32_t d, const doubl
  *   lps [pairs] int32: simplex solves started, the feasibility solve counted;  iters [pairs] int32: all their steps.
  * Method (polyhedra.issubset_pairs_host is its numpy twin and the normative statement; every output is bit-equal to it, by the
  * discipline of qpn_solve_lps, whose set-up, loop and check it runs):  (a) steps 1-8 of qpn_solve_lps on P1 with c = 0: the crash
- * and phase 1 once per pair; an INFEASIBLE end whose Farkas certificate holds is EMPTY, otherwise FAILURE; ITER_LIMIT and FAILURE
- * pass through.  (b) the rows i of P2 ascending, the lower bound (c = +a2_i, beta = l2[i]) before the upper (c = -a2_i, beta =
+ * and phase 1 once per pair; an INFEASIBLE end whose Farkas certificate holds is EMPTY, otherwise (after step 10's rebuild and
+ * second loop) FAILURE; ITER_LIMIT and FAILURE pass through.  (b) the rows i of P2 ascending, the lower bound (c = +a2_i, beta = l2[i]) before the upper (c = -a2_i, beta =
  * -u2[i]); a non-finite bound is skipped.  (c) own-row skip: when rows k of P1 equal row i of P2 entry by entry (IEEE ==, unscaled)
  * and max l1[k] >= l2[i] - tol (min u1[k] <= u2[i] + tol) over them, the bound holds on all of P1 and needs no work.  (d) point
  * test: v = c'x at the point the previous solve ended at; v < beta - tol is BY_POINT.  (e) no second crash: the cost row of c in the
  * current dictionary, column j: acc = 0; rows i ascending that hold an x: acc = acc + c[id] * T[i][j]; then + c[id] when column j
- * holds an x.  (f) the loop with fresh step and degeneracy counters (max_iters per objective), then the check of step 9 on P1:
- * OPTIMAL with obj < beta - tol is BY_OPTIMUM, otherwise the next bound; a certified ray is UNBOUNDED; a certificate that fails, or
- * an INFEASIBLE end, is FAILURE.  (g) no bound left: HOLDS.
+ * holds an x.  (f) the loop with fresh step and degeneracy counters (max_iters per objective), then the check of step 9 on P1 and,
+ * where the end is not certified, step 10: OPTIMAL with obj < beta - tol is BY_OPTIMUM, otherwise the next bound; a certified ray is
+ * UNBOUNDED; a certificate that fails, or an INFEASIBLE end, after the rebuild too, is FAILURE.  (g) no bound left: HOLDS.
  * Kernel classes are those of qpn_lp_kernel_class(r1, d); nothing of P2 is copied.  Host pi / pj out of range: QPN_ERR_ARG; device
  * ones: that pair answers sub = 0, QPN_SUBSET_FAILURE, bound = -1, zeros elsewhere and reads nothing.  1 <= d <= 256, 1 <= r1, r2
  * <= 1024 (QPN_ERR_SIZE beyond).  pairs == 0 succeeds. */
@@ -571,15 +585,15 @@ int qpn_issubset_pairs(qpn_ctx *ctx, int32_t d, int32_t B1, int32_t r1, const do
  * val = 0.5 (l + u); no LP takes it as objective.  Another row with l > u makes the polyhedron EMPTY before any LP (lps = 0).
  * (a) steps 1-8 of qpn_solve_lps with c = 0: the crash and phase 1 once per
  * polyhedron; an infeasible all-zero row, or an INFEASIBLE end whose Farkas certificate holds, is EMPTY, a certificate that fails
- * FAILURE, ITER_LIMIT itself; the polyhedron stops there and its other rows keep eq = 0, val = +inf, UNDECIDED.  (b) witnesses: s =
+ * (after step 10's rebuild and second loop) FAILURE, ITER_LIMIT itself; the polyhedron stops there and its other rows keep eq = 0, val = +inf, UNDECIDED.  (b) witnesses: s =
  * A x at the end point on the unscaled rows, columns ascending (acc = acc + a * x); wlo = whi = s, and after every later solve
  * whose certificate holds wlo = s where s < wlo, whi = s where s > whi.  (c) the rows r - 1 ... 0 that are not explicit: whi - wlo
  * > tol is BY_POINTS without an LP; otherwise the minimum, c = +a_i from the current basis (the cost row as in qpn_issubset_pairs
  * (e), fresh step and degeneracy counters, max_iters per objective, the loop, the point, the check of step 9): a certified ray
  * gives lo = -inf, UNBOUNDED; an optimum lo = obj, and whi - lo > tol is BY_POINTS; then the maximum with c = -a_i: hi = -obj or
  * +inf.  eq = lo, hi finite and |lo - hi| <= tol: val = 0.5 (hi + lo), IMPLICIT; else BY_EXTREMES, or UNBOUNDED when one of the two
- * is infinite.  ITER_LIMIT, an INFEASIBLE end or a failed certificate in one of these solves ends the polyhedron with that status
- * and fail_row = the row.  flags & QPN_IB_ALL_EXTREMES: no BY_POINTS and no early exit after an unbounded minimum; every row that
+ * is infinite.  ITER_LIMIT, or an INFEASIBLE end or a failed certificate that step 10's rebuild and second loop do not mend, in
+ * one of these solves ends the polyhedron with that status and fail_row = the row.  flags & QPN_IB_ALL_EXTREMES: no BY_POINTS and no early exit after an unbounded minimum; every row that
  * is not explicit gets both extremes and is decided by them alone.
  * Kernel classes are those of qpn_lp_kernel_class(r, d).  1 <= d <= 256, 1 <= r <= 1024 (QPN_ERR_SIZE beyond).  polys == 0 succeeds. */
 enum {

@@ -139,8 +139,10 @@ __device__ inline LpProb lp_prob(int r, int d, const double *Ab, const double *l
     return LpProb{r, d, Ab, lb, ub, t.piv_tol, t.feas_tol, t.opt_tol, t.check_tol, t.max_iters};
 }
 
-// Steps 1-4 with the objective in S.cv: scaling, the dictionary, the crash, the nonbasic values.  -> QPN_LP_INFEASIBLE when an
-// all-zero row outside its bounds settles the job (its unit Farkas vector in S.lam), 0 otherwise.
+// Steps 0-4 with the objective in S.cv: the data screen, scaling, the dictionary, the crash, the nonbasic values.
+// -> QPN_LP_FAILURE when the screen fails the job (an entry of A or c that is not finite, a bound that is not a number, l = +inf
+// or u = -inf; nothing is claimed, S.lam stays zero), QPN_LP_INFEASIBLE when an all-zero row outside its bounds settles it (its
+// unit Farkas vector in S.lam), 0 otherwise.
 template <int T> __device__ int lp_setup(const LpProb &P, const LpSlice &S, int tid)
 {
     const int r = P.r, d = P.d, ld = lp_ld(r);
@@ -150,11 +152,19 @@ template <int T> __device__ int lp_setup(const LpProb &P, const LpSlice &S, int 
     int *rb = S.rb, *cn = S.cn;
 
     // 1. row scaling, 2. the dictionary
-    for (int j = tid; j < d; j += T) { Tm[(size_t)j * ld + r] = S.cv[j]; cn[j] = j; S.xn[j] = 0.0; }
-    int zbad = INT_MAX;
+    int zbad = INT_MAX;                                   // -1: the data screen (0.) fails the job
+    for (int j = tid; j < d; j += T) {
+        if (!(fabs(S.cv[j]) < QINF)) zbad = -1;
+        Tm[(size_t)j * ld + r] = S.cv[j]; cn[j] = j; S.xn[j] = 0.0;
+    }
     for (int i = tid; i < r; i += T) {
         double m = 0.0;
-        for (int j = 0; j < d; ++j) m = fmax(m, fabs(Ab[(size_t)j * r + i]));
+        for (int j = 0; j < d; ++j) {
+            const double v = fabs(Ab[(size_t)j * r + i]);
+            if (!(v < QINF)) zbad = -1;
+            m = fmax(m, v);
+        }
+        if (!(lb[i] < QINF) || !(ub[i] > -QINF)) zbad = -1;
         if (m == 0.0 && (ub[i] < 0.0 || lb[i] > 0.0)) zbad = min(zbad, i);
         const double s = m > 0.0 ? 1.0 / m : 1.0;
         S.amx[i] = m; S.sc[i] = s; S.ls[i] = lb[i] * s; S.us[i] = ub[i] * s; rb[i] = d + i;
@@ -162,6 +172,7 @@ template <int T> __device__ int lp_setup(const LpProb &P, const LpSlice &S, int 
     }
     team_sync<T>();
     zbad = team_min_int<T>(zbad, red, tid);
+    if (zbad < 0) return QPN_LP_FAILURE;
     if (zbad < r) {                                       // an all-zero row outside its bounds: the unit Farkas vector
         if (tid == 0) S.lam[zbad] = ub[zbad] < 0.0 ? 1.0 : -1.0;
         team_sync<T>();
@@ -200,15 +211,17 @@ template <int T> __device__ int lp_setup(const LpProb &P, const LpSlice &S, int 
     return 0;
 }
 
-// Steps 5-8: the simplex loop from the slice's dictionary, with its own step and degeneracy counters.  -> status; the steps,
-// and the last entering column and its direction (the ray of an UNBOUNDED end).
-template <int T> __device__ int lp_loop(const LpProb &P, const LpSlice &S, int tid, int *iters_out, int *e_out, double *dirn_out)
+// Steps 5-8: the simplex loop from the slice's dictionary, with a fresh degeneracy counter and the step counter at iters0 (the
+// steps before a rebuild count against the same max_iters).  -> status; the steps, and the last entering column and its direction
+// (the ray of an UNBOUNDED end).
+template <int T>
+__device__ int lp_loop(const LpProb &P, const LpSlice &S, int tid, int iters0, int *iters_out, int *e_out, double *dirn_out)
 {
     const int r = P.r, d = P.d, ld = lp_ld(r);
     const double piv_tol = P.piv_tol, feas_tol = P.feas_tol, opt_tol = P.opt_tol;
     double *Tm = S.Tm, *red = S.red;
     int *rb = S.rb, *cn = S.cn;
-    int status = QPN_LP_FAILURE, iters = 0, degen = 0, e = -1;
+    int status = QPN_LP_FAILURE, iters = iters0, degen = 0, e = -1;
     double dirn = 0.0;
     for (;;) {
         // basic values, violations
@@ -382,12 +395,13 @@ template <int T> __device__ int lp_check(const LpProb &P, const LpSlice &S, int 
                 S.lam[k] = y * S.sc[k];
             }
         team_sync<T>();
-        double ymax = 0.0, bound = 0.0;
+        // the Farkas sum is negative by more than every bound relaxed by the tolerance primal feasibility is judged at accounts for
+        double ymax = 0.0, bound = 0.0, slack = 0.0;
         for (int i = 0; i < r; ++i) {
             const double y = S.lam[i];
             ymax = fmax(ymax, fabs(y));
-            if (y > 0.0) bound = bound + y * ub[i];
-            else if (y < 0.0) bound = bound + y * lb[i];
+            if (y > 0.0) { bound = bound + y * ub[i]; slack = slack + y * (ct * fmax(1.0, fabs(ub[i]))); }
+            else if (y < 0.0) { bound = bound + y * lb[i]; slack = slack - y * (ct * fmax(1.0, fabs(lb[i]))); }
         }
         ymax = fmax(1.0, ymax);
         for (int k = tid; k < d; k += T) {
@@ -395,16 +409,90 @@ template <int T> __device__ int lp_check(const LpProb &P, const LpSlice &S, int 
             for (int i = 0; i < r; ++i) acc = acc + Ab[(size_t)k * r + i] * S.lam[i];
             if (!(fabs(acc) <= ct * ymax)) ok = 0;
         }
-        if (!(bound < 0.0)) ok = 0;
+        if (!(bound < -slack)) ok = 0;
     }
     team_sync<T>();
     return team_min_int<T>(ok, red, tid) ? status : QPN_LP_FAILURE;
 }
 
-// The feasibility solve of the subset tests and the implicit bounds (sections 5g (a), 5h (a); the twin's _lp_feasible): steps 1-8 with
-// c = 0 from zeroed slice vectors.  -> QPN_LP_OPTIMAL (a point of the polyhedron in S.xf, its basis in the dictionary),
+// Step 10, the dictionary of the current basis once more from the scaled rows (the twin's _lp_rebuild): T = A * sc with the cost
+// row S.cv, every x nonbasic; then, for the columns j ascending whose x is basic in the current basis (a row's id stands in column
+// j: a nonbasic x never left its own column), the crash's pivot restricted to the rows whose id is nonbasic in the current basis
+// and still basic here.  At most d pivots; the nonbasic rows keep their values.  S.g, S.tgt and S.dj hold the basis meanwhile (the
+// loop writes them before it reads them).  -> false when a pivot is not above piv_tol.
+template <int T> __device__ bool lp_rebuild(const LpProb &P, const LpSlice &S, int tid)
+{
+    const int r = P.r, d = P.d, ld = lp_ld(r);
+    double *Tm = S.Tm, *red = S.red;
+    int *rb = S.rb, *cn = S.cn;
+    team_sync<T>();
+    for (int i = tid; i < r; i += T) { S.g[i] = 0.0; S.tgt[i] = 0.0; }
+    team_sync<T>();
+    for (int j = tid; j < d; j += T) {
+        const int id = cn[j];
+        S.dj[j] = id >= d ? 1.0 : 0.0;
+        if (id >= d) { S.g[id - d] = 1.0; S.tgt[id - d] = S.xn[j]; }
+        Tm[(size_t)j * ld + r] = S.cv[j]; cn[j] = j;
+    }
+    for (int i = tid; i < r; i += T) {
+        const double s = S.sc[i];
+        rb[i] = d + i;
+        for (int j = 0; j < d; ++j) Tm[(size_t)j * ld + i] = P.Ab[(size_t)j * r + i] * s;
+    }
+    team_sync<T>();
+    for (int j = 0; j < d; ++j) {
+        if (S.dj[j] == 0.0) continue;                     // (the same in every thread)
+        const double *col = Tm + (size_t)j * ld;
+        double m = 0.0;
+        for (int i = tid; i < r; i += T) if (S.g[i] != 0.0 && rb[i] >= d) m = fmax(m, fabs(col[i]));
+        const double best = team_max<T>(m, red, tid);
+        if (!(best > P.piv_tol)) return false;
+        const double thr = best * LP_BAND;
+        int mi = INT_MAX;
+        for (int i = tid; i < r; i += T) if (S.g[i] != 0.0 && rb[i] >= d && fabs(col[i]) >= thr) mi = min(mi, i);
+        const int pi = team_min_int<T>(mi, red, tid);
+        lp_pivot<T>(Tm, S.colb, r, d, ld, pi, j, tid);
+        if (tid == 0) { const int v = rb[pi]; rb[pi] = cn[j]; cn[j] = v; }
+        team_sync<T>();
+    }
+    for (int j = tid; j < d; j += T) if (cn[j] >= d) S.xn[j] = S.tgt[cn[j] - d];
+    team_sync<T>();
+    return true;
+}
+
+// Steps 5-10 from the slice's dictionary with the objective in S.cv and S.lam, S.ray zero (the twin's _lp_finish): the loop, the
+// point and step 9's check; an end that is not certified -- a FAILURE of the loop, an INFEASIBLE end of a warm solve (the
+// polyhedron has a point), a certificate that fails -- rebuilds the dictionary and runs the loop once more, the step counter going
+// on; what that ends with stands.  LP_COLD: an INFEASIBLE end is an outcome, checked like the others; LP_FEASIBLE: that, and an
+// OPTIMAL end is taken unchecked (c = 0); LP_WARM: an INFEASIBLE end is a FAILURE.  -> status; every status but a certified one
+// leaves S.lam = S.ray = 0.  x in S.xf, c'x in *obj_out and, after a check, A x in S.xb.
+enum { LP_WARM = 0, LP_COLD = 1, LP_FEASIBLE = 2 };
+template <int T> __device__ int lp_finish(const LpProb &P, const LpSlice &S, int tid, int mode, int *iters_out, double *obj_out)
+{
+    int iters = 0, status;
+    for (int attempt = 0;; ++attempt) {
+        int e;
+        double dirn;
+        status = lp_loop<T>(P, S, tid, iters, &iters, &e, &dirn);
+        *obj_out = lp_point<T>(P, S, tid);
+        if (status == QPN_LP_ITER_LIMIT || (status == QPN_LP_OPTIMAL && mode == LP_FEASIBLE)) break;
+        if (status == QPN_LP_OPTIMAL || status == QPN_LP_UNBOUNDED || (status == QPN_LP_INFEASIBLE && mode != LP_WARM))
+            if (lp_check<T>(P, S, status, e, dirn, tid) == status) break;
+        status = QPN_LP_FAILURE;
+        team_sync<T>();
+        for (int j = tid; j < P.d; j += T) S.ray[j] = 0.0;
+        for (int i = tid; i < P.r; i += T) S.lam[i] = 0.0;
+        team_sync<T>();
+        if (attempt == 1 || !lp_rebuild<T>(P, S, tid)) break;
+    }
+    *iters_out = iters;
+    return status;
+}
+
+// The feasibility solve of the subset tests and the implicit bounds (sections 5g (a), 5h (a); the twin's _lp_feasible): the set-up and
+// lp_finish with c = 0 from zeroed slice vectors.  -> QPN_LP_OPTIMAL (a point of the polyhedron in S.xf, its basis in the dictionary),
 // QPN_LP_INFEASIBLE (an all-zero row outside its bounds, *iters_out = 0, or an INFEASIBLE end whose Farkas certificate holds),
-// QPN_LP_ITER_LIMIT, or QPN_LP_FAILURE (a certificate that fails included).
+// QPN_LP_ITER_LIMIT, or QPN_LP_FAILURE (the data screen, *iters_out = 0, and an end the rebuild does not certify included).
 template <int T> __device__ int lp_feasible(const LpProb &P, const LpSlice &S, int tid, int *iters_out)
 {
     const int r = P.r, d = P.d;
@@ -412,20 +500,15 @@ template <int T> __device__ int lp_feasible(const LpProb &P, const LpSlice &S, i
     for (int j = tid; j < d; j += T) { S.cv[j] = 0.0; S.xf[j] = 0.0; S.ray[j] = 0.0; }
     for (int i = tid; i < r; i += T) S.lam[i] = 0.0;
     team_sync<T>();
-    if (lp_setup<T>(P, S, tid)) return QPN_LP_INFEASIBLE;
-    int e;
-    double dirn;
-    const int status = lp_loop<T>(P, S, tid, iters_out, &e, &dirn);
-    lp_point<T>(P, S, tid);
-    if (status == QPN_LP_INFEASIBLE)
-        return lp_check<T>(P, S, status, e, dirn, tid) == QPN_LP_INFEASIBLE ? QPN_LP_INFEASIBLE : QPN_LP_FAILURE;
-    return status == QPN_LP_OPTIMAL || status == QPN_LP_ITER_LIMIT ? status : QPN_LP_FAILURE;
+    if (const int settled = lp_setup<T>(P, S, tid)) return settled;
+    double obj;
+    return lp_finish<T>(P, S, tid, LP_FEASIBLE, iters_out, &obj);
 }
 
 // The solve of the objective in S.cv (all threads past a barrier) from the basis the previous solve over the polyhedron left
-// (the twin's _lp_resolve): the cost row of c in the current dictionary (section 5g (e)), the loop with fresh counters, the point
-// and the check.  -> QPN_LP_OPTIMAL or QPN_LP_UNBOUNDED, certified; QPN_LP_ITER_LIMIT; QPN_LP_FAILURE (of the loop, an INFEASIBLE
-// end, a certificate that fails).  x in S.xf, c'x in *obj_out and, after a check, A x in S.xb.
+// (the twin's _lp_resolve): the cost row of c in the current dictionary (section 5g (e)), then lp_finish with fresh
+// counters.  -> QPN_LP_OPTIMAL or QPN_LP_UNBOUNDED, certified; QPN_LP_ITER_LIMIT; QPN_LP_FAILURE (of the loop, an INFEASIBLE end, a
+// certificate that fails, each after the rebuild and the second loop).  x in S.xf, c'x in *obj_out and, after a check, A x in S.xb.
 template <int T> __device__ int lp_resolve(const LpProb &P, const LpSlice &S, int tid, int *iters_out, double *obj_out)
 {
     const int r = P.r, d = P.d, ld = lp_ld(r);
@@ -442,13 +525,7 @@ template <int T> __device__ int lp_resolve(const LpProb &P, const LpSlice &S, in
     for (int j = tid; j < d; j += T) S.ray[j] = 0.0;
     for (int k = tid; k < r; k += T) S.lam[k] = 0.0;
     team_sync<T>();
-    int e;
-    double dirn;
-    const int status = lp_loop<T>(P, S, tid, iters_out, &e, &dirn);
-    *obj_out = lp_point<T>(P, S, tid);
-    if (status == QPN_LP_ITER_LIMIT) return status;
-    if (status == QPN_LP_FAILURE || status == QPN_LP_INFEASIBLE) return QPN_LP_FAILURE;
-    return lp_check<T>(P, S, status, e, dirn, tid);
+    return lp_finish<T>(P, S, tid, LP_WARM, iters_out, obj_out);
 }
 
 // The solve of job t over polyhedron b.  Leaves x in S.xf, the multipliers / Farkas vector in S.lam, the ray in S.ray (zeroed by
@@ -461,13 +538,8 @@ __device__ int lp_core(const LpArgs &a, const LpSlice &S, int t, int b, int orow
     *iters_out = 0; *obj_out = 0.0;
     for (int j = tid; j < d; j += T)
         S.cv[j] = a.cost ? a.cost[(size_t)t * d + j] : (double)a.obj_sign[t] * P.Ab[(size_t)j * r + orow];
-    if (lp_setup<T>(P, S, tid)) return QPN_LP_INFEASIBLE;
-    int e;
-    double dirn;
-    const int status = lp_loop<T>(P, S, tid, iters_out, &e, &dirn);
-    *obj_out = lp_point<T>(P, S, tid);
-    if (status == QPN_LP_ITER_LIMIT || status == QPN_LP_FAILURE) return status;
-    return lp_check<T>(P, S, status, e, dirn, tid);
+    if (const int settled = lp_setup<T>(P, S, tid)) return settled;
+    return lp_finish<T>(P, S, tid, LP_COLD, iters_out, obj_out);
 }
 
 template <int T> __device__ void lp_job(const LpArgs &a, int t, double *base, int tid)

@@ -899,8 +899,9 @@ class _LpState:
 
 
 def _lp_setup(A, l, u, c, o):
-    """Steps 1-4 of qpn_solve_lps: scaling, the dictionary, the crash, the nonbasic values.  -> _LpState; S.zbad is the all-zero row
-    outside its bounds that settles the job (its unit Farkas vector in S.zlam), or None."""
+    """Steps 0-4 of qpn_solve_lps: the data screen, scaling, the dictionary, the crash, the nonbasic values.  -> _LpState; S.nonfinite
+    is set when step 0 fails the job; S.zbad is the all-zero row outside its bounds that settles the job (its unit Farkas vector in
+    S.zlam), or None."""
     r, d = A.shape
     S = _LpState()
     S.A, S.l, S.u, S.r, S.d, S.o = A, l, u, r, d, o
@@ -908,6 +909,10 @@ def _lp_setup(A, l, u, c, o):
     S.zbad, S.iters, S.e, S.dirn, S.a, S.g, S.dj, S.xb = None, 0, -1, 0.0, None, None, None, np.zeros(r)
     piv_tol = o["piv_tol"]
     with np.errstate(all="ignore"):
+        # 0. the data screen: an entry of A or c that is not finite, a bound that is not a number, l = +inf or u = -inf
+        S.nonfinite = not bool(np.all(np.abs(A) < INF) and np.all(np.abs(c) < INF) and np.all(l < INF) and np.all(u > -INF))
+        if S.nonfinite:
+            return S
         # 1. row scaling; an all-zero row outside its bounds settles the job
         amax = np.max(np.abs(A), axis=1)
         S.amax = amax
@@ -950,14 +955,14 @@ def _lp_setup(A, l, u, c, o):
     return S
 
 
-def _lp_loop(S):
-    """Steps 5-8: the simplex loop from the state's dictionary, with its own step and degeneracy counters.  -> status; the
-    steps in S.iters, the basic values, violations and reduced costs of the last round in S.xb, S.g, S.dj, the last entering
-    column and direction in S.e, S.dirn, S.a."""
+def _lp_loop(S, iters0=0):
+    """Steps 5-8: the simplex loop from the state's dictionary, with a fresh degeneracy counter and the step counter at iters0 (the
+    steps of the loop before a rebuild count against the same max_iters).  -> status; the steps in S.iters, the basic values,
+    violations and reduced costs of the last round in S.xb, S.g, S.dj, the last entering column and direction in S.e, S.dirn, S.a."""
     r, d, T, rb, cn, xn, ls, us = S.r, S.d, S.T, S.rb, S.cn, S.xn, S.ls, S.us
     piv_tol, feas_tol, opt_tol, max_iters = S.o["piv_tol"], S.o["feas_tol"], S.o["opt_tol"], S.max_iters
     with np.errstate(all="ignore"):
-        status, iters, degen = LP_FAILURE, 0, 0
+        status, iters, degen = LP_FAILURE, iters0, 0
         e, dirn, a, g, dj = -1, 0.0, None, None, None
         while True:
             lob = np.where(rb >= d, ls[np.maximum(rb - d, 0)], -INF); upb = np.where(rb >= d, us[np.maximum(rb - d, 0)], INF)
@@ -1096,50 +1101,110 @@ def _lp_check(S, status, c, x):
                 for i in range(r):
                     acc = acc + A[i, k] * lam[i]
                 ok = ok and bool(abs(acc) <= ct * ymax)
-            bound = 0.0
+            # the Farkas sum is negative by more than every bound relaxed by the tolerance primal feasibility is judged at accounts for
+            bound, slack = 0.0, 0.0
             for i in range(r):
                 if lam[i] > 0.0:
                     bound = bound + lam[i] * u[i]
+                    slack = slack + lam[i] * tu[i]
                 elif lam[i] < 0.0:
                     bound = bound + lam[i] * l[i]
-            ok = ok and bool(bound < 0.0)
+                    slack = slack - lam[i] * tl[i]
+            ok = ok and bool(bound < -slack)
     return ok, lam, ray
+
+
+def _lp_rebuild(S, c):
+    """The dictionary of the current basis once more from the scaled rows (step 10): T = A * sc with the cost row c, every x
+    nonbasic; then, for the columns j ascending whose x is basic in the current basis (a row's id stands in column j), the crash's
+    pivot restricted to the rows whose id is nonbasic in the current basis and still basic here: the largest |T[i, j]|, the lowest
+    i within PIV_BAND of it.  At most d pivots.  The nonbasic rows keep their values.  -> False when a pivot is not above piv_tol."""
+    r, d, T, rb, cn, xn = S.r, S.d, S.T, S.rb, S.cn, S.xn
+    with np.errstate(all="ignore"):
+        out = np.zeros(r, bool); val = np.zeros(r)
+        for j in range(d):
+            if cn[j] >= d:
+                out[cn[j] - d] = True; val[cn[j] - d] = xn[j]
+        want = cn >= d                                  # (a nonbasic x never left its own column)
+        T[:r] = S.A * S.sc[:, None]
+        T[r] = c
+        rb[:] = d + np.arange(r); cn[:] = np.arange(d)
+        for j in range(d):
+            if not want[j]:
+                continue
+            cand = out & (rb >= d)
+            col = np.where(cand, np.abs(T[:r, j]), 0.0)
+            best = np.max(col)
+            if not best > S.o["piv_tol"]:
+                return False
+            i = int(np.nonzero(cand & (col >= best * LP_PIV_BAND))[0][0])
+            _lp_pivot(T, i, j)
+            rb[i], cn[j] = cn[j], rb[i]
+        for j in range(d):
+            if cn[j] >= d:
+                xn[j] = val[cn[j] - d]
+    return True
+
+
+def _lp_finish(S, c, cold):
+    """Steps 5-10 from the state's dictionary: the loop, the point and step 9's check; an end that is not certified -- a FAILURE of
+    the loop, an INFEASIBLE end of a warm solve (the polyhedron has a point), a certificate that fails -- rebuilds the dictionary
+    (_lp_rebuild) and runs the loop once more, the step counter going on; what that ends with stands.  cold: an INFEASIBLE end is
+    an outcome (checked like the others), and with cold == "feasible" an OPTIMAL end is taken unchecked (c = 0: lp_feasible).
+    -> (status, x, obj, lambda, ray); every status but a certified one comes with lambda = ray = 0."""
+    r, d = S.r, S.d
+    iters0 = 0
+    for attempt in (0, 1):
+        status = _lp_loop(S, iters0)
+        iters0 = S.iters
+        x, obj = _lp_point(S, c)
+        if status == LP_ITER_LIMIT:
+            return status, x, obj, np.zeros(r), np.zeros(d)
+        if status == LP_OPTIMAL and cold == "feasible":
+            return status, x, obj, np.zeros(r), np.zeros(d)
+        if status in (LP_OPTIMAL, LP_UNBOUNDED) or (status == LP_INFEASIBLE and cold):
+            ok, lam, ray = _lp_check(S, status, c, x)
+            if ok:
+                return status, x, obj, lam, ray
+        if attempt == 1 or not _lp_rebuild(S, c):
+            break
+    return LP_FAILURE, x, obj, np.zeros(r), np.zeros(d)
 
 
 def _lp_one(A, l, u, c, o):
     """One LP  min c'x  s.t.  l <= A x <= u  (A [r, d] math layout) by the method of qpn_solve_lps (include/qpn_hip.h states it):
-    set-up, loop, check -- the three parts issubset_pairs_host runs too.  -> (status, x [d], obj, lambda [r], ray [d], iters)."""
+    set-up, then loop, check and at most one rebuild (_lp_finish) -- the parts issubset_pairs_host runs too.
+    -> (status, x [d], obj, lambda [r], ray [d], iters)."""
     S = _lp_setup(A, l, u, c, o)
+    if S.nonfinite:
+        return LP_FAILURE, np.zeros(S.d), 0.0, np.zeros(S.r), np.zeros(S.d), 0
     if S.zbad is not None:
         return LP_INFEASIBLE, np.zeros(S.d), 0.0, S.zlam, np.zeros(S.d), 0
-    status = _lp_loop(S)
-    x, obj = _lp_point(S, c)
-    if status in (LP_ITER_LIMIT, LP_FAILURE):
-        return status, x, obj, np.zeros(S.r), np.zeros(S.d), S.iters
-    ok, lam, ray = _lp_check(S, status, c, x)
-    return (status if ok else LP_FAILURE), x, obj, lam, ray, S.iters
+    status, x, obj, lam, ray = _lp_finish(S, c, True)
+    return status, x, obj, lam, ray, S.iters
 
 
 def _lp_feasible(A, l, u, o):
-    """The feasibility solve of issubset_pairs_host (a) and implicit_bounds_host (a) (the kernel's lp_feasible): steps 1-8 with
-    c = 0.  An infeasible all-zero row, or an INFEASIBLE end whose Farkas certificate holds, is LP_INFEASIBLE; one whose
-    certificate fails LP_FAILURE.  -> (LP_OPTIMAL / LP_INFEASIBLE / LP_ITER_LIMIT / LP_FAILURE, S, x [d]); the steps in S.iters."""
+    """The feasibility solve of issubset_pairs_host (a) and implicit_bounds_host (a) (the kernel's lp_feasible): steps 0-8 and 10
+    with c = 0.  Data the screen rejects is LP_FAILURE at 0 steps; an infeasible all-zero row, or an INFEASIBLE end whose Farkas
+    certificate holds, is LP_INFEASIBLE; one whose certificate fails after the rebuild too LP_FAILURE.
+    -> (LP_OPTIMAL / LP_INFEASIBLE / LP_ITER_LIMIT / LP_FAILURE, S, x [d]); the steps in S.iters."""
     zero = np.zeros(A.shape[1])
     S = _lp_setup(A, l, u, zero, o)
+    if S.nonfinite:
+        return LP_FAILURE, S, zero
     if S.zbad is not None:
         return LP_INFEASIBLE, S, zero
-    status = _lp_loop(S)
-    x, _ = _lp_point(S, zero)
-    if status == LP_INFEASIBLE:
-        return (LP_INFEASIBLE if _lp_check(S, status, zero, x)[0] else LP_FAILURE), S, x
-    return (status if status in (LP_OPTIMAL, LP_ITER_LIMIT) else LP_FAILURE), S, x
+    status, x, _, _, _ = _lp_finish(S, zero, "feasible")
+    return status, S, x
 
 
 def _lp_resolve(S, c):
     """The solve of objective c from the basis the previous solve over the polyhedron left (the kernel's lp_resolve): the cost
-    row of c in the current dictionary (issubset_pairs_host (e)), the loop with fresh step and degeneracy counters, the point and
-    step 9's check.  -> (LP_OPTIMAL or LP_UNBOUNDED, certified / LP_ITER_LIMIT / LP_FAILURE: a FAILURE of the loop, an INFEASIBLE
-    end, a certificate that fails; x [d]; obj = c'x); the steps in S.iters."""
+    row of c in the current dictionary (issubset_pairs_host (e)), then _lp_finish: the loop with fresh step and degeneracy counters,
+    the point, step 9's check and, where the end is not certified, the rebuild and the loop once more.  -> (LP_OPTIMAL or
+    LP_UNBOUNDED, certified / LP_ITER_LIMIT / LP_FAILURE: a FAILURE of the loop, an INFEASIBLE end, a certificate that fails, after
+    the rebuild too; x [d]; obj = c'x); the steps in S.iters."""
     T, rb, cn, r, d = S.T, S.rb, S.cn, S.r, S.d
     with np.errstate(all="ignore"):
         row = np.zeros(d)
@@ -1150,10 +1215,7 @@ def _lp_resolve(S, c):
             if cn[j] < d:
                 row[j] = row[j] + c[cn[j]]
         T[r] = row
-    status = _lp_loop(S)
-    x, obj = _lp_point(S, c)
-    if status == LP_INFEASIBLE or (status in (LP_OPTIMAL, LP_UNBOUNDED) and not _lp_check(S, status, c, x)[0]):
-        status = LP_FAILURE
+    status, x, obj, _, _ = _lp_finish(S, c, False)
     return status, x, obj
 
 
@@ -1163,7 +1225,8 @@ def solve_lps_host(Ac, l, u, poly_of, cost=None, obj_row=None, obj_sign=None, op
     bit-equal.  Ac [polys, d, r] (the polyhedra's matrices in the ABI layout), l, u [polys, r] (+-inf allowed), poly_of [jobs];
     the objective of job t is cost[t] or, without `cost`, obj_sign[t] * row obj_row[t] of its polyhedron.
     -> dict(status [jobs] int32, x [jobs, d], obj [jobs], lam [jobs, r], ray [jobs, d], iters [jobs] int32).  A job whose
-    poly_of / obj_row is out of range answers LP_FAILURE with zeros (the kernel's rule for device index arrays)."""
+    poly_of / obj_row is out of range answers LP_FAILURE with zeros (the kernel's rule for device index arrays), and so does one
+    whose data the screen of step 0 rejects; every LP_FAILURE and LP_ITER_LIMIT has lam = ray = 0."""
     Ac = np.asarray(Ac, dtype=np.float64); l = np.asarray(l, dtype=np.float64); u = np.asarray(u, dtype=np.float64)
     polys, d, r = Ac.shape
     poly_of = np.asarray(poly_of, dtype=np.int64)
@@ -1254,8 +1317,8 @@ def issubset_pairs_host(A1c, l1, u1, A2c, l2, u2, pi, pj, tol=1e-6, opts=None):
     row of c in the current dictionary: column j, acc = 0, over the rows i ascending with an x basic acc = acc + c[rb[i]] * T[i, j],
     then + c[cn[j]] when an x is nonbasic there.  (f) the loop with fresh step and degeneracy counters, step 9's check on P1
     ((e) and (f) are _lp_resolve):
-    OPTIMAL with obj < beta - tol is BY_OPTIMUM, a certified ray UNBOUNDED, a failed certificate or an INFEASIBLE end FAILURE,
-    ITER_LIMIT / FAILURE themselves.  (g) no bound left: HOLDS.
+    OPTIMAL with obj < beta - tol is BY_OPTIMUM, a certified ray UNBOUNDED, a failed certificate or an INFEASIBLE end that the
+    rebuild and the second loop of _lp_finish do not mend FAILURE, ITER_LIMIT / FAILURE themselves.  (g) no bound left: HOLDS.
     -> dict(sub [pairs] uint8, how [pairs] int32 (SUBSET_*), bound [pairs] int32 (2 i + side of the deciding bound, -1 without),
     val [pairs] (the value that decided: BY_POINT, BY_OPTIMUM), lps [pairs] int32 (solves started, the feasibility solve counted),
     iters [pairs] int32 (all steps)).  A pair whose pi / pj is out of range answers FAILURE with bound -1 and zeros (the kernel's
@@ -1373,8 +1436,9 @@ def implicit_bounds_host(Ac, l, u, tol=1e-4, all_extremes=False, opts=None):
     +a_i from the current basis (the cost row as in issubset_pairs_host (e), fresh step and degeneracy counters, the loop, the
     point and step 9's check: _lp_resolve): a certified ray gives lo = -inf, UNBOUNDED; an optimum lo = obj, and whi - lo > tol is BY_POINTS;
     then the maximum with c = -a_i: hi = -obj or +inf.  eq = lo, hi finite and |lo - hi| <= tol: val = 0.5 (hi + lo), IMPLICIT;
-    else BY_EXTREMES, or UNBOUNDED when one of the two is infinite.  ITER_LIMIT, an INFEASIBLE end or a failed certificate in one
-    of these solves ends the polyhedron with that status and fail_row = i.  all_extremes (QPN_IB_ALL_EXTREMES): no BY_POINTS and
+    else BY_EXTREMES, or UNBOUNDED when one of the two is infinite.  ITER_LIMIT, or an INFEASIBLE end or a failed certificate that
+    the rebuild and the second loop of _lp_finish do not mend, in one of these solves ends the polyhedron with that status and
+    fail_row = i.  all_extremes (QPN_IB_ALL_EXTREMES): no BY_POINTS and
     no early exit after an unbounded minimum; every row that is not explicit gets both extremes and is decided by them alone.
     -> dict(status [polys] int32 (IB_*), fail_row [polys] int32 (-1 without), eq [polys, r] uint8, vals [polys, r] (+inf where eq
     = 0), how [polys, r] int32 (IB_HOW_*), lo, hi [polys, r] (NaN where no LP computed them), lps [polys] int32 (solves started,
