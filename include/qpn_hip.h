@@ -615,6 +615,39 @@ int qpn_implicit_bounds(qpn_ctx *ctx, int32_t polys, int32_t r, int32_t d, const
                         int32_t flags, const qpn_lp_opts *opts, int32_t *status, int32_t *fail_row, uint8_t *eq, double *vals, int32_t *how,
                         double *lo, double *hi, int32_t *lps, int32_t *iters, int mem);
 
+/* qpn_exemplar_polys: `exemplar` / `isempty` (src/sets.jl:591-655) of `polys` polyhedra {x : l <= A x <= u} of one shape whose
+ * bounds may be open, one job per polyhedron.  A [polys][n][d] column-major per item, l, u [polys][n] (+-inf allowed), open_lo,
+ * open_hi [polys][n] uint8 (nonzero: that bound is open; NULL: every such bound is closed).  Outputs (how, eps, x, row, lambda,
+ * iters may be NULL):
+ *   empty [polys] uint8;  how [polys] int32 (QPN_EX_*);  eps [polys]: the optimal slack, NaN for ITER_LIMIT and FAILURE;
+ *   x [polys][d]: a member, zeros when the polyhedron is empty or the job ended in ITER_LIMIT or FAILURE;
+ *   row [polys] int32: 2 i + side (side 0 = l[i], 1 = u[i]) of the lowest open bound that decided EMPTY_OPEN, -1 otherwise;
+ *   lambda [polys][2 n + 1]: the multipliers of the slack LP's rows (below), zeros for ITER_LIMIT and FAILURE;
+ *   iters [polys] int32: the steps of the solve.
+ * Method (polyhedra.exemplar_polys_host is its numpy twin and the normative statement; every output is bit-equal to it, by the
+ * discipline of qpn_solve_lps, whose steps 0-10 it runs):  (a) the slack LP in the variables (x, eps): rows i < n: [a_i, 1] >= l_i;
+ * rows n + i: [-a_i, 1] >= -u_i; row 2 n: eps >= -slack_cap; every upper bound +inf; the objective is the last row, eps.  The job
+ * writes these rows into its own region of the context workspace -- the host expands nothing -- and solves the LP as qpn_solve_lps
+ * solves a job, the data screen of step 0 included: l_i = +inf, u_i = -inf or an entry of A that is not finite is FAILURE.
+ * (b) the rule on the certified optimum, eps = its last coordinate:  eps > tol: EMPTY_SLACK.  eps > -tol (the band): a bound
+ * is active when it is open, finite (an open flag on an infinite bound is ignored, src/sets.jl:354-356) and its multiplier has
+ * |lambda_i| > tol (lower bound of row i) or |lambda_{n+i}| > tol (upper bound); any active bound: EMPTY_OPEN, row = the lowest 2 i +
+ * side; none: MEMBER_BAND.  eps <= -tol: MEMBER.  (c) an iteration limit is ITER_LIMIT; every other end that is no certified
+ * optimum is FAILURE (the slack LP is feasible and bounded below, so INFEASIBLE and UNBOUNDED cannot be true answers).
+ * Kernel classes are those of qpn_lp_kernel_class(2 n + 1, d + 1); a call whose regions exceed the workspace chunk is launched in
+ * chunks.  1 <= n <= 511, 1 <= d <= 255 (QPN_ERR_SIZE beyond).  max_iters <= 0: 50 (2 n + d + 2) + 100.  polys == 0 succeeds. */
+enum {
+    QPN_EX_MEMBER = 0,       /* eps <= -tol: x is a member with slack                                   empty = 0 */
+    QPN_EX_MEMBER_BAND = 1,  /* -tol < eps <= tol and no open bound is active: x is a member             empty = 0 */
+    QPN_EX_EMPTY_SLACK = 2,  /* eps > tol                                                                empty = 1 */
+    QPN_EX_EMPTY_OPEN = 3,   /* -tol < eps <= tol and an open, finite bound is active (row names it)     empty = 1 */
+    QPN_EX_ITER_LIMIT = 4,   /* the iteration limit was reached: no answer                               empty = 0 */
+    QPN_EX_FAILURE = 5       /* the data screen, or an end that is no certified optimum: no answer       empty = 0 */
+};
+int qpn_exemplar_polys(qpn_ctx *ctx, int32_t polys, int32_t n, int32_t d, const double *A, const double *l, const double *u,
+                       const uint8_t *open_lo, const uint8_t *open_hi, double tol, double slack_cap, const qpn_lp_opts *opts,
+                       uint8_t *empty, int32_t *how, double *eps, double *x, int32_t *row, double *lambda, int32_t *iters, int mem);
+
 #ifdef __cplusplus
 }
 #endif

@@ -415,6 +415,37 @@ function implicit_bounds(polys::Vector{<:Tuple{Matrix{Float64},Vector{Float64},V
     out
 end
 
+"""
+    exemplar_polys(A, l, u; open_lo=nothing, open_hi=nothing, tol=1e-2, slack_cap=1.0, max_iters=0)
+        -> (empty, how, eps, x, row, lambda, iters)
+
+qpn_exemplar_polys: `exemplar(poly; tol)` / `isempty` (src/sets.jl:591-655) for polyhedra of one shape whose bounds may be open, one
+job per polyhedron: A [n, d, polys], l, u [n, polys], open_lo, open_hi [n, polys] (Bool or UInt8; nothing: closed).  The job expands
+the slack LP min eps s.t. A x + eps >= l, -A x + eps >= -u, eps >= -slack_cap on the device, solves it and applies the reference's
+rule to eps and the multipliers of the open, finite bounds.  how: 0 member (eps <= -tol), 1 member in the band, 2 empty (eps > tol),
+3 empty by an active open bound (row: 2 i + side, 0-based row i, side 0 = lower, 1 = upper; -1 otherwise), 4 iteration limit, 5
+failure (both without an answer: empty = 0, eps = NaN).  x [d, polys]: a member, zeros when empty or unanswered; lambda [2 n + 1,
+polys]: the multipliers of the slack LP's rows.  n <= 511, d <= 255.
+"""
+function exemplar_polys(A::Array{Float64,3}, l::Matrix{Float64}, u::Matrix{Float64};
+                        open_lo::Union{Nothing,AbstractMatrix} = nothing, open_hi::Union{Nothing,AbstractMatrix} = nothing,
+                        tol::Float64 = 1e-2, slack_cap::Float64 = 1.0, max_iters::Integer = 0)
+    n, d, polys = size(A)
+    size(l) == (n, polys) && size(u) == (n, polys) || error("exemplar_polys: inconsistent shapes")
+    flags(o) = o === nothing ? nothing : (size(o) == (n, polys) || error("exemplar_polys: inconsistent shapes"); Matrix{UInt8}(o .!= 0))
+    olo = flags(open_lo); ohi = flags(open_hi)
+    opts = Ref((1e-9, 1e-9, 1e-9, 1e-6, Int32(max_iters), Int32(0)))      # qpn_lp_opts
+    empty = zeros(UInt8, polys); how = zeros(Int32, polys); eps = zeros(polys); x = zeros(d, polys); row = zeros(Int32, polys)
+    lam = zeros(2n + 1, polys); iters = zeros(Int32, polys)
+    rc = ccall((:qpn_exemplar_polys, LIB), Cint,
+               (Ptr{Cvoid}, Int32, Int32, Int32, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{UInt8}, Ptr{UInt8}, Cdouble, Cdouble,
+                Ptr{Cvoid}, Ptr{UInt8}, Ptr{Int32}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int32}, Ptr{Cdouble}, Ptr{Int32}, Cint),
+               ctx(), polys, n, d, A, l, u, olo === nothing ? C_NULL : olo, ohi === nothing ? C_NULL : ohi, tol, slack_cap, opts,
+               empty, how, eps, x, row, lam, iters, QPN_MEM_HOST)
+    rc == 0 || error("qpn_exemplar_polys failed ($rc)")
+    (empty, how, eps, x, row, lam, iters)
+end
+
 function verify_nodes(nodes::Nodes, xd::Matrix{Float64}, w::VecOrMat{Float64}; tol::Float64 = 1e-4)
     solution = zeros(Int32, nodes.batch); path = zeros(Int32, nodes.batch); lambda = zeros(max(nodes.m, 1), nodes.batch)
     rc = ccall((:qpn_verify_nodes_h, LIB), Cint,

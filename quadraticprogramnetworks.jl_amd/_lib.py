@@ -25,6 +25,7 @@ ABI_SYMBOLS = (
     "qpn_multiplier_vertices", "qpn_recipe_filter",
     "qpn_assemble_interior_nodes", "qpn_interior_members", "qpn_members_outside",
     "qpn_lp_default_opts", "qpn_lp_kernel_class", "qpn_solve_lps", "qpn_issubset_pairs", "qpn_implicit_bounds",
+    "qpn_exemplar_polys",
 )
 
 MEM_HOST, MEM_DEVICE = 0, 1
@@ -66,6 +67,8 @@ SUBSET_HOLDS, SUBSET_BY_POINT, SUBSET_BY_OPTIMUM, SUBSET_UNBOUNDED, SUBSET_ITER_
 IB_OK, IB_EMPTY, IB_ITER_LIMIT, IB_FAILURE = 0, 1, 2, 3
 IB_HOW_UNDECIDED, IB_HOW_EXPLICIT, IB_HOW_IMPLICIT, IB_HOW_BY_POINTS, IB_HOW_BY_EXTREMES, IB_HOW_UNBOUNDED = 0, 1, 2, 3, 4, 5
 IB_ALL_EXTREMES = 1
+EX_MEMBER, EX_MEMBER_BAND, EX_EMPTY_SLACK, EX_EMPTY_OPEN, EX_ITER_LIMIT, EX_FAILURE = 0, 1, 2, 3, 4, 5
+EX_MAX_N, EX_MAX_D = 511, 255
 
 _lib = None
 
@@ -166,6 +169,8 @@ def load_library():
                                        C.c_double, C.POINTER(LpOpts), vp, vp, vp, vp, vp, vp, C.c_int]
     lib.qpn_implicit_bounds.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, C.c_double, C.c_int32, C.POINTER(LpOpts),
                                         vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int]
+    lib.qpn_exemplar_polys.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, C.c_double, C.c_double, C.POINTER(LpOpts),
+                                       vp, vp, vp, vp, vp, vp, vp, C.c_int]
     del dp, ip, bp
     _lib = lib
     return lib

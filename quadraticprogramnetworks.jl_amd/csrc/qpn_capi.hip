@@ -1863,6 +1863,39 @@ int qpn_implicit_bounds(qpn_ctx *ctx, int32_t polys, int32_t r, int32_t d, const
     return st.finish();
 }
 
+int qpn_exemplar_polys(qpn_ctx *ctx, int32_t polys, int32_t n, int32_t d, const double *A, const double *l, const double *u,
+                       const uint8_t *open_lo, const uint8_t *open_hi, double tol, double slack_cap, const qpn_lp_opts *opts,
+                       uint8_t *empty, int32_t *how, double *eps, double *x, int32_t *row, double *lambda, int32_t *iters, int mem)
+{
+    if (!ctx) return QPN_ERR_ARG;
+    if (polys < 0 || n <= 0 || d <= 0) return fail_arg(ctx, "qpn_exemplar_polys: bad sizes");
+    if (n > QPN_EX_MAX_N || d > QPN_EX_MAX_D) { ctx->last_error = "qpn_exemplar_polys: n <= 511, d <= 255 in ABI v1"; return QPN_ERR_SIZE; }
+    Stage st(ctx, mem, "qpn_exemplar_polys");
+    if (int rc = st.check()) return rc;
+    if (polys == 0) return QPN_OK;
+    if (!A || !l || !u || !empty) return fail_arg(ctx, "qpn_exemplar_polys: null pointer");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t P = (size_t)polys, R = 2 * (size_t)n + 1;
+    ExArgs a{};
+    a.polys = polys; a.n = n; a.d = d; a.tol = tol; a.slack_cap = slack_cap;
+    a.lp = lp_tol(opts, 2 * n + 1, d + 1);
+    void *gws;
+    st.in(a.A, A, P * n * d * 8); st.in(a.l, l, P * n * 8); st.in(a.u, u, P * n * 8);
+    st.in(a.open_lo, open_lo, P * n); st.in(a.open_hi, open_hi, P * n);
+    st.out(a.empty, empty, P);
+    st.out_opt(a.how, how, P * 4);
+    st.out_opt(a.eps, eps, P * 8);
+    st.out_opt(a.x, x, P * d * 8);
+    st.out_opt(a.row, row, P * 4);
+    st.out_opt(a.lam, lambda, P * R * 8);
+    st.out_opt(a.iters, iters, P * 4);
+    st.scratch(gws, qpn_exemplar_workspace_bytes(polys, n, d));
+    int rc = st.begin();
+    if (rc != QPN_OK) return rc;
+    HIPCHK(ctx, qpn_launch_exemplar_polys(a, gws, ctx->stream));
+    return st.finish();
+}
+
 } // extern "C"
 
 namespace {

@@ -324,6 +324,27 @@ struct IbArgs {
     LpTol lp;
 };
 hipError_t qpn_launch_implicit_bounds(const IbArgs &a, void *gws, hipStream_t s);     // gws: qpn_lp_workspace_bytes(polys, r, d)
+// ... and the emptiness of polyhedra with open bounds (qpn_exemplar_polys), one job per polyhedron over its slack LP of 2 n + 1 rows
+// in d + 1 variables.  open_lo, open_hi null: closed;  how, eps, x, row, lam, iters may be null.
+struct ExArgs {
+    int32_t polys, n, d;
+    const double *A, *l, *u;
+    const uint8_t *open_lo, *open_hi;
+    double tol, slack_cap;
+    uint8_t *empty;
+    int32_t *how;
+    double *eps, *x;
+    int32_t *row;
+    double *lam;
+    int32_t *iters;
+    LpTol lp;
+    int32_t first;                             // set by the launcher: the polyhedron of a launch's job 0, and where the jobs'
+    unsigned char *rows;                       // regions of expanded rows start
+};
+#define QPN_EX_MAX_N 511
+#define QPN_EX_MAX_D 255
+size_t qpn_exemplar_workspace_bytes(int32_t polys, int32_t n, int32_t d);
+hipError_t qpn_launch_exemplar_polys(const ExArgs &a, void *gws, hipStream_t s);      // gws: qpn_exemplar_workspace_bytes(polys, n, d)
 #define QPN_CONVEXITY_MAX_N 256
 #define QPN_CONVEXITY_MAX_M 1024
 

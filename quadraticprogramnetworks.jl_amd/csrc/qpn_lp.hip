@@ -24,8 +24,13 @@
 // polyhedra.implicit_bounds_host is its twin).  The slice is that of an LP; the witnesses stay in the registers of the lane that
 // owns the row, the answers go straight to the job's output rows.
 //
-// The three entries share the kernels and the launcher: lp_wave_kernel<Job> and lp_group_kernel<Job, LDS>
-// run the job function of the kind Job (LpJob, SubsetJob, IbJob), lp_launch<Job> picks the class and launches.
+// qpn_exemplar_polys runs them with one team per polyhedron whose bounds may be open: the team writes the rows
+// of the polyhedron's slack LP (min eps, A x + eps >= l, -A x + eps >= -u, eps >= -cap) into its region of the workspace, solves
+// it as a job of qpn_solve_lps is solved (lp_setup, lp_finish cold) and applies the reference's rule to eps and the multipliers of
+// the open bounds (ex_job; polyhedra.exemplar_polys_host is its twin).  The slice is that of an LP of 2 n + 1 rows in d + 1 variables.
+//
+// The four entries share the kernels and the launcher: lp_wave_kernel<Job> and lp_group_kernel<Job, LDS>
+// run the job function of the kind Job (LpJob, SubsetJob, IbJob, ExJob), lp_launch<Job> picks the class and launches.
 #include <climits>
 
 #include "qpn_internal.h"
@@ -792,6 +797,74 @@ template <int T> __device__ void ib_job(const IbArgs &a, int b, double *base, in
     }
 }
 
+// ---- emptiness of polyhedra with open bounds: one team per polyhedron -----------------------------------------------------------
+// A job's region of the workspace: the rows of its slack LP, A [(d + 1) x (2 n + 1)] column-major, then l and u [2 n + 1 each]
+__host__ __device__ inline size_t ex_rows_bytes(int n, int d)
+{
+    const size_t R = 2 * (size_t)n + 1;
+    return ((R * (size_t)(d + 1) + 2 * R) * 8 + 15) & ~(size_t)15;
+}
+
+// Job t of a launch: polyhedron a.first + t, the rows in region t.  Every value a branch depends on is the same in all threads
+// of the team (the status of the solve, values read from the slice after a barrier, a team reduction).
+template <int T> __device__ void ex_job(const ExArgs &a, int t, double *base, int tid)
+{
+    const int n = a.n, d = a.d, R = 2 * n + 1, D = d + 1;
+    const size_t b = (size_t)a.first + (size_t)t;
+    const double *A = a.A + b * n * d, *l = a.l + b * n, *u = a.u + b * n;
+    double *Ae = reinterpret_cast<double *>(a.rows + (size_t)t * ex_rows_bytes(n, d)), *le = Ae + (size_t)R * D, *ue = le + R;
+    const LpSlice S(base, R, D);
+    // (a) the rows of the slack LP: [a_i, 1] >= l_i, [-a_i, 1] >= -u_i, eps >= -slack_cap; the objective is the last row
+    for (int i = tid; i < R; i += T) {
+        const int k = i < n ? i : i - n;
+        for (int j = 0; j < d; ++j) Ae[(size_t)j * R + i] = i < n ? A[(size_t)j * n + k] : i < 2 * n ? -A[(size_t)j * n + k] : 0.0;
+        Ae[(size_t)d * R + i] = 1.0;
+        le[i] = i < n ? l[k] : i < 2 * n ? -u[k] : -a.slack_cap;
+        ue[i] = QINF;
+        S.lam[i] = 0.0;
+    }
+    for (int j = tid; j < D; j += T) { S.cv[j] = j == d ? 1.0 : 0.0; S.xf[j] = 0.0; S.ray[j] = 0.0; }
+    if (tid < 8) S.red[tid] = 0.0;
+    team_sync<T>();
+    const LpProb P = lp_prob(R, D, Ae, le, ue, a.lp);
+    int iters = 0;
+    double obj = 0.0;
+    int status = lp_setup<T>(P, S, tid);
+    if (!status) status = lp_finish<T>(P, S, tid, LP_COLD, &iters, &obj);
+    team_sync<T>();
+    // (b) the rule on the certified optimum
+    const double tol = a.tol;
+    int how = status == QPN_LP_ITER_LIMIT ? QPN_EX_ITER_LIMIT : QPN_EX_FAILURE, row = -1;
+    double eps = __builtin_nan("");
+    if (status == QPN_LP_OPTIMAL) {
+        eps = S.xf[d];
+        if (eps > tol) {
+            how = QPN_EX_EMPTY_SLACK;
+        } else if (eps > -tol) {
+            int low = INT_MAX;
+            for (int i = tid; i < n; i += T) {
+                if (a.open_hi && a.open_hi[b * n + i] && fabs(u[i]) < QINF && fabs(S.lam[n + i]) > tol) low = min(low, 2 * i + 1);
+                if (a.open_lo && a.open_lo[b * n + i] && fabs(l[i]) < QINF && fabs(S.lam[i]) > tol) low = min(low, 2 * i);
+            }
+            low = team_min_int<T>(low, S.red, tid);
+            how = low == INT_MAX ? QPN_EX_MEMBER_BAND : QPN_EX_EMPTY_OPEN;
+            if (low != INT_MAX) row = low;
+        } else {
+            how = QPN_EX_MEMBER;
+        }
+    }
+    const bool member = how == QPN_EX_MEMBER || how == QPN_EX_MEMBER_BAND, solved = status == QPN_LP_OPTIMAL;
+    if (a.x) for (int j = tid; j < d; j += T) a.x[b * d + j] = member ? S.xf[j] : 0.0;
+    if (a.lam) for (int i = tid; i < R; i += T) a.lam[b * R + i] = solved ? S.lam[i] : 0.0;
+    if (tid == 0) {
+        a.empty[b] = how == QPN_EX_EMPTY_SLACK || how == QPN_EX_EMPTY_OPEN ? 1 : 0;
+        if (a.how) a.how[b] = how;
+        if (a.eps) a.eps[b] = eps;
+        if (a.row) a.row[b] = row;
+        if (a.iters) a.iters[b] = iters;
+    }
+}
+
 // ---- the kernels and the launcher of every job kind ------------------------------------------------------------------------------
 // A job kind names its argument struct and runs job t of it with a team of T threads on the slice at base.
 struct LpJob {
@@ -805,6 +878,10 @@ struct SubsetJob {
 struct IbJob {
     using Args = IbArgs;
     template <int T> static __device__ void run(const Args &a, int t, double *base, int tid) { ib_job<T>(a, t, base, tid); }
+};
+struct ExJob {
+    using Args = ExArgs;
+    template <int T> static __device__ void run(const Args &a, int t, double *base, int tid) { ex_job<T>(a, t, base, tid); }
 };
 
 template <class Job> __global__ __launch_bounds__(64 * LP_WAVES) void lp_wave_kernel(typename Job::Args a, int32_t count, size_t slice)
@@ -864,6 +941,18 @@ template <class Job> hipError_t lp_launch(const typename Job::Args &a, int32_t c
     return hipSuccess;
 }
 
+// What a job of qpn_exemplar_polys takes of the workspace: its rows and, in the workspace class, its slice; and the jobs of a launch
+size_t ex_job_bytes(int32_t n, int32_t d)
+{
+    return ex_rows_bytes(n, d) + (qpn_lp_class(2 * n + 1, d + 1) == 2 ? lp_slice_bytes(2 * n + 1, d + 1) : 0);
+}
+int32_t ex_chunk(int32_t polys, int32_t n, int32_t d)
+{
+    size_t c = LP_WS_CHUNK_BYTES / ex_job_bytes(n, d);
+    if (c < 1) c = 1;
+    return (int32_t)(c < (size_t)polys ? c : (size_t)polys);
+}
+
 } // namespace
 
 int qpn_lp_class(int32_t r, int32_t d)
@@ -882,3 +971,25 @@ size_t qpn_lp_workspace_bytes(int32_t jobs, int32_t r, int32_t d)
 hipError_t qpn_launch_solve_lps(const LpArgs &a, void *gws, hipStream_t s) { return lp_launch<LpJob>(a, a.jobs, a.r, a.d, gws, s); }
 hipError_t qpn_launch_issubset_pairs(const SubsetArgs &a, void *gws, hipStream_t s) { return lp_launch<SubsetJob>(a, a.pairs, a.r1, a.d, gws, s); }
 hipError_t qpn_launch_implicit_bounds(const IbArgs &a, void *gws, hipStream_t s) { return lp_launch<IbJob>(a, a.polys, a.r, a.d, gws, s); }
+
+size_t qpn_exemplar_workspace_bytes(int32_t polys, int32_t n, int32_t d)
+{
+    if (polys <= 0 || qpn_lp_class(2 * n + 1, d + 1) < 0) return 0;
+    return (size_t)ex_chunk(polys, n, d) * ex_job_bytes(n, d);
+}
+
+// The workspace holds the slices of a chunk's jobs (workspace class), then their rows; a chunk is one launch of lp_launch (at most
+// lp_chunk jobs, as a job takes more than its slice), and the chunks of a call follow one another on the stream.
+hipError_t qpn_launch_exemplar_polys(const ExArgs &a0, void *gws, hipStream_t s)
+{
+    if (a0.polys <= 0) return hipSuccess;
+    const int32_t R = 2 * a0.n + 1, D = a0.d + 1, chunk = ex_chunk(a0.polys, a0.n, a0.d);
+    ExArgs a = a0;
+    a.rows = static_cast<unsigned char *>(gws) + (qpn_lp_class(R, D) == 2 ? (size_t)chunk * lp_slice_bytes(R, D) : 0);
+    for (int32_t first = 0; first < a0.polys; first += chunk) {
+        a.first = first;
+        const int32_t count = a0.polys - first < chunk ? a0.polys - first : chunk;
+        if (const hipError_t e = lp_launch<ExJob>(a, count, R, D, gws, s); e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}

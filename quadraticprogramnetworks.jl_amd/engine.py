@@ -730,6 +730,28 @@ class Engine:
                    _ptr(out["how"]), _ptr(out["lo"]), _ptr(out["hi"]), _ptr(out["lps"]), _ptr(out["iters"]), self._mem(dev))
         return out
 
+    def exemplar_polys(self, Ac, l, u, open_lo=None, open_hi=None, tol=1e-2, slack_cap=1.0, opts=None):
+        """`exemplar` / `isempty` of polyhedra of one shape whose bounds may be open, one job per polyhedron (qpn_exemplar_polys;
+        polyhedra.exemplar_polys_host is its numpy twin, bit for bit): Ac [polys, d, n] (ABI layout, ``colmajor(A)``), l, u
+        [polys, n], open_lo, open_hi [polys, n] uint8 or None (closed).  opts: LpOpts, a dict of its fields, or None.
+        Returns dict(empty [polys] uint8, how [polys] int32 (_lib.EX_*), eps [polys], x [polys, d], row [polys] int32, lam
+        [polys, 2 n + 1], iters [polys] int32)."""
+        dev, Ac, l, u, open_lo, open_hi = self._stage("exemplar_polys", "Ac l u open_lo open_hi", f64=(Ac, l, u), u8=(open_lo, open_hi))
+        if Ac.ndim != 3:
+            raise QpnError("exemplar_polys: inconsistent shapes")
+        polys, d, n = (int(v) for v in Ac.shape)
+        if tuple(l.shape) != (polys, n) or tuple(u.shape) != (polys, n) or any(
+                o is not None and tuple(o.shape) != (polys, n) for o in (open_lo, open_hi)):
+            raise QpnError("exemplar_polys: inconsistent shapes")
+        opts = self._lp_opts(opts)
+        out = dict(empty=self._alloc(dev, (polys,), np.uint8), how=self._alloc(dev, (polys,), np.int32), eps=self._alloc(dev, (polys,), np.float64),
+                   x=self._alloc(dev, (polys, d), np.float64), row=self._alloc(dev, (polys,), np.int32),
+                   lam=self._alloc(dev, (polys, 2 * n + 1), np.float64), iters=self._alloc(dev, (polys,), np.int32))
+        self._call("qpn_exemplar_polys", polys, n, d, _ptr(Ac), _ptr(l), _ptr(u), _ptr(open_lo), _ptr(open_hi), float(tol), float(slack_cap),
+                   C.byref(opts) if opts is not None else None, _ptr(out["empty"]), _ptr(out["how"]), _ptr(out["eps"]), _ptr(out["x"]),
+                   _ptr(out["row"]), _ptr(out["lam"]), _ptr(out["iters"]), self._mem(dev))
+        return out
+
 
 class Nodes:
     """Resident node records (``qpn_nodes_upload``): the records of a level's single-node pools live in HBM owned by the

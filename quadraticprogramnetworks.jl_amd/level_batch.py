@@ -1401,8 +1401,8 @@ def process_level(qpn, players: Sequence[int], x, S: Dict[int, list], engine=Non
             else:
                 jobs.append(([[S[j][ji] for j, ji in zip(children, combo)] for combo in combos], per_combo))
                 job_pid.append(pid)
-        if jobs:                                                                    # all kinks of the level: one batch of LPs
-            for pid, got in zip(job_pid, combine_many(jobs, x, eng)):
+        if jobs:                                                                    # all kinks of the level: one batch of LPs,
+            for pid, got in zip(job_pid, combine_many(jobs, x, eng, route=None)):   # on qp_processing.EMPTINESS_ROUTE
                 if isinstance(got, RuntimeError):
                     results[pid] = dict(solution=False, failed=True, S=None)        # :219-223
                 else:

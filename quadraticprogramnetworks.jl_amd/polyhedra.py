@@ -25,7 +25,9 @@ for each) the LPs of exemplar_slack_batch and implicit_bounds_batch are jobs ove
 bounds of P2 as objectives one after the other, from the basis the previous one left, until one refutes; issubset_batch packs the
 distinct polyhedra by shape and builds no query.  solve_lps_host and issubset_pairs_host are the numpy twins of the two entries:
 the normative statements of their methods, to which the kernels are bit-equal.  An engine without the methods (the oracle engine)
-keeps the node-AVI route.
+keeps the node-AVI route.  On an engine with `exemplar_polys` (qpn_exemplar_polys) the emptiness question of a polyhedron whose
+bounds may be open is ONE job too, opt-in through route="polyhedron": the job expands the slack LP, solves it and applies the
+reference's rule to its own duals (exemplar_polys_host is the twin).
 """
 from __future__ import annotations
 
@@ -573,7 +575,7 @@ def _isapprox(x, y, atol, rtol):
         return bool(np.all((x == y) | (fin & close)))
 
 
-def exemplar_slack_batch(polys, engine, tol=1e-2, slack_cap=1.0, strict=True):
+def exemplar_slack_batch(polys, engine, tol=1e-2, slack_cap=1.0, strict=True, route=None):
     """`exemplar(poly; tol)` (src/sets.jl:591-642), the reference's own emptiness rule, for a batch:
         min eps  s.t.  A x + eps >= l,  -A x + eps >= -u                       (:608-619)
         eps > tol -> empty;  eps > -tol -> empty iff an OPEN bound is active (|dual| > tol), else a member;
@@ -581,8 +583,14 @@ def exemplar_slack_batch(polys, engine, tol=1e-2, slack_cap=1.0, strict=True):
     plus the square-equality shortcut x = A \\ l (:599-606).  One LP per polyhedron in variables (x, eps), all in one call of
     the node solver.  eps is capped below at -slack_cap (an unbounded LP -- OSQP's status 4, which the reference does not
     handle -- means slack without end: a member either way).  -> (empty [B] bool, example list, eps [B]).
+    route="polyhedron" on an engine with `exemplar_polys` (qpn_exemplar_polys): every item the shortcuts leave, closed or open,
+    is ONE job of the batched simplex that expands its own slack LP and applies the rule to its own duals -- one call per shape,
+    no node solve and no solve_lps call (_exemplar_slack_polyhedra); any other engine, and a shape beyond the kernel's limits,
+    keeps today's route (route=None or "nodes").
     Parity unpinned: the reference holds no fixture for this rule; checked against HiGHS on seeded polyhedra and the hand-checked
     edge cases of tests/test_polyhedra.py (the norm-based `isapprox` of :599, the slack cap)."""
+    if route not in (None, "nodes", "polyhedron"):
+        raise ValueError(f"exemplar_slack_batch: unknown route {route!r}")
     Bn = len(polys)
     if Bn == 0:
         return np.zeros(0, bool), [], np.zeros(0)
@@ -604,6 +612,8 @@ def exemplar_slack_batch(polys, engine, tol=1e-2, slack_cap=1.0, strict=True):
             empty[b] = not ok; example[b] = x if ok else None
             continue
         todo.append(b)
+    if todo and route == "polyhedron" and callable(getattr(engine, "exemplar_polys", None)):
+        todo = _exemplar_slack_polyhedra(todo, trips, opens, engine, tol, slack_cap, strict, empty, example, eps_out)
     if todo and _has_lps(engine):
         # closed polyhedra: the answer depends on eps alone -- the LP solver; with an open bound it depends on which duals the
         # solver returns: today's route
@@ -640,8 +650,9 @@ def exemplar_slack_batch(polys, engine, tol=1e-2, slack_cap=1.0, strict=True):
     return empty, example, eps_out
 
 
-def isempty_slack_batch(polys, engine, tol=1e-4, x=None):
-    """`isempty(poly; tol, x)` (src/sets.jl:647-655) for a batch: membership of the given point first, else the exemplar rule."""
+def isempty_slack_batch(polys, engine, tol=1e-4, x=None, route=None):
+    """`isempty(poly; tol, x)` (src/sets.jl:647-655) for a batch: membership of the given point first, else the exemplar rule
+    (by `route`, see exemplar_slack_batch)."""
     out = np.zeros(len(polys), bool)
     rest = []
     for b, p in enumerate(polys):
@@ -649,7 +660,7 @@ def isempty_slack_batch(polys, engine, tol=1e-4, x=None):
             continue
         rest.append(b)
     if rest:
-        e, _, _ = exemplar_slack_batch([polys[b] for b in rest], engine, tol=tol)
+        e, _, _ = exemplar_slack_batch([polys[b] for b in rest], engine, tol=tol, route=route)
         out[rest] = e
     return out
 
@@ -871,6 +882,42 @@ def _exemplar_slack_lps(items, trips, engine, tol, slack_cap, strict, empty, exa
             empty[b] = bool(x[t, d] > tol)
             if not empty[b]:
                 example[b] = x[t, :d].copy()
+
+
+def _exemplar_slack_polyhedra(items, trips, opens, engine, tol, slack_cap, strict, empty, example, eps_out):
+    """exemplar_slack_batch on an engine with `exemplar_polys`: the items packed by shape (rows, columns), one call per shape; the
+    engine expands the slack LPs and applies the rule, open bounds included.  Fills empty, example, eps_out at `items`; an item
+    that ends in EX_ITER_LIMIT or EX_FAILURE raises (strict; the lowest-numbered one is named) or stays unanswered.
+    -> the items whose shape is beyond the kernel's limits (they take today's route)."""
+    from .engine import colmajor
+    packs, beyond = {}, []
+    for b in items:
+        n, d = trips[b][0].shape
+        if n < 1 or d < 1 or n > EX_MAX_N or d > EX_MAX_D:
+            beyond.append(b)
+        else:
+            packs.setdefault((n, d), []).append(b)
+    failed = []
+    for (n, d), members in sorted(packs.items()):
+        k = len(members)
+        A = np.stack([trips[b][0] for b in members]).reshape(k, n, d)
+        l = np.stack([trips[b][1] for b in members]).reshape(k, n); u = np.stack([trips[b][2] for b in members]).reshape(k, n)
+        ol = np.stack([opens[b][0] for b in members]).reshape(k, n).astype(np.uint8)
+        oh = np.stack([opens[b][1] for b in members]).reshape(k, n).astype(np.uint8)
+        res = engine.exemplar_polys(colmajor(A), l, u, ol, oh, tol=tol, slack_cap=slack_cap)
+        em = _to_host(res["empty"]); how = _to_host(res["how"]); eps = _to_host(res["eps"]); x = _to_host(res["x"])
+        for t, b in enumerate(members):
+            if how[t] in (EX_ITER_LIMIT, EX_FAILURE):
+                failed.append((b, int(how[t])))
+                continue                                    # (not strict: no answer for this item -- empty False, no example, eps nan)
+            eps_out[b] = eps[t]
+            empty[b] = bool(em[t])
+            if not empty[b]:
+                example[b] = x[t].copy()
+    if failed and strict:
+        b, how = min(failed)
+        raise RuntimeError(f"exemplar_slack_batch: exemplar status {how} on item {b}")
+    return beyond
 
 
 # ---- the LP solver (qpn_solve_lps): bounded-variable primal simplex, the numpy twin -----------------------------------------
@@ -1454,5 +1501,76 @@ def implicit_bounds_host(Ac, l, u, tol=1e-4, all_extremes=False, opts=None):
     for b in range(polys):
         got = _implicit_one(np.ascontiguousarray(Ac[b].T), l[b], u[b], float(tol), flags, o)
         for k, v in zip(("status", "fail_row", "eq", "vals", "how", "lo", "hi", "lps", "iters"), got):
+            out[k][b] = v
+    return out
+
+
+# ---- emptiness with open bounds (qpn_exemplar_polys): one job per polyhedron, the numpy twin -------------------------------------
+EX_MEMBER, EX_MEMBER_BAND, EX_EMPTY_SLACK, EX_EMPTY_OPEN, EX_ITER_LIMIT, EX_FAILURE = 0, 1, 2, 3, 4, 5
+EX_MAX_N, EX_MAX_D = 511, 255
+
+
+def exemplar_rows(A, l, u, slack_cap=1.0):
+    """The slack LP of `exemplar` (src/sets.jl:608-619) over {x : l <= A x <= u} (A [n, d] math layout) in the variables (x, eps):
+    rows i < n: [a_i, 1] >= l_i; rows n + i: [-a_i, 1] >= -u_i; row 2 n: eps >= -slack_cap.  -> (A2 [2 n + 1, d + 1], l2, u2 = +inf)."""
+    n, d = A.shape
+    A2 = np.zeros((2 * n + 1, d + 1)); l2 = np.empty(2 * n + 1)
+    A2[:n, :d] = A; A2[n:2 * n, :d] = -A; A2[:, d] = 1.0
+    l2[:n] = l; l2[n:2 * n] = -u; l2[2 * n] = -slack_cap
+    return A2, l2, np.full(2 * n + 1, INF)
+
+
+def _exemplar_one(A, l, u, open_lo, open_hi, tol, slack_cap, o):
+    """One polyhedron by the method of qpn_exemplar_polys (A [n, d] math layout, open_lo / open_hi [n] bool).
+    -> (empty, how, eps, x [d], row, lam [2 n + 1], iters)."""
+    n, d = A.shape
+    with np.errstate(all="ignore"):
+        A2, l2, u2 = exemplar_rows(A, l, u, slack_cap)                      # (a)
+        status, x, _, lam, _, iters = _lp_one(A2, l2, u2, 1.0 * A2[2 * n], o)
+        if status != LP_OPTIMAL:                                            # (c)
+            how = EX_ITER_LIMIT if status == LP_ITER_LIMIT else EX_FAILURE
+            return 0, how, np.nan, np.zeros(d), -1, np.zeros(2 * n + 1), iters
+        eps = x[d]                                                          # (b)
+        row = -1
+        if eps > tol:
+            how = EX_EMPTY_SLACK
+        elif eps > -tol:
+            act_lo = (np.abs(lam[:n]) > tol) & open_lo & (np.abs(l) < INF)
+            act_hi = (np.abs(lam[n:2 * n]) > tol) & open_hi & (np.abs(u) < INF)
+            ids = np.concatenate([2 * np.nonzero(act_lo)[0], 2 * np.nonzero(act_hi)[0] + 1])
+            how = EX_EMPTY_OPEN if ids.size else EX_MEMBER_BAND
+            if ids.size:
+                row = int(ids.min())
+        else:
+            how = EX_MEMBER
+    empty = how in (EX_EMPTY_SLACK, EX_EMPTY_OPEN)
+    return int(empty), how, eps, (np.zeros(d) if empty else x[:d]), row, lam, iters
+
+
+def exemplar_polys_host(Ac, l, u, open_lo=None, open_hi=None, tol=1e-2, slack_cap=1.0, opts=None):
+    """The numpy twin of Engine.exemplar_polys (qpn_exemplar_polys), the normative statement of the method; every output of the
+    kernel is bit-equal to it.  `exemplar` / `isempty` (src/sets.jl:591-655) with one job per polyhedron: Ac [polys, d, n] (ABI
+    layout), l, u [polys, n] (+-inf allowed), open_lo, open_hi [polys, n] (nonzero: that bound is open; None: closed).
+
+    (a) The slack LP in (x, eps) (exemplar_rows): min eps over [a_i, 1] >= l_i, [-a_i, 1] >= -u_i, eps >= -slack_cap, the objective
+    being the last row; solved as solve_lps_host solves a job (_lp_one: the data screen, the crash, the loop, step 9's check and
+    at most one rebuild).  (b) On the certified optimum, eps = x[d]: eps > tol is EX_EMPTY_SLACK; eps > -tol is the band, where a
+    bound is active when it is open, finite (an open flag on an infinite bound is ignored, src/sets.jl:354-356) and |lam_i| > tol
+    (the lower bound of row i) or |lam_{n+i}| > tol (the upper): any active bound is EX_EMPTY_OPEN with row = the lowest 2 i +
+    side, none EX_MEMBER_BAND; eps <= -tol is EX_MEMBER.  (c) LP_ITER_LIMIT is EX_ITER_LIMIT, every other end that is no certified
+    optimum EX_FAILURE (the data screen included; the slack LP is feasible and bounded below, so INFEASIBLE and UNBOUNDED cannot be
+    true answers): empty = 0, eps = NaN, x = 0, row = -1, lam = 0; iters is the count of the steps taken.
+    -> dict(empty [polys] uint8, how [polys] int32 (EX_*), eps [polys], x [polys, d] (a member; zeros when empty or unanswered),
+    row [polys] int32, lam [polys, 2 n + 1], iters [polys] int32)."""
+    Ac = np.asarray(Ac, dtype=np.float64); l = np.asarray(l, dtype=np.float64); u = np.asarray(u, dtype=np.float64)
+    polys, d, n = Ac.shape
+    flags = [np.zeros((polys, n), bool) if f is None else np.asarray(f).reshape(polys, n) != 0 for f in (open_lo, open_hi)]
+    o = dict(LP_DEFAULT_OPTS)
+    o.update(opts or {})
+    out = dict(empty=np.zeros(polys, np.uint8), how=np.zeros(polys, np.int32), eps=np.zeros(polys), x=np.zeros((polys, d)),
+               row=np.full(polys, -1, np.int32), lam=np.zeros((polys, 2 * n + 1)), iters=np.zeros(polys, np.int32))
+    for b in range(polys):
+        got = _exemplar_one(np.ascontiguousarray(Ac[b].T), l[b], u[b], flags[0][b], flags[1][b], float(tol), float(slack_cap), o)
+        for k, v in zip(("empty", "how", "eps", "x", "row", "lam", "iters"), got):
             out[k][b] = v
     return out

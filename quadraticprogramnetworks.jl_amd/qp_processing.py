@@ -17,6 +17,7 @@ INF = np.inf
 
 CONVEXITY_TOL = 1e-6                        # check_qp_convexity's tol (src/qp_processing.jl:39)
 IMPLICIT_BOUNDS_ROUTE = "jobs"              # implicit_bounds_batch's route for the convexity check: "jobs" or "polyhedron"
+EMPTINESS_ROUTE = "nodes"                   # isempty_slack_batch's route for combine's products: "nodes" or "polyhedron"
 
 
 class NonConvexQPError(RuntimeError):
@@ -264,7 +265,7 @@ def _combine_products(regions: List[List[Poly]], solutions: List[List[Poly]], x)
     return cols, ncols, prods
 
 
-def combine_many(jobs, x, engine, tol=1e-4):
+def combine_many(jobs, x, engine, tol=1e-4, route=None):
     """combine(regions, solutions, x) (src/qp_processing.jl:260-291) for ALL nodes of a level that are optimal under SEVERAL
     combinations of their children's pieces (x sits on a kink of a child's solution graph).  Per node
 
@@ -275,7 +276,7 @@ def combine_many(jobs, x, engine, tol=1e-4):
     lies in its closure and it is not empty (:74, :83), skipping products made of complement pieces only (the "redzone",
     :124).  Only candidates whose closure contains x can survive, so they alone are expanded; the emptiness questions of all
     nodes go to the engine as ONE batch of LPs (polyhedra.isempty_slack_batch: `isempty`, src/sets.jl:647-655 -> `exemplar`,
-    :591-642, open bounds included).  jobs: list of (regions, solutions); returns per job the list of pieces (global
+    :591-642, open bounds included; by `route`, None: the module's EMPTINESS_ROUTE).  jobs: list of (regions, solutions); returns per job the list of pieces (global
     coordinates) or the RuntimeError of the reference's size guard (:281-285) for the caller to turn into failed = true."""
     from .polyhedra import isempty_slack_batch
     prep, flat, owner = [], [], []
@@ -287,7 +288,7 @@ def combine_many(jobs, x, engine, tol=1e-4):
             continue
         prep.append((cols, ncols, prods))
         flat += prods; owner += [k] * len(prods)
-    empty = isempty_slack_batch(flat, engine, tol=tol) if flat else []
+    empty = isempty_slack_batch(flat, engine, tol=tol, route=EMPTINESS_ROUTE if route is None else route) if flat else []
     out = []
     for k, pr in enumerate(prep):
         if isinstance(pr, RuntimeError):
@@ -299,9 +300,9 @@ def combine_many(jobs, x, engine, tol=1e-4):
     return out
 
 
-def combine_at(regions: List[List[Poly]], solutions: List[List[Poly]], x, engine, tol=1e-4):
+def combine_at(regions: List[List[Poly]], solutions: List[List[Poly]], x, engine, tol=1e-4, route=None):
     """combine_many for one node; raises the size guard's RuntimeError."""
-    got = combine_many([(regions, solutions)], x, engine, tol=tol)[0]
+    got = combine_many([(regions, solutions)], x, engine, tol=tol, route=route)[0]
     if isinstance(got, RuntimeError):
         raise got
     return got
