@@ -1,17 +1,18 @@
 #!/usr/bin/env python3
-"""Writes tests/golden/lp_twin_record.json: what the numpy twins of the three LP entries (polyhedra.solve_lps_host,
+"""Writes tests/golden/lp_twin_record.json: what the numpy twins of the three LP entries (polyhedra_host.solve_lps_host,
 issubset_pairs_host, implicit_bounds_host) answer on the seeded families of the GPU suites -- the shapes, seeds and variants of
 the ..._equals_the_twin_bit_for_bit family tests of tests/test_gpu_lp.py, test_gpu_subset_pairs.py and test_gpu_implicit_bounds.py.
 For every output array the dtype, the shape and the SHA-256 of its C-contiguous bytes; the status / how histograms in clear, so
 that a mismatch can be read.
 
-The record pins the twin ACROSS commits: it is written from the polyhedra.py of the commit BEFORE a change to the twin and
+The record pins the twin ACROSS commits: it is written from the polyhedra_host.py of the commit BEFORE a change to the twin and
 tests/test_lp_host.py recomputes it with the working tree's.  From a checkout of that commit's file:
 
-    git show <parent>:quadraticprogramnetworks.jl_amd/polyhedra.py > /tmp/parent_polyhedra.py
-    python tests/golden/make_lp_twin_record.py --twin /tmp/parent_polyhedra.py
+    git show <parent>:quadraticprogramnetworks.jl_amd/polyhedra_host.py > /tmp/parent_polyhedra_host.py
+    python tests/golden/make_lp_twin_record.py --twin /tmp/parent_polyhedra_host.py
 
-(the twins need numpy alone).  Without --twin it reads the working tree's polyhedra.py.
+(the twins need numpy alone; before the twins had a module of their own the file was polyhedra.py).  Without --twin it reads the
+working tree's polyhedra_host.py.
 """
 import argparse
 import hashlib
@@ -31,7 +32,7 @@ import lp_cases  # noqa: E402
 import subset_cases  # noqa: E402
 
 RECORD = os.path.join(HERE, "lp_twin_record.json")
-TWIN = os.path.join(ROOT, "quadraticprogramnetworks.jl_amd", "polyhedra.py")
+TWIN = os.path.join(ROOT, "quadraticprogramnetworks.jl_amd", "polyhedra_host.py")
 LP_SHAPES = [(1, 1), (3, 2), (2, 3), (5, 2), (16, 8)]
 SUBSET_SHAPES = [(1, 1, 1), (3, 2, 2), (5, 4, 2), (16, 16, 8)]
 IB_SHAPES = [(1, 1), (3, 2), (8, 4), (16, 8)]
@@ -63,7 +64,7 @@ def digest(out):
 
 
 def record(twin):
-    """The record of one polyhedra module: {case name: digest}."""
+    """The record of one twin module: {case name: digest}."""
     cases = {}
     for shape in LP_SHAPES:
         seeds = list(range(40, 56))
@@ -88,7 +89,7 @@ def record(twin):
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
-    ap.add_argument("--twin", default=TWIN, help="the polyhedra.py to record (default: the working tree's)")
+    ap.add_argument("--twin", default=TWIN, help="the polyhedra_host.py to record (default: the working tree's)")
     ap.add_argument("--out", default=RECORD)
     a = ap.parse_args()
     cases = record(load_twin(a.twin))

@@ -15,7 +15,7 @@ import implicit_cases
 import lp_cases
 from implicit_cases import BY_EXTREMES, BY_POINTS, EMPTY, EXPLICIT, FAILURE, IMPLICIT, ITER_LIMIT, OK, PINNED, UNBOUNDED, UNDECIDED
 
-from qpn_amd import polyhedra
+from qpn_amd import polyhedra, polyhedra_host
 from qpn_amd.engine import colmajor
 
 INF = np.inf
@@ -197,8 +197,8 @@ def test_steps_1_to_8_do_not_see_crossed_bounds():
     two, so on {1 <= x <= 0} with c = 0 the loop ends OPTIMAL and only step 9's check objects (FAILURE, not INFEASIBLE)."""
     A = np.array([[1.0]]); l = np.array([1.0]); u = np.array([0.0])
     o = dict(polyhedra.LP_DEFAULT_OPTS)
-    S = polyhedra._lp_setup(A, l, u, np.zeros(1), o)
-    assert S.zbad is None and polyhedra._lp_loop(S) == polyhedra.LP_OPTIMAL
+    S = polyhedra_host._lp_setup(A, l, u, np.zeros(1), o)
+    assert S.zbad is None and polyhedra_host._lp_loop(S) == polyhedra.LP_OPTIMAL
     got = polyhedra.solve_lps_host(colmajor(A[None]), l[None], u[None], [0], cost=np.zeros((1, 1)))
     assert got["status"][0] == polyhedra.LP_FAILURE
     assert _one(A, l, u)["status"] == EMPTY

@@ -10,7 +10,7 @@ import pytest
 from scipy.optimize import linear_sum_assignment, linprog
 
 import qpn_amd  # noqa: F401
-from qpn_amd import polyhedra
+from qpn_amd import polyhedra, polyhedra_host
 from qpn_amd.engine import colmajor
 
 import degenerate_cases as dc
@@ -139,7 +139,7 @@ def test_the_cone_reaches_the_lowest_id_rule(monkeypatch):
     runs = {}
     assert polyhedra.LP_BLAND_AFTER == 20
     for bland in (20, 10 ** 9):
-        monkeypatch.setattr(polyhedra, "LP_BLAND_AFTER", bland)
+        monkeypatch.setattr(polyhedra_host, "LP_BLAND_AFTER", bland)       # (patched where _lp_loop reads it)
         for seed in range(10):
             A, l, u, c, x0 = dc.cone(seed, 130, 24)
             got = polyhedra.solve_lps_host(colmajor(A[None]), l[None], u[None], [0], cost=c[None])
@@ -179,13 +179,13 @@ def test_a_non_finite_row_of_the_second_piece_fails_the_pair():
 
 def _count_rebuilds(monkeypatch):
     n = [0]
-    real = polyhedra._lp_rebuild
+    real = polyhedra_host._lp_rebuild               # (patched where _lp_finish looks it up)
 
     def counted(S, c):
         n[0] += 1
         return real(S, c)
 
-    monkeypatch.setattr(polyhedra, "_lp_rebuild", counted)
+    monkeypatch.setattr(polyhedra_host, "_lp_rebuild", counted)
     return n
 
 

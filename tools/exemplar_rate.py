@@ -13,58 +13,17 @@ Today's route runs on the same engine with the method hidden.  Three rounds, the
 synchronise.  Prints one JSON line per measurement and one with the medians per workload and route.
 usage: python tools/exemplar_rate.py [--polys 2000] [--nodes 200] [--rounds 3]"""
 import argparse
-import json
-import os
-import sys
-import time
-import warnings
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+from rate_common import emit, examples, on_device, polyhedra, qpn_amd, quiet_solve, report, without
+from qpn_amd.engine import colmajor
+from qpn_amd.programs import Poly
 
-import qpn_amd  # noqa: E402
-from qpn_amd import algorithm, examples, polyhedra  # noqa: E402
-from qpn_amd.engine import colmajor  # noqa: E402
-from qpn_amd.programs import Poly  # noqa: E402
-
-import goldenio  # noqa: E402
-import lp_cases  # noqa: E402
+import goldenio
+import lp_cases
 
 TOL = 1e-4
-
-
-class WithoutExemplar:
-    """The engine without exemplar_polys: the host functions take today's route."""
-
-    def __init__(self, eng):
-        self._eng = eng
-
-    def __getattr__(self, name):
-        if name == "exemplar_polys":
-            raise AttributeError(name)
-        return getattr(self._eng, name)
-
-
-def timed(fn):
-    import torch
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    fn()
-    torch.cuda.synchronize()
-    return time.perf_counter() - t0
-
-
-def report(what, routes, rounds, **info):
-    times = {name: [] for name, _ in routes}
-    for rnd in range(rounds):
-        for name, fn in routes:
-            s = timed(fn)
-            times[name].append(s)
-            print(json.dumps(dict(what=what, route=name, round=rnd, seconds=s, **info)), flush=True)
-    print(json.dumps(dict(what=what, medians={name: float(np.median(v)) for name, v in times.items()}, **info)), flush=True)
 
 
 def kink_products(eng):
@@ -79,25 +38,22 @@ def kink_products(eng):
     c = goldenio.load("simple_bilevel_cases.json")
     polyhedra.isempty_slack_batch = capture
     try:
-        with warnings.catch_warnings():
-            warnings.simplefilter("ignore")
-            for w in c["w"]:
-                algorithm.solve(examples.setup("simple_bilevel", gen_solution_map=True), np.array(list(w) + c["x0"], float), engine=eng)
+        for w in c["w"]:
+            quiet_solve(examples.setup("simple_bilevel", gen_solution_map=True), np.array(list(w) + c["x0"], float), engine=eng)
     finally:
         polyhedra.isempty_slack_batch = real
     return seen
 
 
 def main():
-    import torch
     ap = argparse.ArgumentParser()
     ap.add_argument("--polys", type=int, default=2000)
     ap.add_argument("--nodes", type=int, default=200)
     ap.add_argument("--rounds", type=int, default=3)
     a = ap.parse_args()
     eng = qpn_amd.default_engine(0)
-    old = WithoutExemplar(eng)
-    print(json.dumps(dict(what="library", path=qpn_amd._lib.LIB_PATH)), flush=True)
+    old = without(eng, "exemplar_polys")                    # (the host functions take today's route)
+    emit(what="library", path=qpn_amd._lib.LIB_PATH)
 
     # (a) a level of kinked nodes: the products of the golden kinks, `--nodes` nodes in all
     kinks = kink_products(old)
@@ -127,8 +83,7 @@ def main():
            verdicts_differ=int(np.sum(answers["nodes"][0] != answers["polyhedron"][0])))
 
     # (c) the bare call over device tensors
-    dv = f"cuda:{eng.device}"
-    dev = tuple(torch.as_tensor(np.ascontiguousarray(v), device=dv) for v in (colmajor(A), l, u, ol.astype(np.uint8), oh.astype(np.uint8)))
+    dev = on_device(eng, (colmajor(A), l, u, ol.astype(np.uint8), oh.astype(np.uint8)))
     out = eng.exemplar_polys(*dev, tol=TOL)
     how = out["how"].cpu().numpy()
     report("gauss_24x12_open_bare", (("polyhedron_device", lambda: eng.exemplar_polys(*dev, tol=TOL)),), a.rounds, polys=a.polys,

@@ -12,53 +12,18 @@ Three rounds, the routes alternating in each; a host clock around a synchronise.
 with the medians per workload and route.
 usage: python tools/implicit_bounds_rate.py [--polys 2000] [--pairs 200] [--rounds 3] [--skip-solve]"""
 import argparse
-import json
-import os
-import sys
-import time
-import warnings
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+from rate_common import convexity_stacks, emit, examples, on_device, polyhedra, qpn_amd, quiet_solve, report
+from qpn_amd import qp_processing
+from qpn_amd.engine import colmajor
 
-import qpn_amd  # noqa: E402
-from qpn_amd import algorithm, examples, polyhedra, qp_processing  # noqa: E402
-from qpn_amd.engine import colmajor  # noqa: E402
-
-import lp_cases  # noqa: E402
-
-
-def timed(fn):
-    import torch
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    fn()
-    torch.cuda.synchronize()
-    return time.perf_counter() - t0
-
-
-def report(what, routes, rounds, **info):
-    times = {name: [] for name, _ in routes}
-    for rnd in range(rounds):
-        for name, fn in routes:
-            s = timed(fn)
-            times[name].append(s)
-            print(json.dumps(dict(what=what, route=name, round=rnd, seconds=s, **info)), flush=True)
-    print(json.dumps(dict(what=what, medians={name: float(np.median(v)) for name, v in times.items()}, **info)), flush=True)
+import lp_cases
 
 
 def measure(what, trips, eng, rounds, tol):
-    import torch
-    packs = {}
-    for A, l, u in trips:
-        packs.setdefault(A.shape, []).append((A, l, u))
-    dev = []
-    for (r, d), members in sorted(packs.items()):
-        arrs = (colmajor(np.stack([m[0] for m in members])), np.stack([m[1] for m in members]), np.stack([m[2] for m in members]))
-        dev.append(tuple(torch.as_tensor(np.ascontiguousarray(a), device=f"cuda:{eng.device}") for a in arrs))
+    dev = [on_device(eng, (colmajor(A), l, u)) for _, _, A, l, u in polyhedra.pack_by_shape(trips)[0]]
 
     def bare():
         return [eng.implicit_bounds(*args, tol=tol) for args in dev]
@@ -85,7 +50,7 @@ def main():
     ap.add_argument("--skip-solve", action="store_true")
     a = ap.parse_args()
     eng = qpn_amd.default_engine(0)
-    print(json.dumps(dict(what="library", path=qpn_amd._lib.LIB_PATH)), flush=True)
+    emit(what="library", path=qpn_amd._lib.LIB_PATH)
     tol = 1e-6
 
     # (a) the three workloads of the CPU count
@@ -104,22 +69,8 @@ def main():
     measure("pinned_30x24", pinned, eng, a.rounds, tol)
 
     # (b) the stacks of check_convexity
-    seen = []
-    real = polyhedra.implicit_bounds_batch
-
-    def capture(polys, engine, tol=1e-4, **kw):
-        seen.append([tuple(np.asarray(v, dtype=np.float64) for v in p) for p in polys])
-        return real(polys, engine, tol=tol, **kw)
-
     net = lambda: examples.setup("synthetic_pairs", pairs=a.pairs, n=16, m=16, check_convexity=True)
-    polyhedra.implicit_bounds_batch = capture
-    try:
-        with warnings.catch_warnings():
-            warnings.simplefilter("ignore")
-            algorithm.solve(net(), engine=eng)
-    finally:
-        polyhedra.implicit_bounds_batch = real
-    stacks = [(np.atleast_2d(A), l, u) for A, l, u in max(seen, key=len)]
+    stacks = [(np.atleast_2d(A), l, u) for A, l, u in convexity_stacks(eng, a.pairs)]
     measure("stacks_16x16", stacks, eng, a.rounds, qp_processing.CONVEXITY_TOL)
 
     # (c) solve() with the option on, by either route
@@ -130,9 +81,7 @@ def main():
         def run():
             qp_processing.IMPLICIT_BOUNDS_ROUTE = route
             try:
-                with warnings.catch_warnings():
-                    warnings.simplefilter("ignore")
-                    r = algorithm.solve(net(), engine=eng)
+                r = quiet_solve(net(), engine=eng)
             finally:
                 qp_processing.IMPLICIT_BOUNDS_ROUTE = "jobs"
             assert r["solved"]

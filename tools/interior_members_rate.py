@@ -10,19 +10,12 @@ The three routes alternate, `--rounds` times; every time is a host clock around 
 moved per query are computed from the shapes.  Prints one JSON line per measurement.
 usage: python tools/interior_members_rate.py [--queries 20000] [--rounds 3]"""
 import argparse
-import json
-import os
-import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-import qpn_amd  # noqa: E402
-from qpn_amd import polyhedra  # noqa: E402
-from qpn_amd.engine import colmajor  # noqa: E402
+from rate_common import emit, on_device, polyhedra, qpn_amd
+from qpn_amd.engine import colmajor
 
 DELTA = 1e-2
 
@@ -43,7 +36,6 @@ def main():
     a = ap.parse_args()
     import torch
     eng = qpn_amd.default_engine(0)
-    dv = "cuda:0"
     B = a.queries
     A, l, u = queries(B)
     r, d = A.shape[1:]
@@ -52,10 +44,10 @@ def main():
     mp = max(16, -(-(nlo + nhi) // 16) * 16)
     N = nf + mp
     rec_bytes = 8 * (nf * nf + nf + nf * mp + 2 * mp)
-    print(json.dumps(dict(what="bytes_per_query", r=r, d=d, nf=nf, mp=mp, polyhedron=8 * (r * d + 2 * r), record=rec_bytes,
-                          records_host_up=rec_bytes + 8 * (nf + mp + 1), records_host_down=8 * N + 4 + 8 + 4 + N,
-                          members_host_up=8 * (r * d + 2 * r), members_host_down=8 * d + 1 + 4, members_dev_pcie=0,
-                          assembly_hbm_written=rec_bytes + 1, assembly_hbm_read=8 * (r * d + 2 * r))), flush=True)
+    emit(what="bytes_per_query", r=r, d=d, nf=nf, mp=mp, polyhedron=8 * (r * d + 2 * r), record=rec_bytes,
+         records_host_up=rec_bytes + 8 * (nf + mp + 1), records_host_down=8 * N + 4 + 8 + 4 + N,
+         members_host_up=8 * (r * d + 2 * r), members_host_down=8 * d + 1 + 4, members_dev_pcie=0,
+         assembly_hbm_written=rec_bytes + 1, assembly_hbm_read=8 * (r * d + 2 * r))
 
     def records_host():
         Qc, qd, Ac, ll, uu = polyhedra.interior_member_records(A, l, u, DELTA)
@@ -67,7 +59,7 @@ def main():
         x, ok, _ = eng.interior_members(colmajor(A), l, u, DELTA, ne, nlo, nhi)
         return x, ok.astype(bool)
 
-    Ad, ld, ud = (torch.as_tensor(v, device=dv) for v in (colmajor(A), l, u))
+    Ad, ld, ud = on_device(eng, (colmajor(A), l, u))
 
     def members_dev():
         x, ok, _ = eng.interior_members(Ad, ld, ud, DELTA, ne, nlo, nhi)
@@ -89,7 +81,7 @@ def main():
     A, l, u, B = A_, l_, u_, A_.shape[0]
     for f in (members_dev, assemble_dev):
         f()
-    print(json.dumps(dict(what="routes_agree_bitwise", queries=int(small.stop), same=same, members=int(ok0.sum()))), flush=True)
+    emit(what="routes_agree_bitwise", queries=int(small.stop), same=same, members=int(ok0.sum()))
     for rnd in range(a.rounds):
         for name, f in routes.items():
             t0 = time.perf_counter()
@@ -101,7 +93,7 @@ def main():
             else:
                 line["members"] = int(np.asarray(out[1].cpu() if hasattr(out[1], "cpu") else out[1]).sum())
             del out
-            print(json.dumps(line), flush=True)
+            emit(**line)
 
 
 if __name__ == "__main__":

@@ -11,31 +11,12 @@ In a checkout whose engine has no solve_lps (the commit before this solver: copy
 run, so one job can alternate the two checkouts.  Prints one JSON line per measurement.
 usage: python tools/lp_rate.py [--pairs 200] [--polys 2000] [--avi-polys 100] [--reps 3]"""
 import argparse
-import json
-import os
-import sys
 import time
-import warnings
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-import qpn_amd  # noqa: E402
-from qpn_amd import algorithm, examples, polyhedra  # noqa: E402
-from qpn_amd.engine import colmajor  # noqa: E402
-
-
-class WithoutLps:
-    """The engine without solve_lps: the host functions take the node-AVI route."""
-    def __init__(self, eng):
-        self._eng = eng
-
-    def __getattr__(self, name):
-        if name == "solve_lps":
-            raise AttributeError(name)
-        return getattr(self._eng, name)
+from rate_common import convexity_stacks, emit, examples, on_device, polyhedra, qpn_amd, quiet_solve, without
+from qpn_amd.engine import colmajor
 
 
 def median_time(fn, reps):
@@ -48,11 +29,10 @@ def median_time(fn, reps):
     return float(np.median(ts))
 
 
-def row_jobs(trips):
-    """Polyhedra of one shape -> (A, l, u, poly_of, obj_row, obj_sign): every (row, sign) a job."""
-    A = np.stack([t[0] for t in trips]); l = np.stack([t[1] for t in trips]); u = np.stack([t[2] for t in trips])
+def row_jobs(A, l, u):
+    """A pack of polyhedra of one shape -> (Ac, l, u, poly_of, obj_row, obj_sign): every (row, sign) a job."""
     B, r, _ = A.shape
-    return (A, l, u, np.repeat(np.arange(B), 2 * r).astype(np.int32), np.tile(np.repeat(np.arange(r), 2), B).astype(np.int32),
+    return (colmajor(A), l, u, np.repeat(np.arange(B), 2 * r).astype(np.int32), np.tile(np.repeat(np.arange(r), 2), B).astype(np.int32),
             np.tile([1, -1], B * r).astype(np.int32))
 
 
@@ -60,13 +40,9 @@ def bare_calls(eng, what, trips, reps, has_lps):
     if not has_lps:
         return
     import torch
-    by_shape = {}
-    for t in trips:
-        by_shape.setdefault(t[0].shape, []).append(t)
-    packs = [row_jobs(ts) for _, ts in sorted(by_shape.items())]
-    jobs = sum(len(p[3]) for p in packs)
-    host = [(colmajor(p[0]),) + p[1:] for p in packs]
-    dev = [tuple(torch.as_tensor(np.ascontiguousarray(a), device=f"cuda:{eng.device}") for a in h) for h in host]
+    host = [row_jobs(A, l, u) for _, _, A, l, u in polyhedra.pack_by_shape(trips)[0]]
+    jobs = sum(len(p[3]) for p in host)
+    dev = [on_device(eng, h) for h in host]
 
     def run(args):
         for Ac, l, u, po, row, sg in args:
@@ -75,7 +51,7 @@ def bare_calls(eng, what, trips, reps, has_lps):
 
     for mode, args in (("host", host), ("device", dev)):
         s = median_time(lambda: run(args), reps)
-        print(json.dumps(dict(what=what, route="solve_lps_" + mode, jobs=jobs, calls=len(args), median_s=s, jobs_per_s=jobs / s)), flush=True)
+        emit(what=what, route="solve_lps_" + mode, jobs=jobs, calls=len(args), median_s=s, jobs_per_s=jobs / s)
 
 
 def main():
@@ -87,29 +63,16 @@ def main():
     a = ap.parse_args()
     eng = qpn_amd.default_engine(0)
     has_lps = callable(getattr(eng, "solve_lps", None))
-    plain = WithoutLps(eng)
-    print(json.dumps(dict(what="library", path=qpn_amd._lib.LIB_PATH, has_solve_lps=bool(has_lps))), flush=True)
+    plain = without(eng, "solve_lps")                       # (the host functions take the node-AVI route)
+    emit(what="library", path=qpn_amd._lib.LIB_PATH, has_solve_lps=bool(has_lps))
 
     # (a) the stacks of check_convexity
-    seen = []
     real = polyhedra.implicit_bounds_batch
-
-    def capture(polys, engine, tol=1e-4, **kw):
-        seen.append([tuple(np.asarray(v, dtype=np.float64) for v in p) for p in polys])
-        return real(polys, engine, tol=tol, **kw)
-
-    polyhedra.implicit_bounds_batch = capture
-    try:
-        with warnings.catch_warnings():
-            warnings.simplefilter("ignore")
-            algorithm.solve(examples.setup("synthetic_pairs", pairs=a.pairs, n=16, m=16, check_convexity=True), engine=plain)
-    finally:
-        polyhedra.implicit_bounds_batch = real
-    stacks = max(seen, key=len)
+    stacks = convexity_stacks(plain, a.pairs)
     shapes = sorted({t[0].shape for t in stacks})
     for route, e in (("avi", plain),) + ((("lp", eng),) if has_lps else ()):
         s = median_time(lambda: real(stacks, e), a.reps)
-        print(json.dumps(dict(what="stacks_implicit_bounds", route=route, polys=len(stacks), shapes=shapes[:4], median_s=s)), flush=True)
+        emit(what="stacks_implicit_bounds", route=route, polys=len(stacks), shapes=shapes[:4], median_s=s)
     bare_calls(eng, "stacks_rows", stacks, a.reps, has_lps)
 
     # (b) Gaussian polyhedra, row objectives
@@ -120,25 +83,20 @@ def main():
     bare_calls(eng, "gauss_48x24_rows", gauss, a.reps, has_lps)
     few = gauss[:a.avi_polys]
     s = median_time(lambda: real(few, plain), 1)
-    print(json.dumps(dict(what="gauss_48x24_implicit_bounds", route="avi", polys=len(few), jobs=96 * len(few), median_s=s,
-                          jobs_per_s=96 * len(few) / s)), flush=True)
+    emit(what="gauss_48x24_implicit_bounds", route="avi", polys=len(few), jobs=96 * len(few), median_s=s, jobs_per_s=96 * len(few) / s)
     if has_lps:
         s = median_time(lambda: real(few, eng), 1)
-        print(json.dumps(dict(what="gauss_48x24_implicit_bounds", route="lp", polys=len(few), jobs=96 * len(few), median_s=s,
-                              jobs_per_s=96 * len(few) / s)), flush=True)
+        emit(what="gauss_48x24_implicit_bounds", route="lp", polys=len(few), jobs=96 * len(few), median_s=s, jobs_per_s=96 * len(few) / s)
 
     # (c) solve() with and without the check
     for check in (False, True):
         for route, e in (("avi", plain),) + ((("lp", eng),) if has_lps else ()):
             if not check and route == "lp":
                 continue
-            with warnings.catch_warnings():
-                warnings.simplefilter("ignore")
-                t0 = time.perf_counter()
-                r = algorithm.solve(examples.setup("synthetic_pairs", pairs=a.pairs, n=16, m=16, check_convexity=check), engine=e)
-                dt = time.perf_counter() - t0
-            print(json.dumps(dict(what="solve", pairs=a.pairs, n=16, m=16, check_convexity=check, route=route if check else "-",
-                                  solved=bool(r["solved"]), seconds=dt)), flush=True)
+            t0 = time.perf_counter()
+            r = quiet_solve(examples.setup("synthetic_pairs", pairs=a.pairs, n=16, m=16, check_convexity=check), engine=e)
+            dt = time.perf_counter() - t0
+            emit(what="solve", pairs=a.pairs, n=16, m=16, check_convexity=check, route=route if check else "-", solved=bool(r["solved"]), seconds=dt)
 
 
 if __name__ == "__main__":

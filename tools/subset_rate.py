@@ -13,38 +13,19 @@ issubset_batch_chunked (host arrays) and as the bare call over device tensors.
 Three rounds, the routes alternating in each; a host clock around a synchronise.  Prints one JSON line per measurement.
 usage: python tools/subset_rate.py [--pairs 2000] [--scaled 200] [--net-pairs 250] [--rounds 3] [--skip-gauss] [--level-cap 2000]"""
 import argparse
-import json
-import os
-import sys
 import time
-import warnings
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-import qpn_amd  # noqa: E402
-from qpn_amd import algorithm, examples, polyhedra  # noqa: E402
-
-
-class WithoutPairs:
-    """The engine without issubset_pairs: issubset_batch builds its emptiness queries."""
-    def __init__(self, eng):
-        self._eng = eng
-
-    def __getattr__(self, name):
-        if name == "issubset_pairs":
-            raise AttributeError(name)
-        return getattr(self._eng, name)
+from rate_common import algorithm, emit, examples, on_device, polyhedra, qpn_amd, quiet_solve, report, without
 
 
 def measure(what, pairs, eng, rounds):
     import torch
-    old = WithoutPairs(eng)
-    calls, beyond = polyhedra._subset_packs(pairs)
+    old = without(eng, "issubset_pairs")                    # (issubset_batch builds its emptiness queries)
+    calls, beyond = polyhedra.subset_packs(pairs)
     assert not beyond
-    dev = [tuple(torch.as_tensor(np.ascontiguousarray(a), device=f"cuda:{eng.device}") for a in args) for _, args in calls]
+    dev = [on_device(eng, args) for _, args in calls]
 
     def bare():
         outs = [eng.issubset_pairs(*args) for args in dev]
@@ -64,14 +45,7 @@ def measure(what, pairs, eng, rounds):
                 verdicts_differ=int(np.sum(answers["pairs_host"] != answers["queries"])),
                 lps=int(sum(int(o["lps"].sum()) for o in answers["pairs_device"])),
                 iters=int(sum(int(o["iters"].sum()) for o in answers["pairs_device"])))
-    for rnd in range(rounds):
-        for name, fn in routes:
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            fn()
-            torch.cuda.synchronize()
-            s = time.perf_counter() - t0
-            print(json.dumps(dict(what=what, route=name, round=rnd, seconds=s, pairs_per_s=len(pairs) / s, **info)), flush=True)
+    report(what, routes, rounds, medians=False, per=lambda s: dict(pairs_per_s=len(pairs) / s), **info)
 
 
 def main():
@@ -84,7 +58,7 @@ def main():
     ap.add_argument("--level-cap", type=int, default=2000, help="at most this many pairs of a level set are timed")
     a = ap.parse_args()
     eng = qpn_amd.default_engine(0)
-    print(json.dumps(dict(what="library", path=qpn_amd._lib.LIB_PATH)), flush=True)
+    emit(what="library", path=qpn_amd._lib.LIB_PATH)
 
     # (a) Gaussian pieces
     rng = np.random.default_rng(0)
@@ -120,11 +94,9 @@ def main():
     polyhedra.issubset_batch_chunked = capture
     algorithm.remove_subsets_many = recording
     try:
-        with warnings.catch_warnings():
-            warnings.simplefilter("ignore")
-            t0 = time.perf_counter()
-            r = algorithm.solve(examples.setup("synthetic_pairs", pairs=a.net_pairs, n=32, m=32), engine=eng)
-            dt = time.perf_counter() - t0
+        t0 = time.perf_counter()
+        r = quiet_solve(examples.setup("synthetic_pairs", pairs=a.net_pairs, n=32, m=32), engine=eng)
+        dt = time.perf_counter() - t0
     finally:
         algorithm.remove_subsets_many = real_many
     undecided = list(seen)
@@ -136,8 +108,8 @@ def main():
         polyhedra.issubset_batch_chunked = real
     every = list(seen)[:a.level_cap]
     seen = undecided[:a.level_cap]
-    print(json.dumps(dict(what="solve", pairs=a.net_pairs, n=32, m=32, solved=bool(r["solved"]), seconds=dt, undecided_pairs=len(undecided),
-                          timed_undecided=len(seen), timed_all_pairs=len(every))), flush=True)
+    emit(what="solve", pairs=a.net_pairs, n=32, m=32, solved=bool(r["solved"]), seconds=dt, undecided_pairs=len(undecided),
+         timed_undecided=len(seen), timed_all_pairs=len(every))
     if seen:
         measure("level_undecided", seen, eng, a.rounds)
     if every:
