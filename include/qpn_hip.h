@@ -642,11 +642,43 @@ enum {
     QPN_EX_EMPTY_SLACK = 2,  /* eps > tol                                                                empty = 1 */
     QPN_EX_EMPTY_OPEN = 3,   /* -tol < eps <= tol and an open, finite bound is active (row names it)     empty = 1 */
     QPN_EX_ITER_LIMIT = 4,   /* the iteration limit was reached: no answer                               empty = 0 */
-    QPN_EX_FAILURE = 5       /* the data screen, or an end that is no certified optimum: no answer       empty = 0 */
+    QPN_EX_FAILURE = 5,      /* the data screen, or an end that is no certified optimum: no answer       empty = 0 */
+    QPN_EX_NOT_NEAR = 6      /* qpn_exemplar_products: the point is outside the product's closure         empty = 0 */
 };
 int qpn_exemplar_polys(qpn_ctx *ctx, int32_t polys, int32_t n, int32_t d, const double *A, const double *l, const double *u,
                        const uint8_t *open_lo, const uint8_t *open_hi, double tol, double slack_cap, const qpn_lp_opts *opts,
                        uint8_t *empty, int32_t *how, double *eps, double *x, int32_t *row, double *lambda, int32_t *iters, int mem);
+
+/* qpn_exemplar_products: the emptiness test of the intersection tree (`combine`, src/qp_processing.jl:260-291; src/intersection.jl:66-105:
+ * a product of pieces is kept when the current point lies in its closure, :74, and it is not empty, :83) for `products` products of
+ * pieces, one job per product.  The pieces are runs of rows of one pool that goes up once: A [rows][d], l, u [rows] (+-inf allowed),
+ * open_lo, open_hi [rows] uint8 (NULL: closed), piece_row [pieces + 1] int32 ascending, piece p = the pool rows piece_row[p] ..
+ * piece_row[p + 1] - 1 (an empty piece is allowed).  The unit of the pool is the ROW, not the polyhedron, so A is ROW-major: entry c of
+ * row i is at i * d + c -- unlike the per-item column-major A of the entries above.  factors [products][k] int32: product t is the
+ * intersection of the pieces factors[t][0 .. k - 1] in slot order, -1 = no factor in that slot; its rows are the factors' rows one
+ * after the other, `n` in all, the same n for every product of a call (the caller groups by n).  point [points][d], point_of [products]
+ * int32: the point whose closure test product t takes; both NULL: no closure test, every product is near.
+ * Outputs (how, eps, x, row, lambda, iters may be NULL): near [products] uint8, and empty, how, eps, x [products][d], row, lambda
+ * [products][2 n + 1], iters as qpn_exemplar_polys gives them for the polyhedron of the product's n rows; row counts product rows.
+ * Method (polyhedra.exemplar_products_host is its numpy twin and the normative statement; every output is bit-equal to it):
+ * (a) gather: the job writes the map product row i -> pool row into its own region of the context workspace.  (b) closure test, when
+ * point is given: per product row s_i = a_i'p over the ascending columns, acc = acc + a * p, no contraction; the product is near when
+ * l_i - point_tol <= s_i and s_i - point_tol <= u_i on every row -- closed relations whatever the open flags.  A product that is not
+ * near answers near = 0, how = QPN_EX_NOT_NEAR, empty = 0, eps = NaN, x = 0, lambda = 0, iters = 0 and row = the lowest 2 i + side
+ * violated (a comparison with a NaN counts as violated); no LP is started.  (c) otherwise near = 1 and the job runs the method of
+ * qpn_exemplar_polys on the n gathered rows and their flags: it writes the slack LP of 2 n + 1 rows in d + 1 variables into its region
+ * and solves it; the rule, the outputs and the codes are those of QPN_EX_*.  (d) a product is bad when a factor is outside [-1, pieces),
+ * when a factor's piece_row entries are not 0 <= first <= last <= rows, when its factors' rows do not add up to n, or when its point_of
+ * is outside [0, points).  Host arrays: QPN_ERR_ARG.  Device arrays: that product answers near = 0, empty = 0, QPN_EX_FAILURE, eps =
+ * NaN, row = -1, zeros elsewhere, and nothing is read through the bad index.
+ * Kernel classes are those of qpn_lp_kernel_class(2 n + 1, d + 1); a call whose regions exceed the workspace chunk is launched in
+ * chunks.  1 <= n <= 511, 1 <= d <= 255, 1 <= k <= 32 (QPN_ERR_SIZE beyond).  max_iters <= 0: 50 (2 n + d + 2) + 100.  products == 0
+ * succeeds. */
+int qpn_exemplar_products(qpn_ctx *ctx, int32_t d, int32_t rows, const double *A, const double *l, const double *u,
+                          const uint8_t *open_lo, const uint8_t *open_hi, int32_t pieces, const int32_t *piece_row, int32_t products,
+                          int32_t n, int32_t k, const int32_t *factors, int32_t points, const double *point, const int32_t *point_of,
+                          double point_tol, double tol, double slack_cap, const qpn_lp_opts *opts, uint8_t *near, uint8_t *empty,
+                          int32_t *how, double *eps, double *x, int32_t *row, double *lambda, int32_t *iters, int mem);
 
 #ifdef __cplusplus
 }

@@ -446,6 +446,45 @@ function exemplar_polys(A::Array{Float64,3}, l::Matrix{Float64}, u::Matrix{Float
     (empty, how, eps, x, row, lam, iters)
 end
 
+"""
+    exemplar_products(A, l, u, piece_row, factors, n; open_lo=nothing, open_hi=nothing, point=nothing, point_of=nothing,
+                      point_tol=1e-6, tol=1e-2, slack_cap=1.0, max_iters=0) -> (near, empty, how, eps, x, row, lambda, iters)
+
+qpn_exemplar_products: the test of the intersection tree (src/intersection.jl:66-105) for products of pieces, one job per product.
+The pieces are runs of rows of one pool: A [d, rows] (a pool row is a COLUMN of the Julia matrix, which is the row-major pool of the
+ABI), l, u [rows], open_lo, open_hi [rows] (Bool or UInt8; nothing: closed), piece_row [pieces + 1] 0-based and ascending: piece p
+(0-based) = the pool rows piece_row[p] .. piece_row[p + 1] - 1.  factors [k, products] Int32: the 0-based pieces of a product in slot
+order, -1 = no factor in that slot; the rows of every product add up to n.  point [d, points] and point_of [products] (0-based), or
+both nothing: the closure test l - point_tol <= a'p <= u + point_tol on every row; a product that fails it has near = 0, how = 6 and
+row = the lowest 2 i + side violated, and no LP is solved for it.  The other outputs are those of exemplar_polys for the polyhedron
+of the product's rows.  n <= 511, d <= 255, k <= 32.
+"""
+function exemplar_products(A::Matrix{Float64}, l::Vector{Float64}, u::Vector{Float64}, piece_row::Vector{Int32}, factors::Matrix{Int32},
+                           n::Integer; open_lo::Union{Nothing,AbstractVector} = nothing, open_hi::Union{Nothing,AbstractVector} = nothing,
+                           point::Union{Nothing,Matrix{Float64}} = nothing, point_of::Union{Nothing,Vector{Int32}} = nothing,
+                           point_tol::Float64 = 1e-6, tol::Float64 = 1e-2, slack_cap::Float64 = 1.0, max_iters::Integer = 0)
+    d, rows = size(A)
+    k, products = size(factors)
+    length(l) == rows && length(u) == rows && length(piece_row) >= 1 || error("exemplar_products: inconsistent shapes")
+    (point === nothing) == (point_of === nothing) || error("exemplar_products: point and point_of go together")
+    point === nothing || (size(point, 1) == d && length(point_of) == products) || error("exemplar_products: inconsistent shapes")
+    flags(o) = o === nothing ? nothing : (length(o) == rows || error("exemplar_products: inconsistent shapes"); Vector{UInt8}(o .!= 0))
+    olo = flags(open_lo); ohi = flags(open_hi)
+    opts = Ref((1e-9, 1e-9, 1e-9, 1e-6, Int32(max_iters), Int32(0)))      # qpn_lp_opts
+    near = zeros(UInt8, products); empty = zeros(UInt8, products); how = zeros(Int32, products); eps = zeros(products)
+    x = zeros(d, products); row = zeros(Int32, products); lam = zeros(2n + 1, products); iters = zeros(Int32, products)
+    rc = ccall((:qpn_exemplar_products, LIB), Cint,
+               (Ptr{Cvoid}, Int32, Int32, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{UInt8}, Ptr{UInt8}, Int32, Ptr{Int32}, Int32, Int32,
+                Int32, Ptr{Int32}, Int32, Ptr{Cdouble}, Ptr{Int32}, Cdouble, Cdouble, Cdouble, Ptr{Cvoid}, Ptr{UInt8}, Ptr{UInt8},
+                Ptr{Int32}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int32}, Ptr{Cdouble}, Ptr{Int32}, Cint),
+               ctx(), d, rows, A, l, u, olo === nothing ? C_NULL : olo, ohi === nothing ? C_NULL : ohi, length(piece_row) - 1, piece_row,
+               products, n, k, factors, point === nothing ? 0 : size(point, 2), point === nothing ? C_NULL : point,
+               point_of === nothing ? C_NULL : point_of, point_tol, tol, slack_cap, opts, near, empty, how, eps, x, row, lam, iters,
+               QPN_MEM_HOST)
+    rc == 0 || error("qpn_exemplar_products failed ($rc)")
+    (near, empty, how, eps, x, row, lam, iters)
+end
+
 function verify_nodes(nodes::Nodes, xd::Matrix{Float64}, w::VecOrMat{Float64}; tol::Float64 = 1e-4)
     solution = zeros(Int32, nodes.batch); path = zeros(Int32, nodes.batch); lambda = zeros(max(nodes.m, 1), nodes.batch)
     rc = ccall((:qpn_verify_nodes_h, LIB), Cint,

@@ -1896,6 +1896,66 @@ int qpn_exemplar_polys(qpn_ctx *ctx, int32_t polys, int32_t n, int32_t d, const 
     return st.finish();
 }
 
+int qpn_exemplar_products(qpn_ctx *ctx, int32_t d, int32_t rows, const double *A, const double *l, const double *u,
+                          const uint8_t *open_lo, const uint8_t *open_hi, int32_t pieces, const int32_t *piece_row, int32_t products,
+                          int32_t n, int32_t k, const int32_t *factors, int32_t points, const double *point, const int32_t *point_of,
+                          double point_tol, double tol, double slack_cap, const qpn_lp_opts *opts, uint8_t *near, uint8_t *empty,
+                          int32_t *how, double *eps, double *x, int32_t *row, double *lambda, int32_t *iters, int mem)
+{
+    if (!ctx) return QPN_ERR_ARG;
+    if (products < 0 || rows < 0 || pieces < 0 || points < 0 || n <= 0 || d <= 0 || k <= 0) return fail_arg(ctx, "qpn_exemplar_products: bad sizes");
+    if (n > QPN_EX_MAX_N || d > QPN_EX_MAX_D || k > QPN_PROD_MAX_K) {
+        ctx->last_error = "qpn_exemplar_products: n <= 511, d <= 255, k <= 32 in ABI v1";
+        return QPN_ERR_SIZE;
+    }
+    Stage st(ctx, mem, "qpn_exemplar_products");
+    if (int rc = st.check()) return rc;
+    if (products == 0) return QPN_OK;
+    if (!A || !l || !u || !piece_row || !factors || !near || !empty || rows == 0 || pieces == 0)
+        return fail_arg(ctx, "qpn_exemplar_products: null pointer");
+    if ((point == nullptr) != (point_of == nullptr) || (point && points == 0))
+        return fail_arg(ctx, "qpn_exemplar_products: point and point_of go together");
+    // host index arrays are checked here; device ones by the kernel (such a product answers QPN_EX_FAILURE)
+    if (st.host) {
+        for (int p = 0; p <= pieces; ++p)
+            if (piece_row[p] < (p ? piece_row[p - 1] : 0) || piece_row[p] > rows) return fail_arg(ctx, "qpn_exemplar_products: piece_row not ascending within the pool");
+        for (int t = 0; t < products; ++t) {
+            int64_t total = 0;
+            for (int s = 0; s < k; ++s) {
+                const int32_t f = factors[(size_t)t * k + s];
+                if (f < -1 || f >= pieces) return fail_arg(ctx, "qpn_exemplar_products: factor out of range");
+                if (f >= 0) total += piece_row[f + 1] - piece_row[f];
+            }
+            if (total != n) return fail_arg(ctx, "qpn_exemplar_products: a product's rows do not add up to n");
+            if (point_of && (point_of[t] < 0 || point_of[t] >= points)) return fail_arg(ctx, "qpn_exemplar_products: point_of out of range");
+        }
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t P = (size_t)products, R = 2 * (size_t)n + 1;
+    ProdArgs a{};
+    a.d = d; a.rows = rows; a.pieces = pieces; a.products = products; a.n = n; a.k = k; a.points = points;
+    a.point_tol = point_tol; a.tol = tol; a.slack_cap = slack_cap;
+    a.lp = lp_tol(opts, 2 * n + 1, d + 1);
+    void *gws;
+    st.in(a.A, A, (size_t)rows * d * 8); st.in(a.l, l, (size_t)rows * 8); st.in(a.u, u, (size_t)rows * 8);
+    st.in(a.open_lo, open_lo, (size_t)rows); st.in(a.open_hi, open_hi, (size_t)rows);
+    st.in(a.piece_row, piece_row, ((size_t)pieces + 1) * 4); st.in(a.factors, factors, P * k * 4);
+    st.in(a.point, point, (size_t)points * d * 8); st.in(a.point_of, point_of, P * 4);
+    st.out(a.near, near, P);
+    st.out(a.empty, empty, P);
+    st.out_opt(a.how, how, P * 4);
+    st.out_opt(a.eps, eps, P * 8);
+    st.out_opt(a.x, x, P * d * 8);
+    st.out_opt(a.row, row, P * 4);
+    st.out_opt(a.lam, lambda, P * R * 8);
+    st.out_opt(a.iters, iters, P * 4);
+    st.scratch(gws, qpn_products_workspace_bytes(products, n, d));
+    int rc = st.begin();
+    if (rc != QPN_OK) return rc;
+    HIPCHK(ctx, qpn_launch_exemplar_products(a, gws, ctx->stream));
+    return st.finish();
+}
+
 } // extern "C"
 
 namespace {

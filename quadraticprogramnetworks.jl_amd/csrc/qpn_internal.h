@@ -345,6 +345,30 @@ struct ExArgs {
 #define QPN_EX_MAX_D 255
 size_t qpn_exemplar_workspace_bytes(int32_t polys, int32_t n, int32_t d);
 hipError_t qpn_launch_exemplar_polys(const ExArgs &a, void *gws, hipStream_t s);      // gws: qpn_exemplar_workspace_bytes(polys, n, d)
+// ... and of products of pieces (qpn_exemplar_products), one job per product: the factors' rows, n in all, gathered from a pool of
+// rows (A [rows][d] ROW-major) into the job's slack LP.  open_lo, open_hi null: closed;  point, point_of null: no closure test;
+// how, eps, x, row, lam, iters may be null.
+struct ProdArgs {
+    int32_t d, rows, pieces, products, n, k, points;
+    const double *A, *l, *u;
+    const uint8_t *open_lo, *open_hi;
+    const int32_t *piece_row, *factors;
+    const double *point;
+    const int32_t *point_of;
+    double point_tol, tol, slack_cap;
+    uint8_t *near, *empty;
+    int32_t *how;
+    double *eps, *x;
+    int32_t *row;
+    double *lam;
+    int32_t *iters;
+    LpTol lp;
+    int32_t first;                             // set by the launcher, as in ExArgs
+    unsigned char *regions;
+};
+#define QPN_PROD_MAX_K 32
+size_t qpn_products_workspace_bytes(int32_t products, int32_t n, int32_t d);
+hipError_t qpn_launch_exemplar_products(const ProdArgs &a, void *gws, hipStream_t s); // gws: qpn_products_workspace_bytes(products, n, d)
 #define QPN_CONVEXITY_MAX_N 256
 #define QPN_CONVEXITY_MAX_M 1024
 

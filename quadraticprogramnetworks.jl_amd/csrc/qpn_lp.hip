@@ -29,8 +29,13 @@
 // it as a job of qpn_solve_lps is solved (lp_setup, lp_finish cold) and applies the reference's rule to eps and the multipliers of
 // the open bounds (ex_job; polyhedra.exemplar_polys_host is its twin).  The slice is that of an LP of 2 n + 1 rows in d + 1 variables.
 //
-// The four entries share the kernels and the launcher: lp_wave_kernel<Job> and lp_group_kernel<Job, LDS>
-// run the job function of the kind Job (LpJob, SubsetJob, IbJob, ExJob), lp_launch<Job> picks the class and launches.
+// qpn_exemplar_products asks the same question of products of pieces, one team per product: the team gathers
+// the rows of the product's factors from a pool of rows by index, tests the closure at the product's point, and solves the slack LP of
+// the gathered rows as ex_job does (prod_job; polyhedra.exemplar_products_host is its twin).  Nothing of the pool is copied per product
+// but the rows of the LP the job solves.
+//
+// The five entries share the kernels and the launcher: lp_wave_kernel<Job> and lp_group_kernel<Job, LDS>
+// run the job function of the kind Job (LpJob, SubsetJob, IbJob, ExJob, ProdJob), lp_launch<Job> picks the class and launches.
 #include <climits>
 
 #include "qpn_internal.h"
@@ -865,6 +870,122 @@ template <int T> __device__ void ex_job(const ExArgs &a, int t, double *base, in
     }
 }
 
+// ---- emptiness of products of pieces: one team per product ------------------------------------------------------------------------
+// A job's region of the workspace: the rows of its slack LP as in ex_rows_bytes, then the map product row -> pool row [n] int32
+__host__ __device__ inline size_t prod_region_bytes(int n, int d) { return (ex_rows_bytes(n, d) + (size_t)n * 4 + 15) & ~(size_t)15; }
+
+// Job t of a launch: product a.first + t, region t.  Every value a branch depends on is the same in all threads of the team: the
+// factor slots every thread walks, team reductions, the status of the solve, values read from the slice after a barrier.  The rule
+// (c) is ex_job's own (b), stated again here: ex_job is not edited, so that its kernels stay what they were.
+template <int T> __device__ void prod_job(const ProdArgs &a, int t, double *base, int tid)
+{
+    const int n = a.n, d = a.d, R = 2 * n + 1, D = d + 1;
+    const size_t b = (size_t)a.first + (size_t)t;
+    const int32_t *fac = a.factors + b * a.k;
+    double *Ae = reinterpret_cast<double *>(a.regions + (size_t)t * prod_region_bytes(n, d)), *le = Ae + (size_t)R * D, *ue = le + R;
+    int32_t *map = reinterpret_cast<int32_t *>(reinterpret_cast<unsigned char *>(Ae) + ex_rows_bytes(n, d));
+    const LpSlice S(base, R, D);
+    if (tid < 8) S.red[tid] = 0.0;
+    team_sync<T>();
+    // (d) a bad product (device arrays are not read by the host) fails and reads nothing through the bad index
+    bool ok = true;
+    long long total = 0;
+    for (int s = 0; s < a.k && ok; ++s) {
+        const int f = fac[s];
+        if (f == -1) continue;
+        if (f < -1 || f >= a.pieces) { ok = false; break; }
+        const int lo = a.piece_row[f], hi = a.piece_row[f + 1];
+        if (lo < 0 || hi < lo || hi > a.rows) ok = false;
+        total += hi - lo;
+    }
+    if (total != n) ok = false;
+    const int po = a.point ? a.point_of[b] : 0;
+    if (a.point && (po < 0 || po >= a.points)) ok = false;
+    int how = QPN_EX_FAILURE, row = -1, iters = 0, status = QPN_LP_FAILURE, near = 0;
+    double eps = __builtin_nan("");
+    if (ok) {
+        // (a) the map, (b) the closure test at the product's point: a lane per product row
+        const double *p = a.point ? a.point + (size_t)po * d : nullptr;
+        int low = INT_MAX;
+        for (int i = tid; i < n; i += T) {
+            int at = 0, pr = 0;
+            for (int s = 0; s < a.k; ++s) {
+                const int f = fac[s];
+                if (f < 0) continue;
+                const int lo = a.piece_row[f], cnt = a.piece_row[f + 1] - lo;
+                if (i < at + cnt) { pr = lo + (i - at); break; }
+                at += cnt;
+            }
+            map[i] = pr;
+            if (p) {
+                const double *ar = a.A + (size_t)pr * d;
+                double acc = 0.0;
+                for (int j = 0; j < d; ++j) acc = acc + ar[j] * p[j];
+                if (!(a.l[pr] - a.point_tol <= acc)) low = min(low, 2 * i);
+                else if (!(acc - a.point_tol <= a.u[pr])) low = min(low, 2 * i + 1);
+            }
+        }
+        low = team_min_int<T>(low, S.red, tid);
+        if (low != INT_MAX) {
+            how = QPN_EX_NOT_NEAR; row = low;
+        } else {
+            near = 1;
+            // (c) the rows of the slack LP from the pool, as ex_job (a) writes them from its polyhedron
+            for (int i = tid; i < n; i += T) {
+                const int pr = map[i];
+                const double *ar = a.A + (size_t)pr * d;
+                for (int j = 0; j < d; ++j) { const double v = ar[j]; Ae[(size_t)j * R + i] = v; Ae[(size_t)j * R + n + i] = -v; }
+                Ae[(size_t)d * R + i] = 1.0; Ae[(size_t)d * R + n + i] = 1.0;
+                le[i] = a.l[pr]; le[n + i] = -a.u[pr];
+                ue[i] = QINF; ue[n + i] = QINF;
+                S.lam[i] = 0.0; S.lam[n + i] = 0.0;
+            }
+            for (int j = tid; j < D; j += T) {
+                Ae[(size_t)j * R + 2 * n] = j == d ? 1.0 : 0.0;
+                S.cv[j] = j == d ? 1.0 : 0.0; S.xf[j] = 0.0; S.ray[j] = 0.0;
+            }
+            if (tid == 0) { le[2 * n] = -a.slack_cap; ue[2 * n] = QINF; S.lam[2 * n] = 0.0; }
+            team_sync<T>();
+            const LpProb P = lp_prob(R, D, Ae, le, ue, a.lp);
+            double obj = 0.0;
+            status = lp_setup<T>(P, S, tid);
+            if (!status) status = lp_finish<T>(P, S, tid, LP_COLD, &iters, &obj);
+            team_sync<T>();
+            const double tol = a.tol;
+            how = status == QPN_LP_ITER_LIMIT ? QPN_EX_ITER_LIMIT : QPN_EX_FAILURE;
+            if (status == QPN_LP_OPTIMAL) {
+                eps = S.xf[d];
+                if (eps > tol) {
+                    how = QPN_EX_EMPTY_SLACK;
+                } else if (eps > -tol) {
+                    int act = INT_MAX;
+                    for (int i = tid; i < n; i += T) {
+                        const int pr = map[i];
+                        if (a.open_hi && a.open_hi[pr] && fabs(a.u[pr]) < QINF && fabs(S.lam[n + i]) > tol) act = min(act, 2 * i + 1);
+                        if (a.open_lo && a.open_lo[pr] && fabs(a.l[pr]) < QINF && fabs(S.lam[i]) > tol) act = min(act, 2 * i);
+                    }
+                    act = team_min_int<T>(act, S.red, tid);
+                    how = act == INT_MAX ? QPN_EX_MEMBER_BAND : QPN_EX_EMPTY_OPEN;
+                    if (act != INT_MAX) row = act;
+                } else {
+                    how = QPN_EX_MEMBER;
+                }
+            }
+        }
+    }
+    const bool member = how == QPN_EX_MEMBER || how == QPN_EX_MEMBER_BAND, solved = status == QPN_LP_OPTIMAL;
+    if (a.x) for (int j = tid; j < d; j += T) a.x[b * d + j] = member ? S.xf[j] : 0.0;
+    if (a.lam) for (int i = tid; i < R; i += T) a.lam[b * R + i] = solved ? S.lam[i] : 0.0;
+    if (tid == 0) {
+        a.near[b] = (uint8_t)near;
+        a.empty[b] = how == QPN_EX_EMPTY_SLACK || how == QPN_EX_EMPTY_OPEN ? 1 : 0;
+        if (a.how) a.how[b] = how;
+        if (a.eps) a.eps[b] = eps;
+        if (a.row) a.row[b] = row;
+        if (a.iters) a.iters[b] = iters;
+    }
+}
+
 // ---- the kernels and the launcher of every job kind ------------------------------------------------------------------------------
 // A job kind names its argument struct and runs job t of it with a team of T threads on the slice at base.
 struct LpJob {
@@ -882,6 +1003,10 @@ struct IbJob {
 struct ExJob {
     using Args = ExArgs;
     template <int T> static __device__ void run(const Args &a, int t, double *base, int tid) { ex_job<T>(a, t, base, tid); }
+};
+struct ProdJob {
+    using Args = ProdArgs;
+    template <int T> static __device__ void run(const Args &a, int t, double *base, int tid) { prod_job<T>(a, t, base, tid); }
 };
 
 template <class Job> __global__ __launch_bounds__(64 * LP_WAVES) void lp_wave_kernel(typename Job::Args a, int32_t count, size_t slice)
@@ -941,16 +1066,32 @@ template <class Job> hipError_t lp_launch(const typename Job::Args &a, int32_t c
     return hipSuccess;
 }
 
-// What a job of qpn_exemplar_polys takes of the workspace: its rows and, in the workspace class, its slice; and the jobs of a launch
-size_t ex_job_bytes(int32_t n, int32_t d)
+// What a job that writes the rows of its own LP (R rows in D variables) takes of the workspace: its region of `region` bytes and, in
+// the workspace class, its slice; and the jobs of a launch
+size_t region_job_bytes(size_t region, int32_t R, int32_t D) { return region + (qpn_lp_class(R, D) == 2 ? lp_slice_bytes(R, D) : 0); }
+int32_t region_chunk(int32_t jobs, size_t job_bytes)
 {
-    return ex_rows_bytes(n, d) + (qpn_lp_class(2 * n + 1, d + 1) == 2 ? lp_slice_bytes(2 * n + 1, d + 1) : 0);
-}
-int32_t ex_chunk(int32_t polys, int32_t n, int32_t d)
-{
-    size_t c = LP_WS_CHUNK_BYTES / ex_job_bytes(n, d);
+    size_t c = LP_WS_CHUNK_BYTES / job_bytes;
     if (c < 1) c = 1;
-    return (int32_t)(c < (size_t)polys ? c : (size_t)polys);
+    return (int32_t)(c < (size_t)jobs ? c : (size_t)jobs);
+}
+
+// The workspace holds the slices of a chunk's jobs (workspace class), then their regions; a chunk is one launch of lp_launch (at most
+// lp_chunk jobs, as a job takes more than its slice), and the chunks of a call follow one another on the stream.  first, regions: the
+// members of the argument struct that tell a launch its first job and where the regions start.
+template <class Job>
+hipError_t lp_launch_regions(typename Job::Args a, int32_t Job::Args::*first, unsigned char *Job::Args::*regions, int32_t jobs, int32_t R,
+                             int32_t D, size_t region, void *gws, hipStream_t s)
+{
+    if (jobs <= 0) return hipSuccess;
+    const int32_t chunk = region_chunk(jobs, region_job_bytes(region, R, D));
+    a.*regions = static_cast<unsigned char *>(gws) + (qpn_lp_class(R, D) == 2 ? (size_t)chunk * lp_slice_bytes(R, D) : 0);
+    for (int32_t f = 0; f < jobs; f += chunk) {
+        a.*first = f;
+        const int32_t count = jobs - f < chunk ? jobs - f : chunk;
+        if (const hipError_t e = lp_launch<Job>(a, count, R, D, gws, s); e != hipSuccess) return e;
+    }
+    return hipSuccess;
 }
 
 } // namespace
@@ -975,21 +1116,24 @@ hipError_t qpn_launch_implicit_bounds(const IbArgs &a, void *gws, hipStream_t s)
 size_t qpn_exemplar_workspace_bytes(int32_t polys, int32_t n, int32_t d)
 {
     if (polys <= 0 || qpn_lp_class(2 * n + 1, d + 1) < 0) return 0;
-    return (size_t)ex_chunk(polys, n, d) * ex_job_bytes(n, d);
+    const size_t job = region_job_bytes(ex_rows_bytes(n, d), 2 * n + 1, d + 1);
+    return (size_t)region_chunk(polys, job) * job;
 }
 
-// The workspace holds the slices of a chunk's jobs (workspace class), then their rows; a chunk is one launch of lp_launch (at most
-// lp_chunk jobs, as a job takes more than its slice), and the chunks of a call follow one another on the stream.
-hipError_t qpn_launch_exemplar_polys(const ExArgs &a0, void *gws, hipStream_t s)
+hipError_t qpn_launch_exemplar_polys(const ExArgs &a, void *gws, hipStream_t s)
 {
-    if (a0.polys <= 0) return hipSuccess;
-    const int32_t R = 2 * a0.n + 1, D = a0.d + 1, chunk = ex_chunk(a0.polys, a0.n, a0.d);
-    ExArgs a = a0;
-    a.rows = static_cast<unsigned char *>(gws) + (qpn_lp_class(R, D) == 2 ? (size_t)chunk * lp_slice_bytes(R, D) : 0);
-    for (int32_t first = 0; first < a0.polys; first += chunk) {
-        a.first = first;
-        const int32_t count = a0.polys - first < chunk ? a0.polys - first : chunk;
-        if (const hipError_t e = lp_launch<ExJob>(a, count, R, D, gws, s); e != hipSuccess) return e;
-    }
-    return hipSuccess;
+    return lp_launch_regions<ExJob>(a, &ExArgs::first, &ExArgs::rows, a.polys, 2 * a.n + 1, a.d + 1, ex_rows_bytes(a.n, a.d), gws, s);
+}
+
+size_t qpn_products_workspace_bytes(int32_t products, int32_t n, int32_t d)
+{
+    if (products <= 0 || qpn_lp_class(2 * n + 1, d + 1) < 0) return 0;
+    const size_t job = region_job_bytes(prod_region_bytes(n, d), 2 * n + 1, d + 1);
+    return (size_t)region_chunk(products, job) * job;
+}
+
+hipError_t qpn_launch_exemplar_products(const ProdArgs &a, void *gws, hipStream_t s)
+{
+    return lp_launch_regions<ProdJob>(a, &ProdArgs::first, &ProdArgs::regions, a.products, 2 * a.n + 1, a.d + 1,
+                                      prod_region_bytes(a.n, a.d), gws, s);
 }

@@ -752,6 +752,37 @@ class Engine:
                    _ptr(out["row"]), _ptr(out["lam"]), _ptr(out["iters"]), self._mem(dev))
         return out
 
+    def exemplar_products(self, A, l, u, open_lo, open_hi, piece_row, factors, n, point=None, point_of=None, point_tol=1e-6, tol=1e-2,
+                          slack_cap=1.0, opts=None):
+        """The emptiness test of products of pieces, one job per product (qpn_exemplar_products; polyhedra.exemplar_products_host
+        is its numpy twin, bit for bit): the pool A [rows, d] (ROW-major: one row per pool row), l, u [rows], open_lo, open_hi
+        [rows] uint8 or None (closed); piece_row [pieces + 1] int32; factors [products, k] int32 (-1: no factor in that slot), the
+        rows of every product adding up to n; point [points, d] and point_of [products] int32, or both None (no closure test).
+        opts: LpOpts, a dict of its fields, or None.  Returns dict(near, empty [products] uint8, how [products] int32 (_lib.EX_*),
+        eps [products], x [products, d], row [products] int32, lam [products, 2 n + 1], iters [products] int32)."""
+        dev, A, l, u, point, open_lo, open_hi, piece_row, factors, point_of = self._stage(
+            "exemplar_products", "A l u point open_lo open_hi piece_row factors point_of", f64=(A, l, u, point), u8=(open_lo, open_hi),
+            i32=(piece_row, factors, point_of))
+        if A.ndim != 2 or factors.ndim != 2 or piece_row.ndim != 1 or piece_row.shape[0] < 1 or (point is None) != (point_of is None):
+            raise QpnError("exemplar_products: inconsistent shapes")
+        rows, d = (int(v) for v in A.shape)
+        products, k = (int(v) for v in factors.shape)
+        pieces, n = int(piece_row.shape[0]) - 1, int(n)
+        points = 0 if point is None else int(point.shape[0])
+        if tuple(l.shape) != (rows,) or tuple(u.shape) != (rows,) or any(o is not None and tuple(o.shape) != (rows,) for o in (open_lo, open_hi)) or (
+                point is not None and (point.ndim != 2 or int(point.shape[1]) != d or tuple(point_of.shape) != (products,))):
+            raise QpnError("exemplar_products: inconsistent shapes")
+        opts = self._lp_opts(opts)
+        out = dict(near=self._alloc(dev, (products,), np.uint8), empty=self._alloc(dev, (products,), np.uint8),
+                   how=self._alloc(dev, (products,), np.int32), eps=self._alloc(dev, (products,), np.float64),
+                   x=self._alloc(dev, (products, d), np.float64), row=self._alloc(dev, (products,), np.int32),
+                   lam=self._alloc(dev, (products, 2 * max(n, 0) + 1), np.float64), iters=self._alloc(dev, (products,), np.int32))
+        self._call("qpn_exemplar_products", d, rows, _ptr(A), _ptr(l), _ptr(u), _ptr(open_lo), _ptr(open_hi), pieces, _ptr(piece_row),
+                   products, n, k, _ptr(factors), points, _ptr(point), _ptr(point_of), float(point_tol), float(tol), float(slack_cap),
+                   C.byref(opts) if opts is not None else None, _ptr(out["near"]), _ptr(out["empty"]), _ptr(out["how"]), _ptr(out["eps"]),
+                   _ptr(out["x"]), _ptr(out["row"]), _ptr(out["lam"]), _ptr(out["iters"]), self._mem(dev))
+        return out
+
 
 class Nodes:
     """Resident node records (``qpn_nodes_upload``): the records of a level's single-node pools live in HBM owned by the

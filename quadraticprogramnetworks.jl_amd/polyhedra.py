@@ -27,7 +27,8 @@ distinct polyhedra by shape and builds no query.  solve_lps_host and issubset_pa
 the normative statements of their methods, to which the kernels are bit-equal.  An engine without the methods (the oracle engine)
 keeps the node-AVI route.  On an engine with `exemplar_polys` (qpn_exemplar_polys) the emptiness question of a polyhedron whose
 bounds may be open is ONE job too, opt-in through route="polyhedron": the job expands the slack LP, solves it and applies the
-reference's rule to its own duals (exemplar_polys_host is the twin).
+reference's rule to its own duals (exemplar_polys_host is the twin).  On one with `exemplar_products` (qpn_exemplar_products) the
+products of pieces of the intersection tree are jobs over one pool of rows (isempty_products; exemplar_products_host is the twin).
 
 These are the batch front ends: they normalise their inputs (_triple), pick a route, pack by shape (pack_by_shape), call the
 engine and unpack.  The numpy twins and the result codes are polyhedra_host.py; their public names stay importable from here.
@@ -608,6 +609,91 @@ def isempty_slack_batch(polys, engine, tol=1e-4, x=None, route=None):
     if rest:
         out[rest] = exemplar_slack_batch([polys[b] for b in rest], engine, tol=tol, route=route)[0]
     return out
+
+
+def isempty_products(pieces, products, engine, tol=1e-4, points=None, point_of=None, point_tol=1e-6, slack_cap=1.0, strict=True):
+    """The intersection tree's test of products of pieces (src/intersection.jl:66-105) for a batch, on an engine with
+    `exemplar_products` (qpn_exemplar_products): a product is kept when its point lies in its closure (:74) and it is not empty
+    (:83, `isempty` -> `exemplar`, the rule of exemplar_slack_batch).  pieces: [(A [r, d], l, u, open_lo, open_hi)], every distinct
+    piece once, open flags on finite bounds only (Poly.open_bounds); products: tuples of positions in `pieces`, the factors in
+    order, all of one product over the same d columns; points: the points (each of its products' d coordinates) and point_of: the
+    point of each product -- both None: no closure test.
+    The pieces go up once per d as one pool of rows, a product is the tuple of its factors' positions there, and the products are
+    grouped by (d, n), n the number of their rows: one call per group, no copy of a piece per product.  The products
+    exemplar_slack_batch answers without an LP (n == 0, the square-equality shortcut, :594-606) and the shapes beyond the kernel's
+    limits (n > 511, d > 255, more than 32 factors) are stacked on the host, tested against their point there and go through
+    exemplar_slack_batch(route="polyhedron").  A product that ends in EX_ITER_LIMIT or EX_FAILURE raises (strict; the lowest-numbered
+    one is named) or stays unanswered.  -> (near [products] bool, empty [products] bool; a product that is not near is not asked)."""
+    P = len(products)
+    near = np.ones(P, bool); empty = np.zeros(P, bool)
+    if P == 0:
+        return near, empty
+    rows_of = [p[0].shape[0] for p in pieces]
+    any_open = [bool(p[3].any() or p[4].any()) for p in pieces]
+    stacked = lambda t, c: np.concatenate([pieces[f][c] for f in products[t]])
+    groups, host = {}, []
+    for t, fs in enumerate(products):
+        d = pieces[fs[0]][0].shape[1]
+        n = sum(rows_of[f] for f in fs)
+        shortcut = n == d and not any(any_open[f] for f in fs) and _isapprox(stacked(t, 1), stacked(t, 2), tol, tol)
+        if n == 0 or shortcut or n > EX_MAX_N or d > EX_MAX_D or d < 1 or len(fs) > PROD_MAX_K:
+            host.append(t)
+        else:
+            groups.setdefault(d, {}).setdefault(n, []).append(t)
+    if host:
+        polys = []
+        for t in host:
+            A = np.vstack([pieces[f][0] for f in products[t]]); l = stacked(t, 1); u = stacked(t, 2)
+            if points is not None:
+                ax = A @ np.asarray(points[point_of[t]], dtype=np.float64)
+                near[t] = bool(np.all(l - point_tol <= ax) and np.all(ax - point_tol <= u))
+            polys.append(_Flagged(A, l, u, stacked(t, 3), stacked(t, 4)))
+        ask = [k for k, t in enumerate(host) if near[t]]
+        if ask:
+            empty[[host[k] for k in ask]] = exemplar_slack_batch([polys[k] for k in ask], engine, tol=tol, slack_cap=slack_cap, strict=strict,
+                                                                 route="polyhedron")[0]
+    failed = []
+    for d in sorted(groups):
+        used = sorted({f for ts in groups[d].values() for t in ts for f in products[t]})
+        at = {f: i for i, f in enumerate(used)}
+        A = np.vstack([pieces[f][0] for f in used]); l = np.concatenate([pieces[f][1] for f in used]); u = np.concatenate([pieces[f][2] for f in used])
+        ol = np.concatenate([pieces[f][3] for f in used]).astype(np.uint8); oh = np.concatenate([pieces[f][4] for f in used]).astype(np.uint8)
+        piece_row = np.concatenate([[0], np.cumsum([rows_of[f] for f in used])]).astype(np.int32)
+        pts, pt_at = None, {}
+        if points is not None:
+            for ts in groups[d].values():
+                for t in ts:
+                    pt_at.setdefault(point_of[t], len(pt_at))
+            pts = np.array([points[j] for j in pt_at], dtype=np.float64).reshape(len(pt_at), d)
+        for n in sorted(groups[d]):
+            ts = groups[d][n]
+            k = max(len(products[t]) for t in ts)
+            factors = np.full((len(ts), k), -1, np.int32)
+            for i, t in enumerate(ts):
+                factors[i, :len(products[t])] = [at[f] for f in products[t]]
+            pof = None if pts is None else np.array([pt_at[point_of[t]] for t in ts], np.int32)
+            res = engine.exemplar_products(A, l, u, ol, oh, piece_row, factors, n, point=pts, point_of=pof, point_tol=point_tol, tol=tol,
+                                           slack_cap=slack_cap)
+            nr = _to_host(res["near"]); em = _to_host(res["empty"]); how = _to_host(res["how"])
+            near[ts] = nr != 0; empty[ts] = em != 0
+            failed += [(t, int(h)) for t, h in zip(ts, how) if h in (EX_ITER_LIMIT, EX_FAILURE)]
+    if failed and strict:
+        t, how = min(failed)
+        raise RuntimeError(f"isempty_products: exemplar status {how} on product {t}")
+    return near, empty
+
+
+class _Flagged:
+    """A stacked product for exemplar_slack_batch: the triple and its open flags."""
+
+    def __init__(self, A, l, u, open_lo, open_hi):
+        self._t, self._o = (A, l, u), (np.asarray(open_lo, bool), np.asarray(open_hi, bool))
+
+    def vectorize(self):
+        return self._t
+
+    def open_bounds(self):
+        return self._o
 
 
 def implicit_bounds_batch(polys, engine, tol=1e-4, route="jobs"):

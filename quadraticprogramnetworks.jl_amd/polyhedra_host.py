@@ -1,5 +1,5 @@
 """The numpy twins of the polyhedral entries, the normative statements of the kernels' methods (the kernels are bit-equal to them):
-solve_lps_host, issubset_pairs_host, implicit_bounds_host, exemplar_polys_host, interior_member_records and members_outside_host,
+solve_lps_host, issubset_pairs_host, implicit_bounds_host, exemplar_polys_host, exemplar_products_host, interior_member_records and members_outside_host,
 with the entries' result codes, defined here once (_lib.py and polyhedra.py import them).  Numpy alone, loadable as a stand-alone
 file: tests/golden/lp_twin_record.json pins it across commits.  The front ends that pack, route and call an engine are polyhedra.py.
 """
@@ -596,8 +596,8 @@ def implicit_bounds_host(Ac, l, u, tol=1e-4, all_extremes=False, opts=None):
 
 
 # ---- emptiness with open bounds (qpn_exemplar_polys): one job per polyhedron, the numpy twin -------------------------------------
-EX_MEMBER, EX_MEMBER_BAND, EX_EMPTY_SLACK, EX_EMPTY_OPEN, EX_ITER_LIMIT, EX_FAILURE = 0, 1, 2, 3, 4, 5
-EX_MAX_N, EX_MAX_D = 511, 255
+EX_MEMBER, EX_MEMBER_BAND, EX_EMPTY_SLACK, EX_EMPTY_OPEN, EX_ITER_LIMIT, EX_FAILURE, EX_NOT_NEAR = 0, 1, 2, 3, 4, 5, 6
+EX_MAX_N, EX_MAX_D, PROD_MAX_K = 511, 255, 32
 
 
 def exemplar_rows(A, l, u, slack_cap=1.0):
@@ -664,6 +664,79 @@ def exemplar_polys_host(Ac, l, u, open_lo=None, open_hi=None, tol=1e-2, slack_ca
         got = _exemplar_one(np.ascontiguousarray(Ac[b].T), l[b], u[b], flags[0][b], flags[1][b], float(tol), float(slack_cap), o)
         for k, v in zip(("empty", "how", "eps", "x", "row", "lam", "iters"), got):
             out[k][b] = v
+    return out
+
+
+# ---- emptiness of products of pieces (qpn_exemplar_products): one job per product, the numpy twin ------------------------------------
+def exemplar_products_host(A, l, u, open_lo, open_hi, piece_row, factors, n, point=None, point_of=None, point_tol=1e-6, tol=1e-2,
+                           slack_cap=1.0, opts=None, device=False):
+    """The numpy twin of Engine.exemplar_products (qpn_exemplar_products), the normative statement of the method; every output of the
+    kernel is bit-equal to it.  The emptiness test of the intersection tree (src/intersection.jl:66-105) with one job per product of
+    pieces: the pool A [rows, d] (one ROW per pool row), l, u [rows] (+-inf allowed), open_lo, open_hi [rows] (nonzero: open; None:
+    closed); piece p = the pool rows piece_row[p] .. piece_row[p + 1] - 1; factors [products, k] int32, -1 = no factor in that slot:
+    product t is the intersection of its factors in slot order, its rows the factors' rows one after the other, n in all.  point
+    [points, d], point_of [products] (both None: no closure test).
+
+    (a) The map product row i -> pool row.  (b) The closure test at point[point_of[t]]: per row s_i = a_i'p over the ascending
+    columns, acc = acc + a * p; near when l_i - point_tol <= s_i and s_i - point_tol <= u_i on every row, closed relations whatever
+    the flags (`closure`, :74).  Not near: near = 0, how = EX_NOT_NEAR, empty = 0, eps = NaN, x = 0, lam = 0, iters = 0, row = the
+    lowest 2 i + side violated; no LP.  (c) Otherwise near = 1 and _exemplar_one on the n gathered rows and flags: the outputs and
+    codes of exemplar_polys_host; row counts product rows.  (d) A bad product -- a factor outside [-1, pieces), piece_row entries of a
+    factor not 0 <= first <= last <= rows, rows that do not add up to n, a point_of outside [0, points) -- raises ValueError as host
+    arrays do; device=True: it answers what the kernel answers for device arrays, near = 0, empty = 0, EX_FAILURE, eps = NaN, row =
+    -1, zeros elsewhere.
+    -> dict(near, empty [products] uint8, how [products] int32, eps [products], x [products, d], row [products] int32,
+    lam [products, 2 n + 1], iters [products] int32)."""
+    A = np.asarray(A, dtype=np.float64); l = np.asarray(l, dtype=np.float64); u = np.asarray(u, dtype=np.float64)
+    rows, d = A.shape
+    piece_row = np.asarray(piece_row, dtype=np.int64); factors = np.asarray(factors, dtype=np.int64)
+    pieces = len(piece_row) - 1
+    products, k = factors.shape
+    n = int(n)
+    flags = [np.zeros(rows, bool) if f is None else np.asarray(f).reshape(rows) != 0 for f in (open_lo, open_hi)]
+    if (point is None) != (point_of is None):
+        raise ValueError("exemplar_products: point and point_of go together")
+    if point is not None:
+        point = np.asarray(point, dtype=np.float64).reshape(-1, d); point_of = np.asarray(point_of, dtype=np.int64)
+    o = dict(LP_DEFAULT_OPTS)
+    o.update(opts or {})
+    out = dict(near=np.zeros(products, np.uint8), empty=np.zeros(products, np.uint8), how=np.full(products, EX_FAILURE, np.int32),
+               eps=np.full(products, np.nan), x=np.zeros((products, d)), row=np.full(products, -1, np.int32),
+               lam=np.zeros((products, 2 * n + 1)), iters=np.zeros(products, np.int32))
+    for t in range(products):
+        fs = [int(f) for f in factors[t] if f != -1]
+        bad = None
+        if any(f < -1 or f >= pieces for f in fs):
+            bad = "factor out of range"
+        elif any(not 0 <= piece_row[f] <= piece_row[f + 1] <= rows for f in fs):
+            bad = "piece_row not ascending within the pool"
+        elif sum(int(piece_row[f + 1] - piece_row[f]) for f in fs) != n:
+            bad = "rows do not add up to n"
+        elif point is not None and not 0 <= point_of[t] < len(point):
+            bad = "point_of out of range"
+        if bad:                                                             # (d)
+            if not device:
+                raise ValueError(f"exemplar_products: product {t}: {bad}")
+            continue
+        idx = np.concatenate([np.arange(piece_row[f], piece_row[f + 1]) for f in fs]).astype(np.int64)      # (a)
+        low = -1
+        if point is not None:                                               # (b)
+            pt = point[point_of[t]]
+            with np.errstate(all="ignore"):
+                acc = np.zeros(n)
+                for c in range(d):
+                    acc = acc + A[idx, c] * pt[c]
+                side = np.where(~(l[idx] - point_tol <= acc), 0, np.where(~(acc - point_tol <= u[idx]), 1, -1))
+            hit = np.nonzero(side >= 0)[0]
+            if hit.size:
+                low = 2 * int(hit[0]) + int(side[hit[0]])
+        if low >= 0:
+            out["how"][t] = EX_NOT_NEAR; out["row"][t] = low
+            continue
+        out["near"][t] = 1                                                  # (c)
+        got = _exemplar_one(np.ascontiguousarray(A[idx]), l[idx], u[idx], flags[0][idx], flags[1][idx], float(tol), float(slack_cap), o)
+        for key, v in zip(("empty", "how", "eps", "x", "row", "lam", "iters"), got):
+            out[key][t] = v
     return out
 
 

@@ -17,7 +17,7 @@ INF = np.inf
 
 CONVEXITY_TOL = 1e-6                        # check_qp_convexity's tol (src/qp_processing.jl:39)
 IMPLICIT_BOUNDS_ROUTE = "jobs"              # implicit_bounds_batch's route for the convexity check: "jobs" or "polyhedron"
-EMPTINESS_ROUTE = "nodes"                   # isempty_slack_batch's route for combine's products: "nodes" or "polyhedron"
+EMPTINESS_ROUTE = "nodes"                   # the route of combine's products: "nodes" or "polyhedron" (isempty_slack_batch), "products"
 
 
 class NonConvexQPError(RuntimeError):
@@ -234,9 +234,10 @@ def _halfspace_complements(P: Poly, cols, x, tol=1e-6):
     return every, near
 
 
-def _combine_products(regions: List[List[Poly]], solutions: List[List[Poly]], x):
-    """The candidate products of combine(...) for one node: (cols, ncols, products), every product a Poly over the compressed
-    columns `cols` whose closure contains x; raises RuntimeError on the reference's size guard (src/qp_processing.jl:281-285)."""
+def _combine_candidates(regions: List[List[Poly]], solutions: List[List[Poly]], x):
+    """The candidates of combine(...) for one node: (cols, ncols, cands), per combination the list of (is a complement piece,
+    Poly over the compressed columns `cols`) -- its solution pieces and the half-space complements of its region whose closure
+    contains x; raises RuntimeError on the reference's size guard (src/qp_processing.jl:281-285)."""
     x = np.asarray(x, dtype=np.float64)
     polys = [P for R in regions for P in R] + [P for Sg in solutions for P in Sg]
     cols = np.unique(np.concatenate([P.support() for P in polys])) if polys else np.zeros(0, np.int64)
@@ -252,7 +253,14 @@ def _combine_products(regions: List[List[Poly]], solutions: List[List[Poly]], x)
         cands.append(mine + [(True, H) for H in near])
     if len(widths) > 3 and sum(widths) > 20:                # :281-285
         raise RuntimeError("Too many solutions to combine.")
-    xs = x[cols]
+    return cols, ncols, cands
+
+
+def _combine_products(regions: List[List[Poly]], solutions: List[List[Poly]], x):
+    """The candidate products of combine(...) for one node: (cols, ncols, products), every product a Poly over the compressed
+    columns `cols` whose closure contains x; raises RuntimeError on the reference's size guard (src/qp_processing.jl:281-285)."""
+    cols, ncols, cands = _combine_candidates(regions, solutions, x)
+    xs = np.asarray(x, dtype=np.float64)[cols]
     prods = []
     for choice in itertools.product(*cands):
         if all(c[0] for c in choice):                       # complement pieces only: the redzone (src/intersection.jl:124)
@@ -263,6 +271,50 @@ def _combine_products(regions: List[List[Poly]], solutions: List[List[Poly]], x)
             continue
         prods.append(Poly(A, l, u, normalise=False, open_lo=olo, open_hi=ohi))
     return cols, ncols, prods
+
+
+def _combine_many_products(jobs, x, engine, tol):
+    """combine_many with route="products" (polyhedra.isempty_products, qpn_exemplar_products): every candidate of every node goes
+    into the pool once, a product is the tuple of its candidates' positions there, the closure test (src/intersection.jl:74) and the
+    emptiness test (:83) are the device's, and a Poly is built for the products that survive only."""
+    from .polyhedra import isempty_products
+    x = np.asarray(x, dtype=np.float64)
+    prep, pieces, polys, products, points, point_of = [], [], [], [], [], []
+    for regions, solutions in jobs:
+        try:
+            cols, ncols, cands = _combine_candidates(regions, solutions, x)
+        except RuntimeError as err:
+            prep.append(err)
+            continue
+        at = []                                                 # per combination: (is a complement piece, position in the pool)
+        for cand in cands:
+            at.append([(comp, len(pieces) + i) for i, (comp, _) in enumerate(cand)])
+            pieces += [(P.A, P.l, P.u) + P.open_bounds() for _, P in cand]
+            polys += [P for _, P in cand]
+        first = len(products)
+        for choice in itertools.product(*at):
+            if all(c[0] for c in choice):                       # complement pieces only: the redzone (src/intersection.jl:124)
+                continue
+            products.append(tuple(c[1] for c in choice))
+        point_of += [len(points)] * (len(products) - first)
+        points.append(x[cols])
+        prep.append((cols, ncols, first, len(products)))
+    near, empty = isempty_products(pieces, products, engine, tol=tol, points=points, point_of=point_of) if products else ([], [])
+    out = []
+    for pr in prep:
+        if isinstance(pr, RuntimeError):
+            out.append(pr)
+            continue
+        cols, ncols, first, last = pr
+        kept = []
+        for t in range(first, last):
+            if near[t] and not empty[t]:
+                fs = [polys[f] for f in products[t]]
+                kept.append(Poly.from_local(ncols, cols, np.vstack([P.A for P in fs]), np.concatenate([P.l for P in fs]),
+                                            np.concatenate([P.u for P in fs]), normalise=False,
+                                            open_lo=np.concatenate([P.open_lo for P in fs]), open_hi=np.concatenate([P.open_hi for P in fs])))
+        out.append(kept)
+    return out
 
 
 def combine_many(jobs, x, engine, tol=1e-4, route=None):
@@ -276,9 +328,16 @@ def combine_many(jobs, x, engine, tol=1e-4, route=None):
     lies in its closure and it is not empty (:74, :83), skipping products made of complement pieces only (the "redzone",
     :124).  Only candidates whose closure contains x can survive, so they alone are expanded; the emptiness questions of all
     nodes go to the engine as ONE batch of LPs (polyhedra.isempty_slack_batch: `isempty`, src/sets.jl:647-655 -> `exemplar`,
-    :591-642, open bounds included; by `route`, None: the module's EMPTINESS_ROUTE).  jobs: list of (regions, solutions); returns per job the list of pieces (global
+    :591-642, open bounds included; by `route`, None: the module's EMPTINESS_ROUTE).  route="products" on an engine with
+    `exemplar_products`: no product is expanded on the host (_combine_many_products); an engine without it takes route="polyhedron".
+    jobs: list of (regions, solutions); returns per job the list of pieces (global
     coordinates) or the RuntimeError of the reference's size guard (:281-285) for the caller to turn into failed = true."""
     from .polyhedra import isempty_slack_batch
+    route = EMPTINESS_ROUTE if route is None else route
+    if route == "products":
+        if callable(getattr(engine, "exemplar_products", None)):
+            return _combine_many_products(jobs, x, engine, tol)
+        route = "polyhedron"
     prep, flat, owner = [], [], []
     for k, (regions, solutions) in enumerate(jobs):
         try:
@@ -288,7 +347,7 @@ def combine_many(jobs, x, engine, tol=1e-4, route=None):
             continue
         prep.append((cols, ncols, prods))
         flat += prods; owner += [k] * len(prods)
-    empty = isempty_slack_batch(flat, engine, tol=tol, route=EMPTINESS_ROUTE if route is None else route) if flat else []
+    empty = isempty_slack_batch(flat, engine, tol=tol, route=route) if flat else []
     out = []
     for k, pr in enumerate(prep):
         if isinstance(pr, RuntimeError):
