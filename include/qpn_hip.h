@@ -355,6 +355,8 @@ int qpn_recipes_from_masks(qpn_ctx *ctx, int32_t N, const uint8_t *mask, int64_t
  *   lr, ur [cap], rows = the number of rows that remain (in their original order), flags: bit 0 = a multiplier column was pinned
  *   by no equality row while an alive row still holds it (degenerate active set: the projection needs Fourier-Motzkin / vertex
  *   enumeration, which stays with the caller -- the piece's output is then incomplete), bit 1 = more than cap rows remained.
+ *   Beyond rows[t] every output is filled: Ar with zeros, lr with -inf, ur with +inf (a piece whose device-side node_of entry
+ *   is out of range is all fill: rows = 0, flags = 0).
  *   The local pieces themselves live in the context's workspace only.  n + m <= 512. */
 int qpn_recipes_batch(qpn_ctx *ctx, int32_t nodes, int32_t N, const uint8_t *masks, const int64_t *offsets, uint8_t *K,
                       int32_t *node_of, int mem);
