@@ -60,7 +60,8 @@ struct SchurDebug { double *S, *c, *W, *h; };
 // q alone, and of Stage A's products only the extra column kx (g -> h = H^-1 g) carries q.  0 = compute, keep nothing;
 // 1 = compute and STORE the panels U' of the eight steps, the tiles W~ and S(0,0), S(0,1), S(1,1) and a pass / fail flag in
 // the handle's crash cache (layout: qpn_internal.h, kCrash*); 2 = REUSE them: no Qd staging, no factorisation, no MFMA --
-// kx is replayed with the stored U' by the same operations in the same order, so every output has the same bits;
+// kx is replayed with the stored U' by the same operations in the same order, so every output has the same bits (W~ is fetched
+// after the pivot loop, and only its columns with a nonzero multiplier: see the read-back);
 // 3 = MIXED: the cache is valid and every wavefront picks one of the two Stage A bodies -- reuse as 2, or compute as 0 (storing
 // nothing) -- by a wave-uniform rule on its position in the launch (crash_mix_recomputes, qpn_internal.h: the launcher's share
 // of the positions below a.crash_reuse_from compute, spread evenly over each XCD's dispatch sequence).  The reuse body is bound
@@ -557,16 +558,28 @@ __global__ __launch_bounds__(WAVE, 4) void avi_solve_schur(AviBatchArgs a, Schur
 #undef FMS
 #undef M_COLTILE
 #undef M_GATHER
+    if constexpr (SYM) {
+        // W~ is final.  The reuse sweeps skip the columns of W~ whose multiplier is zero (read-back, below), which gives the bits of
+        // the full product only where W~ is finite (0 x inf = NaN).  The pivot test does not settle that: it bounds every pivot from
+        // below, not the growth of the entries, and it is made on H alone (a NaN in Ad passes it).  So a node whose W~ holds an
+        // infinity or a NaN fails Stage A like one that failed the pivot test -- in EVERY symmetric variant, computing, filling or
+        // mixed, so that the set of declining nodes stays a property of the records (the handle asks for it once) and a reuse
+        // sweep, which reads flag 2, declines exactly the nodes a computing sweep declines.  The general kernel takes them.
+        bool wfin = true;
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+            wfin = wfin && fabs(TL(0, 2)[g]) < QINF && fabs(TL(0, 3)[g]) < QINF && fabs(TL(1, 2)[g]) < QINF && fabs(TL(1, 3)[g]) < QINF;
+        if (qpn_ballot(!wfin) != 0ull) fail = true;
+    }
     if constexpr (CRASH == 1) { if (l == 0) *crash_flag() = fail ? 2 : 1; }
     if (fail) { decline(); return; }
     if constexpr (CRASH == 1) {
-        // W~ is final: tile register g of tile t at ((4 t + g) * 64 + lane), 512 contiguous bytes per store
+        // column by column (crash_w_index): a lane's four registers of a tile are one 32-byte piece
         double *const cw = crash_base() + kCrashW;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            cw[(0 * 4 + g) * 64 + l] = TL(0, 2)[g]; cw[(1 * 4 + g) * 64 + l] = TL(0, 3)[g];
-            cw[(2 * 4 + g) * 64 + l] = TL(1, 2)[g]; cw[(3 * 4 + g) * 64 + l] = TL(1, 3)[g];
-        }
+        *reinterpret_cast<d4 *>(cw + crash_w_index(lq, lc)) = TL(0, 2);
+        *reinterpret_cast<d4 *>(cw + crash_w_index(lq, 16 + lc)) = TL(0, 3);
+        *reinterpret_cast<d4 *>(cw + crash_w_index(16 + lq, lc)) = TL(1, 2);
+        *reinterpret_cast<d4 *>(cw + crash_w_index(16 + lq, 16 + lc)) = TL(1, 3);
     }
 
     // ---- S = D - A W on the matrix cores, c = b - A h -----------------------------------------------------
@@ -729,23 +742,16 @@ stage_a_done: __attribute__((unused));
     wave_sync();                      // Stage A and the c sweep are done with sbuf
     // the fixed bounds of pair k as the pivot loop asks for them (wave-uniform k).  Reuse variant: they wait in the idle sz block
     // of sbuf instead of three register pairs, and h waits for the read-back in sbuf[96 .. 127] (idle from here on: the
-    // transposition of S is done with it) -- the registers W~ arrives in while the loop runs
-    if constexpr (CRASH >= 2) { if (actb) { sbuf[128 + l] = lo0; sbuf[160 + l] = hi0; sbuf[96 + l] = kx; } }
+    // transposition of S is done with it).  W~ is not requested here: a reusing wavefront fetches it after the loop, and only the
+    // columns whose multiplier is not zero (read-back, below)
+    if constexpr (CRASH >= 2) {
+        if (actb) { sbuf[128 + l] = lo0; sbuf[160 + l] = hi0; sbuf[96 + l] = kx; }
+    }
     auto lo0_of = [&](int k) -> double { if constexpr (CRASH >= 2) return udbl(sbuf[128 + k]); else return readlane_f64(lo0, k); };
     auto hi0_of = [&](int k) -> double { if constexpr (CRASH >= 2) return udbl(sbuf[160 + k]); else return readlane_f64(hi0, k); };
     auto rng_of = [&](int k) -> double {
         if constexpr (CRASH >= 2) return udbl(sbuf[160 + k]) - udbl(sbuf[128 + k]); else return readlane_f64(rngv, k);
     };
-    if constexpr (CRASH >= 2) if (reuse_w) {
-        // W~ is needed by the read-back only: requested here, it arrives behind the pivot loop (in the registers the computing
-        // variants -- and the computing wavefronts of a mixed launch -- keep it in)
-        const double *const cw = crash_base() + kCrashW;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            TL(0, 2)[g] = cw[(0 * 4 + g) * 64 + l]; TL(0, 3)[g] = cw[(1 * 4 + g) * 64 + l];
-            TL(1, 2)[g] = cw[(2 * 4 + g) * 64 + l]; TL(1, 3)[g] = cw[(3 * 4 + g) * 64 + l];
-        }
-    }
 
     // the dictionary as two 8-vectors per lane: element 4 Ib + g of SJ<Jb> = row 16 Ib + 4 g + lq, column
     // 16 Jb + lc.  Static element accesses are plain registers; the pivot row is read with a wave-uniform
@@ -1090,6 +1096,18 @@ stage_a_done: __attribute__((unused));
     double lk, uk; int gk;
     row_bounds_e(lk, uk, gk);
     double mq32[32];
+    // this lane's 32 operands of the post-check: x rows take their row of Qd from global memory, constraint rows their row of Ad
+    // from the LDS block buffer -- two exec-masked batches into the SAME registers, so that the post-check is ONE fma chain over
+    // the x columns
+#define M_REQUEST_MQ32                                                                              \
+    if constexpr (NODES && FULL32) {                                                                \
+        if (l < 32) {                                                                               \
+            const double *qc = Qe_ + l;                                                             \
+            _Pragma("unroll") for (int j = 0; j < 32; ++j) mq32[j] = qc[(size_t)j * 32];            \
+        } else {                                                                                    \
+            _Pragma("unroll") for (int j = 0; j < 32; ++j) mq32[j] = sA[j * SAS + (l - 32)];        \
+        }                                                                                           \
+    }
     // ---- read back: lambda_k, then x = -(W lambda + h) ---------------------------------------------------
     // lane coordinates recomputed from the lane id here (two VALU instructions): kept alive across the pivot loops they
     // are what the register allocator spills to scratch
@@ -1101,6 +1119,39 @@ stage_a_done: __attribute__((unused));
     if (l <= XC) sval[colvar] = nbval;
     wave_sync();
     const double lam0 = sval[NBP + lcE], lam1 = sval[NBP + 16 + lcE];     // lambda of this lane's two columns
+    if constexpr (CRASH >= 2) {
+        // ---- reusing wavefronts fetch W~ HERE, by column and under the multipliers' mask: a lane loads its entries of tile column
+        // Jb only if its multiplier for that column is not zero (written so that a NaN multiplier loads, and propagates), and holds
+        // +0.0 otherwise.  lambda is zero for every constraint row that is not active, and a column of the cache owns its two
+        // 128-byte lines (crash_w_index), so the lines of the inactive columns are never requested.  The arithmetic below is the
+        // same, instruction for instruction.  Bits: a skipped column contributes +0 to its rows' sums where the full product
+        // contributes +-0 (W~ is finite for a node that gets here: Stage A declines the others, in every variant), so a sum differs only if EVERY term
+        // of it is a zero, x_l = sum - h_l only if in addition h_l is exactly zero, and then only in the sign of a zero.
+        // The post-check's operands are requested in the same round, behind W~, so that no dependent round trip is added: the
+        // dictionary's registers are free by now.  (Both requests sit under lane masks, and behind such a join the compiler's
+        // wait in front of the products is vmcnt(0): they wait for the whole round, not for W~ alone.  Measured the same to
+        // +-0.2 %: the post-check's request behind the products as in the computing variants -- two rounds --, and in front of
+        // the lambda exchange)  The computing wavefronts of a mixed launch share this code, so their
+        // post-check request sits in front of the products too (in <..., 0> and <..., 1> it follows them): the same loads into
+        // the same registers, no arithmetic moves.
+        bool reuse_e = CRASH == 2;
+        if constexpr (CRASH == 3) reuse_e = !crash_mix_recomputes((int)blockIdx.x, kp->crash_share, kp->crash_reuse_from);
+        if (reuse_e) {
+            const double *const cw = kp->crash + (size_t)b * kCrashDoubles + kCrashW;
+            const d4 z4 = {0.0, 0.0, 0.0, 0.0};
+            TL(0, 2) = z4; TL(1, 2) = z4; TL(0, 3) = z4; TL(1, 3) = z4;
+            if (!(lam0 == 0.0)) {
+                TL(0, 2) = *reinterpret_cast<const d4 *>(cw + crash_w_index(lqE, lcE));
+                TL(1, 2) = *reinterpret_cast<const d4 *>(cw + crash_w_index(16 + lqE, lcE));
+            }
+            if (!(lam1 == 0.0)) {
+                TL(0, 3) = *reinterpret_cast<const d4 *>(cw + crash_w_index(lqE, 16 + lcE));
+                TL(1, 3) = *reinterpret_cast<const d4 *>(cw + crash_w_index(16 + lqE, 16 + lcE));
+            }
+        }
+        M_REQUEST_MQ32
+        __builtin_amdgcn_sched_barrier(0);
+    }
     {
         // (W lambda)_row = sum over the 16 lanes of a DPP row of this lane's two-column partial, for the 8
         // rows j = 4 Ib + g a lane holds.  Folded butterfly: at each of the first three stages a lane gives
@@ -1111,20 +1162,11 @@ stage_a_done: __attribute__((unused));
         double p4 = fma(TL(1, 2)[0], lam0, TL(1, 3)[0] * lam1), p5 = fma(TL(1, 2)[1], lam0, TL(1, 3)[1] * lam1);
         double p6 = fma(TL(1, 2)[2], lam0, TL(1, 3)[2] * lam1), p7 = fma(TL(1, 2)[3], lam0, TL(1, 3)[3] * lam1);
         // (the W tiles are dead from here on: their 32 registers take the 32 entries of Qd this lane needs for the
-        // post-check, requested now so that the round trip hides behind the reduction and its LDS hops)
+        // post-check, requested now so that the round trip hides behind the reduction and its LDS hops.  The cache variants have
+        // requested them already, in one round with W~: above)
         __builtin_amdgcn_sched_barrier(0);
-        if constexpr (NODES && FULL32) {
-            // (x rows: this lane's row of Qd from global memory; constraint rows: this lane's row of Ad from the LDS block buffer
-            //  -- two exec-masked batches into the SAME registers, so that the post-check is ONE fma chain over the x columns)
-            if (l < 32) {
-                const double *qc = Qe_ + l;
-#pragma unroll
-                for (int j = 0; j < 32; ++j) mq32[j] = qc[(size_t)j * 32];
-            } else {
-#pragma unroll
-                for (int j = 0; j < 32; ++j) mq32[j] = sA[j * SAS + (l - 32)];
-            }
-        }
+        if constexpr (CRASH < 2) { M_REQUEST_MQ32 }
+#undef M_REQUEST_MQ32
         __builtin_amdgcn_sched_barrier(0);
         const bool b0 = (lcE & 1) != 0, b1 = (lcE & 2) != 0, b2 = (lcE & 4) != 0;
         // stage 1 (partner lc ^ 1): keep rows with bit0 == b0

@@ -71,7 +71,7 @@ struct AviBatchArgs {
     // (key <- key - key/32 + pivots); the longest-first order of a resident-records handle is made from it.  May be null.
     int32_t *sched_key;
     // fused node kernel, symmetric n = m = 32 resident records only: the handle's crash cache (kCrashDoubles per node) and its
-    // per-node flags (1 = crash passed, 2 = pivot test failed); crash_mode 0 = not used, 1 = this sweep fills it, 2 = reuses it
+    // per-node flags (1 = crash passed, 2 = Stage A failed: pivot test, or W~ not finite); crash_mode 0 = not used, 1 = this sweep fills it, 2 = reuses it
     double *crash;
     uint8_t *crash_flag;
     int32_t crash_mode;
@@ -100,10 +100,23 @@ __host__ __device__ inline bool crash_mix_recomputes(int pos, int share, int reu
     return ((k * share + phase) & 255) + share >= 256;
 }
 
-// Crash cache of one symmetric n = m = 32 node, in doubles from the node's base.  Everything sits in the layout the registers
-// have: U' step-major, [8 steps][32 rows] of 4 doubles (what lane < 32 writes to sU in step KB); the four W~ tiles and the three
-// S tiles with register g of tile t at ((4 t + g) * 64 + lane), so that every load and store moves 512 contiguous bytes.
+// Crash cache of one symmetric n = m = 32 node, in doubles from the node's base.  U' and S sit in the layout the registers
+// have: U' step-major, [8 steps][32 rows] of 4 doubles (what lane < 32 writes to sU in step KB); the three S tiles with register
+// g of tile t at ((4 t + g) * 64 + lane), so that every load and store moves 512 contiguous bytes.  W~ sits column by column
+// (crash_w_index below).  The node stride is 176 cache lines and kCrashW 64 of them: with the allocation's alignment (hipMalloc:
+// at least 256 bytes) every block of a node starts on a 128-byte line.
 constexpr int kCrashU = 0, kCrashW = 1024, kCrashS = 2048, kCrashDoubles = 2816;      // 22 528 bytes per node
+static_assert(kCrashW % 16 == 0 && kCrashDoubles % 16 == 0, "W~ of every node starts on a 128-byte line");
+
+// W~ (32 x 32) in the crash cache: the offset, in doubles from kCrashW, of entry (row, col).  A column owns its cache lines:
+// column j is the 32 doubles from 32 j on, two 128-byte lines, one per row half Ib = row >> 4 -- so a reuse sweep's read-back
+// fetches only the columns whose multiplier is not zero.  Inside a line the four tile registers g of one lane group lq (row =
+// 16 Ib + 4 g + lq) are neighbours, position 4 lq + g: a lane moves them as one 32-byte piece, at crash_w_index(16 Ib + lq, col).
+__host__ __device__ inline int crash_w_index(int row, int col)
+{
+    const int ib = row >> 4, g = (row >> 2) & 3, lq = row & 3;
+    return 32 * col + 16 * ib + 4 * lq + g;
+}
 
 // Function attributes (dynamic LDS limits) are per device: a launcher raises its kernels' limits once per device it is used on,
 // through a static QpnLdsLimits:  static QpnLdsLimits lds_limits;  ... lds_limits.raise({{kernel_a, bytes_a}, {kernel_b, bytes_b}})
