@@ -221,7 +221,8 @@ int qpn_nodes_free(qpn_ctx *ctx, qpn_nodes *nodes);
  * in states 2, 3); info[2] = bit 0: a longest-first schedule is installed, bit 1: every Qd block of the records is bitwise
  * symmetric (settled by one pass when the records arrive or Qd is replaced; QPN_OPT_SYM_ROUTE), bit 2: a valid crash cache is
  * installed, bit 3: the crash cache is refused (QPN_OPT_CRASH_CACHE = 0, records of a shape or route that is not cached, or its
- * memory could not be had); info[3] = sweeps since the last schedule reset. */
+ * memory could not be had), bit 4: the last sweep streamed the crash cache past the last-level cache (QPN_OPT_LLC_BUDGET_MB);
+ * info[3] = sweeps since the last schedule reset. */
 int qpn_nodes_info(qpn_ctx *ctx, qpn_nodes *nodes, int32_t info[4]);
 int qpn_solve_nodes_h(qpn_ctx *ctx, qpn_nodes *nodes, const double *w, int64_t stride_w, double *z,
                       int32_t *status, double *resid, int32_t *pivots, uint8_t *active,
@@ -270,12 +271,19 @@ int qpn_ctx_set_auto_schedule(qpn_ctx *ctx, int32_t period);
  *                      per node) and later sweeps reuse it instead of recomputing it (default), 0 = never.  The cached sweeps
  *                      perform the parameter-dependent operations in the same order on the same numbers: results are
  *                      bit-identical either way, and the same nodes decline.
+ *   QPN_OPT_LLC_BUDGET_MB sweeps that reuse the crash cache: the share of the GPU's last-level cache, in MiB, that a sweep counts on
+ *                      (default: a tuning constant of the build).  A sweep whose node records and outputs fit
+ *                      that budget while records + crash cache do not fetches the crash cache with non-temporal loads, so that the
+ *                      records stay in the cache from sweep to sweep; smaller and larger sweeps use the default policy throughout.
+ *                      0 = never, -1 = every sweep that reuses the crash cache (tests, A/B runs).  A policy of the loads only:
+ *                      results are bit-identical.
  * A resident handle remembers under which option values it learned that none of its nodes declines; after a change it asks again
  * on its next sweep (another kernel variant applies its pivot test to slightly different numbers). */
 #define QPN_OPT_MID_ROUTE 1
 #define QPN_OPT_BIG_ROUTE 2
 #define QPN_OPT_SYM_ROUTE 3
 #define QPN_OPT_CRASH_CACHE 4
+#define QPN_OPT_LLC_BUDGET_MB 5
 int qpn_ctx_set_option(qpn_ctx *ctx, int32_t option, int32_t value);
 
 /* ---- multi-GPU: replicas of the iterate on peer GPUs, written by the solve itself -----------------------

@@ -660,8 +660,11 @@ const QPN_OPT_MID_ROUTE = Int32(1)
 const QPN_OPT_BIG_ROUTE = Int32(2)
 # CRASH_CACHE 1 = resident symmetric n = m = 32 records keep the part of the crash that Qd and Ad alone decide across sweeps
 # (22 KB of HBM per node on top of the 22 KB of records; bit-identical results; default), 0 = never.
+# LLC_BUDGET_MB: MiB of the last-level cache that sweeps over the crash cache count on -- a sweep whose records fit it while
+# records + crash cache do not streams the crash cache (non-temporal loads) so that the records stay cached; 0 = never, -1 = always.
 const QPN_OPT_SYM_ROUTE = Int32(3)
 const QPN_OPT_CRASH_CACHE = Int32(4)
+const QPN_OPT_LLC_BUDGET_MB = Int32(5)
 function set_option!(option::Integer, value::Integer)
     rc = ccall((:qpn_ctx_set_option, LIB), Cint, (Ptr{Cvoid}, Int32, Int32), ctx(), Int32(option), Int32(value))
     rc == 0 || error("qpn_ctx_set_option failed ($rc)")

@@ -38,6 +38,7 @@ OPT_MID_ROUTE = 1
 OPT_BIG_ROUTE = 2
 OPT_SYM_ROUTE = 3
 OPT_CRASH_CACHE = 4
+OPT_LLC_BUDGET_MB = 5
 
 
 class LibraryMissing(RuntimeError):

@@ -68,11 +68,16 @@ struct SchurDebug { double *S, *c, *W, *h; };
 // by HBM bytes and leaves the fp64 pipe half idle, the compute body the reverse; both give the same
 // bits, so the choice is free per wavefront.  The bodies join before the transposition of S(1,0); from there on there is one
 // copy of the code, with the fixed bounds and h parked in sbuf as in 2.
-template <bool NODES, int STAGGER = 0, int SHAPE = 0, bool SYM = false, int CRASH = 0>
+// STREAM (CRASH 2 and 3 only): the cache policy of a sweep whose node records fit the last-level cache while records + crash
+// cache do not (llc_streams_crash, qpn_internal.h).  The crash cache -- U', S and the W~ columns, each read once per sweep -- is
+// then fetched with non-temporal loads, so that it does not push the records (Ad, Qd, R, B, qd, l, u: default policy) out of
+// the cache before the next sweep reads them again.  The same loads into the same registers: no arithmetic moves.
+template <bool NODES, int STAGGER = 0, int SHAPE = 0, bool SYM = false, int CRASH = 0, bool STREAM = false>
 __global__ __launch_bounds__(WAVE, 4) void avi_solve_schur(AviBatchArgs a, SchurDebug dbg)
 {
     static_assert(CRASH == 0 || (NODES && SHAPE == 32 && SYM), "the crash cache exists for symmetric n = m = 32 node records");
     static_assert(CRASH >= 0 && CRASH <= 3, "crash modes: 0 compute, 1 fill, 2 reuse, 3 mixed");
+    static_assert(!STREAM || CRASH >= 2, "only the sweeps that read the crash cache stream it");
     static_assert(SHAPE == 0 || SHAPE == 16 || SHAPE == 32, "compile-time shapes: 16 and 32");
     static_assert(!SYM || (NODES && SHAPE == 32), "the symmetric variant exists for n = m = 32 node records");
     static_assert(NODES || SHAPE != 16, "explicit M: N alone settles the split only at N = 64");
@@ -232,6 +237,10 @@ __global__ __launch_bounds__(WAVE, 4) void avi_solve_schur(AviBatchArgs a, Schur
         const int src = ((l & 31) + 32) * 4;
         return __hiloint2double(__builtin_amdgcn_ds_bpermute(src, __double2hiint(v)), __builtin_amdgcn_ds_bpermute(src, __double2loint(v)));
     };
+    // a load from the crash cache under the launch's policy
+    auto crash_load = [](const auto *ptr) {
+        if constexpr (STREAM) return __builtin_nontemporal_load(ptr); else return *ptr;
+    };
     auto crash_flag = [&]() -> uint8_t * {
         typedef const AviBatchArgs __attribute__((address_space(4))) *kargs_c;
         return ((kargs_c)__builtin_amdgcn_kernarg_segment_ptr())->crash_flag + b;
@@ -260,13 +269,13 @@ __global__ __launch_bounds__(WAVE, 4) void avi_solve_schur(AviBatchArgs a, Schur
                 __builtin_amdgcn_global_load_lds((gptr_t)(ga + cj * 256), (lptr_t)(sA + cj * SAS), 4, 0, 0);
         }
         const double *const cu = cc + kCrashU + (l >> 5) * 512 + (l & 31) * 4;
-        d4 up0 = *reinterpret_cast<const d4 *>(cu), up1 = *reinterpret_cast<const d4 *>(cu + 128);
-        d4 up2 = *reinterpret_cast<const d4 *>(cu + 256), up3 = *reinterpret_cast<const d4 *>(cu + 384);
+        d4 up0 = crash_load(reinterpret_cast<const d4 *>(cu)), up1 = crash_load(reinterpret_cast<const d4 *>(cu + 128));
+        d4 up2 = crash_load(reinterpret_cast<const d4 *>(cu + 256)), up3 = crash_load(reinterpret_cast<const d4 *>(cu + 384));
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-            SB(0, 0)[g] = cc[kCrashS + ((0 * 4 + g) * 64 + l)];
-            SB(0, 1)[g] = cc[kCrashS + ((1 * 4 + g) * 64 + l)];
-            SB(1, 1)[g] = cc[kCrashS + ((2 * 4 + g) * 64 + l)];
+            SB(0, 0)[g] = crash_load(&cc[kCrashS + ((0 * 4 + g) * 64 + l)]);
+            SB(0, 1)[g] = crash_load(&cc[kCrashS + ((1 * 4 + g) * 64 + l)]);
+            SB(1, 1)[g] = crash_load(&cc[kCrashS + ((2 * 4 + g) * 64 + l)]);
         }
         if (l < 32) { lo_pre = a.nd.l[(size_t)b * 32 + l]; hi_pre = a.nd.u[(size_t)b * 32 + l]; }
         const double ql = qelem(l);
@@ -1141,12 +1150,12 @@ stage_a_done: __attribute__((unused));
             const d4 z4 = {0.0, 0.0, 0.0, 0.0};
             TL(0, 2) = z4; TL(1, 2) = z4; TL(0, 3) = z4; TL(1, 3) = z4;
             if (!(lam0 == 0.0)) {
-                TL(0, 2) = *reinterpret_cast<const d4 *>(cw + crash_w_index(lqE, lcE));
-                TL(1, 2) = *reinterpret_cast<const d4 *>(cw + crash_w_index(16 + lqE, lcE));
+                TL(0, 2) = crash_load(reinterpret_cast<const d4 *>(cw + crash_w_index(lqE, lcE)));
+                TL(1, 2) = crash_load(reinterpret_cast<const d4 *>(cw + crash_w_index(16 + lqE, lcE)));
             }
             if (!(lam1 == 0.0)) {
-                TL(0, 3) = *reinterpret_cast<const d4 *>(cw + crash_w_index(lqE, 16 + lcE));
-                TL(1, 3) = *reinterpret_cast<const d4 *>(cw + crash_w_index(16 + lqE, 16 + lcE));
+                TL(0, 3) = crash_load(reinterpret_cast<const d4 *>(cw + crash_w_index(lqE, 16 + lcE)));
+                TL(1, 3) = crash_load(reinterpret_cast<const d4 *>(cw + crash_w_index(16 + lqE, 16 + lcE)));
             }
         }
         M_REQUEST_MQ32
@@ -1370,9 +1379,15 @@ hipError_t qpn_launch_avi_solve_schur_nodes(const AviBatchArgs &a, hipStream_t s
     const dim3 grid((unsigned)a.batch), block(WAVE);
     if (full && a.nd.sym) {
         const int crash = (a.crash && a.crash_flag) ? a.crash_mode : 0;
+        // (qpn_capi.hip decides, per launch, whether the crash cache is streamed past the last-level cache)
+        const bool nt = crash == 2 && a.crash_stream != 0;
         // a mixed launch (qpn_capi.hip sets the share): only beyond the resident set, where the reuse variant saturates HBM
         if (crash == 2 && a.crash_share > 0 && a.crash_reuse_from > 0 && stag) {
-            hipLaunchKernelGGL((avi_solve_schur<true, kResidentMI355X, 32, true, 3>), grid, block, 0, stream, a, d);
+            if (nt) hipLaunchKernelGGL((avi_solve_schur<true, kResidentMI355X, 32, true, 3, true>), grid, block, 0, stream, a, d);
+            else hipLaunchKernelGGL((avi_solve_schur<true, kResidentMI355X, 32, true, 3>), grid, block, 0, stream, a, d);
+        } else if (crash == 2 && nt) {
+            if (stag) hipLaunchKernelGGL((avi_solve_schur<true, kResidentMI355X, 32, true, 2, true>), grid, block, 0, stream, a, d);
+            else hipLaunchKernelGGL((avi_solve_schur<true, 0, 32, true, 2, true>), grid, block, 0, stream, a, d);
         } else if (crash == 2) {
             if (stag) hipLaunchKernelGGL((avi_solve_schur<true, kResidentMI355X, 32, true, 2>), grid, block, 0, stream, a, d);
             else hipLaunchKernelGGL((avi_solve_schur<true, 0, 32, true, 2>), grid, block, 0, stream, a, d);

@@ -44,6 +44,9 @@ struct qpn_ctx {
     int32_t sym_route = 1;
     // QPN_OPT_CRASH_CACHE: 1 = resident symmetric n = m = 32 records keep the parameter-free part of the crash across sweeps
     int32_t crash_cache = 1;
+    // QPN_OPT_LLC_BUDGET_MB: the share of the last-level cache, in MiB, that sweeps over the crash cache count on (llc_streams_crash,
+    // qpn_internal.h); 0 = never stream the crash cache, -1 = always
+    int32_t llc_budget_mb = kLlcBudgetMB;
 };
 
 namespace {
@@ -338,6 +341,11 @@ int qpn_ctx_set_option(qpn_ctx *ctx, int32_t option, int32_t value)
         // (no new route epoch: cached sweeps return the same bits, so what a handle knows about its declines stays true)
         if (value < 0 || value > 1) return fail_arg(ctx, "qpn_ctx_set_option: QPN_OPT_CRASH_CACHE takes 0 or 1");
         ctx->crash_cache = value;
+        return QPN_OK;
+    case QPN_OPT_LLC_BUDGET_MB:
+        // (a cache policy of the loads: the same bits either way, no new route epoch)
+        if (value < -1) return fail_arg(ctx, "qpn_ctx_set_option: QPN_OPT_LLC_BUDGET_MB takes a size in MiB, 0 (never stream) or -1 (always)");
+        ctx->llc_budget_mb = value;
         return QPN_OK;
     default:
         return fail_arg(ctx, "qpn_ctx_set_option: unknown option");
@@ -901,6 +909,8 @@ struct qpn_nodes {
     uint8_t *crash_flag = nullptr;
     int crash_state = 0;
     hipStream_t crash_stream = nullptr;
+    // did the last sweep fetch the crash cache with non-temporal loads?  (qpn_nodes_info bit 4)
+    bool crash_streamed = false;
 };
 
 namespace {
@@ -1128,6 +1138,9 @@ int solve_nodes_launch(qpn_ctx *ctx, qpn_nodes *h, int32_t batch, int32_t n, int
             a.crash_share = kCrashMixShare;
             a.crash_reuse_from = crash_mix_reuse_from(batch);
         }
+        // ... and it streams the crash cache past the last-level cache when that lets the node records stay there until the next sweep
+        if (crash == 2 && llc_streams_crash(batch, n, m, p, ctx->llc_budget_mb)) a.crash_stream = 1;
+        if (h) h->crash_streamed = a.crash_stream != 0;
         bool need_general;
         if ((rc = declines_begin(ctx, h, a, &need_general)) != QPN_OK) return rc;
         HIPCHK(ctx, qpn_launch_avi_solve_schur_nodes(a, s));
@@ -1369,7 +1382,7 @@ int qpn_nodes_info(qpn_ctx *ctx, qpn_nodes *h, int32_t info[4])
     info[0] = h->decl_state; info[1] = h->decl_state >= 2 ? *h->decl_host : 0;
     const bool cached = h->crash_state == 1 && crash_cache_applies(ctx, h);
     const bool refused = !crash_cache_applies(ctx, h) || h->crash_state < 0;
-    info[2] = (h->order_valid ? 1 : 0) | (h->sym ? 2 : 0) | (cached ? 4 : 0) | (refused ? 8 : 0); info[3] = h->calls;
+    info[2] = (h->order_valid ? 1 : 0) | (h->sym ? 2 : 0) | (cached ? 4 : 0) | (refused ? 8 : 0) | (h->crash_streamed ? 16 : 0); info[3] = h->calls;
     return QPN_OK;
 }
 

@@ -80,6 +80,9 @@ struct AviBatchArgs {
     // (the tail of the launch, which no longer saturates HBM).  The results do not depend on either (crash_mix_recomputes).
     int32_t crash_share;
     int32_t crash_reuse_from;
+    // crash_mode 2 only: 1 = this sweep fetches the crash cache with non-temporal loads (llc_streams_crash below; read by the
+    // launcher alone -- the policy is a template parameter of the kernel)
+    int32_t crash_stream;
 };
 
 // Wavefronts of the fused 32-class kernel resident at once on an MI355X: 16 per CU (LDS- and VGPR-bound), 256 CUs.
@@ -116,6 +119,29 @@ __host__ __device__ inline int crash_w_index(int row, int col)
 {
     const int ib = row >> 4, g = (row >> 2) & 3, lq = row & 3;
     return 32 * col + 16 * ib + 4 * lq + g;
+}
+
+// Cache policy of a sweep that reads the crash cache (reuse and mixed launches).  The last-level cache (256 MiB on an MI355X) keeps
+// a line from one sweep to the next only while everything loaded or stored in between fits it.  R = what a sweep touches of the
+// node records and the outputs, C = the crash cache.  While R + C fits, default loads keep all of it resident; when R alone does
+// not fit, nothing can be kept; in between, the crash cache is streamed (non-temporal loads: read once per sweep, not retained) and
+// the records stay.  budget_mb: the share of the cache counted on, in MiB (QPN_OPT_LLC_BUDGET_MB; 0 = never stream, negative =
+// always).  The default is a tuning constant taken from node-count runs, not the datasheet's 256: a mixed
+// sweep reads about half of C (3/8 of its wavefronts compute, and the read-back fetches a third of W~), so with C counted in
+// full the lower edge of the window sits where the streamed sweeps start to win only for a budget above the cache's size.  No
+// result depends on it.
+#ifndef QPN_LLC_BUDGET_MB
+#define QPN_LLC_BUDGET_MB 320
+#endif
+constexpr int kLlcBudgetMB = QPN_LLC_BUDGET_MB;
+__host__ inline bool llc_streams_crash(int64_t batch, int64_t n, int64_t m, int64_t p, int64_t budget_mb)
+{
+    if (budget_mb < 0) return true;
+    if (budget_mb == 0) return false;
+    const int64_t record = 8 * (n * n + n * p + n + m * n + m * p + 2 * m);      // Qd, R, qd, Ad, B, l, u
+    const int64_t outputs = 8 * (n + m) + (n + m) + 4 + 8 + 4 + 8 * n;            // z, active, status, resid, pivots, x
+    const int64_t R = batch * (record + outputs), C = batch * (int64_t)kCrashDoubles * 8, budget = budget_mb << 20;
+    return R <= budget && budget < R + C;
 }
 
 // Function attributes (dynamic LDS limits) are per device: a launcher raises its kernels' limits once per device it is used on,

@@ -1,7 +1,11 @@
 """Developer probe: does the memory-side cache (256 MB) hold part of the records from one sweep to the next, and does the
-ORDER in which a sweep takes the nodes decide what the next sweep's first round finds there?  10 000 nodes x 32 vars
-(348 MB of records: more than the cache, so a cyclic pass in the same order is the LRU worst case).  Two static orders on
-alternate sweeps, both with the shortest nodes last:  X = [A | B | C],  Y = [B | A | C]  (A, B: 4 096 nodes each).
+ORDER in which a sweep takes the nodes decide what the next sweep's first round finds there?  10 000 nodes x 32 vars: 221 MB
+of records and outputs (an earlier version of this text said 348 MB: that counted Qd twice), which FIT the cache -- when the
+probe was written that was all a sweep touched, so everything was resident whatever the order and "the order makes no
+difference" said nothing about the cache.  With the crash cache a sweep touches about 340 MB; sweeps inside the window of
+llc_streams_crash (csrc/qpn_internal.h) stream the crash cache so that the records stay resident, and the order still makes no
+difference (profiles/llc_resident_ab.txt).  Two static orders on alternate sweeps, both with the shortest nodes last:
+X = [A | B | C],  Y = [B | A | C]  (A, B: 4 096 nodes each).
 Usage: python tools/mall_probe.py [steps]"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
