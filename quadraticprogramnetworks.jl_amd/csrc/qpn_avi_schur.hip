@@ -114,9 +114,6 @@ __global__ __launch_bounds__(WAVE, 4) void avi_solve_schur(AviBatchArgs a, Schur
         if (a.order) { b = a.order[blockIdx.x]; if ((unsigned)b >= (unsigned)a.batch) return; }
     }
     const int lc = l & 15, lq = l >> 4;
-    // l & 15 recomputed on the spot (one v_and) where the pivot loop compares it: kept in a register for the whole
-    // kernel it is what the allocator spills to scratch first
-    auto lc_now = [&]() -> int { int t_ = l; asm volatile("" : "+v"(t_)); return t_ & 15; };
     // this wavefront hands its item to the general kernel (status = -1); node path: counted for the owner of the records
     // (the counter's address is read from the kernarg segment on the spot, not kept in registers)
     auto decline = [&]() {
@@ -728,6 +725,13 @@ stage_a_done: __attribute__((unused));
     // column-tile / row-register dispatch live inside the block.
     // Pair bounds / bound flags sit in lane k and are fetched with v_readlane; the only LDS traffic per
     // pivot is the entering column and the pivot row.
+    // More than half of what a pivot issues is scalar-side (SALU, branches, s_nop), and most of that is what
+    // the compiler makes of wave-uniform control flow, not the algorithm.  So the uniform decisions that sit
+    // on every pivot's path are written out: the entering column's stores are one asm block with one scalar
+    // branch per decision (tile column, extra column) under a shifted owner mask; the direction sigma of the
+    // entering variable is carried as a sign mask and applied by xor (s_xor_b64 for wave-uniform values);
+    // the ratio reduction's v_min carry no wait states of their own (the hazard recogniser places them); and
+    // the loop has no condition at its head -- every exit is a break that has set `status`.
     constexpr int NBP = 32, XC = 32, VTH = 64;
     const bool actb = l < NBP;
     double lo = -QINF, hi = QINF;
@@ -774,7 +778,12 @@ stage_a_done: __attribute__((unused));
     const int max_piv = a.max_pivots > 0 ? a.max_pivots : 50 * N + 100;
     int status = QPN_FAILURE;
     int c = XC;
-    bool sneg = true;                     // direction of the entering variable: sigma = sneg ? -1 : +1
+    // direction of the entering variable, sigma = -1 or +1, as the sign MASK it is applied with: bit 63 or nothing.  A value
+    // takes sigma by one xor (exact: a sign flip) -- a lane vector by v_xor_b32 on its high word, a wave-uniform value by one
+    // s_xor_b64 (asm: written in C++ the compiler splits the pair and puts it together again, 4 SALU)
+    unsigned long long sgn = 1ull << 63;
+    auto sigma_times = [&](double x) -> double { return __hiloint2double(__double2hiint(x) ^ (int)(sgn >> 32), __double2loint(x)); };
+    auto sigma_times_uni = [&](double x) -> double { double r_; asm("s_xor_b64 %0, %1, %2" : "=s"(r_) : "s"(x), "s"(sgn) : "scc"); return r_; };
     double self_lim = 0.0, elo = 0.0, ehi = QINF;
     const double slack = 1e-10, ptol = a.piv_tol;
     {
@@ -801,22 +810,53 @@ stage_a_done: __attribute__((unused));
             status = QPN_MAX_ITERS;
         }
     }
-    while (status == QPN_MAX_ITERS) {
+    // (every exit of the loop is a break that has set `status`: it is not a loop condition, so it is neither carried in a
+    // register nor tested at the head)
+    if (status == QPN_MAX_ITERS) for (;;) {
         if (pivots >= max_piv) break;
         c = uni(c);
         // ---- entering column -> sucol, permuted so that a lane group reads its 8 rows as 8 consecutive doubles
         // (row r = q + 4 g + 16 Ib sits at q*8 + 4 Ib + g)
-        if (c == XC) { if (actb) sucol[(l & 3) * 8 + ((l >> 4) << 2) + ((l >> 2) & 3)] = tcol; }
-        else if (lc_now() == (c & 15)) {
-            d4 *const dst = reinterpret_cast<d4 *>(sucol + lq * 8);
-            if (c < 16) { dst[0] = d4{SD(0, 0, 0), SD(0, 0, 1), SD(0, 0, 2), SD(0, 0, 3)}; dst[1] = d4{SD(1, 0, 0), SD(1, 0, 1), SD(1, 0, 2), SD(1, 0, 3)}; }
-            else { dst[0] = d4{SD(0, 1, 0), SD(0, 1, 1), SD(0, 1, 2), SD(0, 1, 3)}; dst[1] = d4{SD(1, 1, 0), SD(1, 1, 1), SD(1, 1, 2), SD(1, 1, 3)}; }
+        // ONE asm block, like the exchange: the lanes of tile column c & 15 come as a shifted mask (no compare), the tile
+        // column is one scalar branch, the extra column another.  Written as nested ifs the same stores cost three
+        // flag-and-branch diamonds of the structurizer and a v_cmp + s_and_saveexec per pivot.  Like the exchange block it
+        // expects all 64 lanes active on entry (it leaves EXEC at -1) and 0 <= c <= 32; the later reads of sucol need no
+        // wait on these stores (LDS operations of one wave complete in issue order), and the "memory" clobber keeps the
+        // compiler's own LDS accesses on their side of the block.
+        {
+            typedef double d2 __attribute__((ext_vector_type(2)));
+            const unsigned long long mown = 0x0001000100010001ull << (c & 15), mact = 0xFFFFFFFFull;      // owner lanes; lanes 0 .. 31
+            const unsigned acol = (unsigned)(uintptr_t)(sucol + lq * 8);
+            const unsigned aext = (unsigned)(uintptr_t)(sucol + ((l & 3) * 8 + ((l >> 4) << 2) + ((l >> 2) & 3)));
+            asm volatile(
+                "s_cmp_gt_i32 %[c], 31\n\ts_cbranch_scc1 .Lqc_x%=\n\t"
+                "s_mov_b64 exec, %[mown]\n\t"
+                "s_cmp_gt_i32 %[c], 15\n\ts_cbranch_scc1 .Lqc_1%=\n\t"
+                "ds_write_b128 %[ad], %[a0]\n\tds_write_b128 %[ad], %[a1] offset:16\n\t"
+                "ds_write_b128 %[ad], %[a2] offset:32\n\tds_write_b128 %[ad], %[a3] offset:48\n\t"
+                "s_branch .Lqc_end%=\n"
+                ".Lqc_1%=:\n\t"
+                "ds_write_b128 %[ad], %[b0]\n\tds_write_b128 %[ad], %[b1] offset:16\n\t"
+                "ds_write_b128 %[ad], %[b2] offset:32\n\tds_write_b128 %[ad], %[b3] offset:48\n\t"
+                "s_branch .Lqc_end%=\n"
+                ".Lqc_x%=:\n\t"
+                "s_mov_b64 exec, %[mact]\n\t"
+                "ds_write_b64 %[ax], %[tc]\n"
+                ".Lqc_end%=:\n\t"
+                "s_mov_b64 exec, -1"
+                :
+                : [c] "s"(c), [mown] "s"(mown), [mact] "s"(mact), [ad] "v"(acol), [ax] "v"(aext), [tc] "v"(tcol),
+                  [a0] "v"(d2{SD(0, 0, 0), SD(0, 0, 1)}), [a1] "v"(d2{SD(0, 0, 2), SD(0, 0, 3)}),
+                  [a2] "v"(d2{SD(1, 0, 0), SD(1, 0, 1)}), [a3] "v"(d2{SD(1, 0, 2), SD(1, 0, 3)}),
+                  [b0] "v"(d2{SD(0, 1, 0), SD(0, 1, 1)}), [b1] "v"(d2{SD(0, 1, 2), SD(0, 1, 3)}),
+                  [b2] "v"(d2{SD(1, 1, 0), SD(1, 1, 1)}), [b3] "v"(d2{SD(1, 1, 2), SD(1, 1, 3)})
+                : "scc", "memory");
         }
         wave_sync();
         const double cm = actb ? sucol[(l & 3) * 8 + ((l >> 4) << 2) + ((l >> 2) & 3)] : 0.0;
         STAMP(1);   // entering column through LDS
         // ---- ratio test (same rule as the general kernel; reciprocal by Newton instead of a division)
-        const double gdir = __hiloint2double(__double2hiint(cm) ^ (sneg ? (int)0x80000000 : 0), __double2loint(cm));
+        const double gdir = sigma_times(cm);
         const double rc = rcp64(gdir);
         // the bound the row's basic variable moves towards: lo when it decreases (gdir < 0), hi when it increases; a row is a
         // candidate when that bound is finite and |gdir| is above the pivot tolerance.  (t - xb) * rc = |t - xb| * |rc|, both
@@ -847,19 +887,19 @@ stage_a_done: __attribute__((unused));
         bool stop = false;
         if (bal == 0ull) {
             // the entering variable reaches its own opposite bound first: no basis change
-            const double dl = sneg ? -self_lim : self_lim;
+            const double dl = sigma_times(self_lim);
             if (actb) xb = fma(dl, cm, xb);
             const int ve = readlane_i32(colvar, c);
             if (ve == VTH) { nbW = 0.0; status = QPN_SUCCESS; stop = true; }
             else {
                 const int k = ve;
-                const int au = sneg ? 0 : 1;
+                const int au = (long long)sgn < 0 ? 0 : 1;
                 nbW = au ? hi0_of(k) : lo0_of(k);
                 kW = k; auW = au;
                 pivots++;
                 cnext = col_of(NBP + k);
                 if (cnext < 0) { status = QPN_FAILURE; stop = true; }
-                sneg = au != 0;
+                sgn = (unsigned long long)au << 63;
                 self_lim = QINF;
                 if (au) { elo = -QINF; ehi = 0.0; } else { elo = 0.0; ehi = QINF; }
             }
@@ -890,8 +930,8 @@ stage_a_done: __attribute__((unused));
             if (step < 0.0) step = 0.0;
             const double leave_val = readlane_f64(tb, r);
             const double rcr = readlane_f64(rc, r);
-            inv = sneg ? -rcr : rcr;
-            const double delta = sneg ? -step : step;
+            inv = sigma_times_uni(rcr);
+            const double delta = sigma_times_uni(step);
             const int vl = readlane_i32(rowvar, r);
             const double enter_val = readlane_f64(nbval, c) + delta;
             wave_sync();
@@ -927,7 +967,7 @@ stage_a_done: __attribute__((unused));
                     // its multiplier d_k enters from 0
                     au = uni(__double2hiint(rcr)) >= 0 ? 1 : 0; kW = k; auW = au;      // (sign bit of the pivot, |pivot| > ptol: gdir_r > 0 <=> left at hi)
                     vn = NBP + k;
-                    sneg = au != 0;
+                    sgn = (unsigned long long)au << 63;
                     self_lim = QINF;
                     if (cls == 2) { elo = 0.0; ehi = 0.0; }
                     else if (au) { elo = -QINF; ehi = 0.0; }
@@ -935,9 +975,8 @@ stage_a_done: __attribute__((unused));
                 } else {
                     // the multiplier d_k left at 0: p_k enters, moving off the bound it rests at
                     vn = k;
-                    sneg = au != 0;
+                    sgn = cls == 2 ? 0ull : (unsigned long long)au << 63;
                     self_lim = rng_of(k);           // +inf for a free pair
-                    if (cls == 2) sneg = false;
                     elo = lo0_of(k); ehi = hi0_of(k);
                 }
             }

@@ -558,11 +558,23 @@ __device__ __forceinline__ double wave_min32_f64(double v)
     return qpn_min2(r0, r1);
 }
 // v_min_f64 without the canonicalising v_max the compiler puts in front of fmin() (callers feed no NaNs).
-// Inline asm is invisible to the hazard recognizer: the s_nop covers a DPP read of the result.
+// The asm carries no wait states of its own: the compiler's hazard recogniser treats the VGPR an asm block defines like
+// any VALU result and puts the wait states in front of the DPP move or v_readlane that reads it (2 and 1 on gfx950).  An
+// s_nop inside the asm only doubled them.  This is a property of the toolchain, not a guarantee of the ISA: with another
+// compiler, dump every unit that uses these helpers (tools/isa.sh on qpn_avi_schur, _wg, _wg2) and see in the listing that
+// an s_nop 1 stands between each of these v_min_f64 and a v_mov_b32_dpp of its result, an s_nop 0 in front of a v_readlane;
+// if one is missing, the s_nop 1 goes back into the asm.
 __device__ __forceinline__ double min_f64_nc(double a, double b)
 {
     double r;
-    asm("v_min_f64 %0, %1, %2\n\ts_nop 1" : "=v"(r) : "v"(a), "v"(b));
+    asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+// the same with a wave-uniform second operand (an SGPR pair)
+__device__ __forceinline__ double min_f64_nc_s(double a, double bs)
+{
+    double r;
+    asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "s"(bs));
     return r;
 }
 // min over lanes 0..31, returned in EVERY lane 0..31 (lanes 32..63 get the min of their own half):
@@ -593,12 +605,7 @@ __device__ __forceinline__ double wave_min32_all_lowlat_f64(double v)
 // rides in as one v_min with a scalar operand before the stages instead of a v_mov + v_min after them
 __device__ __forceinline__ double wave_min32_with_limit_f64(double v, double lim)
 {
-    {
-        const double ls = udbl(lim);
-        double r;
-        asm("v_min_f64 %0, %1, %2\n\ts_nop 1" : "=v"(r) : "v"(v), "s"(ls));
-        v = r;
-    }
+    v = min_f64_nc_s(v, udbl(lim));
     v = min_f64_nc(v, dpp_f64<0xB1>(v));
     v = min_f64_nc(v, dpp_f64<0x4E>(v));
     v = min_f64_nc(v, dpp_f64<0x141>(v));
@@ -616,12 +623,7 @@ __device__ __forceinline__ double wave_min32_with_limit_f64(double v, double lim
 // 1 and 3, row_bcast:31 into rows 2 and 3, lane 63 read out (callers feed no NaNs; non-candidates carry +inf)
 __device__ __forceinline__ double wave_min64_with_limit_f64(double v, double lim)
 {
-    {
-        const double ls = udbl(lim);
-        double r;
-        asm("v_min_f64 %0, %1, %2\n\ts_nop 1" : "=v"(r) : "v"(v), "s"(ls));
-        v = r;
-    }
+    v = min_f64_nc_s(v, udbl(lim));
     v = min_f64_nc(v, dpp_f64<0xB1>(v));
     v = min_f64_nc(v, dpp_f64<0x4E>(v));
     v = min_f64_nc(v, dpp_f64<0x141>(v));
