@@ -856,9 +856,7 @@ def _multiplier_vertices(eng, Ac, g, cls, lam0, V):
 
 def _recipe_filter(eng, masks, K, vrow_of, first_of):
     fn = getattr(eng, "recipe_filter", None)
-    if callable(fn):
-        return np.asarray(fn(masks, K, vrow_of, first_of))
-    return recipe_filter_host(masks, K, vrow_of, first_of)
+    return fn(masks, K, vrow_of, first_of) if callable(fn) else recipe_filter_host(masks, K, vrow_of, first_of)
 
 
 def explore_products(b, sel, rets, want, masks, total, tol, eng, E):
@@ -927,54 +925,76 @@ def explore_products(b, sel, rets, want, masks, total, tol, eng, E):
                 distinct=distinct)
 
 
-def _explored_capped(eng, explore, cap):
-    """The first `cap` distinct recipes of every item over its products (explore_products), products in order and each in its
-    own recipe order: windows of at most the item's remaining need, enumerated from a running start per product and filtered
-    against the item's earlier products, until the item has `cap` recipes or its products are spent.  Returns (K, vrow_of)."""
-    vm, vt, vf = explore["vmasks"], explore["vtotal"].astype(np.int64), explore["vfirst"]
+def _recipe_rounds(eng, vm, vt, vf, cap, chunk, filtered, up, down):
+    """The one source of recipes.  A row is a product of codes (vm [rows, N], vt [rows] its recipes); an item's rows are
+    consecutive and share vf, the item's first row.  The rule: an item keeps its products in order, each in its own recipe
+    order, minus -- when `filtered` -- the recipes an earlier product of the item holds (recipe_filter), cut after `cap`
+    recipes (None: not cut).  Yields rounds (K, row_of) with the rows ascending; an item's recipes keep that order over the rounds.
+    How the windows lie is efficiency, not meaning.  With a cap: one window per item and pass, on the item's first live
+    unspent row and no longer than what the item still needs, pass after pass until every item is full or spent; the passes
+    make ONE round.  Without a filter that is one pass whose windows all start at recipe 0: the plain recipes_batch call.  Every
+    other layout is ranged, its first round included, and asks once whether the engine takes `first`: the entries called and
+    their number stay what they were when each layout had a body of its own.  cap None: consecutive rows until a round holds
+    `chunk` recipes.
+    (up, down): the arrays' home, see solution_pieces; the masks go there once."""
     rows = vm.shape[0]
-    cur = np.zeros(rows, np.int64)                       # per product: the next recipe to enumerate
-    got = {}                                             # per item (its first row): recipes kept so far
-    kept = [[] for _ in range(rows)]                     # per product: the kept recipe blocks
-    ranged = _supports_first(eng)
-    # products that hold no recipe of their own (every one lies in an earlier product) are skipped outright
-    live = np.ones(rows, bool)
-    for v in range(rows):
-        if v > vf[v]:
+    # (a product of 64 two-code rows has 2^64 recipes: the float counts are bounded before the cast; no window runs past the
+    #  cap, or past MAX_RECIPES without one)
+    vt = np.minimum(vt, 2.0 ** 62).astype(np.int64)
+    live = vt > 0
+    vm_h = up(vm)
+    if filtered:
+        # a product that holds no recipe of its own (every one lies in an earlier product of the item) is skipped outright
+        for v in np.nonzero(live & (np.arange(rows) > vf))[0].tolist():
             live[v] = distinct_recipes(list(vm[vf[v]:v + 1])) > distinct_recipes(list(vm[vf[v]:v]))
-    while True:
-        act, cnt = [], []
-        for f0 in sorted(set(vf.tolist())):
-            have = got.get(f0, 0)
-            if have >= cap:
-                continue
-            v = f0
-            while v < rows and vf[v] == f0 and (not live[v] or cur[v] >= vt[v]):
-                v += 1
-            if v < rows and vf[v] == f0:
-                act.append(v); cnt.append(int(min(vt[v] - cur[v], cap - have)))
-        if not act:
-            break
-        act = np.asarray(act); cnt = np.asarray(cnt, dtype=np.int64)
+        vf_h = up(vf)
+    plain = cap is not None and not filtered
+    ranged = None                                        # does recipes_batch take `first`?  Asked off the plain path only
+
+    def window(act, first, cnt):
+        nonlocal ranged
         offsets = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)
-        if ranged:
-            K, _ = eng.recipes_batch(vm[act], offsets, first=cur[act])
+        if plain:
+            K, _ = eng.recipes_batch(vm[act], offsets)
         else:
-            K, _ = _recipes_range_host(vm[act], cur[act], cnt)
-        K = np.asarray(K)
-        node_of = np.repeat(np.arange(act.size), cnt)
-        keep = _recipe_filter(eng, vm, K, act[node_of], vf).astype(bool)
-        for q, v in enumerate(act.tolist()):
-            blk = K[offsets[q]:offsets[q + 1]][keep[offsets[q]:offsets[q + 1]]]
-            f0 = int(vf[v])
-            blk = blk[:cap - got.get(f0, 0)]
-            kept[v].append(blk)
-            got[f0] = got.get(f0, 0) + blk.shape[0]
-            cur[v] += cnt[q]
-    N = vm.shape[1]
-    Ks = [np.concatenate(kept[v]) if kept[v] else np.zeros((0, N), np.uint8) for v in range(rows)]
-    vrow_of = np.repeat(np.arange(rows), [k.shape[0] for k in Ks])
-    return (np.concatenate(Ks).astype(np.uint8) if rows else np.zeros((0, N), np.uint8)), vrow_of
+            if ranged is None:
+                ranged = _supports_first(eng)
+            K, _ = eng.recipes_batch(vm_h[up(act)], offsets, first=first) if ranged else _recipes_range_host(vm[act], first, cnt)
+        row_of = np.repeat(act, cnt)
+        if filtered:
+            keep = _recipe_filter(eng, vm_h, K, up(row_of.astype(np.int32)), vf_h) != 0
+            K, row_of = K[keep], row_of[down(keep)]
+        return K, row_of
+
+    if cap is None:
+        lv = np.nonzero(live)[0]
+        G = np.concatenate([[0], np.cumsum(vt[lv])]).astype(np.int64)
+        for c0 in range(0, int(G[-1]), chunk):
+            lo = np.maximum(G[:-1], c0); hi = np.minimum(G[1:], c0 + chunk)
+            part = np.nonzero(hi > lo)[0]                # the rows with recipes in this round
+            K, row_of = window(lv[part], lo[part] - G[:-1][part], hi[part] - lo[part])
+            if row_of.size:
+                yield K, row_of
+        return
+    cur = np.zeros(rows, np.int64)                       # per row: the next recipe to enumerate
+    got = np.zeros(rows, np.int64)                       # per item (at its first row): recipes kept so far
+    Ks, rs = [], []
+    while True:
+        act = np.nonzero(live & (cur < vt) & (got[vf] < cap))[0]
+        act = act[np.unique(vf[act], return_index=True)[1]]                         # the first such row of every item
+        if not act.size:
+            break
+        need = cap - got[vf[act]]
+        cnt = np.minimum(vt[act] - cur[act], need)
+        K, row_of = window(act, cur[act], cnt)
+        got[vf[act]] += np.bincount(row_of, minlength=rows)[act]                    # (the filter may have left fewer than cnt)
+        cur[act] += cnt
+        Ks.append(np.asarray(K)); rs.append(row_of)
+    if len(rs) > 1:
+        order = np.argsort(np.concatenate(rs), kind="stable")
+        Ks, rs = [np.concatenate(Ks)[order]], [np.concatenate(rs)[order]]
+    if rs:
+        yield Ks[0], rs[0]
 
 
 def _recipes_range_host(masks, first, counts):
@@ -995,6 +1015,81 @@ def _recipes_range_host(masks, first, counts):
     return K, node_of
 
 
+def _record_spans(rec_of):
+    """(record, first piece, end) for a round whose pieces come record by record, ascending."""
+    ks, starts = np.unique(rec_of, return_index=True)
+    return zip(ks.tolist(), starts.tolist(), starts.tolist()[1:] + [len(rec_of)])
+
+
+def _read_lean(eng, b, K, rec_of, colsel, x, member_tol):
+    """A round read on the host, the capped route's reader: reduced_pieces, then _finish_host record by record -- no hashes, no
+    store, and one record's finished rows alive at a time.  Yields per record (k, first piece t0, status and worst of its
+    pieces as lists, piece, spare).  Status as qpn_finish_pieces writes it: 1 member, 2 merge candidate, 8 flagged.  piece(t)
+    -> the finished rows (A, l, u) of plain piece t and its key in the node's piece set, None for a merge candidate;
+    spare(t) -> a non-member's rows held for the node's fallback: a call gives (A, l, u).
+    (The status, worst and row counts are Python lists and the records come one by one on purpose: the default path has about
+    one piece per record, so its cost is what is done per record, and a record's rows are megabytes at n = m = 32.)"""
+    from .avi_solutions import _probe_vector
+    Ar, lr, ur, rows, flags = (np.asarray(a) for a in eng.reduced_pieces(b.Qc, b.Rc, b.qd, b.Ac, b.Bc, b.l, b.u, np.asarray(K), rec_of))
+    Rmax, rows_l = Ar.shape[2], rows.tolist()
+    for k, t0, t1 in _record_spans(rec_of):
+        cols_k, take_k = colsel[k]
+        st, worst, at = [8] * (t1 - t0), [0.0] * (t1 - t0), {}
+        plain = t0 + np.nonzero(flags[t0:t1] == 0)[0]
+        if plain.size:
+            wk, A3, L2, U2, merge, A6, LU6 = _finish_host(Ar, lr, ur, rows, plain, take_k, x[cols_k], _probe_vector(len(cols_k)))
+            # the parent's verify_solution tests feasibility on exactly these normalised rows with 1e-3 (src/qp_processing.jl:86):
+            # a piece the point fails here would be "infeasible" there by construction (MEMBER_TOL)
+            merge = merge.tolist()
+            for j, (t, w, mg) in enumerate(zip(plain.tolist(), wk.tolist(), merge)):
+                st[t - t0], worst[t - t0], at[t] = (w <= member_tol) + 2 * mg, w, j
+        ckey = cols_k.tobytes()
+
+        def piece(t):
+            j, r = at[t], rows_l[t]
+            key = None if merge[j] else (ckey, A6[j, :r].tobytes(), np.concatenate([LU6[j, :r], LU6[j, Rmax:Rmax + r]]).tobytes())
+            return A3[j, :r].copy(), L2[j, :r].copy(), U2[j, :r].copy(), key
+
+        def spare(t):
+            held = piece(t)[:3]                          # (copies: the record's arrays go when the next record is read)
+            return lambda: held
+        yield k, t0, st, worst, piece, spare
+
+
+def _read_store(eng, finish, b, recd, fin_in, K, rec_of, colsel, x, member_tol, up, down):
+    """A round read through the ABI's store, the uncapped route's reader: reduced_pieces, then `finish` where the arrays live
+    (the engine's finish_pieces on the device, whence only the store and the per-piece words come back; finish_pieces_host,
+    the kernel's twin, on the host).  Status bit 4: a member equal to an earlier one of the round.  Yields what _read_lean
+    yields; a non-member is not in the store: spare keeps its reduced rows, and _finish_host finishes them, bit-equal to the
+    device, only if the node still needs them in the end."""
+    from .avi_solutions import _probe_vector
+    rec_h = up(rec_of)
+    red = eng.reduced_pieces(*recd, K, rec_h)
+    fin = finish(*red, rec_h, *fin_in, b.n, b.m, member_tol=member_tol)
+    st, worst, store_of, As, ls, us, rows_s = (down(fin[key]) for key in ("status", "worst", "store_of", "As", "ls", "us", "rows_s"))
+    rec_l, store_of, rows_s, merged = rec_of.tolist(), store_of.tolist(), rows_s.tolist(), (st & 2).tolist()
+
+    def piece(t):
+        cols_k, j = colsel[rec_l[t]][0], store_of[t]
+        r = rows_s[j]
+        A, l, u = np.ascontiguousarray(As[j, :len(cols_k), :r].T), ls[j, :r].copy(), us[j, :r].copy()
+        key = None if merged[t] else (cols_k.tobytes(), (np.round(A, 6) + 0.0).tobytes(), np.round(np.concatenate([l, u]), 6).tobytes())
+        return A, l, u, key
+
+    def spare(t):
+        one = [down(a[t:t + 1]) for a in red[:4]]        # the reduced rows are kept, and finished only if the node needs them in the end
+        cols_k, take_k = colsel[rec_l[t]]
+
+        def rows():
+            _, A3, L2, U2, _, _, _ = _finish_host(*one, np.zeros(1, np.int64), take_k, x[cols_k], _probe_vector(len(cols_k)))
+            r = int(one[3][0])
+            return A3[0, :r].copy(), L2[0, :r].copy(), U2[0, :r].copy()
+        return rows
+    st, worst = st.tolist(), worst.tolist()
+    for k, t0, t1 in _record_spans(rec_of):
+        yield k, t0, st[t0:t1], worst[t0:t1], piece, spare
+
+
 def solution_pieces(qpn, recs, batches, rets, x, engine, want: Sequence[bool], tol=1e-2, max_pieces=64, member_tol=MEMBER_TOL,
                     truncated=None, _chunk=None, exploration_vertices=0):
     """The solution-graph pieces of MANY nodes around (x, lambda) (process_solution_graph, src/avi.jl:447-477 ->
@@ -1006,101 +1101,102 @@ def solution_pieces(qpn, recs, batches, rets, x, engine, want: Sequence[bool], t
     device when the engine has finish_pieces (its numpy twin otherwise).
     exploration_vertices E >= 2: the recipes of up to E - 1 further vertices of the multiplier set Lambda(x) join each item's
     own (explore_products); a recipe an earlier product of the item holds is skipped, and max_pieces counts the distinct
-    recipes of the item.  E <= 1 launches nothing new."""
+    recipes of the item.  E <= 1 launches nothing new.
+
+    One pipeline serves every mode: _recipe_rounds is the source of recipes, a round is read by _read_lean (a cap) or
+    _read_store (None), and its pieces are admitted below, in recipe order.  The modes differ in the windows' layout and in the
+    reader, nowhere else."""
     from .avi_solutions import _dedupe, _probe_vector
     eng = engine
     x = np.asarray(x, dtype=np.float64)
     out: List[Optional[list]] = [None] * len(recs)
+    # the arrays' home, chosen once: the device for the uncapped route of an engine that finishes pieces there, else the host
+    if max_pieces is None and callable(getattr(eng, "finish_pieces", None)) and getattr(eng, "device", -1) >= 0:
+        import torch
+        up = lambda a: torch.as_tensor(np.ascontiguousarray(a), device=f"cuda:{eng.device}")
+        down = lambda a: a.cpu().numpy()
+        finish = eng.finish_pieces
+    else:
+        up, down, finish = (lambda a: a), np.asarray, finish_pieces_host
+
+    def build(cols_k, A, l, u, merge):
+        Pg = Poly.from_sorted(qpn.num_vars, cols_k, A, l, u, normalise=False)
+        return _dedupe(Pg) if merge else Pg
     for b in batches:
         sel = [k for k, i in enumerate(b.where) if want[i]]
         if not sel:
             continue
         n, m, p = b.n, b.m, b.p
         masks, total = _piece_masks(b, sel, rets, want, tol, eng)
-        explore = None
+        # the rows: one per wanted record, or the products of its explored vertices
+        vsel, vm, vt, vf, distinct = np.asarray(sel), masks, total, np.arange(len(sel), dtype=np.int32), total
         if exploration_vertices >= 2:
-            explore = explore_products(b, sel, rets, want, masks, total, tol, eng, exploration_vertices)
-        if max_pieces is None:
-            _pieces_uncapped(qpn, recs, b, sel, masks, total, x, eng, member_tol, out, _chunk, explore)
-            continue
-        if explore is None:
-            counts = np.minimum(total, max_pieces).astype(np.int64)
-            for t, k in enumerate(sel):
-                if total[t] > max_pieces:
-                    warnings.warn(f"node {recs[b.where[k]]['pid']}: {int(total[t])} local recipes, only the first {max_pieces} "
-                                  "are expanded (max_pieces)")
-                    if truncated is not None:
-                        truncated.add(b.where[k])
-            offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
-            if offsets[-1] == 0:
-                for k in sel:
-                    out[b.where[k]] = []
-                continue
-            K, node_of = eng.recipes_batch(masks, offsets)
-            node_of = np.asarray(node_of)
-            rec_of = np.asarray(sel, dtype=np.int32)[node_of]    # recipe -> record inside the batch
-        else:
-            for t, k in enumerate(sel):
-                if explore["distinct"][t] > max_pieces:
-                    warnings.warn(f"node {recs[b.where[k]]['pid']}: {int(explore['distinct'][t])} local recipes, only the first "
-                                  f"{max_pieces} are expanded (max_pieces)")
-                    if truncated is not None:
-                        truncated.add(b.where[k])
-            K, vrow_of = _explored_capped(eng, explore, max_pieces)
-            if K.shape[0] == 0:
-                for k in sel:
-                    out[b.where[k]] = []
-                continue
-            rec_of = explore["vsel"][vrow_of].astype(np.int32)
-        Ar, lr, ur, rows, flags = eng.reduced_pieces(b.Qc, b.Rc, b.qd, b.Ac, b.Bc, b.l, b.u, np.asarray(K), rec_of)
-        Ar = np.asarray(Ar); lr = np.asarray(lr); ur = np.asarray(ur); rows = np.asarray(rows); flags = np.asarray(flags)
+            ex = explore_products(b, sel, rets, want, masks, total, tol, eng, exploration_vertices)
+            vsel, vm, vt, vf, distinct = ex["vsel"], ex["vmasks"], ex["vtotal"], ex["vfirst"], ex["distinct"]
+        for t in np.nonzero(distinct > (MAX_RECIPES if max_pieces is None else max_pieces))[0].tolist():
+            pid = recs[b.where[sel[t]]]["pid"]
+            if max_pieces is None:
+                raise RuntimeError(f"node {pid}: {int(distinct[t])} local recipes, more than the 2^24 the uncapped solution graph "
+                                   "(max_pieces=None) enumerates")
+            warnings.warn(f"node {pid}: {int(distinct[t])} local recipes, only the first {max_pieces} are expanded (max_pieces)")
+            if truncated is not None:
+                truncated.add(b.where[sel[t]])
         for k in sel:
-            out[b.where[k]] = []
-        colsel = {k: _colsel(b, k) for k in sel}             # per record: the piece's columns [x_d; x_p present] in ascending order
-        seen = {b.where[k]: set() for k in sel}
-        fallback = {}                                        # per node: the piece the point misses least, for a node none of whose
-                                                             # pieces passes (a solution graph is never empty, src/qp_processing.jl:233)
-        def admit(i, Pg, miss, key=None):
-            # the parent's verify_solution tests feasibility on exactly these normalised rows with 1e-3 (src/qp_processing.jl:86):
-            # a piece the point fails here would be "infeasible" there by construction (MEMBER_TOL)
-            if miss <= member_tol:
-                if key is None:
-                    key = _poly_key(Pg)
-                if key not in seen[i]:                       # the reference collects the pieces in a Set (src/avi_solutions.jl:104)
-                    seen[i].add(key)
-                    out[i].append(Pg)
-            elif i not in fallback or miss < fallback[i][0]:
-                fallback[i] = (miss, Pg)
-
-        Rmax = Ar.shape[2]
-        starts = np.searchsorted(rec_of, np.asarray(sel), side="left"); stops = np.searchsorted(rec_of, np.asarray(sel), side="right")
-        for k, t0, t1 in zip(sel, starts.tolist(), stops.tolist()):             # (recipes come record by record, ascending)
-            if t1 <= t0:
-                continue
-            i = b.where[k]
-            cols_k, take_k = colsel[k]
-            ts = np.arange(t0, t1)
-            plain = ts[flags[t0:t1] == 0]
-            miss_of = {}
-            if plain.size:
-                worst, A3, L2, U2, merge, A6, LU6 = _finish_host(Ar, lr, ur, rows, plain, take_k, x[cols_k], _probe_vector(len(cols_k)))
-                ckey = cols_k.tobytes()
-                for j, t in enumerate(plain.tolist()):
-                    r = int(rows[t])
-                    key = None if merge[j] else (ckey, A6[j, :r].tobytes(), np.concatenate([LU6[j, :r], LU6[j, Rmax:Rmax + r]]).tobytes())
-                    miss_of[t] = (float(worst[j]), A3[j, :r].copy(), L2[j, :r].copy(), U2[j, :r].copy(), bool(merge[j]), key)
-            for t in ts.tolist():
-                if flags[t]:
-                    Pg, miss = _flagged_piece(qpn, b, k, np.asarray(K)[t], eng, cols_k, take_k, x)
-                    if Pg is not None:
-                        admit(i, Pg, miss)
-                else:
-                    miss, Aj, lj, uj, mg, key = miss_of[t]
-                    Pg = Poly.from_sorted(qpn.num_vars, cols_k, Aj, lj, uj, normalise=False)
-                    admit(i, _dedupe(Pg) if mg else Pg, miss, key)
+            out[b.where[k]] = []                         # (an item without a recipe keeps an empty graph)
+        colsel = {k: _colsel(b, k) for k in sel}         # per record: the piece's columns [x_d; x_p present] in ascending order
+        chunk = _chunk
+        if max_pieces is None:
+            oc, cap, N = n + p, n + 2 * m, n + m
+            if chunk is None:
+                # per piece: K, reduced_pieces' output and its local-piece workspace, finish_pieces' scratch and store
+                chunk = max(1, CHUNK_BYTES // (N + 8 * (2 * (oc * cap + 2 * cap + 1) + 2 * N * (N + p) + 4 * N + 4 * cap + 4) + 64))
+            take = np.zeros((len(b), oc), np.int32); ncols = np.zeros(len(b), np.int32); xk = np.zeros((len(b), oc)); probe = np.zeros((len(b), oc))
+            for k, (cols_k, take_k) in colsel.items():
+                nc = len(cols_k)
+                ncols[k] = nc; take[k, :nc] = take_k; xk[k, :nc] = x[cols_k]; probe[k, :nc] = _probe_vector(nc)
+            recd = tuple(up(a) for a in (b.Qc, b.Rc, b.qd, b.Ac, b.Bc, b.l, b.u))  # (on the device: the records go up once per batch)
+            fin_in = tuple(up(a) for a in (ncols, take, xk, probe))
+        seen = {b.where[k]: set() for k in sel}          # per node: the keys of its pieces (the reference collects them in a
+                                                         # Set, src/avi_solutions.jl:104)
+        fallback = {}                                    # per node: (miss, Poly or (columns, spare rows, merge)) of the piece the point misses
+                                                         # least, first on ties, for a node none of whose pieces passes (a solution
+                                                         # graph is never empty, src/qp_processing.jl:233)
+        for K, row_of in _recipe_rounds(eng, vm, vt, vf, max_pieces, chunk, exploration_vertices >= 2, up, down):
+            rec_of = vsel[row_of].astype(np.int32)       # recipe -> record inside the batch (records ascend)
+            if max_pieces is None:
+                records = _read_store(eng, finish, b, recd, fin_in, K, rec_of, colsel, x, member_tol, up, down)
+            else:
+                records = _read_lean(eng, b, K, rec_of, colsel, x, member_tol)
+            for k, t0, st, worst, piece, spare in records:
+                i = b.where[k]
+                cols_k, take_k = colsel[k]
+                seen_i, out_i = seen[i], out[i]
+                for t, (s_, miss) in enumerate(zip(st, worst), t0):     # (the miss is the finished rows', taken before _dedupe)
+                    if s_ & 4:                           # an equal earlier piece of this round is in the set already
+                        continue
+                    if s_ & 8:                           # flagged by the device elimination: the host restatement
+                        Pg, miss = _flagged_piece(qpn, b, k, down(K[t]), eng, cols_k, take_k, x)
+                        if Pg is None:
+                            continue
+                        member, key = miss <= member_tol, None
+                    else:
+                        member, Pg = s_ & 1, None
+                    if not member:                       # kept only while it is the node's fallback, and not built before the end
+                        if not out_i and (i not in fallback or miss < fallback[i][0]):
+                            fallback[i] = (miss, Pg if s_ & 8 else (cols_k, spare(t), s_ & 2))
+                        continue
+                    if Pg is None:
+                        A, l, u, key = piece(t)
+                        if key is None:                  # a merge candidate: keyed, as a flagged piece, by what _dedupe leaves
+                            Pg = build(cols_k, A, l, u, True)
+                    if key is None:
+                        key = _poly_key(Pg)
+                    if key not in seen_i:
+                        seen_i.add(key)
+                        out_i.append(Poly.from_sorted(qpn.num_vars, cols_k, A, l, u, normalise=False) if Pg is None else Pg)
         for i, (miss, Pg) in fallback.items():
             if not out[i]:
-                out[i].append(Pg)
+                out[i].append(Pg if isinstance(Pg, Poly) else build(Pg[0], *Pg[1](), Pg[2]))
     return out
 
 
@@ -1131,157 +1227,6 @@ def _supports_first(eng):
         return "first" in inspect.signature(eng.recipes_batch).parameters
     except (TypeError, ValueError):
         return False
-
-
-def _pieces_uncapped(qpn, recs, b, sel, masks, total, x, eng, member_tol, out, chunk, explore=None):
-    """Every recipe of the wanted records of batch b (max_pieces = None), in chunks of at most `chunk` pieces across the records'
-    concatenated recipes.  With an engine that has finish_pieces the batch's records go to the device once, the reduced pieces
-    stay there, and only the finished store and the per-piece words come back; otherwise finish_pieces_host does the same on
-    the host.  The pieces are admitted in recipe order exactly as the capped route admits them.
-    explore (explore_products): the products of the explored vertices take the place of the records' own, one row each, and the
-    recipes an earlier product of the same item holds are dropped after each chunk's enumeration (recipe_filter)."""
-    from .avi_solutions import _dedupe, _probe_vector
-    n, m, p = b.n, b.m, b.p
-    for t, k in enumerate(sel):
-        cnt_t = total[t] if explore is None else explore["distinct"][t]
-        if cnt_t > MAX_RECIPES:
-            raise RuntimeError(f"node {recs[b.where[k]]['pid']}: {int(cnt_t)} local recipes, more than the 2^24 the uncapped "
-                               "solution graph (max_pieces=None) enumerates")
-    if explore is not None:
-        for k in sel:
-            out[b.where[k]] = []                         # (an item without a product keeps an empty graph)
-        sel, masks, total = list(explore["vsel"].tolist()), explore["vmasks"], explore["vtotal"]
-    for k in sel:
-        out[b.where[k]] = []
-    counts = total.astype(np.int64)
-    G = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
-    if G[-1] == 0:
-        return
-    oc, cap, N = n + p, n + 2 * m, n + m
-    if chunk is None:
-        # per piece: K, reduced_pieces' output and its local-piece workspace, finish_pieces' scratch and store
-        per = N + 8 * (2 * (oc * cap + 2 * cap + 1) + 2 * N * (N + p) + 4 * N + 4 * cap + 4) + 64
-        chunk = max(1, CHUNK_BYTES // per)
-    dev = callable(getattr(eng, "finish_pieces", None)) and getattr(eng, "device", -1) >= 0
-    ranged = _supports_first(eng)
-    nb = len(b)
-    colsel = {k: _colsel(b, k) for k in sel}
-    take = np.zeros((nb, oc), np.int32); ncols = np.zeros(nb, np.int32); xk = np.zeros((nb, oc)); probe = np.zeros((nb, oc))
-    for k in sel:
-        cols_k, take_k = colsel[k]
-        nc = len(cols_k)
-        ncols[k] = nc; take[k, :nc] = take_k; xk[k, :nc] = x[cols_k]; probe[k, :nc] = _probe_vector(nc)
-    if dev:
-        import torch
-        dv = f"cuda:{eng.device}"
-        to = lambda a, dt=torch.float64: torch.as_tensor(np.ascontiguousarray(a), dtype=dt, device=dv)
-        recd = tuple(to(a) for a in (b.Qc, b.Rc, b.qd, b.Ac, b.Bc, b.l, b.u))      # the records go up once per batch
-        fin_in = (to(ncols, torch.int32), to(take, torch.int32), to(xk), to(probe))
-        masks_d = to(masks, torch.uint8)
-        if explore is not None:
-            vfirst_d = to(explore["vfirst"], torch.int32)
-    seen = {b.where[k]: {} for k in sel}                 # per node: (columns, hash) -> the exact keys of its pieces
-    fallback = {}                                        # per node: (miss, Poly or the reduced piece to finish, record)
-    members = {b.where[k]: False for k in sel}
-
-    def admit(i, Pg, miss, key=None, h=None):
-        if miss <= member_tol:
-            members[i] = True
-            if key is None:
-                key = _poly_key(Pg)
-                cl, Al_ = Pg.local()
-                L6 = np.round(Pg.l, 6)[None]; U6 = np.round(Pg.u, 6)[None]
-                h = int(_key_hash((np.round(Al_, 6) + 0.0)[None], L6, U6, [Al_.shape[0]])[0])
-            bucket = seen[i].setdefault((key[0], h), [])
-            if key not in bucket:                        # the reference collects the pieces in a Set (src/avi_solutions.jl:104)
-                bucket.append(key)
-                out[i].append(Pg)
-        elif i not in fallback or miss < fallback[i][0]:
-            fallback[i] = (miss, Pg)
-
-    sel_a = np.asarray(sel, dtype=np.int32)
-    for c0 in range(0, int(G[-1]), chunk):
-        c1 = min(c0 + chunk, int(G[-1]))
-        lo = np.maximum(G[:-1], c0); hi = np.minimum(G[1:], c1)
-        part = np.nonzero(hi > lo)[0]                    # the wanted records with recipes in this chunk
-        first = (lo[part] - G[:-1][part]).astype(np.int64); cnt = (hi[part] - lo[part]).astype(np.int64)
-        offsets = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)
-        rec_of = np.repeat(sel_a[part], cnt)             # recipe -> record inside the batch (records ascend)
-        if dev:
-            part_d = torch.as_tensor(part, device=dv)
-            K, node_of = eng.recipes_batch(masks_d[part_d].contiguous(), offsets, first=first)
-            rec_d = to(rec_of, torch.int32)
-            if explore is not None:
-                node_of = node_of.long()
-                keep = eng.recipe_filter(masks_d, K, part_d[node_of].to(torch.int32).contiguous(), vfirst_d).bool()
-                K = K[keep].contiguous(); rec_d = rec_d[keep].contiguous()
-                cnt_k = torch.bincount(node_of[keep], minlength=len(part)).cpu().numpy()
-                offsets = np.concatenate([[0], np.cumsum(cnt_k)]).astype(np.int64)
-                if offsets[-1] == 0:
-                    continue
-            Ar, lr, ur, rows, flags = eng.reduced_pieces(*recd, K, rec_d)
-            fin = eng.finish_pieces(Ar, lr, ur, rows, flags, rec_d, *fin_in, n, m, member_tol=member_tol)
-            st = fin["status"].cpu().numpy(); worst = fin["worst"].cpu().numpy()
-            hsh = fin["hash"].cpu().numpy().view(np.uint64); store_of = fin["store_of"].cpu().numpy()
-            As = fin["As"].cpu().numpy(); ls = fin["ls"].cpu().numpy(); us = fin["us"].cpu().numpy(); rows_s = fin["rows_s"].cpu().numpy()
-            Kh = None
-        else:
-            if ranged:
-                K, _ = eng.recipes_batch(masks[part], offsets, first=first)
-            else:
-                K, _ = _recipes_range_host(masks[part], first, cnt)
-            Kh = np.asarray(K)
-            if explore is not None:
-                node_of = np.repeat(np.arange(len(part)), cnt)
-                keep = _recipe_filter(eng, masks, Kh, part[node_of], explore["vfirst"]).astype(bool)
-                Kh = Kh[keep]; rec_of = rec_of[keep]
-                offsets = np.concatenate([[0], np.cumsum(np.bincount(node_of[keep], minlength=len(part)))]).astype(np.int64)
-                if offsets[-1] == 0:
-                    continue
-            Ar, lr, ur, rows, flags = eng.reduced_pieces(b.Qc, b.Rc, b.qd, b.Ac, b.Bc, b.l, b.u, Kh, rec_of)
-            Ar = np.asarray(Ar); lr = np.asarray(lr); ur = np.asarray(ur)
-            fin = finish_pieces_host(Ar, lr, ur, rows, flags, rec_of, ncols, take, xk, probe, n, m, member_tol=member_tol)
-            st, worst, hsh, store_of = fin["status"], fin["worst"], fin["hash"], fin["store_of"]
-            As, ls, us, rows_s = fin["As"], fin["ls"], fin["us"], fin["rows_s"]
-        for q, k in enumerate(sel_a[part].tolist()):
-            i = b.where[k]
-            cols_k, take_k = colsel[k]
-            nc = len(cols_k); ckey = cols_k.tobytes()
-            for t in range(int(offsets[q]), int(offsets[q + 1])):
-                s_ = int(st[t])
-                if s_ & 8:                               # flagged: the host restatement, as on the capped route
-                    Krow = Kh[t] if Kh is not None else K[t].cpu().numpy()
-                    Pg, miss = _flagged_piece(qpn, b, k, Krow, eng, cols_k, take_k, x)
-                    if Pg is not None:
-                        admit(i, Pg, miss)
-                elif s_ & 1:
-                    if s_ & 4:                           # an equal earlier piece of this chunk is in the set already
-                        continue
-                    j = int(store_of[t]); r = int(rows_s[j])
-                    Aj = np.ascontiguousarray(As[j, :nc, :r].T); lj = ls[j, :r].copy(); uj = us[j, :r].copy()
-                    Pg = Poly.from_sorted(qpn.num_vars, cols_k, Aj, lj, uj, normalise=False)
-                    if s_ & 2:
-                        admit(i, _dedupe(Pg), 0.0)
-                    else:
-                        key = (ckey, (np.round(Aj, 6) + 0.0).tobytes(), np.round(np.concatenate([lj, uj]), 6).tobytes())
-                        admit(i, Pg, 0.0, key, int(hsh[t]))
-                elif not members[i] and (i not in fallback or float(worst[t]) < fallback[i][0]):
-                    # a candidate for the node without member pieces: kept reduced, finished only if it is still needed
-                    piece = tuple(np.asarray(a[t:t + 1].cpu() if dev else a[t:t + 1]) for a in (Ar, lr, ur, rows))
-                    fallback[i] = (float(worst[t]), piece, k, bool(s_ & 2))
-    for i, ent in fallback.items():
-        if out[i]:
-            continue
-        miss, Pg = ent[0], ent[1]
-        if not isinstance(Pg, Poly):                     # the reduced piece, finished on the host now (bit-equal to the device)
-            Ar1, lr1, ur1, rows1 = Pg
-            k, mg = ent[2], ent[3]
-            cols_k, take_k = colsel[k]
-            _, A3, L2, U2, _, _, _ = _finish_host(Ar1, lr1, ur1, rows1, np.zeros(1, np.int64), take_k, x[cols_k], _probe_vector(len(cols_k)))
-            r = int(rows1[0])
-            Pg = Poly.from_sorted(qpn.num_vars, cols_k, A3[0, :r].copy(), L2[0, :r].copy(), U2[0, :r].copy(), normalise=False)
-            Pg = _dedupe(Pg) if mg else Pg
-        out[i].append(Pg)
 
 
 def _refine_row_codes(m2, s, lam, l, u, mt):

@@ -108,9 +108,47 @@ def _same_pieces(a, b):
             assert np.array_equal(p.l, q.l) and np.array_equal(p.u, q.u)
 
 
+def follower_net(rows, lo):
+    """counterexample_net with the follower's rows given: y in R^d minimises 1/2 |y - x|^2 s.t. rows y >= lo."""
+    rows = np.asarray(rows, dtype=np.float64)
+    d = rows.shape[1]
+    net = QPNet(2 * d)
+    cid = net.add_constraint(np.hstack([np.zeros_like(rows), rows]), np.asarray(lo, dtype=np.float64), np.full(len(rows), INF))
+    fol = net.add_qp(np.block([[np.eye(d), -np.eye(d)], [-np.eye(d), np.eye(d)]]), np.zeros(2 * d), [cid], list(range(d, 2 * d)))
+    Ql = np.zeros((2 * d, 2 * d)); Ql[:d, :d] = np.eye(d)
+    ql = np.zeros(2 * d); ql[2 * d - 1] = -1.0
+    lead = net.add_qp(Ql, ql, [], list(range(d)))
+    net.add_edges([(lead, fol)])
+    net.assign_constraint_groups()
+    return net, fol
+
+
+def hand_built_levels():
+    """Follower levels on which the capped and the uncapped reader have something to differ in -- name -> (net, players, x):
+    offpoint      rows y >= 0 in R^3 at x = y = (5e-5, 0, 0): 8 pieces, 4 of them non-members (a code kept by CODE_TOL whose piece
+                  misses the point by more than MEMBER_TOL)
+    nomember      y_1 >= 0 at x = 0, y = 5e-5: both pieces are non-members, the node keeps its fallback
+    parallel      y_1 >= 0, 2 y_1 >= -1, y_2 >= 0 at 0: every piece is a merge candidate (_dedupe)
+    twice         y_1 >= 0 twice, y_2 >= 0 at 0: 8 recipes, 6 merge candidates and 2 flagged (_flagged_piece); 6 pieces are kept,
+                  2 are duplicates found by _poly_key
+    twice_scaled  the same with the second row 2 y_1 >= 0."""
+    e = np.eye(3)
+    out = {}
+    net, fol = follower_net(e, np.zeros(3))
+    out["offpoint"] = (net, [fol], np.array([5e-5, 0, 0, 5e-5, 0, 0]))
+    net, fol = follower_net([[1.0]], [0.0])
+    out["nomember"] = (net, [fol], np.array([0.0, 5e-5]))
+    net, fol = follower_net([e[0], 2 * e[0], e[1]], [0.0, -1.0, 0.0])
+    out["parallel"] = (net, [fol], np.zeros(6))
+    for name, s in (("twice", 1.0), ("twice_scaled", 2.0)):
+        net, fol = follower_net([e[0], s * e[0], e[1]], np.zeros(3))
+        out[name] = (net, [fol], np.zeros(6))
+    return out
+
+
 def parity_levels(eng):
     """Follower levels of three record shapes: the counterexample at its start (128 recipes) and two pair nets at a point
-    off their equilibria (the solve's first iterate)."""
+    off their equilibria (the solve's first iterate); then hand_built_levels."""
     out = []
     net, lead, fol = counterexample_net()
     out.append((net, [fol], np.zeros(14)))
@@ -119,7 +157,7 @@ def parity_levels(eng):
         r = algorithm.solve(net, engine=eng)
         assert r["solved"]
         out.append((net, sorted(net.network_depth_map[2]), r["x_opt"]))
-    return out
+    return out + list(hand_built_levels().values())
 
 
 @pytest.mark.parametrize("chunk", [None, 5])
