@@ -164,7 +164,20 @@ __global__ __launch_bounds__(WAVE, 4) void avi_solve_schur(AviBatchArgs a, Schur
             const double *col = isx ? R_ + it : B_ + (it - nn);
             const size_t cs = isx ? (size_t)nn : (size_t)nm;
             double s = isx ? a.nd.qd[(size_t)b * nn + it] : 0.0;
-            for (int k0 = 0; k0 < np_; k0 += 8) {
+            // whole groups of eight carry no predicate: the column's entries sit at immediate offsets from one address, and w --
+            // the same address on every lane, and not written by this launch -- comes by scalar loads.  The same products
+            // enter the same chain in the same order as in the predicated form below, which takes the last p % 8 terms
+            typedef const double __attribute__((address_space(4))) *wptr_t;
+            const wptr_t ws_ = (wptr_t)w_;
+            int k0 = 0;
+            for (; k0 + 8 <= np_; k0 += 8) {
+                double rv[8], wv[8];
+#pragma unroll
+                for (int k = 0; k < 8; ++k) { rv[k] = col[(size_t)(k0 + k) * cs]; wv[k] = ws_[k0 + k]; }
+#pragma unroll
+                for (int k = 0; k < 8; ++k) s = fma(rv[k], wv[k], s);
+            }
+            if (k0 < np_) {
                 double rv[8], wv[8];
 #pragma unroll
                 for (int k = 0; k < 8; ++k) {
@@ -260,10 +273,23 @@ __global__ __launch_bounds__(WAVE, 4) void avi_solve_schur(AviBatchArgs a, Schur
         {
             typedef const __attribute__((address_space(1))) void *gptr_t;
             typedef __attribute__((address_space(3))) void *lptr_t;
-            const char *const ga = reinterpret_cast<const char *>(A_) + l * 4;
-#pragma unroll
-            for (int cj = 0; cj < 32; ++cj)
-                __builtin_amdgcn_global_load_lds((gptr_t)(ga + cj * 256), (lptr_t)(sA + cj * SAS), 4, 0, 0);
+            // One global base per 16 columns; the column's 256 B step rides in the instruction's immediate offset (12 bits: 15 x 256
+            // fits).  That offset enters BOTH addresses -- global = base + offset, LDS = M0 + offset + 4 x lane -- so the LDS
+            // pointer handed over (it becomes M0) carries only the 16 B per column by which the padded LDS stride exceeds the
+            // global one: column 16 h + cj lands at (16 h + cj) * SAS * 8 as before.  Two instructions per column instead of four
+            // (test_gpu_nonloop_paths.py pins the layout: a misplaced column changes resid and active).
+            const unsigned l4 = (unsigned)l * 4u;       // (a 32-bit lane offset on a scalar base: no 64-bit vector add)
+            __attribute__((address_space(3))) char *const la = (__attribute__((address_space(3))) char *)sA;      // (LDS arithmetic: no generic-pointer null test)
+            // (the offset is an immediate: the columns are written out, not looped over)
+#define M_DMA(H, CJ)                                                                                \
+            __builtin_amdgcn_global_load_lds((gptr_t)(reinterpret_cast<const char *>(A_ + (H) * 512) + l4), (lptr_t)(la + (H) * (16 * SAS * 8) + (CJ) * (SAS * 8 - 256)), 4, \
+                                             (CJ) * 256, 0);
+#define M_DMA16(H)                                                                                  \
+            M_DMA(H, 0) M_DMA(H, 1) M_DMA(H, 2) M_DMA(H, 3) M_DMA(H, 4) M_DMA(H, 5) M_DMA(H, 6) M_DMA(H, 7)                \
+            M_DMA(H, 8) M_DMA(H, 9) M_DMA(H, 10) M_DMA(H, 11) M_DMA(H, 12) M_DMA(H, 13) M_DMA(H, 14) M_DMA(H, 15)
+            M_DMA16(0) M_DMA16(1)
+#undef M_DMA16
+#undef M_DMA
         }
         const double *const cu = cc + kCrashU + (l >> 5) * 512 + (l & 31) * 4;
         d4 up0 = crash_load(reinterpret_cast<const d4 *>(cu)), up1 = crash_load(reinterpret_cast<const d4 *>(cu + 128));
@@ -789,7 +815,8 @@ stage_a_done: __attribute__((unused));
     {
         double viol = 0.0;
         if (actb) viol = xb < lo ? lo - xb : (xb > hi ? xb - hi : 0.0);
-        const double theta0 = wave_max_f64(viol);
+        // (viol is lo - xb or xb - hi under the compare that makes it positive, or the constant 0: a computed value, never a NaN)
+        const double theta0 = wave_max_f64_nc(viol);
         if (ubool(theta0 <= a.feas_tol)) status = QPN_SUCCESS;
         else {
             if (actb) {
@@ -1352,9 +1379,11 @@ stage_a_done: __attribute__((unused));
         } else mask = 8u;
         if (gk) mask <<= 4;
     }
-    bad = wave_sum_i32(bad);
-    nres = wave_max_f64(nres);
-    if (bad > 0 && status == QPN_SUCCESS) status = QPN_FAILURE;
+    // the counts are >= 0 and only "any" is asked of their sum: one lane mask instead of six cross-lane additions.
+    // nres is |pp - tt| with a NaN already replaced by +inf, or the constant 0: a computed value, never a NaN
+    const bool anybad = qpn_ballot(bad != 0) != 0ull;
+    nres = wave_max_f64_nc(nres);
+    if (anybad && status == QPN_SUCCESS) status = QPN_FAILURE;
     if (act) {
         ae.z[vo + l] = zk;
         if (ae.x && l < n) {                                                    // primal block -> the caller's iterate

@@ -577,6 +577,40 @@ __device__ __forceinline__ double min_f64_nc_s(double a, double bs)
     asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "s"(bs));
     return r;
 }
+// v_max_f64 without the canonicalising v_max x, x the compiler puts in front of each operand of fmax() (the same toolchain
+// property as min_f64_nc above, and the same listing check).  For operands that are COMPUTED values and never NaNs: the
+// result of an fp64 add, subtract or |.| of one, a constant, or a NaN already replaced by a select.  On such operands the
+// canonicalisation is the identity (it only quiets signalling NaNs; fp64 denormals are kept), so both forms give the same bits.
+__device__ __forceinline__ double max_f64_nc(double a, double b)
+{
+    double r;
+    asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+// wave_max_f64 for such operands, wave-uniform result: the four row stages, then the rows cross as in
+// wave_min64_with_limit_f64 (row_bcast:15 into rows 1 and 3, row_bcast:31 into rows 2 and 3) and lane 63 is read out --
+// 6 v_max_f64 and 2 v_readlane where fmax() and four row read-outs cost 7 + 14 v_max_f64, 8 v_readlane and their copies.
+// A maximum does not depend on the order of its operands, so the other crossing gives the same bits.
+__device__ __forceinline__ double wave_max_f64_nc(double v)
+{
+    v = max_f64_nc(v, dpp_f64<0xB1>(v));
+    v = max_f64_nc(v, dpp_f64<0x4E>(v));
+    v = max_f64_nc(v, dpp_f64<0x141>(v));
+    v = max_f64_nc(v, dpp_f64<0x140>(v));
+    {
+        int lo = __double2loint(v), hi = __double2hiint(v);
+        lo = __builtin_amdgcn_update_dpp(lo, lo, 0x142, 0xA, 0xF, false);      // rows 1, 3 <- lane 15 of rows 0, 2
+        hi = __builtin_amdgcn_update_dpp(hi, hi, 0x142, 0xA, 0xF, false);
+        v = max_f64_nc(v, __hiloint2double(hi, lo));
+    }
+    {
+        int lo = __double2loint(v), hi = __double2hiint(v);
+        lo = __builtin_amdgcn_update_dpp(lo, lo, 0x143, 0xC, 0xF, false);      // rows 2, 3 <- lane 31
+        hi = __builtin_amdgcn_update_dpp(hi, hi, 0x143, 0xC, 0xF, false);
+        v = max_f64_nc(v, __hiloint2double(hi, lo));
+    }
+    return readlane_f64(v, 63);
+}
 // min over lanes 0..31, returned in EVERY lane 0..31 (lanes 32..63 get the min of their own half):
 // four DPP row stages + one ds_swizzle (lane ^ 16, on the LDS crossbar) -- no v_readlane, no SGPR detour
 __device__ __forceinline__ double wave_min32_all_f64(double v)
