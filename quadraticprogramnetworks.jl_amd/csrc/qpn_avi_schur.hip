@@ -62,12 +62,17 @@ struct SchurDebug { double *S, *c, *W, *h; };
 // the handle's crash cache (layout: qpn_internal.h, kCrash*); 2 = REUSE them: no Qd staging, no factorisation, no MFMA --
 // kx is replayed with the stored U' by the same operations in the same order, so every output has the same bits (W~ is fetched
 // after the pivot loop, and only its columns with a nonzero multiplier: see the read-back);
-// 3 = MIXED: the cache is valid and every wavefront picks one of the two Stage A bodies -- reuse as 2, or compute as 0 (storing
-// nothing) -- by a wave-uniform rule on its position in the launch (crash_mix_recomputes, qpn_internal.h: the launcher's share
-// of the positions below a.crash_reuse_from compute, spread evenly over each XCD's dispatch sequence).  The reuse body is bound
-// by HBM bytes and leaves the fp64 pipe half idle, the compute body the reverse; both give the same
-// bits, so the choice is free per wavefront.  The bodies join before the transposition of S(1,0); from there on there is one
-// copy of the code, with the fixed bounds and h parked in sbuf as in 2.
+// 3 = MIXED: the cache is valid and every wavefront picks one of two Stage A bodies -- reuse as 2, or REPLAY W~ -- by a
+// wave-uniform rule on its position in the launch (crash_mix_recomputes, qpn_internal.h: the launcher's share of the positions
+// below a.crash_reuse_from replay, spread evenly over each XCD's dispatch sequence).  So Stage A has three bodies in all:
+//   compute (0, 1): stage Qd, factor the eight pivot blocks, solve the panels U', update the H and the C tiles;
+//   reuse (2, 3):   load U', S and later the needed columns of W~; replay kx; no MFMA;
+//   replay W~ (3):  load U' alone (and the flag); replay kx as reuse does, and rebuild W~ by applying the compute body's MFMAs to
+//                   the C tiles with U' as their A operands -- no Qd, no factorisation, no H tile --, then S = A W~ as compute.
+// The reuse body is bound by HBM bytes and leaves the fp64 pipe idle, the replay body asks for neither S nor W~ and works
+// on the matrix cores; all bodies give the same bits -- the same operations on the same operands --, so
+// the choice is free per wavefront.  The bodies join before the transposition of S(1,0); from there on there is one copy of the
+// code, with the fixed bounds and h parked in sbuf as in 2.
 // STREAM (CRASH 2 and 3 only): the cache policy of a sweep whose node records fit the last-level cache while records + crash
 // cache do not (llc_streams_crash, qpn_internal.h).  The crash cache -- U', S and the W~ columns, each read once per sweep -- is
 // then fetched with non-temporal loads, so that it does not push the records (Ad, Qd, R, B, qd, l, u: default policy) out of
@@ -263,34 +268,47 @@ __global__ __launch_bounds__(WAVE, 4) void avi_solve_schur(AviBatchArgs a, Schur
         const kargs_m km = (kargs_m)__builtin_amdgcn_kernarg_segment_ptr();
         reuse_w = !crash_mix_recomputes((int)blockIdx.x, km->crash_share, km->crash_reuse_from);
     }
-    if constexpr (CRASH >= 2) if (reuse_w) {
-        // ---- reuse.  ONE round of loads brings everything Stage B needs (each further dependent round trip costs a wave as much
-        // as the crash it replaces): Ad, U', S, the bounds and q.  To fit the registers, Ad goes straight into the LDS block
-        // buffer (LDS-DMA, one column of 32 rows = 256 B per instruction, lane <-> 4 bytes: the padded column stride stays) and
-        // U' is split over the two halves of the wavefront: lane l holds steps 0..3 of row l, lane l + 32 steps 4..7 of row l.
-        const uint8_t fl = *crash_flag();
-        const double *const cc = crash_base();
-        {
-            typedef const __attribute__((address_space(1))) void *gptr_t;
-            typedef __attribute__((address_space(3))) void *lptr_t;
-            // One global base per 16 columns; the column's 256 B step rides in the instruction's immediate offset (12 bits: 15 x 256
-            // fits).  That offset enters BOTH addresses -- global = base + offset, LDS = M0 + offset + 4 x lane -- so the LDS
-            // pointer handed over (it becomes M0) carries only the 16 B per column by which the padded LDS stride exceeds the
-            // global one: column 16 h + cj lands at (16 h + cj) * SAS * 8 as before.  Two instructions per column instead of four
-            // (test_gpu_nonloop_paths.py pins the layout: a misplaced column changes resid and active).
-            const unsigned l4 = (unsigned)l * 4u;       // (a 32-bit lane offset on a scalar base: no 64-bit vector add)
-            __attribute__((address_space(3))) char *const la = (__attribute__((address_space(3))) char *)sA;      // (LDS arithmetic: no generic-pointer null test)
-            // (the offset is an immediate: the columns are written out, not looped over)
+    // Ad straight into the LDS block buffer (LDS-DMA, one column of 32 rows = 256 B per instruction, lane <-> 4 bytes: the padded
+    // column stride stays) -- the first round of both cache-reading bodies, reuse and replay.
+    // One global base per 16 columns; the column's 256 B step rides in the instruction's immediate offset (12 bits: 15 x 256
+    // fits).  That offset enters BOTH addresses -- global = base + offset, LDS = M0 + offset + 4 x lane -- so the LDS
+    // pointer handed over (it becomes M0) carries only the 16 B per column by which the padded LDS stride exceeds the
+    // global one: column 16 h + cj lands at (16 h + cj) * SAS * 8 as before.  Two instructions per column instead of four
+    // (test_gpu_nonloop_paths.py pins the layout: a misplaced column changes resid and active).
+    // l4: a 32-bit lane offset on a scalar base, no 64-bit vector add; la: LDS arithmetic, no generic-pointer null test; the
+    // offset is an immediate, so the columns are written out, not looped over.
 #define M_DMA(H, CJ)                                                                                \
             __builtin_amdgcn_global_load_lds((gptr_t)(reinterpret_cast<const char *>(A_ + (H) * 512) + l4), (lptr_t)(la + (H) * (16 * SAS * 8) + (CJ) * (SAS * 8 - 256)), 4, \
                                              (CJ) * 256, 0);
 #define M_DMA16(H)                                                                                  \
             M_DMA(H, 0) M_DMA(H, 1) M_DMA(H, 2) M_DMA(H, 3) M_DMA(H, 4) M_DMA(H, 5) M_DMA(H, 6) M_DMA(H, 7)                \
             M_DMA(H, 8) M_DMA(H, 9) M_DMA(H, 10) M_DMA(H, 11) M_DMA(H, 12) M_DMA(H, 13) M_DMA(H, 14) M_DMA(H, 15)
-            M_DMA16(0) M_DMA16(1)
-#undef M_DMA16
-#undef M_DMA
+#define M_DMA_AD                                                                                    \
+        {                                                                                           \
+            typedef const __attribute__((address_space(1))) void *gptr_t;                           \
+            typedef __attribute__((address_space(3))) void *lptr_t;                                 \
+            const unsigned l4 = (unsigned)l * 4u;                                                   \
+            __attribute__((address_space(3))) char *const la = (__attribute__((address_space(3))) char *)sA; \
+            M_DMA16(0) M_DMA16(1)                                                                   \
         }
+    // kx += U'[l] . kx[p0 .. p0 + 3], step by step: M_USOLVE's update with the stored panel (lane = row, lanes 0..31)
+#define M_REPLAY(KB, UP)                                                                            \
+        {                                                                                           \
+            const double x0 = readlane_f64(kx, 4 * (KB)), x1 = readlane_f64(kx, 4 * (KB) + 1);      \
+            const double x2 = readlane_f64(kx, 4 * (KB) + 2), x3 = readlane_f64(kx, 4 * (KB) + 3);  \
+            if (l < 32) {                                                                           \
+                const double t_ = fma(UP[3], x3, fma(UP[2], x2, fma(UP[1], x1, UP[0] * x0)));       \
+                kx = kx + t_;                                                                       \
+            }                                                                                       \
+        }
+    if constexpr (CRASH >= 2) if (reuse_w) {
+        // ---- reuse.  ONE round of loads brings everything Stage B needs (each further dependent round trip costs a wave as much
+        // as the crash it replaces): Ad, U', S, the bounds and q.  To fit the registers, Ad goes straight into the LDS block
+        // buffer (M_DMA_AD) and U' is split over the two halves of the wavefront: lane l holds steps 0..3 of row l, lane l + 32
+        // steps 4..7 of row l.
+        const uint8_t fl = *crash_flag();
+        const double *const cc = crash_base();
+        M_DMA_AD
         const double *const cu = cc + kCrashU + (l >> 5) * 512 + (l & 31) * 4;
         d4 up0 = crash_load(reinterpret_cast<const d4 *>(cu)), up1 = crash_load(reinterpret_cast<const d4 *>(cu + 128));
         d4 up2 = crash_load(reinterpret_cast<const d4 *>(cu + 256)), up3 = crash_load(reinterpret_cast<const d4 *>(cu + 384));
@@ -309,16 +327,6 @@ __global__ __launch_bounds__(WAVE, 4) void avi_solve_schur(AviBatchArgs a, Schur
         SQ(l) = ql;
         wave_sync();
         kx = (l < 32) ? ql : 0.0;
-        // kx += U'[l] . kx[p0 .. p0 + 3], step by step: M_USOLVE's update with the stored panel
-#define M_REPLAY(KB, UP)                                                                            \
-        {                                                                                           \
-            const double x0 = readlane_f64(kx, 4 * (KB)), x1 = readlane_f64(kx, 4 * (KB) + 1);      \
-            const double x2 = readlane_f64(kx, 4 * (KB) + 2), x3 = readlane_f64(kx, 4 * (KB) + 3);  \
-            if (l < 32) {                                                                           \
-                const double t_ = fma(UP[3], x3, fma(UP[2], x2, fma(UP[1], x1, UP[0] * x0)));       \
-                kx = kx + t_;                                                                       \
-            }                                                                                       \
-        }
         M_REPLAY(0, up0) M_REPLAY(1, up1) M_REPLAY(2, up2) M_REPLAY(3, up3)
         // steps 4..7 come over from the upper half (data movement only)
 #pragma unroll
@@ -327,11 +335,76 @@ __global__ __launch_bounds__(WAVE, 4) void avi_solve_schur(AviBatchArgs a, Schur
             up2[k] = from_upper_half(up2[k]); up3[k] = from_upper_half(up3[k]);
         }
         M_REPLAY(4, up0) M_REPLAY(5, up1) M_REPLAY(6, up2) M_REPLAY(7, up3)
-#undef M_REPLAY
         if (l < 32) sz[l] = kx;
         goto stage_a_done;          // (one diamond: a second test of reuse_w hides from the compiler that the bodies exclude each other)
     }
     if constexpr (CRASH != 2) {
+    // the tiles of C from the block buffer's copy of Ad
+#define M_LOADC(I, J, FULL)                                                                         \
+    _Pragma("unroll") for (int g = 0; g < 4; ++g) {                                                 \
+        const int rr = 16 * (I) + 4 * g + lq, ck = 16 * ((J) - 2) + lc;                             \
+        const double t_ = sA[rr * SAS + ck];        /* the tiles hold -C = +Ad': W~ = -W, signs folded in below */ \
+        TL(I, J)[g] = ((FULL) || (rr < n && ck < m)) ? t_ : 0.0;                                    \
+    }
+    // explicit M: the smallest accepted pivot of Stage A, kept in an idle LDS slot (see `minpiv`)
+    double *const sMinPiv = sbuf + 191;
+    if constexpr (CRASH == 3) {
+        // ---- replay W~ (the positions of a mixed launch that do not reuse).  The C tiles, which end as W~, and the extra column
+        // depend on H only through the eight panels U' -- and those sit in the crash cache (M_USOLVE stores them in CRASH 1).  So
+        // this body neither stages Qd nor factors a pivot block nor touches an H tile: it applies the compute body's MFMAs of
+        // M_COLTILE(2 / 3, ...) to the C tiles -- the same instructions on the same operands, the cache holds the NEGF form -U' --
+        // with the A operands taken from the cache, and replays kx as the reuse body does.  W~ then stays in its tiles through
+        // Stage B, and S is formed from it below: no S and no W~ comes from HBM, which is what a mixed launch wants of these
+        // positions (the fp64 pipe is idle while the reusing wavefronts wait for their bytes).
+        // ONE round of loads, as in the reuse body: Ad by LDS-DMA, the bounds, q, and U' twice -- in the lane = row layout of the
+        // reuse body for kx, and as MFMA A operands: panel KB, row r, entry k sits at KB * 128 + r * 4 + k, so the operand
+        // element (i = lc, k = lq) of row tile I is one double at KB * 128 + (16 I + lc) * 4 + lq, 64 lanes = 512 contiguous
+        // bytes.  The second request hits the lines of the first.
+        // The stored flag carries the pivot test and the "W~ is finite" test of the filling sweep: a node declines here exactly
+        // when the compute body would decline it, so neither max |M| nor either test is formed again.
+        const uint8_t fl = *crash_flag();
+        const double *const cc = crash_base();
+        M_DMA_AD
+        const double *const cu = cc + kCrashU + (l >> 5) * 512 + (l & 31) * 4;
+        d4 up0 = crash_load(reinterpret_cast<const d4 *>(cu)), up1 = crash_load(reinterpret_cast<const d4 *>(cu + 128));
+        d4 up2 = crash_load(reinterpret_cast<const d4 *>(cu + 256)), up3 = crash_load(reinterpret_cast<const d4 *>(cu + 384));
+        const double *const ca = cc + kCrashU + lc * 4 + lq;
+        double au0[8], au1[8];
+#pragma unroll
+        for (int kb = 0; kb < 8; ++kb) { au0[kb] = crash_load(ca + kb * 128); au1[kb] = crash_load(ca + kb * 128 + 64); }
+        if (l < 32) { lo_pre = a.nd.l[(size_t)b * 32 + l]; hi_pre = a.nd.u[(size_t)b * 32 + l]; }
+        const double ql = qelem(l);
+        // (the LDS-DMA writes are ordered for the readers below by this wait: they count on vmcnt like the loads)
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (ubool(fl != 1)) { decline(); return; }
+        SQ(l) = ql;
+        wave_sync();
+        STAMP(0);   // setup + load
+        kx = (l < 32) ? ql : 0.0;
+        M_LOADC(0, 2, true) M_LOADC(0, 3, true) M_LOADC(1, 2, true) M_LOADC(1, 3, true)
+        // step KB: the pivot rows 4 KB .. 4 KB + 3 of a column tile are register GP of tile (JP, J), raw -- the B operand, as in
+        // M_COLTILE (a private, opaque copy: they are part of an accumulator tile too)
+#define M_WCOL(J, KB, JP, GP)                                                                       \
+        {                                                                                           \
+            double vraw = TL(JP, J)[GP];                                                            \
+            asm volatile("" : "+v"(vraw));                                                          \
+            TL(0, J) = MFMA(au0[KB], vraw, TL(0, J));                                               \
+            TL(1, J) = MFMA(au1[KB], vraw, TL(1, J));                                               \
+        }
+#define M_WSTEP(KB, JP, GP) M_WCOL(2, KB, JP, GP) M_WCOL(3, KB, JP, GP)
+        M_REPLAY(0, up0) M_WSTEP(0, 0, 0) M_REPLAY(1, up1) M_WSTEP(1, 0, 1)
+        M_REPLAY(2, up2) M_WSTEP(2, 0, 2) M_REPLAY(3, up3) M_WSTEP(3, 0, 3)
+        // steps 4..7 of kx come over from the upper half (data movement only)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            up0[k] = from_upper_half(up0[k]); up1[k] = from_upper_half(up1[k]);
+            up2[k] = from_upper_half(up2[k]); up3[k] = from_upper_half(up3[k]);
+        }
+        M_REPLAY(4, up0) M_WSTEP(4, 1, 0) M_REPLAY(5, up1) M_WSTEP(5, 1, 1)
+        M_REPLAY(6, up2) M_WSTEP(6, 1, 2) M_REPLAY(7, up3) M_WSTEP(7, 1, 3)
+#undef M_WSTEP
+#undef M_WCOL
+    } else {
     double mabs = 0.0;
     if constexpr (NODES) {
         // Qd and Ad with fully coalesced loads (two columns of 32 rows per instruction = 512 contiguous
@@ -344,12 +417,6 @@ __global__ __launch_bounds__(WAVE, 4) void avi_solve_schur(AviBatchArgs a, Schur
         double v = sA[cc * SQS + rr];                                                               \
         if (!(FULL) && rr == cc && rr >= n) v = 1.0;                /* padded x rows: identity */     \
         TL(I, J)[g] = v;                                                                            \
-    }
-#define M_LOADC(I, J, FULL)                                                                         \
-    _Pragma("unroll") for (int g = 0; g < 4; ++g) {                                                 \
-        const int rr = 16 * (I) + 4 * g + lq, ck = 16 * ((J) - 2) + lc;                             \
-        const double t_ = sA[rr * SAS + ck];        /* the tiles hold -C = +Ad': W~ = -W, signs folded in below */ \
-        TL(I, J)[g] = ((FULL) || (rr < n && ck < m)) ? t_ : 0.0;                                    \
     }
 #define M_NODE_LOAD(FULL)                                                                           \
     {                                                                                               \
@@ -481,8 +548,7 @@ __global__ __launch_bounds__(WAVE, 4) void avi_solve_schur(AviBatchArgs a, Schur
     // explicit M: the pivot threshold is relative to max |M| over the WHOLE item, and the D block is read only after the
     // crash.  The smallest accepted pivot is kept; once max |D| is known, an item with a pivot below 1e-4 max |D| is declined
     // after all -- the same items as a threshold known in advance would have declined (the pivots do not depend on it).
-    // (kept in an idle LDS slot, not in a register pair across the eight steps)
-    double *const sMinPiv = sbuf + 191;
+    // (kept in an idle LDS slot, not in a register pair across the eight steps: sMinPiv)
     if constexpr (!NODES) { if (l == 0) sMinPiv[0] = QINF; }
     // NEGF (node path): the factorisation carries the opposite sign throughout -- nrd = -1 / u_ss, the multipliers kept in pm are
     // -l_is, the panel solve yields -U' -- so that every step is a plain fma and no operand is negated by an instruction of
@@ -613,6 +679,7 @@ __global__ __launch_bounds__(WAVE, 4) void avi_solve_schur(AviBatchArgs a, Schur
         *reinterpret_cast<d4 *>(cw + crash_w_index(16 + lq, lc)) = TL(1, 2);
         *reinterpret_cast<d4 *>(cw + crash_w_index(16 + lq, 16 + lc)) = TL(1, 3);
     }
+    }   // (the compute body; the replay body of CRASH 3 joins here)
 
     // ---- S = D - A W on the matrix cores, c = b - A h -----------------------------------------------------
     // W = TL(0..1, 2..3) (rows = x, an aligned group of 4 rows is a B operand), h = kx (lanes 0..31).
@@ -655,8 +722,9 @@ __global__ __launch_bounds__(WAVE, 4) void avi_solve_schur(AviBatchArgs a, Schur
             SB(1, 1) = M_SACC(a1_, TL(I, 3)[g], SB(1, 1));                                          \
         }                                                                                           \
     }
-    // bounds of pair l for Stage B: requested here so that the round trip hides behind the 32 MFMAs
-    if constexpr (NODES) {
+    // bounds of pair l for Stage B: requested here so that the round trip hides behind the 32 MFMAs (the replay body has them
+    // from its first round)
+    if constexpr (NODES && CRASH != 3) {
         if (l < m) { lo_pre = a.nd.l[(size_t)b * nm + l]; hi_pre = a.nd.u[(size_t)b * nm + l]; }
     }
     M_SK(0, 0, 0) M_SK(0, 1, 1) M_SK(0, 2, 2) M_SK(0, 3, 3) M_SK(1, 0, 4) M_SK(1, 1, 5) M_SK(1, 2, 6) M_SK(1, 3, 7)
@@ -669,7 +737,11 @@ __global__ __launch_bounds__(WAVE, 4) void avi_solve_schur(AviBatchArgs a, Schur
             cs[(0 * 4 + g) * 64 + l] = SB(0, 0)[g]; cs[(1 * 4 + g) * 64 + l] = SB(0, 1)[g]; cs[(2 * 4 + g) * 64 + l] = SB(1, 1)[g];
         }
     }
-    }   // (the computing body)
+    }   // (the computing bodies: compute and replay)
+#undef M_REPLAY
+#undef M_DMA_AD
+#undef M_DMA16
+#undef M_DMA
 stage_a_done: __attribute__((unused));
     if constexpr (SYM) {
         // S(1,0) = S(0,1)'.  (Also exact and 0.5 % slower: on the matrix cores -- register kb of a tile in the accumulator layout IS
