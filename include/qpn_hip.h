@@ -362,7 +362,8 @@ int qpn_recipes_from_masks(qpn_ctx *ctx, int32_t N, const uint8_t *mask, int64_t
  *   the columns [x_d (n); x_p (p)] and with room for cap = n + 2m rows: Ar = the cap x (n+p) matrix, column-major,
  *   lr, ur [cap], rows = the number of rows that remain (in their original order), flags: bit 0 = a multiplier column was pinned
  *   by no equality row while an alive row still holds it (degenerate active set: the projection needs Fourier-Motzkin / vertex
- *   enumeration, which stays with the caller -- the piece's output is then incomplete), bit 1 = more than cap rows remained.
+ *   enumeration: qpn_project_pieces below takes such pieces -- the piece's output here is then incomplete), bit 1 = more than cap
+ *   rows remained.
  *   Beyond rows[t] every output is filled: Ar with zeros, lr with -inf, ur with +inf (a piece whose device-side node_of entry
  *   is out of range is all fill: rows = 0, flags = 0).
  *   The local pieces themselves live in the context's workspace only.  n + m <= 512. */
@@ -372,6 +373,34 @@ int qpn_reduced_pieces(qpn_ctx *ctx, int32_t pieces, int32_t nodes, int32_t n, i
                        const double *R, const double *qd, const double *Ad, const double *B, const double *l,
                        const double *u, const int32_t *node_of, const uint8_t *K, double tol, double *Ar, double *lr, double *ur,
                        int32_t *rows, int32_t *flags, int mem);
+
+/* ---- degenerate pieces: the projection onto [x_d; x_p] by Fourier-Motzkin steps ------------------------------------------------
+ * qpn_project_pieces: qpn_reduced_pieces for the pieces it flags with bit 0.  Arguments as there, plus cap: the rows of room per
+ *   piece, cap >= n + 2m (else QPN_ERR_ARG).  Per piece:
+ *   1. local_piece and the elimination through the piece's own equality rows, operation by operation as qpn_reduced_pieces does
+ *      them; a multiplier column that no equality row pins while an alive row holds it (|a| > tol) is not flagged but joins the
+ *      list `left`, ascending.  The alive rows are then taken in their order.
+ *   2. One Fourier-Motzkin step per column j of `left`, ascending, on the rows the step before it left:
+ *        the rows with |a_kj| <= tol come first, in order, unchanged;
+ *        every other row k, in order, gives up to two one-sided inequalities, in this order: (a_k, u_k) if u_k is finite, then
+ *        (-a_k, -l_k) if l_k is finite; each is divided, entry by entry and in its bound, by |a_kj|, and goes to the list ub if
+ *        its entry j is > 0, else to the list lb;
+ *        the new rows are au + al with the bounds (-inf, bu + bl), for every entry of ub (outer loop) against every entry of lb
+ *        (inner loop); column j is then 0 in all rows.
+ *      Divisions and additions only, no contraction: bit-equal to the same steps in IEEE double arithmetic on the host.
+ *      A step first counts its rows, nz + |ub| |lb|, in 64 bits: more than cap gives the piece flag bit 2, its outputs are all
+ *      fill with rows = 0, and nothing more is computed for it.  Redundant rows are not removed.
+ *   3. Output over the columns [x_d (n); x_p (p)]: Ar = the cap x (n+p) matrix, column-major, lr, ur [cap], rows, flags; beyond
+ *      rows[t] the fill of qpn_reduced_pieces (0, -inf, +inf).  For a piece without a left column the first n + 2m rows equal
+ *      qpn_reduced_pieces' output.
+ *   flags: bit 0 is never set;  bit 1 = more than cap rows were alive after step 1 (the first cap go out, step 2 is skipped: not
+ *   possible for cap >= n + 2m unless the x_d rows carry codes other than 2);  bit 2 (value 4) = a step needed more than cap rows.
+ *   The local pieces and the steps' rows live in the context's workspace: a call is split into chunks of pieces that fit 512 MiB
+ *   of it; a cap of which not even one piece fits is QPN_ERR_SIZE.  n + m <= 512. */
+int qpn_project_pieces(qpn_ctx *ctx, int32_t pieces, int32_t nodes, int32_t n, int32_t m, int32_t p, const double *Qd,
+                       const double *R, const double *qd, const double *Ad, const double *B, const double *l,
+                       const double *u, const int32_t *node_of, const uint8_t *K, double tol, int32_t cap, double *Ar, double *lr,
+                       double *ur, int32_t *rows, int32_t *flags, int mem);
 
 /* ---- every recipe of a solution graph, chunk by chunk, finished on the device (QPNetOptions.max_pieces = None) --------------
  * qpn_recipes_batch_range: qpn_recipes_batch from a starting recipe per node: node b gets the recipes

@@ -639,6 +639,31 @@ function reduced_pieces(Qd::Array{Float64,3}, R::Array{Float64,3}, qd::Matrix{Fl
 end
 
 """
+    project_pieces(Qd, R, qd, Ad, B, l, u, K, node_of; tol = 1e-9, cap = min(4096, max(256, 4(n + 2m)))) -> (Ar, lr, ur, rows, flags)
+
+`reduced_pieces` for the pieces it flags (`qpn_project_pieces`): after the elimination through a piece's own equality rows, every
+multiplier column that no equality pins takes one Fourier-Motzkin step, in ascending order, all on the device.  `Ar[:, :, t]` is
+the cap x (n + p) row matrix over `[x_d; x_p]` with `cap >= n + 2m` rows of room, of which the first `rows[t]` are live (redundant
+rows are not removed).  `flags[t] == 4`: a step needed more than `cap` rows -- the piece comes back empty (`rows[t] == 0`); call
+again with a larger `cap`.  `flags[t] == 2`: more than `cap` rows were alive before the first step.
+"""
+function project_pieces(Qd::Array{Float64,3}, R::Array{Float64,3}, qd::Matrix{Float64}, Ad::Array{Float64,3}, B::Array{Float64,3},
+                        l::Matrix{Float64}, u::Matrix{Float64}, K::Matrix{UInt8}, node_of::Vector{Int32}; tol::Float64 = 1e-9,
+                        cap::Integer = min(4096, max(256, 4 * (size(qd, 1) + 2 * size(l, 1)))))
+    n, nodes = size(qd); m = size(l, 1); p = size(R, 2); pieces = size(K, 2)
+    cap >= n + 2m || error("project_pieces: cap < n + 2m")
+    Ar = zeros(cap, n + p, pieces); lr = zeros(cap, pieces); ur = zeros(cap, pieces)
+    rows = zeros(Int32, pieces); flags = zeros(Int32, pieces)
+    rc = ccall((:qpn_project_pieces, LIB), Cint,
+               (Ptr{Cvoid}, Int32, Int32, Int32, Int32, Int32, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                Ptr{Cdouble}, Ptr{Int32}, Ptr{UInt8}, Cdouble, Int32, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int32}, Ptr{Int32}, Cint),
+               ctx(), Int32(pieces), Int32(nodes), Int32(n), Int32(m), Int32(p), Qd, R, qd, Ad, B, l, u, node_of, K, tol, Int32(cap), Ar, lr, ur,
+               rows, flags, QPN_MEM_HOST)
+    rc == 0 || error("qpn_project_pieces failed ($rc)")
+    (Ar, lr, ur, rows, flags)
+end
+
+"""
     order_nodes_by_pivots!(pivots)
 
 Schedule hint for later `solve_nodes!` calls over the same nodes (longest solves first); `pivots` is the

@@ -21,7 +21,7 @@ ABI_SYMBOLS = (
     "qpn_sweep_status", "qpn_ctx_set_auto_schedule", "qpn_ctx_set_option",
     "qpn_nodes_upload", "qpn_nodes_update", "qpn_nodes_set_schedule", "qpn_nodes_free", "qpn_nodes_info", "qpn_solve_nodes_h",
     "qpn_verify_nodes_h", "qpn_pool_size", "qpn_assemble_pools", "qpn_local_pieces", "qpn_recipes_from_masks",
-    "qpn_recipes_batch", "qpn_reduced_pieces", "qpn_convexity_nodes", "qpn_recipes_batch_range", "qpn_finish_pieces",
+    "qpn_recipes_batch", "qpn_reduced_pieces", "qpn_project_pieces", "qpn_convexity_nodes", "qpn_recipes_batch_range", "qpn_finish_pieces",
     "qpn_multiplier_vertices", "qpn_recipe_filter",
     "qpn_assemble_interior_nodes", "qpn_interior_members", "qpn_members_outside",
     "qpn_lp_default_opts", "qpn_lp_kernel_class", "qpn_solve_lps", "qpn_issubset_pairs", "qpn_implicit_bounds",
@@ -148,6 +148,8 @@ def load_library():
     lib.qpn_recipes_batch.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, vp, vp, C.c_int]
     lib.qpn_reduced_pieces.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                        C.c_double, vp, vp, vp, vp, vp, C.c_int]
+    lib.qpn_project_pieces.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                       C.c_double, C.c_int32, vp, vp, vp, vp, vp, C.c_int]
     lib.qpn_recipes_batch_range.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, C.c_int]
     lib.qpn_finish_pieces.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                       C.c_double, vp, vp, vp, vp, vp, C.c_int32, vp, vp, vp, vp, C.POINTER(C.c_int32), C.c_int]

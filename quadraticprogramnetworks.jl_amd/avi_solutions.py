@@ -71,14 +71,11 @@ def all_Ks(mask, engine=None, limit=4096):
     return eng.recipes_from_masks(np.asarray(mask, dtype=np.uint8), 0, min(total, limit))
 
 
-def eliminate_multipliers(P: Poly, n: int, m: int, tol=1e-9, max_rows=4096) -> Poly:
-    """A local piece over [x_d (n); lambda (m); x_p] brought down to [x_d; x_p]: the multipliers are eliminated through
-    the piece's OWN equality rows (stationarity rows of free x_d, lambda_j = 0 of inactive rows, constraint rows of active
-    ones) -- the substitution x2 = Ae_elim^+ (rhs - Ae_keep x1) of eliminate_variables, src/sets.jl:731-800, one column at a
-    time with partial pivoting -- and, for a multiplier no equality pins (degenerate active sets), by one Fourier-Motzkin
-    step.  The path's counterpart of project_and_permute (src/avi_solutions.jl:79-91), which the reference does by vertex
-    enumeration (CDD: out of scope)."""
-    A, l, u = (np.array(a, dtype=np.float64) for a in P.vectorize())
+def pin_multipliers(A, l, u, n: int, m: int, tol=1e-9):
+    """The first half of project_rows: every multiplier column eliminated through the alive equality row with the largest entry
+    (the first of equal ones; that row then leaves).  -> (A, l, u of the rows still alive, in order; left: the columns that no
+    equality pins while an alive row holds them above tol, ascending)."""
+    A, l, u = (np.array(a, dtype=np.float64) for a in (A, l, u))
     alive = np.ones(A.shape[0], bool)
     left = []
     for j in range(n, n + m):
@@ -96,7 +93,12 @@ def eliminate_multipliers(P: Poly, n: int, m: int, tol=1e-9, max_rows=4096) -> P
             A[k] -= f * A[i]; A[k, j] = 0.0
             l[k] -= f * l[i]; u[k] -= f * u[i]          # (row i is an equality: both bounds move by f b)
         alive[i] = False
-    A, l, u = A[alive], l[alive], u[alive]
+    return A[alive], l[alive], u[alive], left
+
+
+def fourier_motzkin(A, l, u, left, tol=1e-9, max_rows=4096):
+    """The second half of project_rows: one Fourier-Motzkin step per column of `left`, in the order given.  -> (A, l, u), or None
+    when a step would make more than max_rows rows (counted before anything is made)."""
     for j in left:
         # Fourier-Motzkin on column j: rows as one-sided inequalities a.y <= b
         zero = np.abs(A[:, j]) <= tol
@@ -108,13 +110,38 @@ def eliminate_multipliers(P: Poly, n: int, m: int, tol=1e-9, max_rows=4096) -> P
                     continue
                 (ub if a_[j] > 0 else lb).append((a_ / abs(a_[j]), b_ / abs(a_[j])))
         if len(ub) * len(lb) + Az.shape[0] > max_rows:
-            raise RuntimeError("eliminate_multipliers: the piece needs a polyhedral projection (too many rows)")
+            return None
         rows = [(au + al, bu + bl) for au, bu in ub for al, bl in lb]
         A = np.vstack([Az] + [r[0][None] for r in rows]) if rows else Az
         l = np.concatenate([lz, np.full(len(rows), -INF)]); u = np.concatenate([uz, np.array([r[1] for r in rows])])
         A[:, j] = 0.0
+    return A, l, u
+
+
+def project_rows(A, l, u, n: int, m: int, tol=1e-9, max_rows=4096):
+    """The array core of eliminate_multipliers: rows l <= A y <= u over [x_d (n); lambda (m); x_p] -> the raw rows (A, l, u) over
+    [x_d; x_p], nothing normalised -- or None when a Fourier-Motzkin step would make more than max_rows rows.  The arithmetic
+    contract of qpn_project_pieces (csrc/qpn_project.hip does the same operations in the same order, bit for bit)."""
+    A, l, u, left = pin_multipliers(A, l, u, n, m, tol)
+    out = fourier_motzkin(A, l, u, left, tol, max_rows)
+    if out is None:
+        return None
+    A, l, u = out
     keep_cols = [c for c in range(A.shape[1]) if c < n or c >= n + m]
-    return Poly(A[:, keep_cols], l, u)
+    return A[:, keep_cols], l, u
+
+
+def eliminate_multipliers(P: Poly, n: int, m: int, tol=1e-9, max_rows=4096) -> Poly:
+    """A local piece over [x_d (n); lambda (m); x_p] brought down to [x_d; x_p]: the multipliers are eliminated through
+    the piece's OWN equality rows (stationarity rows of free x_d, lambda_j = 0 of inactive rows, constraint rows of active
+    ones) -- the substitution x2 = Ae_elim^+ (rhs - Ae_keep x1) of eliminate_variables, src/sets.jl:731-800, one column at a
+    time with partial pivoting -- and, for a multiplier no equality pins (degenerate active sets), by one Fourier-Motzkin
+    step.  The path's counterpart of project_and_permute (src/avi_solutions.jl:79-91), which the reference does by vertex
+    enumeration (CDD: out of scope).  The arithmetic is project_rows'; the result is a normalised Poly."""
+    out = project_rows(*P.vectorize(), n, m, tol=tol, max_rows=max_rows)
+    if out is None:
+        raise RuntimeError("eliminate_multipliers: the piece needs a polyhedral projection (too many rows)")
+    return Poly(*out)
 
 
 def solution_graph_pieces(Q, q, A, l, u, dec_inds, x, lam, engine=None, tol=1e-2, max_pieces=64):

@@ -617,6 +617,58 @@ int qpn_reduced_pieces(qpn_ctx *ctx, int32_t pieces, int32_t nodes, int32_t n, i
     return st.finish();
 }
 
+int qpn_project_pieces(qpn_ctx *ctx, int32_t pieces, int32_t nodes, int32_t n, int32_t m, int32_t p, const double *Qd,
+                       const double *R, const double *qd, const double *Ad, const double *B, const double *l,
+                       const double *u, const int32_t *node_of, const uint8_t *K, double tol, int32_t cap, double *Ar, double *lr,
+                       double *ur, int32_t *rows, int32_t *flags, int mem)
+{
+    if (!ctx) return QPN_ERR_ARG;
+    Stage st(ctx, mem, "qpn_project_pieces");
+    if (int rc = pieces_check(ctx, st.who, st.host, pieces, nodes, n, m, p, Qd, R, qd, Ad, B, l, u, node_of, K, Ar && lr && ur && rows && flags))
+        return rc;
+    if ((int64_t)cap < (int64_t)n + 2 * (int64_t)m) return fail_arg(ctx, "qpn_project_pieces: cap < n + 2m");
+    if (pieces == 0) return QPN_OK;
+    if (int rc = st.check()) return rc;
+    if (!(tol >= 0.0)) return fail_arg(ctx, "qpn_project_pieces: bad tolerance");
+    if (qpn_project_pieces_lds(n, m, p) > (size_t)kProjectLdsMax) { ctx->last_error = "qpn_project_pieces: too many parameters for one workgroup's LDS"; return QPN_ERR_SIZE; }
+    const int N = n + m;
+    const size_t rws = 2 * (size_t)N, cols = (size_t)N + p, capz = (size_t)cap, oc = (size_t)n + p;
+    // one piece's share of the workspace: its local piece and the scratch of the Fourier-Motzkin steps (the first test keeps the
+    // products below inside size_t)
+    const size_t slack = 16 * 256;                                   // the slots' alignment
+    size_t per = 0;
+    if (capz <= kProjectWsBytes / (16 * cols)) per = rws * cols * 8 + 2 * rws * 8 + rws + qpn_project_pieces_scratch(n, m, p, cap);
+    if (per == 0 || per > kProjectWsBytes - slack) {
+        ctx->last_error = "qpn_project_pieces: cap rows of one piece do not fit the workspace";
+        return QPN_ERR_SIZE;
+    }
+    const size_t chunk = std::min((size_t)pieces, (kProjectWsBytes - slack) / per);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    NodeDev d{};
+    const int32_t *dno; const uint8_t *dK;
+    double *dAp, *dlp, *dup, *dbuf, *dbnd, *dAr, *dlr, *dur; uint8_t *dkeep; int32_t *dlists, *drows, *dflags;
+    st.scratch(dAp, chunk * rws * cols * 8); st.scratch(dlp, chunk * rws * 8); st.scratch(dup, chunk * rws * 8); st.scratch(dkeep, chunk * rws);
+    st.scratch(dbuf, chunk * 2 * capz * cols * 8); st.scratch(dbnd, chunk * 4 * capz * 8); st.scratch(dlists, chunk * 5 * capz * 4);
+    stage_records(st, d, node_sizes(nodes, n, m, p, 0), Qd, R, qd, Ad, B, l, u);
+    st.in(dno, node_of, (size_t)pieces * 4); st.in(dK, K, (size_t)pieces * N);
+    st.out(dAr, Ar, (size_t)pieces * oc * capz * 8); st.out(dlr, lr, (size_t)pieces * capz * 8); st.out(dur, ur, (size_t)pieces * capz * 8);
+    st.out(drows, rows, (size_t)pieces * 4); st.out(dflags, flags, (size_t)pieces * 4);
+    int rc = st.begin();
+    if (rc != QPN_OK) return rc;
+    for (size_t t0 = 0; t0 < (size_t)pieces; t0 += chunk) {
+        const int32_t cnt = (int32_t)std::min(chunk, (size_t)pieces - t0);
+        // without node_of piece t reads record t: a chunk's records start at its first piece
+        const size_t b0 = dno ? 0 : t0;
+        HIPCHK(ctx, qpn_launch_local_pieces(cnt, nodes - (int32_t)b0, n, m, p, d.Q + b0 * n * n, d.R + b0 * n * p, d.q + b0 * n, d.A + b0 * m * n,
+                                            d.B + b0 * m * p, d.l + b0 * m, d.u + b0 * m, dno ? dno + t0 : nullptr, dK + t0 * N, dAp, dlp, dup,
+                                            dkeep, s));
+        HIPCHK(ctx, qpn_launch_project_pieces(cnt, n, m, p, tol, cap, dAp, dlp, dup, dkeep, dbuf, dbnd, dlists, dAr + t0 * oc * capz,
+                                              dlr + t0 * capz, dur + t0 * capz, drows + t0, dflags + t0, s));
+    }
+    return st.finish();
+}
+
 int qpn_recipes_batch_range(qpn_ctx *ctx, int32_t nodes, int32_t N, const uint8_t *masks, const int64_t *first, const int64_t *offsets,
                             uint8_t *K, int32_t *node_of, int mem)
 {

@@ -259,6 +259,16 @@ hipError_t qpn_launch_finish_store(int32_t stored, const int32_t *src, int32_t o
 hipError_t qpn_launch_reduce_pieces(int32_t pieces, int32_t n, int32_t m, int32_t p, double tol, double *Ap, const double *lp,
                                     const double *up, const uint8_t *keep, double *Ar, double *lr, double *ur, int32_t *rows_out,
                                     int32_t *flags_out, hipStream_t stream);
+// qpn_project.hip: the pieces reduce_pieces_kernel would flag, projected by Fourier-Motzkin steps (qpn_project_pieces).  buf, bnd, lists:
+// qpn_project_pieces_scratch bytes per piece (2 cap cols doubles, 4 cap doubles, 5 cap ints).  A call is split into chunks of
+// pieces whose local pieces and scratch fit kProjectWsBytes of the context's workspace.
+constexpr int kProjectLdsMax = 64 * 1024;
+constexpr size_t kProjectWsBytes = (size_t)512 << 20;
+size_t qpn_project_pieces_lds(int32_t n, int32_t m, int32_t p);
+size_t qpn_project_pieces_scratch(int32_t n, int32_t m, int32_t p, int32_t cap);
+hipError_t qpn_launch_project_pieces(int32_t pieces, int32_t n, int32_t m, int32_t p, double tol, int32_t cap, double *Ap, const double *lp,
+                                     const double *up, const uint8_t *keep, double *buf, double *bnd, int32_t *lists, double *Ar,
+                                     double *lr, double *ur, int32_t *rows_out, int32_t *flags_out, hipStream_t stream);
 // pool assembly (combine_gavis): all pointers device
 struct QpnPoolLaunch {
     int32_t batch, form, nd, sn, sm, p;

@@ -10,7 +10,7 @@
 //                          the alive equality row with the largest entry first -- which is what project_and_permute
 //                          (src/avi_solutions.jl:79-91) comes to when the active rows pin the multipliers.  A column that no
 //                          equality pins while an alive row still holds it (a degenerate active set: Fourier-Motzkin, polyhedral)
-//                          raises the piece's flag and is left to the host.
+//                          raises the piece's flag; qpn_project_pieces (qpn_project.hip) takes such pieces, on the device.
 //
 // Arithmetic contract (the host restatement and the tests' CPU twin do the same operations in the same order, fp contraction
 // off): f = A[k][j] / A[i][j];  A[k][c] = A[k][c] - f * A[i][c] (c != j), A[k][j] = 0;  l[k] = l[k] - f * l[i], u likewise.

@@ -389,6 +389,34 @@ class Engine:
                    _ptr(node_of), _ptr(K), float(tol), _ptr(Ar), _ptr(lr), _ptr(ur), _ptr(rows), _ptr(flags), self._mem(dev))
         return Ar, lr, ur, rows, flags
 
+    def project_pieces(self, Qc, Rc, qd, Ac, Bc, l, u, K, node_of=None, tol=1e-9, cap=None):
+        """reduced_pieces for the pieces it flags with bit 0 (qpn_project_pieces; level_batch.project_pieces_host is its numpy
+        twin): the multipliers eliminated through each piece's own equality rows, then one Fourier-Motzkin step per column that
+        no equality pins, all of them in this one call.  cap >= n + 2m: the rows of room per piece (default
+        level_batch.project_cap(n, m)).  Returns (Ar [pieces, n+p, cap] column-major per piece, lr, ur [pieces, cap], rows, flags
+        [pieces]); flags: 2 = more than cap rows alive before the first step, 4 = a step needed more than cap rows (the piece is
+        all fill, rows 0)."""
+        dev, Qc, Rc, qd, Ac, Bc, l, u, K, node_of = self._stage("project_pieces", "Qc Rc qd Ac Bc l u K node_of",
+                                                                f64=(Qc, Rc, qd, Ac, Bc, l, u), u8=(K,), i32=(node_of,))
+        nodes, n = qd.shape
+        m = l.shape[1]
+        p = Rc.shape[1]
+        pieces = int(K.shape[0])
+        if cap is None:
+            from .level_batch import project_cap
+            cap = project_cap(n, m)
+        cap = int(cap)
+        if cap < n + 2 * m:
+            raise QpnError("project_pieces: cap < n + 2m")
+        Ar = self._alloc(dev, (pieces, n + p, cap), np.float64)
+        lr = self._alloc(dev, (pieces, cap), np.float64)
+        ur = self._alloc(dev, (pieces, cap), np.float64)
+        rows = self._alloc(dev, (pieces,), np.int32)
+        flags = self._alloc(dev, (pieces,), np.int32)
+        self._call("qpn_project_pieces", pieces, nodes, n, m, p, _ptr(Qc), _ptr(Rc), _ptr(qd), _ptr(Ac), _ptr(Bc), _ptr(l), _ptr(u),
+                   _ptr(node_of), _ptr(K), float(tol), cap, _ptr(Ar), _ptr(lr), _ptr(ur), _ptr(rows), _ptr(flags), self._mem(dev))
+        return Ar, lr, ur, rows, flags
+
     # -- (A6) pool assembly ----------------------------------------------------------------------
     def assemble_pools(self, n_i, m_i, dpos, nd, Qd, Qp, qd, Ad, Bp, l, u, w, form="reduced", share_M=None):
         """combine_gavis (src/avi.jl:305-377) for `batch` instances of one pool shape, on the device.

@@ -1021,7 +1021,7 @@ def _record_spans(rec_of):
     return zip(ks.tolist(), starts.tolist(), starts.tolist()[1:] + [len(rec_of)])
 
 
-def _read_lean(eng, b, K, rec_of, colsel, x, member_tol):
+def _read_lean(eng, b, K, rec_of, colsel, x, member_tol, projected):
     """A round read on the host, the capped route's reader: reduced_pieces, then _finish_host record by record -- no hashes, no
     store, and one record's finished rows alive at a time.  Yields per record (k, first piece t0, status and worst of its
     pieces as lists, piece, spare).  Status as qpn_finish_pieces writes it: 1 member, 2 merge candidate, 8 flagged.  piece(t)
@@ -1030,7 +1030,9 @@ def _read_lean(eng, b, K, rec_of, colsel, x, member_tol):
     (The status, worst and row counts are Python lists and the records come one by one on purpose: the default path has about
     one piece per record, so its cost is what is done per record, and a record's rows are megabytes at n = m = 32.)"""
     from .avi_solutions import _probe_vector
-    Ar, lr, ur, rows, flags = (np.asarray(a) for a in eng.reduced_pieces(b.Qc, b.Rc, b.qd, b.Ac, b.Bc, b.l, b.u, np.asarray(K), rec_of))
+    recd, K = (b.Qc, b.Rc, b.qd, b.Ac, b.Bc, b.l, b.u), np.asarray(K)
+    Ar, lr, ur, rows, flags = (np.asarray(a) for a in eng.reduced_pieces(*recd, K, rec_of))
+    projected.update(_project_flagged(eng, recd, K, rec_of, flags, b.n, b.m))
     Rmax, rows_l = Ar.shape[2], rows.tolist()
     for k, t0, t1 in _record_spans(rec_of):
         cols_k, take_k = colsel[k]
@@ -1056,7 +1058,7 @@ def _read_lean(eng, b, K, rec_of, colsel, x, member_tol):
         yield k, t0, st, worst, piece, spare
 
 
-def _read_store(eng, finish, b, recd, fin_in, K, rec_of, colsel, x, member_tol, up, down):
+def _read_store(eng, finish, b, recd, fin_in, K, rec_of, colsel, x, member_tol, up, down, projected):
     """A round read through the ABI's store, the uncapped route's reader: reduced_pieces, then `finish` where the arrays live
     (the engine's finish_pieces on the device, whence only the store and the per-piece words come back; finish_pieces_host,
     the kernel's twin, on the host).  Status bit 4: a member equal to an earlier one of the round.  Yields what _read_lean
@@ -1067,6 +1069,7 @@ def _read_store(eng, finish, b, recd, fin_in, K, rec_of, colsel, x, member_tol, 
     red = eng.reduced_pieces(*recd, K, rec_h)
     fin = finish(*red, rec_h, *fin_in, b.n, b.m, member_tol=member_tol)
     st, worst, store_of, As, ls, us, rows_s = (down(fin[key]) for key in ("status", "worst", "store_of", "As", "ls", "us", "rows_s"))
+    projected.update(_project_flagged(eng, recd, K, rec_h, st & 8, b.n, b.m, down))       # (status bit 8: flagged)
     rec_l, store_of, rows_s, merged = rec_of.tolist(), store_of.tolist(), rows_s.tolist(), (st & 2).tolist()
 
     def piece(t):
@@ -1105,7 +1108,9 @@ def solution_pieces(qpn, recs, batches, rets, x, engine, want: Sequence[bool], t
 
     One pipeline serves every mode: _recipe_rounds is the source of recipes, a round is read by _read_lean (a cap) or
     _read_store (None), and its pieces are admitted below, in recipe order.  The modes differ in the windows' layout and in the
-    reader, nowhere else."""
+    reader, nowhere else.  The pieces of a round that the device elimination flags (degenerate active sets) are projected in one
+    project_pieces call by the round's reader when the engine has that method (_project_flagged), piece by piece on the host
+    otherwise (_reduce_on_host); the pieces are the same either way."""
     from .avi_solutions import _dedupe, _probe_vector
     eng = engine
     x = np.asarray(x, dtype=np.float64)
@@ -1163,10 +1168,12 @@ def solution_pieces(qpn, recs, batches, rets, x, engine, want: Sequence[bool], t
                                                          # graph is never empty, src/qp_processing.jl:233)
         for K, row_of in _recipe_rounds(eng, vm, vt, vf, max_pieces, chunk, exploration_vertices >= 2, up, down):
             rec_of = vsel[row_of].astype(np.int32)       # recipe -> record inside the batch (records ascend)
+            projected = {}                               # flagged piece -> its projected rows: filled by the reader, in one call
+                                                         # per round, before it yields the first record
             if max_pieces is None:
-                records = _read_store(eng, finish, b, recd, fin_in, K, rec_of, colsel, x, member_tol, up, down)
+                records = _read_store(eng, finish, b, recd, fin_in, K, rec_of, colsel, x, member_tol, up, down, projected)
             else:
-                records = _read_lean(eng, b, K, rec_of, colsel, x, member_tol)
+                records = _read_lean(eng, b, K, rec_of, colsel, x, member_tol, projected)
             for k, t0, st, worst, piece, spare in records:
                 i = b.where[k]
                 cols_k, take_k = colsel[k]
@@ -1174,8 +1181,9 @@ def solution_pieces(qpn, recs, batches, rets, x, engine, want: Sequence[bool], t
                 for t, (s_, miss) in enumerate(zip(st, worst), t0):     # (the miss is the finished rows', taken before _dedupe)
                     if s_ & 4:                           # an equal earlier piece of this round is in the set already
                         continue
-                    if s_ & 8:                           # flagged by the device elimination: the host restatement
-                        Pg, miss = _flagged_piece(qpn, b, k, down(K[t]), eng, cols_k, take_k, x)
+                    if s_ & 8:                           # flagged by the device elimination: its projected rows, or the host restatement
+                        raw = projected.get(t)
+                        Pg, miss = _flagged_piece(qpn, b, k, down(K[t]) if raw is None else None, eng, cols_k, take_k, x, raw)
                         if Pg is None:
                             continue
                         member, key = miss <= member_tol, None
@@ -1200,16 +1208,81 @@ def solution_pieces(qpn, recs, batches, rets, x, engine, want: Sequence[bool], t
     return out
 
 
+# rows of room per piece in the batched projection of a round's flagged pieces (Engine.project_pieces): PROJECT_CAP_FACTOR times
+# the n + 2m rows a piece starts with, inside [PROJECT_CAP_MIN, PROJECT_CAP_MAX].  Any value keeps the results: a piece that needs
+# more comes back with flag 4 and takes the per-piece route (_reduce_on_host), whose own limit is PROJECT_CAP_MAX rows.
+PROJECT_CAP_MIN, PROJECT_CAP_FACTOR, PROJECT_CAP_MAX = 256, 4, 4096
+
+
+def project_cap(n, m):
+    return max(n + 2 * m, min(PROJECT_CAP_MAX, max(PROJECT_CAP_MIN, PROJECT_CAP_FACTOR * (n + 2 * m))))
+
+
+def project_pieces_host(Ap, lp, up, keep, n, m, tol=1e-9, cap=None):
+    """The numpy twin of qpn_project_pieces from the lifted pieces on (local_pieces' output: Ap [pieces, N+p, 2N] column-major
+    per piece, lp, up, keep [pieces, 2N]): the multipliers eliminated through each piece's equality rows, then one
+    Fourier-Motzkin step per column that no equality pins (avi_solutions.project_rows, the entry's arithmetic contract).
+    Returns (Ar [pieces, n+p, cap] column-major per piece, lr, ur [pieces, cap], rows, flags [pieces]) with the entry's fill
+    (0, -inf, +inf beyond rows[t]) and flags: 2 = more than cap rows alive after the equalities (the first cap go out, no
+    Fourier-Motzkin step), 4 = a step needed more than cap rows (all fill, rows 0).  cap >= n + 2m; default project_cap(n, m)."""
+    from .avi_solutions import fourier_motzkin, pin_multipliers
+    Ap, lp, up, keep = np.asarray(Ap, dtype=np.float64), np.asarray(lp, dtype=np.float64), np.asarray(up, dtype=np.float64), np.asarray(keep)
+    n, m = int(n), int(m)
+    cap = project_cap(n, m) if cap is None else int(cap)
+    if cap < n + 2 * m:
+        raise ValueError("project_pieces_host: cap < n + 2m")
+    pieces, cols = Ap.shape[0], Ap.shape[1]
+    ycols = [c for c in range(cols) if c < n or c >= n + m]
+    Ar = np.zeros((pieces, len(ycols), cap)); lr = np.full((pieces, cap), -INF); ur = np.full((pieces, cap), INF)
+    rows = np.zeros(pieces, np.int32); flags = np.zeros(pieces, np.int32)
+    for t in range(pieces):
+        kept = keep[t].astype(bool)
+        A, l, u, left = pin_multipliers(Ap[t].T[kept], lp[t][kept], up[t][kept], n, m, tol)
+        if A.shape[0] > cap:
+            flags[t] = 2
+            A, l, u = A[:cap], l[:cap], u[:cap]
+        else:
+            out = fourier_motzkin(A, l, u, left, tol, cap)
+            if out is None:
+                flags[t] = 4
+                continue
+            A, l, u = out
+        r = A.shape[0]
+        Ar[t, :, :r] = A[:, ycols].T; lr[t, :r] = l; ur[t, :r] = u; rows[t] = r
+    return Ar, lr, ur, rows, flags
+
+
 def _poly_key(Pg):
     """The key of a piece in its node's piece set: columns, rows rounded to 6 digits (no negative zeros), bounds rounded."""
     cl, Al_ = Pg.local()
     return (cl.tobytes(), (np.round(Al_, 6) + 0.0).tobytes(), np.round(np.concatenate([Pg.l, Pg.u]), 6).tobytes())
 
 
-def _flagged_piece(qpn, b, k, Krow, eng, cols_k, take_k, x):
-    """A piece the device elimination flagged, through the host restatement, normalised and merged; (Poly, miss) or (None, None)."""
+def _project_flagged(eng, recd, K, rec_of, flags, n, m, down=np.asarray):
+    """The flagged pieces of a round through the engine's project_pieces, ALL IN ONE CALL (qpn_project_pieces: the equality
+    elimination again and the Fourier-Motzkin steps, on the device).  recd, K, rec_of: what the round's reduced_pieces call took
+    (host arrays or device tensors); flags: nonzero for its flagged pieces, on the host.  -> {piece: the raw rows (A, l, u) over [x_d; x_p]}; a piece that does not
+    fit project_cap rows is left out and takes the per-piece route.  {} for an engine without the method."""
+    project = getattr(eng, "project_pieces", None)
+    if not callable(project):
+        return {}
+    idx = np.nonzero(flags)[0]
+    if not idx.size:
+        return {}
+    sel = idx
+    if not isinstance(K, np.ndarray):
+        import torch
+        sel = torch.as_tensor(idx, device=K.device)
+    Ar, lr, ur, rows, fl = (down(a) for a in project(*recd, K[sel], rec_of[sel], cap=project_cap(n, m)))
+    return {t: (np.ascontiguousarray(Ar[i, :, :rows[i]].T), lr[i, :rows[i]].copy(), ur[i, :rows[i]].copy())
+            for i, t in enumerate(idx.tolist()) if fl[i] == 0}
+
+
+def _flagged_piece(qpn, b, k, Krow, eng, cols_k, take_k, x, raw=None):
+    """A piece the device elimination flagged, normalised and merged; (Poly, miss) or (None, None).  raw: its projected rows from
+    the round's project_pieces call (_project_flagged); without them, the host restatement piece by piece."""
     from .avi_solutions import _dedupe
-    P = _reduce_on_host(b, k, Krow, eng)
+    P = Poly(*raw).vectorize() if raw is not None else _reduce_on_host(b, k, Krow, eng)
     if P is None:
         return None, None
     Ah = np.ascontiguousarray(P[0][:, take_k]); big = np.max(np.abs(Ah), axis=1, initial=0.0)
