@@ -861,7 +861,7 @@ stage_a_done: __attribute__((unused));
     auto lo0_of = [&](int k) -> double { if constexpr (CRASH >= 2) return udbl(sbuf[128 + k]); else return readlane_f64(lo0, k); };
     auto hi0_of = [&](int k) -> double { if constexpr (CRASH >= 2) return udbl(sbuf[160 + k]); else return readlane_f64(hi0, k); };
     auto rng_of = [&](int k) -> double {
-        if constexpr (CRASH >= 2) return udbl(sbuf[160 + k]) - udbl(sbuf[128 + k]); else return readlane_f64(rngv, k);
+        if constexpr (CRASH >= 2) return udbl(udbl(sbuf[160 + k]) - udbl(sbuf[128 + k])); else return readlane_f64(rngv, k);      // (fp64 subtraction is VALU: back to SGPRs)
     };
 
     // the dictionary as two 8-vectors per lane: element 4 Ib + g of SJ<Jb> = row 16 Ib + 4 g + lq, column
@@ -882,7 +882,22 @@ stage_a_done: __attribute__((unused));
     unsigned long long sgn = 1ull << 63;
     auto sigma_times = [&](double x) -> double { return __hiloint2double(__double2hiint(x) ^ (int)(sgn >> 32), __double2loint(x)); };
     auto sigma_times_uni = [&](double x) -> double { double r_; asm("s_xor_b64 %0, %1, %2" : "=s"(r_) : "s"(x), "s"(sgn) : "scc"); return r_; };
-    double self_lim = 0.0, elo = 0.0, ehi = QINF;
+    // Wave-uniform state stays in SGPRs from its definition to its scalar use, across the loop's joins and its back edge
+    // (the listing of the loop showed 22 v_readfirstlane and 27 v_mov_b64 that only carried such values through VGPRs):
+    //  * fp64 values that are carried or joined -- the entering variable's own travel limit self_lim, the bounds elo / ehi it
+    //    will have as a basic variable, 1 / pivot, the write-back's values -- travel as their 64-bit PATTERN.  The compiler keeps
+    //    an integer pair in SGPRs across a join and moves a double into VGPRs there: the loop is structurized as a whole, the
+    //    undefined inputs the structurizer gives its join phis are vector registers for doubles and scalar ones for integers,
+    //    and one vector input moves the whole web of phis.  The casts at the uses are free;
+    //  * what the loop carries is pinned at the head (keep_scalar, qpn_internal.h) and kept alive behind the loop, so that no
+    //    exit path leaves it undefined;
+    //  * a value computed on the vector unit from scalars (the range u_k - l_k) goes back through v_readfirstlane where it is
+    //    made, once, and the scalar consumers (the first v_min of the ratio test, the write-back and exchange blocks) take their
+    //    operands as they are.
+    constexpr unsigned long long B_ZERO = 0ull, B_PINF = 0x7FF0000000000000ull, B_NINF = 0xFFF0000000000000ull;
+    auto bits_of = [](double x) -> unsigned long long { return (unsigned long long)__double_as_longlong(x); };
+    auto dbl_of = [](unsigned long long b_) -> double { return __longlong_as_double((long long)b_); };
+    unsigned long long self_lim = B_ZERO, elo = B_ZERO, ehi = B_PINF;
     const double slack = 1e-10, ptol = a.piv_tol;
     {
         double viol = 0.0;
@@ -905,7 +920,7 @@ stage_a_done: __attribute__((unused));
                 tcol = cov;
             }
             if (l == XC) nbval = theta0;
-            self_lim = theta0;
+            self_lim = bits_of(udbl(theta0));
             status = QPN_MAX_ITERS;
         }
     }
@@ -913,7 +928,8 @@ stage_a_done: __attribute__((unused));
     // register nor tested at the head)
     if (status == QPN_MAX_ITERS) for (;;) {
         if (pivots >= max_piv) break;
-        c = uni(c);
+        // (no copy of the carried state into a VGPR at the latch and no v_readfirstlane back here)
+        keep_scalar(c); keep_scalar(self_lim); keep_scalar(elo); keep_scalar(ehi); keep_scalar(sgn);
         // ---- entering column -> sucol, permuted so that a lane group reads its 8 rows as 8 consecutive doubles
         // (row r = q + 4 g + 16 Ib sits at q*8 + 4 Ib + g)
         // ONE asm block, like the exchange: the lanes of tile column c & 15 come as a shifted mask (no compare), the tile
@@ -971,36 +987,39 @@ stage_a_done: __attribute__((unused));
         // minimum nor the tie set needs the candidate flag again: the tie set is ONE compare
         const double dd = cnd ? (tb - xb) * rc : QINF;
         const double d1 = fma(slack, arc, dd);
-        const double dmax = wave_min32_with_limit_f64(d1, self_lim);         // wave-uniform (an SGPR pair)
+        const double dmax = wave_min32_with_limit_s_f64(d1, dbl_of(self_lim));         // wave-uniform (an SGPR pair)
         if (uni(__double2hiint(dmax)) == 0x7ff00000) { status = QPN_RAY_TERM; break; }      // +inf: nothing blocks the ray
         const unsigned long long bal = qpn_ballot(dd <= dmax);
         // Both outcomes below end in the SAME exchange block (a bound flip runs it with v = 0 and empty lane
         // masks: a no-op), so the dictionary registers have one definition per iteration.
-        double v0 = 0.0, v1 = 0.0, inv = 0.0;
+        double v0 = 0.0, v1 = 0.0;
+        unsigned long long inv = B_ZERO;               // (1 / pivot, and the write-back's fp64 values below: patterns, as above)
         unsigned long long mcol = 0ull, mrow = 0ull;
         int cx = XC, rsel = 0, cnext = -1;
         // ... and the same single-lane writes of the bookkeeping vectors (a write that does not apply goes to
         // idle lane 63), so those registers are never copied around a branch either
         int rW = 63, veW = 0, cW = 63, vlW = 0, kW = 63, auW = 0;
-        double eloW = 0.0, ehiW = 0.0, nbW = 0.0;
+        unsigned long long eloW = B_ZERO, ehiW = B_ZERO, nbW = B_ZERO;
         bool stop = false;
         if (bal == 0ull) {
             // the entering variable reaches its own opposite bound first: no basis change
-            const double dl = sigma_times(self_lim);
+            const double dl = dbl_of(self_lim ^ sgn);      // sigma * self_lim, on the scalar unit
             if (actb) xb = fma(dl, cm, xb);
             const int ve = readlane_i32(colvar, c);
-            if (ve == VTH) { nbW = 0.0; status = QPN_SUCCESS; stop = true; }
+            if (ve == VTH) { nbW = B_ZERO; status = QPN_SUCCESS; stop = true; }
             else {
                 const int k = ve;
-                const int au = (long long)sgn < 0 ? 0 : 1;
-                nbW = au ? hi0_of(k) : lo0_of(k);
+                int sh = (int)(sgn >> 32); keep_scalar(sh);       // (the sign as a 32-bit scalar compare: there is no 64-bit one)
+                int au = sh < 0 ? 0 : 1;
+                keep_scalar(au);            // (an integer in an SGPR, not a lane mask that a v_cndmask turns into one for the write-back)
+                nbW = bits_of(au ? hi0_of(k) : lo0_of(k));
                 kW = k; auW = au;
                 pivots++;
                 cnext = col_of(NBP + k);
                 if (cnext < 0) { status = QPN_FAILURE; stop = true; }
                 sgn = (unsigned long long)au << 63;
-                self_lim = QINF;
-                if (au) { elo = -QINF; ehi = 0.0; } else { elo = 0.0; ehi = QINF; }
+                self_lim = B_PINF;
+                if (au) { elo = B_NINF; ehi = B_ZERO; } else { elo = B_ZERO; ehi = B_PINF; }
             }
             STAMP(4);
         } else {
@@ -1029,7 +1048,7 @@ stage_a_done: __attribute__((unused));
             if (step < 0.0) step = 0.0;
             const double leave_val = readlane_f64(tb, r);
             const double rcr = readlane_f64(rc, r);
-            inv = sigma_times_uni(rcr);
+            inv = bits_of(rcr) ^ sgn;                  // sigma / pivot
             const double delta = sigma_times_uni(step);
             const int vl = readlane_i32(rowvar, r);
             const double enter_val = readlane_f64(nbval, c) + delta;
@@ -1037,10 +1056,11 @@ stage_a_done: __attribute__((unused));
             {
                 double pa = svrow[lc], pb = svrow[16 + lc], px = svrow[XC];
                 asm volatile("" : "+v"(pa), "+v"(pb), "+v"(px));
-                v0 = pa * inv; v1 = pb * inv;
+                const double invd = dbl_of(inv);
+                v0 = pa * invd; v1 = pb * invd;
                 // extra column and values (lane l <-> row l): the same exchange formulas, the pivot column's own
                 // entries start from 0 when it is the extra column
-                const double vx = px * inv;
+                const double vx = px * invd;
                 const double tc0 = (c == XC) ? 0.0 : tcol;
                 double xbn = fma(delta, cm, xb);
                 double tcn = fma(-cm, vx, tc0);
@@ -1052,7 +1072,7 @@ stage_a_done: __attribute__((unused));
             }
             STAMP(3);   // pivot row through LDS
             rW = r; veW = readlane_i32(colvar, c); eloW = elo; ehiW = ehi;      // row r now holds the entering variable
-            cW = c; vlW = vl; nbW = leave_val;                                  // column c the leaving one
+            cW = c; vlW = vl; nbW = bits_of(leave_val);                                 // column c the leaving one
             pivots++;
             if (vl == VTH) { status = QPN_SUCCESS; stop = true; }
             else {
@@ -1064,19 +1084,20 @@ stage_a_done: __attribute__((unused));
                 if (vl < NBP) {
                     // the bounded variable p_k left at a bound -- the upper one iff row r was a `hi` ratio --:
                     // its multiplier d_k enters from 0
-                    au = uni(__double2hiint(rcr)) >= 0 ? 1 : 0; kW = k; auW = au;      // (sign bit of the pivot, |pivot| > ptol: gdir_r > 0 <=> left at hi)
+                    int ph = __double2hiint(rcr); keep_scalar(ph);
+                    au = ph >= 0 ? 1 : 0; keep_scalar(au); kW = k; auW = au;      // (sign bit of the pivot, |pivot| > ptol: gdir_r > 0 <=> left at hi)
                     vn = NBP + k;
                     sgn = (unsigned long long)au << 63;
-                    self_lim = QINF;
-                    if (cls == 2) { elo = 0.0; ehi = 0.0; }
-                    else if (au) { elo = -QINF; ehi = 0.0; }
-                    else { elo = 0.0; ehi = QINF; }
+                    self_lim = B_PINF;
+                    if (cls == 2) { elo = B_ZERO; ehi = B_ZERO; }
+                    else if (au) { elo = B_NINF; ehi = B_ZERO; }
+                    else { elo = B_ZERO; ehi = B_PINF; }
                 } else {
                     // the multiplier d_k left at 0: p_k enters, moving off the bound it rests at
                     vn = k;
                     sgn = cls == 2 ? 0ull : (unsigned long long)au << 63;
-                    self_lim = rng_of(k);           // +inf for a free pair
-                    elo = lo0_of(k); ehi = hi0_of(k);
+                    self_lim = bits_of(rng_of(k));           // +inf for a free pair
+                    elo = bits_of(lo0_of(k)); ehi = bits_of(hi0_of(k));
                 }
             }
             // (colvar still holds the entering id veW at column c here -- the write-back is below --, so that
@@ -1095,11 +1116,12 @@ stage_a_done: __attribute__((unused));
         // saved and restored once instead of six times, and the four lane selects follow each other without the
         // compiler's copies in between: ~20 instructions less on the pivot's dependent chain)
         {
-            const int s_rW = uni(rW), s_cW = uni(cW), s_cc = uni(c), s_kW = uni(kW);
-            const int s_ve = uni(veW), s_vl = uni(vlW), s_au = uni(auW);
-            const int s_el = uni(__double2loint(eloW)), s_eh = uni(__double2hiint(eloW));
-            const int s_fl = uni(__double2loint(ehiW)), s_fh = uni(__double2hiint(ehiW));
-            const int s_nl = uni(__double2loint(nbW)), s_nh = uni(__double2hiint(nbW));
+            // (every operand is a scalar register already: no v_readfirstlane)
+            const int s_rW = rW, s_cW = cW, s_cc = c, s_kW = kW;
+            const int s_ve = veW, s_vl = vlW, s_au = auW;
+            const int s_el = (int)eloW, s_eh = (int)(eloW >> 32);
+            const int s_fl = (int)ehiW, s_fh = (int)(ehiW >> 32);
+            const int s_nl = (int)nbW, s_nh = (int)(nbW >> 32);
             int lol = __double2loint(lo), loh = __double2hiint(lo), hil = __double2loint(hi), hih = __double2hiint(hi);
             int nbl = __double2loint(nbval), nbh = __double2hiint(nbval);
             int m0save;
@@ -1126,8 +1148,7 @@ stage_a_done: __attribute__((unused));
         {
             // (row r becomes -v: a multiplication by -1.0 inside the block, exact, instead of two negated copies kept ready;
             //  1 / pivot goes in as the scalar it is)
-            const double inv_s = udbl(inv);
-            cx = uni(cx); rsel = uni(rsel);
+            const double inv_s = dbl_of(inv);
             if constexpr (HALF16) {
                 // n = m = 16: pairs 16.. are padding -- the other three tiles stay zero (u = 0 in rows 16.., v = 0 in columns 16..)
                 asm volatile(
@@ -1209,6 +1230,7 @@ stage_a_done: __attribute__((unused));
         wave_sync();
         STAMP(3);
     }
+    asm volatile("" :: "s"(c), "s"(self_lim), "s"(elo), "s"(ehi), "s"(sgn));      // (alive on every exit path: see the carried state above)
     STAMP(4);   // Lemke: exit paths
     // ---- everything below reads its kernel arguments AFRESH from the kernarg segment (through an opaque
     // pointer), so that output pointers, tolerances and record bases are not kept in SGPRs -- and spilled to

@@ -514,6 +514,15 @@ __device__ __forceinline__ int readlane_i32(int v, int l)
 {
     return __builtin_amdgcn_readlane(v, __builtin_amdgcn_readfirstlane(l));
 }
+// Keeps a wave-uniform value in scalar registers across a join: an empty asm with a scalar in/out operand.  The compiler
+// selects the phi of a uniform value into SGPRs and then moves it into VGPRs -- with every phi that feeds it, a copy at each
+// join and a v_readfirstlane in front of each scalar use -- when one of its inputs is a vector register or more than one of its
+// uses wants a vector operand (the VGPR copy in front of a v_readfirstlane counts).  Behind keep_scalar the phi has ONE use, the
+// asm, and what follows reads the asm's result, which is no phi.  No instruction is issued.  (An input that is a vector register
+// after all -- the undefined value the structurizer puts into the join phis of a double is one -- is no silent fallback: the
+// build stops with "illegal VGPR to SGPR copy".)
+__device__ __forceinline__ void keep_scalar(int &x) { asm volatile("" : "+s"(x)); }
+__device__ __forceinline__ void keep_scalar(unsigned long long &x) { asm volatile("" : "+s"(x)); }
 // v with lane `lane` (wave-uniform) replaced by the wave-uniform value `x`: v_writelane_b32, no
 // compare/select.  (No clang builtin on this toolchain, hence asm; gfx9 allows one SGPR per VALU instruction, so the lane
 // select goes through M0 (saved and restored: the compiler owns M0); the s_nop covers the wait states between the SALU write of M0 / a VALU-written
@@ -647,9 +656,10 @@ __device__ __forceinline__ double wave_min32_all_lowlat_f64(double v)
 // stages, then row 0's minimum crosses into row 1 with row_bcast:15 (gfx9 DPP: lane 15 of a row to every lane of the next
 // one) and lane 31 is read out -- 2 DPP moves + 2 v_readlane for the crossing instead of 4 v_readlane + 4 v_mov; `lim`
 // rides in as one v_min with a scalar operand before the stages instead of a v_mov + v_min after them
-__device__ __forceinline__ double wave_min32_with_limit_f64(double v, double lim)
+// (_s: `lim` is an SGPR pair already and goes in as it is)
+__device__ __forceinline__ double wave_min32_with_limit_s_f64(double v, double lim)
 {
-    v = min_f64_nc_s(v, udbl(lim));
+    v = min_f64_nc_s(v, lim);
     v = min_f64_nc(v, dpp_f64<0xB1>(v));
     v = min_f64_nc(v, dpp_f64<0x4E>(v));
     v = min_f64_nc(v, dpp_f64<0x141>(v));
@@ -663,6 +673,7 @@ __device__ __forceinline__ double wave_min32_with_limit_f64(double v, double lim
     }
     return readlane_f64(v, 31);
 }
+__device__ __forceinline__ double wave_min32_with_limit_f64(double v, double lim) { return wave_min32_with_limit_s_f64(v, udbl(lim)); }
 // min over all 64 lanes of v and the wave-uniform `lim`, returned wave-uniform: four DPP row stages, row_bcast:15 into rows
 // 1 and 3, row_bcast:31 into rows 2 and 3, lane 63 read out (callers feed no NaNs; non-candidates carry +inf)
 __device__ __forceinline__ double wave_min64_with_limit_f64(double v, double lim)
