@@ -654,6 +654,45 @@ int qpn_implicit_bounds(qpn_ctx *ctx, int32_t polys, int32_t r, int32_t d, const
                         int32_t flags, const qpn_lp_opts *opts, int32_t *status, int32_t *fail_row, uint8_t *eq, double *vals, int32_t *how,
                         double *lo, double *hi, int32_t *lps, int32_t *iters, int mem);
 
+/* qpn_irredundant_bounds: which bounds of `polys` polyhedra {x : l <= A x <= u} of one shape their other bounds imply, one job per
+ * polyhedron (the reference's `project`, src/sets.jl:501-523, returns the facets of a projected piece; this engine projects by
+ * elimination, qpn_reduced_pieces and qpn_project_pieces, and prunes here).  A [polys][r][d] column-major per item, l, u [polys][r]
+ * (+-inf allowed), as for qpn_solve_lps.  Outputs (how, ext, lps, iters, fail_row may be NULL):
+ *   status [polys] int32 (QPN_IB_OK, _EMPTY, _ITER_LIMIT, _FAILURE);  fail_row [polys] int32: the row whose solve ended the polyhedron,
+ *   -1 without one;  lr, ur [polys][r]: l and u with every removed bound at -inf / +inf; where status is not QPN_IB_OK, l and u as given;
+ *   how [polys][r][2] int32 (QPN_RED_*), [..][0] the lower bound;  ext [polys][r][2]: the extreme of a_i'x an LP found with the bound
+ *   relaxed, -+inf when unbounded, NaN where no LP ran;
+ *   lps [polys] int32: simplex solves started, the feasibility solve counted;  iters [polys] int32: all their steps.
+ * Method (polyhedra.irredundant_bounds_host is its numpy twin and the normative statement; every output is bit-equal to it, by the
+ * discipline of qpn_solve_lps, whose set-up, loop and check it runs).  A bound the others imply shows only with that bound out of
+ * the way -- a sum of two facet rows is tight exactly where both are, so its extreme over the whole set equals its bound -- hence
+ * the test relaxes the bound it tests, and a removed bound stays removed for every later test, which keeps one of two equal rows.
+ * A row with l > u makes the polyhedron EMPTY before any LP (lps = 0).  (a) steps 1-8 of qpn_solve_lps with c = 0 over the working
+ * bounds (the job's lr, ur, filled from l, u): EMPTY, FAILURE, ITER_LIMIT as in qpn_implicit_bounds (a).  (b) the rows r - 1 ... 0,
+ * on each the lower bound before the upper: l == u is KEPT_EQUALITY on both sides, no LP; an all-zero row has both bounds
+ * REMOVED_ZERO_ROW, no LP; an infinite bound is NONE; any other bound is set to -+inf in the working bounds, unscaled (the check of
+ * step 9 reads those) and scaled (the loop reads those), nothing else of the state changing, and c = +a_i (lower) or c = -a_i
+ * (upper) is solved from the current basis as in qpn_implicit_bounds (c).  (c) a certified ray: KEPT_UNBOUNDED, ext = -+inf; an
+ * optimum, ext = obj (lower) or -obj (upper): ext < l - tol max(1, |l|) (ext > u + tol max(1, |u|)) is KEPT_BY_OPTIMUM, anything
+ * else REMOVED and the bound stays infinite.  ITER_LIMIT, or a FAILURE that step 10 does not mend, ends the polyhedron with
+ * fail_row = the row.  (d) a kept bound is restored, unscaled and as bound * scale_i; a basic s_i outside it is a phase-1 violation
+ * the next solve repairs, a nonbasic s_i whose value lies outside it takes the bound's value.  (e) a polyhedron that does not end
+ * OK returns lr = l, ur = u, and its REMOVED / REMOVED_ZERO_ROW verdicts read UNDECIDED again: a finished pruning, or the input.
+ * lr, ur must not overlap l, u.  Kernel classes are those of qpn_lp_kernel_class(r, d).  1 <= d <= 256, 1 <= r <= 1024
+ * (QPN_ERR_SIZE beyond).  max_iters is per solve.  polys == 0 succeeds. */
+enum {
+    QPN_RED_UNDECIDED = 0,        /* the polyhedron ended before the bound's turn, or did not end OK    bound as given */
+    QPN_RED_NONE = 1,             /* the bound is infinite                                               bound as given */
+    QPN_RED_KEPT_EQUALITY = 2,    /* l == u                                                              bound as given */
+    QPN_RED_REMOVED_ZERO_ROW = 3, /* an all-zero row of a polyhedron that has a point                    removed        */
+    QPN_RED_KEPT_UNBOUNDED = 4,   /* without the bound the row is unbounded on that side, by a ray       bound as given */
+    QPN_RED_KEPT_BY_OPTIMUM = 5,  /* without the bound the row passes it by more than tol max(1, |b|)    bound as given */
+    QPN_RED_REMOVED = 6           /* without the bound the row stays within tol max(1, |b|) of it        removed        */
+};
+int qpn_irredundant_bounds(qpn_ctx *ctx, int32_t polys, int32_t r, int32_t d, const double *A, const double *l, const double *u, double tol,
+                           const qpn_lp_opts *opts, int32_t *status, int32_t *fail_row, double *lr, double *ur, int32_t *how, double *ext,
+                           int32_t *lps, int32_t *iters, int mem);
+
 /* qpn_exemplar_polys: `exemplar` / `isempty` (src/sets.jl:591-655) of `polys` polyhedra {x : l <= A x <= u} of one shape whose
  * bounds may be open, one job per polyhedron.  A [polys][n][d] column-major per item, l, u [polys][n] (+-inf allowed), open_lo,
  * open_hi [polys][n] uint8 (nonzero: that bound is open; NULL: every such bound is closed).  Outputs (how, eps, x, row, lambda,

@@ -416,6 +416,44 @@ function implicit_bounds(polys::Vector{<:Tuple{Matrix{Float64},Vector{Float64},V
 end
 
 """
+    irredundant_bounds(polys; tol=1e-8, max_iters=0) -> [(l, u, status), ...]
+
+qpn_irredundant_bounds: the bounds of a list of polyhedra `(A, l, u)` (A [r, d], l, u [r]) that their other bounds imply, one job per
+polyhedron: the crash and phase 1 once, then the finite bounds of the rows from the last, each relaxed and its row minimised
+(maximised) from the basis the previous solve left; a bound the optimum does not pass by more than tol * max(1, |bound|) is
+removed and stays removed for the later tests.  What the reference's `project` (src/sets.jl:501-523) returns as facets.  Polyhedra of
+one shape go up in one call.  Returns per polyhedron the bounds with every removed one at -Inf / Inf and the status (0 OK; 1 empty, 2
+iteration limit, 3 failure: the bounds come back as given).
+"""
+function irredundant_bounds(polys::Vector{<:Tuple{Matrix{Float64},Vector{Float64},Vector{Float64}}}; tol::Float64 = 1e-8,
+                            max_iters::Integer = 0)
+    out = Vector{Tuple{Vector{Float64},Vector{Float64},Int}}(undef, length(polys))
+    packs = Dict{Tuple{Int,Int},Vector{Int}}()
+    for (k, (A, l, u)) in enumerate(polys)
+        length(l) == size(A, 1) && length(u) == size(A, 1) || error("irredundant_bounds: inconsistent shapes (polyhedron $k)")
+        push!(get!(packs, size(A), Int[]), k)
+    end
+    opts = Ref((1e-9, 1e-9, 1e-9, 1e-6, Int32(max_iters), Int32(0)))      # qpn_lp_opts
+    for ((r, d), members) in sort(collect(packs))
+        n = length(members)
+        A = Array{Float64,3}(undef, r, d, n); l = Matrix{Float64}(undef, r, n); u = Matrix{Float64}(undef, r, n)
+        for (t, k) in enumerate(members)
+            A[:, :, t] = polys[k][1]; l[:, t] = polys[k][2]; u[:, t] = polys[k][3]
+        end
+        status = zeros(Int32, n); lr = zeros(r, n); ur = zeros(r, n)
+        rc = ccall((:qpn_irredundant_bounds, LIB), Cint,
+                   (Ptr{Cvoid}, Int32, Int32, Int32, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cdouble, Ptr{Cvoid}, Ptr{Int32},
+                    Ptr{Int32}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int32}, Ptr{Cdouble}, Ptr{Int32}, Ptr{Int32}, Cint),
+                   ctx(), n, r, d, A, l, u, tol, opts, status, C_NULL, lr, ur, C_NULL, C_NULL, C_NULL, C_NULL, QPN_MEM_HOST)
+        rc == 0 || error("qpn_irredundant_bounds failed ($rc)")
+        for (t, k) in enumerate(members)
+            out[k] = (lr[:, t], ur[:, t], Int(status[t]))
+        end
+    end
+    out
+end
+
+"""
     exemplar_polys(A, l, u; open_lo=nothing, open_hi=nothing, tol=1e-2, slack_cap=1.0, max_iters=0)
         -> (empty, how, eps, x, row, lambda, iters)
 

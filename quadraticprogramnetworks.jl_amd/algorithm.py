@@ -7,7 +7,7 @@ import numpy as np
 
 from .avi import AVISolveError, solve_qep
 from .level_batch import process_level
-from .polyhedra import remove_subsets_many
+from .polyhedra import irredundant_batch, remove_subsets_many
 
 
 class CyclingError(RuntimeError):
@@ -24,6 +24,7 @@ def solve(qpn, x_init=None, engine=None, rng=None):
     qpn.iterate_cache = {}
     qpn.__dict__["_process_memo"] = {}          # level_batch.process_level / the subset reduction below: results of the last sweep
     qpn.__dict__["_subset_memo"] = {}
+    qpn.__dict__["_irredundant_memo"] = {}
     return solve_base(qpn, np.asarray(x_init, dtype=np.float64), level=1, proj_vectors=[], rng=rng, engine=engine)
 
 
@@ -76,6 +77,23 @@ def solve_base(qpn, x_init, level=1, proj_vectors=None, rng=None, engine=None):
                             sub_assign[child] = S[child][sp]; sub_ids[child] = sp
                 else:
                     graphs[pid] = r["S"]
+            if graphs and getattr(opts, "irredundant_pieces", False):                # all pieces of the level in one batch, before
+                pmemo = qpn.__dict__.setdefault("_irredundant_memo", {})             # the subset LPs read them
+                todo = []
+                for pid in graphs:
+                    ent = pmemo.get(pid)
+                    if ent is not None and ent[0] is graphs[pid]:                    # the graph process_level handed back unchanged:
+                        graphs[pid] = ent[1]                                         # its pruning is known
+                    elif graphs[pid]:
+                        todo.append(pid)
+                if todo:
+                    from .avi import _eng
+                    pruned = irredundant_batch([p for pid in todo for p in graphs[pid]], _eng(engine))
+                    at = 0
+                    for pid in todo:
+                        got = pruned[at:at + len(graphs[pid])]; at += len(graphs[pid])
+                        pmemo[pid] = (graphs[pid], got)
+                        graphs[pid] = got
             lv = opts.levels_to_remove_subsets                                       # None = NaturalNumbers(): every level
             if graphs and (lv is None or level in lv):                               # :84, all nodes of the level in one batch
                 ids = [pid for pid in graphs if graphs[pid] is not None and len(graphs[pid]) > 1]

@@ -1928,6 +1928,37 @@ int qpn_implicit_bounds(qpn_ctx *ctx, int32_t polys, int32_t r, int32_t d, const
     return st.finish();
 }
 
+int qpn_irredundant_bounds(qpn_ctx *ctx, int32_t polys, int32_t r, int32_t d, const double *A, const double *l, const double *u, double tol,
+                           const qpn_lp_opts *opts, int32_t *status, int32_t *fail_row, double *lr, double *ur, int32_t *how, double *ext,
+                           int32_t *lps, int32_t *iters, int mem)
+{
+    if (!ctx) return QPN_ERR_ARG;
+    if (polys < 0 || r <= 0 || d <= 0) return fail_arg(ctx, "qpn_irredundant_bounds: bad sizes");
+    if (r > QPN_LP_MAX_R || d > QPN_LP_MAX_D) { ctx->last_error = "qpn_irredundant_bounds: d <= 256, r <= 1024 in ABI v1"; return QPN_ERR_SIZE; }
+    Stage st(ctx, mem, "qpn_irredundant_bounds");
+    if (int rc = st.check()) return rc;
+    if (polys == 0) return QPN_OK;
+    if (!A || !l || !u || !status || !lr || !ur) return fail_arg(ctx, "qpn_irredundant_bounds: null pointer");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t P = (size_t)polys;
+    RedArgs a{};
+    a.polys = polys; a.r = r; a.d = d; a.tol = tol;
+    a.lp = lp_tol(opts, r, d);
+    void *gws;
+    st.in(a.A, A, P * r * d * 8); st.in(a.l, l, P * r * 8); st.in(a.u, u, P * r * 8);
+    st.out(a.status, status, P * 4); st.out(a.lr, lr, P * r * 8); st.out(a.ur, ur, P * r * 8);
+    st.out_opt(a.fail_row, fail_row, P * 4);
+    st.out_opt(a.how, how, P * r * 2 * 4);
+    st.out_opt(a.ext, ext, P * r * 2 * 8);
+    st.out_opt(a.lps, lps, P * 4);
+    st.out_opt(a.iters, iters, P * 4);
+    st.scratch(gws, qpn_lp_workspace_bytes(polys, r, d));
+    int rc = st.begin();
+    if (rc != QPN_OK) return rc;
+    HIPCHK(ctx, qpn_launch_irredundant_bounds(a, gws, ctx->stream));
+    return st.finish();
+}
+
 int qpn_exemplar_polys(qpn_ctx *ctx, int32_t polys, int32_t n, int32_t d, const double *A, const double *l, const double *u,
                        const uint8_t *open_lo, const uint8_t *open_hi, double tol, double slack_cap, const qpn_lp_opts *opts,
                        uint8_t *empty, int32_t *how, double *eps, double *x, int32_t *row, double *lambda, int32_t *iters, int mem)

@@ -373,6 +373,20 @@ struct IbArgs {
     LpTol lp;
 };
 hipError_t qpn_launch_implicit_bounds(const IbArgs &a, void *gws, hipStream_t s);     // gws: qpn_lp_workspace_bytes(polys, r, d)
+// ... and the bounds of polyhedra that their other bounds imply (qpn_irredundant_bounds), one job per polyhedron.  lr, ur are the
+// job's working bounds while it runs.  how, ext, lps, iters, fail_row may be null.
+struct RedArgs {
+    int32_t polys, r, d;
+    const double *A, *l, *u;
+    double tol;
+    int32_t *status, *fail_row;
+    double *lr, *ur;
+    int32_t *how;                              // [polys][r][2]
+    double *ext;                               // [polys][r][2]
+    int32_t *lps, *iters;
+    LpTol lp;
+};
+hipError_t qpn_launch_irredundant_bounds(const RedArgs &a, void *gws, hipStream_t s); // gws: qpn_lp_workspace_bytes(polys, r, d)
 // ... and the emptiness of polyhedra with open bounds (qpn_exemplar_polys), one job per polyhedron over its slack LP of 2 n + 1 rows
 // in d + 1 variables.  open_lo, open_hi null: closed;  how, eps, x, row, lam, iters may be null.
 struct ExArgs {

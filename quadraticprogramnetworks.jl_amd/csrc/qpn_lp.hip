@@ -34,8 +34,13 @@
 // the gathered rows as ex_job does (prod_job; polyhedra.exemplar_products_host is its twin).  Nothing of the pool is copied per product
 // but the rows of the LP the job solves.
 //
-// The five entries share the kernels and the launcher: lp_wave_kernel<Job> and lp_group_kernel<Job, LDS>
-// run the job function of the kind Job (LpJob, SubsetJob, IbJob, ExJob, ProdJob), lp_launch<Job> picks the class and launches.
+// qpn_irredundant_bounds runs them with one team per polyhedron: lp_feasible once, then the finite bounds of
+// the rows from the last to the first, each relaxed in the job's working bounds and its row minimised (maximised) by lp_resolve
+// from the basis the previous solve left; a bound the optimum does not pass is implied by the others and stays out, any other
+// comes back (red_core; polyhedra.irredundant_bounds_host is its twin).  The working bounds are the job's own output rows.
+//
+// The six entries share the kernels and the launcher: lp_wave_kernel<Job> and lp_group_kernel<Job, LDS>
+// run the job function of the kind Job (LpJob, SubsetJob, IbJob, ExJob, ProdJob, RedJob), lp_launch<Job> picks the class and launches.
 #include <climits>
 
 #include "qpn_internal.h"
@@ -986,6 +991,133 @@ template <int T> __device__ void prod_job(const ProdArgs &a, int t, double *base
     }
 }
 
+// ---- irredundant bounds: one team per polyhedron -----------------------------------------------------------------------------------
+struct RedOut { int status, fail_row, lps, iters; };
+
+// Polyhedron b.  The working copy of the unscaled bounds is the job's own output rows lr, ur: P.lb, P.ub point at them, so lp_check
+// reads a relaxed bound as relaxed; the scaled copy is S.ls, S.us.  Row i belongs to lane i % T, which alone writes its bounds, its
+// verdicts and its extremes; a barrier stands between such a write and the solve that reads it.  Every value a branch depends on is
+// the same in all threads of the team (the polyhedron's own bounds, S.amx after the set-up's barriers, the status and the
+// objective of a solve), so a whole team leaves together.  At most 2 r solves of max_iters steps each.
+template <int T> __device__ void red_core(const RedArgs &a, const LpSlice &S, int b, int tid, RedOut &o)
+{
+    const int r = a.r, d = a.d;
+    const double *l = a.l + (size_t)b * r, *u = a.u + (size_t)b * r;
+    double *lr = a.lr + (size_t)b * r, *ur = a.ur + (size_t)b * r;
+    int32_t *how = a.how ? a.how + (size_t)b * r * 2 : nullptr;
+    double *ext = a.ext ? a.ext + (size_t)b * r * 2 : nullptr;
+    const LpProb P = lp_prob(r, d, a.A + (size_t)b * r * d, lr, ur, a.lp);
+    const double tol = a.tol;
+    // (0) the working bounds; crossed bounds: no LP is started
+    int uncrossed = 1;
+    for (int i = tid; i < r; i += T) {
+        const double li = l[i], ui = u[i];
+        if (li > ui) uncrossed = 0;
+        lr[i] = li; ur[i] = ui;
+        if (how) { how[2 * i] = QPN_RED_UNDECIDED; how[2 * i + 1] = QPN_RED_UNDECIDED; }
+        if (ext) { ext[2 * i] = __builtin_nan(""); ext[2 * i + 1] = __builtin_nan(""); }
+    }
+    if (!team_min_int<T>(uncrossed, S.red, tid)) { o.status = QPN_IB_EMPTY; return; }
+    // (a) the feasibility solve
+    int it;
+    o.lps = 1;
+    int status = lp_feasible<T>(P, S, tid, &it);
+    o.iters = it;
+    if (status != QPN_LP_OPTIMAL) {
+        o.status = status == QPN_LP_INFEASIBLE ? QPN_IB_EMPTY : status == QPN_LP_ITER_LIMIT ? QPN_IB_ITER_LIMIT : QPN_IB_FAILURE;
+        return;
+    }
+    // (b) the rows from the last, the lower bound before the upper
+    for (int i = r - 1; i >= 0; --i) {
+        const double li = l[i], ui = u[i];
+        const bool mine = i % T == tid;                   // this lane owns the row
+        if (li == ui) {
+            if (mine && how) { how[2 * i] = QPN_RED_KEPT_EQUALITY; how[2 * i + 1] = QPN_RED_KEPT_EQUALITY; }
+            continue;
+        }
+        if (S.amx[i] == 0.0) {                            // (a) has shown 0 within its bounds
+            team_sync<T>();
+            if (mine) {
+                lr[i] = -QINF; ur[i] = QINF; S.ls[i] = -QINF; S.us[i] = QINF;
+                if (how) { how[2 * i] = QPN_RED_REMOVED_ZERO_ROW; how[2 * i + 1] = QPN_RED_REMOVED_ZERO_ROW; }
+            }
+            continue;
+        }
+        for (int side = 0; side < 2; ++side) {
+            const double bound = side ? ui : li;
+            if (!(fabs(bound) < QINF)) {
+                if (mine && how) how[2 * i + side] = QPN_RED_NONE;
+                continue;
+            }
+            // the bound leaves the working bounds, its row is the objective
+            team_sync<T>();
+            if (mine) {
+                if (side) { ur[i] = QINF; S.us[i] = QINF; } else { lr[i] = -QINF; S.ls[i] = -QINF; }
+            }
+            for (int j = tid; j < d; j += T) { const double v = P.Ab[(size_t)j * r + i]; S.cv[j] = side ? -v : v; }
+            team_sync<T>();
+            double obj;
+            ++o.lps;
+            status = lp_resolve<T>(P, S, tid, &it, &obj);
+            o.iters += it;
+            if (status == QPN_LP_ITER_LIMIT) { o.status = QPN_IB_ITER_LIMIT; o.fail_row = i; return; }
+            if (status == QPN_LP_FAILURE) { o.status = QPN_IB_FAILURE; o.fail_row = i; return; }
+            // (c) the verdict
+            const double margin = tol * fmax(1.0, fabs(bound));
+            double e;
+            int verdict;
+            if (status == QPN_LP_UNBOUNDED) {
+                e = side ? QINF : -QINF;
+                verdict = QPN_RED_KEPT_UNBOUNDED;
+            } else {
+                e = side ? -obj : obj;
+                const bool beyond = side ? e > bound + margin : e < bound - margin;
+                verdict = beyond ? QPN_RED_KEPT_BY_OPTIMUM : QPN_RED_REMOVED;
+            }
+            if (mine) {
+                if (ext) ext[2 * i + side] = e;
+                if (how) how[2 * i + side] = verdict;
+            }
+            if (verdict == QPN_RED_REMOVED) continue;
+            // (d) a kept bound comes back; a nonbasic s_i outside it takes its value
+            const double v = bound * S.sc[i];
+            team_sync<T>();
+            if (mine) {
+                if (side) { ur[i] = bound; S.us[i] = v; } else { lr[i] = bound; S.ls[i] = v; }
+            }
+            for (int j = tid; j < d; j += T)
+                if (S.cn[j] == d + i && (side ? S.xn[j] > v : S.xn[j] < v)) S.xn[j] = v;
+        }
+    }
+    o.status = QPN_IB_OK;
+}
+
+template <int T> __device__ void red_job(const RedArgs &a, int b, double *base, int tid)
+{
+    const int r = a.r;
+    const LpSlice S(base, r, a.d);
+    if (tid < 8) S.red[tid] = 0.0;
+    team_sync<T>();
+    RedOut o{QPN_IB_FAILURE, -1, 0, 0};
+    red_core<T>(a, S, b, tid, o);
+    if (o.status != QPN_IB_OK) {                          // (e) the input back; a removal is no verdict any more (a lane's own rows)
+        for (int i = tid; i < r; i += T) {
+            a.lr[(size_t)b * r + i] = a.l[(size_t)b * r + i]; a.ur[(size_t)b * r + i] = a.u[(size_t)b * r + i];
+            if (a.how)
+                for (int side = 0; side < 2; ++side) {
+                    int32_t *h = a.how + ((size_t)b * r + i) * 2 + side;
+                    if (*h == QPN_RED_REMOVED || *h == QPN_RED_REMOVED_ZERO_ROW) *h = QPN_RED_UNDECIDED;
+                }
+        }
+    }
+    if (tid == 0) {
+        a.status[b] = o.status;
+        if (a.fail_row) a.fail_row[b] = o.fail_row;
+        if (a.lps) a.lps[b] = o.lps;
+        if (a.iters) a.iters[b] = o.iters;
+    }
+}
+
 // ---- the kernels and the launcher of every job kind ------------------------------------------------------------------------------
 // A job kind names its argument struct and runs job t of it with a team of T threads on the slice at base.
 struct LpJob {
@@ -1007,6 +1139,10 @@ struct ExJob {
 struct ProdJob {
     using Args = ProdArgs;
     template <int T> static __device__ void run(const Args &a, int t, double *base, int tid) { prod_job<T>(a, t, base, tid); }
+};
+struct RedJob {
+    using Args = RedArgs;
+    template <int T> static __device__ void run(const Args &a, int t, double *base, int tid) { red_job<T>(a, t, base, tid); }
 };
 
 template <class Job> __global__ __launch_bounds__(64 * LP_WAVES) void lp_wave_kernel(typename Job::Args a, int32_t count, size_t slice)
@@ -1112,6 +1248,7 @@ size_t qpn_lp_workspace_bytes(int32_t jobs, int32_t r, int32_t d)
 hipError_t qpn_launch_solve_lps(const LpArgs &a, void *gws, hipStream_t s) { return lp_launch<LpJob>(a, a.jobs, a.r, a.d, gws, s); }
 hipError_t qpn_launch_issubset_pairs(const SubsetArgs &a, void *gws, hipStream_t s) { return lp_launch<SubsetJob>(a, a.pairs, a.r1, a.d, gws, s); }
 hipError_t qpn_launch_implicit_bounds(const IbArgs &a, void *gws, hipStream_t s) { return lp_launch<IbJob>(a, a.polys, a.r, a.d, gws, s); }
+hipError_t qpn_launch_irredundant_bounds(const RedArgs &a, void *gws, hipStream_t s) { return lp_launch<RedJob>(a, a.polys, a.r, a.d, gws, s); }
 
 size_t qpn_exemplar_workspace_bytes(int32_t polys, int32_t n, int32_t d)
 {

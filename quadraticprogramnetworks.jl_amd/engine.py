@@ -758,6 +758,28 @@ class Engine:
                    _ptr(out["how"]), _ptr(out["lo"]), _ptr(out["hi"]), _ptr(out["lps"]), _ptr(out["iters"]), self._mem(dev))
         return out
 
+    def irredundant_bounds(self, Ac, l, u, tol=1e-8, opts=None):
+        """Which bounds of polyhedra of one shape their other bounds imply, one job per polyhedron (qpn_irredundant_bounds;
+        polyhedra.irredundant_bounds_host is its numpy twin, bit for bit): Ac [polys, d, r] (ABI layout, ``colmajor(A)``), l, u
+        [polys, r].  opts: LpOpts, a dict of its fields, or None.
+        Returns dict(status [polys] int32 (_lib.IB_*), fail_row [polys] int32, lr, ur [polys, r] (a removed bound is -+inf), how
+        [polys, r, 2] int32 (_lib.RED_*), ext [polys, r, 2], lps, iters [polys] int32)."""
+        dev, Ac, l, u = self._stage("irredundant_bounds", "Ac l u", f64=(Ac, l, u))
+        if Ac.ndim != 3:
+            raise QpnError("irredundant_bounds: inconsistent shapes")
+        polys, d, r = (int(v) for v in Ac.shape)
+        if tuple(l.shape) != (polys, r) or tuple(u.shape) != (polys, r):
+            raise QpnError("irredundant_bounds: inconsistent shapes")
+        opts = self._lp_opts(opts)
+        out = dict(status=self._alloc(dev, (polys,), np.int32), fail_row=self._alloc(dev, (polys,), np.int32),
+                   lr=self._alloc(dev, (polys, r), np.float64), ur=self._alloc(dev, (polys, r), np.float64),
+                   how=self._alloc(dev, (polys, r, 2), np.int32), ext=self._alloc(dev, (polys, r, 2), np.float64),
+                   lps=self._alloc(dev, (polys,), np.int32), iters=self._alloc(dev, (polys,), np.int32))
+        self._call("qpn_irredundant_bounds", polys, r, d, _ptr(Ac), _ptr(l), _ptr(u), float(tol), C.byref(opts) if opts is not None else None,
+                   _ptr(out["status"]), _ptr(out["fail_row"]), _ptr(out["lr"]), _ptr(out["ur"]), _ptr(out["how"]), _ptr(out["ext"]),
+                   _ptr(out["lps"]), _ptr(out["iters"]), self._mem(dev))
+        return out
+
     def exemplar_polys(self, Ac, l, u, open_lo=None, open_hi=None, tol=1e-2, slack_cap=1.0, opts=None):
         """`exemplar` / `isempty` of polyhedra of one shape whose bounds may be open, one job per polyhedron (qpn_exemplar_polys;
         polyhedra.exemplar_polys_host is its numpy twin, bit for bit): Ac [polys, d, n] (ABI layout, ``colmajor(A)``), l, u

@@ -29,6 +29,8 @@ keeps the node-AVI route.  On an engine with `exemplar_polys` (qpn_exemplar_poly
 bounds may be open is ONE job too, opt-in through route="polyhedron": the job expands the slack LP, solves it and applies the
 reference's rule to its own duals (exemplar_polys_host is the twin).  On one with `exemplar_products` (qpn_exemplar_products) the
 products of pieces of the intersection tree are jobs over one pool of rows (isempty_products; exemplar_products_host is the twin).
+On one with `irredundant_bounds` (qpn_irredundant_bounds) irredundant_batch removes the bounds of polyhedra that their other bounds
+imply, one job per polyhedron (irredundant_bounds_host is the twin); there is no other route for it.
 
 These are the batch front ends: they normalise their inputs (_triple), pick a route, pack by shape (pack_by_shape), call the
 engine and unpack.  The numpy twins and the result codes are polyhedra_host.py; their public names stay importable from here.
@@ -742,6 +744,41 @@ def _implicit_bounds_polyhedra(trips, engine, tol):
     if beyond:
         for b, got in zip(beyond, _implicit_bounds_jobs([trips[b] for b in beyond], engine, tol, names=beyond, empt=empt)):
             out[b] = got
+    return out
+
+
+def irredundant_batch(polys, engine, tol=1e-8):
+    """The polyhedra without the bounds their other bounds imply (qpn_irredundant_bounds; irredundant_bounds_host states the
+    method): what the reference's `project` (src/sets.jl:501-523) gives a projected piece by going through its vertices.  The
+    polyhedra packed by shape (rows, columns), one call per shape; a Poly in local form goes up over its own columns.
+    -> a list of the same length and order: a Poly with the removed bounds at -+inf, a row with both bounds gone dropped, the
+    order of the rows and the open flags of the bounds that stay kept.  An item comes back as it was given -- the same object --
+    when nothing of it is removed, when its shape is beyond the kernel's limits, when the engine has no `irredundant_bounds`, and
+    when its status is not OK; that includes EMPTY: emptiness is `combine`'s business.  There is no other route."""
+    from .engine import colmajor
+    from .programs import Poly
+    polys = list(polys)
+    if not polys or not _has(engine, "irredundant_bounds"):
+        return polys
+    trips = [_triple((p.local()[1], p.l, p.u) if hasattr(p, "local") else p) for p in polys]
+    packs, _ = pack_by_shape(trips, beyond=lambda s: min(s) < 1 or s[0] > LP_MAX_R or s[1] > LP_MAX_D)
+    out = list(polys)
+    for _, members, A, l, u in packs:
+        res = engine.irredundant_bounds(colmajor(A), l, u, tol=tol)
+        st = _to_host(res["status"]); lr = _to_host(res["lr"]); ur = _to_host(res["ur"])
+        for t, b in enumerate(members):
+            if st[t] != IB_OK or (np.array_equal(lr[t], l[t]) and np.array_equal(ur[t], u[t])):
+                continue
+            keep = np.isfinite(lr[t]) | np.isfinite(ur[t])
+            p = polys[b]
+            olo, ohi = _open(p, len(keep))
+            olo = (olo & np.isfinite(lr[t]))[keep]; ohi = (ohi & np.isfinite(ur[t]))[keep]
+            if getattr(p, "_cols", None) is not None:
+                cols, Al = p.local()
+                out[b] = Poly.from_local(p.ncols, cols, Al[keep], lr[t][keep], ur[t][keep], normalise=False, open_lo=olo, open_hi=ohi)
+            else:
+                Ad = np.atleast_2d(np.asarray(p.vectorize()[0] if hasattr(p, "vectorize") else p[0], dtype=np.float64))
+                out[b] = Poly(Ad[keep], lr[t][keep], ur[t][keep], normalise=False, open_lo=olo, open_hi=ohi)
     return out
 
 

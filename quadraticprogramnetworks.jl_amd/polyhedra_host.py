@@ -1,5 +1,5 @@
 """The numpy twins of the polyhedral entries, the normative statements of the kernels' methods (the kernels are bit-equal to them):
-solve_lps_host, issubset_pairs_host, implicit_bounds_host, exemplar_polys_host, exemplar_products_host, interior_member_records and members_outside_host,
+solve_lps_host, issubset_pairs_host, implicit_bounds_host, irredundant_bounds_host, exemplar_polys_host, exemplar_products_host, interior_member_records and members_outside_host,
 with the entries' result codes, defined here once (_lib.py and polyhedra.py import them).  Numpy alone, loadable as a stand-alone
 file: tests/golden/lp_twin_record.json pins it across commits.  The front ends that pack, route and call an engine are polyhedra.py.
 """
@@ -595,8 +595,136 @@ def implicit_bounds_host(Ac, l, u, tol=1e-4, all_extremes=False, opts=None):
     return out
 
 
+# ---- irredundant bounds (qpn_irredundant_bounds): one job per polyhedron, the numpy twin -----------------------------------------
+RED_UNDECIDED, RED_NONE, RED_KEPT_EQUALITY, RED_REMOVED_ZERO_ROW, RED_KEPT_UNBOUNDED, RED_KEPT_BY_OPTIMUM, RED_REMOVED = 0, 1, 2, 3, 4, 5, 6
+
+
+def _red_relax(S, lw, uw, i, side):
+    """Bound `side` (0 lower, 1 upper) of row i leaves the working bounds: the unscaled copy the check reads (lw, uw = S.l, S.u)
+    and the scaled one the loop reads.  Nothing else of the state changes: a nonbasic s_i keeps its value, now strictly inside."""
+    if side == 0:
+        lw[i] = -INF; S.ls[i] = -INF
+    else:
+        uw[i] = INF; S.us[i] = INF
+
+
+def _red_restore(S, lw, uw, i, side, bound):
+    """... and comes back: the unscaled value and bound * sc[i], the product the set-up made.  A basic s_i outside the bound is the
+    next loop's phase-1 violation.  A nonbasic s_i whose value lies outside the restored bound takes the bound's value (the loop
+    moves a nonbasic variable between its bounds and never towards them from outside)."""
+    with np.errstate(all="ignore"):
+        v = bound * S.sc[i]
+    if side == 0:
+        lw[i] = bound; S.ls[i] = v
+    else:
+        uw[i] = bound; S.us[i] = v
+    for j in range(S.d):
+        if S.cn[j] == S.d + i and (S.xn[j] < v if side == 0 else S.xn[j] > v):
+            S.xn[j] = v
+
+
+def _irredundant_one(A, l, u, tol, o):
+    """One polyhedron by the method of qpn_irredundant_bounds (A [r, d] math layout).
+    -> (status, fail_row, lr [r], ur [r], how [r, 2] int32, ext [r, 2], lps, iters)."""
+    r, d = A.shape
+    lw, uw = l.copy(), u.copy()                             # the working bounds; what an OK end returns
+    how = np.full((r, 2), RED_UNDECIDED, np.int32); ext = np.full((r, 2), np.nan)
+
+    def ended(status, row, lps, iters):                     # (e) the input back; a removal is no verdict any more
+        how[(how == RED_REMOVED) | (how == RED_REMOVED_ZERO_ROW)] = RED_UNDECIDED
+        return status, row, l.copy(), u.copy(), how, ext, lps, iters
+
+    with np.errstate(all="ignore"):
+        if np.any(l > u):                                   # crossed bounds: no LP is started
+            return ended(IB_EMPTY, -1, 0, 0)
+        # (a) the feasibility solve
+        status, S, x = _lp_feasible(A, lw, uw, o)
+        lps, iters = 1, S.iters
+        if status != LP_OPTIMAL:
+            return ended({LP_INFEASIBLE: IB_EMPTY, LP_ITER_LIMIT: IB_ITER_LIMIT}.get(status, IB_FAILURE), -1, lps, iters)
+        # (b) the rows from the last, the lower bound before the upper
+        for i in range(r - 1, -1, -1):
+            if l[i] == u[i]:
+                how[i] = RED_KEPT_EQUALITY
+                continue
+            if S.amax[i] == 0.0:                            # (a) has shown 0 within its bounds
+                how[i] = RED_REMOVED_ZERO_ROW
+                _red_relax(S, lw, uw, i, 0); _red_relax(S, lw, uw, i, 1)
+                continue
+            for side in (0, 1):
+                bound = l[i] if side == 0 else u[i]
+                if not abs(bound) < INF:
+                    how[i, side] = RED_NONE
+                    continue
+                _red_relax(S, lw, uw, i, side)
+                c = A[i].copy() if side == 0 else -A[i]
+                lps += 1
+                status, x, obj = _lp_resolve(S, c)
+                iters += S.iters
+                if status == LP_ITER_LIMIT:
+                    return ended(IB_ITER_LIMIT, i, lps, iters)
+                if status == LP_FAILURE:
+                    return ended(IB_FAILURE, i, lps, iters)
+                # (c) the verdict
+                margin = tol * max(1.0, abs(bound))
+                if status == LP_UNBOUNDED:
+                    ext[i, side] = -INF if side == 0 else INF
+                    how[i, side] = RED_KEPT_UNBOUNDED
+                else:
+                    e = obj if side == 0 else -obj
+                    ext[i, side] = e
+                    beyond = e < bound - margin if side == 0 else e > bound + margin
+                    how[i, side] = RED_KEPT_BY_OPTIMUM if beyond else RED_REMOVED
+                if how[i, side] != RED_REMOVED:
+                    _red_restore(S, lw, uw, i, side, bound)     # (d)
+    return IB_OK, -1, lw, uw, how, ext, lps, iters
+
+
+def irredundant_bounds_host(Ac, l, u, tol=1e-8, opts=None):
+    """The numpy twin of Engine.irredundant_bounds (qpn_irredundant_bounds), the normative statement of the method; every output of
+    the kernel is bit-equal to it.  Which bounds of {x : l <= A x <= u} the other bounds imply, one job per polyhedron: Ac [polys, d, r]
+    (ABI layout), l, u [polys, r] (+-inf allowed).  The reference gets irredundant pieces from `project` (src/sets.jl:501-523: vertices,
+    then facets); this engine projects by elimination and prunes afterwards.
+
+    A bound implied by the others is found only with that bound out of the way: a sum of two facet rows is tight exactly where both
+    are, so its extreme over the whole set equals its bound.  The method therefore relaxes the bound it tests, and a removed bound
+    stays removed for every later test, which keeps one of two equal rows.
+
+    A row with l > u makes the polyhedron EMPTY before any LP (lps = 0), as in implicit_bounds_host (0).  (a) _lp_feasible once
+    over working copies of l and u: an infeasible all-zero row, or an INFEASIBLE end whose Farkas certificate holds, is EMPTY, a
+    certificate that fails FAILURE, ITER_LIMIT itself (the codes are IB_*).  (b) the rows r - 1 ... 0 (generated Fourier-Motzkin rows
+    come last and go first), on each the lower bound before the upper: l == u is KEPT_EQUALITY on both sides, no LP; an all-zero row
+    (max|a_i| = 0) has both bounds REMOVED_ZERO_ROW, no LP; an infinite bound is NONE; any other bound is relaxed to -+inf in the
+    working bounds, unscaled (what step 9's check reads) and scaled (what the loop reads), nothing else of the state changing, and
+    _lp_resolve runs c = +a_i (lower) or c = -a_i (upper) from the basis the previous solve left.  (c) a certified ray: KEPT_UNBOUNDED,
+    ext = -+inf; an optimum, ext = obj (lower) or -obj (upper): ext < l - tol max(1, |l|) (ext > u + tol max(1, |u|)) is
+    KEPT_BY_OPTIMUM, anything else REMOVED and the bound stays infinite.  ITER_LIMIT or FAILURE of the solve ends the polyhedron
+    with fail_row = i.  (d) a kept bound is restored: the unscaled value and bound * sc_i.  A basic s_i now outside it is a phase-1
+    violation the next solve's loop repairs (the phase is decided before every step).  A nonbasic s_i whose value lies outside the
+    restored bound takes the bound's value.  (The loop does not produce that state: a nonbasic value is where the set-up put it, or
+    a bound the variable reached, and the relaxed side has none to reach; the rule is there so that the state after a restore is
+    one the loop is defined on whatever the solve did, and tests/test_irredundant_host.py exercises it on a state made by hand.)
+    (e) a polyhedron that does not end OK returns lr = l, ur = u, and a REMOVED / REMOVED_ZERO_ROW becomes UNDECIDED again: the
+    caller gets a finished pruning or its input back.  The other verdicts, and ext, stay as they were reached.
+    -> dict(status [polys] int32 (IB_*), fail_row [polys] int32 (-1 without), lr, ur [polys, r] (the input, a removed bound -+inf),
+    how [polys, r, 2] int32 (RED_*, [.., 0] the lower bound), ext [polys, r, 2] (the extreme an LP found, NaN where none ran),
+    lps [polys] int32 (solves started, the feasibility solve counted), iters [polys] int32 (all steps))."""
+    Ac = np.asarray(Ac, dtype=np.float64); l = np.asarray(l, dtype=np.float64); u = np.asarray(u, dtype=np.float64)
+    polys, d, r = Ac.shape
+    o = dict(LP_DEFAULT_OPTS)
+    o.update(opts or {})
+    out = dict(status=np.zeros(polys, np.int32), fail_row=np.full(polys, -1, np.int32), lr=np.zeros((polys, r)), ur=np.zeros((polys, r)),
+               how=np.zeros((polys, r, 2), np.int32), ext=np.full((polys, r, 2), np.nan), lps=np.zeros(polys, np.int32),
+               iters=np.zeros(polys, np.int32))
+    for b in range(polys):
+        got = _irredundant_one(np.ascontiguousarray(Ac[b].T), l[b], u[b], float(tol), o)
+        for k, v in zip(("status", "fail_row", "lr", "ur", "how", "ext", "lps", "iters"), got):
+            out[k][b] = v
+    return out
+
+
 # ---- emptiness with open bounds (qpn_exemplar_polys): one job per polyhedron, the numpy twin -------------------------------------
-EX_MEMBER, EX_MEMBER_BAND, EX_EMPTY_SLACK, EX_EMPTY_OPEN, EX_ITER_LIMIT, EX_FAILURE, EX_NOT_NEAR = 0, 1, 2, 3, 4, 5, 6
+EX_MEMBER,EX_MEMBER_BAND, EX_EMPTY_SLACK, EX_EMPTY_OPEN, EX_ITER_LIMIT, EX_FAILURE, EX_NOT_NEAR = 0, 1, 2, 3, 4, 5, 6
 EX_MAX_N, EX_MAX_D, PROD_MAX_K = 511, 255, 32
 
 

@@ -270,6 +270,10 @@ class QPNetOptions:
     # not in the reference, which builds every node's whole solution graph (src/qp_processing.jl:193-198, :231): the recipes a
     # node's graph is built from, per sub-piece combination (level_batch.solution_pieces).  None = every recipe, as the reference.
     max_pieces: Optional[int] = 64
+    # not in the reference, whose `project` hands a parent the facets of a projected piece (src/sets.jl:501-523): prune the bounds
+    # of every solution-graph piece that its other bounds imply before the pieces go up a level (polyhedra.irredundant_batch).
+    # False = the pieces as the elimination leaves them.
+    irredundant_pieces: bool = False
 
 
 class QPNet:
