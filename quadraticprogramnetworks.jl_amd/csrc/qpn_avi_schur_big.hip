@@ -1154,7 +1154,38 @@ __global__ __launch_bounds__(TPB, 2) void schur_big_bpp(AviBatchArgs a, SchurBig
         const bool bad_s = act && st == 0 && (s < li - tol_s || s > ui + tol_s);
         const bool bad = bad_l || bad_s;
         const int nb = sb_block_sum_i(bad ? 1 : 0, B, tid);
-        if (nb == 0) { solved = true; break; }
+        if (nb == 0) {
+            // One step of iterative refinement on the final set, with the residual of the active rows taken from the ROWS of S
+            // as stage A computed them: t_i - c_i - sum_a S(i, a) lambda_a.  The rounds above read S(:, A) as rows A and factor
+            // the lower triangle, i.e. they solve with a symmetrised S; the computed S = Ad (H^-1 Ad') is symmetric only to
+            // cond(H) eps, and the read-back x = -(W lambda + h) uses the W of the same factorisation, so the active rows of
+            // Ad x + B w miss their bounds by |S - S'| |lambda| unless lambda solves the system of S itself (found by
+            // tests/test_gpu_solve_reference.py at cond(H) = 1e4: 10 x the error of Lemke's pivots on the same S and c).
+            // The factor of the symmetrised S_AA is the preconditioner: one step contracts by |S - S'| / |S|.
+            if (k > 0) {
+                __syncthreads();
+                if (st != 0) {
+                    const double *row = Tb + (size_t)tid * ld;
+                    double r0 = (st == 1 ? li : ui) - ci, r1 = 0.0;
+                    int a0 = 0;
+                    for (; a0 + 2 <= k; a0 += 2) {
+                        r0 = fma(-row[B.aidx[a0]], B.rhs[a0], r0);
+                        r1 = fma(-row[B.aidx[a0 + 1]], B.rhs[a0 + 1], r1);
+                    }
+                    if (a0 < k) r0 = fma(-row[B.aidx[a0]], B.rhs[a0], r0);
+                    acc0 = r0 + r1;
+                }
+                __syncthreads();                // (every active thread has read the whole of lambda_A)
+                if (st != 0) B.rhs[mypos] = acc0;
+                if (tid >= k && tid < kp) B.rhs[tid] = 0.0;
+                __syncthreads();
+                if (wave == 0) tc_solve(tiles, B.rhs, T, lane);
+                __syncthreads();
+                if (st != 0) lam += B.rhs[mypos];
+            }
+            solved = true;
+            break;
+        }
         bool flip = bad;
         if (nb < nbest) { nbest = nb; patience = 3; }
         else if (patience > 0) patience--;
