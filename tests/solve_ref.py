@@ -81,13 +81,9 @@ def _exact_residual(K, y, rhs):
     return s + c
 
 
-def solve_reference(Q, R, qd, A, B, l, u, w, active_hint):
-    """-> (z* = [x; lam] as longdouble, info).  info: resid (longdouble residual of the KKT system over |rhs|_inf), cond (cond_2 of
-    the KKT matrix), min_slack (least distance of an inactive row from its bounds), min_lam (least |multiplier| of an active row),
-    ok / why (the certificate's verdict)."""
-    side = np.asarray(active_hint, dtype=np.int8)
-    n, m = Q.shape[0], A.shape[0]
-    K, rhs, rows = kkt_system(Q, R, qd, A, B, l, u, w, side)
+def refined_solve(K, rhs):
+    """K y = rhs for the fp64 matrix K and the longdouble rhs: a float64 LU plus iterative refinement with longdouble residuals
+    -> (y as longdouble, its residual over |rhs|_inf: at most RESID_BOUND, asserted)."""
     Kl = _ld(K)
     lu = sla.lu_factor(K)
     y = _ld(sla.lu_solve(lu, np.asarray(rhs, dtype=np.float64)))
@@ -119,6 +115,17 @@ def solve_reference(Q, R, qd, A, B, l, u, w, active_hint):
             f"refinement stalled at {best_r:.2e} |rhs| (cond {np.linalg.cond(K):.1e})"
         best_r = min(best_r, RESID_BOUND)
     assert best_r <= RESID_BOUND, f"refinement stalled at {best_r:.2e} |rhs| (cond {np.linalg.cond(K):.1e})"
+    return best, best_r
+
+
+def solve_reference(Q, R, qd, A, B, l, u, w, active_hint):
+    """-> (z* = [x; lam] as longdouble, info).  info: resid (longdouble residual of the KKT system over |rhs|_inf), cond (cond_2 of
+    the KKT matrix), min_slack (least distance of an inactive row from its bounds), min_lam (least |multiplier| of an active row),
+    ok / why (the certificate's verdict)."""
+    side = np.asarray(active_hint, dtype=np.int8)
+    n, m = Q.shape[0], A.shape[0]
+    K, rhs, rows = kkt_system(Q, R, qd, A, B, l, u, w, side)
+    best, best_r = refined_solve(K, rhs)
     z = np.zeros(n + m, dtype=LD)
     z[:n] = best[:n]
     z[n + rows] = best[n:]

@@ -73,6 +73,7 @@ def test_box_mcp_with_warm_start(engine, oracle):
         rc = oracle.solve_avi_batch(M, q, l, u, z0=z0)
         rg = engine.solve_avi_batch(colmajor(M), q, l, u, z0=z0)
         _cmp(rg, rc, f"box N={N}")
+        assert np.all(rc["status"] == 1)                    # (random_box_mcp is strongly monotone: every item is solvable)
 
 
 def test_reference_form_equals_reduced_form(engine, oracle):

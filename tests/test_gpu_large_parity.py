@@ -66,6 +66,7 @@ def test_large_box_mcp_and_device_path(engine, oracle):
     rg = engine.solve_avi_batch(t(colmajor(M)), t(q), t(l), t(u), z0=t(z0))
     torch.cuda.synchronize()
     _cmp({k: v.cpu().numpy() for k, v in rg.items()}, rc, "large box device")
+    assert np.all(rc["status"] == 1)                        # (random_box_mcp is strongly monotone: every item is solvable)
 
 
 def test_robust_avoid_deepest_pool_reference_form(engine, oracle):
