@@ -514,6 +514,44 @@ int qpn_interior_members(qpn_ctx *ctx, int32_t batch, int32_t r, int32_t d, cons
 int qpn_members_outside(qpn_ctx *ctx, int32_t pairs, int32_t d, int32_t rj, const double *Aj, const double *lj, const double *uj,
                         int32_t Bj, const double *X, int32_t Bi, const int32_t *pi, const int32_t *pj, double t, uint8_t *out, int mem);
 
+/* ---- inner-node records made on the device from a pool of child pieces (src/qp_processing.jl:62-66, :183-187: a node's
+ *      constraint stack is [base; child pieces]) ----------
+ * An ITEM is one parent under one choice of its children's pieces.  Its record is made from inputs that go up once:
+ *   static store, `parents` parents of one shape, in the layout of qpn_solve_nodes: sQd [parents][n0][n0], sR [parents][ps][n0],
+ *     sqd [parents][n0], sAd [parents][n0][mb] (row t, column j at j * mb + t), sB [parents][ps][mb], sl, su [parents][mb],
+ *     mb_true [parents] int32: the parent's own base row count (<= mb, the common padded count);
+ *   piece pool: piece_desc [pieces][4] int32 = (row0, rows, c, off): the piece's rows are pl, pu [row0 .. row0 + rows) (of
+ *     pool_rows) and its coefficients pA [off .. off + rows * c) (of pool_words), row-major over its own c columns;
+ *   column maps: map k is map_data [map_off[k] .. map_off[k + 1]) (map_off [maps + 1], map_data [map_words], int32), one entry
+ *     per piece column: j in [0, n0) = decision column j (Ad), n0 + k with k < p = parameter column k (B), -1 = the parent does
+ *     not read that variable (legal only under coefficients that are all zero).  No column may be named twice by one map;
+ *   items: parent_of [items], piece_of, map_of [items][QPN_PARENT_SLOTS] int32 (piece_of -1 = empty slot).
+ * The stack of an item is its parent's mb_true base rows, then the rows of its slots in slot order; parameter columns
+ * k >= ps of a base row are zero.
+ *   form 0 (the verify form): n = n0;  Qd = sQd, R = [sR, 0], qd = sqd, rows 0 .. T-1 the stack, rows T .. m-1 inert
+ *     (0'x in (-inf, +inf)).  `ne` is ignored.
+ *   form 1 (the solve form, equality rows in the free block): E = the stack rows with finite l == u, in order, I = the others,
+ *     in order; n = n0 + ne with ne = |E| for EVERY item of the call;  Qd = [[sQd, -A_E'], [A_E, 0]], R = [R; B_E],
+ *     qd = [sqd; -l_E], rows [A_I 0], B_I, l_I, u_I, then inert rows up to m.  The negation is applied to every entry of A_E'
+ *     and l_E (a zero becomes -0.0); every other structural zero is +0.0.  No other arithmetic is done.
+ * Outputs, every word written: Qd [items][n][n], R [items][p][n], qd [items][n], Ad [items][n][m], B [items][p][m], l, u
+ * [items][m] (the layout of qpn_solve_nodes / qpn_verify_nodes, which take them in place in device mode), err [items] int32:
+ *   0 good;  1 a parent, piece or map index (or a piece's range in the pool, or mb_true) out of range;  2 a map that is not as
+ *   long as its piece has columns, has an entry outside [-1, n0 + p) or names a column twice;  3 a -1 map entry under a
+ *   non-zero coefficient;  4 more rows than m (or than 1024 in the stack);  5 form 1: |E| != ne.  The lowest code that applies.
+ * A bad item's record is its parent's static blocks (zeros when the parent index itself is bad) over all-inert rows, the ne
+ * extra free variables zero.  Nothing is read through a bad index.  Host mode: a bad item gives QPN_ERR_ARG (err is still
+ * written); device mode: QPN_OK, err tells.  Limits: n + m <= 1024 (QPN_ERR_SIZE), p >= 1.  items == 0 succeeds.
+ * level_batch.assemble_parent_records_host is the numpy twin and the normative statement: every output is bit-equal to it. */
+#define QPN_PARENT_SLOTS 8
+int qpn_assemble_parent_nodes(qpn_ctx *ctx, int32_t items, int32_t form, int32_t n0, int32_t ne, int32_t m, int32_t p,
+                              int32_t parents, int32_t mb, int32_t ps, const double *sQd, const double *sR, const double *sqd,
+                              const double *sAd, const double *sB, const double *sl, const double *su, const int32_t *mb_true,
+                              int32_t pieces, const int32_t *piece_desc, int32_t pool_rows, int32_t pool_words, const double *pA,
+                              const double *pl, const double *pu, int32_t maps, const int32_t *map_off, int32_t map_words,
+                              const int32_t *map_data, const int32_t *parent_of, const int32_t *piece_of, const int32_t *map_of,
+                              double *Qd, double *R, double *qd, double *Ad, double *B, double *l, double *u, int32_t *err, int mem);
+
 /* ---- batched LP solver for the polyhedral primitives: `exemplar`, `isempty`, `issubset`, `implicit_bounds` (src/sets.jl:591-713,
  *      :376-407; one OSQP LP per question there) ----------
  * qpn_solve_lps: `jobs` LPs over `polys` shared polyhedra {x : l <= A x <= u} of one size.  A [polys][r][d] column-major per item

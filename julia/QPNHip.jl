@@ -309,6 +309,44 @@ function members_outside(Aj::Array{Float64,3}, lj::Matrix{Float64}, uj::Matrix{F
 end
 
 """
+    assemble_parent_nodes(form, ne, m, p, sQd, sR, sqd, sAd, sB, sl, su, mb_true, piece_desc, pA, pl, pu, map_off, map_data,
+                          parent_of, piece_of, map_of) -> (Qd, R, qd, Ad, B, l, u, err)
+
+qpn_assemble_parent_nodes: the records of inner nodes, an item being one parent under one choice of its children's pieces (the
+constraint stack [base; child pieces], src/qp_processing.jl:62-66), from a static store sQd [n0, n0, parents], sR [n0, ps,
+parents], sqd [n0, parents], sAd [mb, n0, parents], sB [mb, ps, parents], sl, su [mb, parents], mb_true [parents]; a piece pool
+piece_desc [4, pieces] = (row0, rows, c, off) with pA (row-major per piece), pl, pu; column maps map_off [maps + 1], map_data;
+and items parent_of [items], piece_of, map_of [8, items].  Every index and offset is 0-BASED, as the ABI has it (piece_of -1 = an
+empty slot, a map entry -1 = a variable the parent does not read).  form 0: the verify form (n = n0); form 1: the solve form,
+the ne equality rows in the free block (n = n0 + ne).  Qd [n, n, items], R [n, p, items], qd [n, items], Ad [m, n, items],
+B [m, p, items], l, u [m, items]; a bad item is an error (include/qpn_hip.h lists the err words).
+"""
+function assemble_parent_nodes(form::Integer, ne::Integer, m::Integer, p::Integer, sQd::Array{Float64,3}, sR::Array{Float64,3},
+                               sqd::Matrix{Float64}, sAd::Array{Float64,3}, sB::Array{Float64,3}, sl::Matrix{Float64},
+                               su::Matrix{Float64}, mb_true::Vector{Int32}, piece_desc::Matrix{Int32}, pA::Vector{Float64},
+                               pl::Vector{Float64}, pu::Vector{Float64}, map_off::Vector{Int32}, map_data::Vector{Int32},
+                               parent_of::Vector{Int32}, piece_of::Matrix{Int32}, map_of::Matrix{Int32})
+    n0, parents = size(sqd)
+    ps = size(sR, 2); mb = size(sl, 1)
+    items = length(parent_of); pieces = size(piece_desc, 2); maps = length(map_off) - 1
+    (size(piece_desc, 1) == 4 && size(piece_of) == (8, items) && size(map_of) == (8, items) && maps >= 0) ||
+        error("assemble_parent_nodes: inconsistent shapes")
+    n = n0 + (form == 0 ? 0 : ne)
+    Qd = zeros(n, n, items); R = zeros(n, p, items); qd = zeros(n, items); Ad = zeros(m, n, items); B = zeros(m, p, items)
+    l = zeros(m, items); u = zeros(m, items); err = zeros(Int32, items)
+    rc = ccall((:qpn_assemble_parent_nodes, LIB), Cint,
+               (Ptr{Cvoid}, Int32, Int32, Int32, Int32, Int32, Int32, Int32, Int32, Int32, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int32}, Int32, Ptr{Int32}, Int32, Int32, Ptr{Cdouble},
+                Ptr{Cdouble}, Ptr{Cdouble}, Int32, Ptr{Int32}, Int32, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Cdouble},
+                Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int32}, Cint),
+               ctx(), items, form, n0, ne, m, p, parents, mb, ps, sQd, sR, sqd, sAd, sB, sl, su, mb_true, pieces, piece_desc,
+               length(pl), length(pA), pA, pl, pu, maps, map_off, length(map_data), map_data, parent_of, piece_of, map_of,
+               Qd, R, qd, Ad, B, l, u, err, QPN_MEM_HOST)
+    rc == 0 || error("qpn_assemble_parent_nodes failed ($rc)")
+    (Qd, R, qd, Ad, B, l, u, err)
+end
+
+"""
     solve_lps(A, l, u, poly_of; cost=nothing, obj_row=nothing, obj_sign=nothing, max_iters=0)
         -> (status, x, obj, lambda, ray, iters)
 

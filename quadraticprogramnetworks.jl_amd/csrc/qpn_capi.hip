@@ -1810,6 +1810,59 @@ int qpn_members_outside(qpn_ctx *ctx, int32_t pairs, int32_t d, int32_t rj, cons
     return st.finish();
 }
 
+// ---- inner-node records from a static store, a piece pool and column maps (qpn_parent.hip) ----------------------------------
+int qpn_assemble_parent_nodes(qpn_ctx *ctx, int32_t items, int32_t form, int32_t n0, int32_t ne, int32_t m, int32_t p,
+                              int32_t parents, int32_t mb, int32_t ps, const double *sQd, const double *sR, const double *sqd,
+                              const double *sAd, const double *sB, const double *sl, const double *su, const int32_t *mb_true,
+                              int32_t pieces, const int32_t *piece_desc, int32_t pool_rows, int32_t pool_words, const double *pA,
+                              const double *pl, const double *pu, int32_t maps, const int32_t *map_off, int32_t map_words,
+                              const int32_t *map_data, const int32_t *parent_of, const int32_t *piece_of, const int32_t *map_of,
+                              double *Qd, double *R, double *qd, double *Ad, double *B, double *l, double *u, int32_t *err, int mem)
+{
+    if (!ctx) return QPN_ERR_ARG;
+    Stage st(ctx, mem, "qpn_assemble_parent_nodes");
+    if (items < 0 || (form != 0 && form != 1) || n0 <= 0 || ne < 0 || m < 0 || p < 1 || parents < 0 || mb < 0 || ps < 0 || pieces < 0 ||
+        pool_rows < 0 || pool_words < 0 || maps < 0 || map_words < 0)
+        return fail_arg(ctx, st.who, "bad sizes");
+    if (form == 0) ne = 0;
+    const int64_t n64 = (int64_t)n0 + ne;
+    if (n64 + m > qpn_avi_max_n()) {
+        ctx->last_error = std::string(st.who) + ": n0 + ne + m <= 1024 in ABI v1";
+        return QPN_ERR_SIZE;
+    }
+    if (int rc = st.check()) return rc;
+    if (items == 0) return QPN_OK;
+    const size_t I = (size_t)items, n = (size_t)n64, P = (size_t)parents;
+    if (!parent_of || !piece_of || !map_of || !Qd || !R || !qd || !err || (m && (!Ad || !B || !l || !u)) ||
+        (parents && (!sQd || !sqd || !mb_true || (ps && !sR) || (mb && (!sAd || !sl || !su || (ps && !sB))))) ||
+        (pieces && !piece_desc) || (pool_rows && (!pl || !pu)) || (pool_words && !pA) || (maps && !map_off) || (map_words && !map_data))
+        return fail_arg(ctx, st.who, "null pointer");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    ParentArgs a{};
+    a.items = items; a.form = form; a.n0 = n0; a.ne = ne; a.m = m; a.p = p; a.parents = parents; a.mb = mb; a.ps = ps;
+    a.pieces = pieces; a.pool_rows = pool_rows; a.pool_words = pool_words; a.maps = maps; a.map_words = map_words;
+    st.in(a.sQd, sQd, P * n0 * n0 * 8); st.in(a.sR, sR, P * ps * n0 * 8); st.in(a.sqd, sqd, P * n0 * 8);
+    st.in(a.sAd, sAd, P * n0 * mb * 8); st.in(a.sB, sB, P * ps * mb * 8); st.in(a.sl, sl, P * mb * 8); st.in(a.su, su, P * mb * 8);
+    st.in(a.mb_true, mb_true, P * 4);
+    st.in(a.piece_desc, piece_desc, (size_t)pieces * 16); st.in(a.pA, pA, (size_t)pool_words * 8);
+    st.in(a.pl, pl, (size_t)pool_rows * 8); st.in(a.pu, pu, (size_t)pool_rows * 8);
+    st.in(a.map_off, map_off, maps ? ((size_t)maps + 1) * 4 : 0); st.in(a.map_data, map_data, (size_t)map_words * 4);
+    st.in(a.parent_of, parent_of, I * 4); st.in(a.piece_of, piece_of, I * QPN_PARENT_SLOTS * 4);
+    st.in(a.map_of, map_of, I * QPN_PARENT_SLOTS * 4);
+    st.scratch(a.map_bad, (size_t)maps);
+    st.out(a.Qd, Qd, I * n * n * 8); st.out(a.R, R, I * p * n * 8); st.out(a.qd, qd, I * n * 8);
+    st.out(a.Ad, Ad, I * n * m * 8); st.out(a.B, B, I * p * m * 8); st.out(a.l, l, I * m * 8); st.out(a.u, u, I * m * 8);
+    st.out(a.err, err, I * 4);
+    int rc = st.begin();
+    if (rc != QPN_OK) return rc;
+    HIPCHK(ctx, qpn_launch_parent_records(a, ctx->stream));
+    if ((rc = st.finish()) != QPN_OK) return rc;
+    // host arrays: the kernel's own verdicts are the check (nothing was read through a bad index)
+    for (size_t i = 0; st.host && i < I; ++i)
+        if (err[i]) return fail_arg(ctx, st.who, "bad item (see err)");
+    return QPN_OK;
+}
+
 // ---- batched LP solver (qpn_lp.hip) ----------------------------------------------------------------------------------------
 void qpn_lp_default_opts(qpn_lp_opts *o)
 {

@@ -324,6 +324,25 @@ hipError_t qpn_launch_members_extract(int32_t batch, int32_t d, int32_t N, const
 hipError_t qpn_launch_members_outside(int32_t pairs, int32_t d, int32_t rj, const double *Aj, const double *lj, const double *uj, int32_t Bj,
                                       const double *X, int32_t Bi, const int32_t *pi, const int32_t *pj, double t, uint8_t *out, hipStream_t s);
 #define QPN_MEMBERS_MAX_ROWS 4096
+// qpn_parent.hip: inner-node records from a static store, a pool of child pieces and column maps (qpn_assemble_parent_nodes).
+// Pointers are device pointers; map_bad [maps] uint8 is scratch the launch fills first.
+struct ParentArgs {
+    int32_t items, form, n0, ne, m, p;
+    int32_t parents, mb, ps;
+    const double *sQd, *sR, *sqd, *sAd, *sB, *sl, *su;
+    const int32_t *mb_true;
+    int32_t pieces, pool_rows, pool_words;
+    const int32_t *piece_desc;
+    const double *pA, *pl, *pu;
+    int32_t maps, map_words;
+    const int32_t *map_off, *map_data;
+    const int32_t *parent_of, *piece_of, *map_of;
+    uint8_t *map_bad;
+    double *Qd, *R, *qd, *Ad, *B, *l, *u;
+    int32_t *err;
+};
+#define QPN_PARENT_MAX_ROWS 1024
+hipError_t qpn_launch_parent_records(const ParentArgs &a, hipStream_t s);
 
 // qpn_lp.hip: the batched LP solver (qpn_solve_lps).  Pointers are device pointers; x, obj, lam, ray, iters may be null.
 struct LpTol {                                 // the resolved tolerances of an entry's solves

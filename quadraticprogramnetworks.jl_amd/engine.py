@@ -656,6 +656,44 @@ class Engine:
                    _ptr(status), self._mem(dev))
         return x, ok, status
 
+    def assemble_parent_nodes(self, form, ne, m, p, sQc, sRc, sqd, sAc, sBc, sl, su, mb_true, piece_desc, pA, pl, pu, map_off,
+                              map_data, parent_of, piece_of, map_of):
+        """The records of inner nodes made on the device (qpn_assemble_parent_nodes; level_batch.assemble_parent_records_host
+        is its numpy twin and says what every argument is).  form 0: the verify form, 1: the solve form with ne equality rows
+        in the free block; m, p: the output's padded row and parameter counts.  Static store: sQc [P, n0, n0], sRc [P, ps, n0],
+        sqd [P, n0], sAc [P, n0, mb], sBc [P, ps, mb], sl, su [P, mb], mb_true [P] int32.  Piece pool: piece_desc [pieces, 4]
+        int32 (row0, rows, c, off), pA (flat), pl, pu.  Maps: map_off [maps + 1], map_data int32.  Items: parent_of [items],
+        piece_of, map_of [items, 8] int32.  Host arrays in: numpy out, a bad item raises; device tensors in: tensors out, err
+        tells.  Returns (Qc [items, n, n], Rc [items, p, n], qd [items, n], Ac [items, n, m], Bc [items, p, m], l, u
+        [items, m], err [items] int32)."""
+        who = "assemble_parent_nodes"
+        (dev, sQc, sRc, sqd, sAc, sBc, sl, su, pA, pl, pu, mb_true, piece_desc, map_off, map_data, parent_of, piece_of,
+         map_of) = self._stage(who, "sQc sRc sqd sAc sBc sl su pA pl pu mb_true piece_desc map_off map_data parent_of piece_of map_of",
+                               f64=(sQc, sRc, sqd, sAc, sBc, sl, su, pA, pl, pu),
+                               i32=(mb_true, piece_desc, map_off, map_data, parent_of, piece_of, map_of))
+        form, ne, m, p = int(form), int(ne) if form else 0, int(m), int(p)
+        P, n0 = (int(v) for v in sqd.shape)
+        ps, mb = int(sRc.shape[1]), int(sl.shape[1])
+        items, pieces, maps = int(parent_of.shape[0]), int(piece_desc.shape[0]), int(map_off.shape[0]) - 1
+        slots = _lib.PARENT_SLOTS
+        if tuple(sQc.shape) != (P, n0, n0) or tuple(sRc.shape) != (P, ps, n0) or tuple(sAc.shape) != (P, n0, mb) or \
+                tuple(sBc.shape) != (P, ps, mb) or tuple(sl.shape) != (P, mb) or tuple(su.shape) != (P, mb) or \
+                tuple(mb_true.shape) != (P,) or tuple(piece_desc.shape) != (pieces, 4) or maps < 0 or pA.ndim != 1 or pl.ndim != 1 or \
+                tuple(pu.shape) != tuple(pl.shape) or map_data.ndim != 1 or tuple(piece_of.shape) != (items, slots) or \
+                tuple(map_of.shape) != (items, slots) or form not in (0, 1):
+            raise QpnError(f"{who}: inconsistent shapes")
+        n = n0 + ne
+        Qo = self._alloc(dev, (items, n, n), np.float64); Ro = self._alloc(dev, (items, p, n), np.float64)
+        qo = self._alloc(dev, (items, n), np.float64); Ao = self._alloc(dev, (items, n, m), np.float64)
+        Bo = self._alloc(dev, (items, p, m), np.float64)
+        lo = self._alloc(dev, (items, m), np.float64); uo = self._alloc(dev, (items, m), np.float64)
+        err = self._alloc(dev, (items,), np.int32)
+        self._call("qpn_assemble_parent_nodes", items, form, n0, ne, m, p, P, mb, ps, _ptr(sQc), _ptr(sRc), _ptr(sqd), _ptr(sAc), _ptr(sBc),
+                   _ptr(sl), _ptr(su), _ptr(mb_true), pieces, _ptr(piece_desc), int(pl.shape[0]), int(pA.shape[0]), _ptr(pA), _ptr(pl),
+                   _ptr(pu), maps, _ptr(map_off), int(map_data.shape[0]), _ptr(map_data), _ptr(parent_of), _ptr(piece_of), _ptr(map_of),
+                   _ptr(Qo), _ptr(Ro), _ptr(qo), _ptr(Ao), _ptr(Bo), _ptr(lo), _ptr(uo), _ptr(err), self._mem(dev))
+        return Qo, Ro, qo, Ao, Bo, lo, uo, err
+
     def members_outside(self, Ajc, lj, uj, X, pi, pj, t):
         """qpn_members_outside (polyhedra.members_outside_host is its numpy twin): out [pairs] uint8, 1 where member X[pi[q]]
         violates a row of piece pj[q] by more than t.  Ajc [Bj, d, rj] (ABI layout), lj, uj [Bj, rj], X [Bi, d], pi, pj int32."""

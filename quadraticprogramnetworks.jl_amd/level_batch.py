@@ -221,6 +221,306 @@ def batch_records(recs: List[dict], row_pad: int = ROW_PAD) -> List[RecordBatch]
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# inner-node records from a static store, a pool of child pieces and column maps (qpn_assemble_parent_nodes)
+# ---------------------------------------------------------------------------------------------------------------------
+# "host": node_record -> (free_equalities) -> batch_records, per item in numpy, the records uploaded whole with every call.
+# "device": on an engine with assemble_parent_nodes, solve_level (inner single-node components) and verify_items (items with
+# children) send a static store once per net, the distinct child pieces and column maps once per call, and index arrays per
+# item; the records are made in device memory and stay there for solve_nodes / verify_nodes.
+PARENT_RECORDS_ROUTE = "host"
+PARENT_SLOTS = 8               # child pieces per item (QPN_PARENT_SLOTS)
+PARENT_MAX_ROWS = 1024         # rows of an item's constraint stack
+# err words of assemble_parent_nodes; the lowest that applies
+PR_OK, PR_BAD_INDEX, PR_BAD_MAP, PR_BAD_COLUMN, PR_BAD_ROWS, PR_BAD_EQ = 0, 1, 2, 3, 4, 5
+
+
+def assemble_parent_records_host(form, ne, m, p, sQc, sRc, sqd, sAc, sBc, sl, su, mb_true, piece_desc, pA, pl, pu, map_off, map_data,
+                                 parent_of, piece_of, map_of):
+    """The numpy twin of Engine.assemble_parent_nodes (qpn_assemble_parent_nodes) and its normative statement: the records of
+    many ITEMS, an item being one parent under one choice of its children's pieces (the constraint stack is [base; child
+    pieces], src/qp_processing.jl:62-66), in the layout of RecordBatch.
+
+      static store   per parent of one shape, ABI layout: sQc [P, n0, n0], sRc [P, ps, n0], sqd [P, n0], sAc [P, n0, mb],
+                     sBc [P, ps, mb], sl, su [P, mb]; mb_true [P]: the parent's own base row count (mb is the common padded one)
+      piece pool     piece_desc [pieces, 4] = (row0, rows, c, off): piece rows pl, pu [row0 : row0 + rows], coefficients
+                     pA [off : off + rows * c] row-major over the piece's own c columns (Poly.local())
+      column maps    map k = map_data [map_off[k] : map_off[k + 1]], one entry per piece column: j < n0 the decision column (Ad),
+                     n0 + k (k < p) the parameter column (B), -1 a variable the parent does not read
+      items          parent_of [items], piece_of / map_of [items, PARENT_SLOTS] (piece_of -1: empty slot)
+
+    form 0 is node_record as RecordBatch stacks it (base rows, the slots' rows in slot order, inert rows up to m; parameter
+    columns from ps on are zero); form 1 is free_equalities of it, E = the stack rows with finite l == u, which must number ne
+    for every item.  Returns (Qc [items, n, n], Rc [items, p, n], qd [items, n], Ac [items, n, m], Bc [items, p, m], l, u
+    [items, m], err [items] int32 (PR_*)), n = n0 + ne.  A bad item's record is its parent's Qd, R, qd over inert rows (zeros
+    when the parent index is bad)."""
+    f64 = lambda a: np.asarray(a, dtype=np.float64)
+    i64 = lambda a: np.asarray(a, dtype=np.int64)
+    sQc, sRc, sqd, sAc, sBc, sl, su, pA, pl, pu = (f64(a) for a in (sQc, sRc, sqd, sAc, sBc, sl, su, pA, pl, pu))
+    mb_true, piece_desc, map_off, map_data, parent_of, piece_of, map_of = (i64(a) for a in (mb_true, piece_desc, map_off, map_data, parent_of,
+                                                                                          piece_of, map_of))
+    form, m, p = int(form), int(m), int(p)
+    ne = int(ne) if form else 0
+    P, n0 = sqd.shape
+    ps, mb = sRc.shape[1], sl.shape[1]
+    items, pieces, maps = parent_of.shape[0], piece_desc.shape[0], map_off.shape[0] - 1
+    n, pk = n0 + ne, min(p, ps)
+    Qc = np.zeros((items, n, n)); Rc = np.zeros((items, p, n)); qd = np.zeros((items, n))
+    Ac = np.zeros((items, n, m)); Bc = np.zeros((items, p, m))
+    l = np.full((items, m), -INF); u = np.full((items, m), INF)
+    err = np.zeros(items, np.int32)
+    # a map is judged once: its range inside map_data, every entry in [-1, n0 + p), no column named twice
+    map_bad = np.zeros(max(maps, 0), bool)
+    for k in range(maps):
+        a, b = int(map_off[k]), int(map_off[k + 1])
+        if a < 0 or b < a or b > map_data.size:
+            map_bad[k] = True
+            continue
+        mv = map_data[a:b]
+        named = mv[mv >= 0]
+        map_bad[k] = bool(np.any((mv < -1) | (mv >= n0 + p))) or np.unique(named).size != named.size
+    for b in range(items):
+        pa = int(parent_of[b])
+        pa_ok = 0 <= pa < P
+        any1, any2, mbt = not pa_ok, False, 0
+        if pa_ok:
+            mbt = int(mb_true[pa])
+            if mbt < 0 or mbt > mb:
+                any1, mbt = True, 0
+        over = mbt > PARENT_MAX_ROWS
+        if over:
+            mbt = 0
+        T, slots = mbt, []
+        for k in range(PARENT_SLOTS):
+            q, rows = int(piece_of[b, k]), 0
+            if q != -1:
+                mp = int(map_of[b, k])
+                if not (0 <= q < pieces and 0 <= mp < maps):
+                    any1 = True
+                else:
+                    row0, r, c, off = (int(v) for v in piece_desc[q])
+                    if min(row0, r, c, off) < 0 or row0 + r > pl.size or off + r * c > pA.size:
+                        any1 = True
+                    elif map_bad[mp] or int(map_off[mp + 1]) - int(map_off[mp]) != c:
+                        any2 = True
+                    else:
+                        rows = r
+                        slots.append((row0, r, c, off, int(map_off[mp])))
+            over = over or rows > PARENT_MAX_ROWS - T
+            if not over:
+                T += rows
+        e = PR_BAD_INDEX if any1 else PR_BAD_MAP if any2 else PR_BAD_ROWS if over else PR_OK
+        if pa_ok:
+            Qc[b, :n0, :n0] = sQc[pa]; Rc[b, :pk, :n0] = sRc[pa, :pk]; qd[b, :n0] = sqd[pa]
+        if e == PR_OK:
+            # the stack in math layout: rows over the parent's decision and parameter columns
+            Ad = np.zeros((T, n0)); Bs = np.zeros((T, p)); ls = np.zeros(T); us = np.zeros(T)
+            Ad[:mbt] = sAc[pa][:, :mbt].T; Bs[:mbt, :pk] = sBc[pa][:pk, :mbt].T
+            ls[:mbt] = sl[pa, :mbt]; us[:mbt] = su[pa, :mbt]
+            t = mbt
+            for row0, r, c, off, mo in slots:
+                A = pA[off:off + r * c].reshape(r, c)
+                mv = map_data[mo:mo + c]
+                if np.any(A[:, mv == -1] != 0):
+                    e = PR_BAD_COLUMN
+                    break
+                dcol = (mv >= 0) & (mv < n0); pcol = mv >= n0
+                Ad[t:t + r, mv[dcol]] = A[:, dcol]
+                Bs[t:t + r, mv[pcol] - n0] = A[:, pcol]
+                ls[t:t + r] = pl[row0:row0 + r]; us[t:t + r] = pu[row0:row0 + r]
+                t += r
+        if e == PR_OK:
+            eq = np.isfinite(ls) & (ls == us) if form else np.zeros(T, bool)
+            E = np.nonzero(eq)[0]; I = np.nonzero(~eq)[0]
+            if I.size > m:
+                e = PR_BAD_ROWS
+            elif form and E.size != ne:
+                e = PR_BAD_EQ
+        if e == PR_OK:
+            Qc[b, :n0, n0:] = Ad[E].T; Qc[b, n0:, :n0] = -Ad[E]              # Qd' = [[Qd, -A_E'], [A_E, 0]], column-major
+            Rc[b, :, n0:] = Bs[E].T; qd[b, n0:] = -ls[E]
+            Ac[b, :n0, :I.size] = Ad[I].T; Bc[b, :, :I.size] = Bs[I].T
+            l[b, :I.size] = ls[I]; u[b, :I.size] = us[I]
+        err[b] = e
+    return Qc, Rc, qd, Ac, Bc, l, u, err
+
+
+def _parent_route(eng) -> bool:
+    return PARENT_RECORDS_ROUTE == "device" and callable(getattr(eng, "assemble_parent_nodes", None))
+
+
+def _movers(eng):
+    """(up, down): numpy array -> the engine's device and back; the identity for an engine that computes on the host."""
+    if getattr(eng, "device", -1) >= 0:
+        import torch
+        return (lambda a: torch.as_tensor(np.ascontiguousarray(a), device=f"cuda:{eng.device}")), (lambda a: a.cpu().numpy())
+    return (lambda a: a), np.asarray
+
+
+class DeviceRecordBatch(RecordBatch):
+    """A RecordBatch whose record arrays were made by assemble_parent_nodes and live where the engine computes (`dev`: Qc, Rc,
+    qd, Ac, Bc, l, u).  The host metadata (where, m_true, dec, par, nx) is as RecordBatch has it; the record arrays come to the
+    host only when something reads them (solution_pieces): one download fills them, bit-equal to the host route's."""
+
+    def __init__(self, where, n, m, p, nx, m_true, dec, par, dev, movers):
+        self.where = list(where)
+        self.n, self.m, self.p, self.nx = n, m, p, nx
+        self.m_true, self.dec, self.par = m_true, dec, par
+        self.dev, (self.up, self.down) = tuple(dev), movers
+        self._host = None
+        self.handle = self.handle_engine = None
+
+    def _arrays(self):
+        if self._host is None:
+            self._host = tuple(np.asarray(self.down(a)) for a in self.dev)
+        return self._host
+
+    Qc = property(lambda self: self._arrays()[0]); Rc = property(lambda self: self._arrays()[1])
+    qd = property(lambda self: self._arrays()[2]); Ac = property(lambda self: self._arrays()[3])
+    Bc = property(lambda self: self._arrays()[4]); l = property(lambda self: self._arrays()[5])
+    u = property(lambda self: self._arrays()[6])
+
+    def resident(self, engine):
+        return None
+
+    def solve(self, eng, w, z0):
+        res = eng.solve_nodes(*self.dev, self.up(w), z0=self.up(z0))
+        return dict(status=self.down(res["status"]), z=self.down(res["z"]))
+
+    def verify(self, eng, xd, w, tol):
+        return tuple(self.down(a) for a in eng.verify_nodes(*self.dev, self.up(xd), self.up(w), tol=tol))
+
+
+def _is_eq(l, u):
+    return np.isfinite(l) & (l == u)
+
+
+def _parent_store(qpn, n0: int, eng) -> dict:
+    """The static store of every node of the net that has children and n0 decision variables: _static's blocks in the ABI
+    layout, rows padded to the widest base, parameters to the widest list (>= 1).  Built once per net and shape, uploaded once
+    per engine."""
+    cache = qpn.__dict__.setdefault("_parent_store", {})
+    S = cache.get(n0)
+    if S is None:
+        pids = [i for i in sorted(qpn.qps) if qpn.network_edges[i] and _static(qpn, i)["dec"].size == n0]
+        sts = [_static(qpn, i) for i in pids]
+        P = len(pids)
+        mb = max([len(s["l"]) for s in sts], default=0); ps = max([1] + [s["par"].size for s in sts])
+        Qc = np.zeros((P, n0, n0)); Rc = np.zeros((P, ps, n0)); qd = np.zeros((P, n0))
+        Ac = np.zeros((P, n0, mb)); Bc = np.zeros((P, ps, mb)); l = np.full((P, mb), -INF); u = np.full((P, mb), INF)
+        for k, s in enumerate(sts):
+            mi, pi = len(s["l"]), s["par"].size
+            Qc[k] = s["Qd"].T; Rc[k, :pi] = s["R"].T; qd[k] = s["qd"]
+            Ac[k, :, :mi] = s["Ad"].T; Bc[k, :pi, :mi] = s["B"].T; l[k, :mi] = s["l"]; u[k, :mi] = s["u"]
+        S = cache[n0] = dict(index={pid: k for k, pid in enumerate(pids)}, ps=ps, mb=mb,
+                             arrays=(Qc, Rc, qd, Ac, Bc, l, u, np.array([len(s["l"]) for s in sts], np.int32)),
+                             base_eq={pid: int(np.count_nonzero(_is_eq(s["l"], s["u"]))) for pid, s in zip(pids, sts)}, on=None)
+    if S["on"] is None or S["on"][0] is not eng:
+        up, _ = _movers(eng)
+        S["on"] = (eng, tuple(up(a) for a in S["arrays"]))
+    return S
+
+
+def _parent_map(qpn, pid: int, st: dict, cols: np.ndarray):
+    """Where the piece columns `cols` (sorted variable indices) land in parent pid's record: the map, int32.  Cached per
+    (parent, column list)."""
+    cache = qpn.__dict__.setdefault("_parent_maps", {})
+    key = (pid, cols.tobytes())
+    got = cache.get(key)
+    if got is None:
+        pd, okd = _positions(st["dec"], cols)
+        pp, okp = _positions(st["par"], cols)
+        got = cache[key] = np.where(okd, pd, np.where(okp, st["dec"].size + pp, -1)).astype(np.int32)
+    return got
+
+
+def parent_batches(qpn, items, eng, form: int, row_pad: int = ROW_PAD):
+    """The record batches of `items` [(pid, [child Poly, ...])] made by eng.assemble_parent_nodes, grouped as batch_records
+    groups them (form 0) or as it groups their free_equalities (form 1): one call per record shape.  The piece pool holds every
+    distinct Poly once (by id) and goes up once, like the maps.  Returns (batches, rest): DeviceRecordBatch objects, and the
+    positions of the items left to the host route -- a piece brings a column the parent does not read (node_record's second
+    branch), no pieces, more than PARENT_SLOTS of them, or a stack beyond the entry's limits."""
+    movers = up, down = _movers(eng)
+    pool_of: Dict[int, int] = {}
+    desc, cols_of, supp_of, eq_of, pA, pl, pu = [], [], [], [], [], [], []
+    nrows = nwords = 0
+
+    def piece_index(Pc: Poly) -> int:
+        nonlocal nrows, nwords
+        q = pool_of.get(id(Pc))
+        if q is None:
+            q = pool_of[id(Pc)] = len(desc)
+            cols, A = Pc.local()
+            supp = slice(None)
+            if Pc._cols is None:
+                # a dense Poly hands block() its columns as they are: a column of -0.0 alone (a flipped row's zeros) keeps its
+                # signs there, so it comes along, outside the support node_record looks at
+                supp = cols
+                cols = np.nonzero(((Pc._A != 0) | np.signbit(Pc._A)).any(axis=0))[0].astype(np.int64)
+                A = Pc._A[:, cols]
+                supp = np.isin(cols, supp)
+            supp_of.append(supp)
+            desc.append((nrows, A.shape[0], A.shape[1], nwords))
+            cols_of.append(cols); eq_of.append(int(np.count_nonzero(_is_eq(Pc.l, Pc.u))))
+            pA.append(np.ascontiguousarray(A, dtype=np.float64).ravel()); pl.append(Pc.l); pu.append(Pc.u)
+            nrows += A.shape[0]; nwords += A.size
+        return q
+
+    map_ids: Dict[tuple, int] = {}
+    map_list: List[np.ndarray] = []
+    plan, rest = {}, []
+    groups: Dict[tuple, List[int]] = {}
+    for i, (pid, ch) in enumerate(items):
+        st = _static(qpn, pid)
+        n0 = st["dec"].size
+        if not ch or len(ch) > PARENT_SLOTS or not qpn.network_edges[pid]:
+            rest.append(i)
+            continue
+        pcs = [piece_index(Pc) for Pc in ch]
+        mps = [_parent_map(qpn, pid, st, cols_of[q]) for q in pcs]
+        T = len(st["l"]) + sum(desc[q][1] for q in pcs)
+        nE = (_parent_store(qpn, n0, eng)["base_eq"][pid] + sum(eq_of[q] for q in pcs)) if form else 0
+        mi = T - nE
+        mp = max(row_pad, -(-mi // row_pad) * row_pad) if mi else 0
+        if any(np.any(mv[supp_of[q]] < 0) for q, mv in zip(pcs, mps)) or T > PARENT_MAX_ROWS or n0 + nE + mp > 1024:
+            rest.append(i)
+            continue
+        mids = []
+        for mv in mps:
+            key = (pid, id(mv))
+            if key not in map_ids:
+                map_ids[key] = len(map_list); map_list.append(mv)
+            mids.append(map_ids[key])
+        plan[i] = (pcs, mids, mi)
+        groups.setdefault((n0 + nE, mp, n0), []).append(i)
+    batches = []
+    if groups:
+        pool = (up(np.array(desc, np.int32).reshape(-1, 4)), up(np.concatenate(pA + [np.zeros(0)])), up(np.concatenate(pl + [np.zeros(0)])),
+                up(np.concatenate(pu + [np.zeros(0)])))
+        moff = np.zeros(len(map_list) + 1, np.int32); moff[1:] = np.cumsum([mv.size for mv in map_list])
+        maps = (up(moff), up(np.concatenate(map_list + [np.zeros(0, np.int32)]).astype(np.int32)))
+    for (n, mp, n0), idx in sorted(groups.items()):
+        S = _parent_store(qpn, n0, eng)
+        sts = [_static(qpn, items[i][0]) for i in idx]
+        p = max(1, max(s["par"].size for s in sts))
+        nb = len(idx)
+        parent_of = np.array([S["index"][items[i][0]] for i in idx], np.int32)
+        piece_of = np.full((nb, PARENT_SLOTS), -1, np.int32); map_of = np.zeros((nb, PARENT_SLOTS), np.int32)
+        for t, i in enumerate(idx):
+            pcs, mids, _ = plan[i]
+            piece_of[t, :len(pcs)] = pcs; map_of[t, :len(mids)] = mids
+        out = eng.assemble_parent_nodes(form, n - n0, mp, p, *S["on"][1], *pool, *maps, up(parent_of), up(piece_of), up(map_of))
+        err = np.asarray(down(out[7]))
+        if err.any():
+            raise RuntimeError(f"assemble_parent_nodes: bad items {np.nonzero(err)[0][:4].tolist()} (err {err[err != 0][:4].tolist()})")
+        dec = np.stack([s["dec"] for s in sts]).astype(np.int64)
+        par = np.full((nb, p), -1, dtype=np.int64)
+        for t, s in enumerate(sts):
+            par[t, :s["par"].size] = s["par"]
+        batches.append(DeviceRecordBatch(idx, n, mp, p, n0, np.array([plan[i][2] for i in idx], dtype=np.int64), dec, par, out[:7], movers))
+    return batches, rest
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # the level's pool split into connected components
 # ---------------------------------------------------------------------------------------------------------------------
 def components(qpn, players: Sequence[int], assign: Optional[Dict[int, Poly]] = None) -> List[List[int]]:
@@ -349,7 +649,13 @@ def solve_level(qpn, players: Sequence[int], x, assign: Optional[Dict[int, Poly]
         work += [(b, True) for b in batches_u if take[id(b)].any()]
     elif leaf:
         inner = sorted(inner + leaf)
-    if inner:
+    if inner and not reference_form and _parent_route(eng):
+        # the records are made on the device (parent_batches); the few items it leaves go the host way below
+        its = [(i, [assign[j] for j in sorted(qpn.network_edges[i]) if j in assign]) for i in inner]
+        dev_batches, rest = parent_batches(qpn, its, eng, 1)
+        work += [(b, False) for b in dev_batches]
+        work += [(b, False) for b in batch_records([free_equalities(node_record(qpn, *its[t])) for t in rest])]
+    elif inner:
         recs = [node_record(qpn, i, [assign[j] for j in sorted(qpn.network_edges[i]) if j in assign]) for i in inner]
         if reference_form:
             work += [(r, None) for r in recs]
@@ -365,6 +671,8 @@ def solve_level(qpn, players: Sequence[int], x, assign: Optional[Dict[int, Poly]
         h = b.resident(eng) if static else None
         if h is not None:
             res = h.solve(w, want=("z", "resid", "pivots"))
+        elif isinstance(b, DeviceRecordBatch):
+            res = b.solve(eng, w, z0)
         else:
             res = eng.solve_nodes(b.Qc, b.Rc, b.qd, b.Ac, b.Bc, b.l, b.u, w, z0=z0)
         st = np.asarray(res["status"])
@@ -453,6 +761,16 @@ def verify_items(qpn, items, x, engine, tol=1e-4, check_convexity=False):
     all_leaf = len(leaf_ids) == len(items)
     if all_leaf:
         recs, batches = _leaf_batches(qpn, list(leaf_ids), eng)
+    elif _parent_route(eng):
+        # the records are made on the device (parent_batches): the host keeps an item's pid; the items left over go the host way
+        batches, rest = parent_batches(qpn, items, eng, 0)
+        recs = [dict(pid=pid) for pid, _ in items]
+        for i in rest:
+            recs[i] = node_record(qpn, *items[i])
+        host_batches = batch_records([recs[i] for i in rest])
+        for b in host_batches:
+            b.where = [rest[k] for k in b.where]
+        batches = batches + host_batches
     else:
         recs = [node_record(qpn, pid, ch) for pid, ch in items]
         batches = batch_records(recs)
@@ -462,6 +780,8 @@ def verify_items(qpn, items, x, engine, tol=1e-4, check_convexity=False):
         h = b.resident(eng) if all_leaf else None
         if h is not None:
             sol, lam, path = h.verify(xd, w, tol=tol)
+        elif isinstance(b, DeviceRecordBatch):
+            sol, lam, path = b.verify(eng, xd, w, tol)
         else:
             sol, lam, path = eng.verify_nodes(b.Qc, b.Rc, b.qd, b.Ac, b.Bc, b.l, b.u, xd, w, tol=tol)
         sol = np.asarray(sol); lam = np.asarray(lam); path = np.asarray(path)
