@@ -505,7 +505,23 @@ int qpn_recipe_filter(qpn_ctx *ctx, int32_t pieces, int32_t rows, int32_t N, con
  *   size (Aj [Bj][rj][d] column-major, lj, uj [Bj][rj]): out[q] = 1 when a row has a.x < l - t or a.x > u + t, a.x summed over
  *   ascending columns (acc = acc + a * x[c], no contraction).  Order the pairs by piece where many members meet one piece: 16
  *   consecutive pairs over one piece share one read of it.  Host index arrays out of range: QPN_ERR_ARG; device ones: that
- *   pair answers 1 ("not settled here"). */
+ *   pair answers 1 ("not settled here").
+ * qpn_members_outside_lists: the same question list by list, the pairs enumerated on the device.  One call covers one pack of
+ *   Bj second pieces of one size and the members of dimension d, with ok [Bi] as qpn_interior_members wrote it (a member with
+ *   ok == 0 refutes nothing).  list_ptr [lists + 1] and list_mem [list_ptr[lists]] are a CSR: position s of list a is row
+ *   list_mem[list_ptr[a] + s] of X, -1 = that piece has no member; a list names ALL its pieces in list order, those whose own
+ *   matrices sit in another pack included.  list_of [Bj]: the list of piece j; self_pos [Bj]: its own position there;
+ *   word_ptr [Bj + 1] (int64): piece j owns the words bits [word_ptr[j], word_ptr[j + 1]), at least ceil(k / 32) of them for a
+ *   list of k.  Every word of every segment is written: bit (s & 31) of word (s >> 5) of the segment is 1 when s != self_pos[j],
+ *   the member at position s exists and is ok, and it violates a row of piece j by more than t (the arithmetic of
+ *   qpn_members_outside); every other bit is 0.  undecided [Bj] = the number of positions s != self_pos[j] of the list with bit 0:
+ *   the pairs still to be put to an LP.  Host mode: list_ptr and word_ptr start at 0 and are monotone, every index is in range
+ *   (list_of, self_pos, list_mem in [-1, Bi)) and every segment long enough, else QPN_ERR_ARG and nothing is launched.  Device
+ *   mode: list_ptr and word_ptr lie inside their buffers (the caller's duty: list_mem has list_ptr[lists] entries, bits
+ *   word_ptr[Bj] words); a piece with a bad list_of, self_pos or too short a segment gets its whole segment 0 and undecided =
+ *   max(k - 1, 0), or 0 when the list itself is bad, and nothing is read through the bad index; a list_mem entry outside
+ *   [-1, Bi) answers 1 for that position (other than self_pos), the convention of qpn_members_outside.  1 <= d, 1 <= rj <= 4096,
+ *   Bi * d < 2^31 (QPN_ERR_SIZE beyond); Bj == 0 or lists == 0 succeeds (lists == 0: every segment 0, undecided 0). */
 int qpn_assemble_interior_nodes(qpn_ctx *ctx, int32_t batch, int32_t r, int32_t d, const double *A, const double *l, const double *u,
                                 double delta, int32_t ne, int32_t nlo, int32_t nhi, double *Qd, double *qd, double *Ad, double *lo,
                                 double *uo, uint8_t *flag, int mem);
@@ -513,6 +529,10 @@ int qpn_interior_members(qpn_ctx *ctx, int32_t batch, int32_t r, int32_t d, cons
                          double delta, int32_t ne, int32_t nlo, int32_t nhi, double *x_out, uint8_t *ok, int32_t *status, int mem);
 int qpn_members_outside(qpn_ctx *ctx, int32_t pairs, int32_t d, int32_t rj, const double *Aj, const double *lj, const double *uj,
                         int32_t Bj, const double *X, int32_t Bi, const int32_t *pi, const int32_t *pj, double t, uint8_t *out, int mem);
+int qpn_members_outside_lists(qpn_ctx *ctx, int32_t d, int32_t rj, const double *Aj, const double *lj, const double *uj, int32_t Bj,
+                              const double *X, const uint8_t *ok, int32_t Bi, int32_t lists, const int32_t *list_ptr,
+                              const int32_t *list_mem, const int32_t *list_of, const int32_t *self_pos, const int64_t *word_ptr,
+                              double t, uint32_t *bits, int32_t *undecided, int mem);
 
 /* ---- inner-node records made on the device from a pool of child pieces (src/qp_processing.jl:62-66, :183-187: a node's
  *      constraint stack is [base; child pieces]) ----------

@@ -309,6 +309,41 @@ function members_outside(Aj::Array{Float64,3}, lj::Matrix{Float64}, uj::Matrix{F
 end
 
 """
+    members_outside_lists(Aj, lj, uj, X, ok, list_ptr, list_mem, list_of, self_pos; t=1e-5) -> (bits, undecided, word_ptr)
+
+qpn_members_outside_lists: every member of a list against every piece of the same list, the pairs enumerated on the device.  One
+pack of second pieces (Aj [rj, d, Bj], lj, uj [rj, Bj]); members X [d, Bi] with the flags ok [Bi] of interior_members; the lists
+as a CSR: list_ptr [lists + 1] (0-based offsets, as the ABI has them) and list_mem (1-based columns of X, 0 = that piece has no
+member); list_of [Bj] (1-based list of piece j) and self_pos [Bj] (its own 1-based position there).  Piece j owns the words
+bits[word_ptr[j] + 1 : word_ptr[j + 1]] (word_ptr is made here, ceil(k / 32) words for a list of k): bit (s - 1) & 31 of word
+(s - 1) >> 5 is 1 when the member at position s != self_pos[j] exists, is ok and violates a row of piece j by more than t.
+undecided[j] counts the positions other than its own whose bit is 0: the pairs still to be put to an LP.
+"""
+function members_outside_lists(Aj::Array{Float64,3}, lj::Matrix{Float64}, uj::Matrix{Float64}, X::Matrix{Float64}, ok::Vector{UInt8},
+                               list_ptr::Vector{<:Integer}, list_mem::Vector{<:Integer}, list_of::Vector{<:Integer},
+                               self_pos::Vector{<:Integer}; t::Float64 = 1e-5)
+    rj, d, Bj = size(Aj)
+    size(X, 1) == d || error("members_outside_lists: X must have d rows")
+    Bi = size(X, 2)
+    length(ok) == Bi || error("members_outside_lists: one ok flag per member")
+    lists = length(list_ptr) - 1
+    lp = Int32.(list_ptr); lm = Int32.(list_mem .- 1); lo = Int32.(list_of .- 1); sp = Int32.(self_pos .- 1)
+    word_ptr = zeros(Int64, Bj + 1)
+    for j in 1:Bj
+        1 <= list_of[j] <= lists || error("members_outside_lists: list_of out of range")
+        k = lp[list_of[j] + 1] - lp[list_of[j]]
+        word_ptr[j + 1] = word_ptr[j] + cld(k, 32)
+    end
+    bits = zeros(UInt32, word_ptr[end]); undecided = zeros(Int32, Bj)
+    rc = ccall((:qpn_members_outside_lists, LIB), Cint,
+               (Ptr{Cvoid}, Int32, Int32, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Int32, Ptr{Cdouble}, Ptr{UInt8}, Int32, Int32,
+                Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int64}, Cdouble, Ptr{UInt32}, Ptr{Int32}, Cint),
+               ctx(), d, rj, Aj, lj, uj, Bj, X, ok, Bi, lists, lp, lm, lo, sp, word_ptr, t, bits, undecided, QPN_MEM_HOST)
+    rc == 0 || error("qpn_members_outside_lists failed ($rc)")
+    (bits, undecided, word_ptr)
+end
+
+"""
     assemble_parent_nodes(form, ne, m, p, sQd, sR, sqd, sAd, sB, sl, su, mb_true, piece_desc, pA, pl, pu, map_off, map_data,
                           parent_of, piece_of, map_of) -> (Qd, R, qd, Ad, B, l, u, err)
 

@@ -23,7 +23,8 @@ ABI_SYMBOLS = (
     "qpn_verify_nodes_h", "qpn_pool_size", "qpn_assemble_pools", "qpn_local_pieces", "qpn_recipes_from_masks",
     "qpn_recipes_batch", "qpn_reduced_pieces", "qpn_project_pieces", "qpn_convexity_nodes", "qpn_recipes_batch_range", "qpn_finish_pieces",
     "qpn_multiplier_vertices", "qpn_recipe_filter",
-    "qpn_assemble_interior_nodes", "qpn_interior_members", "qpn_members_outside", "qpn_assemble_parent_nodes",
+    "qpn_assemble_interior_nodes", "qpn_interior_members", "qpn_members_outside", "qpn_members_outside_lists",
+    "qpn_assemble_parent_nodes",
     "qpn_lp_default_opts", "qpn_lp_kernel_class", "qpn_solve_lps", "qpn_issubset_pairs", "qpn_implicit_bounds",
     "qpn_exemplar_polys", "qpn_exemplar_products", "qpn_irredundant_bounds",
 )
@@ -165,6 +166,8 @@ def load_library():
                                          vp, vp, vp, C.c_int]
     lib.qpn_members_outside.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, C.c_int32, vp, C.c_int32, vp, vp, C.c_double,
                                         vp, C.c_int]
+    lib.qpn_members_outside_lists.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, vp, C.c_int32, vp, vp, C.c_int32, C.c_int32, vp, vp, vp,
+                                              vp, vp, C.c_double, vp, vp, C.c_int]
     lib.qpn_assemble_parent_nodes.argtypes = [vp] + [C.c_int32] * 9 + [vp] * 8 + [C.c_int32, vp, C.c_int32, C.c_int32, vp, vp, vp,
                                                                                     C.c_int32, vp, C.c_int32, vp, vp, vp, vp] + [vp] * 8 + [C.c_int]
     lib.qpn_lp_default_opts.argtypes = [C.POINTER(LpOpts)]

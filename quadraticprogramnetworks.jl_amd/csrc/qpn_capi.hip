@@ -1810,6 +1810,58 @@ int qpn_members_outside(qpn_ctx *ctx, int32_t pairs, int32_t d, int32_t rj, cons
     return st.finish();
 }
 
+int qpn_members_outside_lists(qpn_ctx *ctx, int32_t d, int32_t rj, const double *Aj, const double *lj, const double *uj, int32_t Bj,
+                              const double *X, const uint8_t *ok, int32_t Bi, int32_t lists, const int32_t *list_ptr,
+                              const int32_t *list_mem, const int32_t *list_of, const int32_t *self_pos, const int64_t *word_ptr,
+                              double t, uint32_t *bits, int32_t *undecided, int mem)
+{
+    if (!ctx) return QPN_ERR_ARG;
+    Stage st(ctx, mem, "qpn_members_outside_lists");
+    if (Bj < 0 || Bi < 0 || lists < 0) return fail_arg(ctx, st.who, "bad sizes");
+    if (d < 1 || rj < 1 || rj > QPN_MEMBERS_MAX_ROWS || (int64_t)Bi * d >= ((int64_t)1 << 31)) {
+        ctx->last_error = std::string(st.who) + ": 1 <= d, 1 <= rj <= 4096 and Bi * d < 2^31 in ABI v1";
+        return QPN_ERR_SIZE;
+    }
+    if (int rc = st.check()) return rc;
+    if (Bj == 0) return QPN_OK;
+    if (!Aj || !lj || !uj || !list_ptr || !list_of || !self_pos || !word_ptr || !undecided || (Bi > 0 && (!X || !ok)))
+        return fail_arg(ctx, st.who, "null pointer");
+    // host index arrays are checked here, all of them; device ones by the kernel, item by item
+    int64_t M = 0, Wn = 0;
+    if (st.host) {
+        if (list_ptr[0] != 0 || word_ptr[0] != 0) return fail_arg(ctx, st.who, "list_ptr and word_ptr start at 0");
+        for (int32_t a = 0; a < lists; ++a)
+            if (list_ptr[a + 1] < list_ptr[a]) return fail_arg(ctx, st.who, "list_ptr is not monotone");
+        M = list_ptr[lists];
+        if (M > 0 && !list_mem) return fail_arg(ctx, st.who, "null pointer");
+        for (int64_t e = 0; e < M; ++e)
+            if (list_mem[e] < -1 || list_mem[e] >= Bi) return fail_arg(ctx, st.who, "list_mem entry out of range");
+        for (int32_t j = 0; j < Bj; ++j) {
+            if (word_ptr[j + 1] < word_ptr[j]) return fail_arg(ctx, st.who, "word_ptr is not monotone");
+            if (lists == 0) continue;                          // (no lists: every segment is written 0)
+            if (list_of[j] < 0 || list_of[j] >= lists) return fail_arg(ctx, st.who, "list_of out of range");
+            const int64_t k = (int64_t)list_ptr[list_of[j] + 1] - list_ptr[list_of[j]];
+            if (self_pos[j] < 0 || self_pos[j] >= k) return fail_arg(ctx, st.who, "self_pos out of range");
+            if (word_ptr[j + 1] - word_ptr[j] < (k + 31) / 32) return fail_arg(ctx, st.who, "segment of bits shorter than its list");
+        }
+        Wn = word_ptr[Bj];
+        if (Wn > 0 && !bits) return fail_arg(ctx, st.who, "null pointer");
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const double *dA, *dl, *du, *dX; const uint8_t *dok; const int32_t *dlp, *dlm, *dlo, *dsp; const int64_t *dwp;
+    uint32_t *dbits; int32_t *dund;
+    st.in(dA, Aj, (size_t)Bj * d * rj * 8); st.in(dl, lj, (size_t)Bj * rj * 8); st.in(du, uj, (size_t)Bj * rj * 8);
+    st.in(dX, X, (size_t)Bi * d * 8); st.in(dok, ok, (size_t)Bi);
+    st.in(dlp, list_ptr, ((size_t)lists + 1) * 4); st.in(dlm, list_mem, (size_t)M * 4);
+    st.in(dlo, list_of, (size_t)Bj * 4); st.in(dsp, self_pos, (size_t)Bj * 4); st.in(dwp, word_ptr, ((size_t)Bj + 1) * 8);
+    st.out(dbits, bits, (size_t)Wn * 4); st.out(dund, undecided, (size_t)Bj * 4);
+    int rc = st.begin();
+    if (rc != QPN_OK) return rc;
+    HIPCHK(ctx, qpn_launch_members_outside_lists(d, rj, dA, dl, du, Bj, dX, dok, Bi, lists, dlp, dlm, dlo, dsp, dwp, t, dbits, dund,
+                                                 ctx->stream));
+    return st.finish();
+}
+
 // ---- inner-node records from a static store, a piece pool and column maps (qpn_parent.hip) ----------------------------------
 int qpn_assemble_parent_nodes(qpn_ctx *ctx, int32_t items, int32_t form, int32_t n0, int32_t ne, int32_t m, int32_t p,
                               int32_t parents, int32_t mb, int32_t ps, const double *sQd, const double *sR, const double *sqd,

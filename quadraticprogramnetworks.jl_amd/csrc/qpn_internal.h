@@ -323,6 +323,11 @@ hipError_t qpn_launch_members_extract(int32_t batch, int32_t d, int32_t N, const
                                       double *x, uint8_t *ok, hipStream_t s);
 hipError_t qpn_launch_members_outside(int32_t pairs, int32_t d, int32_t rj, const double *Aj, const double *lj, const double *uj, int32_t Bj,
                                       const double *X, int32_t Bi, const int32_t *pi, const int32_t *pj, double t, uint8_t *out, hipStream_t s);
+size_t qpn_members_lists_lds(int32_t rj, int32_t d);
+hipError_t qpn_launch_members_outside_lists(int32_t d, int32_t rj, const double *Aj, const double *lj, const double *uj, int32_t Bj,
+                                            const double *X, const uint8_t *ok, int32_t Bi, int32_t lists, const int32_t *list_ptr,
+                                            const int32_t *list_mem, const int32_t *list_of, const int32_t *self_pos,
+                                            const int64_t *word_ptr, double t, uint32_t *bits, int32_t *undecided, hipStream_t s);
 #define QPN_MEMBERS_MAX_ROWS 4096
 // qpn_parent.hip: inner-node records from a static store, a pool of child pieces and column maps (qpn_assemble_parent_nodes).
 // Pointers are device pointers; map_bad [maps] uint8 is scratch the launch fills first.

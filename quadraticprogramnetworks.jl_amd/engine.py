@@ -40,7 +40,7 @@ def _torch_dt(dt):
     return {np.dtype(np.int32): torch.int32, np.dtype(np.float64): torch.float64, np.dtype(np.uint8): torch.uint8}[np.dtype(dt)]
 
 
-_DTYPES = dict(f64="float64", u8="uint8", i32="int32")      # Engine._stage's groups: the ABI's element types, by numpy / torch name
+_DTYPES = dict(f64="float64", u8="uint8", i32="int32", i64="int64")      # Engine._stage's groups: the ABI's element types, by numpy / torch name
 
 
 def _is_dev(x):
@@ -170,7 +170,8 @@ class Engine:
 
     def _alloc(self, dev, shape, dtype):
         if dev:
-            tdt = {np.float64: torch.float64, np.int32: torch.int32, np.uint8: torch.uint8, np.int64: torch.int64}[dtype]
+            tdt = {np.float64: torch.float64, np.int32: torch.int32, np.uint8: torch.uint8, np.int64: torch.int64,
+                   np.uint32: torch.uint32}[dtype]
             return torch.empty(shape, dtype=tdt, device=f"cuda:{self.device}")
         return np.empty(shape, dtype=dtype)
 
@@ -706,6 +707,38 @@ class Engine:
         self._call("qpn_members_outside", pairs, d, rj, _ptr(Ajc), _ptr(lj), _ptr(uj), Bj, _ptr(X), int(X.shape[0]), _ptr(pi), _ptr(pj),
                    float(t), _ptr(out), self._mem(dev))
         return out
+
+    def members_outside_lists(self, Ajc, lj, uj, X, ok, list_ptr, list_mem, list_of, self_pos, word_ptr, t):
+        """qpn_members_outside_lists (polyhedra.members_outside_lists_host is its numpy twin): every member of a list against
+        every piece of it, the pairs enumerated on the device.  One pack of second pieces Ajc [Bj, d, rj] (ABI layout), lj, uj
+        [Bj, rj]; members X [Bi, d] with their flags ok [Bi] uint8; the lists as a CSR, list_ptr [lists + 1] and list_mem int32
+        (rows of X, -1 = no member); list_of, self_pos [Bj] int32: the list of piece j and its own position there; word_ptr
+        [Bj + 1] int64: piece j owns the words [word_ptr[j], word_ptr[j + 1]) of bits, ceil(k / 32) for a list of k.
+        Returns (bits [word_ptr[Bj]] uint32, undecided [Bj] int32): bit s of a piece's segment = the member at position s
+        refutes "piece s is a subset of piece j"; undecided = the positions other than the piece's own whose bit is 0.
+        Host arrays in: numpy out, and an index out of range raises; device tensors in: tensors out, a bad item answers as the
+        header says (list_ptr and word_ptr themselves are checked here in either mode: they bound the buffers)."""
+        who = "members_outside_lists"
+        dev, Ajc, lj, uj, X, ok, list_ptr, list_mem, list_of, self_pos, word_ptr = self._stage(
+            who, "Ajc lj uj X ok list_ptr list_mem list_of self_pos word_ptr", f64=(Ajc, lj, uj, X), u8=(ok,),
+            i32=(list_ptr, list_mem, list_of, self_pos), i64=(word_ptr,))
+        Bj, d, rj = (int(v) for v in Ajc.shape)
+        Bi, lists = int(X.shape[0]), int(list_ptr.shape[0]) - 1
+        if tuple(lj.shape) != (Bj, rj) or tuple(uj.shape) != (Bj, rj) or X.ndim != 2 or int(X.shape[1]) != d or \
+                tuple(ok.shape) != (Bi,) or list_ptr.ndim != 1 or lists < 0 or list_mem.ndim != 1 or tuple(list_of.shape) != (Bj,) or \
+                tuple(self_pos.shape) != (Bj,) or tuple(word_ptr.shape) != (Bj + 1,):
+            raise QpnError(f"{who}: inconsistent shapes")
+        # the two offset arrays say how far the kernel reads list_mem and writes bits: never taken on trust
+        for name, ptr, limit in (("list_ptr", list_ptr, int(list_mem.shape[0])), ("word_ptr", word_ptr, None)):
+            bad = bool(ptr[0] != 0) or (ptr.shape[0] > 1 and bool((ptr[1:] < ptr[:-1]).any())) or \
+                (limit is not None and int(ptr[-1]) > limit)
+            if bad:
+                raise QpnError(f"{who}: {name} must start at 0, not decrease" + (" and end inside list_mem" if limit is not None else ""))
+        bits = self._alloc(dev, (int(word_ptr[-1]),), np.uint32)
+        undecided = self._alloc(dev, (Bj,), np.int32)
+        self._call("qpn_members_outside_lists", d, rj, _ptr(Ajc), _ptr(lj), _ptr(uj), Bj, _ptr(X), _ptr(ok), Bi, lists, _ptr(list_ptr),
+                   _ptr(list_mem), _ptr(list_of), _ptr(self_pos), _ptr(word_ptr), float(t), _ptr(bits), _ptr(undecided), self._mem(dev))
+        return bits, undecided
 
     # -- the LP solver of the polyhedral primitives --------------------------------------------------------------
     def default_lp_opts(self) -> LpOpts:

@@ -305,6 +305,8 @@ def issubset_batch_chunked(pairs, engine, tol=1e-6, chunk_bytes=None):
 
 
 PAIR_CHUNK = 1 << 22             # (member, piece) pairs of one members_outside call of remove_subsets_many, about
+REFUTE_ROUTE = "pairs"           # how remove_subsets_many puts members to pieces on an engine: "pairs" = members_outside over pair
+                                 # lists made here; "lists" = members_outside_lists, the pairs enumerated on the device (opt-in)
 
 
 def _on_device(engine):
@@ -373,6 +375,9 @@ def _refuted_by_members(comp, flat, starts, engine, tol):
     """remove_subsets_many's refutation matrices on an engine with `members_outside`: the members stay where the solve left
     them, every (rows, columns) pack of second pieces is ONE members_outside call over the pack as interior_members got it, and
     only the verdicts come to the host.  -> {list a: refuted [k, k] bool}."""
+    if REFUTE_ROUTE not in ("pairs", "lists"):
+        raise ValueError(f"polyhedra.REFUTE_ROUTE: unknown route {REFUTE_ROUTE!r}")
+    by_lists = REFUTE_ROUTE == "lists" and _has(engine, "members_outside_lists")
     groups = _interior_member_groups(flat, engine)
     nflat = len(flat)
     grp_of = np.zeros(nflat, np.int64); pos_of = np.zeros(nflat, np.int64); xrow = np.zeros(nflat, np.int64)
@@ -383,13 +388,16 @@ def _refuted_by_members(comp, flat, starts, engine, tol):
         d = int(grp["x"].shape[1])
         grp_of[idx] = g; pos_of[idx] = np.arange(len(idx)); xrow[idx] = rows_d.get(d, 0) + np.arange(len(idx))
         rows_d[d] = rows_d.get(d, 0) + len(idx)
-        ok_h[idx] = _to_host(grp["ok"]).astype(bool)
+        if not by_lists:                                    # (the lists route leaves the flags where they are)
+            ok_h[idx] = _to_host(grp["ok"]).astype(bool)
         X_of.setdefault(d, []).append(grp["x"])
     dev = _on_device(engine)
     if dev:
         import torch
     cat = (lambda xs: xs[0] if len(xs) == 1 else torch.cat(xs)) if dev else (lambda xs: xs[0] if len(xs) == 1 else np.concatenate(xs))
     X_of = {d: cat(xs) for d, xs in X_of.items()}
+    if by_lists:
+        return _refuted_by_lists(comp, starts, engine, tol, groups, xrow, X_of, cat)
     refuted = {a: np.zeros((len(trips), len(trips)), bool) for a, trips in enumerate(comp) if trips is not None}
 
     def ask(blocks):
@@ -434,6 +442,90 @@ def _refuted_by_members(comp, flat, starts, engine, tol):
     return refuted
 
 
+def _refuted_matrix(k, cols, segs):
+    """refuted [k, k] bool of a list of k from the segments of `bits` of the pieces `cols` that left something undecided
+    (segs[c]: the ceil(k / 32) words of piece cols[c]): column j = its unpacked bits; a piece that left nothing undecided
+    is refuted by every other piece's member."""
+    refuted = ~np.eye(k, dtype=bool)
+    for j, seg in zip(cols, segs):
+        refuted[:, j] = np.unpackbits(np.ascontiguousarray(seg, dtype="<u4").view(np.uint8), bitorder="little")[:k].astype(bool)
+    return refuted
+
+
+def _refuted_by_lists(comp, starts, engine, tol, groups, xrow, X_of, cat):
+    """_refuted_by_members on an engine with `members_outside_lists` (REFUTE_ROUTE = "lists"): the lists themselves go up, once
+    per level -- per member dimension a CSR of all lists (the rows of their pieces' members, sum of k integers) and the members'
+    ok flags, left where interior_members wrote them -- then ONE call per pack of second pieces.  Only `undecided` comes to
+    the host unconditionally: a list none of whose pieces left a pair undecided holds no subset and gets no matrix (None);
+    for the others the segments of the pieces that left something undecided come down (_refuted_matrix).
+    -> {list a: refuted [k, k] bool, or None = every pair refuted}."""
+    dev = _on_device(engine)
+    if dev:
+        import torch
+        up = lambda v: torch.as_tensor(v, device=f"cuda:{engine.device}")
+    else:
+        up = lambda v: v
+    OK_of = {}
+    for grp in groups:
+        OK_of.setdefault(int(grp["x"].shape[1]), []).append(grp["ok"])
+    OK_of = {d: cat(oks) for d, oks in OK_of.items()}
+    # the lists of one member dimension, as a CSR over the rows of that dimension's X; every piece has a row (ok says
+    # whether it holds a member), so no entry is -1
+    alist = [a for a, trips in enumerate(comp) if trips is not None]
+    klen = {a: len(comp[a]) for a in alist}
+    nflat = sum(klen.values())
+    list_a = np.zeros(nflat, np.int64)                      # the list of a flat piece
+    for a in alist:
+        list_a[starts[a]:starts[a] + klen[a]] = a
+    csr, local = {}, {}
+    for d in X_of:
+        mine = [a for a in alist if comp[a][0][0].shape[1] == d]
+        ptr = np.zeros(len(mine) + 1, np.int64)
+        ptr[1:] = np.cumsum([klen[a] for a in mine])
+        mem = np.concatenate([xrow[starts[a]:starts[a] + klen[a]] for a in mine]).astype(np.int32) if mine else np.zeros(0, np.int32)
+        for n, a in enumerate(mine):
+            local[a] = n
+        csr[d] = (up(ptr.astype(np.int32)), up(mem))
+    need = {}                                               # list a -> [(piece j of it, its words)] where something is undecided
+    open_lists = set()
+    for grp in groups:
+        idx = np.asarray(grp["idx"], dtype=np.int64)
+        Ac = grp["Ac"]
+        d = int(Ac.shape[1])
+        la = list_a[idx]
+        kk = np.array([klen[a] for a in la.tolist()], np.int64)
+        words = -(-kk // 32)
+        wptr = np.zeros(len(idx) + 1, np.int64); wptr[1:] = np.cumsum(words)
+        list_of = np.array([local[a] for a in la.tolist()], np.int32)
+        self_pos = (idx - np.array([starts[a] for a in la.tolist()], np.int64)).astype(np.int32)
+        bits, und = engine.members_outside_lists(Ac, grp["l"], grp["u"], X_of[d], OK_of[d], *csr[d], up(list_of), up(self_pos), up(wptr),
+                                                 10 * tol)
+        und = _to_host(und)
+        hit = np.nonzero(und > 0)[0]
+        if not len(hit):
+            continue
+        # only the segments of the pieces that left something undecided come down
+        widx = np.concatenate([np.arange(wptr[p], wptr[p + 1]) for p in hit])
+        if dev:
+            got = bits.view(torch.int32)[torch.as_tensor(widx, device=bits.device)].cpu().numpy().view(np.uint32)
+        else:
+            got = np.asarray(bits)[widx]
+        q0 = 0
+        for p in hit.tolist():
+            a = int(la[p])
+            need.setdefault(a, []).append((int(self_pos[p]), got[q0:q0 + int(words[p])]))
+            q0 += int(words[p])
+            open_lists.add(a)
+    refuted = {}
+    for a in alist:
+        if a not in open_lists:
+            refuted[a] = None
+            continue
+        cols, segs = zip(*need[a])
+        refuted[a] = _refuted_matrix(klen[a], cols, segs)
+    return refuted
+
+
 def remove_subsets_many(lists, engine, tol=1e-6, prefilter=True):
     """`remove_subsets` (src/sets.jl:889-902) for the solution graphs of ALL nodes of a level at once (src/algorithm.jl:84
     applies it to every node's S).  Every list is first brought down to the columns its pieces touch (a large net's pieces are
@@ -468,6 +560,9 @@ def remove_subsets_many(lists, engine, tol=1e-6, prefilter=True):
             continue
         k = len(trips)
         have = [i for i in range(k) if member and member[starts[a] + i] is not None]
+        if a in refuted_of and refuted_of[a] is None:       # (the lists route: every pair of this list refuted, no matrix)
+            sub[a] = None
+            continue
         refuted = refuted_of.get(a, np.zeros((k, k), bool))  # refuted[i, j]: P1 = piece i has a member outside P2 = piece j
         if have:
             pts = np.stack([member[starts[a] + i] for i in have], axis=1)   # [d, members]
@@ -488,6 +583,9 @@ def remove_subsets_many(lists, engine, tol=1e-6, prefilter=True):
     for a, polys in enumerate(lists):
         if comp[a] is None:
             out.append(polys)
+            continue
+        if sub[a] is None:
+            out.append(list(polys))
             continue
         k = len(polys)
         is_subset = np.zeros(k, bool)

@@ -1,5 +1,5 @@
 """The numpy twins of the polyhedral entries, the normative statements of the kernels' methods (the kernels are bit-equal to them):
-solve_lps_host, issubset_pairs_host, implicit_bounds_host, irredundant_bounds_host, exemplar_polys_host, exemplar_products_host, interior_member_records and members_outside_host,
+solve_lps_host, issubset_pairs_host, implicit_bounds_host, irredundant_bounds_host, exemplar_polys_host, exemplar_products_host, interior_member_records, members_outside_host and members_outside_lists_host,
 with the entries' result codes, defined here once (_lib.py and polyhedra.py import them).  Numpy alone, loadable as a stand-alone
 file: tests/golden/lp_twin_record.json pins it across commits.  The front ends that pack, route and call an engine are polyhedra.py.
 """
@@ -943,3 +943,82 @@ def members_outside_host(Ajc, lj, uj, X, pi, pj, t):
         with np.errstate(invalid="ignore"):
             out[s:s + step] = np.any((acc < lj[qj] - t) | (acc > uj[qj] + t), axis=1)
     return out
+
+
+def members_outside_lists_host(Ajc, lj, uj, X, ok, list_ptr, list_mem, list_of, self_pos, word_ptr, t, strict=False):
+    """The numpy twin of Engine.members_outside_lists (qpn_members_outside_lists) and its normative statement: every member of a
+    list against every piece of the same list, said by the lists.  One pack of second pieces Ajc [Bj, d, rj], lj, uj [Bj, rj];
+    members X [Bi, d] with flags ok [Bi]; list_ptr [lists + 1] and list_mem form a CSR (position s of list a is row
+    list_mem[list_ptr[a] + s] of X, -1 = no member); list_of, self_pos [Bj]: the list of piece j and its own position there;
+    word_ptr [Bj + 1]: piece j owns the words [word_ptr[j], word_ptr[j + 1]) of bits, at least ceil(k / 32) for a list of k.
+    -> (bits [word_ptr[Bj]] uint32, undecided [Bj] int32).  Bit (s & 31) of word (s >> 5) of piece j's segment is 1 when
+    s != self_pos[j], the member at position s exists and is ok, and members_outside_host says it lies outside piece j -- the
+    verdicts ARE members_outside_host's, on the enumerated pairs -- and every other bit of the segment is 0; undecided[j] counts
+    the positions s != self_pos[j] of the list whose bit is 0.
+    Bad items, strict=False (the entry's device mode): a piece whose list_of or self_pos is out of range, or whose segment is
+    shorter than its list needs (or not inside bits at all: then nothing of it is written), has its whole segment 0 and
+    undecided = max(k - 1, 0), or 0 when the list itself is bad (list_of out of range, or its list_ptr entries decreasing or
+    outside list_mem); a list_mem entry outside [-1, Bi) answers 1 for its position, other than self_pos (the convention of
+    qpn_members_outside: not settled here).  strict=True (host mode): any of these raises ValueError, as do list_ptr or
+    word_ptr that do not start at 0 or decrease."""
+    Ajc = np.asarray(Ajc, dtype=np.float64)
+    X = np.asarray(X, dtype=np.float64); ok = np.asarray(ok).astype(bool)
+    list_ptr = np.asarray(list_ptr, dtype=np.int64); list_mem = np.asarray(list_mem, dtype=np.int64)
+    list_of = np.asarray(list_of, dtype=np.int64); self_pos = np.asarray(self_pos, dtype=np.int64)
+    word_ptr = np.asarray(word_ptr, dtype=np.int64)
+    Bj, Bi, lists = Ajc.shape[0], X.shape[0], len(list_ptr) - 1
+    M, W = int(list_ptr[-1]), int(word_ptr[-1]) if Bj else 0
+
+    def bad(what):
+        if strict:
+            raise ValueError(f"members_outside_lists: {what}")
+
+    if strict:
+        if list_ptr[0] != 0 or word_ptr[0] != 0:
+            bad("list_ptr and word_ptr start at 0")
+        if np.any(np.diff(list_ptr) < 0) or np.any(np.diff(word_ptr) < 0):
+            bad("list_ptr or word_ptr is not monotone")
+        if np.any((list_mem[:M] < -1) | (list_mem[:M] >= Bi)):
+            bad("list_mem entry out of range")
+    bits = np.zeros(max(W, 0), np.uint32)
+    undecided = np.zeros(Bj, np.int32)
+    pi, pj, at = [], [], []                               # the enumerated pairs; (piece, positions) of each run of them
+    kept = {}
+    for j in range(Bj):
+        w0, w1 = int(word_ptr[j]), int(word_ptr[j + 1])
+        seg_ok = 0 <= w0 <= w1 <= W
+        a, k = int(list_of[j]), -1
+        if 0 <= a < lists:
+            p0, p1 = int(list_ptr[a]), int(list_ptr[a + 1])
+            if 0 <= p0 <= p1 <= M:
+                k = p1 - p0
+        elif lists:
+            bad("list_of out of range")
+        sp = int(self_pos[j])
+        if lists and k >= 0 and not 0 <= sp < k:
+            bad("self_pos out of range")
+        if lists and k >= 0 and seg_ok and w1 - w0 < -(-k // 32):
+            bad("segment of bits shorter than its list")
+        if not seg_ok or k < 0 or not 0 <= sp < k or w1 - w0 < -(-k // 32):
+            undecided[j] = max(k - 1, 0)
+            continue
+        mem = list_mem[p0:p1]
+        pos = np.arange(k)
+        inr = (mem >= 0) & (mem < Bi)
+        use = inr & (pos != sp)
+        use[use] = ok[mem[use]]
+        kept[j] = (pos != sp) & ((mem < -1) | (mem >= Bi))
+        pi.append(mem[use]); pj.append(np.full(int(use.sum()), j, np.int64)); at.append((j, pos[use]))
+    out = members_outside_host(Ajc, lj, uj, X, np.concatenate(pi), np.concatenate(pj), t) if pi else np.zeros(0, np.uint8)
+    q0 = 0
+    for j, pos in at:
+        k = len(kept[j])
+        flag = kept[j].copy()
+        flag[pos] = out[q0:q0 + len(pos)].astype(bool)
+        q0 += len(pos)
+        nwk = -(-k // 32)
+        padded = np.zeros(32 * nwk, bool); padded[:k] = flag
+        w0 = int(word_ptr[j])
+        bits[w0:w0 + nwk] = np.packbits(padded, bitorder="little").view("<u4")
+        undecided[j] = k - 1 - int(flag.sum())            # (the own position's bit is never set)
+    return bits, undecided
