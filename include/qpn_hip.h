@@ -816,6 +816,46 @@ int qpn_exemplar_products(qpn_ctx *ctx, int32_t d, int32_t rows, const double *A
                           double point_tol, double tol, double slack_cap, const qpn_lp_opts *opts, uint8_t *near, uint8_t *empty,
                           int32_t *how, double *eps, double *x, int32_t *row, double *lambda, int32_t *iters, int mem);
 
+/* qpn_intersection_trees: the lazy enumeration of `combine` (src/qp_processing.jl:260-291): IntersectionRoot's tree walk
+ * (src/intersection.jl:66-105, :116-138), in which a node of depth t is the intersection of one piece from each of the first t unions
+ * and the subtree under an empty prefix is never visited -- for `trees` trees of one depth L over ONE pool of rows, breadth first.
+ * The pool is that of qpn_exemplar_products, unchanged: d, rows, A [rows][d] ROW-major, l, u, open_lo, open_hi [rows] (NULL: closed),
+ * pieces, piece_row [pieces + 1].  list_ptr [trees L + 1] and list_mem [members] int32 form a CSR: list g L + t holds the pieces of
+ * union t of tree g, in the reference's order; its last list_red[g L + t] members are complement pieces (the redzone, :123).  point
+ * [points][d], point_of [trees]: the tree's point; both NULL: no closure test.  cap: the most tuples any frontier or any depth's
+ * candidates may hold (the caller groups trees by (d, L), as it groups products by (d, n)).
+ * Outputs: leaves [cap][L] int32 (pool pieces), leaf_tree, leaf_how [cap] int32 (QPN_EX_*), of which the first n_leaves [1] int64 are
+ * written;  tree_leaves [trees] int32;  tested, alive, unanswered [L] int64, one count per depth;  overflow [1] int32.
+ * Method (polyhedra.intersection_trees_host is its numpy twin and the normative statement; every output is equal to it):
+ * (0) near: a member of a list stays when every row of its piece passes the closure test of qpn_exemplar_products (b) at the tree's
+ * point -- ascending columns, acc = acc + a * p, no contraction, closed relations whatever the flags; the order of the rest is kept.
+ * near(product) is the AND over its rows, so this is the per-product test bit for bit, and no job takes a point afterwards.
+ * (1) expand: F_0 is one empty tuple per tree; for t = 1 .. L the candidates are, for every tuple of F_(t-1) in order and every near
+ * member of list t in order, the tuple with that member appended; at t = L a candidate whose members are all complement pieces is not
+ * formed (prefixes of complement pieces alone are: a later slot may hold a solution piece).  A candidate is one job of
+ * qpn_exemplar_products (c): its tuple as factors, -1 from slot t on, n = its rows.  It is kept when empty == 0; ITER_LIMIT and
+ * FAILURE are no answer: the candidate stays alive and is counted in unanswered[t - 1].  F_t is the kept candidates in candidate
+ * order; tested[t - 1] and alive[t - 1] are the two counts.  (2) the leaves are F_L in order: by tree, then lexicographic in list
+ * positions -- the order `iterate` yields them in.  (3) a depth that forms more than cap candidates ends the call: overflow = that
+ * depth (1-based), tested of that depth = the count it formed, later counts 0, n_leaves = 0; the call still returns QPN_OK and the
+ * caller falls back.  (4) 1 <= d <= 255, 2 <= L <= 32, 1 <= cap <= 2^22 (QPN_ERR_SIZE beyond); every member piece has at least one
+ * row, and per tree the longest pieces of its lists add up to at most 511 rows.  Host arrays: an index out of range, a CSR that is
+ * not ascending within list_mem, a member piece of no rows: QPN_ERR_ARG; a sum beyond 511: QPN_ERR_SIZE; nothing is launched.
+ * Device arrays: a tree with such a list, a list_red outside its list or a point_of outside [0, points) forms no candidate and
+ * answers tree_leaves = -1, the other trees are not affected, and nothing is read through the bad index.  The lists must not overlap
+ * in list_mem: list_ptr ascends as a whole within [0, members], and where a device list_ptr does not, EVERY tree of the call answers
+ * tree_leaves = -1.
+ * The jobs run on the kernels of qpn_exemplar_products, one launch per row count n that a depth's candidates have; the host reads one
+ * small header back per depth (the histogram of n and the counts), nothing per launch or per tree.  max_iters <= 0: as there, by
+ * the n of each job.  trees == 0 succeeds with every count 0. */
+int qpn_intersection_trees(qpn_ctx *ctx, int32_t d, int32_t rows, const double *A, const double *l, const double *u,
+                           const uint8_t *open_lo, const uint8_t *open_hi, int32_t pieces, const int32_t *piece_row, int32_t trees,
+                           int32_t L, int32_t members, const int32_t *list_ptr, const int32_t *list_mem, const int32_t *list_red,
+                           int32_t points, const double *point, const int32_t *point_of, double point_tol, double tol, double slack_cap,
+                           const qpn_lp_opts *opts, int32_t cap, int32_t *leaves, int32_t *leaf_tree, int32_t *leaf_how,
+                           int64_t *n_leaves, int32_t *tree_leaves, int64_t *tested, int64_t *alive, int64_t *unanswered,
+                           int32_t *overflow, int mem);
+
 #ifdef __cplusplus
 }
 #endif

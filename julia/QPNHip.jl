@@ -596,6 +596,49 @@ function exemplar_products(A::Matrix{Float64}, l::Vector{Float64}, u::Vector{Flo
     (near, empty, how, eps, x, row, lam, iters)
 end
 
+"""
+    intersection_trees(A, l, u, piece_row, L, list_ptr, list_mem, list_red, cap; open_lo=nothing, open_hi=nothing, point=nothing,
+                       point_of=nothing, point_tol=1e-6, tol=1e-2, slack_cap=1.0, max_iters=0)
+        -> (leaves, leaf_tree, leaf_how, tree_leaves, tested, alive, unanswered, overflow)
+
+qpn_intersection_trees: IntersectionRoot's walk (src/intersection.jl:66-105, :116-138) for `trees` trees of one depth L over the pool
+of exemplar_products (A [d, rows], l, u, flags, piece_row 0-based), breadth first, the subtree under an empty prefix never formed.
+list_ptr [trees L + 1] (0-based offsets) and list_mem (0-based pieces) are a CSR: list g L + t (0-based) holds the pieces of union t
+of tree g in order, its last list_red[g L + t] members being complement pieces.  point [d, points] and point_of [trees] (0-based), or
+both nothing.  cap: the most tuples a depth may hold.  leaves [L, n_leaves] (0-based pieces), leaf_tree and leaf_how [n_leaves], in
+the order `iterate` yields them; tree_leaves [trees]; tested, alive, unanswered [L]; overflow: 0, or the depth that formed more
+than cap candidates (no leaves then: ask again with a larger cap, or enumerate the products).  2 <= L <= 32, d <= 255, cap <= 2^22.
+"""
+function intersection_trees(A::Matrix{Float64}, l::Vector{Float64}, u::Vector{Float64}, piece_row::Vector{Int32}, L::Integer,
+                            list_ptr::Vector{Int32}, list_mem::Vector{Int32}, list_red::Vector{Int32}, cap::Integer;
+                            open_lo::Union{Nothing,AbstractVector} = nothing, open_hi::Union{Nothing,AbstractVector} = nothing,
+                            point::Union{Nothing,Matrix{Float64}} = nothing, point_of::Union{Nothing,Vector{Int32}} = nothing,
+                            point_tol::Float64 = 1e-6, tol::Float64 = 1e-2, slack_cap::Float64 = 1.0, max_iters::Integer = 0)
+    d, rows = size(A)
+    L >= 1 && length(list_red) % L == 0 && length(list_ptr) == length(list_red) + 1 || error("intersection_trees: inconsistent shapes")
+    trees = length(list_red) ÷ L
+    length(l) == rows && length(u) == rows && length(piece_row) >= 1 || error("intersection_trees: inconsistent shapes")
+    (point === nothing) == (point_of === nothing) || error("intersection_trees: point and point_of go together")
+    point === nothing || (size(point, 1) == d && length(point_of) == trees) || error("intersection_trees: inconsistent shapes")
+    flags(o) = o === nothing ? nothing : (length(o) == rows || error("intersection_trees: inconsistent shapes"); Vector{UInt8}(o .!= 0))
+    olo = flags(open_lo); ohi = flags(open_hi)
+    opts = Ref((1e-9, 1e-9, 1e-9, 1e-6, Int32(max_iters), Int32(0)))      # qpn_lp_opts
+    leaves = zeros(Int32, L, max(cap, 0)); leaf_tree = zeros(Int32, max(cap, 0)); leaf_how = zeros(Int32, max(cap, 0))
+    n_leaves = zeros(Int64, 1); tree_leaves = zeros(Int32, trees)
+    tested = zeros(Int64, L); alive = zeros(Int64, L); unanswered = zeros(Int64, L); overflow = zeros(Int32, 1)
+    rc = ccall((:qpn_intersection_trees, LIB), Cint,
+               (Ptr{Cvoid}, Int32, Int32, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{UInt8}, Ptr{UInt8}, Int32, Ptr{Int32}, Int32, Int32,
+                Int32, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Int32, Ptr{Cdouble}, Ptr{Int32}, Cdouble, Cdouble, Cdouble, Ptr{Cvoid}, Int32,
+                Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int64}, Ptr{Int32}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int32}, Cint),
+               ctx(), d, rows, A, l, u, olo === nothing ? C_NULL : olo, ohi === nothing ? C_NULL : ohi, length(piece_row) - 1, piece_row,
+               trees, L, length(list_mem), list_ptr, list_mem, list_red, point === nothing ? 0 : size(point, 2),
+               point === nothing ? C_NULL : point, point_of === nothing ? C_NULL : point_of, point_tol, tol, slack_cap, opts, cap,
+               leaves, leaf_tree, leaf_how, n_leaves, tree_leaves, tested, alive, unanswered, overflow, QPN_MEM_HOST)
+    rc == 0 || error("qpn_intersection_trees failed ($rc)")
+    k = Int(n_leaves[1])
+    (leaves[:, 1:k], leaf_tree[1:k], leaf_how[1:k], tree_leaves, tested, alive, unanswered, Int(overflow[1]))
+end
+
 function verify_nodes(nodes::Nodes, xd::Matrix{Float64}, w::VecOrMat{Float64}; tol::Float64 = 1e-4)
     solution = zeros(Int32, nodes.batch); path = zeros(Int32, nodes.batch); lambda = zeros(max(nodes.m, 1), nodes.batch)
     rc = ccall((:qpn_verify_nodes_h, LIB), Cint,

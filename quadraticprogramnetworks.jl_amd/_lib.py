@@ -26,7 +26,7 @@ ABI_SYMBOLS = (
     "qpn_assemble_interior_nodes", "qpn_interior_members", "qpn_members_outside", "qpn_members_outside_lists",
     "qpn_assemble_parent_nodes",
     "qpn_lp_default_opts", "qpn_lp_kernel_class", "qpn_solve_lps", "qpn_issubset_pairs", "qpn_implicit_bounds",
-    "qpn_exemplar_polys", "qpn_exemplar_products", "qpn_irredundant_bounds",
+    "qpn_exemplar_polys", "qpn_exemplar_products", "qpn_irredundant_bounds", "qpn_intersection_trees",
 )
 
 MEM_HOST, MEM_DEVICE = 0, 1
@@ -71,7 +71,7 @@ from .polyhedra_host import (  # noqa: E402,F401
     SUBSET_HOLDS, SUBSET_BY_POINT, SUBSET_BY_OPTIMUM, SUBSET_UNBOUNDED, SUBSET_ITER_LIMIT, SUBSET_FAILURE, SUBSET_EMPTY,
     IB_OK, IB_EMPTY, IB_ITER_LIMIT, IB_FAILURE,
     IB_HOW_UNDECIDED, IB_HOW_EXPLICIT, IB_HOW_IMPLICIT, IB_HOW_BY_POINTS, IB_HOW_BY_EXTREMES, IB_HOW_UNBOUNDED, IB_ALL_EXTREMES,
-    EX_MEMBER, EX_MEMBER_BAND, EX_EMPTY_SLACK, EX_EMPTY_OPEN, EX_ITER_LIMIT, EX_FAILURE, EX_NOT_NEAR, EX_MAX_N, EX_MAX_D, PROD_MAX_K,
+    EX_MEMBER, EX_MEMBER_BAND, EX_EMPTY_SLACK, EX_EMPTY_OPEN, EX_ITER_LIMIT, EX_FAILURE, EX_NOT_NEAR, EX_MAX_N, EX_MAX_D, PROD_MAX_K, TREE_MAX_L, TREE_MAX_CAP,
     RED_UNDECIDED, RED_NONE, RED_KEPT_EQUALITY, RED_REMOVED_ZERO_ROW, RED_KEPT_UNBOUNDED, RED_KEPT_BY_OPTIMUM, RED_REMOVED)
 
 _lib = None
@@ -186,6 +186,8 @@ def load_library():
     lib.qpn_exemplar_products.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32, vp,
                                           C.c_int32, vp, vp, C.c_double, C.c_double, C.c_double, C.POINTER(LpOpts), vp, vp, vp, vp, vp, vp,
                                           vp, vp, C.c_int]
+    lib.qpn_intersection_trees.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32, vp, vp,
+                                           vp, C.c_int32, vp, vp, C.c_double, C.c_double, C.c_double, C.POINTER(LpOpts), C.c_int32] + [vp] * 9 + [C.c_int]
     del dp, ip, bp
     _lib = lib
     return lib

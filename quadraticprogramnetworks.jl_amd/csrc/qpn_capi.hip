@@ -2157,6 +2157,92 @@ int qpn_exemplar_products(qpn_ctx *ctx, int32_t d, int32_t rows, const double *A
     return st.finish();
 }
 
+int qpn_intersection_trees(qpn_ctx *ctx, int32_t d, int32_t rows, const double *A, const double *l, const double *u,
+                           const uint8_t *open_lo, const uint8_t *open_hi, int32_t pieces, const int32_t *piece_row, int32_t trees,
+                           int32_t L, int32_t members, const int32_t *list_ptr, const int32_t *list_mem, const int32_t *list_red,
+                           int32_t points, const double *point, const int32_t *point_of, double point_tol, double tol, double slack_cap,
+                           const qpn_lp_opts *opts, int32_t cap, int32_t *leaves, int32_t *leaf_tree, int32_t *leaf_how,
+                           int64_t *n_leaves, int32_t *tree_leaves, int64_t *tested, int64_t *alive, int64_t *unanswered,
+                           int32_t *overflow, int mem)
+{
+    const char *who = "qpn_intersection_trees";
+    if (!ctx) return QPN_ERR_ARG;
+    if (trees < 0 || rows < 0 || pieces < 0 || points < 0 || members < 0 || d <= 0 || L <= 0 || cap <= 0) return fail_arg(ctx, who, "bad sizes");
+    if (d > QPN_EX_MAX_D || L < 2 || L > QPN_TREE_MAX_L || cap > QPN_TREE_MAX_CAP) {
+        ctx->last_error = std::string(who) + ": d <= 255, 2 <= L <= 32, cap <= 2^22 in ABI v1";
+        return QPN_ERR_SIZE;
+    }
+    Stage st(ctx, mem, who);
+    if (int rc = st.check()) return rc;
+    if (!n_leaves || !overflow || !tested || !alive || !unanswered) return fail_arg(ctx, who, "null pointer");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (trees == 0) {
+        if (st.host) {
+            *n_leaves = 0; *overflow = 0;
+            for (int t = 0; t < L; ++t) tested[t] = alive[t] = unanswered[t] = 0;
+            return QPN_OK;
+        }
+        HIPCHK(ctx, hipMemsetAsync(n_leaves, 0, 8, ctx->stream)); HIPCHK(ctx, hipMemsetAsync(overflow, 0, 4, ctx->stream));
+        for (int64_t *p : {tested, alive, unanswered}) HIPCHK(ctx, hipMemsetAsync(p, 0, (size_t)L * 8, ctx->stream));
+        return QPN_OK;
+    }
+    if (!A || !l || !u || !piece_row || !list_ptr || !list_red || (members && !list_mem) || !leaves || !leaf_tree || !leaf_how || !tree_leaves ||
+        rows == 0 || pieces == 0)
+        return fail_arg(ctx, who, "null pointer");
+    if ((point == nullptr) != (point_of == nullptr) || (point && points == 0)) return fail_arg(ctx, who, "point and point_of go together");
+    const size_t TL = (size_t)trees * L;
+    // host index arrays are checked here and nothing is launched on a bad one; device ones by the kernel (such a tree answers -1)
+    if (st.host) {
+        for (int p = 0; p <= pieces; ++p)
+            if (piece_row[p] < (p ? piece_row[p - 1] : 0) || piece_row[p] > rows) return fail_arg(ctx, who, "piece_row not ascending within the pool");
+        if (list_ptr[0] < 0 || list_ptr[TL] > members) return fail_arg(ctx, who, "list_ptr not ascending within list_mem");
+        for (size_t i = 0; i < TL; ++i)
+            if (list_ptr[i + 1] < list_ptr[i]) return fail_arg(ctx, who, "list_ptr not ascending within list_mem");
+        for (int g = 0; g < trees; ++g) {
+            int64_t longest = 0;
+            for (int t = 0; t < L; ++t) {
+                const size_t li = (size_t)g * L + t;
+                if (list_red[li] < 0 || list_red[li] > list_ptr[li + 1] - list_ptr[li]) return fail_arg(ctx, who, "list_red outside its list");
+                int32_t most = 0;
+                for (int32_t j = list_ptr[li]; j < list_ptr[li + 1]; ++j) {
+                    const int32_t f = list_mem[j];
+                    if (f < 0 || f >= pieces) return fail_arg(ctx, who, "member out of range");
+                    if (piece_row[f + 1] == piece_row[f]) return fail_arg(ctx, who, "a member piece has no rows");
+                    most = std::max(most, piece_row[f + 1] - piece_row[f]);
+                }
+                longest += most;
+            }
+            if (longest > QPN_EX_MAX_N) {
+                ctx->last_error = std::string(who) + ": the longest pieces of a tree's lists add up to more than 511 rows";
+                return QPN_ERR_SIZE;
+            }
+            if (point_of && (point_of[g] < 0 || point_of[g] >= points)) return fail_arg(ctx, who, "point_of out of range");
+        }
+    }
+    qpn_lp_opts o;
+    if (opts) o = *opts; else qpn_lp_default_opts(&o);
+    TreeArgs a{};
+    a.d = d; a.rows = rows; a.pieces = pieces; a.trees = trees; a.L = L; a.members = members; a.points = points; a.cap = cap;
+    a.point_tol = point_tol; a.tol = tol; a.slack_cap = slack_cap;
+    a.lp = LpTol{o.piv_tol, o.feas_tol, o.opt_tol, o.check_tol, o.max_iters};      // (max_iters <= 0: the default, by the size of each job)
+    const size_t cp = (size_t)cap;
+    void *ws;
+    st.in(a.A, A, (size_t)rows * d * 8); st.in(a.l, l, (size_t)rows * 8); st.in(a.u, u, (size_t)rows * 8);
+    st.in(a.open_lo, open_lo, (size_t)rows); st.in(a.open_hi, open_hi, (size_t)rows);
+    st.in(a.piece_row, piece_row, ((size_t)pieces + 1) * 4);
+    st.in(a.list_ptr, list_ptr, (TL + 1) * 4); st.in(a.list_mem, list_mem, (size_t)members * 4, 4); st.in(a.list_red, list_red, TL * 4);
+    st.in(a.point, point, (size_t)points * d * 8); st.in(a.point_of, point_of, (size_t)trees * 4);
+    st.out(a.leaves, leaves, cp * L * 4); st.out(a.leaf_tree, leaf_tree, cp * 4); st.out(a.leaf_how, leaf_how, cp * 4);
+    st.out(a.n_leaves, n_leaves, 8); st.out(a.tree_leaves, tree_leaves, (size_t)trees * 4);
+    st.out(a.tested, tested, (size_t)L * 8); st.out(a.alive, alive, (size_t)L * 8); st.out(a.unanswered, unanswered, (size_t)L * 8);
+    st.out(a.overflow, overflow, 4);
+    st.scratch(ws, qpn_tree_workspace_bytes(trees, L, members, cap, d));
+    int rc = st.begin();
+    if (rc != QPN_OK) return rc;
+    HIPCHK(ctx, qpn_run_intersection_trees(a, ws, ctx->stream));
+    return st.finish();
+}
+
 } // extern "C"
 
 namespace {

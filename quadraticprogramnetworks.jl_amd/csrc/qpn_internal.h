@@ -456,6 +456,30 @@ struct ProdArgs {
 #define QPN_PROD_MAX_K 32
 size_t qpn_products_workspace_bytes(int32_t products, int32_t n, int32_t d);
 hipError_t qpn_launch_exemplar_products(const ProdArgs &a, void *gws, hipStream_t s); // gws: qpn_products_workspace_bytes(products, n, d)
+// qpn_tree.hip: the intersection tree of combine, breadth first (qpn_intersection_trees): the frontier machinery around the jobs of
+// qpn_launch_exemplar_products.  Pointers are device pointers; open_lo, open_hi, point and point_of may be null.  lp.max_iters <= 0:
+// the default of the LP entries, per job size.
+struct TreeArgs {
+    int32_t d, rows, pieces, trees, L, members, points, cap;
+    const double *A, *l, *u;
+    const uint8_t *open_lo, *open_hi;
+    const int32_t *piece_row, *list_ptr, *list_mem, *list_red;
+    const double *point;
+    const int32_t *point_of;
+    double point_tol, tol, slack_cap;
+    LpTol lp;
+    int32_t *leaves, *leaf_tree, *leaf_how;    // [cap][L], [cap], [cap]
+    long long *n_leaves;                       // [1]
+    int32_t *tree_leaves;                      // [trees]
+    long long *tested, *alive, *unanswered;    // [L] each
+    int32_t *overflow;                         // [1]
+};
+#define QPN_TREE_MAX_L 32
+#define QPN_TREE_MAX_CAP (1 << 22)
+size_t qpn_tree_workspace_bytes(int32_t trees, int32_t L, int32_t members, int32_t cap, int32_t d);
+// The whole walk on stream s: one read-back of a depth's histogram and counts per depth, and the stream's work is done when it returns
+// only as far as those read-backs need (the outputs are ordered on s like any kernel's).  ws: qpn_tree_workspace_bytes(...).
+hipError_t qpn_run_intersection_trees(const TreeArgs &a, void *ws, hipStream_t s);
 #define QPN_CONVEXITY_MAX_N 256
 #define QPN_CONVEXITY_MAX_M 1024
 

@@ -904,6 +904,48 @@ class Engine:
                    _ptr(out["x"]), _ptr(out["row"]), _ptr(out["lam"]), _ptr(out["iters"]), self._mem(dev))
         return out
 
+    def intersection_trees(self, A, l, u, open_lo, open_hi, piece_row, L, list_ptr, list_mem, list_red, cap, point=None, point_of=None,
+                           point_tol=1e-6, tol=1e-2, slack_cap=1.0, opts=None):
+        """The intersection trees of `combine`, walked breadth first with the empty prefixes pruned depth by depth
+        (qpn_intersection_trees; polyhedra.intersection_trees_host is its numpy twin and says what every argument is): the pool of
+        exemplar_products (A [rows, d] ROW-major, l, u, open_lo, open_hi [rows] or None, piece_row [pieces + 1] int32); the lists
+        of `trees` trees of depth L as a CSR, list_ptr [trees L + 1] and list_mem int32, list_red [trees L] int32 (the trailing
+        complement pieces of each list); cap, the most tuples a frontier or a depth's candidates may hold; point [points, d] and
+        point_of [trees] int32, or both None.  Returns dict(leaves [cap, L] int32, leaf_tree, leaf_how [cap] int32, n_leaves [1]
+        int64, tree_leaves [trees] int32, tested, alive, unanswered [L] int64, overflow [1] int32); only the first n_leaves rows
+        of leaves, leaf_tree and leaf_how are written.  Host arrays in: numpy out, cut to n_leaves rows, and a bad index raises;
+        device tensors in: tensors out, nothing is read back here, and a bad tree answers tree_leaves = -1."""
+        who = "intersection_trees"
+        dev, A, l, u, point, open_lo, open_hi, piece_row, list_ptr, list_mem, list_red, point_of = self._stage(
+            who, "A l u point open_lo open_hi piece_row list_ptr list_mem list_red point_of", f64=(A, l, u, point), u8=(open_lo, open_hi),
+            i32=(piece_row, list_ptr, list_mem, list_red, point_of))
+        L, cap = int(L), int(cap)
+        if A.ndim != 2 or piece_row.ndim != 1 or piece_row.shape[0] < 1 or list_ptr.ndim != 1 or list_mem.ndim != 1 or list_red.ndim != 1 or \
+                L < 1 or int(list_red.shape[0]) % L or int(list_ptr.shape[0]) != int(list_red.shape[0]) + 1 or (point is None) != (point_of is None):
+            raise QpnError(f"{who}: inconsistent shapes")
+        rows, d = (int(v) for v in A.shape)
+        trees, pieces = int(list_red.shape[0]) // L, int(piece_row.shape[0]) - 1
+        points = 0 if point is None else int(point.shape[0])
+        if tuple(l.shape) != (rows,) or tuple(u.shape) != (rows,) or any(o is not None and tuple(o.shape) != (rows,) for o in (open_lo, open_hi)) or (
+                point is not None and (point.ndim != 2 or int(point.shape[1]) != d or tuple(point_of.shape) != (trees,))):
+            raise QpnError(f"{who}: inconsistent shapes")
+        opts = self._lp_opts(opts)
+        rows_out = max(cap, 0)
+        out = dict(leaves=self._alloc(dev, (rows_out, L), np.int32), leaf_tree=self._alloc(dev, (rows_out,), np.int32),
+                   leaf_how=self._alloc(dev, (rows_out,), np.int32), n_leaves=self._alloc(dev, (1,), np.int64),
+                   tree_leaves=self._alloc(dev, (trees,), np.int32), tested=self._alloc(dev, (L,), np.int64),
+                   alive=self._alloc(dev, (L,), np.int64), unanswered=self._alloc(dev, (L,), np.int64), overflow=self._alloc(dev, (1,), np.int32))
+        self._call("qpn_intersection_trees", d, rows, _ptr(A), _ptr(l), _ptr(u), _ptr(open_lo), _ptr(open_hi), pieces, _ptr(piece_row), trees,
+                   L, int(list_mem.shape[0]), _ptr(list_ptr), _ptr(list_mem), _ptr(list_red), points, _ptr(point), _ptr(point_of),
+                   float(point_tol), float(tol), float(slack_cap), C.byref(opts) if opts is not None else None, cap, _ptr(out["leaves"]),
+                   _ptr(out["leaf_tree"]), _ptr(out["leaf_how"]), _ptr(out["n_leaves"]), _ptr(out["tree_leaves"]), _ptr(out["tested"]),
+                   _ptr(out["alive"]), _ptr(out["unanswered"]), _ptr(out["overflow"]), self._mem(dev))
+        if not dev:
+            k = int(out["n_leaves"][0])
+            for key in ("leaves", "leaf_tree", "leaf_how"):
+                out[key] = out[key][:k]
+        return out
+
 
 class Nodes:
     """Resident node records (``qpn_nodes_upload``): the records of a level's single-node pools live in HBM owned by the

@@ -29,6 +29,8 @@ keeps the node-AVI route.  On an engine with `exemplar_polys` (qpn_exemplar_poly
 bounds may be open is ONE job too, opt-in through route="polyhedron": the job expands the slack LP, solves it and applies the
 reference's rule to its own duals (exemplar_polys_host is the twin).  On one with `exemplar_products` (qpn_exemplar_products) the
 products of pieces of the intersection tree are jobs over one pool of rows (isempty_products; exemplar_products_host is the twin).
+On one with `intersection_trees` (qpn_intersection_trees) the tree itself is walked on the device, the empty prefixes pruned depth by
+depth (intersection_trees; intersection_trees_host is the twin).
 On one with `irredundant_bounds` (qpn_irredundant_bounds) irredundant_batch removes the bounds of polyhedra that their other bounds
 imply, one job per polyhedron (irredundant_bounds_host is the twin); there is no other route for it.
 
@@ -36,6 +38,8 @@ These are the batch front ends: they normalise their inputs (_triple), pick a ro
 engine and unpack.  The numpy twins and the result codes are polyhedra_host.py; their public names stay importable from here.
 """
 from __future__ import annotations
+
+import itertools
 
 import numpy as np
 
@@ -781,6 +785,116 @@ def isempty_products(pieces, products, engine, tol=1e-4, points=None, point_of=N
         t, how = min(failed)
         raise RuntimeError(f"isempty_products: exemplar status {how} on product {t}")
     return near, empty
+
+
+TREE_ALIVE_GUESS = 64           # intersection_trees' first cap counts on at most this many live prefixes per tree and depth
+TREE_FRONT_CAP = 1 << 20        # ... and it asks for no larger cap than this: the entry's workspace is about 16 cap L bytes
+
+
+def intersection_trees(pieces, trees, engine, tol=1e-4, points=None, point_of=None, point_tol=1e-6, slack_cap=1.0, strict=True):
+    """The intersection trees of `combine` (src/intersection.jl:66-105, :116-138) for a batch, on an engine with `intersection_trees`
+    (qpn_intersection_trees): per tree the tuples -- one piece of every list -- whose point lies in the closure of every member and
+    none of whose prefixes is empty, in the order `iterate` yields them; no tuple is formed on the host.  pieces: as
+    isempty_products takes them; trees: [(lists, reds)], lists = L lists of positions in `pieces` (union t's pieces in the
+    reference's order), reds = per list the number of its trailing members that are complement pieces (the redzone, :123): a tuple
+    of complement pieces alone is no leaf.  points, point_of: the points and the point of each tree (both None: no closure test).
+    A pool of rows goes up per d, the trees are grouped by (d, L): one call per group.  cap, the most tuples a depth may hold, starts
+    as the largest over the depths of sum over the group's trees of min(prod_{s <= t} w_s, TREE_ALIVE_GUESS w_t) (w: the lists'
+    widths); a call that overflows is made once more with the true products in place of the guess, and when those are beyond
+    TREE_FRONT_CAP (the entry's workspace is about 16 cap L bytes: 48 MiB at this cap and L = 3) its trees fall back.  A tree goes to isempty_products (same pieces, all tuples) when the engine lacks the method, L
+    is outside [2, 32], d is outside [1, 255], a piece of it has no rows, the longest pieces of its lists add up to more than 511
+    rows, a piece of it is closed with isapprox(l, u) (a tuple of such pieces could take exemplar's square-equality shortcut,
+    src/sets.jl:599-606, where the device runs the LP), or its group overflowed twice.  A candidate without an answer raises
+    (strict), as isempty_products does.
+    -> (leaves: per tree the list of tuples of positions in `pieces`, stats: dict(tested: the candidates tested on the tree route,
+    products: the tuples the products route forms for those trees -- those of complement pieces alone are not counted --,
+    fallback: the trees that took isempty_products, calls))."""
+    T = len(trees)
+    leaves = [None] * T
+    stats = dict(tested=0, products=0, fallback=[], calls=0)
+    rows_of = [p[0].shape[0] for p in pieces]
+    flat = lambda p: not (p[3].any() or p[4].any()) and p[0].shape[0] > 0 and _isapprox(p[1], p[2], tol, tol)
+    flat_of = {}
+    groups = {}
+    for g, (lists, reds) in enumerate(trees):
+        L = len(lists)
+        used = [f for mem in lists for f in mem]
+        d = pieces[used[0]][0].shape[1] if used else 0
+        for f in used:
+            if f not in flat_of:
+                flat_of[f] = flat(pieces[f])
+        ok = _has(engine, "intersection_trees") and 2 <= L <= TREE_MAX_L and 1 <= d <= EX_MAX_D and all(rows_of[f] > 0 for f in used) and \
+            sum(max((rows_of[f] for f in mem), default=0) for mem in lists) <= EX_MAX_N and not any(flat_of[f] for f in used)
+        if ok:
+            groups.setdefault((d, L), []).append(g)
+        else:
+            stats["fallback"].append(g)
+    for (d, L) in sorted(groups):
+        gs = groups[(d, L)]
+        used = sorted({f for g in gs for mem in trees[g][0] for f in mem})
+        at = {f: i for i, f in enumerate(used)}
+        A = np.vstack([pieces[f][0] for f in used]); l = np.concatenate([pieces[f][1] for f in used]); u = np.concatenate([pieces[f][2] for f in used])
+        ol = np.concatenate([pieces[f][3] for f in used]).astype(np.uint8); oh = np.concatenate([pieces[f][4] for f in used]).astype(np.uint8)
+        piece_row = np.concatenate([[0], np.cumsum([rows_of[f] for f in used])]).astype(np.int32)
+        list_mem = np.array([at[f] for g in gs for mem in trees[g][0] for f in mem], np.int32)
+        widths = np.array([[len(mem) for mem in trees[g][0]] for g in gs], np.int64).reshape(len(gs), L)
+        list_ptr = np.concatenate([[0], np.cumsum(widths.reshape(-1))]).astype(np.int32)
+        list_red = np.array([trees[g][1] for g in gs], np.int32).reshape(-1)
+        pts, pof = None, None
+        if points is not None:
+            pt_at = {}
+            for g in gs:
+                pt_at.setdefault(point_of[g], len(pt_at))
+            pts = np.array([points[j] for j in pt_at], dtype=np.float64).reshape(len(pt_at), d)
+            pof = np.array([pt_at[point_of[g]] for g in gs], np.int32)
+        full = np.cumprod(widths.astype(object), axis=1)                        # (exact: Python integers)
+        guess = np.minimum(full, TREE_ALIVE_GUESS * widths.astype(object))
+        caps = [int(max(1, guess.sum(0).max())), int(max(1, full.sum(0).max()))]
+        res = None
+        for cap in ([caps[0]] if caps[0] >= caps[1] else caps):
+            if cap > min(TREE_MAX_CAP, TREE_FRONT_CAP):
+                break
+            got = engine.intersection_trees(A, l, u, ol, oh, piece_row, L, list_ptr, list_mem, list_red, cap, point=pts, point_of=pof,
+                                            point_tol=point_tol, tol=tol, slack_cap=slack_cap)
+            stats["calls"] += 1
+            if int(_to_host(got["overflow"])[0]) == 0:
+                res = got
+                break
+        if res is None:
+            stats["fallback"] += gs
+            continue
+        k = int(_to_host(res["n_leaves"])[0])
+        tup = _to_host(res["leaves"])[:k]; owner = _to_host(res["leaf_tree"])[:k]
+        if strict and int(_to_host(res["unanswered"]).sum()):
+            raise RuntimeError(f"intersection_trees: {int(_to_host(res['unanswered']).sum())} candidates of the trees of (d, L) = ({d}, {L}) "
+                               "ended without an answer")
+        for g in gs:
+            leaves[g] = []
+        for row, o in zip(tup, owner):
+            leaves[gs[int(o)]].append(tuple(used[int(f)] for f in row))
+        stats["tested"] += int(_to_host(res["tested"]).sum())
+        stats["products"] += int(full[:, -1].sum()) - sum(int(np.prod(np.array(trees[g][1], dtype=object))) for g in gs)
+    back = sorted(stats["fallback"])
+    stats["fallback"] = back
+    if back:
+        products, owner, pof = [], [], []
+        for g in back:
+            lists, reds = trees[g]
+            comp = [[i >= len(mem) - r for i in range(len(mem))] for mem, r in zip(lists, reds)]
+            for choice in itertools.product(*[list(zip(mem, c)) for mem, c in zip(lists, comp)]):
+                if all(c for _, c in choice):
+                    continue
+                products.append(tuple(f for f, _ in choice)); owner.append(g)
+                if points is not None:
+                    pof.append(point_of[g])
+        near, empty = isempty_products(pieces, products, engine, tol=tol, points=points, point_of=pof if points is not None else None,
+                                       point_tol=point_tol, slack_cap=slack_cap, strict=strict) if products else ([], [])
+        for g in back:
+            leaves[g] = []
+        for t, (fs, g) in enumerate(zip(products, owner)):
+            if near[t] and not empty[t]:
+                leaves[g].append(fs)
+    return leaves, stats
 
 
 class _Flagged:

@@ -1,5 +1,5 @@
 """The numpy twins of the polyhedral entries, the normative statements of the kernels' methods (the kernels are bit-equal to them):
-solve_lps_host, issubset_pairs_host, implicit_bounds_host, irredundant_bounds_host, exemplar_polys_host, exemplar_products_host, interior_member_records, members_outside_host and members_outside_lists_host,
+solve_lps_host, issubset_pairs_host, implicit_bounds_host, irredundant_bounds_host, exemplar_polys_host, exemplar_products_host, intersection_trees_host, interior_member_records, members_outside_host and members_outside_lists_host,
 with the entries' result codes, defined here once (_lib.py and polyhedra.py import them).  Numpy alone, loadable as a stand-alone
 file: tests/golden/lp_twin_record.json pins it across commits.  The front ends that pack, route and call an engine are polyhedra.py.
 """
@@ -865,6 +865,138 @@ def exemplar_products_host(A, l, u, open_lo, open_hi, piece_row, factors, n, poi
         got = _exemplar_one(np.ascontiguousarray(A[idx]), l[idx], u[idx], flags[0][idx], flags[1][idx], float(tol), float(slack_cap), o)
         for key, v in zip(("empty", "how", "eps", "x", "row", "lam", "iters"), got):
             out[key][t] = v
+    return out
+
+
+# ---- the intersection tree of combine (qpn_intersection_trees): prefixes pruned depth by depth, the numpy twin -------------------------
+TREE_MAX_L, TREE_MAX_CAP = 32, 1 << 22
+
+
+def intersection_trees_host(A, l, u, open_lo, open_hi, piece_row, L, list_ptr, list_mem, list_red, cap, point=None, point_of=None,
+                            point_tol=1e-6, tol=1e-2, slack_cap=1.0, opts=None, device=False):
+    """The numpy twin of Engine.intersection_trees (qpn_intersection_trees), the normative statement of the method; every output
+    of the entry is equal to it.  The lazy enumeration of `combine` (src/qp_processing.jl:260-291; IntersectionRoot's walk,
+    src/intersection.jl:66-105, :116-138), breadth first: `trees` trees of one depth L over the pool of exemplar_products_host (A
+    [rows, d] one ROW per pool row, l, u, open_lo, open_hi [rows], piece_row [pieces + 1]).  list_ptr [trees L + 1] and list_mem
+    form a CSR: list g L + t holds the pieces of union t of tree g, in the reference's order, its last list_red[g L + t] members
+    being complement pieces (the redzone, :123).  point [points, d], point_of [trees] (both None: no closure test).  cap: the most
+    tuples a frontier or a depth's candidates may hold.
+
+    (0) Near: a member of a list stays when every row of its piece passes the closure test of exemplar_products_host (b) at the
+    tree's point (acc = acc + a * p over the ascending columns, closed relations whatever the flags); the order of the rest is
+    kept.  No point: every member is near.  (1) Expand: F_0 is one empty tuple per tree; for t = 1 .. L the candidates are, for
+    every tuple of F_(t-1) in order and every near member of list t in order, the tuple with that member appended -- at t = L a
+    candidate whose members are all complement pieces is not formed.  A candidate is one job of exemplar_products_host: its tuple
+    as factors, -1 from slot t on, n = its rows, no point.  It is kept when empty == 0: EX_ITER_LIMIT and EX_FAILURE are no
+    answer, the candidate stays and is counted in unanswered[t - 1].  F_t = the kept candidates in candidate order; tested[t - 1]
+    and alive[t - 1] are the two counts.  (2) The leaves are F_L in order: by tree, then lexicographic in list positions.
+    (3) A depth that forms more than cap candidates ends the call: overflow = that depth (1-based), tested of that depth = the
+    count it formed, no count after it, no leaves, tree_leaves 0.  (4) list_ptr ascends as a whole, 0 <= list_ptr[i] <=
+    list_ptr[i + 1] <= len(list_mem) -- lists must not overlap in list_mem --: where it does not, every tree of the call is bad.  A
+    tree is bad when a list_red is outside [0, its list's length], a member is outside [0, pieces), a member's piece_row entries
+    are not 0 <= first < last <= rows (a piece of no rows included), the longest pieces of its lists add up to more than EX_MAX_N
+    rows, or its point_of is outside [0, points): ValueError as host arrays do; device=True: the tree forms no candidate and
+    answers tree_leaves = -1, as the entry does for device arrays.
+    -> dict(leaves [n_leaves, L] int32 (pool pieces), leaf_tree [n_leaves] int32, leaf_how [n_leaves] int32 (EX_*), n_leaves int,
+    tree_leaves [trees] int32, tested, alive, unanswered [L] int64, overflow int)."""
+    A = np.asarray(A, dtype=np.float64); l = np.asarray(l, dtype=np.float64); u = np.asarray(u, dtype=np.float64)
+    rows, d = A.shape
+    piece_row = np.asarray(piece_row, dtype=np.int64)
+    list_ptr = np.asarray(list_ptr, dtype=np.int64); list_mem = np.asarray(list_mem, dtype=np.int64).reshape(-1)
+    list_red = np.asarray(list_red, dtype=np.int64)
+    pieces, L, cap, M = len(piece_row) - 1, int(L), int(cap), len(list_mem)
+    trees = len(list_red) // L if L > 0 else 0
+    if not 2 <= L <= TREE_MAX_L or not 1 <= cap <= TREE_MAX_CAP or not 1 <= d <= EX_MAX_D:
+        raise ValueError("intersection_trees: 2 <= L <= 32, 1 <= cap <= 2^22, 1 <= d <= 255")
+    if len(list_red) != trees * L or len(list_ptr) != trees * L + 1 or (point is None) != (point_of is None):
+        raise ValueError("intersection_trees: inconsistent arguments")
+    if point is not None:
+        point = np.asarray(point, dtype=np.float64).reshape(-1, d); point_of = np.asarray(point_of, dtype=np.int64)
+    out = dict(leaves=np.zeros((0, L), np.int32), leaf_tree=np.zeros(0, np.int32), leaf_how=np.zeros(0, np.int32), n_leaves=0,
+               tree_leaves=np.zeros(trees, np.int32), tested=np.zeros(L, np.int64), alive=np.zeros(L, np.int64),
+               unanswered=np.zeros(L, np.int64), overflow=0)
+    size = lambda f: int(piece_row[f + 1] - piece_row[f])
+    # (4) the lists must not overlap in list_mem: the offsets ascend as a whole, or no tree is walked
+    csr_bad = bool(trees) and bool(np.any(list_ptr[:-1] < 0) or np.any(np.diff(list_ptr) < 0) or np.any(list_ptr[1:] > M))
+    if csr_bad and not device:
+        raise ValueError("intersection_trees: list_ptr not ascending within list_mem")
+    # (4) the trees, (0) the near members of their lists: (piece, is a complement piece)
+    lists = [[[] for _ in range(L)] for _ in range(trees)]
+    for g in range(trees):
+        bad, longest = "list_ptr not ascending within list_mem" if csr_bad else None, 0
+        for t in range(L if not bad else 0):
+            p0, p1 = int(list_ptr[g * L + t]), int(list_ptr[g * L + t + 1])
+            if not 0 <= p0 <= p1 <= M:
+                bad = "list_ptr not ascending within list_mem"
+                break
+            mem = [int(f) for f in list_mem[p0:p1]]
+            if not 0 <= list_red[g * L + t] <= p1 - p0:
+                bad = "list_red outside its list"
+            elif any(not 0 <= f < pieces for f in mem):
+                bad = "member out of range"
+            elif any(not 0 <= piece_row[f] < piece_row[f + 1] <= rows for f in mem):
+                bad = "a member's piece_row entries are not 0 <= first < last <= rows"
+            if bad:
+                break
+            longest += max([size(f) for f in mem], default=0)
+        if not bad and longest > EX_MAX_N:
+            bad = "the longest pieces of the lists add up to more than 511 rows"
+        if not bad and point is not None and not 0 <= point_of[g] < len(point):
+            bad = "point_of out of range"
+        if bad:
+            if not device:
+                raise ValueError(f"intersection_trees: tree {g}: {bad}")
+            out["tree_leaves"][g] = -1
+            continue
+        for t in range(L):
+            p0, p1 = int(list_ptr[g * L + t]), int(list_ptr[g * L + t + 1])
+            for j in range(p0, p1):
+                f = int(list_mem[j])
+                if point is not None:
+                    idx = np.arange(piece_row[f], piece_row[f + 1])
+                    pt = point[point_of[g]]
+                    with np.errstate(all="ignore"):
+                        acc = np.zeros(len(idx))
+                        for c in range(d):
+                            acc = acc + A[idx, c] * pt[c]
+                        if not (np.all(l[idx] - point_tol <= acc) and np.all(acc - point_tol <= u[idx])):
+                            continue
+                lists[g][t].append((f, j >= p1 - int(list_red[g * L + t])))
+    # (1) breadth first: a tuple of the frontier is (tree, members, all of them complement pieces)
+    frontier = [(g, (), True) for g in range(trees)]
+    hows = []
+    for t in range(1, L + 1):
+        cands = []
+        for g, tup, allc in frontier:
+            for f, comp in lists[g][t - 1]:
+                if t == L and allc and comp:
+                    continue
+                cands.append((g, tup + (f,), allc and comp))
+        out["tested"][t - 1] = len(cands)
+        if len(cands) > cap:                                                # (3)
+            out["overflow"] = t
+            return out
+        ns = [sum(size(f) for f in c[1]) for c in cands]
+        empty = np.zeros(len(cands), bool); how = np.zeros(len(cands), np.int32)
+        for n in sorted(set(ns)):
+            at = [i for i, v in enumerate(ns) if v == n]
+            factors = np.full((len(at), L), -1, np.int64)
+            for k, i in enumerate(at):
+                factors[k, :t] = cands[i][1]
+            got = exemplar_products_host(A, l, u, open_lo, open_hi, piece_row, factors, n, tol=tol, slack_cap=slack_cap, opts=opts)
+            empty[at] = got["empty"] != 0; how[at] = got["how"]
+        keep = np.nonzero(~empty)[0]
+        frontier = [cands[i] for i in keep]
+        hows = how[keep]
+        out["alive"][t - 1] = len(keep)
+        out["unanswered"][t - 1] = int(np.isin(hows, (EX_ITER_LIMIT, EX_FAILURE)).sum())
+    n_leaves = len(frontier)                                                # (2)
+    out["n_leaves"] = n_leaves
+    out["leaves"] = np.array([c[1] for c in frontier], np.int32).reshape(n_leaves, L)
+    out["leaf_tree"] = np.array([c[0] for c in frontier], np.int32)
+    out["leaf_how"] = np.asarray(hows, np.int32).reshape(n_leaves)
+    for g in out["leaf_tree"]:
+        out["tree_leaves"][g] += 1
     return out
 
 

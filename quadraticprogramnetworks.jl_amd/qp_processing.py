@@ -17,7 +17,7 @@ INF = np.inf
 
 CONVEXITY_TOL = 1e-6                        # check_qp_convexity's tol (src/qp_processing.jl:39)
 IMPLICIT_BOUNDS_ROUTE = "jobs"              # implicit_bounds_batch's route for the convexity check: "jobs" or "polyhedron"
-EMPTINESS_ROUTE = "nodes"                   # the route of combine's products: "nodes" or "polyhedron" (isempty_slack_batch), "products"
+EMPTINESS_ROUTE = "nodes"                   # the route of combine's products: "nodes" or "polyhedron" (isempty_slack_batch), "products", "tree"
 
 
 class NonConvexQPError(RuntimeError):
@@ -317,6 +317,45 @@ def _combine_many_products(jobs, x, engine, tol):
     return out
 
 
+def _combine_many_tree(jobs, x, engine, tol):
+    """combine_many with route="tree" (polyhedra.intersection_trees, qpn_intersection_trees): every candidate of every node goes into
+    the pool once, a node's tree is the lists of its candidates' positions there with the complement candidates counted as each
+    list's redzone, the walk -- the closure test (src/intersection.jl:74), the emptiness test of every prefix (:83), the pruning --
+    is the device's, and a Poly is built for the leaves only: no tuple is formed here."""
+    from .polyhedra import intersection_trees
+    x = np.asarray(x, dtype=np.float64)
+    prep, pieces, polys, trees, points = [], [], [], [], []
+    for regions, solutions in jobs:
+        try:
+            cols, ncols, cands = _combine_candidates(regions, solutions, x)
+        except RuntimeError as err:
+            prep.append(err)
+            continue
+        lists = []
+        for cand in cands:
+            lists.append(list(range(len(pieces), len(pieces) + len(cand))))
+            pieces += [(P.A, P.l, P.u) + P.open_bounds() for _, P in cand]
+            polys += [P for _, P in cand]
+        prep.append((cols, ncols, len(trees)))
+        trees.append((lists, [sum(1 for comp, _ in cand if comp) for cand in cands]))
+        points.append(x[cols])
+    leaves, _ = intersection_trees(pieces, trees, engine, tol=tol, points=points, point_of=list(range(len(trees)))) if trees else ([], None)
+    out = []
+    for pr in prep:
+        if isinstance(pr, RuntimeError):
+            out.append(pr)
+            continue
+        cols, ncols, g = pr
+        kept = []
+        for tup in leaves[g]:
+            fs = [polys[f] for f in tup]
+            kept.append(Poly.from_local(ncols, cols, np.vstack([P.A for P in fs]), np.concatenate([P.l for P in fs]),
+                                        np.concatenate([P.u for P in fs]), normalise=False,
+                                        open_lo=np.concatenate([P.open_lo for P in fs]), open_hi=np.concatenate([P.open_hi for P in fs])))
+        out.append(kept)
+    return out
+
+
 def combine_many(jobs, x, engine, tol=1e-4, route=None):
     """combine(regions, solutions, x) (src/qp_processing.jl:260-291) for ALL nodes of a level that are optimal under SEVERAL
     combinations of their children's pieces (x sits on a kink of a child's solution graph).  Per node
@@ -330,13 +369,16 @@ def combine_many(jobs, x, engine, tol=1e-4, route=None):
     nodes go to the engine as ONE batch of LPs (polyhedra.isempty_slack_batch: `isempty`, src/sets.jl:647-655 -> `exemplar`,
     :591-642, open bounds included; by `route`, None: the module's EMPTINESS_ROUTE).  route="products" on an engine with
     `exemplar_products`: no product is expanded on the host (_combine_many_products); an engine without it takes route="polyhedron".
+    route="tree": the reference's own lazy walk, prefixes pruned depth by depth on the device, no tuple formed on the host
+    (_combine_many_tree; for three or more unions); the trees the entry does not take, and an engine without `intersection_trees`,
+    go the way of route="products".
     jobs: list of (regions, solutions); returns per job the list of pieces (global
     coordinates) or the RuntimeError of the reference's size guard (:281-285) for the caller to turn into failed = true."""
     from .polyhedra import isempty_slack_batch
     route = EMPTINESS_ROUTE if route is None else route
-    if route == "products":
+    if route in ("products", "tree"):
         if callable(getattr(engine, "exemplar_products", None)):
-            return _combine_many_products(jobs, x, engine, tol)
+            return (_combine_many_tree if route == "tree" else _combine_many_products)(jobs, x, engine, tol)
         route = "polyhedron"
     prep, flat, owner = [], [], []
     for k, (regions, solutions) in enumerate(jobs):
