@@ -48,6 +48,20 @@ typedef struct qpn_ctx qpn_ctx;
 
 /* qpn_avi_opts.flags */
 #define QPN_AVI_FLAG_COLD_START 1 /* ignore the z input: every item starts from z0 = 0 (no reset pass) */
+/* Warm start of a node solve from the active set of an earlier sweep.  Honoured by qpn_solve_nodes, qpn_solve_nodes_into and
+ * qpn_solve_nodes_h when n, m <= 32, z != NULL and QPN_AVI_FLAG_COLD_START is not set; in every other size class and on every
+ * other entry point the bit is ignored and the solve is cold.  The multiplier part of the incoming z names the hint: row i is
+ * taken to sit at l_i where lambda_i > 0, at u_i where lambda_i < 0, and to be inactive otherwise (z of the previous sweep
+ * over the same nodes is such a hint; its primal part is not read).  Per node, the linear KKT system of the hinted rows is
+ * solved in fp64 and the point takes the post-check, residual and active-set classification of the cold solve.  The node is
+ * ACCEPTED only if every hinted row has a finite bound on its side, there are at most n hinted rows, no pivot of the
+ * factorisations falls under piv_tol, every hinted multiplier comes out with its side's sign and the post-check passes: it
+ * then returns status = QPN_SUCCESS, pivots = 0, and z, resid, active and the x scatter of that point (equal to the cold
+ * solve's up to rounding).  Every other node -- a NaN or an infinity in its hint, an empty hint on a node with active rows, a
+ * wrong row or side -- is solved by the cold route in the same call, with results bit-identical to a call without the bit.
+ * Accepted nodes do not feed a handle's pivot statistics, its schedule or its count of declined nodes, and a sweep with the
+ * bit set does not fill the crash cache (it reuses a valid one). */
+#define QPN_AVI_FLAG_WARM_DUALS 2
 
 typedef struct {
     double check_tol;  /* post-check tolerance, 1e-6       (src/avi.jl:148)                 */
@@ -162,7 +176,8 @@ int qpn_assemble_pools(qpn_ctx *ctx, const qpn_pool_shape *shape, int form, int3
  * Same inputs as qpn_assemble_nodes, same outputs as qpn_solve_avi_batch (N = n+m, z = [x_d; lambda]);
  * identical results to calling the two in sequence, without materialising M in HBM: one pass of the
  * hot path per outer sweep (src/algorithm.jl:95 -> solve_qep -> src/avi.jl:399-409 for single-node
- * pools).  z: in z0 (ignored with QPN_AVI_FLAG_COLD_START), out solution.  n, m <= 32 run on the fused
+ * pools).  z: in z0 (ignored with QPN_AVI_FLAG_COLD_START; with QPN_AVI_FLAG_WARM_DUALS its multipliers are the hint of the
+ * warm start, see there), out solution.  n, m <= 32 run on the fused
  * matrix-core kernel (one wavefront per node); n, m <= 64 on the four-wavefronts-per-node path (crash on the
  * matrix cores straight from the records, cold duals); larger nodes (n+m <= 1024) are assembled and take the
  * blocked matrix-core path for large node-shaped items (n, m <= 512) or the general kernels. */

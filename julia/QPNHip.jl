@@ -21,6 +21,7 @@ const QPN_MEM_HOST = Cint(0)
 const QPN_SUCCESS = Int32(1)
 
 const QPN_AVI_FLAG_COLD_START = Int32(1)   # include/qpn_hip.h
+const QPN_AVI_FLAG_WARM_DUALS = Int32(2)   # n, m <= 32 node solves: the multipliers of the incoming z name the active set to start from
 struct AviOpts                # qpn_avi_opts, include/qpn_hip.h
     check_tol::Cdouble
     piv_tol::Cdouble
@@ -103,13 +104,22 @@ One sweep over `batch` single-node pools: `Qd` n×n×batch, `R` n×p×batch, `qd
 on the fly and solved (`qpn_solve_nodes_into`); `z` is (n+m)×batch = [x_d; λ] and the primal blocks are
 also written into the columns of `x` (n×batch view of the iterate: the write-back of
 src/algorithm.jl:97-101).
+
+`warm = z_prev` (the (n+m)×batch `z` of an earlier sweep over the same nodes; n, m <= 32): its multipliers name the active
+set every node starts from (`QPN_AVI_FLAG_WARM_DUALS`).  A node whose hint holds comes back with `pivots == 0`; every other
+node is solved cold in the same call.
 """
 function solve_nodes!(x::Union{Nothing,StridedMatrix{Float64}}, Qd::Array{Float64,3}, R::Array{Float64,3}, qd::Matrix{Float64},
-                      Ad::Array{Float64,3}, B::Array{Float64,3}, l::Matrix{Float64}, u::Matrix{Float64}, w::VecOrMat{Float64})
+                      Ad::Array{Float64,3}, B::Array{Float64,3}, l::Matrix{Float64}, u::Matrix{Float64}, w::VecOrMat{Float64};
+                      warm::Union{Nothing,Matrix{Float64}} = nothing)
     n, batch = size(qd); m = size(l, 1); p = size(w, 1)
     N = n + m
-    z = zeros(N, batch); status = zeros(Int32, batch); resid = zeros(batch); pivots = zeros(Int32, batch); active = zeros(UInt8, N, batch)
-    o = default_opts(); o = AviOpts(o.check_tol, o.piv_tol, o.feas_tol, o.comp_tol, o.max_pivots, o.flags | QPN_AVI_FLAG_COLD_START)
+    warm === nothing || size(warm) == (N, batch) || error("solve_nodes!: warm must be (n+m)×batch")
+    z = warm === nothing ? zeros(N, batch) : copy(warm)
+    status = zeros(Int32, batch); resid = zeros(batch); pivots = zeros(Int32, batch); active = zeros(UInt8, N, batch)
+    o = default_opts()
+    o = AviOpts(o.check_tol, o.piv_tol, o.feas_tol, o.comp_tol, o.max_pivots,
+                warm === nothing ? o.flags | QPN_AVI_FLAG_COLD_START : o.flags | QPN_AVI_FLAG_WARM_DUALS)
     xp = x === nothing ? Ptr{Cdouble}(C_NULL) : pointer(x)
     sx = x === nothing ? Int64(0) : Int64(stride(x, 2))
     GC.@preserve x begin
@@ -170,20 +180,27 @@ function update_nodes!(nodes::Nodes, field::Int32, data::Array{Float64})
     nothing
 end
 
-function solve_nodes!(nodes::Nodes, x::Union{Nothing,StridedMatrix{Float64}}, w::VecOrMat{Float64}; want_z::Bool = true)
+# warm = the z of an earlier sweep over the handle's nodes: QPN_AVI_FLAG_WARM_DUALS, as in solve_nodes! above (z comes back)
+function solve_nodes!(nodes::Nodes, x::Union{Nothing,StridedMatrix{Float64}}, w::VecOrMat{Float64}; want_z::Bool = true,
+                      warm::Union{Nothing,Matrix{Float64}} = nothing)
     N = nodes.n + nodes.m; batch = nodes.batch
-    z = want_z ? zeros(N, batch) : nothing
+    warm === nothing || size(warm) == (N, batch) || error("solve_nodes!: warm must be (n+m)×batch")
+    want_z = want_z || warm !== nothing
+    z = warm !== nothing ? copy(warm) : (want_z ? zeros(N, batch) : nothing)
+    o = default_opts()
+    oref = Ref(AviOpts(o.check_tol, o.piv_tol, o.feas_tol, o.comp_tol, o.max_pivots, o.flags | QPN_AVI_FLAG_WARM_DUALS))
     status = zeros(Int32, batch); resid = zeros(batch); pivots = zeros(Int32, batch)
     active = want_z ? zeros(UInt8, N, batch) : nothing
     xp = x === nothing ? Ptr{Cdouble}(C_NULL) : pointer(x)
     sx = x === nothing ? Int64(0) : Int64(stride(x, 2))
-    GC.@preserve x z active begin
+    GC.@preserve x z active oref begin
+        optr = warm === nothing ? Ptr{Cvoid}(C_NULL) : Ptr{Cvoid}(Base.unsafe_convert(Ptr{AviOpts}, oref))
         rc = ccall((:qpn_solve_nodes_h, LIB), Cint,
                    (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cdouble}, Int64, Ptr{Cdouble}, Ptr{Int32}, Ptr{Cdouble}, Ptr{Int32}, Ptr{UInt8},
                     Ptr{Cvoid}, Cint, Ptr{Cdouble}, Int64),
                    ctx(), nodes.h, w, ndims(w) == 1 ? Int64(0) : Int64(nodes.p),
                    want_z ? pointer(z) : Ptr{Cdouble}(C_NULL), status, resid, pivots, want_z ? pointer(active) : Ptr{UInt8}(C_NULL),
-                   C_NULL, QPN_MEM_HOST, xp, sx)
+                   optr, QPN_MEM_HOST, xp, sx)
         rc == 0 || error("qpn_solve_nodes_h failed ($rc)")
     end
     (z, status, resid, pivots, active)

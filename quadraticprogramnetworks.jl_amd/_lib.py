@@ -31,6 +31,7 @@ ABI_SYMBOLS = (
 
 MEM_HOST, MEM_DEVICE = 0, 1
 AVI_FLAG_COLD_START = 1
+AVI_FLAG_WARM_DUALS = 2         # n, m <= 32 node solves: the multipliers of the incoming z name the active set to start from
 MAX_MIRRORS = 7
 IPC_HANDLE_BYTES = 64
 SHARED_FINE_GRAINED = 1

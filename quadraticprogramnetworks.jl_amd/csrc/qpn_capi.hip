@@ -1150,14 +1150,15 @@ int solve_general(qpn_ctx *ctx, const AviBatchArgs &a, const NodeWs &ws, bool ga
 // only when h knows that no node declines).
 int solve_nodes_launch(qpn_ctx *ctx, qpn_nodes *h, int32_t batch, int32_t n, int32_t m, int32_t p, const NodeDev &d,
                        int64_t stride_w, const qpn_avi_opts &o, double *x_dev, int64_t stride_x, const NodeWs &ws,
-                       NodeRoute route)
+                       NodeRoute route, int32_t *warm_list = nullptr)
 {
     hipStream_t s = ctx->stream;
     const int N = n + m;
     AviBatchArgs a{};
     a.batch = batch; a.N = N; a.z = d.z; a.status = d.st; a.resid = d.res; a.pivots = d.pv; a.active = d.act;
     a.check_tol = o.check_tol; a.piv_tol = o.piv_tol; a.feas_tol = o.feas_tol; a.comp_tol = o.comp_tol;
-    a.max_pivots = o.max_pivots; a.flags = o.flags & 0xFFFF;
+    // (the warm-start bit is this function's: the solve kernels see the flags of a call without it)
+    a.max_pivots = o.max_pivots; a.flags = o.flags & 0xFFFF & ~QPN_AVI_FLAG_WARM_DUALS;
     a.nd = NodeSrc{n, m, p, d.Q, d.R, d.q, d.A, d.B, d.l, d.u, d.w, stride_w, (h && h->sym && ctx->sym_route == 1) ? 1 : 0};
 #ifdef QPN_STAMPS
     a.stamps = g_stamps;
@@ -1180,6 +1181,17 @@ int solve_nodes_launch(qpn_ctx *ctx, qpn_nodes *h, int32_t batch, int32_t n, int
         if (schedules(h, batch, 4096) && (h->calls < 128 || (h->calls & 3) == 0)) a.sched_key = h->key;
         if (h && h->order_valid) a.order = h->order;
         else if (ctx->order_count == batch && (!h || ctx->order_user)) a.order = ctx->order;     // a caller-installed order also serves handles
+        // QPN_AVI_FLAG_WARM_DUALS: the warm kernel goes first, over the nodes of that order.  What it accepts is done; the
+        // indices of the others come back compacted in warm_list, padded with -1, and that list is the order of the cold
+        // launches below -- out-of-range entries leave a slot unsolved, so nothing waits for the count on the host.  The list is
+        // not the handle's own order, so such a sweep does not FILL the crash cache (crash_cache_mode; it reuses a valid one --
+        // the same bits either way), a mixed launch deals its two Stage A bodies by launch position as ever, and only the
+        // decliners feed the smoothed pivot counts of the schedule.
+        if (warm_list) {
+            HIPCHK(ctx, hipMemsetAsync(warm_list, 0xFF, ((size_t)batch + 1) * 4, s));
+            HIPCHK(ctx, qpn_launch_warm_nodes(a, warm_list, s));
+            a.order = warm_list;
+        }
         // resident symmetric n = m = 32 records: the first whole-batch sweep keeps the parameter-free part of the crash, the
         // later ones reuse it (same stream: no host synchronisation)
         const int crash = crash_cache_mode(ctx, h, batch, a.order == nullptr || (h && a.order == h->order));
@@ -1194,13 +1206,20 @@ int solve_nodes_launch(qpn_ctx *ctx, qpn_nodes *h, int32_t batch, int32_t n, int
         if (crash == 2 && llc_streams_crash(batch, n, m, p, ctx->llc_budget_mb)) a.crash_stream = 1;
         if (h) h->crash_streamed = a.crash_stream != 0;
         bool need_general;
-        if ((rc = declines_begin(ctx, h, a, &need_general)) != QPN_OK) return rc;
+        if (warm_list) {
+            // a sweep over a part of the nodes is no census of the fused kernel's declines: the handle uses what it knows and
+            // learns nothing from this one
+            nodes_poll_declines(h);
+            need_general = !(h && h->decl_state == 2);
+        } else if ((rc = declines_begin(ctx, h, a, &need_general)) != QPN_OK) return rc;
         HIPCHK(ctx, qpn_launch_avi_solve_schur_nodes(a, s));
         if (crash == 1) { h->crash_state = 1; h->crash_stream = s; }
         if (need_general && (rc = solve_general(ctx, a, ws, true, true)) != QPN_OK) return rc;
-        if ((rc = declines_end(ctx, h)) != QPN_OK) return rc;
+        if (!warm_list && (rc = declines_end(ctx, h)) != QPN_OK) return rc;
         if (h) {
             if (schedules(h, batch, 4096) && (rc = schedule_refresh(ctx, h, batch)) != QPN_OK) return rc;
+        } else if (warm_list) {
+            // (the pivot counts of this call are not those of a cold sweep: no schedule is made from them)
         } else if (ctx->auto_period > 0 && !ctx->order_user && d.pv && batch > 4096) {
             // automatic longest-first schedule for the NEXT calls over this batch (launches that fill the GPU only)
             if (ctx->auto_batch != batch) { ctx->auto_batch = batch; ctx->auto_calls = 0; }
@@ -1303,9 +1322,15 @@ int solve_nodes_any(qpn_ctx *ctx, qpn_nodes *h, int32_t batch, int32_t n, int32_
     double *hx = nullptr;
     if (x_ws) st.scratch(hx, (size_t)batch * n * 8);
     if (x) st.out2d(x_ws ? hx : d.z, (size_t)(x_ws ? n : N) * 8, x, (size_t)stride_x * 8, (size_t)n * 8, (size_t)batch);
+    // QPN_AVI_FLAG_WARM_DUALS: honoured by the 32-class when the caller's z carries a hint (z given, no cold start); the list of
+    // the nodes the warm kernel declines and its counter
+    const bool warm = route == NodeRoute::fused32 && (o.flags & QPN_AVI_FLAG_WARM_DUALS) && !(o.flags & QPN_AVI_FLAG_COLD_START);
+    int32_t *warm_list = nullptr;
+    if (warm) st.scratch(warm_list, ((size_t)batch + 1) * 4);
     int rc = st.begin();
     if (rc != QPN_OK) return rc;
-    rc = solve_nodes_launch(ctx, h, batch, n, m, p, d, stride_w, o, st.host ? hx : x, st.host ? (int64_t)n : stride_x, ws, route);
+    rc = solve_nodes_launch(ctx, h, batch, n, m, p, d, stride_w, o, st.host ? hx : x, st.host ? (int64_t)n : stride_x, ws, route,
+                            warm_list);
     if (rc != QPN_OK) return rc;
     return st.finish();
 }

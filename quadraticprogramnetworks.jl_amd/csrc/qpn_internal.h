@@ -219,6 +219,12 @@ hipError_t qpn_launch_avi_solve_schur(const AviBatchArgs &a, double *dbgS, doubl
                                       double *dbgh, hipStream_t stream);
 hipError_t qpn_launch_avi_solve_schur_nodes(const AviBatchArgs &a, hipStream_t stream);   // a.nd set, a.M unused
 
+// qpn_warm.hip: the n, m <= 32 node solve from the active set the multipliers of a.z name (QPN_AVI_FLAG_WARM_DUALS), one wavefront
+// per node, ahead of the cold launch.  Accepted nodes write their outputs (pivots = 0); the others write nothing and append their
+// index to dec_list -- a.batch + 1 words that the caller has set to -1 (the last one counts) --, which then serves as the cold
+// launch's order array: its -1 entries leave their slots unsolved.
+hipError_t qpn_launch_warm_nodes(const AviBatchArgs &a, int32_t *dec_list, hipStream_t stream);
+
 // qpn_avi_reg.hip
 hipError_t qpn_launch_avi_solve(const AviBatchArgs &a, hipStream_t stream);      // dispatcher: Schur kernel, then the register kernel
 hipError_t qpn_launch_avi_solve_reg(const AviBatchArgs &a, hipStream_t stream);  // register-tableau kernel

@@ -478,7 +478,9 @@ class Engine:
         results as assemble_nodes + solve_avi_batch without materialising M.  z = [x_d; lambda].
         x_out (optional, [batch, >= n] fp64, rows may be strided): the primal blocks are also written
         there by the solve itself -- the outer sweep's x[decision_inds] = x_opt[decision_inds]
-        (src/algorithm.jl:97-101)."""
+        (src/algorithm.jl:97-101).
+        With AVI_FLAG_WARM_DUALS in opts.flags (n, m <= 32) the multipliers of z0 name the active set every node starts from:
+        a node whose hint holds comes back with pivots = 0, the others are solved cold in the same call (include/qpn_hip.h)."""
         dev, Qc, Rc, qd, Ac, Bc, l, u, w, z0 = self._stage("solve_nodes", "Qc Rc qd Ac Bc l u w z0", f64=(Qc, Rc, qd, Ac, Bc, l, u, w, z0))
         batch, n = qd.shape
         m = l.shape[1]
@@ -966,7 +968,7 @@ class Nodes:
         eng._call("qpn_nodes_upload", self.batch, self.n, self.m, self.p, _ptr(Qc), _ptr(Rc), _ptr(qd), _ptr(Ac), _ptr(Bc), _ptr(l),
                   _ptr(u), eng._mem(dev), C.byref(h))
         self.h = h
-        self._fast = None
+        self._fast = [None, None]
 
     def close(self):
         if getattr(self, "h", None) and getattr(self.eng, "ctx", None):
@@ -995,15 +997,22 @@ class Nodes:
     def set_schedule(self, period=16):
         self.eng._call("qpn_nodes_set_schedule", self.h, int(period))
 
-    def solve(self, w, opts=None, want=("z", "resid", "pivots", "active"), out=None, x_out=None):
+    def solve(self, w, opts=None, want=("z", "resid", "pivots", "active"), out=None, x_out=None, warm=None):
         """One sweep over the resident nodes with parameters w ((p,) shared or (batch, p)); cold duals.  `want` names the
-        optional outputs (status always comes back); x_out as in Engine.solve_nodes."""
+        optional outputs (status always comes back); x_out as in Engine.solve_nodes.
+
+        warm = the z of an earlier sweep over these nodes ([batch, n + m], where w lives): its multipliers name the active set
+        every node starts from (QPN_AVI_FLAG_WARM_DUALS, include/qpn_hip.h; n, m <= 32, cold elsewhere).  A node whose hint
+        holds comes back with pivots = 0, every other one is solved cold in the same call.  warm may be out["z"] itself (the
+        sweep loop's form: the hint is overwritten by the solution).  The same through opts: with AVI_FLAG_WARM_DUALS set (and
+        AVI_FLAG_COLD_START clear) out["z"] carries the hint."""
         eng = self.eng
         # the sweep loop's call (same output buffers as the previous sweep, device parameters): everything but w's address is
         # what it was -- the checks and conversions below were done when these buffers were first seen
-        fast = self._fast
+        # (a cold and a warm sweep loop over one handle keep an entry each: [0] cold, [1] warm with the hint in out["z"])
+        fast = self._fast[warm is not None]
         if fast is not None and out is fast[0] and x_out is fast[1] and opts is None and _is_dev(w) and w.dtype is torch.float64 \
-                and w.stride(-1) == 1:
+                and w.stride(-1) == 1 and (warm is None or warm is out.get("z")):
             # the cached argument tail holds raw device addresses: it is valid only while every tensor it was built from is
             # the same object at the same address (a swapped or deleted dict entry, or a resized tensor, rebuilds it below),
             # and only for a w of the handle's own shape on the handle's device
@@ -1015,7 +1024,7 @@ class Nodes:
                 rc = eng.lib.qpn_solve_nodes_h(eng.ctx, self.h, w.data_ptr(), 0 if w.ndim == 1 else w.stride(0), *fast[2])
                 eng._chk(rc, "qpn_solve_nodes_h")
                 return out
-            self._fast = None
+            self._fast[warm is not None] = None
         dev, = eng._stage("Nodes.solve", "", raw=(w, x_out))    # (w has its own rule: its rows may be strided)
         if not dev:
             w = np.ascontiguousarray(w, dtype=np.float64)
@@ -1027,8 +1036,17 @@ class Nodes:
         if dev and w.device.index != eng.device:
             raise QpnError("w lives on another device than the engine")
         sw = 0 if w.ndim == 1 else int(w.stride(0) if dev else w.strides[0] // 8)
-        o = opts if opts is not None else eng.default_opts()
-        o.flags |= _lib.AVI_FLAG_COLD_START
+        o = AviOpts.from_buffer_copy(opts) if opts is not None else eng.default_opts()   # (the flags below are this call's)
+        if warm is not None:
+            o.flags = (o.flags | _lib.AVI_FLAG_WARM_DUALS) & ~_lib.AVI_FLAG_COLD_START
+            if _is_dev(warm) != dev or tuple(warm.shape) != (self.batch, N):
+                raise QpnError(f"warm must have shape ({self.batch}, {N}) and live where w lives")
+            want = tuple(want) + ("z",)
+        hinted = bool(o.flags & _lib.AVI_FLAG_WARM_DUALS) and not (o.flags & _lib.AVI_FLAG_COLD_START)
+        if hinted and warm is None and (out is None or out.get("z") is None):
+            raise QpnError("AVI_FLAG_WARM_DUALS: out['z'] has to carry the hint (or pass warm=)")
+        if not hinted:
+            o.flags |= _lib.AVI_FLAG_COLD_START
         if out is not None:
             # a caller-supplied set of output buffers is checked once, when it is first seen
             spec = dict(status=((self.batch,), np.int32), z=((self.batch, N), np.float64), resid=((self.batch,), np.float64),
@@ -1053,16 +1071,24 @@ class Nodes:
                        resid=eng._alloc(dev, (self.batch,), np.float64) if "resid" in want else None,
                        pivots=eng._alloc(dev, (self.batch,), np.int32) if "pivots" in want else None,
                        active=eng._alloc(dev, (self.batch, N), np.uint8) if "active" in want else None)
+        if warm is not None:
+            if out["z"] is None:
+                out["z"] = eng._alloc(dev, (self.batch, N), np.float64)
+            if warm is not out["z"]:                             # the hint goes in through z
+                if dev:
+                    out["z"].copy_(warm)
+                else:
+                    out["z"][...] = warm
         sx = eng._x_stride(x_out, dev, self.batch, self.n)
         tail = (_ptr(out["z"]), _ptr(out["status"]), _ptr(out["resid"]), _ptr(out["pivots"]), _ptr(out["active"]), C.byref(o),
                 eng._mem(dev), _ptr(x_out), sx)
         eng._call("qpn_solve_nodes_h", self.h, _ptr(w), sw, *tail)
-        if dev and opts is None:
+        if dev and opts is None and (warm is None or warm is out["z"]):
             # (o is kept alive: tail holds a reference to it; the tensors the addresses in `tail` came from are recorded with
             #  those addresses, so that the fast path above can tell when they are no longer what they were)
             snap = tuple((k, out.get(k), None if out.get(k) is None else out[k].data_ptr())
                          for k in ("z", "status", "resid", "pivots", "active"))
-            self._fast = (out, x_out, tail, o, snap, None if x_out is None else x_out.data_ptr(), w.device)
+            self._fast[warm is not None] = (out, x_out, tail, o, snap, None if x_out is None else x_out.data_ptr(), w.device)
         return out
 
     def verify(self, xd, w, tol=1e-4):

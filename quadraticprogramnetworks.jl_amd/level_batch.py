@@ -593,6 +593,120 @@ def _pool_blocks_local(qpn, pool: List[int], assign: Dict[int, Poly]):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# warm start of a node sweep from the previous sweep's active set (QPN_AVI_FLAG_WARM_DUALS)
+# ---------------------------------------------------------------------------------------------------------------------
+# False: every sweep of solve_level solves its nodes from cold duals (the code as it was).  True: solve_level keeps the last z of
+# every resident childless batch where the engine computes and hands it to the next sweep's solve as the hint; inner nodes and
+# pools stay cold.
+WARM_DUALS_ROUTE = False
+WARM_CHECK_TOL, WARM_PIV_TOL, WARM_COMP_TOL = 1e-6, 1e-11, 1e-2     # qpn_avi_default_opts
+
+
+def _eliminate(M, rhs, piv_tol):
+    """M y = rhs by Gaussian elimination with partial pivoting, rhs [rows, columns] -> y, or None when a pivot is below piv_tol
+    (or is no number)."""
+    M = np.array(M, dtype=np.float64); y = np.array(rhs, dtype=np.float64)
+    k = M.shape[0]
+    for j in range(k):
+        col = np.abs(M[j:, j])
+        if not np.all(np.isfinite(col)):
+            return None
+        pr = j + int(np.argmax(col))
+        if not abs(M[pr, j]) >= piv_tol:
+            return None
+        if pr != j:
+            M[[j, pr]] = M[[pr, j]]; y[[j, pr]] = y[[pr, j]]
+        f = M[j + 1:, j] / M[j, j]
+        M[j + 1:, j + 1:] -= np.outer(f, M[j, j + 1:])
+        y[j + 1:] -= np.outer(f, y[j])
+    for i in range(k - 1, -1, -1):
+        y[i] = (y[i] - M[i, i + 1:] @ y[i + 1:]) / M[i, i]
+    return y
+
+
+def node_postcheck(z, r, l, u, n, check_tol=WARM_CHECK_TOL, comp_tol=WARM_COMP_TOL):
+    """The post-check of a node solve on z = [x; lam] and r = M z + q (check_avi_solution, src/avi.jl:148-156, on the rows
+    [free STD x n | GAVI x m] with the bounds l, u of the m constraint rows), the natural-map residual and the active-set masks of
+    src/avi_solutions.jl:511-562 (x rows: bit c - 1 for code c, constraint rows: bit c + 3) -> (bad, resid, active)."""
+    z = np.asarray(z, dtype=np.float64); r = np.asarray(r, dtype=np.float64)
+    N = z.size
+    lk = np.concatenate([np.full(n, -INF), l]); uk = np.concatenate([np.full(n, INF), u])
+    gk = np.arange(N) >= n
+    pp = np.where(gk, r, z); dv = np.where(gk, z, r)
+    with np.errstate(invalid="ignore"):
+        bad = ((dv > check_tol) & (np.abs(pp - lk) > check_tol)) | ((dv < -check_tol) & (np.abs(pp - uk) > check_tol)) \
+            | (pp - lk < -check_tol) | (pp - uk > check_tol) | np.isnan(pp) | np.isnan(dv)
+        nres = np.abs(pp - np.minimum(np.maximum(pp - dv, lk), uk))
+        nres = np.where(np.isnan(nres), INF, nres)
+        approx = lambda x, y: (x == y) | (np.abs(x - y) <= comp_tol)
+        mask = np.where(approx(lk, uk), 8,
+                        1 * (approx(pp, lk) & (dv >= -comp_tol)) + 2 * ((lk - comp_tol <= pp) & (pp <= uk + comp_tol) & (np.abs(dv) <= comp_tol))
+                        + 4 * (approx(pp, uk) & (dv <= comp_tol))).astype(np.uint8)
+    mask = np.where(gk, mask << 4, mask).astype(np.uint8)
+    return bool(bad.any()), float(nres.max()) if N else 0.0, mask
+
+
+def warm_nodes_host(records, w, z_prev, opts=None):
+    """Numpy twin of the warm kernel (csrc/qpn_warm.hip).  records = (Qc, Rc, qd, Ac, Bc, l, u) in the ABI layout, w (p,) or
+    (batch, p), z_prev [batch, n + m]: its multipliers name the hint (side +1 where lambda > 0, -1 where < 0, 0 otherwise).
+    Per node the linear KKT system of the hinted rows, [[Qd, -A_act'], [A_act, 0]] [x; lam_act] = [-(qd + R w); bound_act -
+    B_act w], by block elimination through Qd and the k x k Schur block (partial pivoting, fp64).
+
+    THE ACCEPT RULE -- a node is accepted only if all of these hold:
+      every hinted multiplier is finite and its row has a finite bound on its side;  k <= n;  no pivot of the two eliminations
+      is below piv_tol;  every lam_act carries its side's sign (lam_act * side > 0);  the post-check of the cold solve passes
+      (check_tol, on the original blocks).
+    -> dict(accepted [batch] bool, z, status, resid, pivots, active): for an accepted node its point, status 1 (SUCCESS), the
+    natural-map residual, pivots 0 and the masks (comp_tol); a declined node keeps z_prev's row, status 0, resid NaN, pivots -1,
+    active 0 -- the caller solves it cold."""
+    Qc, Rc, qd, Ac, Bc, l, u = (np.asarray(a, dtype=np.float64) for a in records)
+    check_tol = getattr(opts, "check_tol", WARM_CHECK_TOL); piv_tol = getattr(opts, "piv_tol", WARM_PIV_TOL)
+    comp_tol = getattr(opts, "comp_tol", WARM_COMP_TOL)
+    batch, n = qd.shape
+    m = l.shape[1]
+    w = np.asarray(w, dtype=np.float64)
+    z_prev = np.asarray(z_prev, dtype=np.float64).reshape(batch, n + m)
+    out = dict(accepted=np.zeros(batch, bool), z=z_prev.copy(), status=np.zeros(batch, np.int32), resid=np.full(batch, np.nan),
+               pivots=np.full(batch, -1, np.int32), active=np.zeros((batch, n + m), np.uint8))
+    for b in range(batch):
+        Q, R, A, B = Qc[b].T, Rc[b].T.reshape(n, -1), Ac[b].T.reshape(m, n), Bc[b].T.reshape(m, -1)
+        wb = w if w.ndim == 1 else w[b]
+        lam0 = z_prev[b, n:]
+        if not np.all(np.isfinite(lam0)):
+            continue
+        side = np.sign(lam0).astype(np.int64)
+        rows = np.flatnonzero(side)
+        k = rows.size
+        bound = np.where(side > 0, l[b], u[b])[rows]
+        if k > n or not np.all(np.isfinite(bound)):
+            continue
+        q = qd[b] + R @ wb
+        c = B @ wb
+        Aa = A[rows]
+        W = _eliminate(Q, np.column_stack([Aa.T, -q]), piv_tol)            # [Qd^-1 A_act' | h]
+        if W is None:
+            continue
+        lam = np.zeros(0)
+        if k:
+            lam = _eliminate(Aa @ W[:, :k], (bound - c[rows] - Aa @ W[:, k])[:, None], piv_tol)
+            if lam is None:
+                continue
+            lam = lam[:, 0]
+            if not np.all(lam * side[rows] > 0):
+                continue
+        z = np.zeros(n + m)
+        z[:n] = W[:, k] + W[:, :k] @ lam
+        z[n + rows] = lam
+        r = np.concatenate([q + Q @ z[:n] - A.T @ z[n:], c + A @ z[:n]])
+        bad, resid, mask = node_postcheck(z, r, l[b], u[b], n, check_tol, comp_tol)
+        if bad:
+            continue
+        out["accepted"][b] = True
+        out["z"][b] = z; out["status"][b] = 1; out["resid"][b] = resid; out["pivots"][b] = 0; out["active"][b] = mask
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # solve_qep for a level: src/avi.jl:382-444 over the components
 # ---------------------------------------------------------------------------------------------------------------------
 def _leaf_batches(qpn, players, engine, free_eq=False):
@@ -607,6 +721,20 @@ def _leaf_batches(qpn, players, engine, free_eq=False):
             recs = [free_equalities(r) for r in recs]
         got = cache[key] = (recs, batch_records(recs))
     return got
+
+
+def _warm_sweep(b, h, eng, w):
+    """One sweep of a resident childless batch under WARM_DUALS_ROUTE: the outputs of the batch's last sweep stay where the
+    engine computes (b.warm_out, kept per handle), and their z goes into this sweep as the hint -- in place, the solution
+    overwrites it.  The first sweep of a handle has no hint and is the cold call."""
+    up, down = _movers(eng)
+    kept = getattr(b, "warm_out", None)
+    if kept is not None and kept[0] is h:
+        out = h.solve(up(w), out=kept[1], warm=kept[1]["z"])
+    else:
+        out = h.solve(up(w), want=("z", "resid", "pivots"))
+    b.warm_out = (h, out)
+    return dict(status=down(out["status"]), z=down(out["z"]))
 
 
 def solve_level(qpn, players: Sequence[int], x, assign: Optional[Dict[int, Poly]] = None, engine=None, reference_form=False,
@@ -669,7 +797,9 @@ def solve_level(qpn, players: Sequence[int], x, assign: Optional[Dict[int, Poly]
         xd, w = b.gather(x)
         z0 = np.zeros((len(b), b.n + b.m)); z0[:, :b.nx] = xd                       # duals cold, :404
         h = b.resident(eng) if static else None
-        if h is not None:
+        if h is not None and WARM_DUALS_ROUTE:
+            res = _warm_sweep(b, h, eng, w)
+        elif h is not None:
             res = h.solve(w, want=("z", "resid", "pivots"))
         elif isinstance(b, DeviceRecordBatch):
             res = b.solve(eng, w, z0)
