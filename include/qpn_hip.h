@@ -222,7 +222,12 @@ int qpn_solve_nodes_into(qpn_ctx *ctx, int32_t batch, int32_t n, int32_t m, int3
  * node, the crash cache adds 22 KB per node (symmetric records; the general variants -- 24 KB -- are not cached).  It is allocated
  * by the first sweep that would use it; when that memory cannot be had the handle runs uncached.  qpn_nodes_update of
  * QPN_NODE_QD or QPN_NODE_AD (and a change of QPN_OPT_SYM_ROUTE) drops it, the next sweep fills it again; updates of R, qd, B,
- * l, u keep it. */
+ * l, u keep it.
+ * Large records (64 < n <= 256, m <= 256: the blocked crash) have a cache of their own, off by default
+ * (QPN_OPT_CRASH_CACHE_BIG): the eliminated top half at the node's own size with the multipliers of every pass in its dead
+ * tiles, and S -- 8 (pad16(n) (pad16(n) + pad16(m) + 16) + m pad16(m + 1) + 2) + 1 bytes per node, 1 638 417 at n = m = 256
+ * (the records are 1.06 MB), 839 MB for 512 such nodes.  Same life cycle: allocated by the first sweep that would use it, the
+ * handle runs uncached when it cannot be had; an update of QPN_NODE_QD or QPN_NODE_AD drops it, R, qd, B, l, u keep it. */
 typedef struct qpn_nodes qpn_nodes;
 enum { QPN_NODE_QD = 0, QPN_NODE_R = 1, QPN_NODE_Q = 2, QPN_NODE_AD = 3, QPN_NODE_B = 4, QPN_NODE_L = 5, QPN_NODE_U = 6 };
 int qpn_nodes_upload(qpn_ctx *ctx, int32_t batch, int32_t n, int32_t m, int32_t p, const double *Qd,
@@ -236,7 +241,9 @@ int qpn_nodes_free(qpn_ctx *ctx, qpn_nodes *nodes);
  * in states 2, 3); info[2] = bit 0: a longest-first schedule is installed, bit 1: every Qd block of the records is bitwise
  * symmetric (settled by one pass when the records arrive or Qd is replaced; QPN_OPT_SYM_ROUTE), bit 2: a valid crash cache is
  * installed, bit 3: the crash cache is refused (QPN_OPT_CRASH_CACHE = 0, records of a shape or route that is not cached, or its
- * memory could not be had), bit 4: the last sweep streamed the crash cache past the last-level cache (QPN_OPT_LLC_BUDGET_MB);
+ * memory could not be had), bit 4: the last sweep streamed the crash cache past the last-level cache (QPN_OPT_LLC_BUDGET_MB),
+ * bit 5: a valid crash cache of the large class is installed (QPN_OPT_CRASH_CACHE_BIG), bit 6: that cache is refused (the option
+ * is 0, records of a shape or route that is not the blocked crash of large nodes, or its memory could not be had);
  * info[3] = sweeps since the last schedule reset. */
 int qpn_nodes_info(qpn_ctx *ctx, qpn_nodes *nodes, int32_t info[4]);
 int qpn_solve_nodes_h(qpn_ctx *ctx, qpn_nodes *nodes, const double *w, int64_t stride_w, double *z,
@@ -292,6 +299,14 @@ int qpn_ctx_set_auto_schedule(qpn_ctx *ctx, int32_t period);
  *                      records stay in the cache from sweep to sweep; smaller and larger sweeps use the default policy throughout.
  *                      0 = never, -1 = every sweep that reuses the crash cache (tests, A/B runs).  A policy of the loads only:
  *                      results are bit-identical.
+ *   QPN_OPT_CRASH_CACHE_BIG resident records on the blocked crash of large nodes (64 < n <= 256, m <= 256, any Qd): 1 = the first
+ *                      sweep over a handle keeps what the elimination makes of Qd and Ad alone (the multipliers of every rank-64
+ *                      pass, W = -H^-1 C, S = -Ad W, the smallest pivot, max |M| over H and C; 1.6 MB per node at n = m = 256) and
+ *                      later sweeps replay only the column that moves with w; 0 = never (default).  The pivot threshold
+ *                      1e-4 max(1, max |M|) takes in g = qd + R w: a cached sweep forms the same maximum from this sweep's g and
+ *                      declines exactly the nodes whose smallest cached pivot lies below it.  A node whose elimination stops in a
+ *                      filling sweep has no entry and is recomputed by every sweep until it gets through.  Results are
+ *                      bit-identical either way, and the same nodes decline.  Records passed per call are never cached.
  * A resident handle remembers under which option values it learned that none of its nodes declines; after a change it asks again
  * on its next sweep (another kernel variant applies its pivot test to slightly different numbers). */
 #define QPN_OPT_MID_ROUTE 1
@@ -299,6 +314,7 @@ int qpn_ctx_set_auto_schedule(qpn_ctx *ctx, int32_t period);
 #define QPN_OPT_SYM_ROUTE 3
 #define QPN_OPT_CRASH_CACHE 4
 #define QPN_OPT_LLC_BUDGET_MB 5
+#define QPN_OPT_CRASH_CACHE_BIG 6
 int qpn_ctx_set_option(qpn_ctx *ctx, int32_t option, int32_t value);
 
 /* ---- multi-GPU: replicas of the iterate on peer GPUs, written by the solve itself -----------------------

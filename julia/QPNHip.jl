@@ -861,6 +861,10 @@ const QPN_OPT_BIG_ROUTE = Int32(2)
 const QPN_OPT_SYM_ROUTE = Int32(3)
 const QPN_OPT_CRASH_CACHE = Int32(4)
 const QPN_OPT_LLC_BUDGET_MB = Int32(5)
+# CRASH_CACHE_BIG 1 = resident records of the large class (64 < n <= 256, m <= 256: the blocked crash) keep what the elimination
+# makes of Qd and Ad alone across sweeps (1.6 MB of HBM per node at n = m = 256 on top of 1.06 MB of records; bit-identical
+# results, the same nodes decline), 0 = never (default).
+const QPN_OPT_CRASH_CACHE_BIG = Int32(6)
 function set_option!(option::Integer, value::Integer)
     rc = ccall((:qpn_ctx_set_option, LIB), Cint, (Ptr{Cvoid}, Int32, Int32), ctx(), Int32(option), Int32(value))
     rc == 0 || error("qpn_ctx_set_option failed ($rc)")

@@ -41,6 +41,7 @@ OPT_BIG_ROUTE = 2
 OPT_SYM_ROUTE = 3
 OPT_CRASH_CACHE = 4
 OPT_LLC_BUDGET_MB = 5
+OPT_CRASH_CACHE_BIG = 6         # resident records of the large class (64 < n <= 256, m <= 256): 1 = keep the crash across sweeps (default 0)
 PARENT_SLOTS = 8               # QPN_PARENT_SLOTS: child pieces per item of qpn_assemble_parent_nodes
 
 

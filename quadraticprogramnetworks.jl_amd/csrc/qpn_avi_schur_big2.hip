@@ -94,13 +94,18 @@ __device__ bool invert16(const double *P, int ldp, double *D, double thr, double
 // is one contiguous megabyte (a row-major top half made every tile 16 rows 4 KB apart).
 
 // ---- K0: the padded top half, tile by tile, from the records (src/avi.jl:205-251: H = Qd, C = -Ad', g = qd + R w); max |M| -----
-__global__ __launch_bounds__(256) void schur_big2_convert(AviBatchArgs a, SchurBigWs w)
+// FILL (the crash cache of the large class, qpn_crash_big.hip): nodes that have an entry are left alone; max |M| over the H and
+// C tiles alone goes to bc.fig[1] (the threshold of a later sweep is made of it and that sweep's g).
+template <bool FILL>
+__global__ __launch_bounds__(256) void schur_big2_convert(AviBatchArgs a, SchurBigWs w, BigCrash bc)
 {
     const int tid = threadIdx.x, b = blockIdx.x, lane = tid & 63, lc = lane & 15, lq = lane >> 4, wave = tid >> 6;
+    if constexpr (FILL) { if (bc.flag[b]) return; }
     const int n = a.nd.n, m = a.nd.m, np_ = a.nd.p, N = n + m;
     const int nrt = pad16(n) >> 4, mct = pad16(m) >> 4, nct = nrt + mct + 1;
     __shared__ double sG[256];
     __shared__ double red[4];
+    __shared__ double red_hc[4];
     const double *Q_ = a.nd.Qd + (size_t)b * n * n;
     const double *A_ = a.nd.Ad + (size_t)b * m * n;
     const double *R_ = a.nd.R + (size_t)b * n * np_;
@@ -112,7 +117,7 @@ __global__ __launch_bounds__(256) void schur_big2_convert(AviBatchArgs a, SchurB
         sG[i] = s;
     }
     __syncthreads();
-    double mabs = 0.0;
+    double mabs = 0.0, mabs_hc = 0.0;
     // element (g, lane) of the initial tile t = I nct + J (clamped addresses, the value selected afterwards: no branches)
     auto elem = [&](int t, int g) -> double {
         const int I = t / nct, J = t - I * nct;
@@ -144,14 +149,21 @@ __global__ __launch_bounds__(256) void schur_big2_convert(AviBatchArgs a, SchurB
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 mabs = max_abs_nc(mabs, v[q][g]);
+                if constexpr (FILL) { if ((t0 + q) % nct != nct - 1) mabs_hc = max_abs_nc(mabs_hc, v[q][g]); }
                 if (t0 + q < nt) Tt[((size_t)(t0 + q) << 8) + g * 64 + lane] = v[q][g];
             }
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) { const double o = __shfl_xor(mabs, off, 64); mabs = o > mabs ? o : mabs; }
     if (lane == 0) red[wave] = mabs;
+    if constexpr (FILL) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) { const double o = __shfl_xor(mabs_hc, off, 64); mabs_hc = o > mabs_hc ? o : mabs_hc; }
+        if (lane == 0) red_hc[wave] = mabs_hc;
+    }
     __syncthreads();
     if (tid == 0) w.c[(size_t)b * N] = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));       // (until the S product writes c)
+    if constexpr (FILL) { if (tid == 0) bc.fig[2 * (size_t)b + 1] = fmax(fmax(red_hc[0], red_hc[1]), fmax(red_hc[2], red_hc[3])); }
 }
 
 // ---- K1: the elimination, rank-64 block pivots --------------------------------------------------------------------------
@@ -160,11 +172,15 @@ __global__ __launch_bounds__(256) void schur_big2_convert(AviBatchArgs a, SchurB
 // and the pivots it accepted under the threshold's lower bound 1e-4 are looked at again), status -4 behind it; MODE 2: the
 // remaining passes of those nodes.  (Two launches, not two code paths in one kernel: with both pass bodies inlined in one function
 // the register allocator spills a hundred registers.)
-template <int MODE>
-__global__ __launch_bounds__(TPB2, 1) void schur_big2_eliminate(AviBatchArgs a, SchurBigWs w)
+// FILL (the crash cache of the large class, qpn_crash_big.hip; w.Tt is the cache then): nodes that have an entry are left alone;
+// every pass stores its multipliers U' into the H column tiles that die with it; the smallest accepted pivot over all passes
+// goes to bc.fig[0], max |M| over H and C alone (g left out of the records route's running maximum) to bc.fig[1].
+template <int MODE, bool FILL = false>
+__global__ __launch_bounds__(TPB2, 1) void schur_big2_eliminate(AviBatchArgs a, SchurBigWs w, BigCrash bc)
 {
     constexpr bool RECORDS = MODE == 1;
     const int tid = threadIdx.x, b = blockIdx.x;
+    if constexpr (FILL) { if (bc.flag[b]) return; }
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, lc = lane & 15, lq = lane >> 4;
     const int n = a.nd.n, m = a.nd.m;
     const int nrt = pad16(n) >> 4, mct = pad16(m) >> 4, nct = nrt + mct + 1;      // row tiles; column tiles: H | C | the g tile
@@ -183,6 +199,7 @@ __global__ __launch_bounds__(TPB2, 1) void schur_big2_eliminate(AviBatchArgs a, 
     if (__syncthreads_count(bad_row) > 0) { if (tid == 0) a.status[b] = -1; return; }
 
     double minpiv = QINF, mabs = 0.0;
+    [[maybe_unused]] double mabs_g = 0.0;               // (FILL, RECORDS) max |g|, kept apart from mabs
     // the pivot threshold 1e-4 max(1, max |M|), max |M| from K0 (RECORDS: after pass 0)
     double thr = 1e-4;
     if constexpr (!RECORDS) { const double ms = w.c[(size_t)b * (n + m)]; thr = 1e-4 * (ms > 1.0 ? ms : 1.0); }
@@ -197,6 +214,7 @@ __global__ __launch_bounds__(TPB2, 1) void schur_big2_eliminate(AviBatchArgs a, 
             double s_ = a.nd.qd[(size_t)b * n + tid];
             for (int k = 0; k < np_; ++k) s_ = fma(R_[(size_t)k * n + tid], w_[k], s_);
             sG[tid] = s_;
+            if constexpr (FILL) mabs_g = fabs(s_);
         }
         __syncthreads();
     }
@@ -346,6 +364,15 @@ __global__ __launch_bounds__(TPB2, 1) void schur_big2_eliminate(AviBatchArgs a, 
                 for (int g = 0; g < 4; ++g) ua[4 * J + g] = acc[g];
             }
         }
+        if constexpr (FILL) {
+            // the block's own column tiles of this row tile are dead from here on (the pivot block went to LDS before the first
+            // barrier of the pass, u[] above was their last reader): they keep U'
+            if (owner) {
+#pragma unroll
+                for (int s = 0; s < 16; ++s)
+                    if (s < 4 * bw) tile(I, 4 * kb + (s >> 2))[(s & 3) * 64 + lane] = ua[s];
+            }
+        }
         STAMP(3);   // U'
         // ---- T <- T - U' V on the live column tiles, MC at a time (their pivot rows are in LDS): every wave walks its own row
         // tile with the next tile's loads in flight behind the sixteen MFMAs of the current one -- no barrier inside a mega-chunk
@@ -368,7 +395,12 @@ __global__ __launch_bounds__(TPB2, 1) void schur_big2_eliminate(AviBatchArgs a, 
 #pragma unroll
                         for (int g = 0; g < 4; ++g) nx[g] = FIRST ? t0(I, J0 + jj + 1, g) : tile(I, J0 + jj + 1)[g * 64 + lane];
                     }
-                    if constexpr (FIRST) {
+                    if constexpr (FIRST && FILL) {
+                        if (J0 + jj != nct - 1) {           // (the g tile: mabs_g)
+#pragma unroll
+                            for (int g = 0; g < 4; ++g) mabs = max_abs_nc(mabs, ct[g]);
+                        }
+                    } else if constexpr (FIRST) {
 #pragma unroll
                         for (int g = 0; g < 4; ++g) mabs = max_abs_nc(mabs, ct[g]);
                     }
@@ -407,6 +439,17 @@ __global__ __launch_bounds__(TPB2, 1) void schur_big2_eliminate(AviBatchArgs a, 
             double ms = sRed[0];
 #pragma unroll
             for (int k = 1; k < 16; ++k) ms = sRed[k] > ms ? sRed[k] : ms;
+            if constexpr (FILL) {
+                // ms is max |M| over H and C so far: kept, then g joins it (a maximum: the order does not matter)
+                if (tid == 0) { bc.fig[2 * (size_t)b] = sRed[16]; bc.fig[2 * (size_t)b + 1] = ms; }
+                __syncthreads();
+#pragma unroll
+                for (int off = 32; off > 0; off >>= 1) { const double o = __shfl_xor(mabs_g, off, 64); mabs_g = o > mabs_g ? o : mabs_g; }
+                if (lane == 0) sRed[wave] = mabs_g;
+                __syncthreads();
+#pragma unroll
+                for (int k = 0; k < 16; ++k) ms = sRed[k] > ms ? sRed[k] : ms;
+            }
             thr = 1e-4 * (ms > 1.0 ? ms : 1.0);
             if (sRed[16] < thr) { if (tid == 0) a.status[b] = -1; return; }
             if (tid == 0) w.c[(size_t)b * (n + m)] = ms;
@@ -418,13 +461,19 @@ __global__ __launch_bounds__(TPB2, 1) void schur_big2_eliminate(AviBatchArgs a, 
 #ifdef QPN_STAMPS
     if (tid == 0 && a.stamps) for (int k = 0; k < 8; ++k) a.stamps[(size_t)b * 8 + k] += stamp_acc[k];
 #endif
+    if constexpr (FILL && MODE != 1) {
+        // (wave 0 ran the inversions; pass 0 of the records route left its own minimum)
+        if (tid == 0) bc.fig[2 * (size_t)b] = MODE == 2 ? fmin(bc.fig[2 * (size_t)b], minpiv) : minpiv;
+    }
     // eliminated (-3: the S product takes it from here) / pass 0 done (-4: the remaining passes are another launch)
     if (tid == 0) a.status[b] = (MODE == 1 && kb_hi < (nrt + 3) / 4) ? -4 : -3;
 }
 
 // ---- K2: S = -Ad W and c = b - Ad h (b = B w): wave Is holds row tile Is of S, W | h crosses LDS in blocks of 64 rows x JC
 // column tiles (plain copies of tiles: the B operands as they stand); then the reduced problem's bounds and cold start
-__global__ __launch_bounds__(TPB2, 1) void schur_big2_sprod(AviBatchArgs a, SchurBigWs w)
+// FILL: S goes to the node's slot of the crash cache as well, and the node has an entry from here on.
+template <bool FILL>
+__global__ __launch_bounds__(TPB2, 1) void schur_big2_sprod(AviBatchArgs a, SchurBigWs w, BigCrash bc)
 {
     const int tid = threadIdx.x, b = blockIdx.x;
     if (a.status[b] != -3) return;
@@ -507,7 +556,12 @@ __global__ __launch_bounds__(TPB2, 1) void schur_big2_sprod(AviBatchArgs a, Schu
 #pragma unroll
                     for (int g = 0; g < 4; ++g) {
                         const int ri = 16 * Is + 4 * g + lq, cj = 16 * J + lc;
-                        if (J < mct) { if (ri < m && cj < m) Sg[(size_t)ri * ((m + 1 + 15) & ~15) + cj] = acc[jj][g]; }       // straight into the Lemke dictionary
+                        if (J < mct) {
+                            if (ri < m && cj < m) {
+                                Sg[(size_t)ri * ((m + 1 + 15) & ~15) + cj] = acc[jj][g];       // straight into the Lemke dictionary
+                                if constexpr (FILL) bc.S[(size_t)b * (size_t)bc.s_stride + (size_t)ri * ((m + 1 + 15) & ~15) + cj] = acc[jj][g];
+                            }
+                        }
                         else if (J == mct && lc == 0 && ri < m) cg[ri] = acc[jj][g];
                     }
                 }
@@ -521,6 +575,7 @@ __global__ __launch_bounds__(TPB2, 1) void schur_big2_sprod(AviBatchArgs a, Schu
         w.l2[vo + k] = a.nd.l[(size_t)b * m + k]; w.u2[vo + k] = a.nd.u[(size_t)b * m + k]; w.lam[vo + k] = 0.0;
     }
     if (tid == 0) { w.nsplit[b] = n; w.nred[b] = m; a.status[b] = -2; }
+    if constexpr (FILL) { if (tid == 0) bc.flag[b] = 1; }
 }
 
 // ---- finish: x = -(W lambda + h), post-check on the RECORDS ------------------------------------------------------------
@@ -646,9 +701,11 @@ bool qpn_schur_big2_shape(int n, int m)
     return n > 64 && n <= 256 && m >= 1 && m <= 256;
 }
 
-// Stage A from the records (a.nd set, a.N = n + m); `ws` is carved exactly as qpn_launch_schur_big_stage_a carves it (S row-major:
-// the delayed-update Lemke kernel behind it).
-hipError_t qpn_launch_schur_big2_stage_a(const AviBatchArgs &a, void *ws, double *dict, SchurBigWs *out, hipStream_t stream)
+namespace {
+
+// the workspace views of stage A: `ws` is carved exactly as qpn_launch_schur_big_stage_a carves it (S row-major: the delayed-update
+// Lemke kernel behind it)
+hipError_t big2_carve(const AviBatchArgs &a, void *ws, double *dict, SchurBigWs *out)
 {
     const int N = a.N, batch = a.batch;
     const size_t rows = (size_t)((N + 15) & ~15);
@@ -668,24 +725,53 @@ hipError_t qpn_launch_schur_big2_stage_a(const AviBatchArgs &a, void *ws, double
     w.S = dict; w.s_stride = (int64_t)N * (N + 1);      // item b's dictionary: dict + b N (N + 1), as the Lemke kernel addresses it
     *out = w;
     // (the top half of a node: pad16(n) rows of pad16(n) + pad16(m) + 16 doubles -- inside the stride above for n, m <= 256)
-    const size_t need = (size_t)((a.nd.n + 15) & ~15) * (size_t)(((a.nd.n + 15) & ~15) + ((a.nd.m + 15) & ~15) + 16);
+    const size_t need = qpn_big_crash_tt_doubles(a.nd.n, a.nd.m);
     if (!qpn_schur_big2_shape(a.nd.n, a.nd.m) || a.nd.n + a.nd.m != N || need > (size_t)w.tt_stride) return hipErrorInvalidValue;
+    return hipSuccess;
+}
+
+// the launches of stage A: conversion (shapes with padding) or pass 0 from the records, the remaining passes, the S product
+template <bool FILL>
+hipError_t big2_launch_stage_a(const AviBatchArgs &a, const SchurBigWs &w, const BigCrash &bc, hipStream_t stream)
+{
     static QpnLdsLimits lds_limits;
     constexpr int elim_bytes = LDS_DOUBLES * (int)sizeof(double);
-    if (const hipError_t e = lds_limits.raise({{schur_big2_eliminate<0>, elim_bytes}, {schur_big2_eliminate<1>, elim_bytes},
-                                               {schur_big2_eliminate<2>, elim_bytes}, {schur_big2_sprod, LDS_SPROD * (int)sizeof(double)}});
+    if (const hipError_t e = lds_limits.raise({{schur_big2_eliminate<0, FILL>, elim_bytes}, {schur_big2_eliminate<1, FILL>, elim_bytes},
+                                               {schur_big2_eliminate<2, FILL>, elim_bytes}, {schur_big2_sprod<FILL>, LDS_SPROD * (int)sizeof(double)}});
         e != hipSuccess)
         return e;
-    const dim3 grid((unsigned)batch);
+    const dim3 grid((unsigned)a.batch);
     if ((a.nd.n & 15) == 0 && (a.nd.m & 15) == 0) {
-        hipLaunchKernelGGL(schur_big2_eliminate<1>, grid, dim3(TPB2), LDS_DOUBLES * sizeof(double), stream, a, w);
-        if (a.nd.n > 64) hipLaunchKernelGGL(schur_big2_eliminate<2>, grid, dim3(TPB2), LDS_DOUBLES * sizeof(double), stream, a, w);
+        hipLaunchKernelGGL((schur_big2_eliminate<1, FILL>), grid, dim3(TPB2), LDS_DOUBLES * sizeof(double), stream, a, w, bc);
+        if (a.nd.n > 64) hipLaunchKernelGGL((schur_big2_eliminate<2, FILL>), grid, dim3(TPB2), LDS_DOUBLES * sizeof(double), stream, a, w, bc);
     } else {
-        hipLaunchKernelGGL(schur_big2_convert, grid, dim3(256), 0, stream, a, w);
-        hipLaunchKernelGGL(schur_big2_eliminate<0>, grid, dim3(TPB2), LDS_DOUBLES * sizeof(double), stream, a, w);
+        hipLaunchKernelGGL(schur_big2_convert<FILL>, grid, dim3(256), 0, stream, a, w, bc);
+        hipLaunchKernelGGL((schur_big2_eliminate<0, FILL>), grid, dim3(TPB2), LDS_DOUBLES * sizeof(double), stream, a, w, bc);
     }
-    hipLaunchKernelGGL(schur_big2_sprod, grid, dim3(TPB2), LDS_SPROD * sizeof(double), stream, a, w);
+    hipLaunchKernelGGL(schur_big2_sprod<FILL>, grid, dim3(TPB2), LDS_SPROD * sizeof(double), stream, a, w, bc);
     return hipGetLastError();
+}
+
+} // namespace
+
+// Stage A from the records (a.nd set, a.N = n + m)
+hipError_t qpn_launch_schur_big2_stage_a(const AviBatchArgs &a, void *ws, double *dict, SchurBigWs *out, hipStream_t stream)
+{
+    if (const hipError_t e = big2_carve(a, ws, dict, out); e != hipSuccess) return e;
+    return big2_launch_stage_a<false>(a, *out, BigCrash{}, stream);
+}
+
+// ... on a handle with a crash cache (qpn_crash_big.hip): the nodes' top halves live in the cache (its stride), not in the workspace
+hipError_t qpn_launch_schur_big2_stage_a_cached(const AviBatchArgs &a, void *ws, double *dict, SchurBigWs *out, const BigCrash &bc,
+                                                bool replay, bool fill, hipStream_t stream)
+{
+    if (const hipError_t e = big2_carve(a, ws, dict, out); e != hipSuccess) return e;
+    if ((size_t)bc.tt_stride < qpn_big_crash_tt_doubles(a.nd.n, a.nd.m) || (size_t)bc.s_stride < qpn_big_crash_s_doubles(a.nd.m))
+        return hipErrorInvalidValue;
+    out->Tt = bc.tt; out->tt_stride = bc.tt_stride;
+    if (replay) { if (const hipError_t e = qpn_launch_crash_big_replay(a, *out, dict, bc, stream); e != hipSuccess) return e; }
+    if (fill) { if (const hipError_t e = big2_launch_stage_a<true>(a, *out, bc, stream); e != hipSuccess) return e; }
+    return hipSuccess;
 }
 
 hipError_t qpn_launch_schur_big2_finish(const AviBatchArgs &a, const SchurBigWs &w, hipStream_t stream)

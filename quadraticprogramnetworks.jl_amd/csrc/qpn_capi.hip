@@ -44,6 +44,8 @@ struct qpn_ctx {
     int32_t sym_route = 1;
     // QPN_OPT_CRASH_CACHE: 1 = resident symmetric n = m = 32 records keep the parameter-free part of the crash across sweeps
     int32_t crash_cache = 1;
+    // QPN_OPT_CRASH_CACHE_BIG: 1 = resident records on the blocked crash of large nodes keep what Qd and Ad alone decide
+    int32_t crash_cache_big = 0;
     // QPN_OPT_LLC_BUDGET_MB: the share of the last-level cache, in MiB, that sweeps over the crash cache count on (llc_streams_crash,
     // qpn_internal.h); 0 = never stream the crash cache, -1 = always
     int32_t llc_budget_mb = kLlcBudgetMB;
@@ -341,6 +343,11 @@ int qpn_ctx_set_option(qpn_ctx *ctx, int32_t option, int32_t value)
         // (no new route epoch: cached sweeps return the same bits, so what a handle knows about its declines stays true)
         if (value < 0 || value > 1) return fail_arg(ctx, "qpn_ctx_set_option: QPN_OPT_CRASH_CACHE takes 0 or 1");
         ctx->crash_cache = value;
+        return QPN_OK;
+    case QPN_OPT_CRASH_CACHE_BIG:
+        // (no new route epoch either: the same bits, the same declines)
+        if (value < 0 || value > 1) return fail_arg(ctx, "qpn_ctx_set_option: QPN_OPT_CRASH_CACHE_BIG takes 0 or 1");
+        ctx->crash_cache_big = value;
         return QPN_OK;
     case QPN_OPT_LLC_BUDGET_MB:
         // (a cache policy of the loads: the same bits either way, no new route epoch)
@@ -963,6 +970,18 @@ struct qpn_nodes {
     hipStream_t crash_stream = nullptr;
     // did the last sweep fetch the crash cache with non-temporal loads?  (qpn_nodes_info bit 4)
     bool crash_streamed = false;
+    // crash cache of the large class (QPN_OPT_CRASH_CACHE_BIG; layout: BigCrash, qpn_internal.h): one allocation, top halves | S |
+    // figures, and a flag per node.  big_state as crash_state.  A node whose elimination stopped in a filling sweep has no entry
+    // and runs the filling kernels again in every sweep; big_census tells whether any such node is left (0 unknown, 1 the count
+    // of entries is on its way to the host, 2 every node has one: reuse sweeps launch the replay kernel alone, 3 some have none).
+    double *big = nullptr;
+    uint8_t *big_flag = nullptr;
+    int big_state = 0;
+    hipStream_t big_stream = nullptr;
+    int big_census = 0;
+    int32_t *big_cnt_dev = nullptr;
+    int32_t *big_cnt_host = nullptr;
+    hipEvent_t big_ev = nullptr;
 };
 
 namespace {
@@ -1018,6 +1037,76 @@ int crash_cache_mode(qpn_ctx *ctx, qpn_nodes *h, int32_t batch, bool own_order)
     return 1;
 }
 
+// ---- the crash cache of the large class ---------------------------------------------------------------------------------
+enum class NodeRoute;
+NodeRoute node_route(const qpn_ctx *ctx, int32_t n, int32_t m, const qpn_avi_opts &o);
+
+// Does the context's option set, and do the records, admit it?  (Records that the default options send down the blocked crash.)
+bool big_cache_applies(const qpn_ctx *ctx, const qpn_nodes *h);
+
+BigCrash big_cache_views(const qpn_nodes *h)
+{
+    BigCrash bc{};
+    bc.tt_stride = (int64_t)qpn_big_crash_tt_doubles(h->n, h->m);
+    bc.s_stride = (int64_t)qpn_big_crash_s_doubles(h->m);
+    bc.tt = h->big;
+    bc.S = bc.tt + (size_t)h->batch * (size_t)bc.tt_stride;
+    bc.fig = bc.S + (size_t)h->batch * (size_t)bc.s_stride;
+    bc.flag = h->big_flag;
+    return bc;
+}
+
+void big_cache_poll(qpn_nodes *h)
+{
+    if (h->big_census == 1 && hipEventQuery(h->big_ev) == hipSuccess) h->big_census = (*h->big_cnt_host == h->batch) ? 2 : 3;
+}
+// the entries are void (Qd or Ad replaced, the records moved off the route): the memory stays for the next fill
+void big_cache_drop(qpn_nodes *h)
+{
+    if (h->big_census == 1) (void)hipEventSynchronize(h->big_ev);
+    h->big_census = 0;
+    if (h->big_state == 1) h->big_state = 0;
+}
+void big_cache_free(qpn_nodes *h)
+{
+    if (h->big_ev) { (void)hipEventSynchronize(h->big_ev); (void)hipEventDestroy(h->big_ev); }
+    if (h->big) (void)hipFree(h->big);
+    if (h->big_flag) (void)hipFree(h->big_flag);
+    if (h->big_cnt_dev) (void)hipFree(h->big_cnt_dev);
+    if (h->big_cnt_host) (void)hipHostFree(h->big_cnt_host);
+    h->big = nullptr; h->big_flag = nullptr; h->big_cnt_dev = nullptr; h->big_cnt_host = nullptr; h->big_ev = nullptr;
+}
+
+// Mode of the next sweep of the blocked crash over the handle's records: 2 reuse, 1 fill, 0 run uncached (crash_cache_mode's
+// rules).  A sweep under a caller-made order fills nothing: it reuses a cache in which every node has an entry and runs
+// uncached otherwise.
+int big_cache_mode(qpn_ctx *ctx, qpn_nodes *h, int32_t batch, bool own_order)
+{
+    if (!h || batch != h->batch || !big_cache_applies(ctx, h) || h->big_state < 0) return 0;
+    big_cache_poll(h);
+    if (h->big_state == 1) {
+        if (h->big_stream != ctx->stream) return 0;     // (filled on another stream: no ordering with it)
+        return (own_order || h->big_census == 2) ? 2 : 0;
+    }
+    if (!own_order) return 0;
+    if (!h->big) {
+        const BigCrash v = big_cache_views(h);
+        const size_t doubles = (size_t)batch * ((size_t)v.tt_stride + (size_t)v.s_stride + 2);
+        hipError_t e = hipMalloc((void **)&h->big, doubles * sizeof(double));
+        if (e == hipSuccess) e = hipMalloc((void **)&h->big_flag, (size_t)batch);
+        if (e == hipSuccess) e = hipMalloc((void **)&h->big_cnt_dev, 4);
+        if (e == hipSuccess) e = hipHostMalloc((void **)&h->big_cnt_host, 4, hipHostMallocDefault);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&h->big_ev, hipEventDisableTiming);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();            // (the failed allocation is not this sweep's error)
+            big_cache_free(h);
+            h->big_state = -1;
+            return 0;
+        }
+    }
+    return 1;
+}
+
 // one pass over the resident Qd blocks (behind the copies on the context's stream); waits for the answer
 hipError_t nodes_check_symmetry(qpn_ctx *ctx, qpn_nodes *h)
 {
@@ -1043,6 +1132,7 @@ void nodes_sync_route(qpn_ctx *ctx, qpn_nodes *h)
     h->decl_state = 0;
     h->route_epoch = ctx->route_epoch;
     if (h->crash_state == 1) h->crash_state = 0;        // the variants keep different tile sets
+    if (!big_cache_applies(ctx, h)) big_cache_drop(h);  // the records have moved off the blocked crash
 }
 
 // Which kernels take the nodes of one qpn_solve_nodes call: decided once per call, from the shape, the pivot budget and the
@@ -1063,6 +1153,13 @@ NodeRoute node_route(const qpn_ctx *ctx, int32_t n, int32_t m, const qpn_avi_opt
     if (budget && ctx->mid_route == 1 && (qpn_schur_wg_shape(n, m) || qpn_schur_wg2_shape(n, m))) return NodeRoute::mid;
     if (budget && qpn_schur_big2_shape(n, m)) return NodeRoute::big2;
     return NodeRoute::general;
+}
+
+bool big_cache_applies(const qpn_ctx *ctx, const qpn_nodes *h)
+{
+    qpn_avi_opts o;
+    qpn_avi_default_opts(&o);
+    return ctx->crash_cache_big == 1 && node_route(ctx, h->n, h->m, o) == NodeRoute::big2;
 }
 
 struct NodeWs {                 // workspace of the general kernels: assembled blocks, large-item dictionaries (null when not carved)
@@ -1260,7 +1357,25 @@ int solve_nodes_launch(qpn_ctx *ctx, qpn_nodes *h, int32_t batch, int32_t n, int
         SchurBigWs sw{};
         double *dict = ws.big;
         void *sb = ws.big + (size_t)batch * (size_t)N * (size_t)(N + 1);
-        HIPCHK(ctx, qpn_launch_schur_big2_stage_a(a, sb, dict, &sw, s));
+        // QPN_OPT_CRASH_CACHE_BIG, resident records: the first whole-batch sweep runs stage A in the handle's cache and keeps what
+        // Qd and Ad alone decide; later sweeps replay the g column of the nodes that have an entry and run the filling kernels
+        // for the others, as long as there are any (same stream: no host synchronisation)
+        const int crash = big_cache_mode(ctx, h, batch, !(ctx->order_user && ctx->order_count == batch));
+        if (crash) {
+            const BigCrash bc = big_cache_views(h);
+            if (crash == 1) HIPCHK(ctx, hipMemsetAsync(h->big_flag, 0, (size_t)batch, s));
+            const bool fill = crash == 1 || h->big_census != 2;
+            HIPCHK(ctx, qpn_launch_schur_big2_stage_a_cached(a, sb, dict, &sw, bc, crash == 2, fill, s));
+            if (crash == 1) { h->big_state = 1; h->big_stream = s; h->big_census = 0; }
+            if (fill && h->big_census != 1) {
+                HIPCHK(ctx, qpn_launch_crash_big_count(batch, h->big_flag, h->big_cnt_dev, s));
+                HIPCHK(ctx, hipMemcpyAsync(h->big_cnt_host, h->big_cnt_dev, 4, hipMemcpyDeviceToHost, s));
+                HIPCHK(ctx, hipEventRecord(h->big_ev, s));
+                h->big_census = 1;
+            }
+        } else {
+            HIPCHK(ctx, qpn_launch_schur_big2_stage_a(a, sb, dict, &sw, s));
+        }
         // Stage B: resident records with symmetric Qd blocks (a.nd.sym) go through block principal pivoting first; whatever it
         // leaves (and every node otherwise) is the delayed-update Lemke kernel's
         // (a caller-set pivot budget is Lemke's to count: its pivots are the unit of max_pivots)
@@ -1373,6 +1488,7 @@ int qpn_nodes_free(qpn_ctx *ctx, qpn_nodes *h)
     if (h->buf) (void)hipFree(h->buf);
     if (h->crash) (void)hipFree(h->crash);
     if (h->crash_flag) (void)hipFree(h->crash_flag);
+    big_cache_free(h);
     if (h->decl_dev) (void)hipFree(h->decl_dev);
     if (h->decl_host) (void)hipHostFree(h->decl_host);
     if (h->order) (void)hipFree(h->order);
@@ -1438,6 +1554,7 @@ int qpn_nodes_update(qpn_ctx *ctx, qpn_nodes *h, int32_t field, const double *da
     h->decl_state = 0;
     // the crash cache is made of Qd and Ad alone: R, qd, B, l, u keep it (the memory stays for the next fill)
     if ((field == QPN_NODE_QD || field == QPN_NODE_AD) && h->crash_state == 1) h->crash_state = 0;
+    if (field == QPN_NODE_QD || field == QPN_NODE_AD) big_cache_drop(h);
     if (field == QPN_NODE_QD) HIPCHK(ctx, nodes_check_symmetry(ctx, h));
     return QPN_OK;
 }
@@ -1459,7 +1576,10 @@ int qpn_nodes_info(qpn_ctx *ctx, qpn_nodes *h, int32_t info[4])
     info[0] = h->decl_state; info[1] = h->decl_state >= 2 ? *h->decl_host : 0;
     const bool cached = h->crash_state == 1 && crash_cache_applies(ctx, h);
     const bool refused = !crash_cache_applies(ctx, h) || h->crash_state < 0;
-    info[2] = (h->order_valid ? 1 : 0) | (h->sym ? 2 : 0) | (cached ? 4 : 0) | (refused ? 8 : 0) | (h->crash_streamed ? 16 : 0); info[3] = h->calls;
+    info[2] = (h->order_valid ? 1 : 0) | (h->sym ? 2 : 0) | (cached ? 4 : 0) | (refused ? 8 : 0) | (h->crash_streamed ? 16 : 0);
+    const bool big_ok = big_cache_applies(ctx, h);
+    info[2] |= (h->big_state == 1 && big_ok ? 32 : 0) | (!big_ok || h->big_state < 0 ? 64 : 0);
+    info[3] = h->calls;
     return QPN_OK;
 }
 

@@ -203,6 +203,31 @@ bool qpn_schur_big2_shape(int n, int m);
 hipError_t qpn_launch_schur_big2_stage_a(const AviBatchArgs &a, void *ws, double *dict, SchurBigWs *out, hipStream_t stream);   // a.nd set
 hipError_t qpn_launch_schur_big2_finish(const AviBatchArgs &a, const SchurBigWs &w, hipStream_t stream);
 
+// Crash cache of the large class (QPN_OPT_CRASH_CACHE_BIG; qpn_crash_big.hip): what stage A above makes of Qd and Ad alone, per
+// node of a resident handle --
+//   tt    the node's top half at its own size, pad16(n) x (pad16(n) + pad16(m) + 16) doubles, tile by tile as stage A lays it
+//         out: the C tiles hold W, the H column tiles of pass kb (dead once that pass has formed its multipliers) hold the
+//         rank-64 multipliers U' of that pass (register s of row tile I: tile (I, 4 kb + s / 4), doubles (s % 4) 64 + lane), the
+//         g tiles are rewritten by every sweep (h of that sweep: the finish kernel reads W | h from here);
+//   S     m rows of pad16(m + 1) doubles, the layout stage A writes into the Lemke dictionary;
+//   fig   [0] the smallest pivot accepted over all passes, [1] max |M| over the H and C entries (g left out);
+//   flag  1 = the node has an entry (its elimination got through in a filling sweep).
+struct BigCrash {
+    double *tt, *S, *fig;
+    uint8_t *flag;
+    int64_t tt_stride, s_stride;
+};
+inline size_t qpn_big_crash_tt_doubles(int n, int m) { return (size_t)((n + 15) & ~15) * (size_t)(((n + 15) & ~15) + ((m + 15) & ~15) + 16); }
+inline size_t qpn_big_crash_s_doubles(int m) { return (size_t)m * (size_t)((m + 1 + 15) & ~15); }
+// Stage A on a handle with a crash cache: nodes with an entry are replayed (g, h, c, bounds; S copied into the dictionary), and
+// when `fill` is set the others run the elimination and the S product in their slot of the cache and leave an entry behind if
+// they get through.  Same outputs, bit for bit, as qpn_launch_schur_big2_stage_a.
+hipError_t qpn_launch_schur_big2_stage_a_cached(const AviBatchArgs &a, void *ws, double *dict, SchurBigWs *out, const BigCrash &bc,
+                                                bool replay, bool fill, hipStream_t stream);
+hipError_t qpn_launch_crash_big_replay(const AviBatchArgs &a, const SchurBigWs &w, double *dict, const BigCrash &bc, hipStream_t stream);
+// number of nodes with an entry -> *count (device)
+hipError_t qpn_launch_crash_big_count(int batch, const uint8_t *flag, int32_t *count, hipStream_t stream);
+
 // qpn_avi_schur_wg.hip: node records with 49 <= max(n, m) <= 64 in ONE fused workgroup kernel (crash, Lemke, read-back, post-check; no workspace)
 bool qpn_schur_wg_shape(int n, int m);
 hipError_t qpn_launch_schur_wg_nodes(const AviBatchArgs &a, hipStream_t stream);

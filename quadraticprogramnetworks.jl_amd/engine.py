@@ -987,12 +987,13 @@ class Nodes:
         self.eng._call("qpn_nodes_update", self.h, self.FIELDS[field], _ptr(data), self.eng._mem(dev))
 
     def info(self):
-        """dict(decline_state, declined, scheduled, symmetric, crash_cached, crash_refused, crash_streamed, sweeps) -- see
-        qpn_nodes_info."""
+        """dict(decline_state, declined, scheduled, symmetric, crash_cached, crash_refused, crash_streamed, big_cached, big_refused,
+        sweeps) -- see qpn_nodes_info."""
         a = (C.c_int32 * 4)()
         self.eng._call("qpn_nodes_info", self.h, a)
         return dict(decline_state=a[0], declined=a[1], scheduled=bool(a[2] & 1), symmetric=bool(a[2] & 2), crash_cached=bool(a[2] & 4),
-                    crash_refused=bool(a[2] & 8), crash_streamed=bool(a[2] & 16), sweeps=a[3])
+                    crash_refused=bool(a[2] & 8), crash_streamed=bool(a[2] & 16), big_cached=bool(a[2] & 32),
+                    big_refused=bool(a[2] & 64), sweeps=a[3])
 
     def set_schedule(self, period=16):
         self.eng._call("qpn_nodes_set_schedule", self.h, int(period))
