@@ -1,172 +1,21 @@
 // qpn_capi.hip -- the extern "C" boundary of libqpn_hip.so (include/qpn_hip.h).
 // Host-side staging, argument checking and error mapping only; all arithmetic is in the
 // HIP kernels (qpn_avi_*.hip, qpn_kkt.hip, qpn_verify.hip, ...).  No exceptions cross the ABI.
+// The node sweep and the resident node handle are qpn_capi_nodes.hip; qpn_capi.h is what the two units share.
 #include <algorithm>
 #include <climits>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
-#include <string>
-#include <vector>
 
-#include "qpn_internal.h"
+#include "qpn_capi.h"
 
-struct qpn_ctx {
-    int device = 0;
-    hipStream_t own_stream = nullptr;
-    hipStream_t stream = nullptr;
-    std::string last_error;
-    // grow-only device workspace used by the host-pointer paths and multi-kernel entry points
-    void *ws = nullptr;
-    size_t ws_bytes = 0;
-    // schedule hint of qpn_solve_nodes (qpn_order_nodes_by_pivots / qpn_set_node_order): context-owned
-    int32_t *order = nullptr;
-    int32_t order_count = 0;      // 0 = no hint installed
-    int32_t order_cap = 0;
-    // automatic schedule hint (qpn_ctx_set_auto_schedule): refreshed from a call's own pivot counts every `period`
-    // calls of the same batch size, unless the caller has installed a hint of their own
-    int32_t auto_period = 16;
-    int32_t auto_calls = 0;
-    int32_t auto_batch = 0;
-    bool order_user = false;
-    // replicas of the iterate on peer GPUs (qpn_set_primal_mirrors)
-    const double *mirror_own = nullptr;
-    size_t mirror_bytes = 0;
-    int32_t mirror_count = 0;
-    double *mirror_peer[QPN_MAX_MIRRORS] = {};
-    // route of mid-size node records (qpn_ctx_set_option QPN_OPT_MID_ROUTE): 1 the fused kernels (one wavefront per node up to 48,
-    // one workgroup per node beyond), 0 the route of the large nodes / the general kernels (the tests' cross-check)
-    int32_t mid_route = 1;
-    // every route option change bumps this; a resident handle that learned its declines under another epoch asks again
-    int32_t route_epoch = 0;
-    // QPN_OPT_SYM_ROUTE: 1 = resident records whose Qd blocks are all bitwise symmetric take the kernel variants that use it
-    int32_t sym_route = 1;
-    // QPN_OPT_CRASH_CACHE: 1 = resident symmetric n = m = 32 records keep the parameter-free part of the crash across sweeps
-    int32_t crash_cache = 1;
-    // QPN_OPT_CRASH_CACHE_BIG: 1 = resident records on the blocked crash of large nodes keep what Qd and Ad alone decide
-    int32_t crash_cache_big = 0;
-    // QPN_OPT_LLC_BUDGET_MB: the share of the last-level cache, in MiB, that sweeps over the crash cache count on (llc_streams_crash,
-    // qpn_internal.h); 0 = never stream the crash cache, -1 = always
-    int32_t llc_budget_mb = kLlcBudgetMB;
-};
+#ifdef QPN_STAMPS
+unsigned long long *g_stamps = nullptr;
+#endif
 
 namespace {
-
-int fail_hip(qpn_ctx *ctx, hipError_t e, const char *where)
-{
-    if (ctx) {
-        ctx->last_error = std::string(where) + ": " + hipGetErrorString(e);
-    }
-    return QPN_ERR_HIP;
-}
-int fail_arg(qpn_ctx *ctx, const char *msg)
-{
-    if (ctx) ctx->last_error = msg;
-    return QPN_ERR_ARG;
-}
-int fail_arg(qpn_ctx *ctx, const char *who, const char *what) { return fail_arg(ctx, (std::string(who) + ": " + what).c_str()); }
-
-#define HIPCHK(ctx, call)                                        \
-    do {                                                         \
-        hipError_t e__ = (call);                                 \
-        if (e__ != hipSuccess) return fail_hip(ctx, e__, #call); \
-    } while (0)
-
-int order_reserve(qpn_ctx *ctx, int32_t count);
-
-// The buffers of one entry point call.  Device mode (QPN_MEM_DEVICE): the caller's pointers go to the kernels as they are.
-// Host mode (QPN_MEM_HOST): each buffer gets a slot (256-B aligned) of the ctx workspace, begin() uploads the inputs in the
-// order they were registered, finish() downloads the outputs in that order and waits for them.  Scratch and library-owned
-// host data get a slot in both modes.  A slot of 0 bytes is a null pointer.  begin() writes the registered pointer variables
-// and finish() reads them: they have to live until the call returns.
-struct Stage {
-    qpn_ctx *ctx;
-    const char *who;
-    bool host, bad_mem;
-    size_t need = 0;
-    struct Slot { void **dev; size_t off; };
-    struct Copy { void **dev; void *host; size_t bytes, hpitch = 0, dpitch = 0, rows = 0; };   // rows > 0: 2-D, rows x bytes
-    std::vector<Slot> slots;
-    std::vector<Copy> up, down;
-
-    Stage(qpn_ctx *c, int mem, const char *w)
-        : ctx(c), who(w), host(mem == QPN_MEM_HOST), bad_mem(mem != QPN_MEM_HOST && mem != QPN_MEM_DEVICE) {}
-    int check() const { return bad_mem ? fail_arg(ctx, who, "bad mem kind") : QPN_OK; }
-
-    template <class T> void carve(T *&dev, size_t bytes)
-    {
-        dev = nullptr;
-        if (!bytes) return;
-        slots.push_back({(void **)&dev, need});
-        need += (bytes + 255) & ~(size_t)255;
-    }
-    // an input; `pad` extra bytes keep the pointer valid when the array is empty or absent
-    template <class T> void in(T *&dev, const void *src, size_t bytes, size_t pad = 0)
-    {
-        if (!host) { dev = (T *)src; return; }
-        carve(dev, src || pad ? bytes + pad : 0);
-        if (src && bytes) up.push_back({(void **)&dev, (void *)src, bytes});
-    }
-    // an output (host mode carves it even when the caller does not want it)
-    template <class T> void out(T *&dev, void *dst, size_t bytes, size_t pad = 0)
-    {
-        if (!host) { dev = (T *)dst; return; }
-        carve(dev, bytes + pad);
-        if (dst && bytes) down.push_back({(void **)&dev, dst, bytes});
-    }
-    // an optional output: host mode carves it only when the caller wants it (the kernel skips a null one)
-    template <class T> void out_opt(T *&dev, void *dst, size_t bytes)
-    {
-        dev = nullptr;
-        if (dst || !host) out(dev, dst, bytes);
-    }
-    template <class T> void inout(T *&dev, T *p, size_t bytes, bool upload)
-    {
-        if (!host) { dev = p; return; }
-        carve(dev, bytes);
-        if (p && upload) up.push_back({(void **)&dev, p, bytes});
-        if (p) down.push_back({(void **)&dev, p, bytes});
-    }
-    // host mode: `rows` blocks of `bytes` from a staged buffer (pitch dpitch) to the caller's (pitch hpitch)
-    template <class T> void out2d(T *const &dev, size_t dpitch, void *dst, size_t hpitch, size_t bytes, size_t rows)
-    {
-        if (host) down.push_back({(void **)&dev, dst, bytes, hpitch, dpitch, rows});
-    }
-    template <class T> void scratch(T *&dev, size_t bytes) { carve(dev, bytes); }
-    // host data the kernels read in either mode (index maps, offsets)
-    template <class T> void lib_in(T *&dev, const void *src, size_t bytes)
-    {
-        carve(dev, bytes);
-        if (bytes) up.push_back({(void **)&dev, (void *)src, bytes});
-    }
-
-    int begin()
-    {
-        if (int rc = check()) return rc;
-        if (need > ctx->ws_bytes) {
-            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-            if (ctx->ws) HIPCHK(ctx, hipFree(ctx->ws));
-            ctx->ws = nullptr; ctx->ws_bytes = 0;
-            size_t want = need + need / 4;
-            HIPCHK(ctx, hipMalloc(&ctx->ws, want));
-            ctx->ws_bytes = want;
-        }
-        for (auto &s : slots) *s.dev = static_cast<char *>(ctx->ws) + s.off;
-        for (auto &c : up) HIPCHK(ctx, hipMemcpyAsync(*c.dev, c.host, c.bytes, hipMemcpyHostToDevice, ctx->stream));
-        return QPN_OK;
-    }
-    int finish()
-    {
-        if (!host) return QPN_OK;
-        for (auto &c : down) {
-            if (c.rows) HIPCHK(ctx, hipMemcpy2DAsync(c.host, c.hpitch, *c.dev, c.dpitch, c.bytes, c.rows, hipMemcpyDeviceToHost, ctx->stream));
-            else HIPCHK(ctx, hipMemcpyAsync(c.host, *c.dev, c.bytes, hipMemcpyDeviceToHost, ctx->stream));
-        }
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        return QPN_OK;
-    }
-};
 
 // The tolerances of the LP entries' solves over polyhedra of r rows in d variables: the caller's options or, without, the defaults;
 // max_iters <= 0 is 50 (r + d) + 100.
@@ -175,30 +24,6 @@ LpTol lp_tol(const qpn_lp_opts *opts, int32_t r, int32_t d)
     qpn_lp_opts o;
     if (opts) o = *opts; else qpn_lp_default_opts(&o);
     return LpTol{o.piv_tol, o.feas_tol, o.opt_tol, o.check_tol, o.max_iters > 0 ? o.max_iters : 50 * (r + d) + 100};
-}
-
-struct NodeSizes { size_t Q, R, q, A, B, lu, w; };
-NodeSizes node_sizes(int32_t batch, int32_t n, int32_t m, int32_t p, int64_t stride_w)
-{
-    NodeSizes s;
-    s.Q = (size_t)batch * n * n * 8; s.R = (size_t)batch * n * p * 8; s.q = (size_t)batch * n * 8;
-    s.A = (size_t)batch * m * n * 8; s.B = (size_t)batch * m * p * 8; s.lu = (size_t)batch * m * 8;
-    // (w goes up only when p > 0: a stride alone names no data)
-    s.w = p ? (stride_w ? (size_t)(batch - 1) * stride_w + p : (size_t)p) * 8 : 0;
-    return s;
-}
-
-struct NodeDev {                // device views of one call's node records, parameters and outputs
-    const double *Q, *R, *q, *A, *B, *l, *u, *w;
-    double *z; int32_t *st; double *res; int32_t *pv; uint8_t *act;
-};
-
-// the seven record arrays (the padded ones stay valid when empty)
-void stage_records(Stage &st, NodeDev &d, const NodeSizes &sz, const double *Qd, const double *R, const double *qd,
-                   const double *Ad, const double *B, const double *l, const double *u)
-{
-    st.in(d.Q, Qd, sz.Q); st.in(d.R, R, sz.R, 8); st.in(d.q, qd, sz.q); st.in(d.A, Ad, sz.A, 8);
-    st.in(d.B, B, sz.B, 8); st.in(d.l, l, sz.lu, 8); st.in(d.u, u, sz.lu, 8);
 }
 
 // the number of recipes of one row of masks: the product of its codes' popcounts, saturating
@@ -416,7 +241,6 @@ int qpn_debug_schur_stage_a(qpn_ctx *ctx, int32_t batch, int32_t N, const double
 
 #ifdef QPN_STAMPS
 // diagnostic builds only: where the next device-path solve writes its [batch][8] cycle sums
-static unsigned long long *g_stamps = nullptr;
 int qpn_debug_set_stamps(void *p) { g_stamps = static_cast<unsigned long long *>(p); return 0; }
 #endif
 
@@ -925,688 +749,6 @@ int qpn_assemble_pools(qpn_ctx *ctx, const qpn_pool_shape *sh, int form, int32_t
     return QPN_OK;
 }
 
-int qpn_solve_nodes(qpn_ctx *ctx, int32_t batch, int32_t n, int32_t m, int32_t p, const double *Qd,
-                    const double *R, const double *qd, const double *Ad, const double *B,
-                    const double *l, const double *u, const double *w, int64_t stride_w, double *z,
-                    int32_t *status, double *resid, int32_t *pivots, uint8_t *active,
-                    const qpn_avi_opts *opts, int mem)
-{
-    return qpn_solve_nodes_into(ctx, batch, n, m, p, Qd, R, qd, Ad, B, l, u, w, stride_w, z, status, resid,
-                                pivots, active, opts, mem, nullptr, 0);
-}
-
-} // extern "C"
-
-// resident node records (qpn_nodes_upload): library-owned copies in HBM + what depends on them alone
-struct qpn_nodes {
-    int device = 0;
-    int32_t batch = 0, n = 0, m = 0, p = 0;
-    double *buf = nullptr;                      // one allocation, the seven arrays carved from it
-    double *f[7] = {};                          // QPN_NODE_QD .. QPN_NODE_U
-    size_t fbytes[7] = {};
-    // does any node of these records need the general kernel?  0 unknown, 1 a count is on its way to the host,
-    // 2 none (sweeps are ONE launch), 3 some
-    int decl_state = 0;
-    int32_t *decl_dev = nullptr;                // device counter the fused kernel adds to
-    int32_t *decl_host = nullptr;               // pinned host copy
-    hipEvent_t decl_ev = nullptr;
-    // longest-first schedule of these nodes
-    int32_t *order = nullptr;
-    int32_t *key = nullptr;                     // smoothed pivot counts the order is made from
-    bool order_valid = false;
-    int32_t period = 16, calls = 0;
-    // every Qd block bitwise symmetric?  Settled when the records arrive (one pass, nodes_check_symmetry)
-    bool sym = false;
-    // the context's route epoch the decline knowledge was learned under (qpn_ctx_set_option bumps it: another kernel variant
-    // applies its pivot test to slightly different numbers, so "no node declines" has to be asked again)
-    int32_t route_epoch = 0;
-    // crash cache (symmetric n = m = 32 records): what Stage A of the fused kernel makes of Qd and Ad alone -- the panels U',
-    // the tiles W~ and S, a pass / fail flag per node (layout: qpn_internal.h) -- 22 528 bytes per node, allocated by the first
-    // sweep that would use it.  crash_state: 0 none, 1 valid (filled by one whole-batch sweep on crash_stream), -1 its memory
-    // could not be had (not asked for again).
-    double *crash = nullptr;
-    uint8_t *crash_flag = nullptr;
-    int crash_state = 0;
-    hipStream_t crash_stream = nullptr;
-    // did the last sweep fetch the crash cache with non-temporal loads?  (qpn_nodes_info bit 4)
-    bool crash_streamed = false;
-    // crash cache of the large class (QPN_OPT_CRASH_CACHE_BIG; layout: BigCrash, qpn_internal.h): one allocation, top halves | S |
-    // figures, and a flag per node.  big_state as crash_state.  A node whose elimination stopped in a filling sweep has no entry
-    // and runs the filling kernels again in every sweep; big_census tells whether any such node is left (0 unknown, 1 the count
-    // of entries is on its way to the host, 2 every node has one: reuse sweeps launch the replay kernel alone, 3 some have none).
-    double *big = nullptr;
-    uint8_t *big_flag = nullptr;
-    int big_state = 0;
-    hipStream_t big_stream = nullptr;
-    int big_census = 0;
-    int32_t *big_cnt_dev = nullptr;
-    int32_t *big_cnt_host = nullptr;
-    hipEvent_t big_ev = nullptr;
-};
-
-namespace {
-
-// Does the context's option set, and do the records, admit the crash cache?  (Symmetric n = m = 32 records on the symmetric
-// route; the other size classes and the general variants run uncached.)
-bool crash_cache_applies(const qpn_ctx *ctx, const qpn_nodes *h)
-{
-    return ctx->crash_cache == 1 && h->n == 32 && h->m == 32 && h->sym && ctx->sym_route == 1;
-}
-
-// Mixed reuse sweeps (qpn_avi_schur.hip, CRASH = 3): the share of the wavefronts that compute Stage A although the cache is
-// valid, in 1/256ths (0: plain reuse sweeps), and the tail rule -- how many launch positions BEFORE the last partial round of
-// the resident set already reuse, in 1/256ths of that set.  Both are tuning constants (-D for variant builds); no result
-// depends on them.
-#ifndef QPN_CRASH_MIX_SHARE
-#define QPN_CRASH_MIX_SHARE 96
-#endif
-#ifndef QPN_CRASH_MIX_TAIL
-#define QPN_CRASH_MIX_TAIL 0
-#endif
-constexpr int kCrashMixShare = QPN_CRASH_MIX_SHARE;
-constexpr int kCrashMixTail = QPN_CRASH_MIX_TAIL;
-static_assert(kCrashMixShare >= 0 && kCrashMixShare <= 256 && kCrashMixTail >= 0, "share in 1/256ths; tail >= 0");
-
-// First launch position of the all-reuse tail: the last partial round of the resident set (it is bound by latency, not by HBM:
-// the shorter chain wins there) and kCrashMixTail / 256 of a round before it.
-int32_t crash_mix_reuse_from(int32_t batch)
-{
-    const int64_t full = (int64_t)(batch / kResidentMI355X) * kResidentMI355X;
-    const int64_t from = full - (int64_t)kResidentMI355X * kCrashMixTail / 256;
-    return (int32_t)(from > 0 ? from : 0);
-}
-
-// Crash-cache mode of the next fused sweep over the handle's records: 2 reuse, 1 fill, 0 run uncached.  The buffer is
-// allocated here, once; a failed allocation is remembered and the handle runs uncached from then on.
-int crash_cache_mode(qpn_ctx *ctx, qpn_nodes *h, int32_t batch, bool own_order)
-{
-    if (!h || batch != h->batch || !crash_cache_applies(ctx, h) || h->crash_state < 0) return 0;
-    if (h->crash_state == 1) return h->crash_stream == ctx->stream ? 2 : 0;      // (filled on another stream: no ordering with it)
-    // a caller-installed order may leave nodes out (entries outside 0 .. count - 1): such a sweep fills nothing
-    if (!own_order) return 0;
-    if (!h->crash) {
-        hipError_t e = hipMalloc((void **)&h->crash, (size_t)batch * kCrashDoubles * sizeof(double));
-        if (e == hipSuccess) e = hipMalloc((void **)&h->crash_flag, (size_t)batch);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();            // (the failed allocation is not this sweep's error)
-            if (h->crash) (void)hipFree(h->crash);
-            h->crash = nullptr; h->crash_flag = nullptr; h->crash_state = -1;
-            return 0;
-        }
-    }
-    return 1;
-}
-
-// ---- the crash cache of the large class ---------------------------------------------------------------------------------
-enum class NodeRoute;
-NodeRoute node_route(const qpn_ctx *ctx, int32_t n, int32_t m, const qpn_avi_opts &o);
-
-// Does the context's option set, and do the records, admit it?  (Records that the default options send down the blocked crash.)
-bool big_cache_applies(const qpn_ctx *ctx, const qpn_nodes *h);
-
-BigCrash big_cache_views(const qpn_nodes *h)
-{
-    BigCrash bc{};
-    bc.tt_stride = (int64_t)qpn_big_crash_tt_doubles(h->n, h->m);
-    bc.s_stride = (int64_t)qpn_big_crash_s_doubles(h->m);
-    bc.tt = h->big;
-    bc.S = bc.tt + (size_t)h->batch * (size_t)bc.tt_stride;
-    bc.fig = bc.S + (size_t)h->batch * (size_t)bc.s_stride;
-    bc.flag = h->big_flag;
-    return bc;
-}
-
-void big_cache_poll(qpn_nodes *h)
-{
-    if (h->big_census == 1 && hipEventQuery(h->big_ev) == hipSuccess) h->big_census = (*h->big_cnt_host == h->batch) ? 2 : 3;
-}
-// the entries are void (Qd or Ad replaced, the records moved off the route): the memory stays for the next fill
-void big_cache_drop(qpn_nodes *h)
-{
-    if (h->big_census == 1) (void)hipEventSynchronize(h->big_ev);
-    h->big_census = 0;
-    if (h->big_state == 1) h->big_state = 0;
-}
-void big_cache_free(qpn_nodes *h)
-{
-    if (h->big_ev) { (void)hipEventSynchronize(h->big_ev); (void)hipEventDestroy(h->big_ev); }
-    if (h->big) (void)hipFree(h->big);
-    if (h->big_flag) (void)hipFree(h->big_flag);
-    if (h->big_cnt_dev) (void)hipFree(h->big_cnt_dev);
-    if (h->big_cnt_host) (void)hipHostFree(h->big_cnt_host);
-    h->big = nullptr; h->big_flag = nullptr; h->big_cnt_dev = nullptr; h->big_cnt_host = nullptr; h->big_ev = nullptr;
-}
-
-// Mode of the next sweep of the blocked crash over the handle's records: 2 reuse, 1 fill, 0 run uncached (crash_cache_mode's
-// rules).  A sweep under a caller-made order fills nothing: it reuses a cache in which every node has an entry and runs
-// uncached otherwise.
-int big_cache_mode(qpn_ctx *ctx, qpn_nodes *h, int32_t batch, bool own_order)
-{
-    if (!h || batch != h->batch || !big_cache_applies(ctx, h) || h->big_state < 0) return 0;
-    big_cache_poll(h);
-    if (h->big_state == 1) {
-        if (h->big_stream != ctx->stream) return 0;     // (filled on another stream: no ordering with it)
-        return (own_order || h->big_census == 2) ? 2 : 0;
-    }
-    if (!own_order) return 0;
-    if (!h->big) {
-        const BigCrash v = big_cache_views(h);
-        const size_t doubles = (size_t)batch * ((size_t)v.tt_stride + (size_t)v.s_stride + 2);
-        hipError_t e = hipMalloc((void **)&h->big, doubles * sizeof(double));
-        if (e == hipSuccess) e = hipMalloc((void **)&h->big_flag, (size_t)batch);
-        if (e == hipSuccess) e = hipMalloc((void **)&h->big_cnt_dev, 4);
-        if (e == hipSuccess) e = hipHostMalloc((void **)&h->big_cnt_host, 4, hipHostMallocDefault);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&h->big_ev, hipEventDisableTiming);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();            // (the failed allocation is not this sweep's error)
-            big_cache_free(h);
-            h->big_state = -1;
-            return 0;
-        }
-    }
-    return 1;
-}
-
-// one pass over the resident Qd blocks (behind the copies on the context's stream); waits for the answer
-hipError_t nodes_check_symmetry(qpn_ctx *ctx, qpn_nodes *h)
-{
-    h->sym = false;
-    hipError_t e = hipMemsetAsync(h->decl_dev, 0, 4, ctx->stream);       // (the decline counter is idle: no solve is in flight)
-    if (e == hipSuccess) e = qpn_launch_qd_asymmetry(h->batch, h->n, h->f[QPN_NODE_QD], h->decl_dev, ctx->stream);
-    int32_t asym = 1;
-    if (e == hipSuccess) e = hipMemcpyAsync(&asym, h->decl_dev, 4, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e == hipSuccess) h->sym = asym == 0;
-    return e;
-}
-
-void nodes_poll_declines(qpn_nodes *h)
-{
-    if (h && h->decl_state == 1 && hipEventQuery(h->decl_ev) == hipSuccess) h->decl_state = (*h->decl_host == 0) ? 2 : 3;
-}
-// a route option changed since the handle last learned its declines: forget the answer (after the count in flight has landed)
-void nodes_sync_route(qpn_ctx *ctx, qpn_nodes *h)
-{
-    if (!h || h->route_epoch == ctx->route_epoch) return;
-    if (h->decl_state == 1) (void)hipEventSynchronize(h->decl_ev);
-    h->decl_state = 0;
-    h->route_epoch = ctx->route_epoch;
-    if (h->crash_state == 1) h->crash_state = 0;        // the variants keep different tile sets
-    if (!big_cache_applies(ctx, h)) big_cache_drop(h);  // the records have moved off the blocked crash
-}
-
-// Which kernels take the nodes of one qpn_solve_nodes call: decided once per call, from the shape, the pivot budget and the
-// context's route options.
-enum class NodeRoute {
-    fused32,    // n, m <= 32: the fused MFMA kernel (qpn_avi_schur.hip)
-    mid,        // 33 .. 128: the fused mid-size kernels (qpn_avi_schur48.hip, qpn_avi_schur_wg.hip, qpn_avi_schur_wg2.hip)
-    big2,       // n 65 .. 256, m <= 256: the blocked crash straight from the records (qpn_avi_schur_big2.hip)
-    general,    // assembled blocks on qpn_launch_avi_solve / qpn_launch_avi_solve_big
-};
-
-NodeRoute node_route(const qpn_ctx *ctx, int32_t n, int32_t m, const qpn_avi_opts &o)
-{
-    if (n <= 32 && m <= 32 && m >= 1) return NodeRoute::fused32;
-    // the crash of the larger fused routes makes n pivots: a caller-set budget has to leave Lemke at least one
-    const bool budget = o.max_pivots <= 0 || o.max_pivots - n >= 1;
-    // QPN_OPT_MID_ROUTE = 0 sends the mid-size nodes down the general route
-    if (budget && ctx->mid_route == 1 && (qpn_schur_wg_shape(n, m) || qpn_schur_wg2_shape(n, m))) return NodeRoute::mid;
-    if (budget && qpn_schur_big2_shape(n, m)) return NodeRoute::big2;
-    return NodeRoute::general;
-}
-
-bool big_cache_applies(const qpn_ctx *ctx, const qpn_nodes *h)
-{
-    qpn_avi_opts o;
-    qpn_avi_default_opts(&o);
-    return ctx->crash_cache_big == 1 && node_route(ctx, h->n, h->m, o) == NodeRoute::big2;
-}
-
-struct NodeWs {                 // workspace of the general kernels: assembled blocks, large-item dictionaries (null when not carved)
-    double *M, *q, *l, *u; uint8_t *kind; double *big;
-};
-
-// Decline protocol of the fused routes.  Which nodes a fused kernel declines (status = -1) depends on Qd, Ad, l, u alone (block
-// pivots of H, equality rows), never on w: a handle asks once -- the kernel counts its declines into decl_dev, declines_end sends
-// the count to the host behind an event -- and leaves the general launches out once it knows that none does.
-// *need_general: whether the general launches behind the fused kernel are needed.
-int declines_begin(qpn_ctx *ctx, qpn_nodes *h, AviBatchArgs &a, bool *need_general)
-{
-    *need_general = true;
-    if (!h) return QPN_OK;
-    nodes_poll_declines(h);
-    *need_general = h->decl_state != 2;
-    if (h->decl_state == 0) {
-        HIPCHK(ctx, hipMemsetAsync(h->decl_dev, 0, 4, ctx->stream));
-        a.decl_count = h->decl_dev;
-    }
-    return QPN_OK;
-}
-
-int declines_end(qpn_ctx *ctx, qpn_nodes *h)
-{
-    if (!h || h->decl_state != 0) return QPN_OK;
-    HIPCHK(ctx, hipMemcpyAsync(h->decl_host, h->decl_dev, 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipEventRecord(h->decl_ev, ctx->stream));
-    h->decl_state = 1;
-    return QPN_OK;
-}
-
-// Does the handle keep a longest-first schedule for launches of this size?  Only for launches beyond the fused kernel's resident
-// set (`from` nodes): a smaller one has no tail to shorten.
-bool schedules(const qpn_nodes *h, int32_t batch, int32_t from) { return h && h->period > 0 && batch > from; }
-
-// The handle's longest-first schedule for the NEXT sweeps: the fused kernel keeps the smoothed pivot counts h->key up to date,
-// the order is re-sorted from them every `period` sweeps while they settle (eight refreshes), every 4 x period afterwards: the
-// sort is a one-workgroup launch (14 us) that the next sweep waits for.
-int schedule_refresh(qpn_ctx *ctx, qpn_nodes *h, int32_t batch)
-{
-    const int32_t per = h->calls < 8 * h->period ? h->period : 4 * h->period;
-    if (h->calls % per == 0) {
-        HIPCHK(ctx, qpn_launch_order_by_pivots(nullptr, batch, h->order, ctx->stream, h->key));
-        h->order_valid = true;
-    }
-    h->calls++;
-    return QPN_OK;
-}
-
-// the replicas of the iterate on peer GPUs (qpn_set_primal_mirrors): every primal block the kernel stores to x goes there too
-void set_mirrors(const qpn_ctx *ctx, AviBatchArgs &a, ptrdiff_t x_off)
-{
-    a.n_mirror = ctx->mirror_count;
-    for (int k = 0; k < ctx->mirror_count; ++k) a.mirror[k] = ctx->mirror_peer[k] + x_off;
-}
-
-// The general kernels, over the nodes a fused route declined (gated: status = -1) or over all of them.  The 32-class's is ONE
-// small scan-mode register launch (assemble_in_scan: its waves pick the flagged nodes, assemble their blocks into the workspace
-// and solve them); every other route assembles the blocks first and solves them on qpn_launch_avi_solve / _big.
-int solve_general(qpn_ctx *ctx, const AviBatchArgs &a, const NodeWs &ws, bool gated, bool assemble_in_scan)
-{
-    if (!ws.M) return fail_arg(ctx, "qpn_solve_nodes: internal error (no workspace for the general path)");
-    hipStream_t s = ctx->stream;
-    const int N = a.N;
-    AviBatchArgs g = a;
-    g.decl_count = nullptr;
-    g.M = ws.M; g.strideM = (int64_t)N * N; g.q = ws.q; g.l = ws.l; g.u = ws.u; g.kind = ws.kind; g.stride_kind = N;
-    if (gated) { g.only_if = a.status; g.only_if_value = -1; }
-    if (assemble_in_scan) {
-        g.scan = 1; g.assemble_first = 1;
-        HIPCHK(ctx, qpn_launch_avi_solve_reg(g, s));
-        return QPN_OK;
-    }
-    const NodeSrc &r = a.nd;
-    HIPCHK(ctx, qpn_launch_assemble_nodes(a.batch, r.n, r.m, r.p, r.Qd, r.R, r.qd, r.Ad, r.B, r.l, r.u, r.w, r.stride_w, ws.M,
-                                          ws.q, ws.l, ws.u, ws.kind, s, g.only_if, g.only_if_value));
-    if (N > 64) HIPCHK(ctx, qpn_launch_avi_solve_big(g, ws.big, s));
-    else HIPCHK(ctx, qpn_launch_avi_solve(g, s));
-    return QPN_OK;
-}
-
-// The launches of one sweep over device-resident records and outputs.  `h` (may be null) owns the records:
-// its decline knowledge and its schedule are used and refreshed.  ws = workspace of the general kernels (not carved
-// only when h knows that no node declines).
-int solve_nodes_launch(qpn_ctx *ctx, qpn_nodes *h, int32_t batch, int32_t n, int32_t m, int32_t p, const NodeDev &d,
-                       int64_t stride_w, const qpn_avi_opts &o, double *x_dev, int64_t stride_x, const NodeWs &ws,
-                       NodeRoute route, int32_t *warm_list = nullptr)
-{
-    hipStream_t s = ctx->stream;
-    const int N = n + m;
-    AviBatchArgs a{};
-    a.batch = batch; a.N = N; a.z = d.z; a.status = d.st; a.resid = d.res; a.pivots = d.pv; a.active = d.act;
-    a.check_tol = o.check_tol; a.piv_tol = o.piv_tol; a.feas_tol = o.feas_tol; a.comp_tol = o.comp_tol;
-    // (the warm-start bit is this function's: the solve kernels see the flags of a call without it)
-    a.max_pivots = o.max_pivots; a.flags = o.flags & 0xFFFF & ~QPN_AVI_FLAG_WARM_DUALS;
-    a.nd = NodeSrc{n, m, p, d.Q, d.R, d.q, d.A, d.B, d.l, d.u, d.w, stride_w, (h && h->sym && ctx->sym_route == 1) ? 1 : 0};
-#ifdef QPN_STAMPS
-    a.stamps = g_stamps;
-#endif
-    // replicas on peer GPUs: only when the whole written range lies inside the registered buffer
-    const size_t x_span = x_dev ? ((size_t)(batch - 1) * (size_t)stride_x + (size_t)n) * 8 : 0;
-    const bool mirrored = x_dev && ctx->mirror_count > 0 && (const char *)x_dev >= (const char *)ctx->mirror_own &&
-                          (const char *)x_dev + x_span <= (const char *)ctx->mirror_own + ctx->mirror_bytes;
-    const ptrdiff_t x_off = mirrored ? x_dev - ctx->mirror_own : 0;
-    bool x_in_kernel = false;
-    int rc = QPN_OK;
-    if (route == NodeRoute::fused32) {
-        // the fused kernel, and the general kernel behind it, write the primal blocks themselves
-        if (x_dev) { a.x = x_dev; a.stride_x = stride_x; x_in_kernel = true; }
-        if (mirrored) set_mirrors(ctx, a, x_off);
-        // schedule hint (longest first): the handle's own, else the context's
-        // the smoothed counts are fed by every sweep while the schedule settles (128 sweeps), by every fourth one afterwards:
-        // a sample of the sweeps tells the order as well, and the solve kernel's read-modify-write of its node's key is
-        // 0.5 % of the sweep
-        if (schedules(h, batch, 4096) && (h->calls < 128 || (h->calls & 3) == 0)) a.sched_key = h->key;
-        if (h && h->order_valid) a.order = h->order;
-        else if (ctx->order_count == batch && (!h || ctx->order_user)) a.order = ctx->order;     // a caller-installed order also serves handles
-        // QPN_AVI_FLAG_WARM_DUALS: the warm kernel goes first, over the nodes of that order.  What it accepts is done; the
-        // indices of the others come back compacted in warm_list, padded with -1, and that list is the order of the cold
-        // launches below -- out-of-range entries leave a slot unsolved, so nothing waits for the count on the host.  The list is
-        // not the handle's own order, so such a sweep does not FILL the crash cache (crash_cache_mode; it reuses a valid one --
-        // the same bits either way), a mixed launch deals its two Stage A bodies by launch position as ever, and only the
-        // decliners feed the smoothed pivot counts of the schedule.
-        if (warm_list) {
-            HIPCHK(ctx, hipMemsetAsync(warm_list, 0xFF, ((size_t)batch + 1) * 4, s));
-            HIPCHK(ctx, qpn_launch_warm_nodes(a, warm_list, s));
-            a.order = warm_list;
-        }
-        // resident symmetric n = m = 32 records: the first whole-batch sweep keeps the parameter-free part of the crash, the
-        // later ones reuse it (same stream: no host synchronisation)
-        const int crash = crash_cache_mode(ctx, h, batch, a.order == nullptr || (h && a.order == h->order));
-        if (crash) { a.crash = h->crash; a.crash_flag = h->crash_flag; a.crash_mode = crash; }
-        // a reuse sweep beyond the resident set is a mixed launch: kCrashMixShare / 256 of its wavefronts compute Stage A, which
-        // trades HBM bytes for fp64-pipe cycles (the two variants saturate one each); the tail reuses (the shorter chain)
-        if (crash == 2 && kCrashMixShare > 0 && batch > kResidentMI355X) {
-            a.crash_share = kCrashMixShare;
-            a.crash_reuse_from = crash_mix_reuse_from(batch);
-        }
-        // ... and it streams the crash cache past the last-level cache when that lets the node records stay there until the next sweep
-        if (crash == 2 && llc_streams_crash(batch, n, m, p, ctx->llc_budget_mb)) a.crash_stream = 1;
-        if (h) h->crash_streamed = a.crash_stream != 0;
-        bool need_general;
-        if (warm_list) {
-            // a sweep over a part of the nodes is no census of the fused kernel's declines: the handle uses what it knows and
-            // learns nothing from this one
-            nodes_poll_declines(h);
-            need_general = !(h && h->decl_state == 2);
-        } else if ((rc = declines_begin(ctx, h, a, &need_general)) != QPN_OK) return rc;
-        HIPCHK(ctx, qpn_launch_avi_solve_schur_nodes(a, s));
-        if (crash == 1) { h->crash_state = 1; h->crash_stream = s; }
-        if (need_general && (rc = solve_general(ctx, a, ws, true, true)) != QPN_OK) return rc;
-        if (!warm_list && (rc = declines_end(ctx, h)) != QPN_OK) return rc;
-        if (h) {
-            if (schedules(h, batch, 4096) && (rc = schedule_refresh(ctx, h, batch)) != QPN_OK) return rc;
-        } else if (warm_list) {
-            // (the pivot counts of this call are not those of a cold sweep: no schedule is made from them)
-        } else if (ctx->auto_period > 0 && !ctx->order_user && d.pv && batch > 4096) {
-            // automatic longest-first schedule for the NEXT calls over this batch (launches that fill the GPU only)
-            if (ctx->auto_batch != batch) { ctx->auto_batch = batch; ctx->auto_calls = 0; }
-            if (ctx->auto_calls % ctx->auto_period == 0) {
-                if ((rc = order_reserve(ctx, batch)) != QPN_OK) return rc;
-                HIPCHK(ctx, qpn_launch_order_by_pivots(d.pv, batch, ctx->order, s));
-                ctx->order_count = batch;
-            }
-            ctx->auto_calls++;
-        }
-    } else if (route == NodeRoute::mid) {
-        // mid-size nodes (n, m <= 128): one wavefront (max(n, m) <= 48) or one workgroup per node straight from the records, ONE
-        // launch; what they decline (status = -1) is assembled and solved by the general kernels in gated launches
-        bool need_general;
-        if ((rc = declines_begin(ctx, h, a, &need_general)) != QPN_OK) return rc;
-        AviBatchArgs f = a;
-        // the kernel writes the primal blocks into the iterate itself once it is known that nothing declines (the general
-        // kernels behind it do not); until then the strided copy below does
-        if (x_dev && !need_general) {
-            f.x = x_dev; f.stride_x = stride_x; x_in_kernel = true;
-            if (mirrored) set_mirrors(ctx, f, x_off);
-        }
-        // the handle's longest-first schedule as in the 32-class (launches beyond the resident set only: 2 048 wavefronts of the
-        // one-wavefront kernel, 1 024 workgroups of the 49-64 class, 256 of the 65-128 class)
-        const bool one_wave = qpn_schur48_shape(n, m), two_role = qpn_schur_wg2_shape(n, m);
-        const bool sched = schedules(h, batch, one_wave ? 2048 : (two_role ? 256 : 1024));
-        if (sched) { f.sched_key = h->key; if (h->order_valid) f.order = h->order; }
-        if (two_role) HIPCHK(ctx, qpn_launch_schur_wg2_nodes(f, s));
-        else if (one_wave) HIPCHK(ctx, qpn_launch_avi_solve_schur48_nodes(f, s));
-        else HIPCHK(ctx, qpn_launch_schur_wg_nodes(f, s));
-        if (sched && (rc = schedule_refresh(ctx, h, batch)) != QPN_OK) return rc;
-        if (need_general && (rc = solve_general(ctx, a, ws, true, false)) != QPN_OK) return rc;
-        if ((rc = declines_end(ctx, h)) != QPN_OK) return rc;
-    } else if (route == NodeRoute::big2) {
-        // large nodes (BASELINE config 5): the blocked crash straight from the records, the delayed-update Lemke kernel on the
-        // Schur problems, read-back and post-check on the records; no M is assembled unless a node declines -- those
-        // (status = -1) are assembled and solved by the general kernel in gated launches
-        SchurBigWs sw{};
-        double *dict = ws.big;
-        void *sb = ws.big + (size_t)batch * (size_t)N * (size_t)(N + 1);
-        // QPN_OPT_CRASH_CACHE_BIG, resident records: the first whole-batch sweep runs stage A in the handle's cache and keeps what
-        // Qd and Ad alone decide; later sweeps replay the g column of the nodes that have an entry and run the filling kernels
-        // for the others, as long as there are any (same stream: no host synchronisation)
-        const int crash = big_cache_mode(ctx, h, batch, !(ctx->order_user && ctx->order_count == batch));
-        if (crash) {
-            const BigCrash bc = big_cache_views(h);
-            if (crash == 1) HIPCHK(ctx, hipMemsetAsync(h->big_flag, 0, (size_t)batch, s));
-            const bool fill = crash == 1 || h->big_census != 2;
-            HIPCHK(ctx, qpn_launch_schur_big2_stage_a_cached(a, sb, dict, &sw, bc, crash == 2, fill, s));
-            if (crash == 1) { h->big_state = 1; h->big_stream = s; h->big_census = 0; }
-            if (fill && h->big_census != 1) {
-                HIPCHK(ctx, qpn_launch_crash_big_count(batch, h->big_flag, h->big_cnt_dev, s));
-                HIPCHK(ctx, hipMemcpyAsync(h->big_cnt_host, h->big_cnt_dev, 4, hipMemcpyDeviceToHost, s));
-                HIPCHK(ctx, hipEventRecord(h->big_ev, s));
-                h->big_census = 1;
-            }
-        } else {
-            HIPCHK(ctx, qpn_launch_schur_big2_stage_a(a, sb, dict, &sw, s));
-        }
-        // Stage B: resident records with symmetric Qd blocks (a.nd.sym) go through block principal pivoting first; whatever it
-        // leaves (and every node otherwise) is the delayed-update Lemke kernel's
-        // (a caller-set pivot budget is Lemke's to count: its pivots are the unit of max_pivots)
-        const bool bpp = a.nd.sym && o.max_pivots <= 0;
-        if (bpp) HIPCHK(ctx, qpn_launch_schur_big_bpp(a, sw, dict, s));
-        HIPCHK(ctx, qpn_launch_schur_big_lemke(a, sw, dict, s, bpp ? 1 : 0));
-        HIPCHK(ctx, qpn_launch_schur_big2_finish(a, sw, s));
-        if ((rc = solve_general(ctx, a, ws, true, false)) != QPN_OK) return rc;
-    } else {
-        if ((rc = solve_general(ctx, a, ws, false, false)) != QPN_OK) return rc;
-    }
-    if (x_dev && !x_in_kernel) {     // strided device copy of the primal blocks (and to the replicas)
-        HIPCHK(ctx, hipMemcpy2DAsync(x_dev, (size_t)stride_x * 8, d.z, (size_t)N * 8, (size_t)n * 8, (size_t)batch,
-                                     hipMemcpyDeviceToDevice, s));
-        for (int k = 0; mirrored && k < ctx->mirror_count; ++k)
-            HIPCHK(ctx, hipMemcpy2DAsync(ctx->mirror_peer[k] + x_off, (size_t)stride_x * 8, d.z, (size_t)N * 8,
-                                         (size_t)n * 8, (size_t)batch, hipMemcpyDefault, s));
-    }
-    return QPN_OK;
-}
-
-// One sweep: stages host buffers (the records only when h == null), carves the workspace, launches, reads back.
-int solve_nodes_any(qpn_ctx *ctx, qpn_nodes *h, int32_t batch, int32_t n, int32_t m, int32_t p, const double *Qd,
-                    const double *R, const double *qd, const double *Ad, const double *B, const double *l, const double *u,
-                    const double *w, int64_t stride_w, double *z, int32_t *status, double *resid, int32_t *pivots,
-                    uint8_t *active, const qpn_avi_opts *opts, int mem, double *x, int64_t stride_x)
-{
-    Stage st(ctx, mem, "qpn_solve_nodes");
-    if (int rc = st.check()) return rc;
-    const int N = n + m;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    qpn_avi_opts o;
-    if (opts) o = *opts; else qpn_avi_default_opts(&o);
-    const size_t bN = (size_t)batch * N;
-    const NodeRoute route = node_route(ctx, n, m, o);
-    // the handle may already know that the general path behind a fused route has nothing to do: no workspace for it then
-    nodes_poll_declines(h);
-    nodes_sync_route(ctx, h);
-    const bool fused = route == NodeRoute::fused32 || route == NodeRoute::mid;
-    const bool need_ws = !(h && fused && h->decl_state == 2);
-
-    NodeWs ws{};
-    if (need_ws) {
-        st.scratch(ws.M, bN * N * 8); st.scratch(ws.q, bN * 8); st.scratch(ws.l, bN * 8); st.scratch(ws.u, bN * 8);
-        st.scratch(ws.kind, bN);
-        if (N > 64) st.scratch(ws.big, qpn_avi_big_workspace_bytes(batch, N));
-    }
-    const NodeSizes sz = node_sizes(batch, n, m, p, stride_w);
-    NodeDev d{Qd, R, qd, Ad, B, l, u};     // (a handle's records are resident)
-    if (!h) stage_records(st, d, sz, Qd, R, qd, Ad, B, l, u);
-    st.in(d.w, w, sz.w, 8);
-    if (z) st.inout(d.z, z, bN * 8, !(o.flags & QPN_AVI_FLAG_COLD_START));
-    else { st.scratch(d.z, bN * 8); o.flags |= QPN_AVI_FLAG_COLD_START; }   // no z wanted (handle calls): the kernels still need one
-    st.out(d.st, status, (size_t)batch * 4); st.out(d.res, resid, (size_t)batch * 8); st.out(d.pv, pivots, (size_t)batch * 4);
-    st.out(d.act, active, bN);
-    // host mode: the primal blocks come down on their own (2.5 MB at 10 000 nodes; z is twice that), from a buffer of their own
-    // when the fused kernel writes them
-    const bool x_ws = st.host && x && route == NodeRoute::fused32;
-    double *hx = nullptr;
-    if (x_ws) st.scratch(hx, (size_t)batch * n * 8);
-    if (x) st.out2d(x_ws ? hx : d.z, (size_t)(x_ws ? n : N) * 8, x, (size_t)stride_x * 8, (size_t)n * 8, (size_t)batch);
-    // QPN_AVI_FLAG_WARM_DUALS: honoured by the 32-class when the caller's z carries a hint (z given, no cold start); the list of
-    // the nodes the warm kernel declines and its counter
-    const bool warm = route == NodeRoute::fused32 && (o.flags & QPN_AVI_FLAG_WARM_DUALS) && !(o.flags & QPN_AVI_FLAG_COLD_START);
-    int32_t *warm_list = nullptr;
-    if (warm) st.scratch(warm_list, ((size_t)batch + 1) * 4);
-    int rc = st.begin();
-    if (rc != QPN_OK) return rc;
-    rc = solve_nodes_launch(ctx, h, batch, n, m, p, d, stride_w, o, st.host ? hx : x, st.host ? (int64_t)n : stride_x, ws, route,
-                            warm_list);
-    if (rc != QPN_OK) return rc;
-    return st.finish();
-}
-
-int verify_nodes_any(qpn_ctx *ctx, bool records_on_device, int32_t batch, int32_t n, int32_t m, int32_t p,
-                     const double *Qd, const double *R, const double *qd, const double *Ad, const double *B,
-                     const double *l, const double *u, const double *xd, const double *w, int64_t stride_w, double tol,
-                     int32_t *solution, double *lambda, int32_t *path, int mem);
-
-} // namespace
-
-extern "C" {
-
-int qpn_solve_nodes_into(qpn_ctx *ctx, int32_t batch, int32_t n, int32_t m, int32_t p, const double *Qd,
-                         const double *R, const double *qd, const double *Ad, const double *B,
-                         const double *l, const double *u, const double *w, int64_t stride_w, double *z,
-                         int32_t *status, double *resid, int32_t *pivots, uint8_t *active,
-                         const qpn_avi_opts *opts, int mem, double *x, int64_t stride_x)
-{
-    if (!ctx) return QPN_ERR_ARG;
-    if (x && stride_x < n) return fail_arg(ctx, "qpn_solve_nodes_into: stride_x < n");
-    if (batch < 0 || n <= 0 || m < 0 || p < 0) return fail_arg(ctx, "qpn_solve_nodes: bad sizes");
-    if (batch == 0) return QPN_OK;
-    if (!Qd || !qd || (m > 0 && (!Ad || !l || !u)) || (p > 0 && (!R || !w || (m > 0 && !B))) || !z || !status)
-        return fail_arg(ctx, "qpn_solve_nodes: null pointer");
-    if (stride_w != 0 && stride_w < p) return fail_arg(ctx, "qpn_solve_nodes: stride_w < p");
-    if (n + m > qpn_avi_max_n()) { ctx->last_error = "qpn_solve_nodes: n+m > 1024 not supported by ABI v1"; return QPN_ERR_SIZE; }
-    return solve_nodes_any(ctx, nullptr, batch, n, m, p, Qd, R, qd, Ad, B, l, u, w, stride_w, z, status, resid, pivots,
-                           active, opts, mem, x, stride_x);
-}
-
-// ---- resident node records ------------------------------------------------------------------------------------
-int qpn_nodes_free(qpn_ctx *ctx, qpn_nodes *h)
-{
-    if (!ctx) return QPN_ERR_ARG;
-    if (!h) return QPN_OK;
-    (void)hipSetDevice(h->device);
-    (void)hipStreamSynchronize(ctx->stream);
-    if (h->decl_ev) { (void)hipEventSynchronize(h->decl_ev); (void)hipEventDestroy(h->decl_ev); }
-    if (h->buf) (void)hipFree(h->buf);
-    if (h->crash) (void)hipFree(h->crash);
-    if (h->crash_flag) (void)hipFree(h->crash_flag);
-    big_cache_free(h);
-    if (h->decl_dev) (void)hipFree(h->decl_dev);
-    if (h->decl_host) (void)hipHostFree(h->decl_host);
-    if (h->order) (void)hipFree(h->order);
-    if (h->key) (void)hipFree(h->key);
-    delete h;
-    return QPN_OK;
-}
-
-int qpn_nodes_upload(qpn_ctx *ctx, int32_t batch, int32_t n, int32_t m, int32_t p, const double *Qd,
-                     const double *R, const double *qd, const double *Ad, const double *B, const double *l,
-                     const double *u, int mem, qpn_nodes **out)
-{
-    if (!ctx) return QPN_ERR_ARG;
-    if (!out) return fail_arg(ctx, "qpn_nodes_upload: null out");
-    *out = nullptr;
-    if (batch <= 0 || n <= 0 || m < 0 || p < 0) return fail_arg(ctx, "qpn_nodes_upload: bad sizes");
-    if (!Qd || !qd || (m > 0 && (!Ad || !l || !u)) || (p > 0 && (!R || (m > 0 && !B))))
-        return fail_arg(ctx, "qpn_nodes_upload: null pointer");
-    if (mem != QPN_MEM_HOST && mem != QPN_MEM_DEVICE) return fail_arg(ctx, "qpn_nodes_upload: bad mem kind");
-    if (n + m > qpn_avi_max_n()) { ctx->last_error = "qpn_nodes_upload: n+m > 1024 not supported by ABI v1"; return QPN_ERR_SIZE; }
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    qpn_nodes *h = new (std::nothrow) qpn_nodes();
-    if (!h) return fail_arg(ctx, "qpn_nodes_upload: out of host memory");
-    h->device = ctx->device; h->batch = batch; h->n = n; h->m = m; h->p = p;
-    const NodeSizes sz = node_sizes(batch, n, m, p, 0);
-    const size_t fb[7] = {sz.Q, sz.R, sz.q, sz.A, sz.B, sz.lu, sz.lu};
-    const double *src[7] = {Qd, R, qd, Ad, B, l, u};
-    size_t total = 0, off[7];
-    for (int i = 0; i < 7; ++i) { off[i] = total; total += (fb[i] + 8 + 255) & ~(size_t)255; h->fbytes[i] = fb[i]; }
-    hipError_t e = hipMalloc((void **)&h->buf, total);
-    if (e == hipSuccess) e = hipMalloc((void **)&h->decl_dev, 4);
-    if (e == hipSuccess) e = hipHostMalloc((void **)&h->decl_host, 4, hipHostMallocDefault);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&h->decl_ev, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipMalloc((void **)&h->order, (size_t)batch * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&h->key, (size_t)batch * 4);
-    if (e == hipSuccess) e = hipMemsetAsync(h->key, 0, (size_t)batch * 4, ctx->stream);
-    const hipMemcpyKind kind = mem == QPN_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
-    for (int i = 0; i < 7 && e == hipSuccess; ++i) {
-        h->f[i] = reinterpret_cast<double *>(reinterpret_cast<char *>(h->buf) + off[i]);
-        if (fb[i]) e = hipMemcpyAsync(h->f[i], src[i], fb[i], kind, ctx->stream);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);     // the caller's arrays are free again on return
-    if (e == hipSuccess) e = nodes_check_symmetry(ctx, h);
-    if (e != hipSuccess) { int rc = fail_hip(ctx, e, "qpn_nodes_upload"); qpn_nodes_free(ctx, h); return rc; }
-    *h->decl_host = 0;
-    *out = h;
-    return QPN_OK;
-}
-
-int qpn_nodes_update(qpn_ctx *ctx, qpn_nodes *h, int32_t field, const double *data, int mem)
-{
-    if (!ctx) return QPN_ERR_ARG;
-    if (!h || field < 0 || field > 6 || !data) return fail_arg(ctx, "qpn_nodes_update: bad argument");
-    if (mem != QPN_MEM_HOST && mem != QPN_MEM_DEVICE) return fail_arg(ctx, "qpn_nodes_update: bad mem kind");
-    if (h->device != ctx->device) return fail_arg(ctx, "qpn_nodes_update: handle belongs to another device");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (h->fbytes[field])
-        HIPCHK(ctx, hipMemcpyAsync(h->f[field], data, h->fbytes[field],
-                                   mem == QPN_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, ctx->stream));
-    if (mem == QPN_MEM_HOST) HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    // what was known about the old records is void (an answer still in flight must not be read as the new one's)
-    if (h->decl_state == 1) HIPCHK(ctx, hipEventSynchronize(h->decl_ev));
-    h->decl_state = 0;
-    // the crash cache is made of Qd and Ad alone: R, qd, B, l, u keep it (the memory stays for the next fill)
-    if ((field == QPN_NODE_QD || field == QPN_NODE_AD) && h->crash_state == 1) h->crash_state = 0;
-    if (field == QPN_NODE_QD || field == QPN_NODE_AD) big_cache_drop(h);
-    if (field == QPN_NODE_QD) HIPCHK(ctx, nodes_check_symmetry(ctx, h));
-    return QPN_OK;
-}
-
-int qpn_nodes_set_schedule(qpn_ctx *ctx, qpn_nodes *h, int32_t period)
-{
-    if (!ctx) return QPN_ERR_ARG;
-    if (!h || period < 0) return fail_arg(ctx, "qpn_nodes_set_schedule: bad argument");
-    h->period = period; h->calls = 0;
-    if (period == 0) h->order_valid = false;
-    return QPN_OK;
-}
-
-int qpn_nodes_info(qpn_ctx *ctx, qpn_nodes *h, int32_t info[4])
-{
-    if (!ctx) return QPN_ERR_ARG;
-    if (!h || !info) return fail_arg(ctx, "qpn_nodes_info: null argument");
-    nodes_poll_declines(h);
-    info[0] = h->decl_state; info[1] = h->decl_state >= 2 ? *h->decl_host : 0;
-    const bool cached = h->crash_state == 1 && crash_cache_applies(ctx, h);
-    const bool refused = !crash_cache_applies(ctx, h) || h->crash_state < 0;
-    info[2] = (h->order_valid ? 1 : 0) | (h->sym ? 2 : 0) | (cached ? 4 : 0) | (refused ? 8 : 0) | (h->crash_streamed ? 16 : 0);
-    const bool big_ok = big_cache_applies(ctx, h);
-    info[2] |= (h->big_state == 1 && big_ok ? 32 : 0) | (!big_ok || h->big_state < 0 ? 64 : 0);
-    info[3] = h->calls;
-    return QPN_OK;
-}
-
-int qpn_solve_nodes_h(qpn_ctx *ctx, qpn_nodes *h, const double *w, int64_t stride_w, double *z,
-                      int32_t *status, double *resid, int32_t *pivots, uint8_t *active,
-                      const qpn_avi_opts *opts, int mem, double *x, int64_t stride_x)
-{
-    if (!ctx) return QPN_ERR_ARG;
-    if (!h) return fail_arg(ctx, "qpn_solve_nodes_h: null handle");
-    if (h->device != ctx->device) return fail_arg(ctx, "qpn_solve_nodes_h: handle belongs to another device");
-    if (x && stride_x < h->n) return fail_arg(ctx, "qpn_solve_nodes_h: stride_x < n");
-    if (!status || (h->p > 0 && !w)) return fail_arg(ctx, "qpn_solve_nodes_h: null pointer");
-    if (stride_w != 0 && stride_w < h->p) return fail_arg(ctx, "qpn_solve_nodes_h: stride_w < p");
-    return solve_nodes_any(ctx, h, h->batch, h->n, h->m, h->p, h->f[0], h->f[1], h->f[2], h->f[3], h->f[4], h->f[5], h->f[6],
-                           w, stride_w, z, status, resid, pivots, active, opts, mem, x, stride_x);
-}
-
-int qpn_verify_nodes_h(qpn_ctx *ctx, qpn_nodes *h, const double *xd, const double *w, int64_t stride_w,
-                       double tol, int32_t *solution, double *lambda, int32_t *path, int mem)
-{
-    if (!ctx) return QPN_ERR_ARG;
-    if (!h) return fail_arg(ctx, "qpn_verify_nodes_h: null handle");
-    if (h->device != ctx->device) return fail_arg(ctx, "qpn_verify_nodes_h: handle belongs to another device");
-    return verify_nodes_any(ctx, true, h->batch, h->n, h->m, h->p, h->f[0], h->f[1], h->f[2], h->f[3], h->f[4], h->f[5],
-                            h->f[6], xd, w, stride_w, tol, solution, lambda, path, mem);
-}
-
 // ---- multi-GPU: shared iterate buffers and their replicas ------------------------------------------------
 static_assert(sizeof(hipIpcMemHandle_t) == QPN_IPC_HANDLE_BYTES, "IPC handle size");
 
@@ -1702,74 +844,6 @@ int qpn_sweep_status(qpn_ctx *ctx, const int32_t *status, const double *resid, i
     HIPCHK(ctx, qpn_launch_sweep_status(status, resid, count, out, rank, world, bx, epoch,
                                         (unsigned long long)timeout_ms * 100000ull, ctx->stream));   // 100 MHz wall clock
     return QPN_OK;
-}
-
-namespace {
-int order_reserve(qpn_ctx *ctx, int32_t count)
-{
-    if (count <= ctx->order_cap) return QPN_OK;
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));          // earlier launches may still read the old buffer
-    if (ctx->order) { HIPCHK(ctx, hipFree(ctx->order)); ctx->order = nullptr; ctx->order_cap = 0; ctx->order_count = 0; }
-    HIPCHK(ctx, hipMalloc((void **)&ctx->order, (size_t)count * 4));
-    ctx->order_cap = count;
-    return QPN_OK;
-}
-} // namespace
-
-int qpn_order_nodes_by_pivots(qpn_ctx *ctx, const int32_t *pivots, int32_t count, int mem)
-{
-    if (!ctx) return QPN_ERR_ARG;
-    if (!pivots || count <= 0) return fail_arg(ctx, "qpn_order_nodes_by_pivots: bad arguments");
-    Stage st(ctx, mem, "qpn_order_nodes_by_pivots");
-    if (int rc = st.check()) return rc;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    int rc = order_reserve(ctx, count);
-    if (rc != QPN_OK) return rc;
-    const int32_t *dp;
-    st.in(dp, pivots, (size_t)count * 4);
-    if ((rc = st.begin()) != QPN_OK) return rc;
-    HIPCHK(ctx, qpn_launch_order_by_pivots(dp, count, ctx->order, ctx->stream));
-    if ((rc = st.finish()) != QPN_OK) return rc;
-    ctx->order_count = count;
-    ctx->order_user = true;
-    return QPN_OK;
-}
-
-int qpn_set_node_order(qpn_ctx *ctx, const int32_t *order, int32_t count, int mem)
-{
-    if (!ctx) return QPN_ERR_ARG;
-    if (!order) { ctx->order_count = 0; ctx->order_user = false; ctx->auto_calls = 0; return QPN_OK; }
-    if (count <= 0) return fail_arg(ctx, "qpn_set_node_order: bad count");
-    if (mem != QPN_MEM_HOST && mem != QPN_MEM_DEVICE) return fail_arg(ctx, "qpn_set_node_order: bad mem kind");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    int rc = order_reserve(ctx, count);
-    if (rc != QPN_OK) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(ctx->order, order, (size_t)count * 4,
-                               mem == QPN_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, ctx->stream));
-    if (mem == QPN_MEM_HOST) HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->order_count = count;
-    ctx->order_user = true;
-    return QPN_OK;
-}
-
-int qpn_ctx_set_auto_schedule(qpn_ctx *ctx, int32_t period)
-{
-    if (!ctx) return QPN_ERR_ARG;
-    if (period < 0) return fail_arg(ctx, "qpn_ctx_set_auto_schedule: negative period");
-    ctx->auto_period = period;
-    ctx->auto_calls = 0;
-    if (period == 0 && !ctx->order_user) ctx->order_count = 0;      // drop a hint this mechanism installed
-    return QPN_OK;
-}
-
-int qpn_verify_nodes(qpn_ctx *ctx, int32_t batch, int32_t n, int32_t m, int32_t p,
-                     const double *Qd, const double *R, const double *qd, const double *Ad,
-                     const double *B, const double *l, const double *u, const double *xd,
-                     const double *w, int64_t stride_w, double tol, int32_t *solution,
-                     double *lambda, int32_t *path, int mem)
-{
-    return verify_nodes_any(ctx, mem == QPN_MEM_DEVICE, batch, n, m, p, Qd, R, qd, Ad, B, l, u, xd, w, stride_w, tol, solution,
-                            lambda, path, mem);
 }
 
 int qpn_convexity_nodes(qpn_ctx *ctx, int32_t batch, int32_t n, int32_t m, const double *Qd, const double *Ad,
@@ -2389,47 +1463,3 @@ int qpn_intersection_trees(qpn_ctx *ctx, int32_t d, int32_t rows, const double *
 }
 
 } // extern "C"
-
-namespace {
-int verify_nodes_any(qpn_ctx *ctx, bool records_on_device, int32_t batch, int32_t n, int32_t m, int32_t p,
-                     const double *Qd, const double *R, const double *qd, const double *Ad, const double *B,
-                     const double *l, const double *u, const double *xd, const double *w, int64_t stride_w, double tol,
-                     int32_t *solution, double *lambda, int32_t *path, int mem)
-{
-    if (!ctx) return QPN_ERR_ARG;
-    if (batch < 0 || n <= 0 || m < 0 || p < 0) return fail_arg(ctx, "qpn_verify_nodes: bad sizes");
-    if (batch == 0) return QPN_OK;
-    if (n > qpn_verify_max_dim() || m > qpn_verify_max_dim()) { ctx->last_error = "qpn_verify_nodes: n, m <= 512 in ABI v1"; return QPN_ERR_SIZE; }
-    const bool wide_avi = m > 64;         // the bounded-LSQ fallback of wide nodes runs on the large-item AVI kernel
-    if (!Qd || !qd || !xd || (m > 0 && (!Ad || !l || !u || !lambda)) || (p > 0 && (!R || !w || (m > 0 && !B))) ||
-        !solution || !path)
-        return fail_arg(ctx, "qpn_verify_nodes: null pointer");
-    if (stride_w != 0 && stride_w < p) return fail_arg(ctx, "qpn_verify_nodes: stride_w < p");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    const size_t mm = (size_t)(m > 0 ? m : 1);
-    const bool wide = n > QPN_VERIFY_WIDE_FROM || m > QPN_VERIFY_WIDE_FROM;
-    const bool mid = !wide && (n > 32 || m > 32);      // verify_node64's class: a small slot workspace for the nodes it hands on
-    const size_t mp16 = (size_t)((m + 15) & ~15);
-    const NodeSizes sz_ = node_sizes(batch, n, m, p, stride_w);
-    Stage st(ctx, mem, "qpn_verify_nodes");
-    NodeDev d{Qd, R, qd, Ad, B, l, u};
-    if (!records_on_device) stage_records(st, d, sz_, Qd, R, qd, Ad, B, l, u);
-    const double *dx; double *dlam; int32_t *dsol, *dpath;
-    st.in(dx, xd, sz_.q); st.in(d.w, w, sz_.w, 8);
-    st.out(dsol, solution, (size_t)batch * 4); st.out(dpath, path, (size_t)batch * 4); st.out(dlam, lambda, sz_.lu, 8);
-    // scratch of the bounded-LSQ fallback (src/qp_processing.jl:129-137): Gram block + vectors
-    double *sG, *sq, *slb, *sub, *sz, *sres, *wbig = nullptr, *gws = nullptr; int32_t *sst;
-    st.scratch(sG, (size_t)batch * mm * mm * 8); st.scratch(sq, (size_t)batch * mm * 8);
-    st.scratch(slb, (size_t)batch * mm * 8); st.scratch(sub, (size_t)batch * mm * 8);
-    st.scratch(sz, (size_t)batch * mm * 8); st.scratch(sres, (size_t)batch * 8); st.scratch(sst, (size_t)batch * 4);
-    if (wide_avi) st.scratch(wbig, qpn_avi_big_workspace_bytes(batch, m));
-    if (wide && m > 0) st.scratch(gws, (size_t)batch * 2 * mp16 * mp16 * 8);
-    else if (mid && m > 0) st.scratch(gws, (size_t)QPN_VERIFY_MID_SLOTS * 2 * mp16 * mp16 * 8 + 64);
-    int rc = st.begin();
-    if (rc != QPN_OK) return rc;
-    HIPCHK(ctx, qpn_launch_verify_nodes(batch, n, m, p, d.Q, d.R, d.q, d.A, d.B, d.l, d.u, dx, d.w, stride_w, tol,
-                                        dsol, dlam, dpath, sG, sq, slb, sub, sz, sres, sst, ctx->stream, wbig, gws));
-    return st.finish();
-}
-
-} // namespace

@@ -1,5 +1,5 @@
 """Restatement, in Python, of which wavefronts of a mixed reuse sweep compute Stage A (csrc/qpn_internal.h, crash_mix_recomputes;
-csrc/qpn_capi.hip, crash_mix_reuse_from and the two tuning constants).  The tests compare it with the C++ text and its
+csrc/qpn_capi_nodes.hip, crash_mix_reuse_from and the two tuning constants).  The tests compare it with the C++ text and its
 constants; nothing in the package imports it."""
 
 RESIDENT = 16 * 256       # kResidentMI355X

@@ -114,7 +114,7 @@ def truth(node):
     return node["_truth"]
 
 
-# ---- the route matrix of solve_nodes_launch / qpn_solve_avi_batch (csrc/qpn_capi.hip) -----------------------------------------
+# ---- the route matrix of solve_nodes_launch (csrc/qpn_capi_nodes.hip) / qpn_solve_avi_batch (csrc/qpn_capi.hip) -------------
 # cell -> shapes (n, m, p, nodes per family).  The smallest shapes at which each kernel's tiling can go wrong: the class's
 # corners, ragged sides, one side tiny; p = 0 once per fused class.
 CELLS = {
@@ -146,7 +146,7 @@ def cell_families(cell, n, m):
 
 
 def route_of(n, m, mid_route=1, max_pivots=0):
-    """node_route (csrc/qpn_capi.hip) and the shape predicates of the fused kernels, restated."""
+    """node_route (csrc/qpn_capi_nodes.hip) and the shape predicates of the fused kernels, restated."""
     if n <= 32 and 1 <= m <= 32:
         return "fused32"
     budget = max_pivots <= 0 or max_pivots - n >= 1

@@ -26,7 +26,7 @@ def test_header_defines_the_option_and_the_mirrors_agree():
 def test_nodes_info_keeps_its_signature():
     assert re.search(r"int\s+qpn_nodes_info\s*\(\s*qpn_ctx\s*\*\s*ctx\s*,\s*qpn_nodes\s*\*\s*nodes\s*,\s*int32_t\s+info\[4\]\s*\)\s*;",
                      _header())
-    src = open(os.path.join(ROOT, "quadraticprogramnetworks.jl_amd", "csrc", "qpn_capi.hip")).read()
+    src = open(os.path.join(ROOT, "quadraticprogramnetworks.jl_amd", "csrc", "qpn_capi_nodes.hip")).read()
     assert re.search(r"int\s+qpn_nodes_info\s*\(\s*qpn_ctx\s*\*\s*ctx\s*,\s*qpn_nodes\s*\*\s*h\s*,\s*int32_t\s+info\[4\]\s*\)", src)
 
 

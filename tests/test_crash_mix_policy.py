@@ -29,7 +29,7 @@ def _define(text, name):
 
 
 def test_constants_match_the_sources():
-    capi = open(os.path.join(CSRC, "qpn_capi.hip")).read()
+    capi = open(os.path.join(CSRC, "qpn_capi_nodes.hip")).read()
     internal = open(os.path.join(CSRC, "qpn_internal.h")).read()
     assert _define(capi, "QPN_CRASH_MIX_SHARE") == rule.SHARE
     assert _define(capi, "QPN_CRASH_MIX_TAIL") == rule.TAIL
