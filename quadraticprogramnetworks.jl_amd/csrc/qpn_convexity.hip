@@ -6,7 +6,10 @@
 //   2. V = Ae' (n x k): the selected rows of Ad that are not all zero, as columns.  A Householder QR with column pivoting of
 //      V gives the rank r: pivot columns are taken while the largest remaining column norm |R_jj| exceeds
 //      min(k, n) * eps * sigma_max(V) -- Julia's rank(Diagonal(svdvals)) rule with |R_jj| in the place of the singular values;
-//      sigma_max comes from a power iteration and is never taken below the largest column norm.
+//      sigma_max comes from a power iteration and is never taken below the largest column norm.  A remaining column whose
+//      norm has fallen to CVX_DEP * sqrt(n) * eps of its OWN original norm counts as zero: that is the rounding a Householder
+//      sweep leaves of a column that depends exactly on the pivots taken (an implicit equality arrives as two opposing
+//      rows), and min(k, n) * eps * sigma_max underestimates it when k is small and n large.
 //   3. The r reflectors H_0 .. H_{r-1} (Q = H_0 ... H_{r-1}, Z = Q[:, r:n]) are applied on both sides of S; the trailing
 //      (n-r) x (n-r) block is then Z' S Z.
 //   4. That block is brought to tridiagonal form by Householder similarity transforms and its smallest eigenvalue found by
@@ -32,15 +35,19 @@ constexpr int CVX_WAVES = 4;                 // nodes per workgroup in the wave 
 constexpr int CVX_GROUP = 256;               // threads per node in the group and global classes
 constexpr int CVX_POWER_ITERS = 30;
 constexpr int CVX_MAX_ROUNDS = 64;
+// A dependent column's residue was measured at up to 0.63 sqrt(n) eps of its original norm (k = 2 .. 1000, n = 2 .. 256, rank up
+// to n - 2; profiles/convexity_accuracy.txt), the smallest genuine pivot of square Gaussian rows at 3.5e-3 of it: 8 leaves a
+// factor 12 to the one side and eleven orders of magnitude to the other.
+constexpr double CVX_DEP = 8.0;
 constexpr size_t CVX_WAVE_SLICE_MAX = size_t(40) << 10;
 constexpr size_t CVX_GROUP_SLICE_MAX = size_t(128) << 10;
 constexpr size_t CVX_GLOBAL_CHUNK_BYTES = size_t(512) << 20;
 
-// slice layout: doubles S[n*n] V[n*m] tau[n] vb[n] p[n] a[n] b2[n] cn[max(m,1)] red[T], then ints sel[max(m,1)] misc[4]
+// slice layout: doubles S[n*n] V[n*m] tau[n] vb[n] p[n] a[n] b2[n] cn[max(m,1)] c0[max(m,1)] red[T], then ints sel[max(m,1)] misc[4]
 __host__ __device__ inline size_t slice_bytes(int n, int m, int T)
 {
     const size_t mm = m > 0 ? m : 1;
-    const size_t dbl = (size_t)n * n + (size_t)n * m + 5 * (size_t)n + mm + T;
+    const size_t dbl = (size_t)n * n + (size_t)n * m + 5 * (size_t)n + 2 * mm + T;
     return (dbl * 8 + (mm + 4) * 4 + 15) & ~size_t(15);
 }
 
@@ -151,7 +158,7 @@ __device__ void convexity_node(void *slice, int n, int m, const double *__restri
     double *S = static_cast<double *>(slice);
     double *V = S + (size_t)n * n;
     double *tau = V + (size_t)n * m;
-    double *vb = tau + n, *p = vb + n, *a = p + n, *b2 = a + n, *cn = b2 + n, *red = cn + mm;
+    double *vb = tau + n, *p = vb + n, *a = p + n, *b2 = a + n, *cn = b2 + n, *c0 = cn + mm, *red = c0 + mm;
     int *sel = reinterpret_cast<int *>(red + T);
     int *misc = sel + mm;                         // misc[0] = non-finite flag, misc[1] = k, misc[2] = pivot column
 
@@ -202,6 +209,17 @@ __device__ void convexity_node(void *slice, int n, int m, const double *__restri
     // -- 2. rank of V = Ae' by pivoted Householder QR --------------------------------------------------------------------
     int r = 0;
     if (k > 0) {
+        // the columns' own squared norms: c0 travels with its column through the pivoting
+        for (int c = t; c < k; c += T) {
+            double acc = 0.0;
+            for (int i = 0; i < n; ++i) {
+                const double v = V[(size_t)c * n + i];
+                acc += v * v;
+            }
+            c0[c] = acc;
+        }
+        team_sync<T, WAVE>();
+        const double dep2 = CVX_DEP * CVX_DEP * DBL_EPSILON * DBL_EPSILON * (double)n;
         // sigma_max(V) by power iteration on V V' (a lower bound that converges to it)
         for (int j = t; j < n; j += T) vb[j] = 1.0 + 0.5 * sin(0.7 * (double)(j + 1));
         team_sync<T, WAVE>();
@@ -239,6 +257,7 @@ __device__ void convexity_node(void *slice, int n, int m, const double *__restri
                     const double v = V[(size_t)c * n + i];
                     acc += v * v;
                 }
+                if (!(acc > dep2 * c0[c])) acc = 0.0;   // rounding residue of a column that depends on the pivots taken
                 cn[c] = acc;
                 best = fmax(best, acc);
             }
@@ -253,12 +272,18 @@ __device__ void convexity_node(void *slice, int n, int m, const double *__restri
             if (thr < 0.0) thr = (double)steps * DBL_EPSILON * fmax(sqrt(sig2), sqrt(best));
             if (!(sqrt(best) > thr)) break;
             const int pc = misc[2];
-            if (pc != j)
+            if (pc != j) {
                 for (int i = t; i < n; i += T) {
                     const double x = V[(size_t)j * n + i];
                     V[(size_t)j * n + i] = V[(size_t)pc * n + i];
                     V[(size_t)pc * n + i] = x;
                 }
+                if (t == 0) {
+                    const double x = c0[j];
+                    c0[j] = c0[pc];
+                    c0[pc] = x;
+                }
+            }
             team_sync<T, WAVE>();
             double tj, bj;
             house<T, WAVE>(V + (size_t)j * n + j, 1, n - j, vb + j, red, t, tj, bj);

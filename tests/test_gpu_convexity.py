@@ -22,7 +22,7 @@ def _batch(n, m, g):
     """Nodes of every kind the kernel has to tell apart: skew parts, PSD with exact zero eigenvalues, smallest eigenvalue at
     -tol (1 +- 1e-4), indefinite; rows with random masks, duplicated and dependent equality rows.  -> (Qc, Ac, eq)."""
     Qds, As, eqs = [], [], []
-    for kind in ("skew", "psd_zero", "edge_in", "edge_out", "indefinite", "dependent"):
+    for kind in KINDS:
         A = g.standard_normal((m, n))
         eq = (g.random(m) < 0.5).astype(np.uint8)
         if kind == "skew":
@@ -62,10 +62,14 @@ def _clear(sv, thr):
     return not np.any((sv > thr / 16) & (sv < thr * 16))
 
 
+KINDS = ("skew", "psd_zero", "edge_in", "edge_out", "indefinite", "dependent")
+
+
 @pytest.mark.parametrize("n", SIZES)
-def test_kernel_matches_restatement(engine, n):
+def test_kernel_matches_restatement(engine, n, capsys):
     import torch
     g = np.random.Generator(np.random.Philox(key=[7, n]))
+    dropped = dict.fromkeys(KINDS, 0)
     for m in sorted({0, n // 2, 2 * n}):
         Qc, Ac, eq = _batch(n, m, g)
         cvx, lam, nd = engine.convexity_nodes(Qc, Ac, eq, tol=TOL)
@@ -73,6 +77,7 @@ def test_kernel_matches_restatement(engine, n):
         S = Qc + np.swapaxes(Qc, 1, 2)
         for b in range(len(rc)):
             if not _clear(svs[b], thrs[b]):
+                dropped[KINDS[b]] += 1
                 continue
             assert nd[b] == rn[b], (n, m, b)
             assert cvx[b] == rc[b], (n, m, b, lam[b], rl[b])
@@ -93,6 +98,12 @@ def test_kernel_matches_restatement(engine, n):
         torch.cuda.synchronize()
         assert np.array_equal(cd.cpu().numpy(), cvx) and np.array_equal(ld.cpu().numpy(), lam)
         assert np.array_equal(nd_d.cpu().numpy(), nd)
+    # Random rows sit clear of the rank threshold: nothing of the five kinds without planted dependence is left out.  The
+    # `dependent` kind can be (the rounding residue of its dependent rows lands near the threshold); that kind is compared node
+    # by node, with the rank known, in test_gpu_convexity_reference.
+    with capsys.disabled():
+        print(f"\n[convexity restatement n={n}] `dependent` nodes left out by the clearness filter: {dropped['dependent']} of 3")
+    assert all(dropped[k] == 0 for k in KINDS if k != "dependent"), dropped
 
 
 @pytest.mark.parametrize("n", [4, 48, 200])
