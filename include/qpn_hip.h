@@ -60,7 +60,10 @@ typedef struct qpn_ctx qpn_ctx;
  * solve's up to rounding).  Every other node -- a NaN or an infinity in its hint, an empty hint on a node with active rows, a
  * wrong row or side -- is solved by the cold route in the same call, with results bit-identical to a call without the bit.
  * Accepted nodes do not feed a handle's pivot statistics, its schedule or its count of declined nodes, and a sweep with the
- * bit set does not fill the crash cache (it reuses a valid one). */
+ * bit set does not fill the crash cache (it reuses a valid one).
+ * One more class takes the hint once its context opts in: resident records of large nodes (64 < n <= 256, m <= 256) on the
+ * symmetric route, through qpn_solve_nodes_h with QPN_OPT_WARM_BIG = 1 (see there: the hint seeds block principal pivoting,
+ * pivots = n when it held).  Without that option the bit is ignored there as everywhere else. */
 #define QPN_AVI_FLAG_WARM_DUALS 2
 
 typedef struct {
@@ -307,6 +310,16 @@ int qpn_ctx_set_auto_schedule(qpn_ctx *ctx, int32_t period);
  *                      declines exactly the nodes whose smallest cached pivot lies below it.  A node whose elimination stops in a
  *                      filling sweep has no entry and is recomputed by every sweep until it gets through.  Results are
  *                      bit-identical either way, and the same nodes decline.  Records passed per call are never cached.
+ *   QPN_OPT_WARM_BIG   resident records of large nodes (64 < n <= 256, m <= 256) on the symmetric route: 1 = a sweep that carries
+ *                      QPN_AVI_FLAG_WARM_DUALS (z given, QPN_AVI_FLAG_COLD_START clear, no caller-set max_pivots) starts block
+ *                      principal pivoting from the set the multipliers of the incoming z name -- row i at l_i when lambda_i > 0
+ *                      and l_i is finite, at u_i when lambda_i < 0 and u_i is finite, free otherwise (NaN and zeros name nothing;
+ *                      the primal part is not read); 0 = the flag is ignored in this class as in every other but n, m <= 32
+ *                      (default).  A node whose hint names no row or more than 112 rows starts cold, bit for bit; a seeded
+ *                      start that fails is repeated from the cold start in the same launch, so a wrong hint costs rounds, never
+ *                      the result.  `pivots` = n + the pairs switched after the seed: pivots == n says that the hint held.
+ *                      Results equal the un-hinted ones up to rounding (the same post-check certifies them), not bit for bit.
+ *                      The same nodes decline and the crash caches are filled and reused as without it: no new route epoch.
  * A resident handle remembers under which option values it learned that none of its nodes declines; after a change it asks again
  * on its next sweep (another kernel variant applies its pivot test to slightly different numbers). */
 #define QPN_OPT_MID_ROUTE 1
@@ -315,6 +328,7 @@ int qpn_ctx_set_auto_schedule(qpn_ctx *ctx, int32_t period);
 #define QPN_OPT_CRASH_CACHE 4
 #define QPN_OPT_LLC_BUDGET_MB 5
 #define QPN_OPT_CRASH_CACHE_BIG 6
+#define QPN_OPT_WARM_BIG 7
 int qpn_ctx_set_option(qpn_ctx *ctx, int32_t option, int32_t value);
 
 /* ---- multi-GPU: replicas of the iterate on peer GPUs, written by the solve itself -----------------------

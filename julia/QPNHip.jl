@@ -180,7 +180,10 @@ function update_nodes!(nodes::Nodes, field::Int32, data::Array{Float64})
     nothing
 end
 
-# warm = the z of an earlier sweep over the handle's nodes: QPN_AVI_FLAG_WARM_DUALS, as in solve_nodes! above (z comes back)
+# warm = the z of an earlier sweep over the handle's nodes: QPN_AVI_FLAG_WARM_DUALS, as in solve_nodes! above (z comes back).
+# Handles of large symmetric nodes (64 < n <= 256, m <= 256) take it too after set_option!(QPN_OPT_WARM_BIG, 1): the hint seeds
+# block principal pivoting, `pivots == n` says that it held, and a wrong hint costs rounds, never the result; without the option
+# the hint is ignored in that class.
 function solve_nodes!(nodes::Nodes, x::Union{Nothing,StridedMatrix{Float64}}, w::VecOrMat{Float64}; want_z::Bool = true,
                       warm::Union{Nothing,Matrix{Float64}} = nothing)
     N = nodes.n + nodes.m; batch = nodes.batch
@@ -865,6 +868,10 @@ const QPN_OPT_LLC_BUDGET_MB = Int32(5)
 # makes of Qd and Ad alone across sweeps (1.6 MB of HBM per node at n = m = 256 on top of 1.06 MB of records; bit-identical
 # results, the same nodes decline), 0 = never (default).
 const QPN_OPT_CRASH_CACHE_BIG = Int32(6)
+# WARM_BIG 1 = sweeps with `warm =` over large resident nodes (64 < n <= 256, m <= 256) on the symmetric route start block principal
+# pivoting from the set the hint's multipliers name (`pivots == n`: the hint held; results equal up to rounding), 0 = the hint is
+# ignored in that class (default).
+const QPN_OPT_WARM_BIG = Int32(7)
 function set_option!(option::Integer, value::Integer)
     rc = ccall((:qpn_ctx_set_option, LIB), Cint, (Ptr{Cvoid}, Int32, Int32), ctx(), Int32(option), Int32(value))
     rc == 0 || error("qpn_ctx_set_option failed ($rc)")

@@ -31,7 +31,7 @@ ABI_SYMBOLS = (
 
 MEM_HOST, MEM_DEVICE = 0, 1
 AVI_FLAG_COLD_START = 1
-AVI_FLAG_WARM_DUALS = 2         # n, m <= 32 node solves: the multipliers of the incoming z name the active set to start from
+AVI_FLAG_WARM_DUALS = 2         # n, m <= 32 node solves (and large resident ones under OPT_WARM_BIG): the multipliers of the incoming z name the active set to start from
 MAX_MIRRORS = 7
 IPC_HANDLE_BYTES = 64
 SHARED_FINE_GRAINED = 1
@@ -42,6 +42,7 @@ OPT_SYM_ROUTE = 3
 OPT_CRASH_CACHE = 4
 OPT_LLC_BUDGET_MB = 5
 OPT_CRASH_CACHE_BIG = 6         # resident records of the large class (64 < n <= 256, m <= 256): 1 = keep the crash across sweeps (default 0)
+OPT_WARM_BIG = 7                # large resident nodes on the symmetric route: 1 = AVI_FLAG_WARM_DUALS seeds block principal pivoting (default 0)
 PARENT_SLOTS = 8               # QPN_PARENT_SLOTS: child pieces per item of qpn_assemble_parent_nodes
 
 

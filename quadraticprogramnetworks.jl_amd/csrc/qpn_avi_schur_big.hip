@@ -1030,6 +1030,14 @@ __device__ __forceinline__ int bpp_prefix(bool flag, int &total, BppShared &B, i
     return before + __popcll(bal & ((1ull << lane) - 1ull));
 }
 
+// The kernel.  WARM (QPN_OPT_WARM_BIG with QPN_AVI_FLAG_WARM_DUALS): the multipliers of the incoming a.z name the set to start
+// from -- row i at l_i when lambda_i > 0 and l_i is finite, at u_i when lambda_i < 0 and u_i is finite, free otherwise (NaN and
+// +-0 name nothing; the primal part is not read; nothing before schur_big2_finish writes a.z).  A seed of no row or of more than
+// BPP_KMAX rows (the tiles hold no more) is dropped: the node runs the cold start alone, bit for bit.  From the seed on the
+// rounds are the ones above; if they fail (a pivot under the threshold, the round limit) the workgroup starts once more from the
+// cold rule, so a wrong hint never sends a node to the Lemke kernel that the cold start keeps from it.  `changes` counts the
+// pairs switched after the seed, over both attempts: pivots == n says "the hint held".
+template <bool WARM>
 __global__ __launch_bounds__(TPB, 2) void schur_big_bpp(AviBatchArgs a, SchurBigWs w, double *dict)
 {
     const int tid = threadIdx.x, b = blockIdx.x;
@@ -1060,148 +1068,168 @@ __global__ __launch_bounds__(TPB, 2) void schur_big_bpp(AviBatchArgs a, SchurBig
 
     int st = 0;                         // 0: lambda = 0, s free in [l, u]; 1: s = l; 2: s = u
     double lam = 0.0, s = ci;
-    {
-        // the start: the rows violated at lambda = 0 -- when there are more than the cap, the most violated ones (a threshold found
-        // by bisection on the count: the prototype needs 5.9 rounds from there, 6.7 - 7.2 from the first 112 by index)
-        const double v0 = act ? fmax(li - s, s - ui) : 0.0;
-        bool viol = act && v0 > tol_s;
-        int total = sb_block_sum_i(viol ? 1 : 0, B, tid);
-        if (total > BPP_KMAX) {
-            double lo_ = tol_s, hi_ = sb_block_max(v0, B, tid);
-            for (int bi = 0; bi < 12; ++bi) {
-                const double mid = 0.5 * (lo_ + hi_);
-                if (sb_block_sum_i((act && v0 > mid) ? 1 : 0, B, tid) > BPP_KMAX) lo_ = mid; else hi_ = mid;
-            }
-            viol = act && v0 > hi_;
-        }
-        if (viol) st = s < li ? 1 : 2;
+    int seed = 0;                       // (WARM) the side the hint names for this row
+    bool seeded = false;
+    if constexpr (WARM) {
+        const double hz = act ? a.z[vo + a.nd.n + tid] : 0.0;          // one coalesced load: the node's multipliers
+        if (hz > 0.0 && li > -QINF) seed = 1;
+        else if (hz < 0.0 && ui < QINF) seed = 2;
+        const int named = sb_block_sum_i(seed != 0 ? 1 : 0, B, tid);
+        seeded = named >= 1 && named <= BPP_KMAX;                       // (before any gather: the tiles hold BPP_KMAX rows)
     }
-    int nbest = m + 1, patience = 3, changes = 0;
+    int changes = 0;
     bool solved = false, failed = false;
-    for (int it = 0; it < BPP_MAX_IT; ++it) {
-        // ---- the active list (ascending rows)
-        int k;
-        const int mypos = bpp_prefix(st != 0, k, B, tid);
-        B.posof[tid] = st != 0 ? mypos : -1;
-        if (st != 0) { B.aidx[mypos] = tid; B.rhs[mypos] = (st == 1 ? li : ui) - ci; }
-        const int T = (k + 15) >> 4, kp = 16 * T;
-        if (tid >= k && tid < kp) { B.aidx[tid] = 0; B.rhs[tid] = 0.0; }
-        __syncthreads();
-        if (k > 0) {
-            // ---- S_AA (lower triangle) into the tiles: wave <-> active row, lanes <-> the row's 256 entries (coalesced)
-            // (eight rows of a wave in flight: 32 loads, then their scatter)
-            for (int a0 = wave; a0 < kp; a0 += 32) {
-                double v[8][TPB / 64];
-                int pc[TPB / 64];
-#pragma unroll
-                for (int q = 0; q < TPB / 64; ++q) { const int col = lane + 64 * q; pc[q] = col < m ? B.posof[col] : -1; }
-#pragma unroll
-                for (int rr = 0; rr < 8; ++rr) {
-                    const int ar = a0 + 4 * rr;
-                    const double *row = Tb + (size_t)B.aidx[ar < k ? ar : 0] * ld;
-#pragma unroll
-                    for (int q = 0; q < TPB / 64; ++q) { const int col = lane + 64 * q; v[rr][q] = (ar < k && pc[q] >= 0 && pc[q] <= ar) ? row[col] : 0.0; }
+    // at most two attempts: the seeded one (WARM, a usable seed), then the cold start
+    for (int attempt = (WARM && seeded) ? 0 : 1; attempt < 2; ++attempt) {
+        if (WARM && attempt == 0) st = seed;
+        else {
+            // the start: the rows violated at lambda = 0 -- when there are more than the cap, the most violated ones (a threshold found
+            // by bisection on the count: the prototype needs 5.9 rounds from there, 6.7 - 7.2 from the first 112 by index)
+            if constexpr (WARM) { st = 0; s = ci; }
+            const double v0 = act ? fmax(li - s, s - ui) : 0.0;
+            bool viol = act && v0 > tol_s;
+            int total = sb_block_sum_i(viol ? 1 : 0, B, tid);
+            if (total > BPP_KMAX) {
+                double lo_ = tol_s, hi_ = sb_block_max(v0, B, tid);
+                for (int bi = 0; bi < 12; ++bi) {
+                    const double mid = 0.5 * (lo_ + hi_);
+                    if (sb_block_sum_i((act && v0 > mid) ? 1 : 0, B, tid) > BPP_KMAX) lo_ = mid; else hi_ = mid;
                 }
-#pragma unroll
-                for (int rr = 0; rr < 8; ++rr) {
-                    const int ar = a0 + 4 * rr;
-                    if (ar >= kp) break;                                  // (wave-uniform)
-                    const int ti = ar >> 4, ri = ar & 15;
-                    if (ar < k) {
-#pragma unroll
-                        for (int q = 0; q < TPB / 64; ++q) {
-                            const int p = pc[q];
-                            if (p >= 0 && p <= ar) tiles[bpp_toff(ti, p >> 4) + ri * BPP_TLD + (p & 15)] = v[rr][q];
-                        }
-                    } else {
-                        // padding up to a whole tile: the identity
-                        for (int p = lane; p <= ar; p += 64) tiles[bpp_toff(ti, p >> 4) + ri * BPP_TLD + (p & 15)] = p == ar ? 1.0 : 0.0;
-                    }
-                }
+                viol = act && v0 > hi_;
             }
-            __syncthreads();
-            // ---- blocked Cholesky and the two triangular solves (qpn_tile_chol.h)
-            if (!tc_factor(tiles, T, &B.fail, 1e-13, tid)) { failed = true; break; }
-            if (wave == 0) tc_solve(tiles, B.rhs, T, lane);
-            __syncthreads();
+            if (viol) st = s < li ? 1 : 2;
         }
-        // ---- lambda, s = c + S(:, A) lambda_A (S symmetric: rows A of T_base, coalesced over this thread's column)
-        lam = st != 0 ? B.rhs[mypos] : 0.0;
-        double acc0 = ci, acc1 = 0.0;
-        if (act) {
-            int a0 = 0;
-            for (; a0 + 16 <= k; a0 += 16) {
-                double v[16];
-#pragma unroll
-                for (int q = 0; q < 16; ++q) v[q] = Tb[(size_t)B.aidx[a0 + q] * ld + tid];
-#pragma unroll
-                for (int q = 0; q < 16; q += 2) { acc0 = fma(v[q], B.rhs[a0 + q], acc0); acc1 = fma(v[q + 1], B.rhs[a0 + q + 1], acc1); }
-            }
-            for (; a0 + 4 <= k; a0 += 4) {
-                double v[4];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) v[q] = Tb[(size_t)B.aidx[a0 + q] * ld + tid];
-#pragma unroll
-                for (int q = 0; q < 4; q += 2) { acc0 = fma(v[q], B.rhs[a0 + q], acc0); acc1 = fma(v[q + 1], B.rhs[a0 + q + 1], acc1); }
-            }
-            for (; a0 < k; ++a0) acc0 = fma(Tb[(size_t)B.aidx[a0] * ld + tid], B.rhs[a0], acc0);
-        }
-        s = st == 1 ? li : (st == 2 ? ui : acc0 + acc1);
-        // ---- violated pairs
-        const double lmax = sb_block_max(fabs(lam), B, tid);
-        const double tol_l = 1e-10 * fmax(1.0, lmax);
-        const bool bad_l = (st == 1 && lam < -tol_l) || (st == 2 && lam > tol_l);
-        const bool bad_s = act && st == 0 && (s < li - tol_s || s > ui + tol_s);
-        const bool bad = bad_l || bad_s;
-        const int nb = sb_block_sum_i(bad ? 1 : 0, B, tid);
-        if (nb == 0) {
-            // One step of iterative refinement on the final set, with the residual of the active rows taken from the ROWS of S
-            // as stage A computed them: t_i - c_i - sum_a S(i, a) lambda_a.  The rounds above read S(:, A) as rows A and factor
-            // the lower triangle, i.e. they solve with a symmetrised S; the computed S = Ad (H^-1 Ad') is symmetric only to
-            // cond(H) eps, and the read-back x = -(W lambda + h) uses the W of the same factorisation, so the active rows of
-            // Ad x + B w miss their bounds by |S - S'| |lambda| unless lambda solves the system of S itself (found by
-            // tests/test_gpu_solve_reference.py at cond(H) = 1e4: 10 x the error of Lemke's pivots on the same S and c).
-            // The factor of the symmetrised S_AA is the preconditioner: one step contracts by |S - S'| / |S|.
+        int nbest = m + 1, patience = 3;
+        for (int it = 0; it < BPP_MAX_IT; ++it) {
+            // ---- the active list (ascending rows)
+            int k;
+            const int mypos = bpp_prefix(st != 0, k, B, tid);
+            B.posof[tid] = st != 0 ? mypos : -1;
+            if (st != 0) { B.aidx[mypos] = tid; B.rhs[mypos] = (st == 1 ? li : ui) - ci; }
+            const int T = (k + 15) >> 4, kp = 16 * T;
+            if (tid >= k && tid < kp) { B.aidx[tid] = 0; B.rhs[tid] = 0.0; }
+            __syncthreads();
             if (k > 0) {
-                __syncthreads();
-                if (st != 0) {
-                    const double *row = Tb + (size_t)tid * ld;
-                    double r0 = (st == 1 ? li : ui) - ci, r1 = 0.0;
-                    int a0 = 0;
-                    for (; a0 + 2 <= k; a0 += 2) {
-                        r0 = fma(-row[B.aidx[a0]], B.rhs[a0], r0);
-                        r1 = fma(-row[B.aidx[a0 + 1]], B.rhs[a0 + 1], r1);
+                // ---- S_AA (lower triangle) into the tiles: wave <-> active row, lanes <-> the row's 256 entries (coalesced)
+                // (eight rows of a wave in flight: 32 loads, then their scatter)
+                for (int a0 = wave; a0 < kp; a0 += 32) {
+                    double v[8][TPB / 64];
+                    int pc[TPB / 64];
+    #pragma unroll
+                    for (int q = 0; q < TPB / 64; ++q) { const int col = lane + 64 * q; pc[q] = col < m ? B.posof[col] : -1; }
+    #pragma unroll
+                    for (int rr = 0; rr < 8; ++rr) {
+                        const int ar = a0 + 4 * rr;
+                        const double *row = Tb + (size_t)B.aidx[ar < k ? ar : 0] * ld;
+    #pragma unroll
+                        for (int q = 0; q < TPB / 64; ++q) { const int col = lane + 64 * q; v[rr][q] = (ar < k && pc[q] >= 0 && pc[q] <= ar) ? row[col] : 0.0; }
                     }
-                    if (a0 < k) r0 = fma(-row[B.aidx[a0]], B.rhs[a0], r0);
-                    acc0 = r0 + r1;
+    #pragma unroll
+                    for (int rr = 0; rr < 8; ++rr) {
+                        const int ar = a0 + 4 * rr;
+                        if (ar >= kp) break;                                  // (wave-uniform)
+                        const int ti = ar >> 4, ri = ar & 15;
+                        if (ar < k) {
+    #pragma unroll
+                            for (int q = 0; q < TPB / 64; ++q) {
+                                const int p = pc[q];
+                                if (p >= 0 && p <= ar) tiles[bpp_toff(ti, p >> 4) + ri * BPP_TLD + (p & 15)] = v[rr][q];
+                            }
+                        } else {
+                            // padding up to a whole tile: the identity
+                            for (int p = lane; p <= ar; p += 64) tiles[bpp_toff(ti, p >> 4) + ri * BPP_TLD + (p & 15)] = p == ar ? 1.0 : 0.0;
+                        }
+                    }
                 }
-                __syncthreads();                // (every active thread has read the whole of lambda_A)
-                if (st != 0) B.rhs[mypos] = acc0;
-                if (tid >= k && tid < kp) B.rhs[tid] = 0.0;
                 __syncthreads();
+                // ---- blocked Cholesky and the two triangular solves (qpn_tile_chol.h)
+                if (!tc_factor(tiles, T, &B.fail, 1e-13, tid)) { failed = true; break; }
                 if (wave == 0) tc_solve(tiles, B.rhs, T, lane);
                 __syncthreads();
-                if (st != 0) lam += B.rhs[mypos];
             }
-            solved = true;
-            break;
+            // ---- lambda, s = c + S(:, A) lambda_A (S symmetric: rows A of T_base, coalesced over this thread's column)
+            lam = st != 0 ? B.rhs[mypos] : 0.0;
+            double acc0 = ci, acc1 = 0.0;
+            if (act) {
+                int a0 = 0;
+                for (; a0 + 16 <= k; a0 += 16) {
+                    double v[16];
+    #pragma unroll
+                    for (int q = 0; q < 16; ++q) v[q] = Tb[(size_t)B.aidx[a0 + q] * ld + tid];
+    #pragma unroll
+                    for (int q = 0; q < 16; q += 2) { acc0 = fma(v[q], B.rhs[a0 + q], acc0); acc1 = fma(v[q + 1], B.rhs[a0 + q + 1], acc1); }
+                }
+                for (; a0 + 4 <= k; a0 += 4) {
+                    double v[4];
+    #pragma unroll
+                    for (int q = 0; q < 4; ++q) v[q] = Tb[(size_t)B.aidx[a0 + q] * ld + tid];
+    #pragma unroll
+                    for (int q = 0; q < 4; q += 2) { acc0 = fma(v[q], B.rhs[a0 + q], acc0); acc1 = fma(v[q + 1], B.rhs[a0 + q + 1], acc1); }
+                }
+                for (; a0 < k; ++a0) acc0 = fma(Tb[(size_t)B.aidx[a0] * ld + tid], B.rhs[a0], acc0);
+            }
+            s = st == 1 ? li : (st == 2 ? ui : acc0 + acc1);
+            // ---- violated pairs
+            const double lmax = sb_block_max(fabs(lam), B, tid);
+            const double tol_l = 1e-10 * fmax(1.0, lmax);
+            const bool bad_l = (st == 1 && lam < -tol_l) || (st == 2 && lam > tol_l);
+            const bool bad_s = act && st == 0 && (s < li - tol_s || s > ui + tol_s);
+            const bool bad = bad_l || bad_s;
+            const int nb = sb_block_sum_i(bad ? 1 : 0, B, tid);
+            if (nb == 0) {
+                // One step of iterative refinement on the final set, with the residual of the active rows taken from the ROWS of S
+                // as stage A computed them: t_i - c_i - sum_a S(i, a) lambda_a.  The rounds above read S(:, A) as rows A and factor
+                // the lower triangle, i.e. they solve with a symmetrised S; the computed S = Ad (H^-1 Ad') is symmetric only to
+                // cond(H) eps, and the read-back x = -(W lambda + h) uses the W of the same factorisation, so the active rows of
+                // Ad x + B w miss their bounds by |S - S'| |lambda| unless lambda solves the system of S itself (found by
+                // tests/test_gpu_solve_reference.py at cond(H) = 1e4: 10 x the error of Lemke's pivots on the same S and c).
+                // The factor of the symmetrised S_AA is the preconditioner: one step contracts by |S - S'| / |S|.
+                if (k > 0) {
+                    __syncthreads();
+                    if (st != 0) {
+                        const double *row = Tb + (size_t)tid * ld;
+                        double r0 = (st == 1 ? li : ui) - ci, r1 = 0.0;
+                        int a0 = 0;
+                        for (; a0 + 2 <= k; a0 += 2) {
+                            r0 = fma(-row[B.aidx[a0]], B.rhs[a0], r0);
+                            r1 = fma(-row[B.aidx[a0 + 1]], B.rhs[a0 + 1], r1);
+                        }
+                        if (a0 < k) r0 = fma(-row[B.aidx[a0]], B.rhs[a0], r0);
+                        acc0 = r0 + r1;
+                    }
+                    __syncthreads();                // (every active thread has read the whole of lambda_A)
+                    if (st != 0) B.rhs[mypos] = acc0;
+                    if (tid >= k && tid < kp) B.rhs[tid] = 0.0;
+                    __syncthreads();
+                    if (wave == 0) tc_solve(tiles, B.rhs, T, lane);
+                    __syncthreads();
+                    if (st != 0) lam += B.rhs[mypos];
+                }
+                solved = true;
+                break;
+            }
+            bool flip = bad;
+            if (nb < nbest) { nbest = nb; patience = 3; }
+            else if (patience > 0) patience--;
+            else {
+                const int last = -sb_block_min_i(bad ? -tid : 1, B, tid);     // the violated pair with the highest index alone
+                flip = bad && tid == last;
+            }
+            const bool leave = flip && st != 0, enter = flip && st == 0;
+            const int nleave = sb_block_sum_i(leave ? 1 : 0, B, tid);
+            int nenter;
+            const int rank = bpp_prefix(enter, nenter, B, tid);
+            const int room = BPP_KMAX - (k - nleave);
+            if (leave) st = 0;
+            if (enter && rank < room) st = s < li ? 1 : 2;
+            changes += nleave + (nenter < room ? nenter : room);
+            __syncthreads();                // (B.rhs / aidx are rewritten at the top of the next round)
         }
-        bool flip = bad;
-        if (nb < nbest) { nbest = nb; patience = 3; }
-        else if (patience > 0) patience--;
-        else {
-            const int last = -sb_block_min_i(bad ? -tid : 1, B, tid);     // the violated pair with the highest index alone
-            flip = bad && tid == last;
-        }
-        const bool leave = flip && st != 0, enter = flip && st == 0;
-        const int nleave = sb_block_sum_i(leave ? 1 : 0, B, tid);
-        int nenter;
-        const int rank = bpp_prefix(enter, nenter, B, tid);
-        const int room = BPP_KMAX - (k - nleave);
-        if (leave) st = 0;
-        if (enter && rank < room) st = s < li ? 1 : 2;
-        changes += nleave + (nenter < room ? nenter : room);
-        __syncthreads();                // (B.rhs / aidx are rewritten at the top of the next round)
+        if (!WARM || solved || attempt == 1) break;
+        // the seeded attempt failed: once more from the cold rule (the tiles are gathered anew every round)
+        failed = false;
+        __syncthreads();                    // (every thread has read B.fail)
+        if (tid == 0) B.fail = 0;
     }
     if (solved && !failed) {
         if (act) w.lam[vo + tid] = lam;
@@ -1304,11 +1332,15 @@ hipError_t qpn_launch_schur_big_lemke(const AviBatchArgs &a, const SchurBigWs &w
 
 // Stage B by block principal pivoting for the nodes whose Schur problem is symmetric (the caller's promise); what it does not
 // finish keeps st2 = BPP_NOT_SOLVED for the Lemke kernel (launch it with after_bpp = 1).
-hipError_t qpn_launch_schur_big_bpp(const AviBatchArgs &a, const SchurBigWs &w, double *dict, hipStream_t stream)
+// warm: the rounds start from the set that the multipliers of a.z name (schur_big_bpp<true>; the caller has checked that a.z
+// carries a hint).
+hipError_t qpn_launch_schur_big_bpp(const AviBatchArgs &a, const SchurBigWs &w, double *dict, bool warm, hipStream_t stream)
 {
     const size_t bytes = (size_t)bpp_tiles(BPP_KMAX / 16) * BPP_TSZ * sizeof(double);       // 60 928 B: two workgroups per CU
     static QpnLdsLimits lds_limits;
-    if (const hipError_t e = lds_limits.raise({{schur_big_bpp, (int)bytes}}); e != hipSuccess) return e;
-    hipLaunchKernelGGL(schur_big_bpp, dim3((unsigned)a.batch), dim3(TPB), bytes, stream, a, w, dict);
+    if (const hipError_t e = lds_limits.raise({{schur_big_bpp<false>, (int)bytes}, {schur_big_bpp<true>, (int)bytes}}); e != hipSuccess)
+        return e;
+    if (warm) hipLaunchKernelGGL(schur_big_bpp<true>, dim3((unsigned)a.batch), dim3(TPB), bytes, stream, a, w, dict);
+    else hipLaunchKernelGGL(schur_big_bpp<false>, dim3((unsigned)a.batch), dim3(TPB), bytes, stream, a, w, dict);
     return hipGetLastError();
 }

@@ -41,6 +41,9 @@ struct qpn_ctx {
     int32_t crash_cache = 1;
     // QPN_OPT_CRASH_CACHE_BIG: 1 = resident records on the blocked crash of large nodes keep what Qd and Ad alone decide
     int32_t crash_cache_big = 0;
+    // QPN_OPT_WARM_BIG: 1 = sweeps over large resident nodes on the symmetric route that carry QPN_AVI_FLAG_WARM_DUALS start block
+    // principal pivoting from the set the incoming multipliers name
+    int32_t warm_big = 0;
     // QPN_OPT_LLC_BUDGET_MB: the share of the last-level cache, in MiB, that sweeps over the crash cache count on (llc_streams_crash,
     // qpn_internal.h); 0 = never stream the crash cache, -1 = always
     int32_t llc_budget_mb = kLlcBudgetMB;

@@ -174,6 +174,11 @@ int qpn_ctx_set_option(qpn_ctx *ctx, int32_t option, int32_t value)
         if (value < 0 || value > 1) return fail_arg(ctx, "qpn_ctx_set_option: QPN_OPT_CRASH_CACHE_BIG takes 0 or 1");
         ctx->crash_cache_big = value;
         return QPN_OK;
+    case QPN_OPT_WARM_BIG:
+        // (no new route epoch: the same nodes decline, stage A does not see the hint)
+        if (value < 0 || value > 1) return fail_arg(ctx, "qpn_ctx_set_option: QPN_OPT_WARM_BIG takes 0 or 1");
+        ctx->warm_big = value;
+        return QPN_OK;
     case QPN_OPT_LLC_BUDGET_MB:
         // (a cache policy of the loads: the same bits either way, no new route epoch)
         if (value < -1) return fail_arg(ctx, "qpn_ctx_set_option: QPN_OPT_LLC_BUDGET_MB takes a size in MiB, 0 (never stream) or -1 (always)");

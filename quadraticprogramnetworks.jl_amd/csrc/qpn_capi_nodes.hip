@@ -452,7 +452,8 @@ int sweep_mid(qpn_ctx *ctx, qpn_nodes *h, AviBatchArgs &a, const NodeWs &ws, con
 // large nodes (BASELINE config 5): the blocked crash straight from the records, the delayed-update Lemke kernel on the
 // Schur problems, read-back and post-check on the records; no M is assembled unless a node declines -- those
 // (status = -1) are assembled and solved by the general kernel in gated launches
-int sweep_big2(qpn_ctx *ctx, qpn_nodes *h, AviBatchArgs &a, const NodeWs &ws)
+// warm_big: Stage B starts from the set the multipliers of the incoming a.z name (QPN_OPT_WARM_BIG; solve_nodes_launch decides)
+int sweep_big2(qpn_ctx *ctx, qpn_nodes *h, AviBatchArgs &a, const NodeWs &ws, bool warm_big)
 {
     hipStream_t s = ctx->stream;
     const int32_t batch = a.batch;
@@ -483,7 +484,8 @@ int sweep_big2(qpn_ctx *ctx, qpn_nodes *h, AviBatchArgs &a, const NodeWs &ws)
     // leaves (and every node otherwise) is the delayed-update Lemke kernel's
     // (a caller-set pivot budget is Lemke's to count: its pivots are the unit of max_pivots)
     const bool bpp = a.nd.sym && a.max_pivots <= 0;
-    if (bpp) HIPCHK(ctx, qpn_launch_schur_big_bpp(a, sw, dict, s));
+    // (the hint is for the sweeps that launch it: with a pivot budget, or on the general variants, the flag changes nothing)
+    if (bpp) HIPCHK(ctx, qpn_launch_schur_big_bpp(a, sw, dict, warm_big, s));
     HIPCHK(ctx, qpn_launch_schur_big_lemke(a, sw, dict, s, bpp ? 1 : 0));
     HIPCHK(ctx, qpn_launch_schur_big2_finish(a, sw, s));
     return solve_general(ctx, a, ws, true, false);
@@ -509,6 +511,10 @@ int solve_nodes_launch(qpn_ctx *ctx, qpn_nodes *h, int32_t batch, int32_t n, int
     // (the warm-start bit is this function's: the solve kernels see the flags of a call without it)
     a.max_pivots = o.max_pivots; a.flags = o.flags & 0xFFFF & ~QPN_AVI_FLAG_WARM_DUALS;
     a.nd = NodeSrc{n, m, p, d.Q, d.R, d.q, d.A, d.B, d.l, d.u, d.w, stride_w, (h && h->sym && ctx->sym_route == 1) ? 1 : 0};
+    // QPN_OPT_WARM_BIG: large resident nodes on the symmetric route seed block principal pivoting from the caller's multipliers
+    // (d.z carries them when the call is no cold start: solve_nodes_any makes a call without z one)
+    const bool warm_big = ctx->warm_big == 1 && route == NodeRoute::big2 && a.nd.sym && o.max_pivots <= 0 && d.z &&
+                          (o.flags & QPN_AVI_FLAG_WARM_DUALS) && !(o.flags & QPN_AVI_FLAG_COLD_START);
 #ifdef QPN_STAMPS
     a.stamps = g_stamps;
 #endif
@@ -522,7 +528,7 @@ int solve_nodes_launch(qpn_ctx *ctx, qpn_nodes *h, int32_t batch, int32_t n, int
     switch (route) {
     case NodeRoute::fused32: rc = sweep_fused32(ctx, h, a, ws, out, warm_list, &x_in_kernel); break;
     case NodeRoute::mid: rc = sweep_mid(ctx, h, a, ws, out, &x_in_kernel); break;
-    case NodeRoute::big2: rc = sweep_big2(ctx, h, a, ws); break;
+    case NodeRoute::big2: rc = sweep_big2(ctx, h, a, ws, warm_big); break;
     case NodeRoute::general: rc = sweep_general(ctx, a, ws); break;
     }
     if (rc != QPN_OK) return rc;

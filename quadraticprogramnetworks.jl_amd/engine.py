@@ -1004,7 +1004,10 @@ class Nodes:
 
         warm = the z of an earlier sweep over these nodes ([batch, n + m], where w lives): its multipliers name the active set
         every node starts from (QPN_AVI_FLAG_WARM_DUALS, include/qpn_hip.h; n, m <= 32, cold elsewhere).  A node whose hint
-        holds comes back with pivots = 0, every other one is solved cold in the same call.  warm may be out["z"] itself (the
+        holds comes back with pivots = 0, every other one is solved cold in the same call.  Large symmetric records
+        (64 < n <= 256, m <= 256) take the hint too once the engine has set_option(OPT_WARM_BIG, 1): it seeds block principal
+        pivoting, a node whose hint holds comes back with pivots = n (n + the pairs switched otherwise), and a wrong hint costs
+        rounds, never the result; without the option the hint is ignored there.  warm may be out["z"] itself (the
         sweep loop's form: the hint is overwritten by the solution).  The same through opts: with AVI_FLAG_WARM_DUALS set (and
         AVI_FLAG_COLD_START clear) out["z"] carries the hint."""
         eng = self.eng

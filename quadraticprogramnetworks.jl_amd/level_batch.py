@@ -597,7 +597,8 @@ def _pool_blocks_local(qpn, pool: List[int], assign: Dict[int, Poly]):
 # ---------------------------------------------------------------------------------------------------------------------
 # False: every sweep of solve_level solves its nodes from cold duals (the code as it was).  True: solve_level keeps the last z of
 # every resident childless batch where the engine computes and hands it to the next sweep's solve as the hint; inner nodes and
-# pools stay cold.
+# pools stay cold.  The hint is passed for any shape: the engine honours it for n, m <= 32, and for large resident batches
+# (64 < n <= 256, m <= 256, symmetric Qd) once the engine's option OPT_WARM_BIG is set; everywhere else it is ignored.
 WARM_DUALS_ROUTE = False
 WARM_CHECK_TOL, WARM_PIV_TOL, WARM_COMP_TOL = 1e-6, 1e-11, 1e-2     # qpn_avi_default_opts
 
@@ -703,6 +704,117 @@ def warm_nodes_host(records, w, z_prev, opts=None):
             continue
         out["accepted"][b] = True
         out["z"][b] = z; out["status"][b] = 1; out["resid"][b] = resid; out["pivots"][b] = 0; out["active"][b] = mask
+    return out
+
+
+# block principal pivoting of the large class (csrc/qpn_avi_schur_big.hip: schur_big_bpp) and its warm start
+BPP_KMAX, BPP_MAX_IT, BPP_PIV_REL = 112, 30, 1e-13
+
+
+def _bpp_factor_ok(SAA):
+    """The failure test of the kernel's tile Cholesky (csrc/qpn_tile_chol.h) on the lower triangle of SAA: every pivot has to lie
+    above 1e-13 max(1, first diagonal entry of its 16 x 16 tile, as updated by the tile columns before it)."""
+    L = np.tril(np.array(SAA, dtype=np.float64))
+    k = L.shape[0]
+    d0 = 1.0
+    for j in range(k):
+        if j % 16 == 0:
+            d0 = max(1.0, abs(L[j, j]))
+        pv = L[j, j]
+        if not pv > BPP_PIV_REL * d0:
+            return False
+        L[j:, j] /= np.sqrt(pv)
+        col = L[j + 1:, j]
+        L[j + 1:, j + 1:] -= np.tril(np.outer(col, col))
+    return True
+
+
+def warm_big_host(S, c, l, u, lam_hint=None):
+    """Numpy twin of Stage B of a large symmetric node, schur_big_bpp, on its Schur problem: find lam with s = S lam + c in
+    [l, u], lam_i >= 0 only where s_i = l_i, <= 0 only where s_i = u_i (S [m, m] symmetric, m <= 256).
+
+    THE SEED RULE (lam_hint given: QPN_OPT_WARM_BIG with QPN_AVI_FLAG_WARM_DUALS) -- row i starts at l_i if lam_hint_i > 0 and l_i
+    is finite, at u_i if lam_hint_i < 0 and u_i is finite, and inactive otherwise (NaN, +-0).  THE CAP RULE -- a seed of no row or
+    of more than BPP_KMAX rows is dropped: the cold start alone runs.  lam_hint = None is the cold start: the rows violated at
+    lam = 0, the BPP_KMAX most violated ones when there are more.  THE ROUNDS -- with A the rows at a bound, lam_A solves
+    S_AA lam_A = t_A - c_A, lam = 0 elsewhere, s = c + S(:, A) lam_A; rows of A whose multiplier has the wrong sign leave, free
+    rows outside their interval enter (lowest index first while A has room), until no pair is violated (tolerances 1e-10 x
+    scale); the count of violated pairs has to reach a new minimum within three rounds, otherwise only the violated pair of the
+    highest index is switched (Murty).  An attempt fails on a pivot of the Cholesky factorisation under its threshold or after
+    BPP_MAX_IT rounds.  THE RESTART -- a failed seeded attempt is followed by one cold attempt.  The systems are solved with S_AA
+    itself (the kernel factors the lower triangle and refines once with the rows of S on the final set).
+
+    -> dict(lam [m], side [m] int8 (0 free, 1 at l, 2 at u), rounds, switched, finished, seeded, restarted): rounds and switched
+    (the complementarity pairs switched after the start) count over both attempts; finished = False is the kernel's
+    BPP_NOT_SOLVED (an equality row, or every attempt failed) and leaves lam zero."""
+    S = np.asarray(S, dtype=np.float64); c = np.asarray(c, dtype=np.float64)
+    l = np.asarray(l, dtype=np.float64); u = np.asarray(u, dtype=np.float64)
+    m = c.size
+    out = dict(lam=np.zeros(m), side=np.zeros(m, np.int8), rounds=0, switched=0, finished=False, seeded=False, restarted=False)
+    if m < 1 or m > 256 or np.any(l == u):
+        return out
+    scale = max(1.0, np.max(np.abs(c)), np.max(np.abs(l[l > -INF]), initial=0.0), np.max(np.abs(u[u < INF]), initial=0.0))
+    tol_s = 1e-10 * scale
+
+    def cold():
+        v0 = np.maximum(l - c, c - u)
+        viol = v0 > tol_s
+        if viol.sum() > BPP_KMAX:
+            lo_, hi_ = tol_s, float(v0.max())
+            for _ in range(12):
+                mid = 0.5 * (lo_ + hi_)
+                if (v0 > mid).sum() > BPP_KMAX:
+                    lo_ = mid
+                else:
+                    hi_ = mid
+            viol = v0 > hi_
+        return np.where(viol, np.where(c < l, 1, 2), 0).astype(np.int8)
+
+    starts = [cold]
+    if lam_hint is not None:
+        h = np.asarray(lam_hint, dtype=np.float64).reshape(m)
+        with np.errstate(invalid="ignore"):
+            seed = np.where((h > 0) & (l > -INF), 1, np.where((h < 0) & (u < INF), 2, 0)).astype(np.int8)
+        if 1 <= np.count_nonzero(seed) <= BPP_KMAX:
+            starts = [lambda: seed.copy(), cold]
+            out["seeded"] = True
+    for attempt, start in enumerate(starts):
+        st = start()
+        out["restarted"] = attempt > 0
+        nbest, patience = m + 1, 3
+        for _ in range(BPP_MAX_IT):
+            out["rounds"] += 1
+            A = np.flatnonzero(st)
+            k = A.size
+            lam = np.zeros(m)
+            if k:
+                SAA = S[np.ix_(A, A)]
+                if not _bpp_factor_ok(SAA):
+                    break
+                lam[A] = np.linalg.solve(SAA, np.where(st[A] == 1, l[A], u[A]) - c[A])
+            s = c + S[A].T @ lam[A]                             # (rows A of S: the kernel reads the column block this way)
+            s = np.where(st == 1, l, np.where(st == 2, u, s))
+            tol_l = 1e-10 * max(1.0, np.max(np.abs(lam)))
+            bad = ((st == 1) & (lam < -tol_l)) | ((st == 2) & (lam > tol_l)) | ((st == 0) & ((s < l - tol_s) | (s > u + tol_s)))
+            nb = int(bad.sum())
+            if nb == 0:
+                out.update(lam=lam, side=st, finished=True)
+                return out
+            flip = bad
+            if nb < nbest:
+                nbest, patience = nb, 3
+            elif patience > 0:
+                patience -= 1
+            else:
+                flip = np.zeros(m, bool); flip[np.flatnonzero(bad)[-1]] = True
+            leave = flip & (st != 0)
+            enter = np.flatnonzero(flip & (st == 0))
+            room = BPP_KMAX - (k - int(leave.sum()))
+            st = st.copy()
+            st[leave] = 0
+            enter = enter[:max(room, 0)]
+            st[enter] = np.where(s[enter] < l[enter], 1, 2)
+            out["switched"] += int(leave.sum()) + enter.size
     return out
 
 
