@@ -63,7 +63,14 @@ typedef struct qpn_ctx qpn_ctx;
  * bit set does not fill the crash cache (it reuses a valid one).
  * One more class takes the hint once its context opts in: resident records of large nodes (64 < n <= 256, m <= 256) on the
  * symmetric route, through qpn_solve_nodes_h with QPN_OPT_WARM_BIG = 1 (see there: the hint seeds block principal pivoting,
- * pivots = n when it held).  Without that option the bit is ignored there as everywhere else. */
+ * pivots = n when it held).  Without that option the bit is ignored there as everywhere else.
+ * The mid-size classes (n, m <= 128, one of them > 32) take the hint per resident handle: after qpn_nodes_set_warm(ctx, nodes, 1)
+ * a qpn_solve_nodes_h sweep with the bit (z != NULL, QPN_AVI_FLAG_COLD_START clear) that the fused mid-size kernels serve
+ * (QPN_OPT_MID_ROUTE = 1, no pivot budget that closes them) runs the same warm solve, one workgroup per node, with the same accept
+ * rule and outputs (pivots = 0) and one more condition: the k hinted rows have to fit the kernel's LDS,
+ * 8 (k (n | 1) + n ((k + 1) | 1)) + 15 648 <= 163 840 bytes -- every k <= min(n, 64) in every shape, every k <= 71 at n = 128.
+ * A node outside it is solved cold like every other decliner.  Handles that have not opted in, and the per-call entry points,
+ * ignore the bit in these classes. */
 #define QPN_AVI_FLAG_WARM_DUALS 2
 
 typedef struct {
@@ -220,6 +227,10 @@ int qpn_solve_nodes_into(qpn_ctx *ctx, int32_t batch, int32_t n, int32_t m, int3
  * solve kernel updates; the order is re-sorted from them every `period` sweeps at first and every 4 x `period` once
  * settled; qpn_nodes_set_schedule, period 0 = natural order).
  * qpn_nodes_update replaces one array of the records (e.g. the bounds after a new child piece was chosen).
+ * qpn_nodes_set_warm(on = 1) lets the sweeps over a handle of the mid-size classes (n, m <= 128, one of them > 32) honour
+ * QPN_AVI_FLAG_WARM_DUALS (see there); on = 0, the default, makes them cold again.  Any other value of `on` is QPN_ERR_ARG.  On a
+ * handle of another shape the call succeeds and changes nothing: n, m <= 32 honour the flag anyway, and beyond 128
+ * QPN_OPT_WARM_BIG is the switch.
  * Symmetric n = m = 32 records also keep the part of the solve that Qd and Ad alone decide (QPN_OPT_CRASH_CACHE): the first
  * sweep stores it, the later ones reuse it, with bit-identical results.  Cost in HBM: the records are 22 KB per n = m = 32
  * node, the crash cache adds 22 KB per node (symmetric records; the general variants -- 24 KB -- are not cached).  It is allocated
@@ -238,6 +249,7 @@ int qpn_nodes_upload(qpn_ctx *ctx, int32_t batch, int32_t n, int32_t m, int32_t 
                      const double *u, int mem, qpn_nodes **out);
 int qpn_nodes_update(qpn_ctx *ctx, qpn_nodes *nodes, int32_t field, const double *data, int mem);
 int qpn_nodes_set_schedule(qpn_ctx *ctx, qpn_nodes *nodes, int32_t period);
+int qpn_nodes_set_warm(qpn_ctx *ctx, qpn_nodes *nodes, int32_t on);
 int qpn_nodes_free(qpn_ctx *ctx, qpn_nodes *nodes);
 /* info[0] = what is known about the general kernel's share of these records: 0 nothing yet, 1 the count of the first
  * sweep is on its way to the host, 2 no node needs it (sweeps are one launch), 3 some do; info[1] = that count (valid

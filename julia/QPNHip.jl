@@ -21,7 +21,7 @@ const QPN_MEM_HOST = Cint(0)
 const QPN_SUCCESS = Int32(1)
 
 const QPN_AVI_FLAG_COLD_START = Int32(1)   # include/qpn_hip.h
-const QPN_AVI_FLAG_WARM_DUALS = Int32(2)   # n, m <= 32 node solves: the multipliers of the incoming z name the active set to start from
+const QPN_AVI_FLAG_WARM_DUALS = Int32(2)   # n, m <= 32 node solves (mid-size handles after nodes_set_warm!): the multipliers of the incoming z name the active set to start from
 struct AviOpts                # qpn_avi_opts, include/qpn_hip.h
     check_tol::Cdouble
     piv_tol::Cdouble
@@ -180,7 +180,16 @@ function update_nodes!(nodes::Nodes, field::Int32, data::Array{Float64})
     nothing
 end
 
+# Opt a handle of the mid-size classes (n, m <= 128, one of them > 32) in to the warm start (`on = true`) or out of it: with it on,
+# solve_nodes!(nodes, w; warm = z_prev) runs the warm kernel ahead of the cold one.  On a handle of another shape nothing changes.
+function nodes_set_warm!(nodes::Nodes, on::Bool = true)
+    rc = ccall((:qpn_nodes_set_warm, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int32), ctx(), nodes.h, Int32(on))
+    rc == 0 || error("qpn_nodes_set_warm failed ($rc)")
+    nothing
+end
+
 # warm = the z of an earlier sweep over the handle's nodes: QPN_AVI_FLAG_WARM_DUALS, as in solve_nodes! above (z comes back).
+# Handles of the mid-size classes take it after nodes_set_warm!(nodes).
 # Handles of large symmetric nodes (64 < n <= 256, m <= 256) take it too after set_option!(QPN_OPT_WARM_BIG, 1): the hint seeds
 # block principal pivoting, `pivots == n` says that it held, and a wrong hint costs rounds, never the result; without the option
 # the hint is ignored in that class.

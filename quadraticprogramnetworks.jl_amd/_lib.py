@@ -19,7 +19,7 @@ ABI_SYMBOLS = (
     "qpn_set_node_order", "qpn_verify_nodes",
     "qpn_shared_alloc", "qpn_shared_open", "qpn_shared_close", "qpn_shared_free", "qpn_set_primal_mirrors",
     "qpn_sweep_status", "qpn_ctx_set_auto_schedule", "qpn_ctx_set_option",
-    "qpn_nodes_upload", "qpn_nodes_update", "qpn_nodes_set_schedule", "qpn_nodes_free", "qpn_nodes_info", "qpn_solve_nodes_h",
+    "qpn_nodes_upload", "qpn_nodes_update", "qpn_nodes_set_schedule", "qpn_nodes_set_warm", "qpn_nodes_free", "qpn_nodes_info", "qpn_solve_nodes_h",
     "qpn_verify_nodes_h", "qpn_pool_size", "qpn_assemble_pools", "qpn_local_pieces", "qpn_recipes_from_masks",
     "qpn_recipes_batch", "qpn_reduced_pieces", "qpn_project_pieces", "qpn_convexity_nodes", "qpn_recipes_batch_range", "qpn_finish_pieces",
     "qpn_multiplier_vertices", "qpn_recipe_filter",
@@ -31,7 +31,7 @@ ABI_SYMBOLS = (
 
 MEM_HOST, MEM_DEVICE = 0, 1
 AVI_FLAG_COLD_START = 1
-AVI_FLAG_WARM_DUALS = 2         # n, m <= 32 node solves (and large resident ones under OPT_WARM_BIG): the multipliers of the incoming z name the active set to start from
+AVI_FLAG_WARM_DUALS = 2         # n, m <= 32 node solves (mid-size handles after Nodes.set_warm, large resident ones under OPT_WARM_BIG): the multipliers of the incoming z name the active set to start from
 MAX_MIRRORS = 7
 IPC_HANDLE_BYTES = 64
 SHARED_FINE_GRAINED = 1
@@ -140,6 +140,7 @@ def load_library():
                                      C.POINTER(vp)]
     lib.qpn_nodes_update.argtypes = [vp, vp, C.c_int32, vp, C.c_int]
     lib.qpn_nodes_set_schedule.argtypes = [vp, vp, C.c_int32]
+    lib.qpn_nodes_set_warm.argtypes = [vp, vp, C.c_int32]
     lib.qpn_nodes_free.argtypes = [vp, vp]
     lib.qpn_nodes_info.argtypes = [vp, vp, vp]
     lib.qpn_solve_nodes_h.argtypes = [vp, vp, vp, C.c_int64, vp, vp, vp, vp, vp, C.POINTER(AviOpts), C.c_int, vp, C.c_int64]

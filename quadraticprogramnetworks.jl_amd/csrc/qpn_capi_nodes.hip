@@ -132,6 +132,8 @@ struct qpn_nodes {
     // alone).  Allocated with the cache.
     CrashCache big;
     HostCount big_entries;
+    // qpn_nodes_set_warm: sweeps on the mid route that carry QPN_AVI_FLAG_WARM_DUALS run the warm kernel (qpn_warm_mid.hip) first
+    bool warm_mid = false;
 };
 
 NodeRoute node_route(const qpn_ctx *ctx, int32_t n, int32_t m, const qpn_avi_opts &o)
@@ -422,13 +424,20 @@ int sweep_fused32(qpn_ctx *ctx, qpn_nodes *h, AviBatchArgs &a, const NodeWs &ws,
 
 // mid-size nodes (n, m <= 128): one wavefront (max(n, m) <= 48) or one workgroup per node straight from the records, ONE
 // launch; what they decline (status = -1) is assembled and solved by the general kernels in gated launches
-int sweep_mid(qpn_ctx *ctx, qpn_nodes *h, AviBatchArgs &a, const NodeWs &ws, const PrimalOut &out, bool *x_in_kernel)
+// warm_list (a handle that opted in, qpn_nodes_set_warm; solve_nodes_any decides): the warm kernel goes first, as in the 32-class
+int sweep_mid(qpn_ctx *ctx, qpn_nodes *h, AviBatchArgs &a, const NodeWs &ws, const PrimalOut &out, int32_t *warm_list,
+              bool *x_in_kernel)
 {
     hipStream_t s = ctx->stream;
     const int32_t batch = a.batch, n = a.nd.n, m = a.nd.m;
     int rc = QPN_OK;
     bool need_general;
-    if ((rc = declines_begin(ctx, h, a, &need_general)) != QPN_OK) return rc;
+    if (warm_list) {
+        // a sweep over a part of the nodes is no census of the fused kernel's declines: the handle uses what it knows and
+        // learns nothing from this one
+        nodes_poll_declines(h);
+        need_general = !(h && h->declines.state == 2);
+    } else if ((rc = declines_begin(ctx, h, a, &need_general)) != QPN_OK) return rc;
     AviBatchArgs f = a;
     // the kernel writes the primal blocks into the iterate itself once it is known that nothing declines (the general
     // kernels behind it do not); until then the strided copy of solve_nodes_launch does
@@ -441,12 +450,21 @@ int sweep_mid(qpn_ctx *ctx, qpn_nodes *h, AviBatchArgs &a, const NodeWs &ws, con
     const bool one_wave = qpn_schur48_shape(n, m), two_role = qpn_schur_wg2_shape(n, m);
     const bool sched = schedules(h, batch, one_wave ? 2048 : (two_role ? 256 : 1024));
     if (sched) { f.sched_key = h->key; if (h->order_valid) f.order = h->order; }
+    // QPN_AVI_FLAG_WARM_DUALS on a handle that opted in: the warm kernel goes first, over the nodes of that order, and writes the
+    // primal blocks under the same rule.  What it accepts is done; the indices of the others come back compacted in warm_list,
+    // padded with -1, and that list is the order of the cold launch -- out-of-range entries leave a slot unsolved, so nothing
+    // waits for the count on the host, and only the decliners feed the smoothed pivot counts of the schedule.
+    if (warm_list) {
+        HIPCHK(ctx, hipMemsetAsync(warm_list, 0xFF, ((size_t)batch + 1) * 4, s));
+        HIPCHK(ctx, qpn_launch_warm_mid_nodes(f, warm_list, s));
+        f.order = warm_list;
+    }
     if (two_role) HIPCHK(ctx, qpn_launch_schur_wg2_nodes(f, s));
     else if (one_wave) HIPCHK(ctx, qpn_launch_avi_solve_schur48_nodes(f, s));
     else HIPCHK(ctx, qpn_launch_schur_wg_nodes(f, s));
     if (sched && (rc = schedule_refresh(ctx, h, batch)) != QPN_OK) return rc;
     if (need_general && (rc = solve_general(ctx, a, ws, true, false)) != QPN_OK) return rc;
-    return declines_end(ctx, h);
+    return warm_list ? QPN_OK : declines_end(ctx, h);
 }
 
 // large nodes (BASELINE config 5): the blocked crash straight from the records, the delayed-update Lemke kernel on the
@@ -527,7 +545,7 @@ int solve_nodes_launch(qpn_ctx *ctx, qpn_nodes *h, int32_t batch, int32_t n, int
     int rc = QPN_OK;
     switch (route) {
     case NodeRoute::fused32: rc = sweep_fused32(ctx, h, a, ws, out, warm_list, &x_in_kernel); break;
-    case NodeRoute::mid: rc = sweep_mid(ctx, h, a, ws, out, &x_in_kernel); break;
+    case NodeRoute::mid: rc = sweep_mid(ctx, h, a, ws, out, warm_list, &x_in_kernel); break;
     case NodeRoute::big2: rc = sweep_big2(ctx, h, a, ws, warm_big); break;
     case NodeRoute::general: rc = sweep_general(ctx, a, ws); break;
     }
@@ -594,9 +612,10 @@ int solve_nodes_any(qpn_ctx *ctx, qpn_nodes *h, int32_t batch, int32_t n, int32_
     double *hx = nullptr;
     if (x_ws) st.scratch(hx, (size_t)batch * n * 8);
     if (x) st.out2d(x_ws ? hx : d.z, (size_t)(x_ws ? n : N) * 8, x, (size_t)stride_x * 8, (size_t)n * 8, (size_t)batch);
-    // QPN_AVI_FLAG_WARM_DUALS: honoured by the 32-class when the caller's z carries a hint (z given, no cold start); the list of
-    // the nodes the warm kernel declines and its counter
-    const bool warm = route == NodeRoute::fused32 && (o.flags & QPN_AVI_FLAG_WARM_DUALS) && !(o.flags & QPN_AVI_FLAG_COLD_START);
+    // QPN_AVI_FLAG_WARM_DUALS: honoured by the 32-class, and by the mid route on a handle that opted in (qpn_nodes_set_warm), when
+    // the caller's z carries a hint (z given, no cold start); the list of the nodes the warm kernel declines and its counter
+    const bool warm_route = route == NodeRoute::fused32 || (route == NodeRoute::mid && h && h->warm_mid);
+    const bool warm = warm_route && (o.flags & QPN_AVI_FLAG_WARM_DUALS) && !(o.flags & QPN_AVI_FLAG_COLD_START);
     int32_t *warm_list = nullptr;
     if (warm) st.scratch(warm_list, ((size_t)batch + 1) * 4);
     int rc = st.begin();
@@ -761,6 +780,15 @@ int qpn_nodes_set_schedule(qpn_ctx *ctx, qpn_nodes *h, int32_t period)
     if (!h || period < 0) return fail_arg(ctx, "qpn_nodes_set_schedule: bad argument");
     h->period = period; h->calls = 0;
     if (period == 0) h->order_valid = false;
+    return QPN_OK;
+}
+
+int qpn_nodes_set_warm(qpn_ctx *ctx, qpn_nodes *h, int32_t on)
+{
+    if (!ctx) return QPN_ERR_ARG;
+    if (!h || (on != 0 && on != 1)) return fail_arg(ctx, "qpn_nodes_set_warm: bad argument");
+    // only the shapes of the mid route have this switch: n, m <= 32 honour the flag anyway, larger nodes have QPN_OPT_WARM_BIG
+    if (qpn_schur_wg_shape(h->n, h->m) || qpn_schur_wg2_shape(h->n, h->m)) h->warm_mid = on == 1;
     return QPN_OK;
 }
 

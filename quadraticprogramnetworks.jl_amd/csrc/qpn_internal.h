@@ -251,6 +251,17 @@ hipError_t qpn_launch_avi_solve_schur_nodes(const AviBatchArgs &a, hipStream_t s
 // launch's order array: its -1 entries leave their slots unsolved.
 hipError_t qpn_launch_warm_nodes(const AviBatchArgs &a, int32_t *dec_list, hipStream_t stream);
 
+// qpn_warm_mid.hip: the same warm start for the mid-size classes (n, m <= 128, one of them > 32; qpn_nodes_set_warm), one
+// workgroup per node; accept rule, outputs and decliners' list as above.  The kernel keeps A_act (k x n) and W | h (n x (k + 1))
+// in LDS beside kWarmMidFixed bytes of vectors; a hint of k rows that this does not hold declines.  ONE rule, a pure function
+// of (n, k) and monotone in k: every k <= min(n, 64) in every shape, every k <= 71 at n = 128.
+constexpr int kWarmMidLds = 160 * 1024, kWarmMidFixed = 15648;
+__host__ __device__ constexpr bool warm_mid_fits(int n, int k)
+{
+    return k >= 0 && k <= n && 8 * (k * (n | 1) + n * ((k + 1) | 1)) + kWarmMidFixed <= kWarmMidLds;
+}
+hipError_t qpn_launch_warm_mid_nodes(const AviBatchArgs &a, int32_t *dec_list, hipStream_t stream);
+
 // qpn_avi_reg.hip
 hipError_t qpn_launch_avi_solve(const AviBatchArgs &a, hipStream_t stream);      // dispatcher: Schur kernel, then the register kernel
 hipError_t qpn_launch_avi_solve_reg(const AviBatchArgs &a, hipStream_t stream);  // register-tableau kernel

@@ -998,13 +998,21 @@ class Nodes:
     def set_schedule(self, period=16):
         self.eng._call("qpn_nodes_set_schedule", self.h, int(period))
 
+    def set_warm(self, on=True):
+        """Opt this handle's sweeps in to (or out of) the warm start of the mid-size classes (n, m <= 128, one of them > 32;
+        qpn_nodes_set_warm): with it on, solve(..., warm=z_prev) runs the warm kernel ahead of the cold one.  On a handle of another
+        shape the call changes nothing.  on: True / False (or 1 / 0)."""
+        self.eng._call("qpn_nodes_set_warm", self.h, int(on))
+
     def solve(self, w, opts=None, want=("z", "resid", "pivots", "active"), out=None, x_out=None, warm=None):
         """One sweep over the resident nodes with parameters w ((p,) shared or (batch, p)); cold duals.  `want` names the
         optional outputs (status always comes back); x_out as in Engine.solve_nodes.
 
         warm = the z of an earlier sweep over these nodes ([batch, n + m], where w lives): its multipliers name the active set
-        every node starts from (QPN_AVI_FLAG_WARM_DUALS, include/qpn_hip.h; n, m <= 32, cold elsewhere).  A node whose hint
-        holds comes back with pivots = 0, every other one is solved cold in the same call.  Large symmetric records
+        every node starts from (QPN_AVI_FLAG_WARM_DUALS, include/qpn_hip.h): always when n, m <= 32, and in the mid-size classes
+        (n, m <= 128, one of them > 32) once the handle has opted in with set_warm(); without that the hint is ignored there and
+        the sweep is cold.  A node whose hint holds comes back with pivots = 0, every other one -- in the mid-size classes also
+        one whose hint has more rows than level_batch.warm_mid_fits admits -- is solved cold in the same call.  Large symmetric records
         (64 < n <= 256, m <= 256) take the hint too once the engine has set_option(OPT_WARM_BIG, 1): it seeds block principal
         pivoting, a node whose hint holds comes back with pivots = n (n + the pairs switched otherwise), and a wrong hint costs
         rounds, never the result; without the option the hint is ignored there.  warm may be out["z"] itself (the

@@ -196,13 +196,16 @@ class RecordBatch:
         w = np.where(self.par >= 0, x[np.maximum(self.par, 0)], 0.0)
         return xd, w
 
-    def resident(self, engine):
-        """The records as a resident handle of `engine` (made once), or None when the engine has no such thing."""
+    def resident(self, engine, warm_mid=False):
+        """The records as a resident handle of `engine` (made once), or None when the engine has no such thing.  warm_mid: a
+        handle made by this call opts in to the warm start of the mid-size classes (Nodes.set_warm)."""
         if not hasattr(engine, "upload_nodes"):
             return None
         if self.handle is None or self.handle_engine is not engine:
             self.handle = engine.upload_nodes(self.Qc, self.Rc, self.qd, self.Ac, self.Bc, self.l, self.u)
             self.handle_engine = engine
+            if warm_mid:
+                self.handle.set_warm(1)
         return self.handle
 
 
@@ -379,7 +382,7 @@ class DeviceRecordBatch(RecordBatch):
     Bc = property(lambda self: self._arrays()[4]); l = property(lambda self: self._arrays()[5])
     u = property(lambda self: self._arrays()[6])
 
-    def resident(self, engine):
+    def resident(self, engine, warm_mid=False):
         return None
 
     def solve(self, eng, w, z0):
@@ -600,6 +603,9 @@ def _pool_blocks_local(qpn, pool: List[int], assign: Dict[int, Poly]):
 # pools stay cold.  The hint is passed for any shape: the engine honours it for n, m <= 32, and for large resident batches
 # (64 < n <= 256, m <= 256, symmetric Qd) once the engine's option OPT_WARM_BIG is set; everywhere else it is ignored.
 WARM_DUALS_ROUTE = False
+# The mid-size classes (n, m <= 128, one of them > 32) take the hint per handle (Nodes.set_warm).  True, together
+# with WARM_DUALS_ROUTE: the resident childless batches opt in once, when their handle is made.  False: everything as without it.
+WARM_DUALS_MID = False
 WARM_CHECK_TOL, WARM_PIV_TOL, WARM_COMP_TOL = 1e-6, 1e-11, 1e-2     # qpn_avi_default_opts
 
 
@@ -647,8 +653,19 @@ def node_postcheck(z, r, l, u, n, check_tol=WARM_CHECK_TOL, comp_tol=WARM_COMP_T
     return bool(bad.any()), float(nres.max()) if N else 0.0, mask
 
 
-def warm_nodes_host(records, w, z_prev, opts=None):
-    """Numpy twin of the warm kernel (csrc/qpn_warm.hip).  records = (Qc, Rc, qd, Ac, Bc, l, u) in the ABI layout, w (p,) or
+WARM_MID_LDS, WARM_MID_FIXED = 160 * 1024, 15648     # kWarmMidLds, kWarmMidFixed (csrc/qpn_internal.h)
+
+
+def warm_mid_fits(n, k):
+    """warm_mid_fits of csrc/qpn_internal.h restated: does the warm kernel of the mid-size classes (csrc/qpn_warm_mid.hip) hold a
+    hint of k rows on a node with n variables -- A_act (k x n) and W | h (n x (k + 1)), both with odd row strides, beside the
+    fixed part of its LDS?  A pure function of (n, k), monotone in k."""
+    n, k = int(n), int(k)
+    return 0 <= k <= n and 8 * (k * (n | 1) + n * ((k + 1) | 1)) + WARM_MID_FIXED <= WARM_MID_LDS
+
+
+def warm_nodes_host(records, w, z_prev, opts=None, fits=None):
+    """Numpy twin of the warm kernels (csrc/qpn_warm.hip, csrc/qpn_warm_mid.hip).  records = (Qc, Rc, qd, Ac, Bc, l, u) in the ABI layout, w (p,) or
     (batch, p), z_prev [batch, n + m]: its multipliers name the hint (side +1 where lambda > 0, -1 where < 0, 0 otherwise).
     Per node the linear KKT system of the hinted rows, [[Qd, -A_act'], [A_act, 0]] [x; lam_act] = [-(qd + R w); bound_act -
     B_act w], by block elimination through Qd and the k x k Schur block (partial pivoting, fp64).
@@ -656,7 +673,7 @@ def warm_nodes_host(records, w, z_prev, opts=None):
     THE ACCEPT RULE -- a node is accepted only if all of these hold:
       every hinted multiplier is finite and its row has a finite bound on its side;  k <= n;  no pivot of the two eliminations
       is below piv_tol;  every lam_act carries its side's sign (lam_act * side > 0);  the post-check of the cold solve passes
-      (check_tol, on the original blocks).
+      (check_tol, on the original blocks);  with fits= (a predicate of (n, k): warm_mid_fits for the mid-size kernel), fits(n, k).
     -> dict(accepted [batch] bool, z, status, resid, pivots, active): for an accepted node its point, status 1 (SUCCESS), the
     natural-map residual, pivots 0 and the masks (comp_tol); a declined node keeps z_prev's row, status 0, resid NaN, pivots -1,
     active 0 -- the caller solves it cold."""
@@ -680,6 +697,8 @@ def warm_nodes_host(records, w, z_prev, opts=None):
         k = rows.size
         bound = np.where(side > 0, l[b], u[b])[rows]
         if k > n or not np.all(np.isfinite(bound)):
+            continue
+        if fits is not None and not fits(n, k):
             continue
         q = qd[b] + R @ wb
         c = B @ wb
@@ -908,7 +927,7 @@ def solve_level(qpn, players: Sequence[int], x, assign: Optional[Dict[int, Poly]
         b = item
         xd, w = b.gather(x)
         z0 = np.zeros((len(b), b.n + b.m)); z0[:, :b.nx] = xd                       # duals cold, :404
-        h = b.resident(eng) if static else None
+        h = b.resident(eng, WARM_DUALS_ROUTE and WARM_DUALS_MID) if static else None
         if h is not None and WARM_DUALS_ROUTE:
             res = _warm_sweep(b, h, eng, w)
         elif h is not None:
