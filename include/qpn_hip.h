@@ -77,7 +77,7 @@ typedef struct {
     double check_tol;  /* post-check tolerance, 1e-6       (src/avi.jl:148)                 */
     double piv_tol;    /* smallest admissible pivot, 1e-11                                   */
     double feas_tol;   /* basic infeasibility treated as zero, 1e-12                         */
-    double comp_tol;   /* active-set classification tolerance, 1e-2 (src/avi_solutions.jl:511) */
+    double comp_tol;   /* active-set classification tolerance, 1e-2 (src/avi_solutions.jl:511); finite */
     int32_t max_pivots; /* <= 0: 50*N + 100 (cf. PATH limits at src/avi.jl:67-70)             */
     int32_t flags;      /* QPN_AVI_FLAG_* (0 by default)                                        */
 } qpn_avi_opts;

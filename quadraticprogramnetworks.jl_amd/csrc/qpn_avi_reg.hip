@@ -786,26 +786,7 @@ __device__ __forceinline__ void avi_solve_reg_item(const AviBatchArgs &a, const 
     unsigned mask = 0;
     if (act) {
         const double lk = sl[lane], uk = su[lane];
-        const double tol = a.check_tol;
-        if (d > tol && fabs(p - lk) > tol) bad++;
-        if (d < -tol && fabs(p - uk) > tol) bad++;
-        if (p - lk < -tol) bad++;
-        if (p - uk > tol) bad++;
-        if (isnan(p) || isnan(d)) bad++;
-        double tt = p - d;
-        if (tt < lk) tt = lk;
-        if (tt > uk) tt = uk;
-        nres = fabs(p - tt);
-        if (isnan(nres)) nres = QINF;
-        const double ct = a.comp_tol;
-        auto approx = [&](double x, double y) { return x == y || (isfinite(x) && isfinite(y) && fabs(x - y) <= ct); };
-        const bool eq = approx(lk, uk);
-        if (!eq) {
-            if (approx(p, lk) && d >= -ct) mask |= 1u;
-            if (lk - ct <= p && p <= uk + ct && fabs(d) <= ct) mask |= 2u;
-            if (approx(p, uk) && d <= ct) mask |= 4u;
-        } else mask = 8u;
-        if (gk) mask <<= 4;
+        QPN_ROW_POSTCHECK(bad, nres, mask, p, d, lk, uk, gk, a.check_tol, a.comp_tol);
     }
     bad = wave_sum_i32(bad);
     nres = wave_max_f64(nres);
@@ -813,11 +794,7 @@ __device__ __forceinline__ void avi_solve_reg_item(const AviBatchArgs &a, const 
 
     if (act) {
         a.z[vo + lane] = zk;
-        if (a.x && lane < a.nd.n) {                                                   // qpn_solve_nodes_into
-            const size_t xo = (size_t)b * (size_t)a.stride_x + lane;
-            a.x[xo] = zk;
-            for (int k = 0; k < a.n_mirror; ++k) a.mirror[k][xo] = zk;
-        }
+        if (a.x && lane < a.nd.n) qpn_store_primal(&a, a.x, (size_t)b * (size_t)a.stride_x + lane, zk);      // qpn_solve_nodes_into
         if (a.active) a.active[vo + lane] = (uint8_t)mask;
     }
     if (lane == 0) {

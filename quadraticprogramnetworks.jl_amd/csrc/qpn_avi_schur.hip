@@ -123,12 +123,8 @@ __global__ __launch_bounds__(WAVE, 4) void avi_solve_schur(AviBatchArgs a, Schur
     // (the counter's address is read from the kernarg segment on the spot, not kept in registers)
     auto decline = [&]() {
         if (l == 0) {
-            a.status[b] = -1;
-            if constexpr (NODES) {
-                typedef const AviBatchArgs __attribute__((address_space(4))) *kargs_d;
-                int32_t *dc = ((kargs_d)__builtin_amdgcn_kernarg_segment_ptr())->decl_count;
-                if (dc) atomicAdd(dc, 1);
-            }
+            typedef const AviBatchArgs __attribute__((address_space(4))) *kargs_d;
+            qpn_decline_cold(a.status, b, NODES ? ((kargs_d)__builtin_amdgcn_kernarg_segment_ptr())->decl_count : nullptr);
         }
     };
 
@@ -1450,29 +1446,7 @@ stage_a_done: __attribute__((unused));
     int bad = 0;
     double nres = 0.0;
     unsigned mask = 0;
-    if (act) {
-        const double tol = ae.check_tol;
-        if (dv > tol && fabs(pp - lk) > tol) bad++;
-        if (dv < -tol && fabs(pp - uk) > tol) bad++;
-        if (pp - lk < -tol) bad++;
-        if (pp - uk > tol) bad++;
-        if (isnan(pp) || isnan(dv)) bad++;
-        double tt = pp - dv;
-        if (tt < lk) tt = lk;
-        if (tt > uk) tt = uk;
-        nres = fabs(pp - tt);
-        if (isnan(nres)) nres = QINF;
-        const double ct = ae.comp_tol;
-        // x == y, or both finite and within ct: an infinite operand makes |x - y| infinite (or NaN for inf - inf, which the
-        // first clause has already taken), so the finiteness tests of the scalar statement are implied
-        auto approx = [&](double x, double y) { return (x == y) | (fabs(x - y) <= ct); };
-        if (!approx(lk, uk)) {
-            if (approx(pp, lk) && dv >= -ct) mask |= 1u;
-            if (lk - ct <= pp && pp <= uk + ct && fabs(dv) <= ct) mask |= 2u;
-            if (approx(pp, uk) && dv <= ct) mask |= 4u;
-        } else mask = 8u;
-        if (gk) mask <<= 4;
-    }
+    if (act) QPN_ROW_POSTCHECK(bad, nres, mask, pp, dv, lk, uk, gk, ae.check_tol, ae.comp_tol);
     // the counts are >= 0 and only "any" is asked of their sum: one lane mask instead of six cross-lane additions.
     // nres is |pp - tt| with a NaN already replaced by +inf, or the constant 0: a computed value, never a NaN
     const bool anybad = qpn_ballot(bad != 0) != 0ull;
@@ -1480,22 +1454,14 @@ stage_a_done: __attribute__((unused));
     if (anybad && status == QPN_SUCCESS) status = QPN_FAILURE;
     if (act) {
         ae.z[vo + l] = zk;
-        if (ae.x && l < n) {                                                    // primal block -> the caller's iterate
-            const size_t xo = (size_t)b * (size_t)ae.stride_x + l;
-            ae.x[xo] = zk;
-            const int nmir = kp->n_mirror;                                      // ... and its replicas on the peer GPUs
-            for (int k = 0; k < nmir; ++k) kp->mirror[k][xo] = zk;
-        }
+        if (ae.x && l < n) qpn_store_primal(kp, ae.x, (size_t)b * (size_t)ae.stride_x + l, zk);    // primal block -> the caller's iterate and its replicas
         if (ae.active) ae.active[vo + l] = (uint8_t)mask;
     }
     if (l == 0) {
         ae.status[b] = status;
         if (ae.resid) ae.resid[b] = nres;
         if (ae.pivots) ae.pivots[b] = pivots;
-        if constexpr (NODES) {
-            int32_t *const sk = kp->sched_key;                                  // this node's smoothed pivot count
-            if (sk) { const int k0 = sk[b]; sk[b] = k0 > 0 ? k0 - (k0 >> 5) + pivots : 32 * pivots; }
-        }
+        if constexpr (NODES) qpn_update_sched_key(kp->sched_key, b, pivots);
     }
     STAMP(5);   // read-back + post-check + stores
 #ifdef QPN_STAMPS

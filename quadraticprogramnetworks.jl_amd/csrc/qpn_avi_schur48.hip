@@ -20,9 +20,7 @@ __global__ __launch_bounds__(64, 2) void avi_solve_schur48(AviBatchArgs a)
     int b = blockIdx.x;
     if (a.order) { b = a.order[blockIdx.x]; if ((unsigned)b >= (unsigned)a.batch) return; }
     const int n = a.nd.n, m = a.nd.m, np_ = a.nd.p, N = n + m;
-    auto decline = [&]() {
-        if (l == 0) { a.status[b] = -1; if (a.decl_count) atomicAdd(a.decl_count, 1); }
-    };
+    auto decline = [&]() { if (l == 0) qpn_decline_cold(a.status, b, a.decl_count); };
     if (!(n >= 1 && n <= NP && m >= 0 && m <= NP)) { decline(); return; }
     STAMP_DECL;
 
@@ -581,31 +579,12 @@ __global__ __launch_bounds__(64, 2) void avi_solve_schur48(AviBatchArgs a)
         const int gk = !isx;
         const double lk = gk ? a.nd.l[(size_t)b * m + (k - n)] : -QINF, uk = gk ? a.nd.u[(size_t)b * m + (k - n)] : QINF;
         const double pp = gk ? rk : zk, dv = gk ? zk : rk;
-        if (dv > tol && fabs(pp - lk) > tol) bad++;
-        if (dv < -tol && fabs(pp - uk) > tol) bad++;
-        if (pp - lk < -tol) bad++;
-        if (pp - uk > tol) bad++;
-        if (isnan(pp) || isnan(dv)) bad++;
-        double tt = pp - dv;
-        if (tt < lk) tt = lk;
-        if (tt > uk) tt = uk;
-        double e = fabs(pp - tt);
-        if (isnan(e)) e = QINF;
+        double e;
+        unsigned mask;
+        QPN_ROW_POSTCHECK(bad, e, mask, pp, dv, lk, uk, gk, tol, ct);
         nres = fmax(nres, e);
-        unsigned mask = 0;
-        auto approx = [&](double x, double y) { return x == y || (isfinite(x) && isfinite(y) && fabs(x - y) <= ct); };
-        if (!approx(lk, uk)) {
-            if (approx(pp, lk) && dv >= -ct) mask |= 1u;
-            if (lk - ct <= pp && pp <= uk + ct && fabs(dv) <= ct) mask |= 2u;
-            if (approx(pp, uk) && dv <= ct) mask |= 4u;
-        } else mask = 8u;
-        if (gk) mask <<= 4;
         a.z[(size_t)b * N + k] = zk;
-        if (a.x && isx) {
-            const size_t xo = (size_t)b * (size_t)a.stride_x + k;
-            a.x[xo] = zk;
-            for (int q = 0; q < a.n_mirror; ++q) a.mirror[q][xo] = zk;
-        }
+        if (a.x && isx) qpn_store_primal(&a, a.x, (size_t)b * (size_t)a.stride_x + k, zk);
         if (a.active) a.active[(size_t)b * N + k] = (uint8_t)mask;
     };
     if (l < N) check_row(l, zk0, qv0);
@@ -617,7 +596,7 @@ __global__ __launch_bounds__(64, 2) void avi_solve_schur48(AviBatchArgs a)
         a.status[b] = status;
         if (a.resid) a.resid[b] = nres;
         if (a.pivots) a.pivots[b] = pivots;
-        if (a.sched_key) { const int k0 = a.sched_key[b]; a.sched_key[b] = k0 > 0 ? k0 - (k0 >> 5) + pivots : 32 * pivots; }
+        qpn_update_sched_key(a.sched_key, b, pivots);
     }
     STAMP(5);   // post-check + stores
 #ifdef QPN_STAMPS

@@ -647,27 +647,10 @@ __global__ __launch_bounds__(TPB) void schur_big_finish(AviBatchArgs a, SchurBig
         const int gk = k >= n;
         const double zk = zs[k], lk = a.l[vo + k], uk = a.u[vo + k];
         const double p = gk ? rk : zk, d = gk ? zk : rk;
-        const double tol = a.check_tol;
-        if (d > tol && fabs(p - lk) > tol) bad++;
-        if (d < -tol && fabs(p - uk) > tol) bad++;
-        if (p - lk < -tol) bad++;
-        if (p - uk > tol) bad++;
-        if (isnan(p) || isnan(d)) bad++;
-        double tt = p - d;
-        if (tt < lk) tt = lk;
-        if (tt > uk) tt = uk;
-        double e = fabs(p - tt);
-        if (isnan(e)) e = QINF;
+        double e;
+        unsigned mask;
+        QPN_ROW_POSTCHECK(bad, e, mask, p, d, lk, uk, gk, a.check_tol, a.comp_tol);
         if (e > nres) nres = e;
-        unsigned mask = 0;
-        const double ct = a.comp_tol;
-        auto approx = [&](double x, double y) { return x == y || (isfinite(x) && isfinite(y) && fabs(x - y) <= ct); };
-        if (!approx(lk, uk)) {
-            if (approx(p, lk) && d >= -ct) mask |= 1u;
-            if (lk - ct <= p && p <= uk + ct && fabs(d) <= ct) mask |= 2u;
-            if (approx(p, uk) && d <= ct) mask |= 4u;
-        } else mask = 8u;
-        if (gk) mask <<= 4;
         a.z[vo + k] = zk;
         if (a.active) a.active[vo + k] = (uint8_t)mask;
     }

@@ -94,12 +94,7 @@ __global__ __launch_bounds__(128 * NR, (NR >= 7) ? 4 : 3) void schur_wg2_nodes(A
     const double *R_ = a.nd.R + (size_t)b * n * np_;
     const double *B_ = a.nd.B + (size_t)b * m * np_;
     const double *w_ = a.nd.w + (size_t)b * (size_t)a.nd.stride_w;
-    auto decline = [&]() {
-        if (tid == 0) {
-            a.status[b] = -1;
-            if (a.decl_count) atomicAdd(a.decl_count, 1);
-        }
-    };
+    auto decline = [&]() { if (tid == 0) qpn_decline_cold(a.status, b, a.decl_count); };
 
     STAMP_DECL;
     // ---- load ---------------------------------------------------------------------------------------------------------
@@ -940,33 +935,10 @@ __global__ __launch_bounds__(128 * NR, (NR >= 7) ? 4 : 3) void schur_wg2_nodes(A
         const double zk = sz[k];
         const double lk = gk ? le_[(size_t)b * m + (k - n)] : -QINF, uk = gk ? ue_[(size_t)b * m + (k - n)] : QINF;
         const double p = gk ? rk : zk, d = gk ? zk : rk;
-        const double tol = kp->check_tol;
-        if (d > tol && fabs(p - lk) > tol) bad++;
-        if (d < -tol && fabs(p - uk) > tol) bad++;
-        if (p - lk < -tol) bad++;
-        if (p - uk > tol) bad++;
-        if (isnan(p) || isnan(d)) bad++;
-        double tt = p - d;
-        if (tt < lk) tt = lk;
-        if (tt > uk) tt = uk;
-        double e = fabs(p - tt);
-        if (isnan(e)) e = QINF;
-        nres = e;
-        unsigned mask = 0;
-        const double ct = kp->comp_tol;
-        auto approx = [&](double x, double y) { return x == y || (isfinite(x) && isfinite(y) && fabs(x - y) <= ct); };
-        if (!approx(lk, uk)) {
-            if (approx(p, lk) && d >= -ct) mask |= 1u;
-            if (lk - ct <= p && p <= uk + ct && fabs(d) <= ct) mask |= 2u;
-            if (approx(p, uk) && d <= ct) mask |= 4u;
-        } else mask = 8u;
-        if (gk) mask <<= 4;
+        unsigned mask;
+        QPN_ROW_POSTCHECK(bad, nres, mask, p, d, lk, uk, gk, kp->check_tol, kp->comp_tol);
         ze_[(size_t)b * N + k] = zk;
-        if (xe_ && !gk) {                                                       // primal block -> the caller's iterate
-            const size_t xo = (size_t)b * (size_t)kp->stride_x + k;
-            xe_[xo] = zk;
-            for (int q = 0; q < kp->n_mirror; ++q) kp->mirror[q][xo] = zk;          // ... and its replicas on the peer GPUs
-        }
+        if (xe_ && !gk) qpn_store_primal(kp, xe_, (size_t)b * (size_t)kp->stride_x + k, zk);     // primal block -> the caller's iterate and its replicas
         if (ae_) ae_[(size_t)b * N + k] = (uint8_t)mask;
     }
     const int badt = __syncthreads_count(bad > 0);
@@ -992,7 +964,7 @@ __global__ __launch_bounds__(128 * NR, (NR >= 7) ? 4 : 3) void schur_wg2_nodes(A
         for (int k = 1; k < 2 * NR; ++k) rs = sRed[k] > rs ? sRed[k] : rs;
         if (re_) re_[b] = rs;
         if (pe_) pe_[b] = pivots;
-        if (int32_t *const sk = kp->sched_key) { const int k0 = sk[b]; sk[b] = k0 > 0 ? k0 - (k0 >> 5) + pivots : 32 * pivots; }      // smoothed pivot count
+        qpn_update_sched_key(kp->sched_key, b, pivots);
     }
 }
 

@@ -896,6 +896,93 @@ __device__ __forceinline__ int lane_id_fresh()
 }
 __device__ __forceinline__ int pad16(int v) { return (v + 15) & ~15; }
 
+// ---- the epilogue every solver kernel shares ---------------------------------------------------------------------------------
+// THE row post-check: one row with primal part p, dual part d (STD row: p = z_k, d = (M z + q)_k; GAVI row: the other way
+// round) and bounds l <= u.  What a solve reports as status, resid and active[] is made of these and of nothing else; each kernel
+// only maps rows to lanes and reduces the count and the residual over its wavefront or workgroup.
+//   QPN_ROW_VIOLATIONS   adds the violated conditions of check_avi_solution (src/avi.jl:148-156) to `bad`: a count, check_avi
+//                        returns its sum as the degree
+//   QPN_ROW_RESIDUAL     e = the natural-map residual |p - clamp(p - d, l, u)|, a NaN replaced by +inf
+//   QPN_ROW_MASK         mask = the comp_indices mask (src/avi_solutions.jl:511-562), bit c - 1 for code c, before any shift
+//   QPN_ROW_POSTCHECK    the three of a solver row, in that order; the mask of a GAVI row is shifted by 4 (:587-612)
+// Function-like macros for the reason STAMP and QPN_ROW_REDUCE are: the 32-class kernel (qpn_avi_schur.hip) is generated around
+// these statements, and behind a __forceinline__ function -- returning a struct or writing through references alike -- its
+// code is scheduled otherwise and the sweep of the benchmark loses 0.3 % (profiles/postcheck_ab.txt); pasted, the unit's code is
+// the one it was (profiles/postcheck_kernel_resources.md).  The arguments are plain variables or constants: they are evaluated
+// more than once.  level_batch.node_postcheck restates the macros in numpy; tests/test_postcheck_host.py wraps them in a host
+// program and compares them with that twin and with the oracle.
+//
+// qpn_approx: x == y, or both finite and within ct (isapprox with atol = ct).  An infinite operand makes |x - y| infinite (or
+// NaN for inf - inf, which the first clause has already taken), so the finiteness tests of the scalar statement are implied.
+// PRECONDITION: ct (comp_tol) is finite -- with ct = +inf an infinite |x - y| would pass.
+__host__ __device__ __forceinline__ bool qpn_approx(double x, double y, double ct) { return (x == y) | (fabs(x - y) <= ct); }
+#define QPN_ROW_VIOLATIONS(bad, p, d, l, u, tol)                                              \
+    do {                                                                                      \
+        if ((d) > (tol) && fabs((p) - (l)) > (tol)) (bad)++;    /* :152 */                    \
+        if ((d) < -(tol) && fabs((p) - (u)) > (tol)) (bad)++;   /* :153 */                    \
+        if ((p) - (l) < -(tol)) (bad)++;                        /* :154 */                    \
+        if ((p) - (u) > (tol)) (bad)++;                                                       \
+        if (isnan(p) || isnan(d)) (bad)++;                                                    \
+    } while (0)
+#define QPN_ROW_RESIDUAL(e, p, d, l, u)                                                       \
+    do {                                                                                      \
+        double tt__ = (p) - (d);                                                              \
+        if (tt__ < (l)) tt__ = (l);                                                           \
+        if (tt__ > (u)) tt__ = (u);                                                           \
+        (e) = fabs((p) - tt__);                                                               \
+        if (isnan(e)) (e) = QINF;                                                             \
+    } while (0)
+#define QPN_ROW_MASK(mask, p, d, l, u, ct)                                                    \
+    do {                                                                                      \
+        (mask) = 0;                                                                           \
+        if (!qpn_approx(l, u, ct)) {                                               /* :512 */ \
+            if (qpn_approx(p, l, ct) && (d) >= -(ct)) (mask) |= 1u;                /* :543 */ \
+            if ((l) - (ct) <= (p) && (p) <= (u) + (ct) && fabs(d) <= (ct)) (mask) |= 2u;      \
+            if (qpn_approx(p, u, ct) && (d) <= (ct)) (mask) |= 4u;                 /* :549 */ \
+        } else (mask) = 8u;                                                    /* :552-558 */ \
+    } while (0)
+#define QPN_ROW_POSTCHECK(bad, e, mask, p, d, l, u, gavi, check_tol, comp_tol)                \
+    do {                                                                                      \
+        const double tol__ = (check_tol);                                                     \
+        QPN_ROW_VIOLATIONS(bad, p, d, l, u, tol__);                                           \
+        QPN_ROW_RESIDUAL(e, p, d, l, u);                                                      \
+        const double ct__ = (comp_tol);                                                       \
+        QPN_ROW_MASK(mask, p, d, l, u, ct__);                                                 \
+        if (gavi) (mask) <<= 4;                                                               \
+    } while (0)
+
+// Primal store: entry xo of the caller's iterate and of its replicas on the peer GPUs (AviBatchArgs::mirror).  `args` points at
+// the kernel's AviBatchArgs wherever the kernel reads the mirror table from: the kernarg segment, or its by-value argument.
+template <typename ArgsPtr> __device__ __forceinline__ void qpn_store_primal(ArgsPtr args, double *x, size_t xo, double v)
+{
+    x[xo] = v;
+    const int nmir = args->n_mirror;
+    for (int k = 0; k < nmir; ++k) args->mirror[k][xo] = v;
+}
+
+// Smoothed pivot count of a node (AviBatchArgs::sched_key, units of 1/32 pivot): key <- key - key / 32 + pivots, a first
+// sweep starts it at 32 * pivots.
+__host__ __device__ __forceinline__ int qpn_smooth_pivots(int key, int pivots) { return key > 0 ? key - (key >> 5) + pivots : 32 * pivots; }
+__device__ __forceinline__ void qpn_update_sched_key(int32_t *sched_key, int b, int pivots)
+{
+    if (sched_key) sched_key[b] = qpn_smooth_pivots(sched_key[b], pivots);
+}
+
+// THE decline rules; the host protocol of qpn_capi_nodes.hip rests on every kernel doing exactly this, in ONE thread of the
+// wavefront or workgroup that owns node b.
+// Cold: a fused kernel hands node b to the general kernels -- status -1, counted for the owner of the records (decl_count may be null).
+__device__ __forceinline__ void qpn_decline_cold(int32_t *status, int b, int32_t *decl_count)
+{
+    status[b] = -1;
+    if (decl_count) atomicAdd(decl_count, 1);
+}
+// Warm: a warm kernel writes nothing but b, appended to the decliners' list.  The list starts at -1 in every word, its counter
+// (the word behind it) included: slot = old count + 1.
+__device__ __forceinline__ void qpn_decline_warm(int32_t *dec_list, int32_t *dec_count, int b)
+{
+    dec_list[atomicAdd(dec_count, 1) + 1] = b;
+}
+
 // sixteen-way scalar dispatch on a wave-uniform index %[cs] (0..15; anything else: nothing) inside an asm statement: leaf k
 // names register k statically
 #define DISPATCH16(P, L0, L1, L2, L3, L4, L5, L6, L7, L8, L9, L10, L11, L12, L13, L14, L15)                                        \

@@ -33,11 +33,7 @@ __global__ __launch_bounds__(256) void check_avi_kernel(int32_t batch, int32_t N
         const double zi = z[vo + i];
         const double p = g ? r : zi, d = g ? zi : r;
         const double li = l[vo + i], ui = u[vo + i];
-        if (d > tol && fabs(p - li) > tol) bad++;   // :152
-        if (d < -tol && fabs(p - ui) > tol) bad++;  // :153
-        if (p - li < -tol) bad++;                   // :154
-        if (p - ui > tol) bad++;
-        if (isnan(p) || isnan(d)) bad++;
+        QPN_ROW_VIOLATIONS(bad, p, d, li, ui, tol);
     }
     bad = wave_sum_i32(bad);
     if (lane == 0) degree[b] = bad;
@@ -53,15 +49,8 @@ __global__ __launch_bounds__(256) void comp_indices_kernel(int64_t count, const 
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (; i < count; i += stride) {
         const double z = zv[i], r = rv[i], li = l[i], ui = u[i];
-        auto approx = [&](double x, double y) {
-            return x == y || (isfinite(x) && isfinite(y) && fabs(x - y) <= tol);
-        };
-        unsigned m = 0;
-        if (!approx(li, ui)) {                                                   // :512
-            if (approx(z, li) && r >= -tol) m |= 1u;                             // :543
-            if (li - tol <= z && z <= ui + tol && fabs(r) <= tol) m |= 2u;       // :546
-            if (approx(z, ui) && r <= tol) m |= 4u;                              // :549
-        } else m = 8u;                                                           // :552-558
+        unsigned m;
+        QPN_ROW_MASK(m, z, r, li, ui, tol);
         mask[i] = (uint8_t)(m << shift);
     }
 }
@@ -354,7 +343,7 @@ __global__ __launch_bounds__(1024) void order_by_pivots_kernel(const int32_t *pi
         if (pivots) { p = pivots[i]; p = p < 0 ? 0 : (p > 1023 ? 1023 : p); }
         if (key) {
             const int k0 = key[i];
-            const int k1 = !pivots ? k0 : (k0 > 0 ? k0 - (k0 >> 5) + p : 32 * p);
+            const int k1 = !pivots ? k0 : qpn_smooth_pivots(k0, p);
             p = k1 >> 3;                                    // quarter pivots (the key counts 1/32 pivots)
             p = p < 0 ? 0 : (p > 1023 ? 1023 : p);
         }
@@ -379,8 +368,7 @@ __global__ __launch_bounds__(1024) void order_by_pivots_kernel(const int32_t *pi
         if (key && pivots) {
             int p = pivots[i];
             p = p < 0 ? 0 : (p > 1023 ? 1023 : p);
-            const int k0 = key[i];
-            key[i] = k0 > 0 ? k0 - (k0 >> 5) + p : 32 * p;
+            key[i] = qpn_smooth_pivots(key[i], p);
         }
     }
 }

@@ -10,8 +10,8 @@
 //      column, leaves W = Qd^-1 A_act' and h = -Qd^-1 (qd + R w) in place;
 //   2. S = A_act W (k x k) and c = bound_act - B_act w - A_act h go where Qd's factors were (they are dead) and are solved by
 //      the same elimination: S lam_act = c;   x = h + W lam_act.
-// The point then takes the post-check, the residual and the active-set classification of the cold node kernels
-// (qpn_avi_schur.hip: check_tol, comp_tol) on the ORIGINAL blocks.  A node is ACCEPTED only if every hinted row has a finite
+// The point then takes the post-check, the residual and the active-set classification every solver kernel applies
+// (QPN_ROW_POSTCHECK, qpn_internal.h: check_tol, comp_tol) on the ORIGINAL blocks.  A node is ACCEPTED only if every hinted row has a finite
 // bound on its side, k <= n, no pivot of the two eliminations is below piv_tol, every lam_act carries its side's sign and the
 // post-check passes; it then writes z, status = QPN_SUCCESS, resid, pivots = 0, active and the x scatter.  Every other node
 // (a NaN or an infinity among the hinted multipliers included) DECLINES: it writes none of its outputs and appends its index
@@ -42,8 +42,7 @@ __global__ __launch_bounds__(WAVE) void warm_nodes(AviBatchArgs a, int32_t *dec_
     __shared__ double sv[64];           // right-hand side / solution of the Schur system; then z in item order
     __shared__ int srow[32];            // the hinted rows, ascending
 
-    // the list starts at -1 in every word, its counter (the word behind it) included: slot = old count + 1
-    auto decline = [&]() { if (l == 0) dec_list[atomicAdd(dec_count, 1) + 1] = b; };
+    auto decline = [&]() { if (l == 0) qpn_decline_warm(dec_list, dec_count, b); };
 
     const size_t vo = (size_t)b * (size_t)N;
     const double *Q_ = a.nd.Qd + (size_t)b * n * n;
@@ -168,7 +167,7 @@ __global__ __launch_bounds__(WAVE) void warm_nodes(AviBatchArgs a, int32_t *dec_
     if (act) sv[l] = zk;
     wave_sync();
 
-    // ---- post-check against the ORIGINAL blocks, as the cold node kernels (src/avi.jl:71-76 / :148-156) ---------------
+    // ---- post-check against the ORIGINAL blocks: QPN_ROW_POSTCHECK (src/avi.jl:71-76 / :148-156) ------------------------
     double rk = 0.0;
     if (act) {
         rk = sq[l];
@@ -184,39 +183,14 @@ __global__ __launch_bounds__(WAVE) void warm_nodes(AviBatchArgs a, int32_t *dec_
     int bad = 0;
     double nres = 0.0;
     unsigned mask = 0;
-    if (act) {
-        const double tol = a.check_tol;
-        if (dv > tol && fabs(pp - lk) > tol) bad++;
-        if (dv < -tol && fabs(pp - uk) > tol) bad++;
-        if (pp - lk < -tol) bad++;
-        if (pp - uk > tol) bad++;
-        if (isnan(pp) || isnan(dv)) bad++;
-        double tt = pp - dv;
-        if (tt < lk) tt = lk;
-        if (tt > uk) tt = uk;
-        nres = fabs(pp - tt);
-        if (isnan(nres)) nres = QINF;
-        const double ct = a.comp_tol;
-        auto approx = [&](double x, double y) { return (x == y) | (fabs(x - y) <= ct); };
-        if (!approx(lk, uk)) {
-            if (approx(pp, lk) && dv >= -ct) mask |= 1u;
-            if (lk - ct <= pp && pp <= uk + ct && fabs(dv) <= ct) mask |= 2u;
-            if (approx(pp, uk) && dv <= ct) mask |= 4u;
-        } else mask = 8u;
-        if (gk) mask <<= 4;
-    }
+    if (act) QPN_ROW_POSTCHECK(bad, nres, mask, pp, dv, lk, uk, gk, a.check_tol, a.comp_tol);
     if (qpn_ballot(bad != 0) != 0ull) { decline(); return; }
     nres = wave_max_f64_nc(nres);
 
     // ---- accepted ----------------------------------------------------------------------------------------------------
     if (act) {
         a.z[vo + l] = zk;
-        if (a.x && isx) {                                                       // primal block -> the caller's iterate
-            const size_t xo = (size_t)b * (size_t)a.stride_x + l;
-            a.x[xo] = zk;
-            const int nmir = kp->n_mirror;                                      // ... and its replicas on the peer GPUs
-            for (int t = 0; t < nmir; ++t) kp->mirror[t][xo] = zk;
-        }
+        if (a.x && isx) qpn_store_primal(kp, a.x, (size_t)b * (size_t)a.stride_x + l, zk);     // primal block -> the caller's iterate and its replicas
         if (a.active) a.active[vo + l] = (uint8_t)mask;
     }
     if (l == 0) {

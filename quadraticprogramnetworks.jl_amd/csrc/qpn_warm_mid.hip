@@ -5,7 +5,7 @@
 // their sides, and the LINEAR KKT system of those rows,
 //     [[Qd, -A_act'], [A_act, 0]] [x; lam_act] = [-(qd + R w); bound_act - B_act w],      every other multiplier 0,
 // is solved in fp64 by block elimination: W | h = Qd^-1 [A_act' | -(qd + R w)], S = A_act W, c = bound_act - B_act w - A_act h,
-// S lam_act = c, x = h + W lam_act.  The point takes the post-check, the residual and the masks of the cold kernels on the ORIGINAL
+// S lam_act = c, x = h + W lam_act.  The point takes the post-check, the residual and the masks of QPN_ROW_POSTCHECK (qpn_internal.h) on the ORIGINAL
 // blocks.  ACCEPTED: every hinted multiplier finite with a finite bound on its side, k <= n, warm_mid_fits(n, k), no pivot below
 // piv_tol, every lam_act of its side's sign, post-check passed -- the node writes z, status = QPN_SUCCESS, resid, pivots = 0,
 // active and the x scatter.  Every other node writes nothing but its index, appended to the decliners' list.
@@ -107,8 +107,7 @@ __global__ __launch_bounds__(WM_THREADS) void warm_mid_nodes(AviBatchArgs a, int
     int *colof = ints + iCOLOF, *srow = ints + iSROW, *srank = ints + iSRANK, *sside = ints + iSIDE, *flag = ints + iFLAG;
     unsigned long long *smask = reinterpret_cast<unsigned long long *>(ints + iMASK);
 
-    // the list starts at -1 in every word, its counter (the word behind it) included: slot = old count + 1
-    auto decline = [&]() { if (t == 0) dec_list[atomicAdd(dec_count, 1) + 1] = b; };
+    auto decline = [&]() { if (t == 0) qpn_decline_warm(dec_list, dec_count, b); };
 
     const size_t vo = (size_t)b * (size_t)N;
     const double *Q_ = a.nd.Qd + (size_t)b * n * n;
@@ -256,7 +255,7 @@ __global__ __launch_bounds__(WM_THREADS) void warm_mid_nodes(AviBatchArgs a, int
     __syncthreads();
     if (flag[1] != 0) { decline(); return; }
 
-    // ---- post-check against the ORIGINAL blocks, as the cold node kernels ------------------------------------------------
+    // ---- post-check against the ORIGINAL blocks: QPN_ROW_POSTCHECK ------------------------------------------------------
     double rk_ = 0.0, lk = -QINF, uk = QINF;
     if (act) {
         rk_ = sq[t];
@@ -273,27 +272,7 @@ __global__ __launch_bounds__(WM_THREADS) void warm_mid_nodes(AviBatchArgs a, int
     int bad = 0;
     double nres = 0.0;
     unsigned mask = 0;
-    if (act) {
-        const double tol = a.check_tol;
-        if (dv > tol && fabs(pp - lk) > tol) bad++;
-        if (dv < -tol && fabs(pp - uk) > tol) bad++;
-        if (pp - lk < -tol) bad++;
-        if (pp - uk > tol) bad++;
-        if (isnan(pp) || isnan(dv)) bad++;
-        double tt = pp - dv;
-        if (tt < lk) tt = lk;
-        if (tt > uk) tt = uk;
-        nres = fabs(pp - tt);
-        if (isnan(nres)) nres = QINF;
-        const double ct = a.comp_tol;
-        auto approx = [&](double x, double y) { return (x == y) | (fabs(x - y) <= ct); };
-        if (!approx(lk, uk)) {
-            if (approx(pp, lk) && dv >= -ct) mask |= 1u;
-            if (lk - ct <= pp && pp <= uk + ct && fabs(dv) <= ct) mask |= 2u;
-            if (approx(pp, uk) && dv <= ct) mask |= 4u;
-        } else mask = 8u;
-        if (gk) mask <<= 4;
-    }
+    if (act) QPN_ROW_POSTCHECK(bad, nres, mask, pp, dv, lk, uk, gk, a.check_tol, a.comp_tol);
     if (bad != 0) flag[2] = 1;
     nres = wave_max_f64_nc(nres);
     if (lane == 0) pc[wave] = nres;                                        // (the pivot columns are dead)
@@ -303,12 +282,7 @@ __global__ __launch_bounds__(WM_THREADS) void warm_mid_nodes(AviBatchArgs a, int
     // ---- accepted --------------------------------------------------------------------------------------------------------
     if (act) {
         a.z[vo + t] = zk;
-        if (a.x && isx) {                                                       // primal block -> the caller's iterate
-            const size_t xo = (size_t)b * (size_t)a.stride_x + t;
-            a.x[xo] = zk;
-            const int nmir = kp->n_mirror;                                      // ... and its replicas on the peer GPUs
-            for (int e = 0; e < nmir; ++e) kp->mirror[e][xo] = zk;
-        }
+        if (a.x && isx) qpn_store_primal(kp, a.x, (size_t)b * (size_t)a.stride_x + t, zk);     // primal block -> the caller's iterate and its replicas
         if (a.active) a.active[vo + t] = (uint8_t)mask;
     }
     if (t == 0) {

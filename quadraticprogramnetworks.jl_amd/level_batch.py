@@ -634,7 +634,10 @@ def _eliminate(M, rhs, piv_tol):
 def node_postcheck(z, r, l, u, n, check_tol=WARM_CHECK_TOL, comp_tol=WARM_COMP_TOL):
     """The post-check of a node solve on z = [x; lam] and r = M z + q (check_avi_solution, src/avi.jl:148-156, on the rows
     [free STD x n | GAVI x m] with the bounds l, u of the m constraint rows), the natural-map residual and the active-set masks of
-    src/avi_solutions.jl:511-562 (x rows: bit c - 1 for code c, constraint rows: bit c + 3) -> (bad, resid, active)."""
+    src/avi_solutions.jl:511-562 (x rows: bit c - 1 for code c, constraint rows: bit c + 3) -> (bad, resid, active).
+    The numpy twin of QPN_ROW_POSTCHECK (csrc/qpn_internal.h: QPN_ROW_VIOLATIONS, QPN_ROW_RESIDUAL, QPN_ROW_MASK with qpn_approx),
+    the one row post-check of every solver kernel, row for row; bad is "any violation", resid the maximum over the rows.
+    tests/test_postcheck_host.py holds the two together."""
     z = np.asarray(z, dtype=np.float64); r = np.asarray(r, dtype=np.float64)
     N = z.size
     lk = np.concatenate([np.full(n, -INF), l]); uk = np.concatenate([np.full(n, INF), u])
