@@ -264,6 +264,36 @@ int qpn_nodes_info(qpn_ctx *ctx, qpn_nodes *nodes, int32_t info[4]);
 int qpn_solve_nodes_h(qpn_ctx *ctx, qpn_nodes *nodes, const double *w, int64_t stride_w, double *z,
                       int32_t *status, double *resid, int32_t *pivots, uint8_t *active,
                       const qpn_avi_opts *opts, int mem, double *x, int64_t stride_x);
+/* A sweep over a chosen part of a handle's nodes.  The arguments are those of qpn_solve_nodes_h with every per-item array
+ * compact: slot s (0 <= s < count) belongs to node idx[s].  w is [count][p] with item stride stride_w (0 = one shared vector),
+ * z and active are [count][n + m], status, resid and pivots [count], x[s * stride_x + i] receives the primal block of node
+ * idx[s]; idx lives where mem says; z, resid, pivots, active and x may be NULL as in qpn_solve_nodes_h.
+ * Contract: let w_full[idx[s]] = w[s], the other rows arbitrary but finite (and z_full likewise when the call carries a hint).
+ * Slot s of every output -- z, status, resid, pivots, active, x -- then equals the output of node idx[s] in
+ * qpn_solve_nodes_h(nodes, w_full, ...) under the same options and context options, bit for bit; where that sweep is specified
+ * up to rounding (the seeded block principal pivoting of QPN_OPT_WARM_BIG), so is this call.  QPN_AVI_FLAG_WARM_DUALS (the
+ * warm kernel runs over the list, its decliners go cold in the same call), QPN_AVI_FLAG_COLD_START, max_pivots and nodes
+ * that the fused kernel hands to the general one are all covered.
+ * The list: count == 0 succeeds and touches nothing; count < 0 or count > batch is QPN_ERR_ARG.  Entries lie in [0, batch) and
+ * are pairwise distinct, in any order.  A host list is checked before anything is launched (QPN_ERR_ARG, no output written).
+ * A device list is checked on the device, and nothing waits for the answer on the host: a slot whose entry is out of range
+ * answers status = QPN_FAILURE and zeros elsewhere; of the slots that name one node, the first to claim it is solved and
+ * every other one answers the same way.  The other slots are unaffected.
+ * On the fused routes (n, m <= 128 under the default options) only the listed nodes are solved.  The call uses what the handle
+ * knows -- its count of declined nodes (state 2: no general launch, no workspace), a valid crash cache, mixed launches and the
+ * LLC streaming policy -- and changes none of it: it fills no crash cache, takes no census, feeds no pivot statistics, does
+ * not advance info[3] and installs or refreshes no schedule; the handle's order and a caller-installed context order are
+ * ignored and stay in place; qpn_nodes_info reads the same before and after.  The launch still covers `batch` positions,
+ * those without a node ending at once; the primal mirrors of qpn_set_primal_mirrors are not written.
+ * On the other routes (large records on the blocked crash, the general route) there is NO saving: the call runs one ordinary
+ * full sweep -- rows of w_full that no subset call has written are zero, later calls keep the last values -- and returns the
+ * listed rows; the handle's state moves exactly as that sweep moves it.
+ * The handle owns the full-size device buffers this takes (w, z, status, resid, pivots, active and 2 batch + 1 int32),
+ * allocated by the first subset call and freed with the handle; when they cannot be had the call fails with QPN_ERR_HIP and
+ * the handle stays usable. */
+int qpn_solve_nodes_subset_h(qpn_ctx *ctx, qpn_nodes *nodes, int32_t count, const int32_t *idx, const double *w,
+                             int64_t stride_w, double *z, int32_t *status, double *resid, int32_t *pivots,
+                             uint8_t *active, const qpn_avi_opts *opts, int mem, double *x, int64_t stride_x);
 int qpn_verify_nodes_h(qpn_ctx *ctx, qpn_nodes *nodes, const double *xd, const double *w, int64_t stride_w,
                        double tol, int32_t *solution, double *lambda, int32_t *path, int mem);
 

@@ -218,6 +218,40 @@ function solve_nodes!(nodes::Nodes, x::Union{Nothing,StridedMatrix{Float64}}, w:
     (z, status, resid, pivots, active)
 end
 
+# A sweep over the nodes `idx` names (1-based, distinct, any order; qpn_solve_nodes_subset_h): column s of every array belongs to
+# node idx[s] -- w is p×count (or a shared vector), warm and the returned z and active are (n+m)×count, x (n rows or more,
+# count columns) receives the primal blocks.  Column s equals what solve_nodes! returns for node idx[s] given the same w column
+# (and hint), bit for bit.  Handles with n, m <= 128 solve only the listed nodes and their state does not move; larger records
+# run a full sweep and return the listed columns.
+function solve_nodes_subset!(nodes::Nodes, idx::Vector{<:Integer}, x::Union{Nothing,StridedMatrix{Float64}}, w::VecOrMat{Float64};
+                             want_z::Bool = true, warm::Union{Nothing,Matrix{Float64}} = nothing)
+    N = nodes.n + nodes.m; count = length(idx)
+    count <= nodes.batch || error("solve_nodes_subset!: more entries than nodes")
+    ndims(w) == 1 || size(w, 2) == count || error("solve_nodes_subset!: w must be p×count")
+    warm === nothing || size(warm) == (N, count) || error("solve_nodes_subset!: warm must be (n+m)×count")
+    x === nothing || size(x, 2) == count || error("solve_nodes_subset!: x must have count columns")
+    idx0 = Int32.(idx .- 1)
+    want_z = want_z || warm !== nothing
+    z = warm !== nothing ? copy(warm) : (want_z ? zeros(N, count) : nothing)
+    o = default_opts()
+    oref = Ref(AviOpts(o.check_tol, o.piv_tol, o.feas_tol, o.comp_tol, o.max_pivots, o.flags | QPN_AVI_FLAG_WARM_DUALS))
+    status = zeros(Int32, count); resid = zeros(count); pivots = zeros(Int32, count)
+    active = want_z ? zeros(UInt8, N, count) : nothing
+    xp = x === nothing ? Ptr{Cdouble}(C_NULL) : pointer(x)
+    sx = x === nothing ? Int64(0) : Int64(stride(x, 2))
+    GC.@preserve x z active oref begin
+        optr = warm === nothing ? Ptr{Cvoid}(C_NULL) : Ptr{Cvoid}(Base.unsafe_convert(Ptr{AviOpts}, oref))
+        rc = ccall((:qpn_solve_nodes_subset_h, LIB), Cint,
+                   (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ptr{Int32}, Ptr{Cdouble}, Int64, Ptr{Cdouble}, Ptr{Int32}, Ptr{Cdouble}, Ptr{Int32},
+                    Ptr{UInt8}, Ptr{Cvoid}, Cint, Ptr{Cdouble}, Int64),
+                   ctx(), nodes.h, Int32(count), idx0, w, ndims(w) == 1 ? Int64(0) : Int64(nodes.p),
+                   want_z ? pointer(z) : Ptr{Cdouble}(C_NULL), status, resid, pivots, want_z ? pointer(active) : Ptr{UInt8}(C_NULL),
+                   optr, QPN_MEM_HOST, xp, sx)
+        rc == 0 || error("qpn_solve_nodes_subset_h failed ($rc)")
+    end
+    (z, status, resid, pivots, active)
+end
+
 """
     convexity_nodes(Qd, Ad, eq; tol=1e-6) -> (convex, min_eig, null_dim)
 

@@ -204,9 +204,20 @@ struct NodeWs {                 // workspace of the general kernels: assembled b
     double *M, *q, *l, *u; uint8_t *kind; double *big;
 };
 
+// The lists a sweep of the fused routes may run under (batch + 1 words each, device).  Either makes it a sweep over a part of
+// the nodes: no census of declines, no filling of a crash cache (sweep_partial, qpn_capi_nodes.hip).
+struct SweepList {
+    // qpn_solve_nodes_subset_h: the nodes to solve, the rest -1; takes the place of every installed order.  Such a sweep leaves
+    // the handle's schedule and its pivot statistics alone as well.
+    const int32_t *subset = nullptr;
+    // QPN_AVI_FLAG_WARM_DUALS: receives the nodes the warm kernel declines (the order of the cold launches)
+    int32_t *warm = nullptr;
+    bool partial() const { return subset || warm; }
+};
+
 int solve_nodes_launch(qpn_ctx *ctx, qpn_nodes *h, int32_t batch, int32_t n, int32_t m, int32_t p, const NodeDev &d,
                        int64_t stride_w, const qpn_avi_opts &o, double *x_dev, int64_t stride_x, const NodeWs &ws,
-                       NodeRoute route, int32_t *warm_list = nullptr);
+                       NodeRoute route, const SweepList &sl = SweepList{});
 
 int order_reserve(qpn_ctx *ctx, int32_t count);
 

@@ -99,6 +99,39 @@ struct CrashCache {
     int info(bool applies) const { return (state == 1 && applies ? 1 : 0) | (!applies || state < 0 ? 2 : 0); }
 };
 
+// Full-size staging of qpn_solve_nodes_subset_h, owned by the handle: the arrays the node kernels sweep, a node at its own
+// index, and the two index arrays of the list kernel.  ONE allocation, made by the first subset call and kept until the handle
+// goes.  w and z start as zeros (rows that no subset call has written stay finite) and keep what later calls leave in them.
+struct SubsetStage {
+    char *buf = nullptr;
+    double *w = nullptr, *z = nullptr, *resid = nullptr;
+    int32_t *status = nullptr, *pivots = nullptr;
+    int32_t *slot_of = nullptr, *list = nullptr;        // [batch] | [batch + 1], contiguous: one fill sets both
+    uint8_t *active = nullptr;
+
+    hipError_t reserve(int32_t batch, int32_t N, int32_t p, hipStream_t s)
+    {
+        if (buf) return hipSuccess;
+        const size_t b = (size_t)batch;
+        const size_t bytes[7] = {b * (size_t)(p > 0 ? p : 1) * 8, b * N * 8, b * 8, b * 4, b * 4, (2 * b + 1) * 4, b * N};
+        size_t off[7], total = 0;
+        for (int i = 0; i < 7; ++i) { off[i] = total; total += (bytes[i] + 255) & ~(size_t)255; }
+        hipError_t e = hipMalloc((void **)&buf, total);
+        if (e == hipSuccess) e = hipMemsetAsync(buf, 0, off[2], s);
+        if (e != hipSuccess) { free(); return e; }
+        w = (double *)(buf + off[0]); z = (double *)(buf + off[1]); resid = (double *)(buf + off[2]);
+        status = (int32_t *)(buf + off[3]); pivots = (int32_t *)(buf + off[4]);
+        slot_of = (int32_t *)(buf + off[5]); list = slot_of + b;
+        active = (uint8_t *)(buf + off[6]);
+        return hipSuccess;
+    }
+    void free()
+    {
+        if (buf) (void)hipFree(buf);
+        *this = SubsetStage{};
+    }
+};
+
 } // namespace
 
 // resident node records (qpn_nodes_upload): library-owned copies in HBM + what depends on them alone
@@ -134,6 +167,8 @@ struct qpn_nodes {
     HostCount big_entries;
     // qpn_nodes_set_warm: sweeps on the mid route that carry QPN_AVI_FLAG_WARM_DUALS run the warm kernel (qpn_warm_mid.hip) first
     bool warm_mid = false;
+    // qpn_solve_nodes_subset_h: its full-size staging buffers
+    SubsetStage subset;
 };
 
 NodeRoute node_route(const qpn_ctx *ctx, int32_t n, int32_t m, const qpn_avi_opts &o)
@@ -351,10 +386,39 @@ int solve_general(qpn_ctx *ctx, const AviBatchArgs &a, const NodeWs &ws, bool ga
     return QPN_OK;
 }
 
+// ---- a sweep under a list (SweepList): what the fused routes share -------------------------------------------------------
+// The launch arguments under the lists of this sweep.  A subset list takes the place of whatever order `a` carries.
+// QPN_AVI_FLAG_WARM_DUALS: the warm kernel goes first, over the nodes of that order.  What it accepts is done; the indices of
+// the others come back compacted in sl.warm, padded with -1, and that list is the order of the cold launches -- out-of-range
+// entries leave a slot unsolved, so nothing waits for the count on the host.
+int sweep_lists(qpn_ctx *ctx, AviBatchArgs &a, const SweepList &sl,
+                hipError_t (*launch_warm)(const AviBatchArgs &, int32_t *, hipStream_t))
+{
+    if (sl.subset) a.order = sl.subset;
+    if (sl.warm) {
+        HIPCHK(ctx, hipMemsetAsync(sl.warm, 0xFF, ((size_t)a.batch + 1) * 4, ctx->stream));
+        HIPCHK(ctx, launch_warm(a, sl.warm, ctx->stream));
+        a.order = sl.warm;
+    }
+    return QPN_OK;
+}
+
+// Decline protocol of a sweep that may run under a list.  A sweep over a part of the nodes is no census of the fused kernel's
+// declines: the handle uses what it knows and learns nothing from this one.
+int sweep_declines_begin(qpn_ctx *ctx, qpn_nodes *h, AviBatchArgs &a, const SweepList &sl, bool *need_general)
+{
+    if (!sl.partial()) return declines_begin(ctx, h, a, need_general);
+    nodes_poll_declines(h);
+    *need_general = !(h && h->declines.state == 2);
+    return QPN_OK;
+}
+
+int sweep_declines_end(qpn_ctx *ctx, qpn_nodes *h, const SweepList &sl) { return sl.partial() ? QPN_OK : declines_end(ctx, h); }
+
 // ---- the four routes of a sweep (solve_nodes_launch).  *x_in_kernel: the kernels wrote the primal blocks to `out` themselves ----
 
 // n, m <= 32: the fused kernel, and the general kernel behind it, write the primal blocks themselves
-int sweep_fused32(qpn_ctx *ctx, qpn_nodes *h, AviBatchArgs &a, const NodeWs &ws, const PrimalOut &out, int32_t *warm_list,
+int sweep_fused32(qpn_ctx *ctx, qpn_nodes *h, AviBatchArgs &a, const NodeWs &ws, const PrimalOut &out, const SweepList &sl,
                   bool *x_in_kernel)
 {
     hipStream_t s = ctx->stream;
@@ -366,20 +430,15 @@ int sweep_fused32(qpn_ctx *ctx, qpn_nodes *h, AviBatchArgs &a, const NodeWs &ws,
     // the smoothed counts are fed by every sweep while the schedule settles (128 sweeps), by every fourth one afterwards:
     // a sample of the sweeps tells the order as well, and the solve kernel's read-modify-write of its node's key is
     // 0.5 % of the sweep
-    if (schedules(h, batch, 4096) && (h->calls < 128 || (h->calls & 3) == 0)) a.sched_key = h->key;
+    // (a subset call leaves the schedule and its statistics alone)
+    const bool sched = schedules(h, batch, 4096) && !sl.subset;
+    if (sched && (h->calls < 128 || (h->calls & 3) == 0)) a.sched_key = h->key;
     if (h && h->order_valid) a.order = h->order;
     else if (ctx->order_count == batch && (!h || ctx->order_user)) a.order = ctx->order;     // a caller-installed order also serves handles
-    // QPN_AVI_FLAG_WARM_DUALS: the warm kernel goes first, over the nodes of that order.  What it accepts is done; the
-    // indices of the others come back compacted in warm_list, padded with -1, and that list is the order of the cold
-    // launches below -- out-of-range entries leave a slot unsolved, so nothing waits for the count on the host.  The list is
-    // not the handle's own order, so such a sweep does not FILL the crash cache (it reuses a valid one -- the same bits either
-    // way), a mixed launch deals its two Stage A bodies by launch position as ever, and only the decliners feed the smoothed
-    // pivot counts of the schedule.
-    if (warm_list) {
-        HIPCHK(ctx, hipMemsetAsync(warm_list, 0xFF, ((size_t)batch + 1) * 4, s));
-        HIPCHK(ctx, qpn_launch_warm_nodes(a, warm_list, s));
-        a.order = warm_list;
-    }
+    // The lists of this sweep (sweep_lists).  A list is not the handle's own order, so such a sweep does not FILL the crash
+    // cache (it reuses a valid one -- the same bits either way), a mixed launch deals its two Stage A bodies by launch position
+    // as ever, and of a warm sweep only the decliners feed the smoothed pivot counts of the schedule.
+    if ((rc = sweep_lists(ctx, a, sl, qpn_launch_warm_nodes)) != QPN_OK) return rc;
     // resident symmetric n = m = 32 records: the first whole-batch sweep keeps the parameter-free part of the crash, the
     // later ones reuse it (same stream: no host synchronisation).  The handle's own order: none, or h->order -- asked after
     // the warm list has taken the order's place
@@ -393,21 +452,16 @@ int sweep_fused32(qpn_ctx *ctx, qpn_nodes *h, AviBatchArgs &a, const NodeWs &ws,
     }
     // ... and it streams the crash cache past the last-level cache when that lets the node records stay there until the next sweep
     if (crash == 2 && llc_streams_crash(batch, a.nd.n, a.nd.m, a.nd.p, ctx->llc_budget_mb)) a.crash_stream = 1;
-    if (h) h->crash_streamed = a.crash_stream != 0;
+    if (h && !sl.subset) h->crash_streamed = a.crash_stream != 0;
     bool need_general;
-    if (warm_list) {
-        // a sweep over a part of the nodes is no census of the fused kernel's declines: the handle uses what it knows and
-        // learns nothing from this one
-        nodes_poll_declines(h);
-        need_general = !(h && h->declines.state == 2);
-    } else if ((rc = declines_begin(ctx, h, a, &need_general)) != QPN_OK) return rc;
+    if ((rc = sweep_declines_begin(ctx, h, a, sl, &need_general)) != QPN_OK) return rc;
     HIPCHK(ctx, qpn_launch_avi_solve_schur_nodes(a, s));
     if (crash == 1) h->crash.filled(s);
     if (need_general && (rc = solve_general(ctx, a, ws, true, true)) != QPN_OK) return rc;
-    if (!warm_list && (rc = declines_end(ctx, h)) != QPN_OK) return rc;
+    if ((rc = sweep_declines_end(ctx, h, sl)) != QPN_OK) return rc;
     if (h) {
-        if (schedules(h, batch, 4096) && (rc = schedule_refresh(ctx, h, batch)) != QPN_OK) return rc;
-    } else if (warm_list) {
+        if (sched && (rc = schedule_refresh(ctx, h, batch)) != QPN_OK) return rc;
+    } else if (sl.warm) {
         // (the pivot counts of this call are not those of a cold sweep: no schedule is made from them)
     } else if (ctx->auto_period > 0 && !ctx->order_user && a.pivots && batch > 4096) {
         // automatic longest-first schedule for the NEXT calls over this batch (launches that fill the GPU only)
@@ -424,20 +478,15 @@ int sweep_fused32(qpn_ctx *ctx, qpn_nodes *h, AviBatchArgs &a, const NodeWs &ws,
 
 // mid-size nodes (n, m <= 128): one wavefront (max(n, m) <= 48) or one workgroup per node straight from the records, ONE
 // launch; what they decline (status = -1) is assembled and solved by the general kernels in gated launches
-// warm_list (a handle that opted in, qpn_nodes_set_warm; solve_nodes_any decides): the warm kernel goes first, as in the 32-class
-int sweep_mid(qpn_ctx *ctx, qpn_nodes *h, AviBatchArgs &a, const NodeWs &ws, const PrimalOut &out, int32_t *warm_list,
+// sl.warm (a handle that opted in, qpn_nodes_set_warm; the caller decides): the warm kernel goes first, as in the 32-class
+int sweep_mid(qpn_ctx *ctx, qpn_nodes *h, AviBatchArgs &a, const NodeWs &ws, const PrimalOut &out, const SweepList &sl,
               bool *x_in_kernel)
 {
     hipStream_t s = ctx->stream;
     const int32_t batch = a.batch, n = a.nd.n, m = a.nd.m;
     int rc = QPN_OK;
     bool need_general;
-    if (warm_list) {
-        // a sweep over a part of the nodes is no census of the fused kernel's declines: the handle uses what it knows and
-        // learns nothing from this one
-        nodes_poll_declines(h);
-        need_general = !(h && h->declines.state == 2);
-    } else if ((rc = declines_begin(ctx, h, a, &need_general)) != QPN_OK) return rc;
+    if ((rc = sweep_declines_begin(ctx, h, a, sl, &need_general)) != QPN_OK) return rc;
     AviBatchArgs f = a;
     // the kernel writes the primal blocks into the iterate itself once it is known that nothing declines (the general
     // kernels behind it do not); until then the strided copy of solve_nodes_launch does
@@ -448,23 +497,18 @@ int sweep_mid(qpn_ctx *ctx, qpn_nodes *h, AviBatchArgs &a, const NodeWs &ws, con
     // the handle's longest-first schedule as in the 32-class (launches beyond the resident set only: 2 048 wavefronts of the
     // one-wavefront kernel, 1 024 workgroups of the 49-64 class, 256 of the 65-128 class)
     const bool one_wave = qpn_schur48_shape(n, m), two_role = qpn_schur_wg2_shape(n, m);
-    const bool sched = schedules(h, batch, one_wave ? 2048 : (two_role ? 256 : 1024));
+    // (a subset call leaves the schedule and its statistics alone)
+    const bool sched = schedules(h, batch, one_wave ? 2048 : (two_role ? 256 : 1024)) && !sl.subset;
     if (sched) { f.sched_key = h->key; if (h->order_valid) f.order = h->order; }
-    // QPN_AVI_FLAG_WARM_DUALS on a handle that opted in: the warm kernel goes first, over the nodes of that order, and writes the
-    // primal blocks under the same rule.  What it accepts is done; the indices of the others come back compacted in warm_list,
-    // padded with -1, and that list is the order of the cold launch -- out-of-range entries leave a slot unsolved, so nothing
-    // waits for the count on the host, and only the decliners feed the smoothed pivot counts of the schedule.
-    if (warm_list) {
-        HIPCHK(ctx, hipMemsetAsync(warm_list, 0xFF, ((size_t)batch + 1) * 4, s));
-        HIPCHK(ctx, qpn_launch_warm_mid_nodes(f, warm_list, s));
-        f.order = warm_list;
-    }
+    // The lists of this sweep (sweep_lists).  QPN_AVI_FLAG_WARM_DUALS on a handle that opted in: the warm kernel writes the
+    // primal blocks under the same rule, and only its decliners feed the smoothed pivot counts of the schedule.
+    if ((rc = sweep_lists(ctx, f, sl, qpn_launch_warm_mid_nodes)) != QPN_OK) return rc;
     if (two_role) HIPCHK(ctx, qpn_launch_schur_wg2_nodes(f, s));
     else if (one_wave) HIPCHK(ctx, qpn_launch_avi_solve_schur48_nodes(f, s));
     else HIPCHK(ctx, qpn_launch_schur_wg_nodes(f, s));
     if (sched && (rc = schedule_refresh(ctx, h, batch)) != QPN_OK) return rc;
     if (need_general && (rc = solve_general(ctx, a, ws, true, false)) != QPN_OK) return rc;
-    return warm_list ? QPN_OK : declines_end(ctx, h);
+    return sweep_declines_end(ctx, h, sl);
 }
 
 // large nodes (BASELINE config 5): the blocked crash straight from the records, the delayed-update Lemke kernel on the
@@ -519,7 +563,7 @@ int sweep_general(qpn_ctx *ctx, const AviBatchArgs &a, const NodeWs &ws) { retur
 // only when h knows that no node declines).
 int solve_nodes_launch(qpn_ctx *ctx, qpn_nodes *h, int32_t batch, int32_t n, int32_t m, int32_t p, const NodeDev &d,
                        int64_t stride_w, const qpn_avi_opts &o, double *x_dev, int64_t stride_x, const NodeWs &ws,
-                       NodeRoute route, int32_t *warm_list)
+                       NodeRoute route, const SweepList &sl)
 {
     hipStream_t s = ctx->stream;
     const int N = n + m;
@@ -544,8 +588,8 @@ int solve_nodes_launch(qpn_ctx *ctx, qpn_nodes *h, int32_t batch, int32_t n, int
     bool x_in_kernel = false;
     int rc = QPN_OK;
     switch (route) {
-    case NodeRoute::fused32: rc = sweep_fused32(ctx, h, a, ws, out, warm_list, &x_in_kernel); break;
-    case NodeRoute::mid: rc = sweep_mid(ctx, h, a, ws, out, warm_list, &x_in_kernel); break;
+    case NodeRoute::fused32: rc = sweep_fused32(ctx, h, a, ws, out, sl, &x_in_kernel); break;
+    case NodeRoute::mid: rc = sweep_mid(ctx, h, a, ws, out, sl, &x_in_kernel); break;
     case NodeRoute::big2: rc = sweep_big2(ctx, h, a, ws, warm_big); break;
     case NodeRoute::general: rc = sweep_general(ctx, a, ws); break;
     }
@@ -621,8 +665,94 @@ int solve_nodes_any(qpn_ctx *ctx, qpn_nodes *h, int32_t batch, int32_t n, int32_
     int rc = st.begin();
     if (rc != QPN_OK) return rc;
     rc = solve_nodes_launch(ctx, h, batch, n, m, p, d, stride_w, o, st.host ? hx : x, st.host ? (int64_t)n : stride_x, ws, route,
-                            warm_list);
+                            SweepList{nullptr, warm_list});
     if (rc != QPN_OK) return rc;
+    return st.finish();
+}
+
+// A host index list: every entry in 0 .. batch - 1, no entry twice
+bool subset_list_ok(const int32_t *idx, int32_t count, int32_t batch)
+{
+    std::vector<bool> seen((size_t)batch, false);
+    for (int32_t s = 0; s < count; ++s) {
+        if ((uint32_t)idx[s] >= (uint32_t)batch || seen[(size_t)idx[s]]) return false;
+        seen[(size_t)idx[s]] = true;
+    }
+    return true;
+}
+
+// One sweep over the listed nodes of a handle (qpn_solve_nodes_subset_h): the caller's compact arrays are staged like those of
+// any call, their rows go to the handle's full-size buffers and back (qpn_subset.hip), and the sweep in between is
+// solve_nodes_launch over those buffers -- under the list on the fused routes, whose kernels take one, and an ordinary full
+// sweep on the others.
+int solve_nodes_subset(qpn_ctx *ctx, qpn_nodes *h, int32_t count, const int32_t *idx, const double *w, int64_t stride_w,
+                       double *z, int32_t *status, double *resid, int32_t *pivots, uint8_t *active, const qpn_avi_opts *opts,
+                       int mem, double *x, int64_t stride_x)
+{
+    Stage st(ctx, mem, "qpn_solve_nodes_subset_h");
+    if (int rc = st.check()) return rc;
+    const int32_t batch = h->batch, n = h->n, m = h->m, p = h->p;
+    const int N = n + m;
+    // a host list is checked before anything is launched; a device list is the list kernel's to check
+    if (st.host && !subset_list_ok(idx, count, batch))
+        return fail_arg(ctx, "qpn_solve_nodes_subset_h: idx entries must lie in [0, batch) and be pairwise distinct");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    qpn_avi_opts o;
+    if (opts) o = *opts; else qpn_avi_default_opts(&o);
+    const size_t bN = (size_t)batch * N, cN = (size_t)count * N;
+    const NodeRoute route = node_route(ctx, n, m, o);
+    nodes_poll_declines(h);
+    nodes_sync_route(ctx, h);
+    // the fused routes' kernels take a launch list; the others run a full sweep
+    const bool fused = route == NodeRoute::fused32 || route == NodeRoute::mid;
+    const bool need_ws = !(fused && h->declines.state == 2);
+    SubsetStage &S = h->subset;
+    // (a failed allocation is this call's error: the handle stays as it was)
+    HIPCHK(ctx, S.reserve(batch, N, p, ctx->stream));
+
+    NodeWs ws{};
+    if (need_ws) {
+        st.scratch(ws.M, bN * N * 8); st.scratch(ws.q, bN * 8); st.scratch(ws.l, bN * 8); st.scratch(ws.u, bN * 8);
+        st.scratch(ws.kind, bN);
+        if (N > 64) st.scratch(ws.big, qpn_avi_big_workspace_bytes(batch, N));
+    }
+    const int32_t *didx;
+    const double *dw;
+    st.in(didx, idx, (size_t)count * 4);
+    st.in(dw, w, node_sizes(count, n, m, p, stride_w).w, 8);
+    // the compact z: the hint on its way in (no cold start), the solution on its way out
+    SubsetRows out{};
+    if (z) st.inout(out.z, z, cN * 8, !(o.flags & QPN_AVI_FLAG_COLD_START));
+    else o.flags |= QPN_AVI_FLAG_COLD_START;
+    const bool hinted = !(o.flags & QPN_AVI_FLAG_COLD_START);
+    st.out(out.status, status, (size_t)count * 4); st.out_opt(out.resid, resid, (size_t)count * 8);
+    st.out_opt(out.pivots, pivots, (size_t)count * 4); st.out_opt(out.active, active, cN);
+    // host mode: the primal blocks come down from a compact buffer of their own
+    double *dx = x;
+    if (st.host && x) {
+        st.scratch(dx, (size_t)count * n * 8);
+        st.out2d(dx, (size_t)n * 8, x, (size_t)stride_x * 8, (size_t)n * 8, (size_t)count);
+    }
+    const bool warm_route = route == NodeRoute::fused32 || (route == NodeRoute::mid && h->warm_mid);
+    int32_t *warm_list = nullptr;
+    if (warm_route && hinted && (o.flags & QPN_AVI_FLAG_WARM_DUALS)) st.scratch(warm_list, ((size_t)batch + 1) * 4);
+    int rc = st.begin();
+    if (rc != QPN_OK) return rc;
+    hipStream_t s = ctx->stream;
+    HIPCHK(ctx, hipMemsetAsync(S.slot_of, 0xFF, (2 * (size_t)batch + 1) * 4, s));
+    // the gated general launch (status = -1) must see this call's decliners only
+    HIPCHK(ctx, hipMemsetAsync(S.status, 0, (size_t)batch * 4, s));
+    HIPCHK(ctx, qpn_launch_subset_list(count, batch, didx, S.slot_of, S.list, s));
+    // a shared w (stride 0) is read where it is
+    const bool own_w = p > 0 && stride_w != 0;
+    HIPCHK(ctx, qpn_launch_subset_scatter(count, S.list, p, N, own_w ? dw : nullptr, stride_w, S.w, hinted ? out.z : nullptr, S.z, s));
+    const NodeDev d{h->f[0], h->f[1], h->f[2], h->f[3], h->f[4], h->f[5], h->f[6], own_w ? S.w : dw,
+                    S.z, S.status, S.resid, S.pivots, S.active};
+    rc = solve_nodes_launch(ctx, h, batch, n, m, p, d, own_w ? (int64_t)p : 0, o, nullptr, 0, ws, route,
+                            SweepList{fused ? S.list : nullptr, warm_list});
+    if (rc != QPN_OK) return rc;
+    const SubsetRows full{S.z, S.status, S.resid, S.pivots, S.active};
+    HIPCHK(ctx, qpn_launch_subset_gather(count, S.list, n, N, full, out, dx, st.host ? (int64_t)n : stride_x, s));
     return st.finish();
 }
 
@@ -710,6 +840,7 @@ int qpn_nodes_free(qpn_ctx *ctx, qpn_nodes *h)
     h->big_entries.destroy();
     h->crash.free();
     h->big.free();
+    h->subset.free();
     if (h->buf) (void)hipFree(h->buf);
     if (h->order) (void)hipFree(h->order);
     if (h->key) (void)hipFree(h->key);
@@ -817,6 +948,21 @@ int qpn_solve_nodes_h(qpn_ctx *ctx, qpn_nodes *h, const double *w, int64_t strid
     if (stride_w != 0 && stride_w < h->p) return fail_arg(ctx, "qpn_solve_nodes_h: stride_w < p");
     return solve_nodes_any(ctx, h, h->batch, h->n, h->m, h->p, h->f[0], h->f[1], h->f[2], h->f[3], h->f[4], h->f[5], h->f[6],
                            w, stride_w, z, status, resid, pivots, active, opts, mem, x, stride_x);
+}
+
+int qpn_solve_nodes_subset_h(qpn_ctx *ctx, qpn_nodes *h, int32_t count, const int32_t *idx, const double *w,
+                             int64_t stride_w, double *z, int32_t *status, double *resid, int32_t *pivots, uint8_t *active,
+                             const qpn_avi_opts *opts, int mem, double *x, int64_t stride_x)
+{
+    if (!ctx) return QPN_ERR_ARG;
+    if (!h) return fail_arg(ctx, "qpn_solve_nodes_subset_h: null handle");
+    if (h->device != ctx->device) return fail_arg(ctx, "qpn_solve_nodes_subset_h: handle belongs to another device");
+    if (count < 0 || count > h->batch) return fail_arg(ctx, "qpn_solve_nodes_subset_h: count outside [0, batch]");
+    if (count == 0) return QPN_OK;
+    if (x && stride_x < h->n) return fail_arg(ctx, "qpn_solve_nodes_subset_h: stride_x < n");
+    if (!idx || !status || (h->p > 0 && !w)) return fail_arg(ctx, "qpn_solve_nodes_subset_h: null pointer");
+    if (stride_w != 0 && stride_w < h->p) return fail_arg(ctx, "qpn_solve_nodes_subset_h: stride_w < p");
+    return solve_nodes_subset(ctx, h, count, idx, w, stride_w, z, status, resid, pivots, active, opts, mem, x, stride_x);
 }
 
 int qpn_verify_nodes(qpn_ctx *ctx, int32_t batch, int32_t n, int32_t m, int32_t p,

@@ -262,6 +262,22 @@ __host__ __device__ constexpr bool warm_mid_fits(int n, int k)
 }
 hipError_t qpn_launch_warm_mid_nodes(const AviBatchArgs &a, int32_t *dec_list, hipStream_t stream);
 
+// qpn_subset.hip: rows between the compact arrays of qpn_solve_nodes_subset_h (slot s = node idx[s], `count` slots) and the
+// full-size staging buffers of the handle.
+// list: slot_of (batch words) and list (batch + 1 words) arrive filled with -1.  A slot whose entry lies in 0 .. batch - 1 and
+// is the first to claim slot_of[entry] (one compare-and-swap) gets list[s] = entry; every other slot is bad and keeps -1.  The
+// list is then the order array of the node kernels (its -1 entries leave their launch positions idle) and the row map below.
+hipError_t qpn_launch_subset_list(int32_t count, int32_t batch, const int32_t *idx, int32_t *slot_of, int32_t *list,
+                                  hipStream_t stream);
+// scatter: w row s ([p], item stride stride_w) -> w_full[list[s]], z row s ([N]) -> z_full[list[s]]; a null w or z moves nothing
+hipError_t qpn_launch_subset_scatter(int32_t count, const int32_t *list, int32_t p, int32_t N, const double *w, int64_t stride_w,
+                                     double *w_full, const double *z, double *z_full, hipStream_t stream);
+// gather: the outputs of node list[s] -> slot s, x[s * stride_x + i] = z_full[list[s]][i] (i < n); null outputs (all but status)
+// are skipped; a bad slot reads status = QPN_FAILURE and zeros
+struct SubsetRows { double *z; int32_t *status; double *resid; int32_t *pivots; uint8_t *active; };
+hipError_t qpn_launch_subset_gather(int32_t count, const int32_t *list, int32_t n, int32_t N, const SubsetRows &full,
+                                    const SubsetRows &out, double *x, int64_t stride_x, hipStream_t stream);
+
 // qpn_avi_reg.hip
 hipError_t qpn_launch_avi_solve(const AviBatchArgs &a, hipStream_t stream);      // dispatcher: Schur kernel, then the register kernel
 hipError_t qpn_launch_avi_solve_reg(const AviBatchArgs &a, hipStream_t stream);  // register-tableau kernel

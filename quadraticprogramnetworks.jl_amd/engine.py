@@ -1004,6 +1004,40 @@ class Nodes:
         shape the call changes nothing.  on: True / False (or 1 / 0)."""
         self.eng._call("qpn_nodes_set_warm", self.h, int(on))
 
+    def _outputs(self, rows, dev, want, out, warm):
+        """The output buffers of a sweep over `rows` items: a caller-supplied set checked, or the ones `want` names made (status
+        always); a hint goes in through z."""
+        eng, N = self.eng, self.n + self.m
+        spec = dict(status=((rows,), np.int32), z=((rows, N), np.float64), resid=((rows,), np.float64),
+                    pivots=((rows,), np.int32), active=((rows, N), np.uint8))
+        if out is not None:
+            # a caller-supplied set of output buffers is checked once, when it is first seen
+            for k, (shape, dt) in spec.items():
+                t = out.get(k)
+                if t is None:
+                    if k == "status":
+                        raise QpnError("out['status'] is required")
+                    continue
+                if _is_dev(t) != dev:
+                    raise QpnError(f"out['{k}'] and w must both be host arrays or both device tensors")
+                ok = tuple(t.shape) == shape and (t.is_contiguous() and t.dtype == _torch_dt(dt) and t.device.index == eng.device
+                                                  if dev else t.flags["C_CONTIGUOUS"] and t.dtype == dt)
+                if not ok:
+                    raise QpnError(f"out['{k}'] must be a contiguous {np.dtype(dt).name} buffer of shape {shape} on the engine's device")
+            for k in ("z", "resid", "pivots", "active"):
+                out.setdefault(k, None)
+        else:
+            out = {k: eng._alloc(dev, shape, dt) if k == "status" or k in want else None for k, (shape, dt) in spec.items()}
+        if warm is not None:
+            if out["z"] is None:
+                out["z"] = eng._alloc(dev, (rows, N), np.float64)
+            if warm is not out["z"]:                             # the hint goes in through z
+                if dev:
+                    out["z"].copy_(warm)
+                else:
+                    out["z"][...] = warm
+        return out
+
     def solve(self, w, opts=None, want=("z", "resid", "pivots", "active"), out=None, x_out=None, warm=None):
         """One sweep over the resident nodes with parameters w ((p,) shared or (batch, p)); cold duals.  `want` names the
         optional outputs (status always comes back); x_out as in Engine.solve_nodes.
@@ -1059,38 +1093,7 @@ class Nodes:
             raise QpnError("AVI_FLAG_WARM_DUALS: out['z'] has to carry the hint (or pass warm=)")
         if not hinted:
             o.flags |= _lib.AVI_FLAG_COLD_START
-        if out is not None:
-            # a caller-supplied set of output buffers is checked once, when it is first seen
-            spec = dict(status=((self.batch,), np.int32), z=((self.batch, N), np.float64), resid=((self.batch,), np.float64),
-                        pivots=((self.batch,), np.int32), active=((self.batch, N), np.uint8))
-            for k, (shape, dt) in spec.items():
-                t = out.get(k)
-                if t is None:
-                    if k == "status":
-                        raise QpnError("out['status'] is required")
-                    continue
-                if _is_dev(t) != dev:
-                    raise QpnError(f"out['{k}'] and w must both be host arrays or both device tensors")
-                ok = tuple(t.shape) == shape and (t.is_contiguous() and t.dtype == _torch_dt(dt) and t.device.index == eng.device
-                                                  if dev else t.flags["C_CONTIGUOUS"] and t.dtype == dt)
-                if not ok:
-                    raise QpnError(f"out['{k}'] must be a contiguous {np.dtype(dt).name} buffer of shape {shape} on the engine's device")
-            for k in ("z", "resid", "pivots", "active"):
-                out.setdefault(k, None)
-        if out is None:
-            out = dict(status=eng._alloc(dev, (self.batch,), np.int32),
-                       z=eng._alloc(dev, (self.batch, N), np.float64) if "z" in want else None,
-                       resid=eng._alloc(dev, (self.batch,), np.float64) if "resid" in want else None,
-                       pivots=eng._alloc(dev, (self.batch,), np.int32) if "pivots" in want else None,
-                       active=eng._alloc(dev, (self.batch, N), np.uint8) if "active" in want else None)
-        if warm is not None:
-            if out["z"] is None:
-                out["z"] = eng._alloc(dev, (self.batch, N), np.float64)
-            if warm is not out["z"]:                             # the hint goes in through z
-                if dev:
-                    out["z"].copy_(warm)
-                else:
-                    out["z"][...] = warm
+        out = self._outputs(self.batch, dev, want, out, warm)
         sx = eng._x_stride(x_out, dev, self.batch, self.n)
         tail = (_ptr(out["z"]), _ptr(out["status"]), _ptr(out["resid"]), _ptr(out["pivots"]), _ptr(out["active"]), C.byref(o),
                 eng._mem(dev), _ptr(x_out), sx)
@@ -1101,6 +1104,48 @@ class Nodes:
             snap = tuple((k, out.get(k), None if out.get(k) is None else out[k].data_ptr())
                          for k in ("z", "status", "resid", "pivots", "active"))
             self._fast[warm is not None] = (out, x_out, tail, o, snap, None if x_out is None else x_out.data_ptr(), w.device)
+        return out
+
+    def solve_subset(self, idx, w, opts=None, want=("z", "resid", "pivots", "active"), out=None, x_out=None, warm=None):
+        """One sweep over the nodes idx names (qpn_solve_nodes_subset_h): the conventions of solve with count = len(idx) in the
+        place of batch and every array compact -- slot s of w ((p,) shared or (count, p)), of the outputs, of x_out and of the hint
+        warm ([count, n + m]) belongs to node idx[s].  idx: an int32 array or tensor living where w lives, its entries distinct and
+        in [0, batch), in any order.  Slot s of every output equals what solve returns for node idx[s] when that node gets the same
+        w row (and hint), bit for bit.  On the fused routes (n, m <= 128) only the listed nodes are solved and the handle's state --
+        info() -- does not move; larger records run a full sweep and return the listed rows (no saving there).  A device idx with
+        a bad entry is not an error: such a slot answers status = FAILURE and zeros."""
+        eng = self.eng
+        dev, idx = eng._stage("Nodes.solve_subset", "idx", raw=(w, x_out, warm), i32=(idx,))
+        if idx is None or idx.ndim != 1:
+            raise QpnError("idx must be a one-dimensional int32 array")
+        count = int(idx.shape[0])
+        if count > self.batch:
+            raise QpnError(f"idx names {count} nodes, the handle has {self.batch}")
+        if not dev:
+            w = np.ascontiguousarray(w, dtype=np.float64)
+        elif w.dtype != torch.float64 or (w.numel() and w.stride(-1) != 1):       # (an empty tensor's strides say nothing)
+            raise QpnError("w must be a float64 tensor with unit inner stride")
+        N = self.n + self.m
+        if w.shape[-1] != self.p or w.ndim > 2 or (w.ndim == 2 and w.shape[0] != count):
+            raise QpnError(f"w must have shape ({self.p},) or ({count}, {self.p})")
+        if dev and w.device.index != eng.device:
+            raise QpnError("w lives on another device than the engine")
+        sw = 0 if w.ndim == 1 else int(w.stride(0) if dev else w.strides[0] // 8)
+        o = AviOpts.from_buffer_copy(opts) if opts is not None else eng.default_opts()   # (the flags below are this call's)
+        if warm is not None:
+            o.flags = (o.flags | _lib.AVI_FLAG_WARM_DUALS) & ~_lib.AVI_FLAG_COLD_START
+            if tuple(warm.shape) != (count, N):
+                raise QpnError(f"warm must have shape ({count}, {N}) and live where w lives")
+            want = tuple(want) + ("z",)
+        hinted = bool(o.flags & _lib.AVI_FLAG_WARM_DUALS) and not (o.flags & _lib.AVI_FLAG_COLD_START)
+        if hinted and warm is None and (out is None or out.get("z") is None):
+            raise QpnError("AVI_FLAG_WARM_DUALS: out['z'] has to carry the hint (or pass warm=)")
+        if not hinted:
+            o.flags |= _lib.AVI_FLAG_COLD_START
+        out = self._outputs(count, dev, want, out, warm)
+        sx = eng._x_stride(x_out, dev, count, self.n) if count else 0         # (an empty array's strides say nothing)
+        eng._call("qpn_solve_nodes_subset_h", self.h, count, _ptr(idx), _ptr(w), sw, _ptr(out["z"]), _ptr(out["status"]),
+                  _ptr(out["resid"]), _ptr(out["pivots"]), _ptr(out["active"]), C.byref(o), eng._mem(dev), _ptr(x_out), sx)
         return out
 
     def verify(self, xd, w, tol=1e-4):

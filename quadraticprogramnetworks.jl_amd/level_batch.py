@@ -607,6 +607,11 @@ WARM_DUALS_ROUTE = False
 # with WARM_DUALS_ROUTE: the resident childless batches opt in once, when their handle is made.  False: everything as without it.
 WARM_DUALS_MID = False
 WARM_CHECK_TOL, WARM_PIV_TOL, WARM_COMP_TOL = 1e-6, 1e-11, 1e-2     # qpn_avi_default_opts
+# Sweeps over a part of a resident childless batch (Nodes.solve_subset).  False: solve_level solves every record of
+# the batch and keeps the rows of the players asked for (the code as it was).  True, with WARM_DUALS_ROUTE off and a handle that
+# has solve_subset: a sweep that leaves records of a batch out -- the players of settled components -- hands over only the
+# records asked for, their rows of w, and gets only their rows back.  x_opt is the same bit for bit.
+SUBSET_SWEEP_ROUTE = False
 
 
 def _eliminate(M, rhs, piv_tol):
@@ -931,21 +936,28 @@ def solve_level(qpn, players: Sequence[int], x, assign: Optional[Dict[int, Poly]
         xd, w = b.gather(x)
         z0 = np.zeros((len(b), b.n + b.m)); z0[:, :b.nx] = xd                       # duals cold, :404
         h = b.resident(eng, WARM_DUALS_ROUTE and WARM_DUALS_MID) if static else None
-        if h is not None and WARM_DUALS_ROUTE:
-            res = _warm_sweep(b, h, eng, w)
-        elif h is not None:
-            res = h.solve(w, want=("z", "resid", "pivots"))
-        elif isinstance(b, DeviceRecordBatch):
-            res = b.solve(eng, w, z0)
-        else:
-            res = eng.solve_nodes(b.Qc, b.Rc, b.qd, b.Ac, b.Bc, b.l, b.u, w, z0=z0)
-        st = np.asarray(res["status"])
-        z = np.asarray(res["z"])
         sel = take[id(b)] if (static and take is not None) else np.ones(len(b), bool)
-        if np.any(st[sel] != StatusCode.SUCCESS):
-            k = int(np.nonzero((st != StatusCode.SUCCESS) & sel)[0][0])
-            bad.append((int(b.dec[k][0]), int(st[k])))
-        x_opt[b.dec[sel].ravel()] = z[sel][:, :b.nx].ravel()                         # :440-443
+        rows = np.flatnonzero(sel)                       # the records whose players are written back
+        if SUBSET_SWEEP_ROUTE and not WARM_DUALS_ROUTE and h is not None and hasattr(h, "solve_subset") and not sel.all():
+            # only the records asked for go to the engine: slot s of the answer belongs to record rows[s]
+            res = h.solve_subset(rows.astype(np.int32), w[rows], want=("z", "resid", "pivots"))
+            st = np.asarray(res["status"])
+            z = np.asarray(res["z"])
+        else:
+            if h is not None and WARM_DUALS_ROUTE:
+                res = _warm_sweep(b, h, eng, w)
+            elif h is not None:
+                res = h.solve(w, want=("z", "resid", "pivots"))
+            elif isinstance(b, DeviceRecordBatch):
+                res = b.solve(eng, w, z0)
+            else:
+                res = eng.solve_nodes(b.Qc, b.Rc, b.qd, b.Ac, b.Bc, b.l, b.u, w, z0=z0)
+            st = np.asarray(res["status"])[rows]
+            z = np.asarray(res["z"])[rows]
+        if np.any(st != StatusCode.SUCCESS):
+            k = int(np.nonzero(st != StatusCode.SUCCESS)[0][0])
+            bad.append((int(b.dec[rows[k]][0]), int(st[k])))
+        x_opt[b.dec[rows].ravel()] = z[:, :b.nx].ravel()                             # :440-443
     # ---- multi-node components: pool AVIs, one assemble + one solve per pool shape
     if multis:
         blocks = [_pool_blocks_local(qpn, c, assign) for c in multis]
