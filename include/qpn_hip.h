@@ -529,7 +529,10 @@ int qpn_finish_pieces(qpn_ctx *ctx, int32_t pieces, int32_t records, int32_t n, 
  *   bound, - at the upper, :120-123), path [batch] int32: 0 infeasible (:86-89), 1 m==0
  *   shortcut (:91-96), 2 least-squares duals accepted (:114-124), 3 bounded-LSQ fallback
  *   accepted (:129-139), 4 fallback rejected (:141), 5 fallback solver failed (:144).
- *   tol = 1e-4 (:57).  n, m <= 64: one wavefront per node; up to 512: one workgroup per node. */
+ *   tol = 1e-4 (:57).  n, m <= 64: one wavefront per node; up to 512: one workgroup per node.
+ *   QPN_MEM_DEVICE with m == 0: Ad must still point at 8 readable bytes.  The n <= 32 kernel (verify_node32) loads the first
+ *   element of the node's Ad block with a clamped index whatever m is, so a null Ad is a load from address 0 there.  Host memory
+ *   and resident handles are safe: the library pads their empty arrays. */
 int qpn_verify_nodes(qpn_ctx *ctx, int32_t batch, int32_t n, int32_t m, int32_t p,
                      const double *Qd, const double *R, const double *qd, const double *Ad,
                      const double *B, const double *l, const double *u, const double *xd,

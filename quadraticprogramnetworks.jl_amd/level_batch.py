@@ -612,6 +612,11 @@ WARM_CHECK_TOL, WARM_PIV_TOL, WARM_COMP_TOL = 1e-6, 1e-11, 1e-2     # qpn_avi_de
 # has solve_subset: a sweep that leaves records of a batch out -- the players of settled components -- hands over only the
 # records asked for, their rows of w, and gets only their rows back.  x_opt is the same bit for bit.
 SUBSET_SWEEP_ROUTE = False
+# The accept gate over a part of a resident childless batch (Nodes.verify_subset).  False: process_level verifies
+# every node of an all-leaf level in every sweep (the code as it was).  True, with a handle that has verify_subset: the players
+# whose result the memo already holds are left out of the verify call -- none is made when every player is a hit, the full one
+# when none is.  process_level returns the same list, value for value.
+SUBSET_VERIFY_ROUTE = False
 
 
 def _eliminate(M, rhs, piv_tol):
@@ -1024,11 +1029,13 @@ _VERIFY_MSGS = {0: "Current point is infeasible when using tolerance {tol}.", 1:
                 4: "Current point is suboptimal (via QP).", 5: "Solving for duals failed."}
 
 
-def verify_items(qpn, items, x, engine, tol=1e-4, check_convexity=False):
+def verify_items(qpn, items, x, engine, tol=1e-4, check_convexity=False, only=None):
     """verify_solution (src/qp_processing.jl:57-149) for MANY (node, child pieces) items: one qpn_verify_nodes call per
     record shape.  items: list of (pid, [child Poly, ...]).  Returns (records, batches, one result dict per item).
     check_convexity runs check_qp_convexity (:69) on every item first: qp_processing.check_convexity_items, which raises
-    NonConvexQPError for the first non-convex item."""
+    NonConvexQPError for the first non-convex item.
+    only (SUBSET_VERIFY_ROUTE; childless items on a handle that has verify_subset): the positions in `items` to verify.  The
+    other items' results stay None, and a batch none of whose items is asked for makes no call."""
     eng = engine
     if check_convexity:
         from .qp_processing import check_convexity_items
@@ -1051,20 +1058,32 @@ def verify_items(qpn, items, x, engine, tol=1e-4, check_convexity=False):
         recs = [node_record(qpn, pid, ch) for pid, ch in items]
         batches = batch_records(recs)
     out = [None] * len(items)
+    asked = None if only is None else set(only)
     for b in batches:
         xd, w = b.gather(x)
         h = b.resident(eng) if all_leaf else None
-        if h is not None:
+        # the rows of the batch to verify: all of them, or under `only` those asked for (compact call, compact outputs)
+        rows = np.arange(len(b.where), dtype=np.int32)
+        if only is not None and h is not None and hasattr(h, "verify_subset"):
+            rows = rows[[i in asked for i in b.where]]
+        if rows.size == 0:
+            sol, lam, path = (), np.zeros((0, b.m)), ()
+        elif rows.size < len(b.where):
+            sol, lam, path = h.verify_subset(rows, xd[rows], w[rows], tol=tol)
+        elif h is not None:
             sol, lam, path = h.verify(xd, w, tol=tol)
         elif isinstance(b, DeviceRecordBatch):
             sol, lam, path = b.verify(eng, xd, w, tol)
         else:
             sol, lam, path = eng.verify_nodes(b.Qc, b.Rc, b.qd, b.Ac, b.Bc, b.l, b.u, xd, w, tol=tol)
         sol = np.asarray(sol); lam = np.asarray(lam); path = np.asarray(path)
-        for k, i in enumerate(b.where):
-            pth = int(path[k]); ok = bool(sol[k]); mi = int(b.m_true[k])
-            out[i] = dict(solution=ok, lam=(lam[k, :mi].copy() if pth in (1, 2, 3, 4) else None),
-                          e=None if ok else _VERIFY_MSGS.get(pth, "").format(tol=tol), path=pth)
+        for s, k in enumerate(rows):
+            pth = int(path[s]); ok = bool(sol[s]); mi = int(b.m_true[k])
+            out[b.where[k]] = dict(solution=ok, lam=(lam[s, :mi].copy() if pth in (1, 2, 3, 4) else None),
+                                   e=None if ok else _VERIFY_MSGS.get(pth, "").format(tol=tol), path=pth)
+        if rows.size < len(b.where):                                # (the rows left out keep a zero row)
+            lam_r, lam = lam, np.zeros((len(b.where), lam.shape[1]))
+            lam[rows] = lam_r
         b.last = dict(xd=xd, w=w, lam=lam)
     return recs, batches, out
 
@@ -1977,8 +1996,12 @@ def process_level(qpn, players: Sequence[int], x, S: Dict[int, list], engine=Non
         for combo in combos:
             items.append((pid, [S[j][ji] for j, ji in zip(children, combo)]))
             owner.append(pid)
-    recs, batches, rets = verify_items(qpn, items, x, eng, check_convexity=qpn.options.check_convexity)
-    results = {}
+    # (SUBSET_VERIFY_ROUTE: on an all-leaf level item i is player i; the hits' items are not verified again)
+    only = None
+    if SUBSET_VERIFY_ROUTE and all_leaf_level and hits:
+        only = [i for i, pid in enumerate(owner) if pid not in hits]
+    recs, batches, rets = verify_items(qpn, items, x, eng, check_convexity=qpn.options.check_convexity, only=only)
+    results = dict(hits)                                                            # (a hit's result is the memo's)
     first = {}
     for i, (pid, _) in enumerate(items):
         first.setdefault(pid, i)
@@ -1986,6 +2009,8 @@ def process_level(qpn, players: Sequence[int], x, S: Dict[int, list], engine=Non
     for pid in players:
         children, combos = combos_of[pid]
         i0 = first[pid]
+        if pid in hits:
+            continue
         fail = next((t for t in range(len(combos)) if not rets[i0 + t]["solution"]), None)
         if fail is not None:                                                        # the first failure in product order, :206-216
             results[pid] = dict(solution=False, e=rets[i0 + fail]["e"], failed=False,
@@ -1993,8 +2018,6 @@ def process_level(qpn, players: Sequence[int], x, S: Dict[int, list], engine=Non
             continue
         gen = (pid not in qpn.network_depth_map[1]) or qpn.options.gen_solution_map
         results[pid] = dict(solution=True, S=None, failed=False, truncated=False)
-        if pid in hits:
-            continue
         if gen:
             for t in range(len(combos)):
                 want[i0 + t] = True
@@ -2025,9 +2048,7 @@ def process_level(qpn, players: Sequence[int], x, S: Dict[int, list], engine=Non
             if results[pid].get("solution") and want[first[pid]] and len(results[pid]["S"]) == 0:
                 raise RuntimeError("This shouldn't happen. Solution graph is empty.")
     for pid in all_players:
-        if pid in hits:
-            results[pid] = hits[pid]
-        else:
+        if pid not in hits:
             memo[pid] = dict(xkey=xkey[pid], ev=exploration_vertices, result=results[pid],
                              kids={j: S.get(j) for j in qpn.network_edges[pid]})
     return [results[pid] for pid in all_players]
