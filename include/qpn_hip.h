@@ -296,6 +296,25 @@ int qpn_solve_nodes_subset_h(qpn_ctx *ctx, qpn_nodes *nodes, int32_t count, cons
                              uint8_t *active, const qpn_avi_opts *opts, int mem, double *x, int64_t stride_x);
 int qpn_verify_nodes_h(qpn_ctx *ctx, qpn_nodes *nodes, const double *xd, const double *w, int64_t stride_w,
                        double tol, int32_t *solution, double *lambda, int32_t *path, int mem);
+/* The accept gate over a chosen part of a handle's nodes.  The arguments are those of qpn_verify_nodes_h with every per-item
+ * array compact: slot s (0 <= s < count) belongs to node idx[s].  xd is [count][n], w [count][p] with item stride stride_w
+ * (0 = one shared vector), solution and path [count], lambda [count][m]; idx lives where mem says.
+ * Contract: slot s of solution, path and every word of the lambda row equals, bit for bit, what qpn_verify_nodes_h returns for
+ * node idx[s] when that node is given the same xd and w rows and the same tol.  One exception, which the full call has already:
+ * in the 33 .. 64 class, when more nodes of a call than its workspace has slots (256) have more than 32 active rows, which of
+ * them the workgroup kernel takes depends on the order in which workgroups start; flags and paths are equal then, the
+ * multipliers equal up to the kernel that took the node.
+ * The list: entries lie in [0, batch), in any order, and need NOT be distinct -- every slot owns its outputs and scratch and the
+ * records are only read, so one node may be put to several points in one call; count may exceed batch.  count == 0 succeeds and
+ * touches nothing; count < 0 is QPN_ERR_ARG.  A host list is checked before anything is staged or launched (a bad entry:
+ * QPN_ERR_ARG, no output written).  A device list is checked in the kernels, and nothing waits for the answer on the host: a
+ * slot whose entry is out of range reads no record and answers solution = 0, path = 6 ("no such node") and a zero lambda row;
+ * the other slots are unaffected.
+ * The launches cover `count` blocks and all scratch is sized by count: the cost follows the list, not the handle.  The handle's
+ * state does not move. */
+int qpn_verify_nodes_subset_h(qpn_ctx *ctx, qpn_nodes *nodes, int32_t count, const int32_t *idx,
+                              const double *xd, const double *w, int64_t stride_w, double tol,
+                              int32_t *solution, double *lambda, int32_t *path, int mem);
 
 /* ---- schedule hint for qpn_solve_nodes[_into]: longest solves first ---------------------------------
  * The outer loop (src/algorithm.jl:13-117) sweeps the SAME nodes again and again, and a node's pivot
@@ -528,7 +547,8 @@ int qpn_finish_pieces(qpn_ctx *ctx, int32_t pieces, int32_t records, int32_t n, 
  *   solution [batch] int32 (1 = optimal for the node), lambda [batch][m] (sign: + at the lower
  *   bound, - at the upper, :120-123), path [batch] int32: 0 infeasible (:86-89), 1 m==0
  *   shortcut (:91-96), 2 least-squares duals accepted (:114-124), 3 bounded-LSQ fallback
- *   accepted (:129-139), 4 fallback rejected (:141), 5 fallback solver failed (:144).
+ *   accepted (:129-139), 4 fallback rejected (:141), 5 fallback solver failed (:144),
+ *   6 no such node (qpn_verify_nodes_subset_h only: the slot's entry of a device list is out of range).
  *   tol = 1e-4 (:57).  n, m <= 64: one wavefront per node; up to 512: one workgroup per node.
  *   QPN_MEM_DEVICE with m == 0: Ad must still point at 8 readable bytes.  The n <= 32 kernel (verify_node32) loads the first
  *   element of the node's Ad block with a clamped index whatever m is, so a null Ad is a load from address 0 there.  Host memory

@@ -711,6 +711,26 @@ function verify_nodes(nodes::Nodes, xd::Matrix{Float64}, w::VecOrMat{Float64}; t
     (solution, lambda, path)
 end
 
+# The accept gate over the nodes `idx` names (1-based, any order, an entry may come more than once; qpn_verify_nodes_subset_h):
+# column s of every array belongs to node idx[s] -- xd is n×count, w p×count (or a shared vector), the returned lambda m×count.
+# Column s equals what verify_nodes returns for node idx[s] at the same xd and w columns, bit for bit; the launches cover count
+# nodes, not the handle's batch.
+function verify_nodes_subset(nodes::Nodes, idx::Vector{<:Integer}, xd::Matrix{Float64}, w::VecOrMat{Float64}; tol::Float64 = 1e-4)
+    count = length(idx)
+    size(xd) == (nodes.n, count) || error("verify_nodes_subset: xd must be n×count")
+    ndims(w) == 1 || size(w, 2) == count || error("verify_nodes_subset: w must be p×count")
+    all(i -> 1 <= i <= nodes.batch, idx) || error("verify_nodes_subset: idx entries must lie in 1:batch")
+    idx0 = Int32.(idx .- 1)
+    solution = zeros(Int32, count); path = zeros(Int32, count); lambda = zeros(max(nodes.m, 1), count)
+    rc = ccall((:qpn_verify_nodes_subset_h, LIB), Cint,
+               (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ptr{Int32}, Ptr{Cdouble}, Ptr{Cdouble}, Int64, Cdouble, Ptr{Int32}, Ptr{Cdouble},
+                Ptr{Int32}, Cint),
+               ctx(), nodes.h, Int32(count), idx0, xd, w, ndims(w) == 1 ? Int64(0) : Int64(nodes.p), tol, solution, lambda, path,
+               QPN_MEM_HOST)
+    rc == 0 || error("qpn_verify_nodes_subset_h failed ($rc)")
+    (solution, lambda, path)
+end
+
 # ---- pool assembly (combine_gavis, src/avi.jl:305-377) and local pieces (local_piece, src/avi_solutions.jl:400-496) ----
 struct PoolShape          # qpn_pool_shape, include/qpn_hip.h
     players::Int32

@@ -21,7 +21,7 @@ ABI_SYMBOLS = (
     "qpn_sweep_status", "qpn_ctx_set_auto_schedule", "qpn_ctx_set_option",
     "qpn_nodes_upload", "qpn_nodes_update", "qpn_nodes_set_schedule", "qpn_nodes_set_warm", "qpn_nodes_free", "qpn_nodes_info", "qpn_solve_nodes_h",
     "qpn_solve_nodes_subset_h",
-    "qpn_verify_nodes_h", "qpn_pool_size", "qpn_assemble_pools", "qpn_local_pieces", "qpn_recipes_from_masks",
+    "qpn_verify_nodes_h", "qpn_verify_nodes_subset_h", "qpn_pool_size", "qpn_assemble_pools", "qpn_local_pieces", "qpn_recipes_from_masks",
     "qpn_recipes_batch", "qpn_reduced_pieces", "qpn_project_pieces", "qpn_convexity_nodes", "qpn_recipes_batch_range", "qpn_finish_pieces",
     "qpn_multiplier_vertices", "qpn_recipe_filter",
     "qpn_assemble_interior_nodes", "qpn_interior_members", "qpn_members_outside", "qpn_members_outside_lists",
@@ -147,6 +147,7 @@ def load_library():
     lib.qpn_solve_nodes_h.argtypes = [vp, vp, vp, C.c_int64, vp, vp, vp, vp, vp, C.POINTER(AviOpts), C.c_int, vp, C.c_int64]
     lib.qpn_solve_nodes_subset_h.argtypes = [vp, vp, C.c_int32, vp, vp, C.c_int64, vp, vp, vp, vp, vp, C.POINTER(AviOpts), C.c_int, vp, C.c_int64]
     lib.qpn_verify_nodes_h.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_double, vp, vp, vp, C.c_int]
+    lib.qpn_verify_nodes_subset_h.argtypes = [vp, vp, C.c_int32, vp, vp, vp, C.c_int64, C.c_double, vp, vp, vp, C.c_int]
     lib.qpn_pool_size.argtypes = [C.POINTER(PoolShape), C.c_int, C.POINTER(C.c_int32)]
     lib.qpn_assemble_pools.argtypes = [vp, C.POINTER(PoolShape), C.c_int, C.c_int32, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64,
                                        vp, C.c_int64, vp, C.c_int64, vp, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, vp, vp,

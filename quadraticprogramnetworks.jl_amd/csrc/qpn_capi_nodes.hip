@@ -756,44 +756,67 @@ int solve_nodes_subset(qpn_ctx *ctx, qpn_nodes *h, int32_t count, const int32_t 
     return st.finish();
 }
 
+// A host index list of the verify form: every entry in 0 .. batch - 1 (an entry may come more than once)
+bool verify_list_ok(const int32_t *idx, int32_t count, int32_t batch)
+{
+    for (int32_t s = 0; s < count; ++s)
+        if ((uint32_t)idx[s] >= (uint32_t)batch) return false;
+    return true;
+}
+
+// qpn_verify_nodes, qpn_verify_nodes_h and, with a list (idx != nullptr: `count` slots over the `batch` resident records, slot s
+// verifying record idx[s]), qpn_verify_nodes_subset_h.  `items` -- the nodes of the full call, the slots of the list form -- sizes
+// every per-item array and all scratch, and is the grid.
 int verify_nodes_any(qpn_ctx *ctx, bool records_on_device, int32_t batch, int32_t n, int32_t m, int32_t p,
                      const double *Qd, const double *R, const double *qd, const double *Ad, const double *B,
                      const double *l, const double *u, const double *xd, const double *w, int64_t stride_w, double tol,
-                     int32_t *solution, double *lambda, int32_t *path, int mem)
+                     int32_t *solution, double *lambda, int32_t *path, int mem, const char *who = "qpn_verify_nodes",
+                     int32_t count = 0, const int32_t *idx = nullptr)
 {
     if (!ctx) return QPN_ERR_ARG;
-    if (batch < 0 || n <= 0 || m < 0 || p < 0) return fail_arg(ctx, "qpn_verify_nodes: bad sizes");
-    if (batch == 0) return QPN_OK;
-    if (n > qpn_verify_max_dim() || m > qpn_verify_max_dim()) { ctx->last_error = "qpn_verify_nodes: n, m <= 512 in ABI v1"; return QPN_ERR_SIZE; }
+    if (batch < 0 || n <= 0 || m < 0 || p < 0) return fail_arg(ctx, who, "bad sizes");
+    const int32_t items = idx ? count : batch;
+    if (items == 0) return QPN_OK;
+    if (n > qpn_verify_max_dim() || m > qpn_verify_max_dim()) { ctx->last_error = std::string(who) + ": n, m <= 512 in ABI v1"; return QPN_ERR_SIZE; }
     const bool wide_avi = m > 64;         // the bounded-LSQ fallback of wide nodes runs on the large-item AVI kernel
     if (!Qd || !qd || !xd || (m > 0 && (!Ad || !l || !u || !lambda)) || (p > 0 && (!R || !w || (m > 0 && !B))) ||
         !solution || !path)
-        return fail_arg(ctx, "qpn_verify_nodes: null pointer");
-    if (stride_w != 0 && stride_w < p) return fail_arg(ctx, "qpn_verify_nodes: stride_w < p");
+        return fail_arg(ctx, who, "null pointer");
+    if (stride_w != 0 && stride_w < p) return fail_arg(ctx, who, "stride_w < p");
+    Stage st(ctx, mem, who);
+    // a host list is checked before anything is staged or launched; a device list is the kernels' to check
+    if (idx) {
+        if (int rc = st.check()) return rc;
+        if (st.host && !verify_list_ok(idx, count, batch)) return fail_arg(ctx, who, "idx entries must lie in [0, batch)");
+    }
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const size_t mm = (size_t)(m > 0 ? m : 1);
     const bool wide = n > QPN_VERIFY_WIDE_FROM || m > QPN_VERIFY_WIDE_FROM;
     const bool mid = !wide && (n > 32 || m > 32);      // verify_node64's class: a small slot workspace for the nodes it hands on
     const size_t mp16 = (size_t)((m + 15) & ~15);
-    const NodeSizes sz_ = node_sizes(batch, n, m, p, stride_w);
-    Stage st(ctx, mem, "qpn_verify_nodes");
+    const NodeSizes sz_ = node_sizes(items, n, m, p, stride_w);
     NodeDev d{Qd, R, qd, Ad, B, l, u};
     if (!records_on_device) stage_records(st, d, sz_, Qd, R, qd, Ad, B, l, u);
-    const double *dx; double *dlam; int32_t *dsol, *dpath;
+    const double *dx; double *dlam; int32_t *dsol, *dpath; const int32_t *didx = nullptr;
+    if (idx) st.in(didx, idx, (size_t)items * 4);
     st.in(dx, xd, sz_.q); st.in(d.w, w, sz_.w, 8);
-    st.out(dsol, solution, (size_t)batch * 4); st.out(dpath, path, (size_t)batch * 4); st.out(dlam, lambda, sz_.lu, 8);
+    st.out(dsol, solution, (size_t)items * 4); st.out(dpath, path, (size_t)items * 4); st.out(dlam, lambda, sz_.lu, 8);
     // scratch of the bounded-LSQ fallback (src/qp_processing.jl:129-137): Gram block + vectors
     double *sG, *sq, *slb, *sub, *sz, *sres, *wbig = nullptr, *gws = nullptr; int32_t *sst;
-    st.scratch(sG, (size_t)batch * mm * mm * 8); st.scratch(sq, (size_t)batch * mm * 8);
-    st.scratch(slb, (size_t)batch * mm * 8); st.scratch(sub, (size_t)batch * mm * 8);
-    st.scratch(sz, (size_t)batch * mm * 8); st.scratch(sres, (size_t)batch * 8); st.scratch(sst, (size_t)batch * 4);
-    if (wide_avi) st.scratch(wbig, qpn_avi_big_workspace_bytes(batch, m));
-    if (wide && m > 0) st.scratch(gws, (size_t)batch * 2 * mp16 * mp16 * 8);
+    st.scratch(sG, (size_t)items * mm * mm * 8); st.scratch(sq, (size_t)items * mm * 8);
+    st.scratch(slb, (size_t)items * mm * 8); st.scratch(sub, (size_t)items * mm * 8);
+    st.scratch(sz, (size_t)items * mm * 8); st.scratch(sres, (size_t)items * 8); st.scratch(sst, (size_t)items * 4);
+    if (wide_avi) st.scratch(wbig, qpn_avi_big_workspace_bytes(items, m));
+    if (wide && m > 0) st.scratch(gws, (size_t)items * 2 * mp16 * mp16 * 8);
     else if (mid && m > 0) st.scratch(gws, (size_t)QPN_VERIFY_MID_SLOTS * 2 * mp16 * mp16 * 8 + 64);
     int rc = st.begin();
     if (rc != QPN_OK) return rc;
-    HIPCHK(ctx, qpn_launch_verify_nodes(batch, n, m, p, d.Q, d.R, d.q, d.A, d.B, d.l, d.u, dx, d.w, stride_w, tol,
-                                        dsol, dlam, dpath, sG, sq, slb, sub, sz, sres, sst, ctx->stream, wbig, gws));
+    if (idx)
+        HIPCHK(ctx, qpn_launch_verify_nodes_list(items, didx, batch, n, m, p, d.Q, d.R, d.q, d.A, d.B, d.l, d.u, dx, d.w, stride_w,
+                                                 tol, dsol, dlam, dpath, sG, sq, slb, sub, sz, sres, sst, ctx->stream, wbig, gws));
+    else
+        HIPCHK(ctx, qpn_launch_verify_nodes(batch, n, m, p, d.Q, d.R, d.q, d.A, d.B, d.l, d.u, dx, d.w, stride_w, tol,
+                                            dsol, dlam, dpath, sG, sq, slb, sub, sz, sres, sst, ctx->stream, wbig, gws));
     return st.finish();
 }
 
@@ -983,6 +1006,20 @@ int qpn_verify_nodes_h(qpn_ctx *ctx, qpn_nodes *h, const double *xd, const doubl
     if (h->device != ctx->device) return fail_arg(ctx, "qpn_verify_nodes_h: handle belongs to another device");
     return verify_nodes_any(ctx, true, h->batch, h->n, h->m, h->p, h->f[0], h->f[1], h->f[2], h->f[3], h->f[4], h->f[5],
                             h->f[6], xd, w, stride_w, tol, solution, lambda, path, mem);
+}
+
+int qpn_verify_nodes_subset_h(qpn_ctx *ctx, qpn_nodes *h, int32_t count, const int32_t *idx, const double *xd, const double *w,
+                              int64_t stride_w, double tol, int32_t *solution, double *lambda, int32_t *path, int mem)
+{
+    const char *who = "qpn_verify_nodes_subset_h";
+    if (!ctx) return QPN_ERR_ARG;
+    if (!h) return fail_arg(ctx, who, "null handle");
+    if (h->device != ctx->device) return fail_arg(ctx, who, "handle belongs to another device");
+    if (count < 0) return fail_arg(ctx, who, "count < 0");
+    if (count == 0) return QPN_OK;
+    if (!idx) return fail_arg(ctx, who, "null pointer");
+    return verify_nodes_any(ctx, true, h->batch, h->n, h->m, h->p, h->f[0], h->f[1], h->f[2], h->f[3], h->f[4], h->f[5],
+                            h->f[6], xd, w, stride_w, tol, solution, lambda, path, mem, who, count, idx);
 }
 
 // ---- schedule hints of the context ----------------------------------------------------------------------------

@@ -361,6 +361,16 @@ hipError_t qpn_launch_verify_nodes(int32_t batch, int32_t n, int32_t m, int32_t 
                                    double *sz, double *sres, int32_t *sst, hipStream_t stream,
                                    double *wbig = nullptr,       // wbig: large-item AVI workspace (m > 64 only)
                                    double *gws = nullptr);       // gws: [batch][2][pad16(m)^2] Gram block / factor of verify_wide_node (n or m > 64)
+// The list form (qpn_verify_nodes_subset_h): `count` slots, slot s verifies record list[s] of the nrec records (device list;
+// entries outside [0, nrec) answer path 6).  xd, w, the outputs and every scratch array are compact: sized by count.
+hipError_t qpn_launch_verify_nodes_list(int32_t count, const int32_t *list, int32_t nrec, int32_t n, int32_t m, int32_t p,
+                                        const double *Qd, const double *R, const double *qd,
+                                        const double *Ad, const double *B, const double *l,
+                                        const double *u, const double *xd, const double *w,
+                                        int64_t stride_w, double tol, int32_t *solution, double *lambda,
+                                        int32_t *path, double *sG, double *sq, double *slb, double *sub,
+                                        double *sz, double *sres, int32_t *sst, hipStream_t stream,
+                                        double *wbig = nullptr, double *gws = nullptr);
 int qpn_verify_max_dim();
 
 // qpn_convexity.hip: check_qp_convexity for a batch of nodes (n <= 256, m <= 1024); gws: qpn_convexity_workspace_bytes

@@ -34,19 +34,60 @@ struct VerifyArgs {
     int32_t gate;        // verify_stage1 only: != 0 -> take just the nodes whose path is -2 (left over by verify_node64)
 };
 
+// The list form (qpn_verify_nodes_subset_h).  Two indices are kept apart: the SLOT, which is the block -- `batch` counts slots;
+// xd, w, solution, lambda, path, the fallback scratch sG / sq / slb / sub / sz and the workspace are compact and indexed by it --
+// and the RECORD list[slot] of the slot's node (Qd, R, qd, Ad, B, l, u).  Every kernel below is compiled twice.  <LIST = false>
+// on VerifyArgs is the full call: slot == record, and its source is, statement for statement, what it was before the list
+// existed (the LIST blocks are `if constexpr`), so its machine code is too -- tools/verify_fullcall_disasm.py compares it.
+// <LIST = true> on VerifyListArgs opens with verify_bind_record, which moves the seven record pointers of the kernel's OWN copy
+// of the arguments by (record - slot) records: from there on `b` is the slot, `a.Qd + b * n * n` and its like find the record
+// list[b], and the body is the full call's.
+struct VerifyListArgs : VerifyArgs {
+    const int32_t *list;     // [batch] slot -> record; entries outside [0, nrec) answer path 6
+    int32_t nrec;            // records the list may name
+};
+template <bool LIST> using VArgs = std::conditional_t<LIST, VerifyListArgs, VerifyArgs>;
+
+template <class T> __device__ __forceinline__ const T *verify_shift(const T *ptr, long long elems)
+{
+    return reinterpret_cast<const T *>(reinterpret_cast<uintptr_t>(ptr) + (uintptr_t)(elems * (long long)sizeof(T)));
+}
+// Binds the record pointers of `a` to the record of `slot`; false where the list names none (no record address is formed then).
+// Wave-uniform: the slot is the block, the list entry comes by a scalar load and the seven pointers stay in scalar registers.
+__device__ __forceinline__ bool verify_bind_record(VerifyListArgs &a, int slot)
+{
+    const int rec = a.list[slot];
+    if ((unsigned)rec >= (unsigned)a.nrec) return false;
+    const long long d = (long long)rec - slot, n = a.n, m = a.m, p = a.p;
+    a.Qd = verify_shift(a.Qd, d * n * n); a.R = verify_shift(a.R, d * n * p); a.qd = verify_shift(a.qd, d * n);
+    a.Ad = verify_shift(a.Ad, d * m * n); a.B = verify_shift(a.B, d * m * p);
+    a.l = verify_shift(a.l, d * m); a.u = verify_shift(a.u, d * m);
+    return true;
+}
+// "no such node": the answer of a slot whose list entry is out of range.  Path 6 matches none of the gates (-1, -2) of the
+// follow-up launches.
+template <int NT> __device__ __forceinline__ void verify_no_node(const VerifyArgs &a, int slot, int tid)
+{
+    for (int r = tid; r < a.m; r += NT) a.lambda[(size_t)slot * a.m + r] = 0.0;
+    if (tid == 0) { a.solution[slot] = 0; a.path[slot] = 6; }
+}
+
 // Pivot choice of every factorisation below: the largest remaining diagonal, where diagonals within 2^-30 of the largest count as
 // equal and the lowest column wins.  With equilibrated rows every diagonal starts at 1 up to rounding; an exact `==` would let
 // that rounding pick the pivot, and the basic solution of a rank-deficient block (which multipliers are 0) would depend on it.
 // (The CPU restatement used by the tests applies the same rule.)
 constexpr double PIV_BAND = 1.0 - 0x1p-30;
 
-template <int LDV>
-__global__ __launch_bounds__(WAVE) void verify_stage1(VerifyArgs a)
+template <int LDV, bool LIST>
+__global__ __launch_bounds__(WAVE) void verify_stage1(VArgs<LIST> a)
 {
     const int n = a.n, m = a.m, p = a.p;
     const int lane = threadIdx.x;
     const int b = blockIdx.x;
     if (a.gate && a.path[b] != -2) return;
+    if constexpr (LIST) {
+        if (!verify_bind_record(a, b)) { verify_no_node<WAVE>(a, b, lane); return; }
+    }
     __shared__ double sA[LDV * (LDV - 1)];   // Ad, column-major, ld = LDV
     __shared__ double sGa[LDV * (LDV - 1)];  // Gram block of the active rows, then its Cholesky factor
     __shared__ double sqt[64];        // q~
@@ -234,12 +275,15 @@ __device__ __forceinline__ double wave_sum32_f64(double v)   // sum over lanes 0
 constexpr int V32_LDA = 34;      // compacted active rows / all rows: entry (row c, column t) at c * 34 + t
 constexpr int V32_LDG = 33;      // Gram block / factor: entry (i, j) at j * 33 + i
 
-template <bool FULL>
-__global__ __launch_bounds__(WAVE, 4) void verify_node32(VerifyArgs a)
+template <bool FULL, bool LIST>
+__global__ __launch_bounds__(WAVE, 4) void verify_node32(VArgs<LIST> a)
 {
     const int n = FULL ? 32 : a.n, m = FULL ? 32 : a.m, p = a.p;
     const int l = threadIdx.x;
     const int b = blockIdx.x;
+    if constexpr (LIST) {
+        if (!verify_bind_record(a, b)) { verify_no_node<WAVE>(a, b, l); return; }
+    }
     const int r5 = l & 31, ch = l >> 5;
     __shared__ __attribute__((aligned(16))) double sM[32 * V32_LDA];
     __shared__ __attribute__((aligned(16))) double sx[32];       // x, then q~: [parity][16]
@@ -595,11 +639,15 @@ __global__ __launch_bounds__(WAVE, 4) void verify_node32(VerifyArgs a)
 // (16.9 KB) next to the Gram block / factor (8.4 KB): 26.6 KB per wavefront, six wavefronts per CU.
 constexpr int V64_LDA = 66;      // active rows: entry (row c, column t) at c * 66 + t (operand reads conflict-free)
 
-__global__ __launch_bounds__(WAVE, 2) void verify_node64(VerifyArgs a)
+template <bool LIST>
+__global__ __launch_bounds__(WAVE, 2) void verify_node64(VArgs<LIST> a)
 {
     const int n = a.n, m = a.m, p = a.p;
     const int l = threadIdx.x;
     const int b = blockIdx.x;
+    if constexpr (LIST) {
+        if (!verify_bind_record(a, b)) { verify_no_node<WAVE>(a, b, l); return; }
+    }
     __shared__ __attribute__((aligned(16))) double sM[32 * V64_LDA];
     __shared__ __attribute__((aligned(16))) double sG[32 * V32_LDG];
     __shared__ __attribute__((aligned(16))) double sx[64];       // x, then q~, then the residual
@@ -898,12 +946,16 @@ __global__ __launch_bounds__(WAVE, 2) void verify_node64(VerifyArgs a)
     }
 }
 
-__global__ __launch_bounds__(WAVE) void verify_stage2(VerifyArgs a, const int32_t *avi_status)
+template <bool LIST>
+__global__ __launch_bounds__(WAVE) void verify_stage2(VArgs<LIST> a, const int32_t *avi_status)
 {
     const int n = a.n, m = a.m, p = a.p;
     const int lane = threadIdx.x;
     const int b = blockIdx.x;
     if (a.path[b] != -1) return;
+    if constexpr (LIST) {
+        if (!verify_bind_record(a, b)) return;           // (never: verify_stage1 gave this slot its -1)
+    }
     double *lam = a.lambda + (size_t)b * m;
     if (avi_status[b] != QPN_SUCCESS) {   // :143-145
         if (lane < m) lam[lane] = 0.0;
@@ -977,10 +1029,15 @@ __device__ __forceinline__ double block_max_f64(double v, double *red)
 constexpr int VW_KMAX = 128;
 __device__ __forceinline__ int vw_ld(int m) { return m | 1; }
 
-__global__ __launch_bounds__(WTPB) __attribute__((amdgpu_waves_per_eu(2, 2))) void verify_wide_node(VerifyArgs a, double *gws, int wp, int dyn_doubles, int *slot_ctr, int nslots)
+template <bool LIST>
+__global__ __launch_bounds__(WTPB) __attribute__((amdgpu_waves_per_eu(2, 2))) void verify_wide_node(VArgs<LIST> a, double *gws, int wp, int dyn_doubles, int *slot_ctr, int nslots)
 {
     const int n = a.n, m = a.m, p = a.p;
     const int tid = threadIdx.x, b = blockIdx.x;
+    if constexpr (LIST) {
+        // (behind verify_node64 a slot without a node has its 6 already and, like every path but -2, is not this launch's)
+        if (!verify_bind_record(a, b)) { if (!a.gate) verify_no_node<WTPB>(a, b, tid); return; }
+    }
     const int wave = tid >> 6, lane = tid & 63, lc = lane & 15, lq = lane >> 4;
     __shared__ double sx[WMAX];                  // x, then q~, then the residual
     __shared__ double sdv[VW_KMAX], ssgv[VW_KMAX], sco[VW_KMAX];
@@ -1449,12 +1506,16 @@ __global__ __launch_bounds__(WTPB) __attribute__((amdgpu_waves_per_eu(2, 2))) vo
     }
 }
 
-__global__ __launch_bounds__(WTPB) void verify_wide_stage1(VerifyArgs a)
+template <bool LIST>
+__global__ __launch_bounds__(WTPB) void verify_wide_stage1(VArgs<LIST> a)
 {
     const int n = a.n, m = a.m, p = a.p;
     const int tid = threadIdx.x;
     const int b = blockIdx.x;
     if (a.gate && a.path[b] != -2) return;
+    if constexpr (LIST) {
+        if (!verify_bind_record(a, b)) { verify_no_node<WTPB>(a, b, tid); return; }
+    }
     __shared__ double sx[WMAX], sqt[WMAX], ssg[WMAX], sdiag[WMAX], sb[WMAX], sy[WMAX], slv[WMAX];
     __shared__ int srow[WMAX], sstep[WMAX], scls[WMAX], sord[WMAX];
     __shared__ double red[4];
@@ -1614,12 +1675,16 @@ __global__ __launch_bounds__(WTPB) void verify_wide_stage1(VerifyArgs a)
     if (tid == 0) { a.solution[b] = 0; a.path[b] = -1; }
 }
 
-__global__ __launch_bounds__(WTPB) void verify_wide_stage2(VerifyArgs a, const int32_t *avi_status)
+template <bool LIST>
+__global__ __launch_bounds__(WTPB) void verify_wide_stage2(VArgs<LIST> a, const int32_t *avi_status)
 {
     const int n = a.n, m = a.m, p = a.p;
     const int tid = threadIdx.x;
     const int b = blockIdx.x;
     if (a.path[b] != -1) return;
+    if constexpr (LIST) {
+        if (!verify_bind_record(a, b)) return;           // (never: verify_wide_stage1 gave this slot its -1)
+    }
     double *lam = a.lambda + (size_t)b * m;
     __shared__ double sl_[WMAX], sx[WMAX], red[4];
     if (avi_status[b] != QPN_SUCCESS) {   // :143-145
@@ -1655,6 +1720,99 @@ __global__ __launch_bounds__(WTPB) void verify_wide_stage2(VerifyArgs a, const i
 
 int qpn_verify_max_dim() { return WMAX; }
 
+namespace {
+
+// The launches of one call on the filled argument block: `a.batch` blocks per launch -- the nodes of the full call, the slots of
+// the list form; every gate (only_if = path of the AVI launches, the -2 hand-over of verify_node64) is per slot.
+template <bool LIST>
+hipError_t launch_verify(VArgs<LIST> a, double *sres, int32_t *sst, hipStream_t stream, double *wbig, double *gws)
+{
+    const int32_t batch = a.batch, n = a.n, m = a.m;
+    int32_t *const path = a.path;
+    double *const sG = a.sG, *const sq = a.sq, *const slb = a.slb, *const sub = a.sub, *const sz = a.sz;
+    if (n > QPN_VERIFY_WIDE_FROM || m > QPN_VERIFY_WIDE_FROM) {
+        // wide nodes: verify_wide_node (up to 128 active rows, every path inside the workgroup), then round 1's kernels over what it
+        // flagged -2 (their bounded-LSQ fallback is a large box-AVI, N = m, on the large-item kernel)
+        if (m >= 1 && gws) {
+            static QpnLdsLimits lds_limits;
+            if (const hipError_t e = lds_limits.raise({{verify_wide_node<LIST>, 72 * 1024}}); e != hipSuccess) return e;
+            const int wp = m <= 256 ? 16 : 8;
+            // the panels, and room for a k x k factor (k <= min(m, 128)) up to what two workgroups per CU allow
+            size_t dyn = (size_t)2 * wp * (size_t)(m | 1) * sizeof(double);
+            const size_t km = (size_t)(m < 128 ? m : 128), want = km * km * sizeof(double), cap = 71 * 1024;
+            if (dyn < (want < cap ? want : cap)) dyn = want < cap ? want : cap;
+            hipLaunchKernelGGL((verify_wide_node<LIST>), dim3((unsigned)batch), dim3(WTPB), dyn, stream, a, gws, wp, (int)(dyn / sizeof(double)), (int *)nullptr, 0);
+            hipError_t e1 = hipGetLastError();
+            if (e1 != hipSuccess) return e1;
+            a.gate = 1;
+        }
+        hipLaunchKernelGGL((verify_wide_stage1<LIST>), dim3((unsigned)batch), dim3(WTPB), 0, stream, a);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess || m == 0) return e;
+        AviBatchArgs s{};
+        s.batch = batch; s.N = m; s.M = sG; s.strideM = (int64_t)m * m; s.q = sq; s.l = slb; s.u = sub;
+        s.kind = nullptr; s.stride_kind = 0; s.z = sz; s.status = sst; s.resid = sres; s.pivots = nullptr;
+        s.active = nullptr; s.check_tol = 1e-6; s.piv_tol = 1e-11; s.feas_tol = 1e-12; s.comp_tol = 1e-2;
+        s.max_pivots = 0; s.only_if = path; s.only_if_value = -1;
+        e = m > 64 ? qpn_launch_avi_solve_big(s, wbig, stream) : (s.scan = 1, qpn_launch_avi_solve(s, stream));
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL((verify_wide_stage2<LIST>), dim3((unsigned)batch), dim3(WTPB), 0, stream, a, (const int32_t *)sst);
+        return hipGetLastError();
+    }
+    if (n <= 32 && m <= 32) {
+        // ONE launch: the bounded least-squares fallback runs inside the node's wavefront (verify_node32)
+        if (n == 32 && m == 32) hipLaunchKernelGGL((verify_node32<true, LIST>), dim3((unsigned)batch), dim3(WAVE), 0, stream, a);
+        else hipLaunchKernelGGL((verify_node32<false, LIST>), dim3((unsigned)batch), dim3(WAVE), 0, stream, a);
+        return hipGetLastError();
+    }
+    // 33 .. 64: verify_node64 (up to 32 active rows: the usual case), then the older kernels over what it flagged -2
+    if (m >= 1) {
+        hipLaunchKernelGGL((verify_node64<LIST>), dim3((unsigned)batch), dim3(WAVE), 0, stream, a);
+        a.gate = 1;
+        if (gws) {
+            // the nodes it flagged (more than 32 active rows: a handful in thousands) go to the workgroup kernel first -- ~35 us for
+            // such a node instead of ~130 us on the one-wavefront kernels of round 1, which bound the whole call's tail
+            static QpnLdsLimits lds_limits;
+            if (const hipError_t e = lds_limits.raise({{verify_wide_node<LIST>, 72 * 1024}}); e != hipSuccess) return e;
+            const size_t mp16 = (size_t)((m + 15) & ~15);
+            int *ctr = reinterpret_cast<int *>(gws + (size_t)QPN_VERIFY_MID_SLOTS * 2 * mp16 * mp16);
+            hipError_t e0 = hipMemsetAsync(ctr, 0, 4, stream);
+            if (e0 != hipSuccess) return e0;
+            size_t dyn = (size_t)2 * 16 * (size_t)(m | 1) * sizeof(double);
+            const size_t want = (size_t)m * m * sizeof(double);
+            if (dyn < want) dyn = want;
+            hipLaunchKernelGGL((verify_wide_node<LIST>), dim3((unsigned)batch), dim3(WTPB), dyn, stream, a, gws, 16, (int)(dyn / sizeof(double)), ctr, QPN_VERIFY_MID_SLOTS);
+            e0 = hipGetLastError();
+            if (e0 != hipSuccess) return e0;
+        }
+    }
+    hipLaunchKernelGGL((verify_stage1<65, LIST>), dim3((unsigned)batch), dim3(WAVE), 0, stream, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess || m == 0) return e;
+    AviBatchArgs s{};
+    s.batch = batch; s.N = m; s.M = sG; s.strideM = (int64_t)m * m; s.q = sq; s.l = slb; s.u = sub;
+    s.kind = nullptr; s.stride_kind = 0; s.z = sz; s.status = sst; s.resid = sres; s.pivots = nullptr;
+    s.active = nullptr; s.check_tol = 1e-6; s.piv_tol = 1e-11; s.feas_tol = 1e-12; s.comp_tol = 1e-2;
+    s.max_pivots = 0; s.only_if = path; s.only_if_value = -1; s.scan = 1;     // compact fallback launch
+    e = qpn_launch_avi_solve(s, stream);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((verify_stage2<LIST>), dim3((unsigned)batch), dim3(WAVE), 0, stream, a, (const int32_t *)sst);
+    return hipGetLastError();
+}
+
+void fill_verify_args(VerifyArgs &a, int32_t batch, int32_t n, int32_t m, int32_t p, const double *Qd, const double *R,
+                      const double *qd, const double *Ad, const double *B, const double *l, const double *u, const double *xd,
+                      const double *w, int64_t stride_w, double tol, int32_t *solution, double *lambda, int32_t *path, double *sG,
+                      double *sq, double *slb, double *sub, double *sz)
+{
+    a.batch = batch; a.n = n; a.m = m; a.p = p;
+    a.Qd = Qd; a.R = R; a.qd = qd; a.Ad = Ad; a.B = B; a.l = l; a.u = u; a.xd = xd; a.w = w;
+    a.stride_w = stride_w; a.tol = tol; a.solution = solution; a.lambda = lambda; a.path = path;
+    a.sG = sG; a.sq = sq; a.slb = slb; a.sub = sub; a.sz = sz;
+}
+
+} // namespace
+
 hipError_t qpn_launch_verify_nodes(int32_t batch, int32_t n, int32_t m, int32_t p,
                                    const double *Qd, const double *R, const double *qd,
                                    const double *Ad, const double *B, const double *l,
@@ -1665,76 +1823,21 @@ hipError_t qpn_launch_verify_nodes(int32_t batch, int32_t n, int32_t m, int32_t 
 {
     if (batch <= 0) return hipSuccess;
     VerifyArgs a{};
-    a.batch = batch; a.n = n; a.m = m; a.p = p;
-    a.Qd = Qd; a.R = R; a.qd = qd; a.Ad = Ad; a.B = B; a.l = l; a.u = u; a.xd = xd; a.w = w;
-    a.stride_w = stride_w; a.tol = tol; a.solution = solution; a.lambda = lambda; a.path = path;
-    a.sG = sG; a.sq = sq; a.slb = slb; a.sub = sub; a.sz = sz;
-    if (n > QPN_VERIFY_WIDE_FROM || m > QPN_VERIFY_WIDE_FROM) {
-        // wide nodes: verify_wide_node (up to 128 active rows, every path inside the workgroup), then round 1's kernels over what it
-        // flagged -2 (their bounded-LSQ fallback is a large box-AVI, N = m, on the large-item kernel)
-        if (m >= 1 && gws) {
-            static QpnLdsLimits lds_limits;
-            if (const hipError_t e = lds_limits.raise({{verify_wide_node, 72 * 1024}}); e != hipSuccess) return e;
-            const int wp = m <= 256 ? 16 : 8;
-            // the panels, and room for a k x k factor (k <= min(m, 128)) up to what two workgroups per CU allow
-            size_t dyn = (size_t)2 * wp * (size_t)(m | 1) * sizeof(double);
-            const size_t km = (size_t)(m < 128 ? m : 128), want = km * km * sizeof(double), cap = 71 * 1024;
-            if (dyn < (want < cap ? want : cap)) dyn = want < cap ? want : cap;
-            hipLaunchKernelGGL(verify_wide_node, dim3((unsigned)batch), dim3(WTPB), dyn, stream, a, gws, wp, (int)(dyn / sizeof(double)), (int *)nullptr, 0);
-            hipError_t e1 = hipGetLastError();
-            if (e1 != hipSuccess) return e1;
-            a.gate = 1;
-        }
-        hipLaunchKernelGGL(verify_wide_stage1, dim3((unsigned)batch), dim3(WTPB), 0, stream, a);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess || m == 0) return e;
-        AviBatchArgs s{};
-        s.batch = batch; s.N = m; s.M = sG; s.strideM = (int64_t)m * m; s.q = sq; s.l = slb; s.u = sub;
-        s.kind = nullptr; s.stride_kind = 0; s.z = sz; s.status = sst; s.resid = sres; s.pivots = nullptr;
-        s.active = nullptr; s.check_tol = 1e-6; s.piv_tol = 1e-11; s.feas_tol = 1e-12; s.comp_tol = 1e-2;
-        s.max_pivots = 0; s.only_if = path; s.only_if_value = -1;
-        e = m > 64 ? qpn_launch_avi_solve_big(s, wbig, stream) : (s.scan = 1, qpn_launch_avi_solve(s, stream));
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(verify_wide_stage2, dim3((unsigned)batch), dim3(WTPB), 0, stream, a, (const int32_t *)sst);
-        return hipGetLastError();
-    }
-    if (n <= 32 && m <= 32) {
-        // ONE launch: the bounded least-squares fallback runs inside the node's wavefront (verify_node32)
-        if (n == 32 && m == 32) hipLaunchKernelGGL(verify_node32<true>, dim3((unsigned)batch), dim3(WAVE), 0, stream, a);
-        else hipLaunchKernelGGL(verify_node32<false>, dim3((unsigned)batch), dim3(WAVE), 0, stream, a);
-        return hipGetLastError();
-    }
-    // 33 .. 64: verify_node64 (up to 32 active rows: the usual case), then the older kernels over what it flagged -2
-    if (m >= 1) {
-        hipLaunchKernelGGL(verify_node64, dim3((unsigned)batch), dim3(WAVE), 0, stream, a);
-        a.gate = 1;
-        if (gws) {
-            // the nodes it flagged (more than 32 active rows: a handful in thousands) go to the workgroup kernel first -- ~35 us for
-            // such a node instead of ~130 us on the one-wavefront kernels of round 1, which bound the whole call's tail
-            static QpnLdsLimits lds_limits;
-            if (const hipError_t e = lds_limits.raise({{verify_wide_node, 72 * 1024}}); e != hipSuccess) return e;
-            const size_t mp16 = (size_t)((m + 15) & ~15);
-            int *ctr = reinterpret_cast<int *>(gws + (size_t)QPN_VERIFY_MID_SLOTS * 2 * mp16 * mp16);
-            hipError_t e0 = hipMemsetAsync(ctr, 0, 4, stream);
-            if (e0 != hipSuccess) return e0;
-            size_t dyn = (size_t)2 * 16 * (size_t)(m | 1) * sizeof(double);
-            const size_t want = (size_t)m * m * sizeof(double);
-            if (dyn < want) dyn = want;
-            hipLaunchKernelGGL(verify_wide_node, dim3((unsigned)batch), dim3(WTPB), dyn, stream, a, gws, 16, (int)(dyn / sizeof(double)), ctr, QPN_VERIFY_MID_SLOTS);
-            e0 = hipGetLastError();
-            if (e0 != hipSuccess) return e0;
-        }
-    }
-    hipLaunchKernelGGL(verify_stage1<65>, dim3((unsigned)batch), dim3(WAVE), 0, stream, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess || m == 0) return e;
-    AviBatchArgs s{};
-    s.batch = batch; s.N = m; s.M = sG; s.strideM = (int64_t)m * m; s.q = sq; s.l = slb; s.u = sub;
-    s.kind = nullptr; s.stride_kind = 0; s.z = sz; s.status = sst; s.resid = sres; s.pivots = nullptr;
-    s.active = nullptr; s.check_tol = 1e-6; s.piv_tol = 1e-11; s.feas_tol = 1e-12; s.comp_tol = 1e-2;
-    s.max_pivots = 0; s.only_if = path; s.only_if_value = -1; s.scan = 1;     // compact fallback launch
-    e = qpn_launch_avi_solve(s, stream);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(verify_stage2, dim3((unsigned)batch), dim3(WAVE), 0, stream, a, (const int32_t *)sst);
-    return hipGetLastError();
+    fill_verify_args(a, batch, n, m, p, Qd, R, qd, Ad, B, l, u, xd, w, stride_w, tol, solution, lambda, path, sG, sq, slb, sub, sz);
+    return launch_verify<false>(a, sres, sst, stream, wbig, gws);
+}
+
+hipError_t qpn_launch_verify_nodes_list(int32_t count, const int32_t *list, int32_t nrec, int32_t n, int32_t m, int32_t p,
+                                        const double *Qd, const double *R, const double *qd,
+                                        const double *Ad, const double *B, const double *l,
+                                        const double *u, const double *xd, const double *w,
+                                        int64_t stride_w, double tol, int32_t *solution, double *lambda,
+                                        int32_t *path, double *sG, double *sq, double *slb, double *sub,
+                                        double *sz, double *sres, int32_t *sst, hipStream_t stream, double *wbig, double *gws)
+{
+    if (count <= 0) return hipSuccess;
+    VerifyListArgs a{};
+    fill_verify_args(a, count, n, m, p, Qd, R, qd, Ad, B, l, u, xd, w, stride_w, tol, solution, lambda, path, sG, sq, slb, sub, sz);
+    a.list = list; a.nrec = nrec;
+    return launch_verify<true>(a, sres, sst, stream, wbig, gws);
 }

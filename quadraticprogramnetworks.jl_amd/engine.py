@@ -1152,6 +1152,25 @@ class Nodes:
         dev, xd, w = self.eng._stage("Nodes.verify", "xd w", f64=(xd, w))
         return self.eng._verify("qpn_verify_nodes_h", dev, (self.h,), self.batch, self.m, self.p, xd, w, tol)
 
+    def verify_subset(self, idx, xd, w, tol=1e-4):
+        """The accept gate over the nodes idx names (qpn_verify_nodes_subset_h): the conventions of verify with count = len(idx)
+        in the place of batch and every array compact -- slot s of xd ([count, n]), of w ((p,) shared or (count, p)) and of the
+        outputs belongs to node idx[s].  idx: an int32 array or tensor living where xd and w live, its entries in [0, batch), in
+        any order; an entry may come more than once (one node at several points), so count may exceed batch.  Returns
+        (solution [count], lambda [count, m], path [count]); slot s equals what verify returns for node idx[s] at the same xd and
+        w rows, bit for bit.  The launches cover count blocks.  A device idx with a bad entry is not an error: such a slot
+        answers solution 0, a zero lambda row and path 6."""
+        eng = self.eng
+        dev, idx, xd, w = eng._stage("Nodes.verify_subset", "idx xd w", i32=(idx,), f64=(xd, w))
+        if idx is None or idx.ndim != 1:
+            raise QpnError("idx must be a one-dimensional int32 array")
+        count = int(idx.shape[0])
+        if xd is None or tuple(xd.shape) != (count, self.n):
+            raise QpnError(f"xd must have shape ({count}, {self.n})")
+        if w is None or w.shape[-1] != self.p or w.ndim > 2 or (w.ndim == 2 and w.shape[0] != count):
+            raise QpnError(f"w must have shape ({self.p},) or ({count}, {self.p})")
+        return eng._verify("qpn_verify_nodes_subset_h", dev, (self.h, count, _ptr(idx)), count, self.m, self.p, xd, w, tol)
+
 
 _default = {}
 
